@@ -7,13 +7,19 @@ means all-gathered, compact VisionFeature / FeatureMatch payloads gathered to ra
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --config 1080p            # BASELINE configs[2]: 1920x1080, 8000 keypoints
+    python bench.py --full                    # + in-line stage pass, sustained leg, observe_image, other configs, CPU baselines
+    python bench.py --dump-outputs DIR        # + the last timed step's VisionFeature / FeatureMatch records as DIR/*.npy
 
 A "step" is one pass of the hot path over one batch of `--batch` stereo frames per GPU: extract(L) + extract(R) +
 GetMatches(L, R) -- the part BASELINE's metric names and >= 97 % of the step -- followed by the reference's own steps up
 to the output records (RemoveAmbigStereo, GetFeatureMatches against the previous frame, Calculate3DPoints,
 UndistortFeaturePoints) and the packing of the payload; the SAME per-GPU work at every N, plus the collectives for
 N > 1 (vision_slam_frontend_amd/distributed.py).  Rank 0 prints ONE JSON line (task contract + `roofline`,
-`roofline_valu`, `matcher` and `cpu_baseline` objects).
+`roofline_valu` and `matcher` objects from the timed steps' own stage timers).
+
+A plain run sets up (frames, contexts, the FAST launch-form tune call), warms up, times the K steps, writes the outputs if
+asked and prints the line.  Everything that takes runs of its own -- the in-line stage pass, the sustained leg, the drop-in
+API figures (`observe_image`), BASELINE's other configurations and the two CPU baselines -- runs only with `--full`.
 """
 from __future__ import annotations
 
@@ -478,6 +484,62 @@ def start_rank_watchdog(seconds: float):
     return mark
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_payloads(sf):
+    """The packed VisionFeature / FeatureMatch payloads of the last step issued, as host byte arrays in rank order: what rank 0
+    received from every rank (world > 1; None on the other ranks), else this rank's own.  Call after sf.drain()."""
+    last = sf.step_idx - 1
+    if sf.dist_on:
+        if sf.rank != 0:
+            return None
+        bufs = sf.recv[last % sf.PAYLOAD_SLOTS]
+    else:
+        bufs = [sf.local_payload(last)]
+    out = []
+    for b in bufs:
+        total = int(b[:16].cpu().numpy().view("<u4")[3])  # header: magic, frames, pairs, total bytes
+        out.append(b[:total].cpu().numpy().copy())
+    return out
+
+
+def dump_outputs(payloads, directory, limit=DUMP_LIMIT_BYTES):
+    """Writes the records of `payloads` (last_step_payloads) as float32 / float64 .npy files under `directory`; the index
+    fields are uint64 in the records and exact in float64.  Should the records exceed `limit` bytes, a fixed, seeded sample
+    of the rows is written instead, and the rows taken as `*_sample_rows.npy`.  Returns {name: shape}."""
+    import numpy as np
+
+    from vision_slam_frontend_amd import capi
+    feats, pairs = [], []
+    for p in payloads:
+        fl, ml = capi.unpack_outputs(p)
+        feats += fl
+        pairs += ml
+    f = np.concatenate(feats) if feats else np.zeros(0, capi.VISION_FEATURE_DTYPE)
+    m = np.concatenate(pairs) if pairs else np.zeros(0, capi.FEATURE_MATCH_DTYPE)
+    arrays = {"features_per_frame": np.array([len(x) for x in feats], np.float64),
+              "matches_per_pair": np.array([len(x) for x in pairs], np.float64)}
+    rows = {"features": (f, 8 + 8 + 12), "matches": (m, 16)}  # float64 index + float32 fields, bytes per row as written
+    budget = limit - sum(a.nbytes for a in arrays.values()) - 4096  # (.npy headers)
+    if sum(len(r) * w for r, w in rows.values()) > budget:
+        frac = budget / sum(len(r) * (w + 8) for r, w in rows.values())  # (+ the float64 row number of each kept row)
+        rng = np.random.default_rng(20240601)
+        for name, (r, w) in rows.items():
+            keep = np.sort(rng.choice(len(r), size=int(len(r) * frac), replace=False))
+            arrays[name + "_sample_rows"] = keep.astype(np.float64)
+            rows[name] = (r[keep], w)
+    f, m = rows["features"][0], rows["matches"][0]
+    arrays.update({"feature_idx": f["feature_idx"].astype(np.float64),
+                   "feature_pixel": f["pixel"].astype(np.float32),
+                   "feature_point3d": f["point3d"].astype(np.float32),
+                   "match_feature_idx": np.stack([m["feature_idx_initial"], m["feature_idx_current"]], 1).astype(np.float64)})
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -555,8 +617,19 @@ def main() -> int:
                     help="N > 1: a rank whose process group / handshake has not come up after this many seconds exits 124")
     ap.add_argument("--no-gloo-retry", action="store_true",
                     help="bare `--gpus N` form: do not repeat a run whose RCCL set-up failed with the collectives on gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the in-line stage pass, the sustained leg, the drop-in API "
+                         "figures, BASELINE's other configurations and the CPU baselines (each --no-* option still drops one); "
+                         "default: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the VisionFeature / FeatureMatch records of the last timed step (every "
+                         "rank's, as rank 0 receives them) to DIR/<name>.npy in float32 / float64, at most 64 MB")
     args = ap.parse_args()
-    if args.leg:
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_inline_pass = True
+    if args.leg or not args.full:
         args.no_sustained = args.no_observe = args.no_cpu_baseline = args.no_other_configs = True
     cfg = CONFIGS[args.config]
     if args.cpu_baseline_child:
@@ -761,6 +834,11 @@ def main() -> int:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     report_stage("after the timed steps")
+    # the last timed step's records, taken before any further step (the in-line pass, the sustained leg) reuses the buffers
+    if args.dump_outputs:
+        payloads = last_step_payloads(sf)
+        if payloads is not None:
+            dump_outputs(payloads, args.dump_outputs)
     # `stages`: the stream that carries the extraction and the stereo matcher (the step's critical path);
     # `tail_stages`: the tail's own stream when it overlaps the next step (wall intervals under contention with the
     # extraction kernels, so they add up to more than the step -- reported separately, never summed into it)
@@ -1061,7 +1139,8 @@ def main() -> int:
                 and args.nfeatures is None and args.batch is None):
             other = {}
             for name, extra in (("1080p_8000", ["--config", "1080p", "--batch", "64"]), ("window8", ["--window", "8"])):
-                cmd = [sys.executable, str(ROOT / "bench.py"), "--leg", "--steps", "8", "--warmup", "2", "--tune-steps", "4"] + extra
+                cmd = [sys.executable, str(ROOT / "bench.py"), "--leg", "--full", "--steps", "8", "--warmup", "2", "--tune-steps",
+                       "4"] + extra
                 t_leg = time.perf_counter()
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)

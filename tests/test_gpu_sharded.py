@@ -352,13 +352,13 @@ def test_bench_bare_form_two_ranks_on_one_gpu():
     """`python3 bench.py --gpus 2 ...` started EXACTLY like that (no torch.distributed.run, no WORLD_SIZE in the
     environment): the parent launches its two ranks as fresh children before it touches torch or the GPU, relays rank 0's
     one JSON line and returns 0.  On this one-GPU box the ranks share device 0 and talk over gloo (VSF_BENCH_ONE_GPU=1);
-    the launch path is the one an 8-GPU node takes.  The sustained leg runs with a small count."""
+    the launch path is the one an 8-GPU node takes.  The sustained leg (--full) runs with a small count."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["VSF_BENCH_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--batch", "8", "--steps", "3", "--warmup", "1",
-                        "--width", "320", "--height", "240", "--nfeatures", "600", "--sustained-steps", "600"],
+                        "--width", "320", "--height", "240", "--nfeatures", "600", "--full", "--sustained-steps", "600"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -1,36 +1,19 @@
-"""Cross-checks of the oracle against an INDEPENDENT third-party implementation that happens to be installed in the
-build container: scikit-image 0.18.3 under /opt/conda (python 3.9).  It is neither the reference nor OpenCV, so this does
-not pin parity with the reference (DESIGN.md section 2 stays "parity unpinned"); it does show that three definitions the
-oracle restates from memory of OpenCV are not misremembered:
+"""Cross-checks of the oracle against an INDEPENDENT third-party implementation: scikit-image 0.18.3.  It is neither the
+reference nor OpenCV, so this does not pin parity with the reference (DESIGN.md section 2 stays "parity unpinned"); it does
+show that three definitions the oracle restates from memory of OpenCV are not misremembered:
   * the FAST-9/16 segment test (the set of corners before non-max suppression),
   * the intensity-centroid orientation over the radius-15 disc (skimage's OFAST_MASK = OpenCV's umax table),
   * rotated BRIEF: pattern table, rotation, sampling, comparison and bit order (skimage ships OpenCV's bit_pattern_31_).
-Skipped where that interpreter is absent."""
-import os
-import subprocess
+scikit-image's answers (tests/third_party/skimage_probe.py) are stored in tests/golden/skimage/ together with a digest of the
+inputs they were computed from (tests/skimage_golden.py; refreshed by tools/make_skimage_golden.py)."""
 import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-PY39 = "/opt/conda/bin/python3.9"
-PROBE = str(Path(__file__).resolve().parent / "third_party" / "skimage_probe.py")
-
-
-def _probe(*args):
-    env = dict(os.environ, PYTHONWARNINGS="ignore")
-    subprocess.check_call([PY39, PROBE, *map(str, args)], env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-
-
-@pytest.fixture(scope="module")
-def skimage_ok():
-    if not Path(PY39).exists():
-        pytest.skip("no /opt/conda python 3.9")
-    r = subprocess.run([PY39, "-c", "import skimage.feature.orb_cy"], capture_output=True)
-    if r.returncode != 0:
-        pytest.skip("scikit-image not importable")
-    return True
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import skimage_golden as skg  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -41,40 +24,27 @@ def image320():
 
 
 @pytest.mark.parametrize("threshold", [10, 20, 40])
-def test_fast9_corner_set_equals_skimage(oracle, skimage_ok, image320, tmp_path, threshold):
-    np.save(tmp_path / "img.npy", image320)
-    _probe("fast", tmp_path / "img.npy", threshold, tmp_path / "out.npy")
-    theirs = set(map(tuple, np.load(tmp_path / "out.npy").tolist()))
+def test_fast9_corner_set_equals_skimage(oracle, image320, threshold):
+    theirs = skg.corner_set("synth320", image320, threshold)
     kp = oracle.fast9_16(image320, threshold, nms=False)
     ours = set(zip(kp["x"].astype(int).tolist(), kp["y"].astype(int).tolist()))
     assert len(ours) > 3000
     assert ours == theirs
 
 
-def test_ic_angle_agrees_with_skimage(oracle, skimage_ok, image320, tmp_path):
-    o = oracle.Orb(nfeatures=2000, nlevels=1)
-    o.run(image320)
-    kp = o.stage(4, 0)
+def test_ic_angle_agrees_with_skimage(oracle, image320):
+    img, pts, kp = skg.angle_input(oracle, image320)
     assert len(kp) > 500
-    np.save(tmp_path / "img.npy", image320)
-    np.save(tmp_path / "pts.npy", np.stack([kp["x"].astype(np.int32), kp["y"].astype(np.int32)], 1))
-    _probe("angle", tmp_path / "img.npy", tmp_path / "pts.npy", tmp_path / "out.npy")
-    theirs = np.degrees(np.load(tmp_path / "out.npy")) % 360.0
+    theirs = np.degrees(skg.angles("synth320", img, pts)) % 360.0
     diff = np.abs(((kp["angle"] - theirs) + 180.0) % 360.0 - 180.0)
     assert diff.max() < 0.3  # cv::fastAtan2's documented accuracy; measured: < 0.01 degrees
 
 
-def test_rotated_brief_bits_equal_skimage(oracle, skimage_ok, image320, tmp_path):
-    o = oracle.Orb(nfeatures=2000, nlevels=1)  # one level: final keypoints are level coordinates
-    o.run(image320)
-    _, desc = o.result()
-    kp = o.stage(4, 0)
-    assert len(kp) == len(desc) > 500
-    np.save(tmp_path / "img.npy", o.level_image(0, blurred=True))
-    np.save(tmp_path / "pts.npy", np.stack([kp["x"].astype(np.int32), kp["y"].astype(np.int32)], 1))
-    np.save(tmp_path / "ang.npy", np.radians(kp["angle"].astype(np.float64)))
-    _probe("desc", tmp_path / "img.npy", tmp_path / "pts.npy", tmp_path / "ang.npy", tmp_path / "out.npy")
-    theirs = np.load(tmp_path / "out.npy")
+def test_rotated_brief_bits_equal_skimage(oracle, image320):
+    # one level: final keypoints are level coordinates
+    blurred, pts, ang, desc = skg.desc_input(oracle, image320)
+    assert len(pts) == len(desc) > 500
+    theirs = skg.brief_bits("synth320", blurred, pts, ang)
     ours = np.unpackbits(desc, axis=1, bitorder="little")  # bit i of byte k = pair 8 k + i
     # (float vs double trig may move a sample across a rounding boundary once in a long while: allow a stray bit)
     ham = (theirs != ours).sum(1)

@@ -15,7 +15,7 @@ print('$t sclk', g(r'sclk clock level: \\d+: \\((\\d+)Mhz'), 'mclk', g(r'mclk cl
   done ) > "$out/sustained_clocks.txt" &
 SM=$!
 sleep 1
-python3 bench.py --no-cpu-baseline --no-observe "$@" > "$out/sustained_bench.json" 2> "$out/sustained_bench.err"
+python3 bench.py --full --no-cpu-baseline --no-observe "$@" > "$out/sustained_bench.json" 2> "$out/sustained_bench.err"
 kill $SM 2>/dev/null
 wait $SM 2>/dev/null
 python3 - "$out" <<'PY'

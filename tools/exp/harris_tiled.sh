@@ -9,9 +9,9 @@ out=$PWD/gpurun_out/harris_tiled
 mkdir -p $out
 for v in normal exp; do
   cp tools/exp/_so/libvsf_hip_$v.so vision_slam_frontend_amd/libvsf_hip.so
-  python3 bench.py --leg --steps 10 --warmup 2 > $out/bench_$v.json 2> $out/bench_$v.err
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch_$v -o pmc -- python3 bench.py --leg --blur-inline --no-pipeline --steps 3 --warmup 1 > $out/pmc_$v.json 2> $out/pmc_$v.err
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write_$v -o pmc -- python3 bench.py --leg --blur-inline --no-pipeline --steps 3 --warmup 1 > $out/pmcw_$v.json 2> $out/pmcw_$v.err
+  python3 bench.py --leg --full --steps 10 --warmup 2 > $out/bench_$v.json 2> $out/bench_$v.err
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch_$v -o pmc -- python3 bench.py --leg --full --blur-inline --no-pipeline --steps 3 --warmup 1 > $out/pmc_$v.json 2> $out/pmc_$v.err
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write_$v -o pmc -- python3 bench.py --leg --full --blur-inline --no-pipeline --steps 3 --warmup 1 > $out/pmcw_$v.json 2> $out/pmcw_$v.err
 done
 cp tools/exp/_so/libvsf_hip_normal.so vision_slam_frontend_amd/libvsf_hip.so
 python3 - $out <<'PY'

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 out=$PWD/gpurun_out/prof_$tag
 mkdir -p "$out"
 if [ "$mode" = stats ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o bench -- python3 bench.py --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o bench -- python3 bench.py --full --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
   python3 - "$out" <<'PY'
 import sys, glob
 for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):
@@ -16,7 +16,7 @@ for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):
 PY
 else
   counters=$1; shift
-  rocprofv3 --pmc $counters --output-format csv -d "$out" -o pmc -- python3 bench.py --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
+  rocprofv3 --pmc $counters --output-format csv -d "$out" -o pmc -- python3 bench.py --full --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
   python3 - "$out" <<'PY'
 import sys, glob, csv, collections
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):

@@ -5,14 +5,14 @@
 #    rehearsal_2ranks_bare_form_bench.json, capi_collectives_world_of_one_bench.json, cpp_sharded_driver_1gpu.json,
 #    time_match.txt, observe_depth.txt, sustained_clocks.txt / sustained_bench.json
 out=gpurun_out/$1; mkdir -p $out
-B="python3 bench.py --no-cpu-baseline --no-observe"
+B="python3 bench.py --full --no-cpu-baseline --no-observe"
 $B --ingest jpeg > $out/jpeg_ingest_bench.json 2> $out/jpeg_ingest_bench.err
 $B --ingest png --no-sustained > $out/png_ingest_bench.json 2> $out/png_ingest_bench.err
 $B --window 8 > $out/window8_bench.json 2> $out/window8_bench.err
 $B --scene sparse > $out/sparse_scene_bench.json 2> $out/sparse_scene_bench.err
 $B --config 1080p > $out/1080p_batch32_bench.json 2> $out/1080p_batch32_bench.err
 $B --collectives capi --no-sustained > $out/capi_collectives_world_of_one_bench.json 2> $out/capi.err
-VSF_BENCH_ONE_GPU=1 python3 bench.py --gpus 2 --batch 16 --steps 10 --sustained-steps 600 > $out/rehearsal_2ranks_bare_form_bench.json 2> $out/rehearsal.err
+VSF_BENCH_ONE_GPU=1 python3 bench.py --full --gpus 2 --batch 16 --steps 10 --sustained-steps 600 > $out/rehearsal_2ranks_bare_form_bench.json 2> $out/rehearsal.err
 echo "rehearsal rc=$?" >> $out/rehearsal.err
 python3 tools/time_match.py > $out/time_match.txt 2>&1
 python3 tools/time_png.py 512 2>&1 | grep -E "^(synthetic|photographs)" > $out/png_time.txt
