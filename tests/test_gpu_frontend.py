@@ -14,7 +14,7 @@ F_RECT = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)  # l^T F r = y
 POINT_RTOL, PIXEL_ATOL = 1e-5, 1e-4  # floating point: relative per coordinate of point3d; pixels
 
 
-def _model(oracle, frames, frame_life, best_percent=np.float32(0.3), calib=None):
+def _model(oracle, frames, frame_life, best_percent=np.float32(0.3), calib=None, F=F_RECT):
     thr = np.float32(10000.0)
     frame_list, factors, kept_frames = [], [], []
     for fid, (left, right) in enumerate(frames):
@@ -24,7 +24,7 @@ def _model(oracle, frames, frame_life, best_percent=np.float32(0.3), calib=None)
         kl, dl = ol.result()
         kr, dr = orr.result()
         m = oracle.get_matches(dl, dr)
-        keep, _, thr_new, _ = oracle.remove_ambig_stereo(kl, kr, m, F_RECT, float(thr))
+        keep, _, thr_new, _ = oracle.remove_ambig_stereo(kl, kr, m, F, float(thr))
         thr = np.float32(thr_new)
         kl2, dl2 = kl[m["queryIdx"][keep]], dl[m["queryIdx"][keep]]
         kr2, dr2 = kr[m["trainIdx"][keep]], dr[m["trainIdx"][keep]]

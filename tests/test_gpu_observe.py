@@ -12,57 +12,64 @@ F_RECT = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)
 POINT_RTOL, PIXEL_ATOL = 1e-5, 1e-4
 
 
-def _follow_reference_sequence(oracle, frames, width, height, NF, LIFE):
+def _follow_reference_sequence(oracle, frames, width, height, NF, LIFE, F=F_RECT, order=0, max_keypoints=0, results=None):
     """Runs `frames` [(left, right)] through vsf_observe_stereo and through the reference's sequence on the oracle, frame by
-    frame; returns the context (still open), the calibration and the per-frame feature counts."""
+    frame; returns the context (still open), the calibration and the per-frame feature counts.  F: the fundamental matrix;
+    order: vsf_params::residual_order (the oracle follows it); max_keypoints: the context's capacity (0: the default);
+    results: the observations to check, one per frame, instead of the synchronous calls' (a queue's, say)."""
     from vision_slam_frontend_amd import capi, frontend
-    calib = frontend.default_calibration().set("fundamental", F_RECT)
+    calib = frontend.default_calibration().set("fundamental", F)
     bp = float(np.float32(0.3))
-    ctx = capi.Context(capi.default_params(width, height, max_images=2, nfeatures=NF))
+    over = dict(max_keypoints=max_keypoints) if max_keypoints else {}
+    ctx = capi.Context(capi.default_params(width, height, max_images=2, nfeatures=NF, residual_order=order, **over))
     thr = np.float32(10000.0)
     window = []  # filtered left descriptors of the kept frames, oldest first
     sizes = []
-    for fid, (left, right) in enumerate(frames):
-        got = ctx.observe_stereo(left, right, calib, best_percent=bp, frame_life=LIFE)
-        # --- the reference's sequence on the oracle ---
-        ol, orr = oracle.Orb(nfeatures=NF), oracle.Orb(nfeatures=NF)
-        ol.run(left)
-        orr.run(right)
-        kl, dl = ol.result()
-        kr, dr = orr.result()
-        m = oracle.get_matches(dl, dr)
-        keep, res, thr_next, kept = oracle.remove_ambig_stereo(kl, kr, m, F_RECT, float(thr))
-        kl2, dl2 = kl[m["queryIdx"][keep]], dl[m["queryIdx"][keep]]
-        kr2, dr2 = kr[m["trainIdx"][keep]], dr[m["trainIdx"][keep]]
-        assert (got["n_left"], got["n_right"], got["n_stereo_matches"]) == (len(kl), len(kr), len(m))
-        assert got["threshold"].tobytes() == thr.tobytes() or (np.isnan(got["threshold"]) and np.isnan(thr))
-        assert got["threshold_next"].tobytes() == np.float32(thr_next).tobytes() or \
-            (np.isnan(got["threshold_next"]) and np.isnan(thr_next))
-        assert got["keypoints"].tobytes() == kl2.tobytes()
-        np.testing.assert_array_equal(got["descriptors"], dl2)
-        assert len(got["factors"]) == len(window)
-        for past, fac in zip(window, got["factors"]):  # cc:424-434, oldest kept frame first
-            mm = oracle.sort_and_trim(oracle.get_matches(past, dl2), bp)
-            np.testing.assert_array_equal(fac["feature_idx_initial"], mm["queryIdx"])
-            np.testing.assert_array_equal(fac["feature_idx_current"], mm["trainIdx"])
-        rl = oracle.sort_and_trim(oracle.get_matches(dr2, dl2), 1.0)  # cc:129-132
-        np.testing.assert_array_equal(got["stereo_pairs"]["feature_idx_initial"], rl["queryIdx"])
-        np.testing.assert_array_equal(got["stereo_pairs"]["feature_idx_current"], rl["trainIdx"])
-        want, npts = oracle.vision_features(kl2, dl2, kr2, dr2, calib.get("projection_left"), calib.get("projection_right"),
-                                            calib.get("camera_matrix_left"), calib.get("distortion_left"))
-        f = got["features"]
-        assert got["n_points"] == npts and len(f) == len(want)
-        np.testing.assert_array_equal(f["feature_idx"], want["feature_idx"])
-        assert np.abs(f["pixel"].astype(np.float64) - want["pixel"]).max(initial=0.0) <= PIXEL_ATOL
-        g, w = f["point3d"].astype(np.float64), want["point3d"].astype(np.float64)
-        fin = np.isfinite(w)
-        assert np.array_equal(np.isfinite(g), fin)
-        assert (np.abs(g[fin] - w[fin]) / np.maximum(np.abs(w[fin]), 1e-30)).max(initial=0.0) <= POINT_RTOL
-        thr = np.float32(thr_next)
-        if len(window) >= LIFE:
-            window.pop(0)
-        window.append(dl2)
-        sizes.append(len(kl2))
+    oracle.set_residual_order(order)
+    try:
+        for fid, (left, right) in enumerate(frames):
+            got = results[fid] if results is not None else ctx.observe_stereo(left, right, calib, best_percent=bp, frame_life=LIFE)
+            # --- the reference's sequence on the oracle ---
+            ol, orr = oracle.Orb(nfeatures=NF), oracle.Orb(nfeatures=NF)
+            ol.run(left)
+            orr.run(right)
+            kl, dl = ol.result()
+            kr, dr = orr.result()
+            m = oracle.get_matches(dl, dr)
+            keep, res, thr_next, kept = oracle.remove_ambig_stereo(kl, kr, m, F, float(thr))
+            kl2, dl2 = kl[m["queryIdx"][keep]], dl[m["queryIdx"][keep]]
+            kr2, dr2 = kr[m["trainIdx"][keep]], dr[m["trainIdx"][keep]]
+            assert (got["n_left"], got["n_right"], got["n_stereo_matches"]) == (len(kl), len(kr), len(m))
+            assert got["threshold"].tobytes() == thr.tobytes() or (np.isnan(got["threshold"]) and np.isnan(thr))
+            assert got["threshold_next"].tobytes() == np.float32(thr_next).tobytes() or \
+                (np.isnan(got["threshold_next"]) and np.isnan(thr_next))
+            assert got["keypoints"].tobytes() == kl2.tobytes()
+            np.testing.assert_array_equal(got["descriptors"], dl2)
+            assert len(got["factors"]) == len(window)
+            for past, fac in zip(window, got["factors"]):  # cc:424-434, oldest kept frame first
+                mm = oracle.sort_and_trim(oracle.get_matches(past, dl2), bp)
+                np.testing.assert_array_equal(fac["feature_idx_initial"], mm["queryIdx"])
+                np.testing.assert_array_equal(fac["feature_idx_current"], mm["trainIdx"])
+            rl = oracle.sort_and_trim(oracle.get_matches(dr2, dl2), 1.0)  # cc:129-132
+            np.testing.assert_array_equal(got["stereo_pairs"]["feature_idx_initial"], rl["queryIdx"])
+            np.testing.assert_array_equal(got["stereo_pairs"]["feature_idx_current"], rl["trainIdx"])
+            want, npts = oracle.vision_features(kl2, dl2, kr2, dr2, calib.get("projection_left"), calib.get("projection_right"),
+                                                calib.get("camera_matrix_left"), calib.get("distortion_left"))
+            f = got["features"]
+            assert got["n_points"] == npts and len(f) == len(want)
+            np.testing.assert_array_equal(f["feature_idx"], want["feature_idx"])
+            assert np.abs(f["pixel"].astype(np.float64) - want["pixel"]).max(initial=0.0) <= PIXEL_ATOL
+            g, w = f["point3d"].astype(np.float64), want["point3d"].astype(np.float64)
+            fin = np.isfinite(w)
+            assert np.array_equal(np.isfinite(g), fin)
+            assert (np.abs(g[fin] - w[fin]) / np.maximum(np.abs(w[fin]), 1e-30)).max(initial=0.0) <= POINT_RTOL
+            thr = np.float32(thr_next)
+            if len(window) >= LIFE:
+                window.pop(0)
+            window.append(dl2)
+            sizes.append(len(kl2))
+    finally:
+        oracle.set_residual_order(0)
     return ctx, calib, sizes
 
 

@@ -133,3 +133,31 @@ def test_vision_features_follow_sorted_match_order(oracle):
     np.testing.assert_array_equal(feats["point3d"], X[:, :3] / X[:, 3:])
     np.testing.assert_array_equal(feats["pixel"], oracle.undistort_points(np.c_[left["x"], left["y"]], K, dist))
     assert (np.diff(m["distance"]) >= 0).all() and not np.array_equal(m["queryIdx"], np.arange(n))
+
+
+@pytest.mark.parametrize("rows", [6, 4])
+def test_triangulation_within_the_derived_float64_bound(oracle, rows):
+    """The noisy correspondences above against tests/stereo_tail_ref.py's definition: numpy's float64 SVD of the same DLT
+    rows, narrowed and divided in float (cc:159-165), within triangulation_bound (derived there) per coordinate of the
+    point, not of the unit vector -- the bar the HIP kernel is held to as well."""
+    import stereo_tail_ref as R
+    _, P1, P2, _ = _reference_calibration()
+    rng = np.random.default_rng(11)
+    n = 300
+    X = np.c_[rng.uniform(-3, 3, n), rng.uniform(-2, 2, n), rng.uniform(0.5, 30, n), np.ones(n)]
+    x1 = (_project(P1, X) + rng.normal(0, 1.0, (n, 2))).astype(np.float32)
+    x2 = (_project(P2, X) + rng.normal(0, 1.0, (n, 2))).astype(np.float32)
+    Y = oracle.triangulate_points(P1, P2, x1, x2, rows)
+    ref = R.triangulate64(P1, P2, x1, x2, rows)
+    assert R.triangulation_excess(ref, Y[:, :3] / Y[:, 3:]) <= 1.0
+    assert np.isfinite(R.triangulation_bound(ref)).all()
+
+
+def test_undistort_equals_the_float64_restatement_bit_for_bit(oracle):
+    """cvUndistortPoints' loop restated operation for operation in numpy float64 (tests/stereo_tail_ref.py undistort64):
+    the oracle's pixels are the same floats over the whole image and a margin around it."""
+    import stereo_tail_ref as R
+    K, _, _, dist = _reference_calibration()
+    rng = np.random.default_rng(5)
+    pts = np.c_[rng.uniform(-20, 980, 2000), rng.uniform(-20, 620, 2000)].astype(np.float32)
+    assert R.ulp_distance(oracle.undistort_points(pts, K, dist), R.undistort64(pts, K, dist)).max() == 0
