@@ -420,6 +420,48 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx);
  * ran on one stream, launches forced by a collect or a change of parameters, launches that had to wait for a batch slot,
  * depth, frames per batch at most, then the host's nanoseconds inside staging copies, batch launches, waits for results }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
+/* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
+ * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,
+ * draws the stereo image (2w x h) and the match image (w x h) -- GRAY2BGR, 3 bytes per pixel, as vsf_draw_canvases draws --
+ * and copies them into a pinned debug ring beside the result ring.  The stereo lines' colours are
+ * cv::Scalar(rand() % 255, rand() % 255, rand() % 255) from the process's rand(), drawn ahead at submit (GCC's right-to-left
+ * argument order: the first call is channel 2) and taken in frame and match order, so the colours are the reference's
+ * sequence while rand() itself may run ahead of it.  Result header word 14 then says which images the frame has (bit 0
+ * stereo: not without a right -> left match, cc:131-133; bit 1 match: not without a kept frame), word 15 how many colours
+ * it took.  Off (the default): results, launches and their cost are exactly those without the switch.  It changes only
+ * before the queue's first frame (or after vsf_observe_reset); the queue is then rebuilt with the threshold carried over. */
+vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on);
+/* A collected frame's debug images inside the pinned debug ring (NULL where the frame has none); valid under the rule of
+ * vsf_observe_collect_view (until `depth` further frames have been submitted). */
+vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match);
+
+/* ---------------- Debug images: cv::circle / cv::line onto GRAY2BGR canvases (slam_frontend.cc:74-115) ----------------
+ * Each canvas is GRAY2BGR of one grey image, or of two side by side (cv::hconcat), 3 bytes per pixel, with its slice of the
+ * operation list drawn in list order as OpenCV 3.2's drawing.cpp does at thickness 1 / LINE_8 / shift 0: a circle is the
+ * integer midpoint Circle() and writes only the pixels inside the canvas; a line is LineIterator (8-connected, left to
+ * right) after clipLine.  Later operations overwrite earlier ones.  Coordinates are integers (cvRound is the caller's:
+ * round half to even); |coordinate| must stay below 2^29, and a radius above 65535 draws nothing. */
+enum { VSF_DRAW_CIRCLE = 0, VSF_DRAW_LINE = 1 };
+typedef struct {
+  int32_t kind;    /* VSF_DRAW_CIRCLE: centre (x0, y0), radius x1 (0 .. 65535); VSF_DRAW_LINE: (x0, y0)-(x1, y1) */
+  int32_t x0, y0, x1, y1;
+  uint8_t bgr[4];  /* the colour's bytes in canvas order (cv::Scalar channels 0, 1, 2); bgr[3] is ignored */
+} vsf_draw_op;     /* 24 bytes */
+typedef struct {
+  const uint8_t* src0;    /* grey source */
+  const uint8_t* src1;    /* NULL, or a second grey source of the same size drawn to the right of src0 */
+  int32_t width, height;  /* of one source: the canvas is (src1 ? 2 : 1) * width x height */
+  int64_t src_pitch;      /* bytes between rows of either source */
+  uint8_t* out;           /* the canvas, 3 bytes per pixel */
+  int64_t out_pitch;
+  int32_t op_begin, op_count;  /* its operations: ops[op_begin, op_begin + op_count) */
+} vsf_draw_canvas;
+/* n canvases in one batch on the context's stream (does not wait).  `canvases` is host memory; its src0 / src1 / out and
+ * d_ops (n_ops operations) are device pointers. */
+vsf_status vsf_draw_canvases_dev(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int n, const vsf_draw_op* d_ops, int n_ops);
+/* The same with every pointer in host memory (sources, canvases, operations): uploads, draws, copies the canvases back and
+ * waits.  What the host Frontend calls. */
+vsf_status vsf_draw_canvases(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int n, const vsf_draw_op* ops, int n_ops);
 
 /* SURVEY section 8(f) row f4, the decode itself: DecodeImage's cv::imdecode(msg.data, cv::IMREAD_GRAYSCALE)
  * (slam_frontend_main.cc:99-100) for n JPEG files in HOST memory (the CompressedImage payloads), all of width x height:

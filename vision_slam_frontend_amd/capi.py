@@ -38,6 +38,7 @@ EXPORTS = [
     "vsf_observe_configure", "vsf_observe_collect_view", "vsf_observe_stats", "vsf_observe_poll", "vsf_debug_jpeg_serial",
     "vsf_jpeg_decode_gray_batch", "vsf_png_decode_gray_batch", "vsf_imdecode_gray_batch", "vsf_tune_fast_resident", "vsf_set_option", "vsf_get_option", "vsf_debug_inject_hip_error", "vsf_comm_unique_id", "vsf_comm_create", "vsf_comm_destroy", "vsf_comm_info",
     "vsf_allgather_dev", "vsf_gather_payload_dev", "vsf_reserve", "vsf_set_input_event",
+    "vsf_observe_set_debug_images", "vsf_observe_debug_view", "vsf_draw_canvases_dev", "vsf_draw_canvases",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -70,6 +71,19 @@ class VsfCalibration(C.Structure):
 
     def get(self, name: str) -> np.ndarray:
         return np.array(list(getattr(self, name)), np.float32)
+
+
+# vsf_draw_op (include/vsf.h): kind, x0, y0, x1 (a circle's radius), y1, colour bytes in canvas (B, G, R) order
+DRAW_CIRCLE, DRAW_LINE = 0, 1
+DRAW_OP_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("bgr", "u1", (4,))])
+assert DRAW_OP_DTYPE.itemsize == 24
+
+
+class VsfDrawCanvas(C.Structure):
+    """vsf_draw_canvas: GRAY2BGR of src0 (and src1 to its right) with ops[op_begin, op_begin + op_count) drawn on it."""
+    _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("src_pitch", C.c_int64), ("out", C.c_void_p), ("out_pitch", C.c_int64), ("op_begin", C.c_int32),
+                ("op_count", C.c_int32)]
 
 
 class VsfError(RuntimeError):
@@ -156,6 +170,10 @@ def lib() -> C.CDLL:
         L.vsf_observe_stereo.argtypes = [vp, vp, vp, i32, i32, sz, C.POINTER(VsfCalibration), C.c_float, i32, vp, sz,
                                          C.POINTER(sz)]
         L.vsf_observe_reset.argtypes = [vp]
+        L.vsf_observe_set_debug_images.argtypes = [vp, i32]
+        L.vsf_observe_debug_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
+        L.vsf_draw_canvases_dev.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
+        L.vsf_draw_canvases.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
         L.vsf_jpeg_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_png_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_imdecode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
@@ -508,6 +526,16 @@ class Context:
         if st != VSF_OK and st not in allow_status:
             raise VsfError(st, "vsf_png_decode_gray_batch", lib().vsf_last_hip_error(self._h))
         return st
+
+    def draw_canvases_dev(self, canvases, d_ops: int, n_ops: int):
+        """vsf_draw_canvases_dev: canvases is a list of dicts with the fields of VsfDrawCanvas (device pointers as ints);
+        d_ops points at n_ops DRAW_OP_DTYPE records in device memory.  Asynchronous on the context's stream."""
+        arr = (VsfDrawCanvas * max(len(canvases), 1))()
+        for i, c in enumerate(canvases):
+            for k, v in c.items():
+                setattr(arr[i], k, v)
+        return self._check(lib().vsf_draw_canvases_dev(self._h, arr, len(canvases), C.c_void_p(d_ops or None), n_ops),
+                           "vsf_draw_canvases_dev")
 
     def imdecode_gray_batch(self, files, width: int, height: int, d_dst: int, dst_image_stride: int,
                             dst_row_stride: int, allow_status=()):

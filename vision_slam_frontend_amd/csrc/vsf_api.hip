@@ -579,6 +579,10 @@ void vsf_destroy(vsf_ctx* ctx) {
   hipFree(ctx->t_nmatches);
   hipFree(ctx->t_sortkeys);
   free_observe(ctx);
+  hipFree(ctx->dr_win);
+  hipFree(ctx->dr_canv);
+  hipFree(ctx->dr_buf);
+  if (ctx->dr_uploaded) hipEventDestroy(ctx->dr_uploaded);
   hipFree(ctx->jp_flags);
   hipFree(ctx->png_filtered);
   hipFree(ctx->png_file_status);

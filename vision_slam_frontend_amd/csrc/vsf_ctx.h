@@ -150,6 +150,20 @@ struct vsf_ctx {
   struct Observe {
     bool ready = false;
     int frame_life = 0;
+    bool debug = false;  // built with ob_debug: the batches' tails draw the debug images
+    // debug images: device canvases [bmax][dbg_stride], winners [bmax][3 w h], operations [bmax][5 K], canvas table [2 bmax],
+    // the newest kept frame's keypoints, {colour cursor (i64), its count}; pinned: the debug ring [depth][dbg_stride] and the
+    // colour ring [col_ring] (colours drawn: col_generated, taken by collected frames: col_retired)
+    uint8_t* dbg_canvas = nullptr;
+    uint64_t* dbg_win = nullptr;
+    vsf_draw_op* dbg_ops = nullptr;
+    void* dbg_table = nullptr;
+    vsf_keypoint* dbg_prev_kp = nullptr;
+    int64_t* dbg_ints = nullptr;
+    size_t dbg_stride = 0;
+    uint8_t* h_dbg = nullptr;
+    uint32_t* h_col = nullptr;
+    int64_t col_ring = 0, col_generated = 0, col_retired = 0;
     int depth = 0;      // frames that may be submitted and not collected
     int bmax = 0;       // frames per batch at most
     int ring = 0;       // descriptor sets [0, ring): the kept left frames (frame g in set g % ring); [ring, ring + bmax): the
@@ -190,6 +204,17 @@ struct vsf_ctx {
   } ob;
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
+  bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
+  // vsf_draw_canvases(_dev) (k_draw.hip): per-pixel winners (all zero between calls: the resolve clears what it read),
+  // the canvas table (device, and its host image until the upload has left: dr_uploaded), the host call's staging
+  uint64_t* dr_win = nullptr;
+  size_t dr_win_cap = 0;
+  void* dr_canv = nullptr;
+  int dr_canv_cap = 0;
+  std::vector<uint8_t> dr_canv_host;
+  hipEvent_t dr_uploaded = nullptr;
+  uint8_t* dr_buf = nullptr;
+  size_t dr_buf_cap = 0;
   // vsf_jpeg_decode_gray_batch: pinned staging + device copy of the packed headers / tables / entropy-coded segments
   // (two sets, used alternately: the host fills one while the previous call's upload / decode still use the other)
   int32_t* jp_flags = nullptr;  // [jp_flags_cap] per progressive file of a call: damaged, decode again scan after scan

@@ -264,6 +264,34 @@ struct VsfObserveArgs {
   uint32_t out_cap;
 };
 void vsf_launch_observe_pack(const VsfObserveArgs& a, int max_pairs_per_frame, hipStream_t s);
+// The queue's debug images (k_draw.hip, vsf_observe_set_debug_images): per frame of a batch, the operations of
+// CreateStereoDebugImage / CreateMatchDebugImage (slam_frontend.cc:74-115) built from the filtered keypoints and the sorted
+// pairs, drawn into device canvases [n][stereo 2w x h x 3 | match w x h x 3]; then the newest frame's keypoints are kept for
+// the next batch and the colour cursor advances.  Header words 14 / 15 of each result: images present (bit 0 stereo, bit 1
+// match), colours used.
+struct VsfObserveDebugArgs {
+  int n_frames, max_rows, width, height;
+  const uint8_t* images;          // the batch's uploaded images: frame f left at 2f * image_stride, right one stride on
+  size_t image_stride, image_pitch;
+  const vsf_keypoint* kp_f;       // [2n][max_rows] filtered keypoints (left, right)
+  const int32_t* counts_f;        // [2n]
+  const uint64_t* pairs;          // [pairs][max_rows][2]
+  const int32_t* npairs;
+  const VsfObserveFrame* frames;  // [n]
+  vsf_keypoint* prev_kp;          // [max_rows] the newest kept frame of earlier batches
+  int32_t* prev_n;
+  const uint32_t* colours;        // pinned ring of packed b | g << 8 | r << 16, drawn from rand() by the host
+  int64_t colour_ring;
+  int64_t* colour_cursor;         // colours used by every frame launched before this batch
+  vsf_draw_op* ops;               // [n][5 max_rows]
+  void* canvases;                 // [2n] canvas table (k_draw.hip)
+  uint8_t* canvas;                // [n][canvas_stride]
+  size_t canvas_stride;
+  uint64_t* winners;              // [n][3 w h], zero between batches
+  uint8_t* out;                   // result ring: header words 14 / 15
+  size_t out_stride;
+};
+void vsf_launch_observe_debug(const VsfObserveDebugArgs& a, hipStream_t s);
 
 // k_jpeg.hip (cv::imdecode(IMREAD_GRAYSCALE) for baseline JPEG)
 #ifdef __cplusplus

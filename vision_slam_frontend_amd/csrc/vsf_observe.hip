@@ -24,6 +24,7 @@
 #include <cmath>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <condition_variable>
 #include <mutex>
@@ -211,6 +212,14 @@ void free_observe(vsf_ctx* ctx) {
   hipFree(o.features);
   if (o.h_img) hipHostFree(o.h_img);
   if (o.h_out) hipHostFree(o.h_out);
+  hipFree(o.dbg_canvas);
+  hipFree(o.dbg_win);
+  hipFree(o.dbg_ops);
+  hipFree(o.dbg_table);
+  hipFree(o.dbg_prev_kp);
+  hipFree(o.dbg_ints);
+  if (o.h_dbg) hipHostFree(o.h_dbg);
+  if (o.h_col) hipHostFree(o.h_col);
   for (vsf_ctx::ObserveBatch& b : o.batch) {
     hipFree(b.d_img);
     hipFree(b.kp_raw);
@@ -237,7 +246,7 @@ void launcher_thread(vsf_ctx* ctx);
 
 vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.ready && o.frame_life == frame_life) return VSF_OK;
+  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug) return VSF_OK;
   sync_all_streams(ctx);
   float thr_state = 10000.0f;  // cc:353
   if (o.floats) VSF_HIP(hipMemcpy(&thr_state, o.floats + 2 * o.bmax + 1, sizeof(float), hipMemcpyDeviceToHost));
@@ -247,6 +256,7 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.depth = ctx->ob_depth > 0 ? ctx->ob_depth : frames_cap;
   o.bmax = std::min(o.depth, frames_cap);
   o.frame_life = frame_life;
+  o.debug = ctx->ob_debug;
   o.ring = frame_life + o.bmax;
   o.max_pairs = o.bmax * (frame_life + 1);
   const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)o.ring + B;
@@ -274,6 +284,21 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.out_stride = (o.out_cap + 255) & ~(size_t)255;
   VSF_HIP(hipHostMalloc((void**)&o.h_img, (size_t)o.depth * 2 * ctx->st_img_stride, hipHostMallocMapped));
   VSF_HIP(hipHostMalloc((void**)&o.h_out, (size_t)o.depth * o.out_stride, hipHostMallocMapped));
+  if (o.debug) {  // vsf_observe_set_debug_images: canvases, winners, operations, the pinned debug ring and colour ring
+    const size_t wh = (size_t)ctx->p.width * ctx->p.height;
+    o.dbg_stride = (9 * wh + 255) & ~(size_t)255;  // stereo 2w x h x 3 | match w x h x 3
+    o.col_ring = (int64_t)(o.depth + 1) * (int64_t)K;
+    VSF_HIP(hipMalloc((void**)&o.dbg_canvas, B * o.dbg_stride));
+    VSF_HIP(hipMalloc((void**)&o.dbg_win, B * 3 * wh * sizeof(uint64_t)));
+    VSF_HIP(hipMemset(o.dbg_win, 0, B * 3 * wh * sizeof(uint64_t)));
+    VSF_HIP(hipMalloc((void**)&o.dbg_ops, B * 5 * K * sizeof(vsf_draw_op)));
+    VSF_HIP(hipMalloc(&o.dbg_table, 2 * B * 128));
+    VSF_HIP(hipMalloc((void**)&o.dbg_prev_kp, K * sizeof(vsf_keypoint)));
+    VSF_HIP(hipMalloc((void**)&o.dbg_ints, 16));
+    VSF_HIP(hipMemset(o.dbg_ints, 0, 16));
+    VSF_HIP(hipHostMalloc((void**)&o.h_dbg, (size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
+    VSF_HIP(hipHostMalloc((void**)&o.h_col, (size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
+  }
   for (vsf_ctx::ObserveBatch& b : o.batch) {
     VSF_HIP(hipMalloc((void**)&b.d_img, 2 * B * ctx->st_img_stride));
     VSF_HIP(hipMalloc((void**)&b.kp_raw, 2 * B * K * sizeof(vsf_keypoint)));
@@ -455,6 +480,43 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
     a.out_cap = (uint32_t)std::min<size_t>(o.out_cap, 0xFFFFFFF0u);
     vsf_launch_observe_pack(a, max_pairs_per_frame, s_tail);
   }
+  if (o.debug) {
+    // ---- the debug images (slam_frontend.cc:74-115, 167-171, 458-466) of every frame, drawn in the batch's tail from what
+    // it holds in HBM, then into the frames' slots of the pinned debug ring (one copy, two when the slots wrap) ----
+    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 6);
+    VsfObserveDebugArgs d;
+    d.n_frames = n;
+    d.max_rows = Kc;
+    d.width = ctx->p.width;
+    d.height = ctx->p.height;
+    d.images = b.d_img;
+    d.image_stride = ctx->st_img_stride;
+    d.image_pitch = ctx->st_img_pitch;
+    d.kp_f = o.kpf;
+    d.counts_f = counts_f;
+    d.pairs = o.pairs;
+    d.npairs = o.npairs;
+    d.frames = M.frames;
+    d.prev_kp = o.dbg_prev_kp;
+    d.prev_n = reinterpret_cast<int32_t*>(o.dbg_ints + 1);
+    d.colours = o.h_col;
+    d.colour_ring = o.col_ring;
+    d.colour_cursor = o.dbg_ints;
+    d.ops = o.dbg_ops;
+    d.canvases = o.dbg_table;
+    d.canvas = o.dbg_canvas;
+    d.canvas_stride = o.dbg_stride;
+    d.winners = o.dbg_win;
+    d.out = o.h_out;
+    d.out_stride = o.out_stride;
+    vsf_launch_observe_debug(d, s_tail);
+    const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
+    VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
+                           hipMemcpyDeviceToHost, s_tail));
+    if (first < n)
+      VSF_HIP(hipMemcpyAsync(o.h_dbg, o.dbg_canvas + (size_t)first * o.dbg_stride, (size_t)(n - first) * o.dbg_stride,
+                             hipMemcpyDeviceToHost, s_tail));
+  }
   VSF_HIP(hipEventRecord(b.ev_done, s_tail));
   b.used = true;
   b.done_stream = s_tail;
@@ -575,6 +637,33 @@ size_t vsf_observe_capacity(const vsf_ctx* ctx, int frame_life) {
   return 64 + 4 * (size_t)((frame_life + 1 + 3) & ~3) + K * (28 + 28 + 32) + (size_t)(frame_life + 1) * K * 16;
 }
 
+vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx) return VSF_ERR_INVALID_ARG;
+  if ((on != 0) == ctx->ob_debug) return VSF_OK;
+  // only before the window holds a frame: the next submit rebuilds the queue (ensure_observe carries the threshold)
+  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
+  if (ctx->ob.ready) stop_observe_threads(ctx);
+  ctx->ob_debug = on != 0;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !stereo || !match) return VSF_ERR_INVALID_ARG;
+  *stereo = *match = nullptr;
+  const vsf_ctx::Observe& o = ctx->ob;
+  // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_collect_view)
+  if (!o.ready || !o.debug || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+    return VSF_ERR_INVALID_ARG;
+  const int slot = (int)(ticket % o.depth);
+  const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
+  const uint8_t* base = o.h_dbg + (size_t)slot * o.dbg_stride;
+  if (flags & 1) *stereo = base;
+  if (flags & 2) *match = base + (size_t)6 * ctx->p.width * ctx->p.height;
+  return VSF_OK;
+}
+
 vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_flight) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
   if (!ctx || depth < 0 || depth > 1024 || min_batch < 0 || in_flight < 0 || in_flight > vsf_ctx::kObserveBatchSlots - 1)
@@ -648,6 +737,16 @@ vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* 
   }
   // ---- the two images into the frame's slot of the pinned staging ring, rows at the device pitch (the slot's previous
   // frame has been collected: its upload is long done) ----
+  if (o.debug) {
+    // the stereo lines' colours, cv::Scalar(rand() % 255, rand() % 255, rand() % 255) (cc:95) in the reference's order --
+    // GCC evaluates the three calls right to left: the first is channel 2 -- drawn ahead: enough for every frame in the queue
+    // (a frame takes at most max_keypoints); the device takes them in frame order from its cursor
+    const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (o.next_ticket + 1 - o.next_collect) * K;
+    for (; o.col_generated < want; o.col_generated++) {
+      const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
+      o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
+    }
+  }
   uint8_t* h_img = o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
   const int64_t t_copy = now_ns();
   const vsf_ctx::ObserveCopyHelper::Job jr{h_img + ctx->st_img_stride, right, ctx->st_img_pitch, stride, (size_t)w, h};
@@ -707,6 +806,7 @@ static vsf_status observe_wait(vsf_ctx* ctx, int64_t ticket, const uint8_t** vie
   {
     std::unique_lock<std::mutex> lk(L.mu);
     o.next_collect = ticket + 1;
+    if (o.debug) o.col_retired += hdr[15];  // the colours this frame's stereo image took
     if (!L.has_thread) st = caller_pump(ctx, lk, false);  // (the GPU may have room again)
   }
   if (hdr[0] != 0x4F465356u) return VSF_ERR_HIP;

@@ -59,6 +59,10 @@ def lib() -> C.CDLL:
         L.vsfh_serialize_calibration.argtypes = [vp, vp, vp]
         L.vsfh_serialize_calibration.restype = None
         L.vsfh_flush.argtypes = [vp]
+        L.vsfh_set_debug_images.argtypes = [vp, i32]
+        L.vsfh_set_debug_images.restype = None
+        L.vsfh_num_debug_images.argtypes = [vp, i32]
+        L.vsfh_debug_image.argtypes = [vp, i32, i32, vp, sz, vp]
         _lib = L
     return _lib
 
@@ -76,10 +80,12 @@ def default_calibration() -> capi.VsfCalibration:
 
 class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
-                 best_percent: float = 0.0, frame_life: int = 0):
+                 best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False):
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
+        if debug_images:  # FrontendConfig::debug_images_ (the reference's default is on, slam_frontend.cc:552)
+            lib().vsfh_set_debug_images(self._h, 1)
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend")
@@ -122,6 +128,22 @@ class Frontend:
         if fps < 0:
             raise capi.VsfError(lib().vsfh_last_status(self._h), "Frontend::ObserveImage (time_sequence)")
         return float(fps), float(mean.value), float(worst.value)
+
+    def _debug_image(self, stereo: bool, i: int):
+        shape = np.zeros(3, np.int32)
+        if not lib().vsfh_debug_image(self._h, int(stereo), i, None, 0, _p(shape)):
+            return None
+        out = np.zeros(tuple(int(v) for v in shape), np.uint8)
+        lib().vsfh_debug_image(self._h, int(stereo), i, _p(out), out.nbytes, _p(shape))
+        return out
+
+    def debug_images(self, stereo: bool = False):
+        """getDebugImages() (stereo: getDebugStereoImages()) as rows x cols x 3 arrays, bytes in OpenCV's B, G, R order."""
+        return [self._debug_image(stereo, i) for i in range(lib().vsfh_num_debug_images(self._h, int(stereo)))]
+
+    def last_debug_image(self, stereo: bool = False):
+        """GetLastDebugImage() (stereo: GetLastDebugStereoImage()); None for the reference's empty cv::Mat."""
+        return self._debug_image(stereo, -1)
 
     def flush(self) -> bool:
         """Collects and books every frame still in flight."""

@@ -88,6 +88,31 @@ double vsfh_time_sequence(void* f, const uint8_t* frames, int n_src, int w, int 
 }
 int vsfh_flush(void* f) { return static_cast<Frontend*>(f)->Flush() ? 1 : 0; }
 
+// Debug images (slam_frontend.cc:474-495).  stereo = 0: getDebugImages / GetLastDebugImage; 1: the stereo ones.
+void vsfh_set_debug_images(void* f, int on) { static_cast<Frontend*>(f)->set_debug_images(on != 0); }
+int vsfh_num_debug_images(void* f, int stereo) {
+  Frontend* fe = static_cast<Frontend*>(f);
+  return (int)(stereo ? fe->getDebugStereoImages() : fe->getDebugImages()).size();
+}
+// Image i (i = -1: GetLastDebugImage / GetLastDebugStereoImage): its shape into rows_cols_ch[3], min(size, cap) bytes
+// (rows packed) into out.  Returns 1, or 0 when there is no such image (the getter's empty cv::Mat).
+int vsfh_debug_image(void* f, int stereo, int i, uint8_t* out, size_t cap, int rows_cols_ch[3]) {
+  Frontend* fe = static_cast<Frontend*>(f);
+  slam::Image im;
+  if (i < 0) {
+    im = stereo ? fe->GetLastDebugStereoImage() : fe->GetLastDebugImage();
+  } else {
+    const std::vector<slam::Image> all = stereo ? fe->getDebugStereoImages() : fe->getDebugImages();
+    if (i < (int)all.size()) im = all[i];
+  }
+  rows_cols_ch[0] = rows_cols_ch[1] = rows_cols_ch[2] = 0;
+  if (im.empty()) return 0;
+  rows_cols_ch[0] = im.rows, rows_cols_ch[1] = im.cols, rows_cols_ch[2] = im.channels;
+  const size_t row = (size_t)im.cols * im.channels;
+  for (int y = 0; y < im.rows && out && (size_t)(y + 1) * row <= cap; y++) std::memcpy(out + y * row, im.data + y * im.step, row);
+  return 1;
+}
+
 void vsfh_frontend_destroy(void* f) { delete static_cast<Frontend*>(f); }
 
 void vsfh_observe_odometry(void* f, const float t[3], const float q_wxyz[4], double ts) {

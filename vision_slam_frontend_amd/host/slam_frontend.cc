@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 namespace slam {
@@ -118,7 +119,9 @@ void SmallestRightSingularVector(double At[4][6], int M, double out[4]) {
 
 // ---- configuration: the reference's hard-coded defaults (cc:550-652) ----
 FrontendConfig::FrontendConfig() {
-  debug_images_ = false;  // reference: true (quirk Q10: retains every image forever); rendering is out of scope
+  // reference: true (cc:552; quirk Q10: it retains every image forever).  Off here so that nothing is drawn or kept unless
+  // asked for; on, the images are the reference's byte for byte (drawn on the GPU, csrc/k_draw.hip).
+  debug_images_ = false;
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
   descriptor_extract_type_ = DescriptorExtractorType::ORB;
   best_percent_ = 0.3f;
@@ -268,6 +271,8 @@ bool Frontend::EnsureContext(int width, int height) {
   for (const auto& ov : ctx_options_)
     if (last_status_ == VSF_OK) last_status_ = vsf_set_option(ctx_, ov.first, ov.second);
   if (last_status_ == VSF_OK) last_status_ = vsf_observe_configure(ctx_, ctx_depth_, min_batch_, 0);
+  // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
+  if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
   pending_.assign((size_t)ctx_depth_, PendingFrame());
   pending_head_ = pending_count_ = 0;
   return last_status_ == VSF_OK;
@@ -500,11 +505,13 @@ void Frontend::RemoveAmbigStereo(Frame* left, Frame* right, const std::vector<vs
 // singular vector of the smallest singular value of the 6 x 4 system OpenCV 3.2 builds: x*P2-P0, y*P2-P1, x*P1-y*P0 per
 // view, in double) and the homogeneous divide in float.  Same arithmetic as the device kernel (csrc/k_points.hip);
 // against real OpenCV the values agree to rounding (its SVD may run through LAPACK), not bit for bit.
-void Frontend::Calculate3DPoints(Frame* left_frame, Frame* right_frame, std::vector<Vector3f>* points) {
+void Frontend::Calculate3DPoints(Frame* left_frame, Frame* right_frame, std::vector<Vector3f>* points,
+                                 VisionFactor* matches_out) {
   const float best_percent = config_.best_percent_;
   config_.best_percent_ = 1.0f;
   const VisionFactor matches = GetFeatureMatches(right_frame, left_frame);
   config_.best_percent_ = best_percent;
+  if (matches_out) *matches_out = matches;
   if (matches.feature_matches.empty()) return;
   const float* P[2] = {config_.projection_left, config_.projection_right};
   for (const FeatureMatch& match : matches.feature_matches) {
@@ -656,6 +663,17 @@ bool Frontend::RetireOldest() {
     right_temp_frame.frame_ID_ = curr_frame_ID_;
     book(right_temp_frame, &curr_frame, pair_bytes[n_pairs - 1], npairs[n_pairs - 1], nullptr);
   }
+  if (config_.debug_images_) {  // drawn in the batch's tail (vsf_observe_set_debug_images); kept, as the reference keeps them
+    const uint8_t *stereo = nullptr, *match = nullptr;
+    last_status_ = vsf_observe_debug_view(ctx_, pf.ticket, &stereo, &match);
+    if (last_status_ != VSF_OK) return false;
+    vsf_params p;
+    vsf_get_params(ctx_, &p);
+    if (stereo) debug_stereo_images_.push_back(OwnedImage{std::vector<uint8_t>(stereo, stereo + (size_t)6 * p.width * p.height),
+                                                          p.height, 2 * p.width});
+    if (match) debug_images_.push_back(OwnedImage{std::vector<uint8_t>(match, match + (size_t)3 * p.width * p.height),
+                                                  p.height, p.width});
+  }
   std::vector<VisionFeature> features;
   features.reserve((size_t)nfeat);
   for (int i = 0; i < nfeat; i++) {  // cc:438-443, computed on the device
@@ -706,7 +724,16 @@ bool Frontend::ObserveImage(const Image& left_image, const Image& right_image, d
   RemoveAmbigStereo(&curr_frame, &right_temp_frame, stereo_matches);
   GetFeatureMatchesAll(&frame_list_, &curr_frame, &vision_factors_);
   std::vector<Vector3f> points;
-  Calculate3DPoints(&curr_frame, &right_temp_frame, &points);
+  VisionFactor stereo;
+  Calculate3DPoints(&curr_frame, &right_temp_frame, &points, &stereo);
+  if (config_.debug_images_) {
+    const bool match_image = !frame_list_.empty() && !vision_factors_.empty();  // cc:458-466
+    DrawDebugImages(left_image.data, right_image.data, left_image.cols, left_image.rows, left_image.step, curr_frame,
+                    right_temp_frame.keypoints_, stereo.feature_matches.empty() ? nullptr : &stereo.feature_matches,
+                    match_image ? &frame_list_.back() : nullptr,
+                    match_image ? &vision_factors_.back().feature_matches : nullptr);
+    if (last_status_ != VSF_OK) return false;
+  }
   std::vector<VisionFeature> features;
   for (uint64_t i = 0; i < curr_frame.keypoints_.size(); i++) {
     // The reference indexes points[i] by keypoint although `points` is in sorted-match order and may be shorter
@@ -727,6 +754,114 @@ void Frontend::GetSLAMProblem(SLAMProblem* problem) const {
 int Frontend::GetNumPoses() {
   Flush();
   return (int)nodes_.size();
+}
+
+void Frontend::set_debug_images(bool on) {
+  // (before the first ObserveImage: the queue's window and frame_list_ must start together)
+  if (!nodes_.empty() || pending_count_ > 0) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  config_.debug_images_ = on;
+  if (ctx_) last_status_ = vsf_observe_set_debug_images(ctx_, on ? 1 : 0);
+}
+
+std::vector<Image> Frontend::getDebugImages() {
+  Flush();
+  std::vector<Image> out;
+  for (const OwnedImage& im : debug_images_) out.push_back(im.view());
+  return out;
+}
+
+std::vector<Image> Frontend::getDebugStereoImages() {
+  Flush();
+  std::vector<Image> out;
+  for (const OwnedImage& im : debug_stereo_images_) out.push_back(im.view());
+  return out;
+}
+
+Image Frontend::GetLastDebugImage() {
+  Flush();
+  return debug_images_.empty() ? Image() : debug_images_.back().view();
+}
+
+Image Frontend::GetLastDebugStereoImage() {
+  Flush();
+  return debug_stereo_images_.empty() ? Image() : debug_stereo_images_.back().view();
+}
+
+namespace {
+int CvRound(float v) { return (int)std::lrint(v); }  // cvRound: round half to even (the default rounding mode)
+}  // namespace
+
+// cc:74-115.  Points are cvRound(Point2f) as cv::circle / cv::line take them (cv::Point), the stereo image's right points
+// after adding the left image's width to the float x (cc:90).  The line colours are the reference's expression,
+// cv::Scalar(rand() % 255, rand() % 255, rand() % 255), one stereo match after the other, frame by frame -- the process's
+// own rand() stream, called in the reference's order.  The order in which those three calls run is unspecified in C++; GCC
+// evaluates the arguments of that constructor call right to left, so the FIRST draw is channel 2 (the byte the driver
+// labels R), the third is channel 0.  This choice follows the reference's usual build and is not pinned by a test against
+// it.
+void Frontend::DrawDebugImages(const uint8_t* left, const uint8_t* right, int w, int h, size_t pitch,
+                               const Frame& curr_frame, const std::vector<vsf_keypoint>& right_keypoints,
+                               const std::vector<FeatureMatch>* stereo, const Frame* past_frame,
+                               const std::vector<FeatureMatch>* temporal) {
+  std::vector<vsf_draw_op> ops;
+  std::vector<vsf_draw_canvas> canvases;
+  auto circle = [&](int x, int y, const uint8_t bgr[3]) {
+    vsf_draw_op op = {VSF_DRAW_CIRCLE, x, y, 5, 0, {bgr[0], bgr[1], bgr[2], 0}};
+    ops.push_back(op);
+  };
+  auto line = [&](int x0, int y0, int x1, int y1, const uint8_t bgr[3]) {
+    vsf_draw_op op = {VSF_DRAW_LINE, x0, y0, x1, y1, {bgr[0], bgr[1], bgr[2], 0}};
+    ops.push_back(op);
+  };
+  const uint8_t red[3] = {0, 0, 255}, green[3] = {0, 255, 0};  // CV_RGB(255, 0, 0), CV_RGB(0, 255, 0)
+  const std::vector<vsf_keypoint>& lk = curr_frame.keypoints_;
+  OwnedImage stereo_image, match_image;
+  if (stereo) {  // CreateStereoDebugImage
+    vsf_draw_canvas c = {left, right, w, h, (int64_t)pitch, nullptr, (int64_t)6 * w, (int32_t)ops.size(), 0};
+    for (const FeatureMatch& m : *stereo) {
+      uint8_t bgr[3];  // (drawn for every pair, as cc:95 does: the colours keep the reference's sequence)
+      bgr[2] = (uint8_t)(rand() % 255);
+      bgr[1] = (uint8_t)(rand() % 255);
+      bgr[0] = (uint8_t)(rand() % 255);
+      if (m.feature_idx_current >= lk.size() || m.feature_idx_initial >= right_keypoints.size()) continue;
+      const vsf_keypoint& l = lk[m.feature_idx_current];
+      const vsf_keypoint& r = right_keypoints[m.feature_idx_initial];
+      const int lx = CvRound(l.x), ly = CvRound(l.y), rx = CvRound(r.x + (float)w), ry = CvRound(r.y);
+      circle(lx, ly, red);
+      circle(rx, ry, red);
+      line(lx, ly, rx, ry, bgr);
+    }
+    c.op_count = (int32_t)ops.size() - c.op_begin;
+    stereo_image.rows = h;
+    stereo_image.cols = 2 * w;
+    stereo_image.data.resize((size_t)6 * w * h);
+    c.out = stereo_image.data.data();
+    canvases.push_back(c);
+  }
+  if (past_frame && temporal) {  // CreateMatchDebugImage
+    vsf_draw_canvas c = {left, nullptr, w, h, (int64_t)pitch, nullptr, (int64_t)3 * w, (int32_t)ops.size(), 0};
+    const std::vector<vsf_keypoint>& pk = past_frame->keypoints_;
+    for (const FeatureMatch& m : *temporal) {
+      if (m.feature_idx_initial >= pk.size() || m.feature_idx_current >= lk.size()) continue;
+      const vsf_keypoint& a = pk[m.feature_idx_initial];
+      const vsf_keypoint& b = lk[m.feature_idx_current];
+      circle(CvRound(a.x), CvRound(a.y), red);
+      line(CvRound(a.x), CvRound(a.y), CvRound(b.x), CvRound(b.y), green);
+    }
+    c.op_count = (int32_t)ops.size() - c.op_begin;
+    match_image.rows = h;
+    match_image.cols = w;
+    match_image.data.resize((size_t)3 * w * h);
+    c.out = match_image.data.data();
+    canvases.push_back(c);
+  }
+  if (canvases.empty()) return;
+  last_status_ = vsf_draw_canvases(ctx_, canvases.data(), (int)canvases.size(), ops.data(), (int)ops.size());
+  if (last_status_ != VSF_OK) return;
+  if (stereo) debug_stereo_images_.push_back(std::move(stereo_image));
+  if (past_frame && temporal) debug_images_.push_back(std::move(match_image));
 }
 
 }  // namespace slam

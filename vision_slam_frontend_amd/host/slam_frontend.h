@@ -1,7 +1,7 @@
 // slam_frontend.h -- host-side mirror of the reference's slam::Frontend (src/slam_frontend.h:117-142) on top of
 // the C ABI of include/vsf.h.  Same public method names and semantics:
 //   ObserveImage (cc:400-472), ObserveOdometry (cc:250-263), GetSLAMProblem (cc:498-503), GetNumPoses (cc:505),
-//   GetConfig (h:142), debug-image getters (cc:474-495, return empty: debug rendering is out of scope).
+//   GetConfig (h:142), the debug-image getters (cc:474-495; drawn on the GPU by vsf_draw_canvases, csrc/k_draw.hip).
 // cv::Mat is replaced by slam::Image (a non-owning view) and Eigen types by the PODs of slam_types.h; both swaps
 // are mechanical for a maintainer who has OpenCV / Eigen.  The two private methods that call
 // OpenCV in the reference -- ExtractFeatures (cc:266) and GetMatches (cc:521) -- call vsf_extract /
@@ -24,13 +24,15 @@ using slam_types::Quaternionf;
 using slam_types::Vector2f;
 using slam_types::Vector3f;
 
-// Non-owning 8-bit single-channel image view (stands in for `const cv::Mat&`).
+// Non-owning 8-bit image view (stands in for `const cv::Mat&`): single-channel unless `channels` says otherwise (the debug
+// images are 3-channel, bytes in OpenCV's B, G, R order).
 struct Image {
   const uint8_t* data = nullptr;
   int rows = 0, cols = 0;
   size_t step = 0;
+  int channels = 1;
   Image() {}
-  Image(const uint8_t* d, int r, int c, size_t s) : data(d), rows(r), cols(c), step(s) {}
+  Image(const uint8_t* d, int r, int c, size_t s, int ch = 1) : data(d), rows(r), cols(c), step(s), channels(ch) {}
   bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
 };
 
@@ -124,10 +126,14 @@ class Frontend {
   void GetSLAMProblem(slam_types::SLAMProblem* problem) const;
   int GetNumPoses();
   FrontendConfig GetConfig() { return config_; }
-  std::vector<Image> getDebugImages() { return {}; }
-  Image GetLastDebugImage() { return Image(); }
-  Image GetLastDebugStereoImage() { return Image(); }
-  std::vector<Image> getDebugStereoImages() { return {}; }
+  // cc:474-495.  With config.debug_images_ on, every node keeps a match image (CreateMatchDebugImage, cc:100-115; from the
+  // second node on) and a stereo image (CreateStereoDebugImage, cc:74-98; unless the node has no stereo match, cc:131-133)
+  // for the object's lifetime.  Like GetNumPoses these book the frames still in flight first; the views point into memory
+  // the object owns and stay valid while it lives.
+  std::vector<Image> getDebugImages();
+  Image GetLastDebugImage();
+  Image GetLastDebugStereoImage();
+  std::vector<Image> getDebugStereoImages();
 
   // Additions (not in the reference): error reporting instead of abort, and read access for tests.
   vsf_status last_status() const { return last_status_; }
@@ -144,6 +150,8 @@ class Frontend {
   // Flush).  Same nodes, factors and bytes as the
   // synchronous mode; a GPU failure then surfaces in last_status() some calls late.
   void set_pipelined(bool on) { pipelined_ = on; }
+  // config.debug_images_ after construction (before the first ObserveImage; later calls fail with VSF_ERR_INVALID_ARG).
+  void set_debug_images(bool on);
   // Frames ObserveImage may leave in the queue when pipelined (1..1024, default 256) and the most frames one batch carries
   // (default 128; the context's extraction buffers are sized for it: ~25 MB of HBM per 640x480 frame; the queue's staging
   // and result rings are pinned host memory: depth x (two images + vsf_observe_capacity)).  Measured on an MI355X at
@@ -190,7 +198,8 @@ class Frontend {
   void RemoveAmbigStereo(Frame* left, Frame* right, const std::vector<vsf_dmatch>& stereo_matches);
   void AddOdometryFactor();
   void UndistortFeaturePoints(std::vector<slam_types::VisionFeature>* features);
-  void Calculate3DPoints(Frame* left_frame, Frame* right_frame, std::vector<Vector3f>* points);
+  void Calculate3DPoints(Frame* left_frame, Frame* right_frame, std::vector<Vector3f>* points,
+                         slam_types::VisionFactor* matches_out = nullptr);
   bool EnsureContext(int width, int height);
   bool ObserveImageFused(const Image& left_image, const Image& right_image);
   void FinishNode(const Frame& curr_frame, const std::vector<slam_types::VisionFeature>& features);
@@ -202,6 +211,18 @@ class Frontend {
     Quaternionf odom_rotation, prev_odom_rotation;
     double odom_timestamp;
   };
+  // An image the object owns (one entry of debug_images_ / debug_stereo_images_).
+  struct OwnedImage {
+    std::vector<uint8_t> data;
+    int rows = 0, cols = 0;
+    Image view() const { return Image(data.data(), rows, cols, (size_t)cols * 3, 3); }
+  };
+  // Per-call mode: CreateStereoDebugImage (cc:74-98, when `stereo` is given) and CreateMatchDebugImage (cc:100-115, when
+  // `temporal` is) of one node, drawn on the GPU in one vsf_draw_canvases call (the queue draws its own in the batch's tail) and appended to the lists in that order.  stereo pairs are
+  // (right index, left index), temporal pairs (past index, current index), as booked.
+  void DrawDebugImages(const uint8_t* left, const uint8_t* right, int w, int h, size_t pitch, const Frame& curr_frame,
+                       const std::vector<vsf_keypoint>& right_keypoints, const std::vector<slam_types::FeatureMatch>* stereo,
+                       const Frame* past_frame, const std::vector<slam_types::FeatureMatch>* temporal);
   bool RetireOldest();
   void Sync() const { const_cast<Frontend*>(this)->Flush(); }
 
@@ -221,6 +242,7 @@ class Frontend {
   std::vector<slam_types::OdometryFactor> odometry_factors_;
   // The reference keeps this in a file-static shared by all instances (cc:353, quirk Q3); here it is per object.
   float stereo_ambig_constraint_;
+  std::vector<OwnedImage> debug_images_, debug_stereo_images_;  // cc h:202-203: kept for the object's lifetime
   bool fused_;
   bool pipelined_;
   int depth_ = 256, batch_frames_ = 128, min_batch_ = 0;
