@@ -535,6 +535,12 @@ vsf_status vsf_debug_level_image(vsf_ctx* ctx, int image, int level, int blurred
  * with size 7, angle -1, response = score.  */
 vsf_status vsf_debug_fast_candidates(vsf_ctx* ctx, int image, int level, vsf_keypoint* kp_out, int cap,
                                      int* n_out);
+/* Host only, no device needed: the FAST work items vsf_create (orb != 0) or vsf_fast_detect (orb == 0, nms) would build for
+ * *p.  words[0 .. *n_words) receives the full-cell words (level << 24 | band << 16 | strip; *n_full of them), then the
+ * packed items of VSF_FAST_PACK_WORDS words each (layout in csrc/vsf_internal.h).  levels_out (10 ints per level, up to
+ * level_cap levels): w, h, x_lo, x_hi, y_lo, y_hi, fast_a0, nbands, nstrips, unit0.  VSF_ERR_CAPACITY if cap is short. */
+vsf_status vsf_debug_fast_work(const vsf_params* p, int orb, int nms, uint32_t* words, int cap, int* n_words, int* n_full,
+                               int32_t* levels_out, int level_cap);
 /* Final per-level keypoints in level coordinates (after both retainBest cuts, with angle). */
 vsf_status vsf_debug_level_keypoints(vsf_ctx* ctx, int image, int level, vsf_keypoint* kp_out, int cap,
                                      int* n_out);

@@ -1,0 +1,140 @@
+"""CPU checks of the FAST work decomposition (vsf_debug_fast_work, no device needed): the narrow cells of every level are
+packed into waves by lane count, and every cell of every level is walked exactly once, by one full-wave item or by one
+segment of one packed item that has its own two halo lanes."""
+import ctypes as C
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+BAND, SR, PACK_SEGS = 248, 32, 8
+PACK_WORDS = 4 + 2 * PACK_SEGS
+
+SIZES = [(640, 480), (1920, 1080), (97, 71), (1283, 727), (333, 257), (161, 131), (100, 75), (64, 64), (801, 601),
+         (1001, 99), (99, 1001), (515, 322), (1279, 719), (2047, 1535)]
+
+
+@pytest.fixture(scope="module")
+def capi():
+    sys.path.insert(0, str(ROOT))
+    import __graft_entry__ as g
+    from vision_slam_frontend_amd import capi
+    if not capi.LIB_PATH.exists():
+        g.build()
+    return capi
+
+
+def work(capi, p, orb=True, nms=True):
+    cap = 1 << 20
+    words = np.zeros(cap, np.uint32)
+    levels = np.zeros((64, 10), np.int32)
+    nw, nf = C.c_int(), C.c_int()
+    st = capi.lib().vsf_debug_fast_work(C.byref(p), int(orb), int(nms), words.ctypes.data, cap, C.byref(nw), C.byref(nf),
+                                        levels.ctypes.data, 64)
+    assert st == capi.VSF_OK
+    nlev = p.nlevels if orb else 1
+    return words[:nf.value], words[nf.value:nw.value].reshape(-1, PACK_WORDS), levels[:nlev]
+
+
+def cell_shape(lv, band, strip):
+    w, h, x_lo, x_hi, y_lo, y_hi, a0 = (int(v) for v in lv[:7])
+    bx0 = a0 + BAND * band
+    cols = min(x_hi, bx0 + BAND) - bx0
+    rows = min(SR, y_hi - (y_lo + SR * strip))
+    return (cols + 3) // 4 + 2, rows
+
+
+def check(levels, full, packs):
+    seen = {}
+    for wd in full:
+        key = (int(wd >> 24), int((wd >> 16) & 0xFF), int(wd & 0x7FFF))
+        seen[key] = seen.get(key, 0) + 1
+    for it in packs:
+        nseg, rows, mixed, rim = (int(v) for v in it[:4])
+        assert 2 <= nseg <= PACK_SEGS
+        assert not it[4 + 2 * nseg:].any()  # unused slots stay zero
+        first_expected, seg_rows, lvls = 0, [], []
+        for k in range(nseg):
+            w0, w1 = int(it[4 + 2 * k]), int(it[5 + 2 * k])
+            key = (w0 >> 24, (w0 >> 16) & 0xFF, w0 & 0x7FFF)
+            seen[key] = seen.get(key, 0) + 1
+            first, lanes, r = w1 & 0xFF, (w1 >> 8) & 0xFF, w1 >> 16
+            want_lanes, want_rows = cell_shape(levels[key[0]], key[1], key[2])
+            assert lanes == want_lanes >= 3, "segment: its columns plus one halo lane on each side"
+            assert r == want_rows
+            assert first == first_expected, "segments are contiguous and do not overlap"
+            first_expected += lanes
+            seg_rows.append(r)
+            lvls.append(key[0])
+        assert first_expected <= 64
+        assert rows == max(seg_rows) and mixed == int(len(set(seg_rows)) > 1)
+        assert len({l == 0 for l in lvls}) == 1, "level 0 (the input image) never shares a wave with pyramid levels"
+        want_rim = any(levels[l][4] - 1 < 3 or levels[l][5] >= levels[l][1] - 3 for l in lvls)
+        assert rim == int(want_rim)
+    expected = {(l, b, s) for l, lv in enumerate(levels) for s in range(int(lv[8])) for b in range(int(lv[7]))}
+    assert set(seen) == expected, "every cell of every level is walked"
+    assert all(v == 1 for v in seen.values()), "... exactly once"
+    for l, b, s in (tuple(int(x) for x in (wd >> 24, (wd >> 16) & 0xFF, wd & 0x7FFF)) for wd in full):
+        assert cell_shape(levels[l], b, s)[0] <= 64
+    return seen
+
+
+def issued_lane_steps(levels, full, packs):
+    """lanes x score steps (rows + 2 per wave) of the decomposition"""
+    n = sum(64 * (cell_shape(levels[wd >> 24], (wd >> 16) & 0xFF, wd & 0x7FFF)[1] + 2) for wd in full)
+    return n + sum(64 * (int(it[1]) + 2) for it in packs)
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+def test_orb_cells_packed_once(capi, w, h):
+    p = capi.default_params(w, h)
+    full, packs, levels = work(capi, p)
+    check(levels, full, packs)
+    assert all(int(it[3]) == 0 for it in packs)  # the ORB border keeps every score row off FAST's rim
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("nms", [True, False])
+def test_standalone_fast_cells_packed_once(capi, w, h, nms):
+    p = capi.default_params(w, h)
+    full, packs, levels = work(capi, p, orb=False, nms=nms)
+    check(levels, full, packs)
+
+
+def test_other_pyramids(capi):
+    for kw in (dict(nlevels=8, scale_factor=1.2), dict(nlevels=1), dict(nlevels=20, scale_factor=1.1)):
+        for w, h in ((640, 480), (333, 257), (1920, 1080)):
+            p = capi.default_params(w, h)
+            for k, v in kw.items():
+                setattr(p, k, v)
+            full, packs, levels = work(capi, p)
+            check(levels, full, packs)
+
+
+def test_sweep_reaches_short_last_strips_and_mixed_waves(capi):
+    rows_seen, mixed = set(), 0
+    for w, h in SIZES:
+        full, packs, levels = work(capi, capi.default_params(w, h))
+        for it in packs:
+            mixed += int(it[2])
+            rows_seen |= {int(it[5 + 2 * k]) >> 16 for k in range(int(it[0]))}
+    assert {1, 2} <= rows_seen and mixed > 0
+
+
+def test_packing_lowers_issued_lanes_at_640x480(capi):
+    """The work model of the packed form against one wave per cell (the layout before packing)."""
+    full, packs, levels = work(capi, capi.default_params(640, 480))
+    packed = issued_lane_steps(levels, full, packs)
+    per_cell = sum(64 * (cell_shape(lv, b, s)[1] + 2) for lv in levels for s in range(int(lv[8])) for b in range(int(lv[7])))
+    assert packed < 0.80 * per_cell
+
+
+def test_argument_checks(capi):
+    L = capi.lib()
+    p = capi.default_params(640, 480)
+    nw, nf = C.c_int(), C.c_int()
+    assert L.vsf_debug_fast_work(None, 1, 1, None, 0, C.byref(nw), C.byref(nf), None, 0) == capi.VSF_ERR_INVALID_ARG
+    assert L.vsf_debug_fast_work(C.byref(p), 1, 1, None, 0, C.byref(nw), C.byref(nf), None, 0) == capi.VSF_ERR_CAPACITY
+    assert nw.value > nf.value > 0

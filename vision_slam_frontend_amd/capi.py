@@ -30,7 +30,7 @@ EXPORTS = [
     "vsf_params_default", "vsf_params_set_ratio", "vsf_create", "vsf_destroy", "vsf_status_string",
     "vsf_last_hip_error", "vsf_get_params", "vsf_set_stream", "vsf_sync", "vsf_level_info", "vsf_extract",
     "vsf_fast_detect", "vsf_knn2_hamming", "vsf_get_matches", "vsf_extract_pair", "vsf_get_matches_multi", "vsf_extract_batch_dev", "vsf_match_batch_dev",
-    "vsf_stereo_batch_dev", "vsf_set_lanes", "vsf_set_pipeline", "vsf_set_blur_overlap", "vsf_set_fast_resident", "vsf_get_fast_resident", "vsf_remove_ambig_stereo_batch_dev", "vsf_feature_matches_batch_dev", "vsf_bayer_bg_to_gray_batch_dev", "vsf_debug_level_image", "vsf_debug_fast_candidates", "vsf_debug_level_keypoints",
+    "vsf_stereo_batch_dev", "vsf_set_lanes", "vsf_set_pipeline", "vsf_set_blur_overlap", "vsf_set_fast_resident", "vsf_get_fast_resident", "vsf_remove_ambig_stereo_batch_dev", "vsf_feature_matches_batch_dev", "vsf_bayer_bg_to_gray_batch_dev", "vsf_debug_level_image", "vsf_debug_fast_candidates", "vsf_debug_fast_work", "vsf_debug_level_keypoints",
     "vsf_algorithmic_bytes_per_image", "vsf_pyramid_pixels", "vsf_profile_enable", "vsf_profile_read",
     "vsf_stage_name", "vsf_debug_retain_best", "vsf_debug_sort_trim", "vsf_stereo_residuals_batch_dev", "vsf_stereo_thresholds_dev",
     "vsf_stereo_filter_batch_dev", "vsf_vision_features_batch_dev", "vsf_packed_outputs_capacity",
@@ -179,6 +179,7 @@ def lib() -> C.CDLL:
         L.vsf_imdecode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_debug_level_image.argtypes = [vp, i32, i32, i32, vp, sz]
         L.vsf_debug_fast_candidates.argtypes = [vp, i32, i32, vp, i32, ip]
+        L.vsf_debug_fast_work.argtypes = [vp, i32, i32, vp, i32, ip, ip, vp, i32]
         L.vsf_debug_level_keypoints.argtypes = [vp, i32, i32, vp, i32, ip]
         L.vsf_algorithmic_bytes_per_image.argtypes = [vp]
         L.vsf_algorithmic_bytes_per_image.restype = C.c_uint64

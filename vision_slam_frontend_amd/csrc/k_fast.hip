@@ -40,7 +40,8 @@ constexpr int SR = VSF_FAST_STRIP_ROWS;
 
 struct FastArgs {
   const VsfLevel* levels;
-  const uint32_t* units;
+  const uint32_t* units;  // full cells, then the packed items
+  int nwork_full;
   int nunits;  // cells (strip x band) per image: stride of the row-start tables
   const uint8_t* img0;
   size_t img0_stride;
@@ -200,46 +201,69 @@ __device__ __forceinline__ ScoreRow make_score_row(v2s s02, v2s s13) {
   return o;
 }
 
-// HALF = false: the wave is one unit (cell) of 248 keypoint columns x 32 rows.
-// HALF = true : the two 32-lane halves of the wave are two cells of the level's LAST, narrow band (<= 120 keypoint
-//               columns = 30 lanes + 2 halo lanes) in two consecutive strips; each half keeps its own candidate
-//               segment, row-start table and counter, so downstream nothing changes.  (The pyramid's 50 levels leave a
-//               narrow remainder band almost everywhere: 510 -> 446 waves per 640x480 image.)
+// PACK = false: the wave is one unit (cell) of up to 248 keypoint columns x 32 rows of one level.
+// PACK = true : the wave is a packed work item (vsf_internal.h): up to VSF_FAST_PACK_SEGS narrow cells of any levels
+//               side by side, each on ceil(cols / 4) + 2 consecutive lanes with halo lanes of its own, so that the DPP
+//               neighbours of a cell's columns are always the cell's own.  Level, row addresses, row range, masks and
+//               the cell's running count are per lane; each cell keeps its own candidate segment and row-start table,
+//               so downstream nothing changes.  (The pyramid's 50 levels end in a narrow band almost everywhere:
+//               packing them lowers the lanes a 640x480 image keeps busy by 14 %.)
 // NMS = false (standalone FAST without suppression only) keeps every corner and a zero response.
-// (`work`: index into a.units, wave-uniform -- the work item and everything derived from it: level, band, strip, row
-// addresses, is scalar)
-template <bool HALF, bool NMS>
+// (`work`: index into a.units (PACK = false) or into the packed items -- wave-uniform)
+template <bool PACK, bool NMS>
 __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int image) {
   const int lane = threadIdx.x & 63;
-  // (explicitly wave-uniform: in the resident kernels' cell loop these loads follow the previous cell's stores, so the
-  // compiler will not prove them invariant and use scalar loads; vector loads would make every row address, the buffer
-  // descriptor included, a per-lane value)
-  const uint32_t ud = uniform_copy(a.units + work);
-  const int level = (int)(ud >> 24), band = (int)((ud >> 16) & 0xFF), strip0 = (int)(ud & 0x7FFF);
-  const VsfLevel L = uniform_copy(a.levels + level);
-  const uint8_t* src;
-  int pitch;
-  if (level == 0) {
-    src = a.img0 + (size_t)image * a.img0_stride;
-    pitch = a.img0_pitch;
+  int level, band, strip, hl, nl, nrows0 = 0;
+  bool valid = true, mixed = false, rim = false;
+  VsfLevel L;
+  if constexpr (PACK) {
+    struct Item {
+      uint32_t w[VSF_FAST_PACK_WORDS];
+    };
+    const Item P = uniform_copy(reinterpret_cast<const Item*>(a.units + a.nwork_full) + work);
+    uint32_t w0 = P.w[4], w1 = P.w[5];  // the lane's cell: the last one whose first lane is <= lane
+#pragma unroll
+    for (int k = 1; k < VSF_FAST_PACK_SEGS; k++)
+      if (k < (int)P.w[0] && lane >= (int)(P.w[5 + 2 * k] & 0xFFu)) w0 = P.w[4 + 2 * k], w1 = P.w[5 + 2 * k];
+    nrows0 = (int)P.w[1];
+    mixed = P.w[2] != 0u;
+    rim = P.w[3] != 0u;
+    level = (int)(w0 >> 24), band = (int)((w0 >> 16) & 0xFF), strip = (int)(w0 & 0x7FFF);
+    hl = lane - (int)(w1 & 0xFFu);
+    nl = (int)((w1 >> 8) & 0xFFu);
+    valid = hl < nl;  // (lanes past the last cell carry nothing)
+    L = a.levels[level];
   } else {
-    src = a.pyr + (size_t)image * a.pyr_bytes + L.offset;
-    pitch = L.pitch;
+    // (explicitly wave-uniform: in the resident kernels' cell loop these loads follow the previous cell's stores, so the
+    // compiler will not prove them invariant and use scalar loads; vector loads would make every row address, the buffer
+    // descriptor included, a per-lane value)
+    const uint32_t ud = uniform_copy(a.units + work);
+    level = (int)(ud >> 24), band = (int)((ud >> 16) & 0xFF), strip = (int)(ud & 0x7FFF);
+    L = uniform_copy(a.levels + level);
+    hl = lane, nl = 64;
+  }
+  // source rows: level 0 is the input image, levels >= 1 sit in the pyramid block (a packed item never mixes the two)
+  const int pitch = level == 0 ? a.img0_pitch : L.pitch, hrow = L.h;
+  const uint8_t* src;
+  uint32_t src_bytes;
+  if constexpr (PACK) {
+    const bool lvl0 = __builtin_amdgcn_readfirstlane(level) == 0;
+    src = lvl0 ? a.img0 + (size_t)image * a.img0_stride : a.pyr + (size_t)image * a.pyr_bytes;
+    src_bytes = lvl0 ? (uint32_t)(a.img0_pitch * __builtin_amdgcn_readfirstlane(hrow)) : a.pyr_bytes;
+  } else {
+    src = level == 0 ? a.img0 + (size_t)image * a.img0_stride : a.pyr + (size_t)image * a.pyr_bytes + L.offset;
+    src_bytes = (uint32_t)(pitch * hrow);
   }
   const int t = a.threshold;
   // score offset (see score_from_circle): the emitter adds offs - 1 back
   const int offs = NMS ? max(t, 1) : t;
   const v2s toff = {(short)offs, (short)offs};
-  constexpr int HL = HALF ? 32 : 64;                        // lanes per cell
-  const int half = HALF ? (lane >> 5) : 0, hl = lane & (HL - 1);
-  const int strip = strip0 + half;
-  const bool valid = strip < L.nstrips;                     // (the second half of the last odd strip has no cell)
   const int bx0 = L.fast_a0 + VSF_FAST_BAND_COLS * band;
-  const int c0 = bx0 - 4 + 4 * hl;  // first column of this lane's 4 pixels (lane 1 starts the band)
-  const bool loadable = c0 >= 0 && c0 + 3 < pitch;
-  const int ys = L.y_lo + strip * SR;                       // per lane when HALF
-  const int nrows = valid ? min(SR, L.y_hi - ys) : 0;       // rows of this lane's cell
-  const int nrows0 = min(SR, L.y_hi - (L.y_lo + strip0 * SR));  // rows of the first cell (>= the second's): uniform
+  const int c0 = bx0 - 4 + 4 * hl;  // first column of this lane's 4 pixels (lane 1 of the cell starts the band)
+  const bool loadable = valid && c0 >= 0 && c0 + 3 < pitch;
+  const int ys = L.y_lo + strip * SR;
+  const int nrows = valid ? min(SR, L.y_hi - ys) : 0;  // rows of this lane's cell
+  if constexpr (!PACK) nrows0 = nrows;
   // Pixels that may carry a score: FAST's 3-pixel rim and one column beyond the keypoint rectangle (for the NMS).
   const int sx_lo = max(L.x_lo - 1, 3), sx_hi = min(L.x_hi + 1, L.w - 3);
   uint32_t sm02 = 0, sm13 = 0, em02 = 0, em13 = 0;  // per-pixel 16-bit masks in the pair layout: may be scored / emitted
@@ -247,9 +271,10 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
   for (int j = 0; j < 4; j++) {
     const int x = c0 + j;
     const uint32_t bit = 0xFFFFu << (16 * (j >> 1));
-    // lanes 1 .. HL-2 score and emit; lane 0 scores its last pixel only, lane HL-1 its first (the columns next to the band)
-    const bool sc_ok = ((hl >= 1 && hl <= HL - 2) || (hl == 0 && j == 3) || (hl == HL - 1 && j == 0)) && x >= sx_lo && x < sx_hi;
-    const bool em_ok = hl >= 1 && hl <= HL - 2 && x >= L.x_lo && x < L.x_hi && x < bx0 + VSF_FAST_BAND_COLS;
+    // lanes 1 .. nl-2 score and emit; lane 0 scores its last pixel only, lane nl-1 its first (the columns next to the band)
+    const bool sc_ok = valid && ((hl >= 1 && hl <= nl - 2) || (hl == 0 && j == 3) || (hl == nl - 1 && j == 0)) &&
+                       x >= sx_lo && x < sx_hi;
+    const bool em_ok = valid && hl >= 1 && hl <= nl - 2 && x >= L.x_lo && x < L.x_hi && x < bx0 + VSF_FAST_BAND_COLS;
     if (j & 1) {
       if (sc_ok) sm13 |= bit;
       if (em_ok) em13 |= bit;
@@ -258,41 +283,64 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
       if (em_ok) em02 |= bit;
     }
   }
-  if (!valid) sm02 = sm13 = em02 = em13 = 0;
-  const int unit_local = (valid ? strip : strip0) * L.nbands + band;
+  const int unit_local = strip * L.nbands + band;
   uint16_t* rs = a.rowstart + ((size_t)image * a.nunits + L.unit0 + unit_local) * VSF_FAST_RS_STRIDE;
-  const int seg_cap = L.seg_cap, hrow = L.h;
-  // Candidate stores go through a buffer descriptor over the cell's segment: an entry beyond the segment's capacity is
-  // dropped by the range check of the store itself (no compare, no 64-bit address arithmetic per store).  HALF: one
-  // descriptor from the first cell's segment to the end of the second's (L.nbands segments further), the second cell's
-  // lanes add that distance -- and check their capacity themselves, since a first-cell overflow would still be in range.
-  uint32_t* seg0 = a.cand + (size_t)image * a.cand_entries + L.cand_offset + (size_t)(strip0 * L.nbands + band) * L.seg_cap;
+  const int seg_cap = L.seg_cap;
+  // Candidate stores go through a buffer descriptor.  One cell: over the cell's segment, and an entry beyond its capacity
+  // is dropped by the range check of the store itself (no compare, no 64-bit address arithmetic per store).  PACK: over
+  // the image's candidate buffer, every lane adds its cell's segment offset and checks the capacity itself.
   const __amdgpu_buffer_rsrc_t seg_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(seg0, 0, (HALF ? L.nbands + 1 : 1) * seg_cap * 4, 0x00020000);
-  const uint32_t seg_off = (HALF && half && valid) ? (uint32_t)(L.nbands * seg_cap * 4) : 0u;
+      PACK ? __builtin_amdgcn_make_buffer_rsrc(a.cand + (size_t)image * a.cand_entries, 0, a.cand_entries * 4, 0x00020000)
+           : __builtin_amdgcn_make_buffer_rsrc(a.cand + (size_t)image * a.cand_entries + L.cand_offset +
+                                                   (size_t)unit_local * seg_cap,
+                                               0, seg_cap * 4, 0x00020000);
+  const uint32_t seg_off = PACK ? 4u * (L.cand_offset + (uint32_t)(unit_local * seg_cap)) : 0u;
+  // PACK: row starts are stored by the cell's first lane as the rows go (one descriptor over the image's tables)
+  const __amdgpu_buffer_rsrc_t rs_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      a.rowstart + (size_t)image * a.nunits * VSF_FAST_RS_STRIDE, 0, a.nunits * VSF_FAST_RS_STRIDE * 2, 0x00020000);
+  const uint32_t rs_off = 2u * (uint32_t)((L.unit0 + unit_local) * VSF_FAST_RS_STRIDE);
+  const bool rs_lane = PACK && valid && hl == 0;
+  // PACK: the lanes of the lane's own cell, and those from its first lane on (64-bit lane masks as two halves)
+  const int cfirst = lane - hl, cend = min(cfirst + nl, 64);
+  const unsigned long long from_m = ~0ull << cfirst, cell_m = from_m & (cend >= 64 ? ~0ull : (1ull << cend) - 1ull);
+  const uint32_t from_lo = (uint32_t)from_m, from_hi = (uint32_t)(from_m >> 32);
+  const uint32_t cell_lo = (uint32_t)cell_m, cell_hi = (uint32_t)(cell_m >> 32);
 
-  // buffer loads: a lane's column offset sits in a VGPR, the row offset in an SGPR (per lane when HALF); reads outside
-  // the level return 0
-  const __amdgpu_buffer_rsrc_t src_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, pitch * hrow, 0x00020000);
+  // buffer loads: a lane's column offset sits in a VGPR, the row offset in an SGPR (PACK: both per lane, the row clamp
+  // folded into the range of q); reads outside the level return 0
+  const __amdgpu_buffer_rsrc_t src_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, src_bytes, 0x00020000);
   // (a lane outside the row gets an offset beyond the buffer instead of a branch around the load: no divergent control
   // flow, so the row offset stays in an SGPR)
   const uint32_t col_off = loadable ? (uint32_t)c0 : 0xFFFFFFF0u;
+  const int qlo = 1 - ys, qhi = hrow - ys;  // 0 <= ys - 1 + q <= hrow - 1
+  const uint32_t rbase = loadable ? (level == 0 ? 0u : L.offset) + (uint32_t)(c0 + (ys - 1) * pitch) : 0x40000000u;
   auto load_row = [&](int q) -> uint32_t {  // row ys - 1 + q of this lane's cell
+    if (PACK)
+      return __builtin_amdgcn_raw_buffer_load_b32(src_rsrc, rbase + (uint32_t)__mul24(min(max(q, qlo), qhi), pitch), 0u,
+                                                  0);  // (full-rate multiply)
     const int yc = min(max(ys - 1 + q, 0), hrow - 1);
-    if (HALF)
-      return __builtin_amdgcn_raw_buffer_load_b32(
-          src_rsrc, loadable ? __umul24((uint32_t)yc, (uint32_t)pitch) + (uint32_t)c0 : 0xFFFFFFF0u, 0u, 0);  // (full-rate multiply)
     return __builtin_amdgcn_raw_buffer_load_b32(src_rsrc, col_off, (uint32_t)(yc * pitch), 0);
   };
 
   const unsigned long long scorable = __builtin_amdgcn_ballot_w64((sm02 | sm13) != 0u);
   const v2s zero2 = {0, 0};
   ScoreRow S0 = make_score_row(zero2, zero2), S1 = S0, S2 = S0;  // score rows rotate through three sets: q-2, q-1, q
-  int count_lo = 0, count_hi = 0;  // candidates emitted so far by the cell(s) (wave-uniform)
-  uint32_t my_rs = 0;              // lane hl keeps rowstart[hl] of its cell
+  int count = 0;       // candidates emitted so far by the cell (wave-uniform unless PACK)
+  uint32_t my_rs = 0;  // (one cell) lane hl keeps rowstart[hl] of the cell
   // (cell row, first column, score offset) of an emitted candidate: score << 24 | y << 12 | x
   const uint32_t yx0 = ((uint32_t)ys << 12) + (uint32_t)c0 + ((uint32_t)(NMS ? offs - 1 : 0) << 24);
+  // rank among the cell's lanes: v_mbcnt counts the set bits below this lane (two instructions per ballot, chained through
+  // the accumulator); PACK counts those of the lane's own cell only, and adds the cell's bits to its count
+  auto below = [&](unsigned long long b, int acc) -> int {
+    if (PACK)
+      return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32) & from_hi,
+                                            __builtin_amdgcn_mbcnt_lo((uint32_t)b & from_lo, (uint32_t)acc));
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, (uint32_t)acc));
+  };
+  auto in_cell = [&](unsigned long long b) -> int {
+    if (PACK) return __popc((uint32_t)b & cell_lo) + __popc((uint32_t)(b >> 32) & cell_hi);
+    return __popcll(b);
+  };
 
   // One step: scores of cell row q - 1 (image row ys - 1 + q) from the window R0..R6 = image rows ys - 4 + q .. ys + 2 + q,
   // then NMS + emission of cell row q - 2.
@@ -301,17 +349,26 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
     prep_row(R6);  // the row that has just entered the window
     v2s s02 = zero2, s13 = zero2;
     const int sy = ys - 1 + q;
-    const bool row_ok = sy >= 3 && sy < hrow - 3;  // (wave-uniform unless HALF)
+    const bool row_ok = sy >= 3 && sy < hrow - 3;  // (wave-uniform unless PACK; PACK tests it only where a cell needs it)
     // a 9-arc contains circle pixel 0 (row sy+3) or 8 (row sy-3), both in the centre pixel's column
     const uint32_t far = max(__builtin_amdgcn_sad_u8(R0.d, R3.d, 0u), __builtin_amdgcn_sad_u8(R6.d, R3.d, 0u));
-    // (one v_cmp; the lanes that may score at all are a ballot taken once, the row test is scalar unless HALF)
-    const unsigned long long want = __builtin_amdgcn_ballot_w64(far > (uint32_t)t) & scorable &
-                                    (HALF ? __builtin_amdgcn_ballot_w64(row_ok) : (row_ok ? ~0ull : 0ull));
+    // (one v_cmp; the lanes that may score at all are a ballot taken once, the row test is scalar unless PACK)
+    unsigned long long want = __builtin_amdgcn_ballot_w64(far > (uint32_t)t) & scorable;
+    if (PACK) {
+      if (rim) want &= __builtin_amdgcn_ballot_w64(row_ok);
+    } else {
+      want &= row_ok ? ~0ull : 0ull;
+    }
     if (want != 0ull) {
       s02 = score_pair0<NMS>(R0, R1, R2, R3, R4, R5, R6, toff);  // pixels 0 and 2
       s13 = score_pair1<NMS>(R0, R1, R2, R3, R4, R5, R6, toff);  // pixels 1 and 3
-      s02 = as_v2s(as_u32(s02) & ((!HALF || row_ok) ? sm02 : 0u));
-      s13 = as_v2s(as_u32(s13) & ((!HALF || row_ok) ? sm13 : 0u));
+      if (PACK && rim) {
+        s02 = as_v2s(as_u32(s02) & (row_ok ? sm02 : 0u));
+        s13 = as_v2s(as_u32(s13) & (row_ok ? sm13 : 0u));
+      } else {
+        s02 = as_v2s(as_u32(s02) & sm02);
+        s13 = as_v2s(as_u32(s13) & sm13);
+      }
     }
     S_dn = make_score_row(s02, s13);
     const int r = q - 2;  // cell row to emit
@@ -328,12 +385,7 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
           k02 = as_u32(S_mid.s02) & em02;
           k13 = as_u32(S_mid.s13) & em13;
         }
-        if (HALF && r >= nrows) k02 = k13 = 0;  // (the second cell may have fewer rows)
-        // rank among the cell's lanes: v_mbcnt counts the set bits below this lane (two instructions per ballot, chained
-        // through the accumulator); the upper cell of a half-wave pair subtracts the lower cell's bits (scalar)
-        auto below = [](unsigned long long b, int acc) -> int {
-          return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, (uint32_t)acc));
-        };
+        if (PACK && mixed && r >= nrows) k02 = k13 = 0;  // (a cell of the item may have fewer rows)
         const uint32_t yx = yx0 + ((uint32_t)r << 12);
         if (NMS) {
           // Strict NMS: two neighbouring pixels cannot both survive, so at most one of pixels 0 / 1 and at most one of
@@ -343,63 +395,50 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
           const bool hasA = (kk & 0xFFFFu) != 0u, hasB = (kk >> 16) != 0u;
           const unsigned long long bA = __ballot(hasA), bB = __ballot(hasB);
           if ((bA | bB) != 0ull) {  // wave-uniform
-            int pos = below(bB, below(bA, half ? count_hi : count_lo));
-            if (HALF) pos -= half ? __popc((uint32_t)bA) + __popc((uint32_t)bB) : 0;
+            const int pos = below(bB, below(bA, count));
             // entry = (score + offs - 1) << 24 | y << 12 | x;  x = c0 + (0 or 1) for slot A, c0 + 2 + (0 or 1) for slot B
             const uint32_t eA = (kk << 24) + yx + ((k13 & 0xFFFFu) != 0u ? 1u : 0u);
             const uint32_t eB = ((kk & 0xFFFF0000u) << 8) + yx + 2u + ((k13 >> 16) != 0u ? 1u : 0u);
             const int posB = pos + (hasA ? 1 : 0);
-            if (hasA && (!HALF || pos < seg_cap)) __builtin_amdgcn_raw_buffer_store_b32(eA, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
-            if (hasB && (!HALF || posB < seg_cap)) __builtin_amdgcn_raw_buffer_store_b32(eB, seg_rsrc, seg_off + 4u * (uint32_t)posB, 0, 0);
-            if (HALF) {
-              count_lo += __popc((uint32_t)bA) + __popc((uint32_t)bB);
-              count_hi += __popc((uint32_t)(bA >> 32)) + __popc((uint32_t)(bB >> 32));
-            } else {
-              count_lo += __popcll(bA) + __popcll(bB);
-            }
+            if (hasA && (!PACK || pos < seg_cap)) __builtin_amdgcn_raw_buffer_store_b32(eA, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
+            if (hasB && (!PACK || posB < seg_cap)) __builtin_amdgcn_raw_buffer_store_b32(eB, seg_rsrc, seg_off + 4u * (uint32_t)posB, 0, 0);
+            count += in_cell(bA) + in_cell(bB);
           }
         } else {
           const bool k0 = (k02 & 0xFFFFu) != 0, k1 = (k13 & 0xFFFFu) != 0, k2 = (k02 >> 16) != 0, k3 = (k13 >> 16) != 0;
           const unsigned long long b0 = __ballot(k0), b1 = __ballot(k1), b2 = __ballot(k2), b3 = __ballot(k3);
           if ((b0 | b1 | b2 | b3) != 0ull) {  // wave-uniform
-            int pos = below(b3, below(b2, below(b1, below(b0, half ? count_hi : count_lo))));
-            if (HALF) {
-              const int lower = __popc((uint32_t)b0) + __popc((uint32_t)b1) + __popc((uint32_t)b2) + __popc((uint32_t)b3);
-              pos -= half ? lower : 0;
-            }
+            int pos = below(b3, below(b2, below(b1, below(b0, count))));
             // (without NMS cv::FAST_t leaves the response at 0)
             if (k0) {
-              if (!HALF || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
+              if (!PACK || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
               ++pos;
             }
             if (k1) {
-              if (!HALF || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx + 1, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
+              if (!PACK || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx + 1, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
               ++pos;
             }
             if (k2) {
-              if (!HALF || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx + 2, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
+              if (!PACK || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx + 2, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
               ++pos;
             }
             if (k3) {
-              if (!HALF || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx + 3, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
+              if (!PACK || pos < seg_cap) __builtin_amdgcn_raw_buffer_store_b32(yx + 3, seg_rsrc, seg_off + 4u * (uint32_t)pos, 0, 0);
             }
-            if (HALF) {
-              count_lo += __popcll(b0 & 0xFFFFFFFFull) + __popcll(b1 & 0xFFFFFFFFull) + __popcll(b2 & 0xFFFFFFFFull) +
-                          __popcll(b3 & 0xFFFFFFFFull);
-              count_hi += __popcll(b0 >> 32) + __popcll(b1 >> 32) + __popcll(b2 >> 32) + __popcll(b3 >> 32);
-            } else {
-              count_lo += __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
-            }
+            count += in_cell(b0) + in_cell(b1) + in_cell(b2) + in_cell(b3);
           }
         }
       }
-      // rowstart[r + 1] of the cell(s): the running count goes into lane r + 1 of the cell (v_writelane: one instruction;
-      // lane 0 keeps rowstart[0] = 0, rowstart[SR] is written from the final count)
+      // rowstart[r + 1] of the cell (rowstart[0] = 0 and rowstart[SR], the cell's total, are written after the march)
       if (r + 1 < SR) {
-        // (lane select through M0: the value already takes the instruction's one constant-bus slot)
-        asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(my_rs) : "s"(min(count_lo, seg_cap)), "s"(r + 1));
-        if (HALF)
-          asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(my_rs) : "s"(min(count_hi, seg_cap)), "s"(32 + r + 1));
+        if (PACK) {
+          if (rs_lane)
+            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)min(count, seg_cap), rs_rsrc, rs_off, 2u * (uint32_t)(r + 1), 0);
+        } else {
+          // the running count goes into lane r + 1 (v_writelane: one instruction; lane select through M0: the value
+          // already takes the instruction's one constant-bus slot)
+          asm("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %1, m0" : "+v"(my_rs) : "s"(min(count, seg_cap)), "s"(r + 1));
+        }
       }
     }
   };
@@ -430,29 +469,34 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
     VSF_FAST_STEP(8, A8, A0, A1, A2, A3, A4, A5, A7, S2, S0, S1)
   }
 #undef VSF_FAST_STEP
-  if (valid) {
-    if (hl < SR) rs[hl] = (uint16_t)my_rs;                                          // rowstart[0 .. SR-1]
-    if (hl == 0) rs[SR] = (uint16_t)min(half ? count_hi : count_lo, seg_cap);       // rowstart[SR] = cell total
+  if (PACK) {
+    if (rs_lane) {
+      rs[0] = 0;
+      rs[SR] = (uint16_t)min(count, seg_cap);
+    }
+  } else {
+    if (hl < SR) rs[hl] = (uint16_t)my_rs;                 // rowstart[0 .. SR-1]
+    if (hl == 0) rs[SR] = (uint16_t)min(count, seg_cap);   // rowstart[SR] = cell total
   }
 }
 
-template <bool HALF, bool NMS>
-__global__ __launch_bounds__(256) void fast_march_kernel(FastArgs a, int work0, int nwork) {
+template <bool PACK, bool NMS>
+__global__ __launch_bounds__(256) void fast_march_kernel(FastArgs a, int nwork) {
   const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (item >= nwork) return;  // wave-uniform
-  fast_march_body<HALF, NMS>(a, work0 + item, blockIdx.y);
+  fast_march_body<PACK, NMS>(a, item, blockIdx.y);
 }
 
-// Full cells and the half-wave cells of the narrow last bands in ONE launch, for batches that leave the chip nearly
-// empty: there a launch lasts as long as one cell's march, and two launches in a row last twice that.
+// Full cells and the packed items in ONE launch, for batches that leave the chip nearly empty: there a launch lasts as
+// long as one cell's march, and two launches in a row last twice that.
 template <bool NMS>
-__global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int nfull, int nhalf) {
+__global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int nfull, int npack) {
   const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (item >= nfull + nhalf) return;  // wave-uniform
+  if (item >= nfull + npack) return;  // wave-uniform
   if (item < nfull)
     fast_march_body<false, NMS>(a, item, blockIdx.y);
   else
-    fast_march_body<true, NMS>(a, item, blockIdx.y);
+    fast_march_body<true, NMS>(a, item - nfull, blockIdx.y);
 }
 
 // The same cells walked by ONE resident workgroup per CU (4 x `waves per SIMD` waves; a second one does not fit beside it, so
@@ -461,9 +505,8 @@ __global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int nf
 // long as cells are left and whatever else is queued waits behind it; a fixed set of resident waves leaves the rest of each
 // SIMD's registers to the kernel beside it.  Alone, FAST reaches 93 % of the vector ALU's issue rate with five waves per
 // SIMD, the same with four, 92 % of that with three and 76 % with two (occupancy sweep, NOTES.md section 6).
-template <bool HALF, bool NMS>
-__global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, int work0, int nwork, int nimages,
-                                                                  uint32_t* next_cell) {
+template <bool PACK, bool NMS>
+__global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, int nwork, int nimages, uint32_t* next_cell) {
   // cells are handed out through a counter (zeroed by the launcher): a wave slowed down by its neighbours takes fewer
   const int total = nwork * nimages;
   while (true) {  // (wave-uniform; the counter passes `total` for every wave)
@@ -482,7 +525,7 @@ __global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, i
     const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
     if (u >= (uint32_t)total) break;
     const int image = (int)u / nwork, cell = (int)u - image * nwork;
-    fast_march_body<HALF, NMS>(a, work0 + cell, image);
+    fast_march_body<PACK, NMS>(a, cell, image);
   }
 }
 
@@ -526,6 +569,7 @@ void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int
   FastArgs a;
   a.levels = d.levels;
   a.units = d.units;
+  a.nwork_full = g.nwork_full;
   a.nunits = g.nunits;
   a.img0 = im.base;
   a.img0_stride = im.image_stride;
@@ -541,31 +585,29 @@ void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int
     vsf_note(hipMemsetAsync(d_cell_counters, 0, 2 * sizeof(uint32_t), s));
     const dim3 block(256 * resident_waves_per_simd);
     if (g.nwork_full > 0)
-      hipLaunchKernelGGL((fast_march_resident_kernel<false, true>), dim3(n_cus), block, 0, s, a, 0, g.nwork_full, im.n,
+      hipLaunchKernelGGL((fast_march_resident_kernel<false, true>), dim3(n_cus), block, 0, s, a, g.nwork_full, im.n,
                          d_cell_counters);
-    if (g.nwork_half > 0)
-      hipLaunchKernelGGL((fast_march_resident_kernel<true, true>), dim3(n_cus), block, 0, s, a, g.nwork_full,
-                         g.nwork_half, im.n, d_cell_counters + 1);
+    if (g.nwork_pack > 0)
+      hipLaunchKernelGGL((fast_march_resident_kernel<true, true>), dim3(n_cus), block, 0, s, a, g.nwork_pack, im.n,
+                         d_cell_counters + 1);
     return;
   }
-  const dim3 gf((g.nwork_full + 3) / 4, im.n), gh((g.nwork_half + 3) / 4, im.n);
+  const dim3 gf((g.nwork_full + 3) / 4, im.n), gp((g.nwork_pack + 3) / 4, im.n);
   const int both_max = d.tune ? d.tune->fast_both_max : 16;
-  if (im.n <= both_max && g.nwork_full > 0 && g.nwork_half > 0) {
-    const dim3 gb((g.nwork_full + g.nwork_half + 3) / 4, im.n);
+  if (im.n <= both_max && g.nwork_full > 0 && g.nwork_pack > 0) {
+    const dim3 gb((g.nwork_full + g.nwork_pack + 3) / 4, im.n);
     if (nms)
-      hipLaunchKernelGGL((fast_march_both_kernel<true>), gb, dim3(256), 0, s, a, g.nwork_full, g.nwork_half);
+      hipLaunchKernelGGL((fast_march_both_kernel<true>), gb, dim3(256), 0, s, a, g.nwork_full, g.nwork_pack);
     else
-      hipLaunchKernelGGL((fast_march_both_kernel<false>), gb, dim3(256), 0, s, a, g.nwork_full, g.nwork_half);
+      hipLaunchKernelGGL((fast_march_both_kernel<false>), gb, dim3(256), 0, s, a, g.nwork_full, g.nwork_pack);
     return;
   }
   if (nms) {
-    if (g.nwork_full > 0) hipLaunchKernelGGL((fast_march_kernel<false, true>), gf, dim3(256), 0, s, a, 0, g.nwork_full);
-    if (g.nwork_half > 0)
-      hipLaunchKernelGGL((fast_march_kernel<true, true>), gh, dim3(256), 0, s, a, g.nwork_full, g.nwork_half);
+    if (g.nwork_full > 0) hipLaunchKernelGGL((fast_march_kernel<false, true>), gf, dim3(256), 0, s, a, g.nwork_full);
+    if (g.nwork_pack > 0) hipLaunchKernelGGL((fast_march_kernel<true, true>), gp, dim3(256), 0, s, a, g.nwork_pack);
   } else {
-    if (g.nwork_full > 0) hipLaunchKernelGGL((fast_march_kernel<false, false>), gf, dim3(256), 0, s, a, 0, g.nwork_full);
-    if (g.nwork_half > 0)
-      hipLaunchKernelGGL((fast_march_kernel<true, false>), gh, dim3(256), 0, s, a, g.nwork_full, g.nwork_half);
+    if (g.nwork_full > 0) hipLaunchKernelGGL((fast_march_kernel<false, false>), gf, dim3(256), 0, s, a, g.nwork_full);
+    if (g.nwork_pack > 0) hipLaunchKernelGGL((fast_march_kernel<true, false>), gp, dim3(256), 0, s, a, g.nwork_pack);
   }
 }
 

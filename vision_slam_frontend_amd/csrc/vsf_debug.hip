@@ -210,6 +210,28 @@ vsf_status vsf_debug_fast_candidates(vsf_ctx* ctx, int image, int level, vsf_key
   return VSF_OK;
 }
 
+vsf_status vsf_debug_fast_work(const vsf_params* p, int orb, int nms, uint32_t* words, int cap, int* n_words, int* n_full,
+                               int32_t* levels_out, int level_cap) {
+  if (!p || !n_words || !n_full || cap < 0 || level_cap < 0 || (cap > 0 && !words) || (level_cap > 0 && !levels_out))
+    return VSF_ERR_INVALID_ARG;
+  if (p->nlevels < 1 || p->nlevels > VSF_MAX_LEVELS || p->width < 16 || p->height < 16 || !(p->scale_factor > 1.0f) ||
+      p->edge_threshold < 0 || p->first_level != 0)
+    return VSF_ERR_INVALID_ARG;
+  Geometry G;
+  if (!build_geometry(*p, orb != 0, nms != 0, &G)) return VSF_ERR_INVALID_ARG;
+  const int n = G.g.nwork_full + G.g.nwork_pack * VSF_FAST_PACK_WORDS;
+  *n_words = n;
+  *n_full = G.g.nwork_full;
+  for (int l = 0; l < (int)G.levels.size() && l < level_cap; l++) {
+    const VsfLevel& L = G.levels[l];
+    const int32_t v[10] = {L.w, L.h, L.x_lo, L.x_hi, L.y_lo, L.y_hi, L.fast_a0, L.nbands, L.nstrips, L.unit0};
+    memcpy(levels_out + 10 * l, v, sizeof(v));
+  }
+  if (n > cap) return VSF_ERR_CAPACITY;
+  if (n > 0) memcpy(words, G.units.data(), (size_t)n * sizeof(uint32_t));
+  return VSF_OK;
+}
+
 vsf_status vsf_debug_level_keypoints(vsf_ctx* ctx, int image, int level, vsf_keypoint* kp_out, int cap, int* n_out) {
   VsfErrorScope scope_(ctx);
   if (!ctx || !n_out || !ctx->last_valid || image < 0 || image >= ctx->last_images.n || level < 0 ||

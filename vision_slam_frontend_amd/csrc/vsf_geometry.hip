@@ -215,7 +215,10 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
   // FAST units: (240-column band) x (32-row strip) of the keypoint rectangle, one wave each (k_fast.hip)
   uint32_t cand = 0;
   int kp_off = 0, ncells = 0;
-  std::vector<uint32_t> half_items;
+  struct Narrow {
+    int rows, lanes, level, band, strip;
+  };
+  std::vector<Narrow> narrow;  // cells narrower than a wave: packed below
   for (int l = 0; l < nlevels; l++) {
     VsfLevel& L = G.levels[l];
     const int vw = L.x_hi - L.x_lo, vh = L.y_hi - L.y_lo;
@@ -225,17 +228,16 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
     if (L.nbands > 255 || L.nstrips > 32767) return false;
     L.unit0 = ncells;
     ncells += L.nstrips * L.nbands;
-    // work items: one wave per cell, except that a narrow last band is walked two strips per wave (k_fast.hip)
-    const int last_w = L.nbands > 0 ? L.x_hi - (L.fast_a0 + VSF_FAST_BAND_COLS * (L.nbands - 1)) : 0;
-    const bool half_last = L.nbands > 0 && L.nstrips >= 2 && last_w <= VSF_FAST_HALF_COLS;
+    // work items: a full-width cell is one wave; a narrower one (ceil(cols / 4) + 2 lanes) is packed with others
     for (int s = 0; s < L.nstrips; s++)
       for (int b = 0; b < L.nbands; b++) {
-        const uint32_t item = ((uint32_t)l << 24) | ((uint32_t)b << 16) | (uint32_t)s;
-        if (half_last && b == L.nbands - 1) {
-          if ((s & 1) == 0) half_items.push_back(item);
-        } else {
-          G.units.push_back(item);
-        }
+        const int bx0 = L.fast_a0 + VSF_FAST_BAND_COLS * b;
+        const int lanes = (std::min(L.x_hi, bx0 + VSF_FAST_BAND_COLS) - bx0 + 3) / 4 + 2;
+        const int rows = std::min(VSF_FAST_STRIP_ROWS, L.y_hi - (L.y_lo + VSF_FAST_STRIP_ROWS * s));
+        if (lanes < 64)
+          narrow.push_back(Narrow{rows, lanes, l, b, s});
+        else
+          G.units.push_back(((uint32_t)l << 24) | ((uint32_t)b << 16) | (uint32_t)s);
       }
     // Strict 8-neighbour NMS leaves at most one keypoint per 2x2 block, so a segment of that size cannot overflow.
     const int bw = std::min(VSF_FAST_BAND_COLS, std::max(vw, 1)), bh = std::min(VSF_FAST_STRIP_ROWS, std::max(vh, 1));
@@ -249,9 +251,61 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
   }
   G.g.cand_entries = std::max(cand, 1u);
   G.g.nunits = ncells;
+  // Narrow cells into waves: deterministic first fit, tallest and widest first, so that cells of equal row count share a
+  // wave.  A wave reads one image buffer (level 0 is the input image, levels >= 1 the pyramid), so those never mix.  A cell
+  // left alone in its wave stays a one-cell item (the full form, which needs no per-lane bookkeeping).
+  std::stable_sort(narrow.begin(), narrow.end(), [](const Narrow& a, const Narrow& b) {
+    if (a.rows != b.rows) return a.rows > b.rows;
+    if (a.lanes != b.lanes) return a.lanes > b.lanes;
+    if (a.level != b.level) return a.level < b.level;
+    if (a.strip != b.strip) return a.strip < b.strip;
+    return a.band < b.band;
+  });
+  struct Bin {
+    int lanes;
+    std::vector<int> cells;
+  };
+  std::vector<Bin> bins;
+  for (int i = 0; i < (int)narrow.size(); i++) {
+    const Narrow& c = narrow[i];
+    size_t k = 0;
+    for (; k < bins.size(); k++) {
+      const Bin& B = bins[k];
+      if (B.lanes + c.lanes <= 64 && (int)B.cells.size() < VSF_FAST_PACK_SEGS &&
+          (narrow[B.cells[0]].level == 0) == (c.level == 0))
+        break;
+    }
+    if (k == bins.size()) bins.push_back(Bin{0, {}});
+    bins[k].lanes += c.lanes;
+    bins[k].cells.push_back(i);
+  }
+  std::vector<uint32_t> packs;
+  for (const Bin& B : bins) {
+    const Narrow& c0 = narrow[B.cells[0]];
+    if (B.cells.size() == 1) {
+      G.units.push_back(((uint32_t)c0.level << 24) | ((uint32_t)c0.band << 16) | (uint32_t)c0.strip);
+      continue;
+    }
+    uint32_t w[VSF_FAST_PACK_WORDS] = {0};
+    int first = 0, mixed = 0, rim = 0;
+    w[0] = (uint32_t)B.cells.size();
+    w[1] = (uint32_t)c0.rows;  // (sorted: the first cell is the tallest)
+    for (size_t j = 0; j < B.cells.size(); j++) {
+      const Narrow& c = narrow[B.cells[j]];
+      const VsfLevel& L = G.levels[c.level];
+      mixed |= c.rows != c0.rows;
+      rim |= L.y_lo - 1 < 3 || L.y_hi >= L.h - 3;  // score rows y_lo - 1 .. y_hi
+      w[4 + 2 * j] = ((uint32_t)c.level << 24) | ((uint32_t)c.band << 16) | (uint32_t)c.strip;
+      w[5 + 2 * j] = (uint32_t)first | ((uint32_t)c.lanes << 8) | ((uint32_t)c.rows << 16);
+      first += c.lanes;
+    }
+    w[2] = (uint32_t)mixed;
+    w[3] = (uint32_t)rim;
+    packs.insert(packs.end(), w, w + VSF_FAST_PACK_WORDS);
+  }
   G.g.nwork_full = (int)G.units.size();
-  G.g.nwork_half = (int)half_items.size();
-  G.units.insert(G.units.end(), half_items.begin(), half_items.end());
+  G.g.nwork_pack = (int)(packs.size() / VSF_FAST_PACK_WORDS);
+  G.units.insert(G.units.end(), packs.begin(), packs.end());
   if (G.units.empty()) G.units.push_back(0);
   G.g.lvlkp_entries = std::max(kp_off, 1);
   // resize coefficient tables (host only: the kernel evaluates the same arithmetic in place; built here to check

@@ -14,7 +14,13 @@
 // the lane's own dword and its inner neighbour's -- which is all the NMS of the band's edge columns needs) x a strip of 32
 // rows.  (Rounds 1-3: 240 columns, lanes 1 and 62 scored four pixels each for the sake of one.)
 #define VSF_FAST_BAND_COLS 248
-#define VSF_FAST_HALF_COLS 120   // a last band of at most this many columns is walked two strips per wave (30 lanes x 4)
+// Cells narrower than a band (a level's last band) share waves: a packed work item is a list of up to VSF_FAST_PACK_SEGS
+// segments, each one cell on ceil(cols / 4) + 2 consecutive lanes (its own two halo lanes included).  Item layout
+// (VSF_FAST_PACK_WORDS dwords): nseg, rows (the wave's row count: its tallest cell's), mixed (1: a cell has fewer rows),
+// rim (1: a cell's score rows reach FAST's 3-pixel rim, so the row test is per lane), then per segment
+// level << 24 | band << 16 | strip and first lane | lanes << 8 | rows << 16.
+#define VSF_FAST_PACK_SEGS 8
+#define VSF_FAST_PACK_WORDS (4 + 2 * VSF_FAST_PACK_SEGS)
 #define VSF_FAST_STRIP_ROWS 32
 #define VSF_FAST_RS_STRIDE (VSF_FAST_STRIP_ROWS + 2)  // u16 row-start table per unit (SR + 1 used)
 #define VSF_BLUR_MMA_ROWS 26     // output rows per step of the matrix-core blur (32 loaded rows - 2 x 3 halo rows)
@@ -80,7 +86,7 @@ struct VsfGeom {
   uint32_t pyr_bytes;       // one image's pyramid block
   uint32_t cand_entries;    // one image's candidate buffer (u32 entries)
   int nunits;               // FAST cells (32-row strip x 240-column band) per image
-  int nwork_full, nwork_half;  // FAST work items: waves covering one cell / two cells of a narrow last band
+  int nwork_full, nwork_pack;  // FAST work items: waves covering one cell / packed items of narrow cells
   int lvlkp_entries;        // one image's level-keypoint buffer (VsfLevelKp entries)
   uint64_t pyramid_pixels;
 };
@@ -88,7 +94,7 @@ struct VsfGeom {
 // Per-context launch choices (vsf_set_option / vsf_get_option; the defaults are what the measurements of NOTES.md
 // section 6 settled on).  Nothing in the library reads the environment: a switch is a call on a context.
 struct VsfTuning {
-  int fast_both_max = 16;  // VSF_OPT_FAST_BOTH_MAX: largest batch (images) whose full and half-wave FAST cells share one launch
+  int fast_both_max = 16;  // VSF_OPT_FAST_BOTH_MAX: largest batch (images) whose full and packed FAST work items share one launch
   int select_wide = 1;     // VSF_OPT_SELECT_WIDE: 1 = a frame or two takes the 1024-thread whole-level selection class
   int pipe_priority = 0;     // VSF_OPT_PIPE_PRIORITY: stream priority of the pipelined pyramid chain (0 normal, 1 lowest, -1 highest)
   int pipe_after_fast = 1;   // VSF_OPT_PIPE_AFTER_FAST: the pipelined pyramid of call k + 1 starts behind call k's FAST (1) or at once (0)
@@ -145,7 +151,7 @@ hipError_t vsf_prepare_jpeg_kernels(int lds_limit);
 // Kernel launchers (implemented in the k_*.hip files). All asynchronous on `s`.
 struct VsfDev {
   const VsfLevel* levels;   // [nlevels]
-  const uint32_t* units;    // [nwork_full + nwork_half]: level << 24 | band << 16 | (first) strip
+  const uint32_t* units;    // [nwork_full]: level << 24 | band << 16 | strip, then [nwork_pack][VSF_FAST_PACK_WORDS]
   uint8_t* pyr;             // [max_images][pyr_bytes]   unblurred levels 1..L-1 (level 0 is the input)
   uint8_t* blur;            // [max_images][pyr_bytes]   blurred levels 0..L-1
   uint32_t* cand;           // [max_images][cand_entries]  per-unit candidate segments (unit-local raster order)
