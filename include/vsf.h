@@ -389,7 +389,9 @@ vsf_status vsf_pack_outputs_dev(vsf_ctx* ctx, const vsf_vision_feature* d_featur
  * Result (little endian, *out_bytes bytes, at most vsf_observe_capacity()):
  *   u32 magic 'VSFO', n_pairs, nfeat, total_bytes, n_left, n_right (raw keypoints), n_stereo_matches, n_points,
  *   f32 mean residual, threshold applied, threshold in force afterwards, u32 result overflow, u32 extraction overflow
- *   (either makes the collect return VSF_ERR_CAPACITY -- for THIS frame only), 3 x u32 reserved              (64 bytes)
+ *   (either makes the collect return VSF_ERR_CAPACITY -- for THIS frame only), u32 decoder status (word 13; compressed
+ *   frames: bit 0 the LEFT, bit 1 the RIGHT file was refused on the device -- the collect returns VSF_ERR_INVALID_ARG for
+ *   THIS frame only; always 0 for raw frames), 2 x u32 reserved (the debug images' words)                   (64 bytes)
  *   u32 npairs[n_pairs], padded to a multiple of 4 words
  *   vsf_vision_feature x nfeat
  *   vsf_feature_match x npairs[p], p = 0 .. n_pairs-1: the temporal factors, oldest kept frame first (the order of
@@ -412,13 +414,49 @@ vsf_status vsf_observe_collect(vsf_ctx* ctx, int64_t ticket, uint8_t* out, size_
 /* The same without the copy: *out points at the result inside the context's pinned result ring; it stays valid until `depth`
  * further frames have been submitted (the first word, the magic, reads 0 there). */
 vsf_status vsf_observe_collect_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** out, size_t* out_bytes);
+/* The same frames as sensor_msgs::CompressedImage payloads (the reference's caller, slam_frontend_main.cc:98-133: cv::imdecode
+ * IMREAD_GRAYSCALE, then for bayer_rggb8 topics COLOR_BayerBG2BGR + COLOR_BGR2GRAY): baseline / progressive JPEG or PNG of the
+ * context's size, left and right told apart by their first bytes, each whatever it is.  The submit does the decoders' host
+ * half for the two files (every marker, table and chunk length checked: what vsf_imdecode_gray_batch refuses is refused here
+ * with the same status) and copies them into a pinned ring of depth x 2 slots of `cap` bytes (vsf_observe_set_compressed_cap;
+ * a larger file: VSF_ERR_CAPACITY).  A refused submit issues no ticket and leaves the queue as it was.  When the batch
+ * leaves, its files go up in ONE copy command, are decoded on the queue's copy stream (beside the previous batch's
+ * extraction and tail) into the batch's image buffer, demosaiced there when `bayer` is set, and the batched extraction and
+ * tail run as for raw frames: results equal those of vsf_observe_submit on the decoded images, byte for byte.  A batch may
+ * mix formats and raw frames; frames with different `bayer` never share one.
+ * DEFINED DEVIATION -- a file the DEVICE refuses (PNG data libpng answers with png_error, a JPEG stream that broke off at a
+ * missing restart marker; what sets bit 1 of vsf_sync's status after the batched decoders): a frame is never taken out of
+ * the queue once it has a ticket, so that image is replaced by an ALL-ZERO image before extraction (no corners: a node
+ * without features; the threshold chain takes the NaN of a frame without stereo matches, as the reference's does), result
+ * header word 13 says which file it was and THAT ticket's collect returns VSF_ERR_INVALID_ARG; every other frame is what it
+ * would be had the refused image been submitted raw as zeros.  (The reference hands ObserveImage whatever cv::imdecode
+ * returned: an empty Mat.)  No call of the queue waits for the GPU that does not wait for raw frames. */
+vsf_status vsf_observe_submit_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                         size_t right_bytes, int bayer, const vsf_calibration* calib, float best_percent,
+                                         int frame_life, int64_t* ticket);
+vsf_status vsf_observe_stereo_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                         size_t right_bytes, int bayer, const vsf_calibration* calib, float best_percent,
+                                         int frame_life, uint8_t* out, size_t cap, size_t* out_bytes);
+/* Bytes a compressed file may have (0: vsf_observe_default_compressed_cap of the context's size).  Before the first
+ * compressed submit or while the queue is empty; the ring (vsf_observe_compressed_ring_bytes(depth, cap) of pinned memory)
+ * is built by the next compressed submit. */
+vsf_status vsf_observe_set_compressed_cap(vsf_ctx* ctx, size_t cap_per_image);
+/* The default of that cap: width x height + 64 KB (a lossless file of a noisy image is a little larger than the image; a
+ * camera's JPEG is a tenth of it).  0 for a size below 1 x 1.  No context, no device. */
+size_t vsf_observe_default_compressed_cap(int width, int height);
+/* The size a JPEG / PNG file's header states (PNG: IHDR; JPEG: the first SOF0 / SOF1 / SOF2): what sizes a context for a
+ * stream of such files.  Nothing else of the file is checked.  VSF_ERR_UNSUPPORTED for another format.  No context. */
+vsf_status vsf_compressed_image_size(const uint8_t* file, size_t nbytes, int* width, int* height);
 /* Does not wait and sends nothing: *ready = 1 when the frame's result is there (its collect will not wait), 0 while it still
  * waits in staging or is on the GPU.  What a caller that books results as they come asks before each collect. */
 vsf_status vsf_observe_poll(vsf_ctx* ctx, int64_t ticket, int* ready);
 vsf_status vsf_observe_reset(vsf_ctx* ctx);
 /* What the queue did since it was built: out[0..n) of { frames launched, batches, largest batch, batches of one frame that
  * ran on one stream, launches forced by a collect or a change of parameters, launches that had to wait for a batch slot,
- * depth, frames per batch at most, then the host's nanoseconds inside staging copies, batch launches, waits for results }. */
+ * depth, frames per batch at most, then the host's nanoseconds inside staging copies, batch launches, waits for results,
+ * compressed frames launched, copy commands + kernel launches the compressed path issued, bytes of every buffer the
+ * compressed path owns (file ring, blobs, decoder scratch, mosaics) -- the last three are 0 for a queue that has only seen
+ * raw frames }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,
@@ -434,6 +472,20 @@ vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on);
 /* A collected frame's debug images inside the pinned debug ring (NULL where the frame has none); valid under the rule of
  * vsf_observe_collect_view (until `depth` further frames have been submitted). */
 vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match);
+
+/* ---------------- Host checks of the compressed path (no context, no device) ----------------
+ * What vsf_observe_submit_compressed computes and checks on the host, callable on their own so that tests without a GPU --
+ * the sanitizer build among them -- reach it.  Not needed by a caller of the queue. */
+/* Bytes of one file's slot in the pinned ring: the cap rounded up to 64; 0 for a cap of 0 or above 1 GB. */
+size_t vsf_observe_compressed_slot_bytes(size_t cap_per_image);
+/* Bytes of the ring: depth x 2 slots; 0 for a depth outside 1..1024 or a cap without a slot. */
+size_t vsf_observe_compressed_ring_bytes(int depth, size_t cap_per_image);
+/* What a submit does with ONE payload before anything is booked: *kind = 1 (JPEG) / 2 (PNG) and VSF_OK, or
+ * VSF_ERR_UNSUPPORTED (neither format), VSF_ERR_CAPACITY (larger than cap_per_image; before it is parsed), or the
+ * refusal of that decoder's host half.  force_serial: the context's one-wave-JPEG switch (vsf_debug_jpeg_serial), which
+ * changes the plan that is laid out, never what is refused. */
+vsf_status vsf_observe_probe_compressed(const uint8_t* file, size_t nbytes, int width, int height, size_t cap_per_image,
+                                        int force_serial, int* kind);
 
 /* ---------------- Debug images: cv::circle / cv::line onto GRAY2BGR canvases (slam_frontend.cc:74-115) ----------------
  * Each canvas is GRAY2BGR of one grey image, or of two side by side (cv::hconcat), 3 bytes per pixel, with its slice of the

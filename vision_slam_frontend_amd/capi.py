@@ -39,6 +39,9 @@ EXPORTS = [
     "vsf_jpeg_decode_gray_batch", "vsf_png_decode_gray_batch", "vsf_imdecode_gray_batch", "vsf_tune_fast_resident", "vsf_set_option", "vsf_get_option", "vsf_debug_inject_hip_error", "vsf_comm_unique_id", "vsf_comm_create", "vsf_comm_destroy", "vsf_comm_info",
     "vsf_allgather_dev", "vsf_gather_payload_dev", "vsf_reserve", "vsf_set_input_event",
     "vsf_observe_set_debug_images", "vsf_observe_debug_view", "vsf_draw_canvases_dev", "vsf_draw_canvases",
+    "vsf_observe_submit_compressed", "vsf_observe_stereo_compressed", "vsf_observe_set_compressed_cap",
+    "vsf_observe_default_compressed_cap", "vsf_observe_compressed_slot_bytes", "vsf_observe_compressed_ring_bytes",
+    "vsf_compressed_image_size", "vsf_observe_probe_compressed",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -170,6 +173,19 @@ def lib() -> C.CDLL:
         L.vsf_observe_stereo.argtypes = [vp, vp, vp, i32, i32, sz, C.POINTER(VsfCalibration), C.c_float, i32, vp, sz,
                                          C.POINTER(sz)]
         L.vsf_observe_reset.argtypes = [vp]
+        L.vsf_observe_submit_compressed.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32,
+                                                    C.POINTER(C.c_int64)]
+        L.vsf_observe_stereo_compressed.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32, vp,
+                                                    sz, C.POINTER(sz)]
+        L.vsf_observe_set_compressed_cap.argtypes = [vp, sz]
+        L.vsf_observe_default_compressed_cap.argtypes = [i32, i32]
+        L.vsf_observe_default_compressed_cap.restype = sz
+        L.vsf_observe_compressed_slot_bytes.argtypes = [sz]
+        L.vsf_observe_compressed_slot_bytes.restype = sz
+        L.vsf_observe_compressed_ring_bytes.argtypes = [i32, sz]
+        L.vsf_observe_compressed_ring_bytes.restype = sz
+        L.vsf_compressed_image_size.argtypes = [vp, sz, ip, ip]
+        L.vsf_observe_probe_compressed.argtypes = [vp, sz, i32, i32, sz, i32, ip]
         L.vsf_observe_set_debug_images.argtypes = [vp, i32]
         L.vsf_observe_debug_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
         L.vsf_draw_canvases_dev.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
@@ -480,6 +496,54 @@ class Context:
         self._check(lib().vsf_observe_collect(self._h, C.c_int64(ticket), _p(buf), cap, C.byref(n)), "vsf_observe_collect")
         return decode_observation(buf[:n.value])
 
+    def observe_submit_compressed(self, left: bytes, right: bytes, calib: VsfCalibration, bayer: bool = False,
+                                  best_percent: float = 0.3, frame_life: int = 10, allow_status=()):
+        """Queues one ObserveImage given as two CompressedImage payloads (vsf_observe_submit_compressed: JPEG or PNG, decoded
+        on the GPU inside the batch).  Returns (status, ticket); a status not in `allow_status` raises, and a refused submit
+        has ticket -1."""
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        t = C.c_int64(-1)
+        st = lib().vsf_observe_submit_compressed(self._h, _p(lb), len(lb), _p(rb), len(rb), int(bool(bayer)), C.byref(calib),
+                                                 float(np.float32(best_percent)), frame_life, C.byref(t))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_submit_compressed", lib().vsf_last_hip_error(self._h))
+        return st, int(t.value)
+
+    def observe_stereo_compressed(self, left: bytes, right: bytes, calib: VsfCalibration, bayer: bool = False,
+                                  best_percent: float = 0.3, frame_life: int = 10) -> dict:
+        """vsf_observe_stereo_compressed: submit + collect of one frame given as two compressed payloads."""
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        cap = int(lib().vsf_observe_capacity(self._h, frame_life))
+        buf = np.zeros(max(cap, 64), np.uint8)
+        n = C.c_size_t()
+        self._check(lib().vsf_observe_stereo_compressed(self._h, _p(lb), len(lb), _p(rb), len(rb), int(bool(bayer)),
+                                                        C.byref(calib), float(np.float32(best_percent)), frame_life,
+                                                        _p(buf), cap, C.byref(n)), "vsf_observe_stereo_compressed")
+        return decode_observation(buf[:n.value])
+
+    def observe_collect_bytes(self, ticket: int, frame_life: int = 10, allow_status=()):
+        """vsf_observe_collect as (status, the result's bytes): what the tests compare byte for byte.  Header word 13
+        (bytes 52..56) is the decoder status of a compressed frame (include/vsf.h)."""
+        cap = int(lib().vsf_observe_capacity(self._h, frame_life))
+        buf = np.zeros(max(cap, 64), np.uint8)
+        n = C.c_size_t()
+        st = lib().vsf_observe_collect(self._h, C.c_int64(ticket), _p(buf), cap, C.byref(n))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_collect", lib().vsf_last_hip_error(self._h))
+        return st, buf[:n.value].copy()
+
+    def observe_set_compressed_cap(self, cap_per_image: int):
+        """Bytes a compressed payload may have (vsf_observe_set_compressed_cap; 0: width x height + 64 KB)."""
+        self._check(lib().vsf_observe_set_compressed_cap(self._h, cap_per_image), "vsf_observe_set_compressed_cap")
+
+    def observe_stats(self) -> dict:
+        """vsf_observe_stats by name."""
+        v = np.zeros(14, np.int64)
+        self._check(lib().vsf_observe_stats(self._h, _p(v), 14), "vsf_observe_stats")
+        names = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
+                 "wait_ns", "compressed", "ingest_commands", "compressed_bytes")
+        return {k: int(x) for k, x in zip(names, v)}
+
     def debug_jpeg_serial(self, on: bool):
         """Test hook: every JPEG file through the one-wave-per-image decoder (vsf_debug_jpeg_serial)."""
         lib().vsf_debug_jpeg_serial.argtypes = [C.c_void_p, C.c_int]
@@ -677,4 +741,4 @@ def decode_observation(buf: np.ndarray) -> dict:
     assert off == total
     return {"n_left": int(hdr[4]), "n_right": int(hdr[5]), "n_stereo_matches": int(hdr[6]), "n_points": int(hdr[7]),
             "mean": np.float32(f32[8]), "threshold": np.float32(f32[9]), "threshold_next": np.float32(f32[10]),
-            "features": feats, "factors": lists[:-1], "stereo_pairs": lists[-1], "keypoints": kp, "descriptors": desc}
+            "decoder_status": int(hdr[13]), "features": feats, "factors": lists[:-1], "stereo_pairs": lists[-1], "keypoints": kp, "descriptors": desc}

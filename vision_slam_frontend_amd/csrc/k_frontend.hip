@@ -582,10 +582,13 @@ __global__ __launch_bounds__(256) void observe_pack_kernel(VsfObserveArgs a) {
       out[10] = __float_as_uint(a.means[f] + 2.0f);  // the static's value after this frame (cc:392-394)
       out[11] = total > a.out_cap ? 1u : 0u;
       // capacity overflows of THIS frame's two extractions (a status word per image), read and cleared
-      out[12] = (uint32_t)((a.status[2 * f] | a.status[2 * f + 1]) & 1);
+      // ... and bit 1: the image's decoder refused its file on the device (compressed frames; the image was extracted as zeros)
+      const uint32_t st_l = (uint32_t)a.status[2 * f], st_r = (uint32_t)a.status[2 * f + 1];
+      out[12] = (st_l | st_r) & 1u;
       a.status[2 * f] = 0;
       a.status[2 * f + 1] = 0;
-      out[13] = out[14] = out[15] = 0u;
+      out[13] = ((st_l >> 1) & 1u) | (st_r & 2u);
+      out[14] = out[15] = 0u;
       out[0] = 0x4F465356u;  // "VSFO"
     }
     if ((int)threadIdx.x < ((n_pairs + 3) & ~3))

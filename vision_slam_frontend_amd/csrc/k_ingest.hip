@@ -155,6 +155,18 @@ __global__ __launch_bounds__(256) void bayer_bg_gray_kernel(BayerArgs a) {
   }
 }
 
+// The ObserveImage queue's ingest finish: an image whose decoder refused its data on the device (bit 1 of the image's
+// status word: PNG data libpng answers with png_error, a JPEG stream that broke off) holds whatever the decoder had written
+// by then; it becomes all zero -- a frame is never taken out of the queue, and a constant image has no corners.  One
+// workgroup per image: that of an image nobody refused (all of them, normally) reads one word and leaves.
+__global__ __launch_bounds__(256) void ingest_finish_kernel(uint8_t* __restrict__ img, size_t image_stride, uint32_t dwords,
+                                                            const int32_t* __restrict__ status) {
+  const int image = blockIdx.x;
+  if ((status[image] & 2) == 0) return;
+  uint32_t* out = reinterpret_cast<uint32_t*>(img + (size_t)image * image_stride);
+  for (uint32_t i = threadIdx.x; i < dwords; i += 256u) out[i] = 0u;
+}
+
 }  // namespace
 
 void vsf_launch_bayer_bg_gray(const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch,
@@ -162,4 +174,12 @@ void vsf_launch_bayer_bg_gray(const uint8_t* d_src, int n, int w, int h, size_t 
   BayerArgs a{d_src, src_image_stride, src_pitch, d_dst, dst_image_stride, dst_pitch, w, h};
   const int nstrips = (h + kStripRows - 1) / kStripRows;
   hipLaunchKernelGGL(bayer_bg_gray_kernel, dim3((w + 255) / 256, (nstrips + 3) / 4, n), dim3(256), 0, s, a);
+}
+
+// (pitch and image_stride are multiples of 4 and rows * pitch <= image_stride: the queue's staging layout)
+void vsf_launch_ingest_finish(uint8_t* d_img, size_t image_stride, int pitch, int rows, const int32_t* d_status, int n,
+                              hipStream_t s) {
+  const uint32_t dwords = (uint32_t)(((size_t)pitch * (size_t)rows) >> 2);
+  if (n < 1 || dwords == 0) return;
+  hipLaunchKernelGGL(ingest_finish_kernel, dim3(n), dim3(256), 0, s, d_img, image_stride, dwords, d_status);
 }

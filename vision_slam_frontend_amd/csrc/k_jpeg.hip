@@ -334,7 +334,8 @@ __global__ __launch_bounds__(64) void jpeg_gray_kernel(const DevImage* __restric
                                                         const uint8_t* __restrict__ stream, uint32_t stream_total,
                                                         int width, int height,
                                                         uint8_t* __restrict__ dst, size_t dst_image_stride,
-                                                        int dst_pitch, int32_t* __restrict__ status) {
+                                                        int dst_pitch, int32_t* __restrict__ status,
+                                                        int status_stride) {
   __shared__ uint16_t s_qt[64];
   __shared__ __attribute__((aligned(16))) int16_t s_coef[kGroupBlocks][64];
   __shared__ __attribute__((aligned(16))) int32_t s_ws[kGroupBlocks][64];
@@ -456,7 +457,7 @@ __global__ __launch_bounds__(64) void jpeg_gray_kernel(const DevImage* __restric
     }
     if (done) break;
   }
-  if (lane == 0 && broken) atomicOr(status, 2);
+  if (lane == 0 && broken) atomicOr(status + (size_t)image * status_stride, 2);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -801,7 +802,7 @@ __global__ __launch_bounds__(64) void jpeg_prog_kernel(const DevImage* __restric
                                                         const DevHuffLite* __restrict__ huffs,
                                                         const uint8_t* __restrict__ stream, int16_t* __restrict__ coef_all,
                                                         size_t coef_stride, int slot0, int width, int height,
-                                                        int32_t* __restrict__ status,
+                                                        int32_t* __restrict__ status, int status_stride,
                                                         const int32_t* __restrict__ only_flagged) {
   if (only_flagged && in_constant(only_flagged)[blockIdx.x] == 0) return;  // (the second pass over a batch: damaged files only)
   const int lane = threadIdx.x;
@@ -820,7 +821,7 @@ __global__ __launch_bounds__(64) void jpeg_prog_kernel(const DevImage* __restric
   const ProgWait none{nullptr, -1, -1, -1, -1};
   for (int si = 0; si < im.n_scans && !broken; si++)
     prog_scan<false>(im, si, scans, huffs, stream, coef, width, height, lane, nat, none, broken, suspect);
-  if (lane == 0 && broken) atomicOr(status, 2);
+  if (lane == 0 && broken) atomicOr(status + (size_t)image * status_stride, 2);
 }
 
 // The scans of a progressive file, PIPELINED (round 5).  A scan is a serial bit stream, but the scans of a file depend on
@@ -1177,7 +1178,8 @@ __global__ __launch_bounds__(kParThreads) void jpeg_par_decode_kernel(const DevI
                                                                        uint32_t* __restrict__ clean_all,
                                                                        uint32_t* __restrict__ trans_all,
                                                                        int16_t* __restrict__ coef_all, size_t coef_stride,
-                                                                       int max_slots, int32_t* __restrict__ status) {
+                                                                       int max_slots, int32_t* __restrict__ status,
+                                                                       int status_stride) {
   constexpr int kWaves = kParThreads / 64;
   extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];  // max_slots Huffman tables (DevTables::huff): what
                                                                      // the batch's files use -- two for gray streams
@@ -1368,7 +1370,7 @@ __global__ __launch_bounds__(kParThreads) void jpeg_par_decode_kernel(const DevI
       // (an interval whose data run out before its blocks do: gray MCUs, a warning in libjpeg)
       (void)par_write<true>(G, W, tab, zz, s_blk + wid * 64 * kBlkStride, lane, 0u, begin, 0, 0, g, 0, coef32, g + blocks, true, end);
     }
-    if (broken) atomicOr(status, 2);
+    if (broken) atomicOr(status + (size_t)index[blockIdx.x] * status_stride, 2);
     return;
   }
   // ---- 2. segment end states until they stop changing ----
@@ -1553,7 +1555,7 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off
                             void* d_prog_huff, int n_ser, int max_luma_blocks, int max_slots, int width, int height,
                             uint8_t* d_clean,
                             int16_t* d_coef, size_t coef_stride, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
-                            int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags) {
+                            int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags, int status_stride) {
   const DevImage* images = reinterpret_cast<const DevImage*>(d_blob + off_images);
   const DevTables* tables = reinterpret_cast<const DevTables*>(d_blob + off_tables);
   const uint32_t* index = reinterpret_cast<const uint32_t*>(d_blob + off_index);
@@ -1562,7 +1564,7 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off
     hipLaunchKernelGGL(jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads), (size_t)max_slots * sizeof(DevHuff), s, images, index, tables, d_blob + off_stream,
                        reinterpret_cast<uint32_t*>(d_clean),
                        reinterpret_cast<uint32_t*>(d_clean + vsf_jpeg_clean_bytes(total - off_stream, 0)), d_coef, coef_stride,
-                       max_slots, d_status);
+                       max_slots, d_status, status_stride);
   }
   if (n_prog > 0) {  // progressive files: their slots of the coefficient buffer follow the parallel decoder's
     if (n_prog_huff > 0)
@@ -1580,7 +1582,7 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off
     }
     hipLaunchKernelGGL(jpeg_prog_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par,
                        reinterpret_cast<const DevScan*>(d_blob + off_scans), static_cast<const DevHuffLite*>(d_prog_huff),
-                       d_blob + off_stream, d_coef, coef_stride, n_par, width, height, d_status, only);
+                       d_blob + off_stream, d_coef, coef_stride, n_par, width, height, d_status, status_stride, only);
   }
   if (n_par + n_prog > 0)
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((max_luma_blocks + 7) / 8, n_par + n_prog), dim3(64), 0, s, images, index, tables,
@@ -1588,5 +1590,5 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off
   if (n_ser > 0)
     hipLaunchKernelGGL(jpeg_gray_kernel, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, d_blob + off_stream,
                        (uint32_t)((total - off_stream) & ~(size_t)3), width, height, d_dst, dst_image_stride, dst_pitch,
-                       d_status);
+                       d_status, status_stride);
 }

@@ -297,6 +297,7 @@ struct PngArgs {
   size_t dst_image_stride;
   int dst_pitch;
   int32_t* status;         // bit 1: a file's data is broken (what libpng answers with png_error)
+  int status_stride;       // 0: that one word; 1: status[image] (the ObserveImage queue: a word per image of the batch)
   int32_t* file_status;    // [n]: 0 ok, 1 broken: the unfilter kernel leaves such an image alone
 };
 
@@ -1125,7 +1126,7 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(PngArgs a) {
   if (pos > flushed) ring_chunk(ring_lds, out, flushed, pos - flushed, adler_a, adler_b, true);
   if (lane == 0) {
     a.file_status[image] = bad ? 1 : 0;
-    if (bad) atomicOr(a.status, 2);
+    if (bad) atomicOr(a.status + (size_t)image * a.status_stride, 2);
   }
 }
 
@@ -1192,7 +1193,7 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(PngArgs a) {
     }
     __threadfence();  // lane 63's row is the next group's lane 0's "above"
   }
-  if (bad) atomicOr(a.status, 2);  // "bad adaptive filter value": libpng stops with png_error; the image is not to be used
+  if (bad) atomicOr(a.status + (size_t)image * a.status_stride, 2);  // "bad adaptive filter value": libpng stops with png_error; the image is not to be used
 }
 
 // The same for palette files (the index goes through the file's 256 gray values) and interlaced files of either kind: seven
@@ -1271,7 +1272,7 @@ __global__ __launch_bounds__(64) void png_unfilter_general_kernel(PngArgs a) {
     }
     filt += (size_t)rb1 * h;
   }
-  if (bad) atomicOr(a.status, 2);  // "bad adaptive filter value": libpng stops with png_error; the image is not to be used
+  if (bad) atomicOr(a.status + (size_t)image * a.status_stride, 2);  // "bad adaptive filter value": libpng stops with png_error; the image is not to be used
 }
 
 // The same for colour files (types 2 and 6): every byte plane the gray value needs is reconstructed IN PLACE -- red, green,
@@ -1361,14 +1362,14 @@ __global__ __launch_bounds__(64) void png_unfilter_rgb_kernel(PngArgs a) {
     }
     filt += (size_t)rb1 * h;
   }
-  if (bad) atomicOr(a.status, 2);  // "bad adaptive filter value"
+  if (bad) atomicOr(a.status + (size_t)image * a.status_stride, 2);  // "bad adaptive filter value"
 }
 
 }  // namespace
 
 void vsf_launch_png_decode(const uint8_t* d_blob, size_t off_images, size_t off_pieces, size_t off_tables, size_t off_stream, int n, int width, int height,
                            uint8_t* d_filtered, size_t filtered_stride, int32_t* d_file_status, uint8_t* d_dst,
-                           size_t dst_image_stride, int dst_pitch, int32_t* d_status, bool any_general, bool any_rgb, hipStream_t s) {
+                           size_t dst_image_stride, int dst_pitch, int32_t* d_status, bool any_general, bool any_rgb, hipStream_t s, int status_stride) {
   PngArgs a;
   a.blob = d_blob;
   a.off_images = off_images;
@@ -1383,6 +1384,7 @@ void vsf_launch_png_decode(const uint8_t* d_blob, size_t off_images, size_t off_
   a.dst_image_stride = dst_image_stride;
   a.dst_pitch = dst_pitch;
   a.status = d_status;
+  a.status_stride = status_stride;
   a.file_status = d_file_status;
   hipLaunchKernelGGL(png_inflate_kernel, dim3(n), dim3(64), 0, s, a);
   hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(64), 0, s, a);

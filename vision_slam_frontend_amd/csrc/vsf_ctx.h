@@ -138,6 +138,10 @@ struct vsf_ctx {
     int32_t* nmatches = nullptr;     // [bmax]
     int32_t* status = nullptr;       // [2 bmax] a status word per image
     ObserveBatchMeta* h_meta = nullptr;
+    // compressed frames: the batch's ONE upload (every run's headers / tables / entropy-coded or IDAT bytes), pinned + device
+    uint8_t* h_blob = nullptr;
+    uint8_t* d_blob = nullptr;
+    size_t blob_cap = 0;
     hipEvent_t ev_uploaded = nullptr, ev_extracted = nullptr, ev_done = nullptr;
     bool used = false;               // ev_done has been recorded at least once
     hipStream_t done_stream = nullptr;  // the stream its tail ran on
@@ -146,6 +150,9 @@ struct vsf_ctx {
     vsf_calibration calib;
     float best_percent = 0.f;
     int batch = -1;  // batch slot it was launched in, -1 while it waits
+    uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, 1 a JPEG file, 2 a PNG file in h_cmp
+    uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
+    bool bayer = false;          // compressed frames: the decoded images are bayer_rggb8 mosaics
   };
   struct Observe {
     bool ready = false;
@@ -186,6 +193,23 @@ struct vsf_ctx {
     vsf_vision_feature* features = nullptr;  // [bmax][K]
     uint8_t* h_img = nullptr;       // pinned [depth][2] images at the staging pitch
     uint8_t* h_out = nullptr;       // pinned [depth][out_stride], written by observe_pack_kernel
+    // vsf_observe_submit_compressed; nothing of this exists before the first compressed frame.  The files wait in a pinned
+    // ring of their own; a batch's decode runs on the copy stream (one batch after the other: ONE set of decoder scratch)
+    uint8_t* h_cmp = nullptr;       // pinned [depth][2][cmp_slot] the files as submitted
+    size_t cmp_cap = 0, cmp_slot = 0;  // bytes a file may have / bytes of its slot (vsf_observe_compressed_slot_bytes)
+    uint8_t* d_bayer = nullptr;     // [2 bmax] images at the staging pitch: the decoded mosaics of a Bayer batch
+    uint8_t* ing_clean = nullptr;   // the JPEG decoders' scratch (as vsf_ctx::jp_clean / jp_coef / jp_flags) ...
+    size_t ing_clean_cap = 0;
+    int16_t* ing_coef = nullptr;
+    size_t ing_coef_cap = 0;
+    int32_t* ing_flags = nullptr;
+    int ing_flags_cap = 0;
+    uint8_t* ing_filtered = nullptr;  // ... and the PNG decoder's (png_filtered / png_file_status)
+    size_t ing_filtered_cap = 0;
+    int32_t* ing_file_status = nullptr;
+    int ing_file_status_cap = 0;
+    int64_t stat_compressed = 0;    // compressed frames launched
+    int64_t stat_ingest_commands = 0;  // copy commands + launches the compressed path issued
     size_t out_cap = 0, out_stride = 0;
     ObserveBatch batch[kObserveBatchSlots];
     std::vector<ObserveFrame> frames;  // [depth]
@@ -205,6 +229,7 @@ struct vsf_ctx {
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
+  size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // vsf_draw_canvases(_dev) (k_draw.hip): per-pixel winners (all zero between calls: the resolve clears what it read),
   // the canvas table (device, and its host image until the upload has left: dr_uploaded), the host call's staging
   uint64_t* dr_win = nullptr;

@@ -334,7 +334,7 @@ void vsf_png_fill(const VsfPngPlan& plan, const uint8_t* const* png, int n, uint
 #endif
 void vsf_launch_png_decode(const uint8_t* d_blob, size_t off_images, size_t off_pieces, size_t off_tables, size_t off_stream, int n, int width, int height,
                            uint8_t* d_filtered, size_t filtered_stride, int32_t* d_file_status, uint8_t* d_dst,
-                           size_t dst_image_stride, int dst_pitch, int32_t* d_status, bool any_general, bool any_rgb, hipStream_t s);
+                           size_t dst_image_stride, int dst_pitch, int32_t* d_status, bool any_general, bool any_rgb, hipStream_t s, int status_stride = 0);
 size_t vsf_jpeg_clean_bytes(size_t stream_bytes, int n_par);
 size_t vsf_jpeg_prog_huff_bytes(int n_tables);  // device scratch for the expanded tables of progressive scans
 void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off_index, size_t off_tables, size_t off_scans,
@@ -342,7 +342,12 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off
                             void* d_prog_huff, int n_ser, int max_luma_blocks, int max_slots, int width, int height,
                             uint8_t* d_clean,
                             int16_t* d_coef, size_t coef_stride, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
-                            int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags);
+                            int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags, int status_stride = 0);
 // prog_serial: progressive files scan after scan in one wave; d_prog_flags [n_prog]: scratch of the pipelined form
+// status_stride (both decoders): 0 = every file reports into *d_status; 1 = file i into d_status[i] (the ObserveImage queue)
+// The queue's ingest finish (k_ingest.hip): every image of [0, n) whose status word carries bit 1 (its decoder refused the
+// data) becomes all zero, `rows` rows of `pitch` bytes.
+void vsf_launch_ingest_finish(uint8_t* d_img, size_t image_stride, int pitch, int rows, const int32_t* d_status, int n,
+                              hipStream_t s);
 
 #endif  // VSF_INTERNAL_H_

@@ -212,6 +212,13 @@ void free_observe(vsf_ctx* ctx) {
   hipFree(o.features);
   if (o.h_img) hipHostFree(o.h_img);
   if (o.h_out) hipHostFree(o.h_out);
+  if (o.h_cmp) hipHostFree(o.h_cmp);
+  hipFree(o.d_bayer);
+  hipFree(o.ing_clean);
+  hipFree(o.ing_coef);
+  hipFree(o.ing_flags);
+  hipFree(o.ing_filtered);
+  hipFree(o.ing_file_status);
   hipFree(o.dbg_canvas);
   hipFree(o.dbg_win);
   hipFree(o.dbg_ops);
@@ -229,6 +236,8 @@ void free_observe(vsf_ctx* ctx) {
     hipFree(b.nmatches);
     hipFree(b.status);
     if (b.h_meta) hipHostFree(b.h_meta);
+    if (b.h_blob) hipHostFree(b.h_blob);
+    hipFree(b.d_blob);
     if (b.ev_uploaded) hipEventDestroy(b.ev_uploaded);
     if (b.ev_extracted) hipEventDestroy(b.ev_extracted);
     if (b.ev_done) hipEventDestroy(b.ev_done);
@@ -338,6 +347,156 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   return VSF_OK;
 }
 
+// The pinned ring the compressed files wait in (and, for bayer_rggb8 frames, the buffer their mosaics are decoded into):
+// built by the first compressed submit -- a queue that only ever sees raw frames owns none of this.
+// Bytes a compressed file may have: ONE derivation, for the submit's probe and for the ring (vsf_observe_set_compressed_cap
+// retires a ring built for another cap, so a ring that exists was built for this value).
+size_t compressed_cap(const vsf_ctx* ctx) {
+  return ctx->ob_cmp_cap ? ctx->ob_cmp_cap : vsf_observe_default_compressed_cap(ctx->p.width, ctx->p.height);
+}
+
+vsf_status ensure_compressed(vsf_ctx* ctx, bool bayer) {
+  vsf_ctx::Observe& o = ctx->ob;
+  if (!o.h_cmp) {
+    const size_t cap = compressed_cap(ctx);
+    const size_t ring = vsf_observe_compressed_ring_bytes(o.depth, cap);
+    if (ring == 0) return VSF_ERR_INVALID_ARG;
+    VSF_HIP(hipHostMalloc((void**)&o.h_cmp, ring, hipHostMallocDefault));
+    o.cmp_cap = cap;
+    o.cmp_slot = vsf_observe_compressed_slot_bytes(cap);
+  }
+  if (bayer && !o.d_bayer) VSF_HIP(hipMalloc((void**)&o.d_bayer, 2 * (size_t)o.bmax * ctx->st_img_stride));
+  return VSF_OK;
+}
+
+// A scratch buffer of the queue's decoders grown without waiting for the GPU (grow_scratch: the outgrown one is retired).
+template <class T, class N>
+vsf_status grow_ingest(vsf_ctx* ctx, T*& ptr, N& cap, size_t need, size_t unit) {
+  if (need <= (size_t)cap * unit) return VSF_OK;
+  const size_t want = need + need / 4;
+  const vsf_status st = grow_scratch(ctx, ptr, want);
+  if (st != VSF_OK) return st;
+  cap = (N)(want / unit);
+  return VSF_OK;
+}
+
+// The compressed frames of batch [t0, t0 + n): the host half of the decoders over every run of one format among the
+// batch's 2n images (as vsf_imdecode_gray_batch walks a list of files), ONE upload for all of them, the decode kernels on
+// `s` with a status word per image (b.status: damage lands on its own image), BayerBG -> gray for bayer_rggb8 frames, and
+// the ingest finish: an image its decoder refused becomes all zero.  Raw frames of the batch have been copied already.
+vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s) {
+  vsf_ctx::Observe& o = ctx->ob;
+  const int w = ctx->p.width, h = ctx->p.height, N = 2 * n;
+  const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
+  std::vector<const uint8_t*> files((size_t)N);
+  std::vector<size_t> sizes((size_t)N);
+  std::vector<int> kind((size_t)N);
+  for (int i = 0; i < N; i++) {
+    const int slot = (int)((t0 + i / 2) % o.depth);
+    const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
+    kind[i] = fr.kind[i & 1];
+    files[i] = o.h_cmp + ((size_t)slot * 2 + (size_t)(i & 1)) * o.cmp_slot;
+    sizes[i] = fr.nbytes[i & 1];
+  }
+  struct Run {
+    int i0, n, kind;
+    size_t off;
+    VsfJpegPlan jp;
+    VsfPngPlan pp;
+  };
+  std::vector<Run> runs;
+  size_t total = 0, clean_need = 0, coef_need = 0, filtered_need = 0;
+  int flags_need = 0, png_need = 0;
+  for (int i0 = 0; i0 < N;) {
+    int i1 = i0 + 1;
+    while (i1 < N && kind[i1] == kind[i0]) ++i1;
+    if (kind[i0] != 0) {
+      runs.emplace_back();
+      Run& r = runs.back();
+      r.i0 = i0;
+      r.n = i1 - i0;
+      r.kind = kind[i0];
+      r.off = total;
+      vsf_status st;
+      if (r.kind == 1) {
+        st = vsf_jpeg_plan(files.data() + i0, sizes.data() + i0, r.n, w, h, ctx->tuning.jpeg_serial != 0, &r.jp);
+        if (st != VSF_OK) return st;  // (every file passed this at its submit)
+        total += (r.jp.total + 255) & ~(size_t)255;
+        if (r.jp.n_par + r.jp.n_prog > 0) {
+          const size_t coef_stride = (size_t)r.jp.max_luma_blocks * 64 * sizeof(int16_t);
+          if (r.jp.n_par > 0) clean_need = std::max(clean_need, vsf_jpeg_clean_bytes(r.jp.total - r.jp.off_stream, r.jp.n_par));
+          coef_need = std::max(coef_need, (size_t)(r.jp.n_par + r.jp.n_prog) * coef_stride + vsf_jpeg_prog_huff_bytes(r.jp.n_prog_huff));
+        }
+        flags_need = std::max(flags_need, r.jp.n_prog);
+      } else {
+        st = vsf_png_plan(files.data() + i0, sizes.data() + i0, r.n, w, h, &r.pp);
+        if (st != VSF_OK) return st;
+        total += (r.pp.total + 255) & ~(size_t)255;
+        filtered_need = std::max(filtered_need, r.pp.filtered_stride * (size_t)r.n);
+        png_need = std::max(png_need, r.n);
+      }
+    }
+    i0 = i1;
+  }
+  if (runs.empty()) return VSF_OK;
+  if (total > b.blob_cap) {  // (no wait: the slot's previous batch has left the GPU, but hipFree would wait for the device)
+    const size_t cap = total + total / 4 + 4096;
+    void *host = nullptr, *dev = nullptr;
+    VSF_HIP(hipHostMalloc(&host, cap, hipHostMallocDefault));
+    if (hipMalloc(&dev, cap) != hipSuccess) {
+      hipHostFree(host);
+      (void)hipGetLastError();
+      return VSF_ERR_HIP;
+    }
+    if (b.h_blob) ctx->retired_host.push_back(b.h_blob);
+    if (b.d_blob) ctx->retired.push_back(b.d_blob);
+    b.h_blob = static_cast<uint8_t*>(host);
+    b.d_blob = static_cast<uint8_t*>(dev);
+    b.blob_cap = cap;
+  }
+  vsf_status st = grow_ingest(ctx, o.ing_clean, o.ing_clean_cap, clean_need, 1);
+  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_coef, o.ing_coef_cap, coef_need, 1);
+  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_flags, o.ing_flags_cap, (size_t)flags_need * sizeof(int32_t), sizeof(int32_t));
+  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_filtered, o.ing_filtered_cap, filtered_need, 1);
+  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_file_status, o.ing_file_status_cap, (size_t)png_need * sizeof(int32_t), sizeof(int32_t));
+  if (st != VSF_OK) return st;
+  for (const Run& r : runs) {
+    if (r.kind == 1)
+      vsf_jpeg_fill(r.jp, files.data() + r.i0, r.n, b.h_blob + r.off);
+    else
+      vsf_png_fill(r.pp, files.data() + r.i0, r.n, b.h_blob + r.off);
+  }
+  VSF_HIP(hipMemcpyAsync(b.d_blob, b.h_blob, total, hipMemcpyHostToDevice, s));
+  // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
+  o.stat_ingest_commands += 2 + (int64_t)runs.size() + (bayer ? 1 : 0);
+  uint8_t* dst = bayer ? o.d_bayer : b.d_img;
+  const size_t stride = ctx->st_img_stride;
+  const int pitch = (int)ctx->st_img_pitch;
+  for (const Run& r : runs) {
+    const uint8_t* blob = b.d_blob + r.off;
+    uint8_t* d = dst + (size_t)r.i0 * stride;
+    if (r.kind == 1) {
+      const VsfJpegPlan& p = r.jp;
+      const size_t coef_stride = (size_t)p.max_luma_blocks * 64 * sizeof(int16_t);
+      vsf_launch_jpeg_decode(blob, p.off_images, p.off_index, p.off_tables, p.off_scans, p.off_prog_huff, p.off_stream, p.total,
+                             p.n_par, p.n_prog, p.n_prog_huff,
+                             reinterpret_cast<uint8_t*>(o.ing_coef) + (size_t)(p.n_par + p.n_prog) * coef_stride,
+                             r.n - p.n_par - p.n_prog, p.max_luma_blocks, p.max_slots, w, h, o.ing_clean, o.ing_coef, coef_stride, d,
+                             stride, pitch, b.status + r.i0, s, ctx->tuning.jpeg_serial != 0, o.ing_flags, 1);
+    } else {
+      const VsfPngPlan& p = r.pp;
+      vsf_launch_png_decode(blob, p.off_images, p.off_pieces, p.off_tables, p.off_stream, r.n, w, h, o.ing_filtered,
+                            p.filtered_stride, o.ing_file_status, d, stride, pitch, b.status + r.i0, p.any_general, p.any_rgb, s,
+                            1);
+    }
+  }
+  // bayer_rggb8 (slam_frontend_main.cc:101-109): every image of such a batch is a decoded mosaic
+  if (bayer) vsf_launch_bayer_bg_gray(o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
+  vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
+  for (int f = 0; f < n; f++) o.stat_compressed += kind[2 * f] != 0;
+  return VSF_OK;
+}
+
 int batches_on_gpu(vsf_ctx* ctx) {  // launched and not finished (a query costs 0.1 us)
   int n = 0;
   for (vsf_ctx::ObserveBatch& b : ctx->ob.batch)
@@ -365,16 +524,31 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   // solo: a lone frame with nothing else on the GPU runs on ONE stream from upload to result (no event hops in its chain);
   // otherwise copy, extraction and tail have a stream each, so that the next batch's upload and extraction run beside
   // this one's tail.
-  hipStream_t s_copy = solo ? ctx->stream : o.copy_stream, s_ex = ctx->stream, s_tail = solo ? ctx->stream : o.tail_stream;
+  bool any_raw = false, any_cmp = false;
+  for (int f = 0; f < n; f++) {
+    const bool c = o.frames[(size_t)((t0 + f) % o.depth)].kind[0] != 0;
+    any_cmp |= c;
+    any_raw |= !c;
+  }
+  // (compressed frames are decoded on the copy stream whatever else runs: the decoders' scratch exists once, for that stream)
+  hipStream_t s_copy = solo && !any_cmp ? ctx->stream : o.copy_stream, s_ex = ctx->stream,
+              s_tail = solo ? ctx->stream : o.tail_stream;
   // ---- upload: ONE copy command (two when the frames wrap around the staging ring) ----
   {
     const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
     const size_t frame_bytes = 2 * ctx->st_img_stride;
-    VSF_HIP(hipMemcpyAsync(b.d_img, o.h_img + (size_t)slot0 * frame_bytes, (size_t)first * frame_bytes, hipMemcpyHostToDevice,
-                           s_copy));
-    if (first < n)
+    // (a batch that mixes raw and compressed frames copies its whole span of the raw ring: the decoders write behind it)
+    if (any_raw)
+      VSF_HIP(hipMemcpyAsync(b.d_img, o.h_img + (size_t)slot0 * frame_bytes, (size_t)first * frame_bytes,
+                             hipMemcpyHostToDevice, s_copy));
+    if (any_raw && first < n)
       VSF_HIP(hipMemcpyAsync(b.d_img + (size_t)first * frame_bytes, o.h_img, (size_t)(n - first) * frame_bytes,
                              hipMemcpyHostToDevice, s_copy));
+    // ---- compressed frames: one more copy command for their files, the decoders, the ingest finish ----
+    if (any_cmp) {
+      const vsf_status st = ingest_batch(ctx, b, t0, n, s_copy);
+      if (st != VSF_OK) return st;
+    }
     if (s_copy != s_ex) {
       VSF_HIP(hipEventRecord(b.ev_uploaded, s_copy));
       VSF_HIP(hipStreamWaitEvent(s_ex, b.ev_uploaded, 0));
@@ -684,9 +858,16 @@ vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (!ctx || !out || n < 1) return VSF_ERR_INVALID_ARG;
   const vsf_ctx::Observe& o = ctx->ob;
-  const int64_t v[11] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
-                         (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns};
-  for (int i = 0; i < n && i < 11; i++) out[i] = v[i];
+  // every byte the compressed path owns: 0 until the first compressed frame
+  size_t cmp_bytes = o.h_cmp ? vsf_observe_compressed_ring_bytes(o.depth, o.cmp_cap) : 0;
+  if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
+  for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob_cap;
+  cmp_bytes += o.ing_clean_cap + o.ing_coef_cap + o.ing_filtered_cap +
+               ((size_t)o.ing_flags_cap + (size_t)o.ing_file_status_cap) * sizeof(int32_t);
+  const int64_t v[14] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
+                         (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns,
+                         o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes};
+  for (int i = 0; i < n && i < 14; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -700,14 +881,11 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx) {
   return VSF_OK;
 }
 
-vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
-                              const vsf_calibration* calib, float best_percent, int frame_life, int64_t* ticket) {
-  VsfErrorScope scope_(ctx, false);
-  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
-      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
-    return VSF_ERR_INVALID_ARG;
-  *ticket = -1;
-  if (w != ctx->p.width || h != ctx->p.height || stride < (size_t)w || ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
+// Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
+// have passed vsf_observe_probe_compressed as kinds[0 / 1].
+static vsf_status observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
+                                 const int* kinds, const size_t* nbytes, bool bayer, const vsf_calibration* calib,
+                                 float best_percent, int frame_life, int64_t* ticket) {
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6)
     return VSF_ERR_INVALID_ARG;
@@ -729,7 +907,7 @@ vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* 
     if (L.status != VSF_OK) return L.status;
     if (o.next_launch < o.next_ticket) {
       const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)((o.next_ticket - 1) % o.depth)];
-      if (w0.best_percent != best_percent || !same_calibration(w0.calib, *calib)) {
+      if (w0.best_percent != best_percent || !same_calibration(w0.calib, *calib) || w0.bayer != bayer) {
         st = caller_pump(ctx, lk, true);
         if (st != VSF_OK) return st;
       }
@@ -747,8 +925,18 @@ vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* 
       o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
     }
   }
-  uint8_t* h_img = o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
+  vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
   const int64_t t_copy = now_ns();
+  if (kinds) {
+    // ---- the two files into the frame's slots of the compressed ring (built by the first such frame) ----
+    st = ensure_compressed(ctx, bayer);
+    if (st != VSF_OK) return st;
+    if (o.cmp_cap != compressed_cap(ctx) || nbytes[0] > o.cmp_cap || nbytes[1] > o.cmp_cap) return VSF_ERR_CAPACITY;
+    uint8_t* h_cmp = o.h_cmp + (size_t)slot * 2 * o.cmp_slot;
+    std::memcpy(h_cmp, left, nbytes[0]);
+    std::memcpy(h_cmp + o.cmp_slot, right, nbytes[1]);
+  } else {
+  uint8_t* h_img = o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
   const vsf_ctx::ObserveCopyHelper::Job jr{h_img + ctx->st_img_stride, right, ctx->st_img_pitch, stride, (size_t)w, h};
   // frames are streaming in (the previous one is still in the queue): the helper thread takes the right image
   const bool helped = o.copy_helper && o.next_ticket > o.next_collect && o.copy_helper->post(jr);
@@ -757,8 +945,13 @@ vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* 
     o.copy_helper->wait();
   else
     stage_image(jr.dst, jr.dst_pitch, jr.src, jr.src_pitch, jr.width, jr.rows);
+  }
   o.stat_copy_ns += now_ns() - t_copy;
-  vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
+  for (int k = 0; k < 2; k++) {
+    fr.kind[k] = kinds ? (uint8_t)kinds[k] : 0;
+    fr.nbytes[k] = kinds ? (uint32_t)nbytes[k] : 0u;
+  }
+  fr.bayer = bayer;
   fr.calib = *calib;
   fr.best_percent = best_percent;
   fr.batch = -1;
@@ -773,6 +966,52 @@ vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* 
     return VSF_OK;
   }
   return caller_pump(ctx, lk, false);
+}
+
+vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
+                              const vsf_calibration* calib, float best_percent, int frame_life, int64_t* ticket) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
+      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
+    return VSF_ERR_INVALID_ARG;
+  *ticket = -1;
+  if (w != ctx->p.width || h != ctx->p.height || stride < (size_t)w || ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
+  return observe_submit(ctx, left, right, w, h, stride, nullptr, nullptr, false, calib, best_percent, frame_life, ticket);
+}
+
+vsf_status vsf_observe_submit_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                         size_t right_bytes, int bayer, const vsf_calibration* calib, float best_percent,
+                                         int frame_life, int64_t* ticket) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
+      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
+    return VSF_ERR_INVALID_ARG;
+  *ticket = -1;
+  if (ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
+  // the decoders' host half, file by file: a refused file books nothing and leaves the queue as it was
+  const size_t cap = compressed_cap(ctx);
+  const size_t nbytes[2] = {left_bytes, right_bytes};
+  int kinds[2] = {0, 0};
+  vsf_status st = vsf_observe_probe_compressed(left, left_bytes, ctx->p.width, ctx->p.height, cap, ctx->tuning.jpeg_serial, &kinds[0]);
+  if (st == VSF_OK)
+    st = vsf_observe_probe_compressed(right, right_bytes, ctx->p.width, ctx->p.height, cap, ctx->tuning.jpeg_serial, &kinds[1]);
+  if (st != VSF_OK) return st;
+  return observe_submit(ctx, left, right, ctx->p.width, ctx->p.height, 0, kinds, nbytes, bayer != 0, calib, best_percent,
+                        frame_life, ticket);
+}
+
+vsf_status vsf_observe_set_compressed_cap(vsf_ctx* ctx, size_t cap_per_image) {
+  VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
+  if (!ctx || (cap_per_image != 0 && vsf_observe_compressed_slot_bytes(cap_per_image) == 0)) return VSF_ERR_INVALID_ARG;
+  vsf_ctx::Observe& o = ctx->ob;
+  if (o.ready && o.next_collect != o.next_ticket) return VSF_ERR_INVALID_ARG;  // frames in the queue
+  if (o.h_cmp) {  // (every frame has been collected: no upload reads the ring; a pinned buffer is retired, not freed)
+    ctx->retired_host.push_back(o.h_cmp);
+    o.h_cmp = nullptr;
+    o.cmp_cap = o.cmp_slot = 0;
+  }
+  ctx->ob_cmp_cap = cap_per_image;
+  return VSF_OK;
 }
 
 // Waits for the frame of `ticket` and points at its result inside the pinned result ring (valid until `depth` further
@@ -817,6 +1056,7 @@ static vsf_status observe_wait(vsf_ctx* ctx, int64_t ticket, const uint8_t** vie
   *bytes = hdr[3];
   if (st != VSF_OK) return st;
   if (hdr[11] != 0) return VSF_ERR_CAPACITY;  // the result does not fit its slot
+  if (hdr[13] != 0) return VSF_ERR_INVALID_ARG;  // a file of this frame was refused on the device (extracted as zeros)
   return hdr[12] != 0 ? VSF_ERR_CAPACITY : VSF_OK;
 }
 
@@ -872,6 +1112,19 @@ vsf_status vsf_observe_stereo(vsf_ctx* ctx, const uint8_t* left, const uint8_t* 
   *out_bytes = 0;
   int64_t ticket = -1;
   const vsf_status st = vsf_observe_submit(ctx, left, right, w, h, stride, calib, best_percent, frame_life, &ticket);
+  if (st != VSF_OK) return st;
+  return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
+}
+
+vsf_status vsf_observe_stereo_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                         size_t right_bytes, int bayer, const vsf_calibration* calib, float best_percent,
+                                         int frame_life, uint8_t* out, size_t cap, size_t* out_bytes) {
+  VsfErrorScope scope_(ctx, false);
+  if (!out || !out_bytes) return VSF_ERR_INVALID_ARG;
+  *out_bytes = 0;
+  int64_t ticket = -1;
+  const vsf_status st =
+      vsf_observe_submit_compressed(ctx, left, left_bytes, right, right_bytes, bayer, calib, best_percent, frame_life, &ticket);
   if (st != VSF_OK) return st;
   return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
 }

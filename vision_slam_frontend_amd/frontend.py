@@ -27,7 +27,10 @@ def lib() -> C.CDLL:
         L.vsfh_frontend_destroy.argtypes = [vp]
         L.vsfh_observe_odometry.argtypes = [vp, vp, vp, dbl]
         L.vsfh_observe_image.argtypes = [vp, vp, vp, i32, i32, sz, dbl]
+        L.vsfh_observe_compressed_image.argtypes = [vp, vp, sz, vp, sz, i32, dbl]
         L.vsfh_last_status.argtypes = [vp]
+        L.vsfh_refused_frames.argtypes = [vp]
+        L.vsfh_refused_frames.restype = C.c_uint64
         L.vsfh_num_poses.argtypes = [vp]
         L.vsfh_stereo_ambig_constraint.argtypes = [vp]
         L.vsfh_stereo_ambig_constraint.restype = f32
@@ -171,6 +174,27 @@ class Frontend:
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend::ObserveImage")
         return added
+
+    def observe_compressed_image(self, left: bytes, right: bytes, bayer_rggb8: bool = False, time: float = 0.0,
+                                 allow_status=()) -> bool:
+        """Frontend::ObserveCompressedImage: the two CompressedImage payloads (JPEG or PNG) as they came; decoded on the GPU
+        inside the queue.  A status in `allow_status` (a refused file) is left for last_status instead of raising."""
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        added = bool(lib().vsfh_observe_compressed_image(self._h, _p(lb), len(lb), _p(rb), len(rb), int(bool(bayer_rggb8)),
+                                                         time))
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK and st not in allow_status:
+            raise capi.VsfError(st, "Frontend::ObserveCompressedImage")
+        return added
+
+    @property
+    def refused_frames(self) -> int:
+        """Frames booked so far whose compressed file the device refused (observed as an all-zero image); never goes back."""
+        return int(lib().vsfh_refused_frames(self._h))
+
+    @property
+    def last_status(self) -> int:
+        return int(lib().vsfh_last_status(self._h))
 
     @property
     def num_poses(self) -> int:

@@ -1,6 +1,7 @@
 // frontend_capi.cc -- flat C view of slam::Frontend so tests (ctypes) and foreign callers can drive the host
 // class: same call sequence as the reference's driver (slam_frontend_main.cc:132,147,321).
 #include <chrono>
+#include <vector>
 #include <cstring>
 
 #include "slam_frontend.h"
@@ -86,6 +87,58 @@ double vsfh_time_sequence(void* f, const uint8_t* frames, int n_src, int w, int 
   if (max_call_ms) *max_call_ms = 1e3 * worst;
   return n > 0 && wall > 0 ? n / wall : 0.0;
 }
+// The same loop fed from compressed payloads in host memory (n_src stereo frames: file 2i is frame i's left, 2i + 1 its right;
+// file j is blob[offsets[j], offsets[j + 1])), as the reference's CompressedImageCallback is (slam_frontend_main.cc:98-133).
+// decode == NULL: ObserveCompressedImage (the GPU decodes inside the queue).  Otherwise decode-then-observe on the host:
+// decode(file, bytes, w, h, dst, pitch, &w_out, &h_out) -- a libjpeg driven as cv::imdecode drives it -- fills two w x h
+// images per frame and ObserveImage takes them.  Returns the steady frames per second; *mean_call_ms / *max_call_ms: time inside the
+// frame's calls (decode included); < 0 on failure.
+typedef int (*vsfh_decode_fn)(const char* file, size_t bytes, int w, int h, void* dst, size_t pitch, int* w_out, int* h_out);
+double vsfh_time_compressed_sequence(void* f, const uint8_t* blob, const uint64_t* offsets, int n_src, int bayer, int w, int h,
+                                     int n_frames, int warm, vsfh_decode_fn decode, double* mean_call_ms, double* max_call_ms) {
+  using Clock = std::chrono::steady_clock;
+  Frontend* fe = static_cast<Frontend*>(f);
+  const slam::Quaternionf q(1, 0, 0, 0);
+  const int first = fe->GetNumPoses();
+  if (first == 0) fe->ObserveOdometry(slam::Vector3f(0, 0, 0), q, 0.0);
+  std::vector<uint8_t> scratch(decode ? (size_t)2 * w * h : 0);
+  Clock::time_point t0 = Clock::now();
+  double sum = 0, worst = 0;
+  for (int k = 0; k < n_frames; k++) {
+    if (k == warm) {
+      fe->Flush();
+      t0 = Clock::now();
+    }
+    const int i = k % n_src;
+    const uint8_t *l = blob + offsets[2 * i], *r = blob + offsets[2 * i + 1];
+    const size_t nl = (size_t)(offsets[2 * i + 1] - offsets[2 * i]), nr = (size_t)(offsets[2 * i + 2] - offsets[2 * i + 1]);
+    fe->ObserveOdometry(slam::Vector3f(0.3f * (first + k + 1), 0, 0), q, 1.0 + first + k);
+    const Clock::time_point a = Clock::now();
+    bool added;
+    if (decode) {
+      int ww = 0, hh = 0;
+      uint8_t *dl = scratch.data(), *dr = scratch.data() + (size_t)w * h;
+      if (decode(reinterpret_cast<const char*>(l), nl, w, h, dl, (size_t)w, &ww, &hh) != 0 ||
+          decode(reinterpret_cast<const char*>(r), nr, w, h, dr, (size_t)w, &ww, &hh) != 0)
+        return -1.0;
+      added = fe->ObserveImage(slam::Image(dl, h, w, (size_t)w), slam::Image(dr, h, w, (size_t)w), 1.0 + first + k);
+    } else {
+      added = fe->ObserveCompressedImage(l, nl, r, nr, bayer != 0, 1.0 + first + k);
+    }
+    const double dt = std::chrono::duration<double>(Clock::now() - a).count();
+    if (!added || fe->last_status() != VSF_OK) return -1.0;
+    if (k >= warm) {
+      sum += dt;
+      if (dt > worst) worst = dt;
+    }
+  }
+  if (!fe->Flush()) return -1.0;
+  const double wall = std::chrono::duration<double>(Clock::now() - t0).count();
+  const int n = n_frames - warm;
+  if (mean_call_ms) *mean_call_ms = n > 0 ? 1e3 * sum / n : 0;
+  if (max_call_ms) *max_call_ms = 1e3 * worst;
+  return n > 0 && wall > 0 ? n / wall : 0.0;
+}
 int vsfh_flush(void* f) { return static_cast<Frontend*>(f)->Flush() ? 1 : 0; }
 
 // Debug images (slam_frontend.cc:474-495).  stereo = 0: getDebugImages / GetLastDebugImage; 1: the stereo ones.
@@ -126,6 +179,12 @@ int vsfh_observe_image(void* f, const uint8_t* left, const uint8_t* right, int w
              : 0;
 }
 
+int vsfh_observe_compressed_image(void* f, const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
+                                  int bayer_rggb8, double time) {
+  return static_cast<Frontend*>(f)->ObserveCompressedImage(left, left_bytes, right, right_bytes, bayer_rggb8 != 0, time) ? 1 : 0;
+}
+
+unsigned long long vsfh_refused_frames(void* f) { return static_cast<Frontend*>(f)->refused_frames(); }
 int vsfh_last_status(void* f) { return (int)static_cast<Frontend*>(f)->last_status(); }
 int vsfh_num_poses(void* f) { return static_cast<Frontend*>(f)->GetNumPoses(); }
 float vsfh_stereo_ambig_constraint(void* f) { return static_cast<Frontend*>(f)->stereo_ambig_constraint(); }

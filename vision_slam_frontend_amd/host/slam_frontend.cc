@@ -561,7 +561,15 @@ void Frontend::UndistortFeaturePoints(std::vector<VisionFeature>* features_ptr) 
 // descriptors never leave HBM.  What stays here is the reference's bookkeeping (is_initial_ / initial_ids_, nodes,
 // factors, the sliding window), in the reference's order.
 bool Frontend::ObserveImageFused(const Image& left_image, const Image& right_image) {
-  if (!EnsureContext(left_image.cols, left_image.rows)) {
+  FramePayload fp;
+  fp.left = left_image.data;
+  fp.right = right_image.data;
+  fp.step = left_image.step;
+  return ObserveFused(left_image.cols, left_image.rows, fp);
+}
+
+bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
+  if (!EnsureContext(width, height)) {
     if (last_status_ == VSF_OK) last_status_ = VSF_ERR_INVALID_ARG;
     return false;
   }
@@ -570,8 +578,12 @@ bool Frontend::ObserveImageFused(const Image& left_image, const Image& right_ima
   while ((int)pending_count_ >= queue_depth())
     if (!RetireOldest()) return false;
   PendingFrame& pf = pending_[(pending_head_ + pending_count_) % pending_.size()];
-  last_status_ = vsf_observe_submit(ctx_, left_image.data, right_image.data, left_image.cols, left_image.rows,
-                                    left_image.step, &calib, config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
+  if (fp.compressed)  // (a file the host half of the decoders refuses: no ticket, nothing booked, the queue as it was)
+    last_status_ = vsf_observe_submit_compressed(ctx_, fp.left, fp.left_bytes, fp.right, fp.right_bytes, fp.bayer ? 1 : 0, &calib,
+                                                 config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
+  else
+    last_status_ = vsf_observe_submit(ctx_, fp.left, fp.right, width, height, fp.step, &calib, config_.best_percent_,
+                                      (int)config_.frame_life_, &pf.ticket);
   if (last_status_ != VSF_OK) return false;
   pf.odom_translation = odom_translation_;
   pf.odom_rotation = odom_rotation_;
@@ -609,7 +621,12 @@ bool Frontend::RetireOldest() {
   size_t bytes = 0;
   const uint8_t* b = nullptr;  // the result, read where the GPU wrote it (the context's pinned result ring)
   last_status_ = vsf_observe_collect_view(ctx_, pf.ticket, &b, &bytes);
-  if (last_status_ != VSF_OK) return false;
+  // A compressed frame whose file the DEVICE refused (header word 13) is still a frame: it was extracted as an all-zero image
+  // and is booked like any other -- a node without features -- so that the queue's window and frame_list_ stay in step;
+  // refused_frames() counts it; last_status() keeps the VSF_ERR_INVALID_ARG of its collect until the next call's status.
+  const bool refused = last_status_ == VSF_ERR_INVALID_ARG && b && bytes >= 64 && reinterpret_cast<const uint32_t*>(b)[13] != 0;
+  if (last_status_ != VSF_OK && !refused) return false;
+  if (refused) refused_frames_++;
   uint32_t hdr[16];
   std::memcpy(hdr, b, sizeof(hdr));
   const int n_pairs = (int)hdr[1], nfeat = (int)hdr[2];
@@ -665,8 +682,11 @@ bool Frontend::RetireOldest() {
   }
   if (config_.debug_images_) {  // drawn in the batch's tail (vsf_observe_set_debug_images); kept, as the reference keeps them
     const uint8_t *stereo = nullptr, *match = nullptr;
-    last_status_ = vsf_observe_debug_view(ctx_, pf.ticket, &stereo, &match);
-    if (last_status_ != VSF_OK) return false;
+    const vsf_status ds = vsf_observe_debug_view(ctx_, pf.ticket, &stereo, &match);
+    if (ds != VSF_OK) {
+      last_status_ = ds;
+      return false;
+    }
     vsf_params p;
     vsf_get_params(ctx_, &p);
     if (stereo) debug_stereo_images_.push_back(OwnedImage{std::vector<uint8_t>(stereo, stereo + (size_t)6 * p.width * p.height),
@@ -708,6 +728,35 @@ void Frontend::FinishNode(const Frame& curr_frame, const std::vector<VisionFeatu
   curr_frame_ID_++;
   if (frame_list_.size() >= config_.frame_life_ && !frame_list_.empty()) frame_list_.erase(frame_list_.begin());
   frame_list_.push_back(curr_frame);
+}
+
+// slam_frontend_main.cc:98-133 + cc:400-472: the payloads of the two sensor_msgs::CompressedImage messages as they came.
+bool Frontend::ObserveCompressedImage(const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
+                                      bool bayer_rggb8, double /*time*/) {
+  if (!OdomCheck()) return false;  // (a gated frame is not even parsed)
+  if (!fused_ || config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::ORB ||
+      config_.orb_nfeatures + 256 >= 65536 || config_.frame_life_ < 1 || config_.frame_life_ + 1 > 64) {
+    last_status_ = VSF_ERR_UNSUPPORTED;  // compressed frames exist in the queue only
+    return false;
+  }
+  int width = 0, height = 0;
+  if (ctx_) {
+    vsf_params p;
+    vsf_get_params(ctx_, &p);
+    width = p.width;
+    height = p.height;
+  } else {  // the first frame sizes the context, as the first ObserveImage does
+    last_status_ = left && right ? vsf_compressed_image_size(left, left_bytes, &width, &height) : VSF_ERR_INVALID_ARG;
+    if (last_status_ != VSF_OK) return false;
+  }
+  FramePayload fp;
+  fp.left = left;
+  fp.right = right;
+  fp.left_bytes = left_bytes;
+  fp.right_bytes = right_bytes;
+  fp.compressed = true;
+  fp.bayer = bayer_rggb8;
+  return ObserveFused(width, height, fp);
 }
 
 // cc:400-472

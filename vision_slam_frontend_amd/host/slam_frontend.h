@@ -122,6 +122,19 @@ class Frontend {
 
   // True iff a new SLAM node was added.  Never throws; a failing GPU call is reported by last_status().
   bool ObserveImage(const Image& left_image, const Image& right_image, double time);
+  // The reference's CompressedImageCallback in one call (slam_frontend_main.cc:98-133): the two messages' payloads -- JPEG
+  // (baseline or progressive) or PNG -- are decoded on the GPU inside the queue (cv::imdecode IMREAD_GRAYSCALE; with
+  // bayer_rggb8 also COLOR_BayerBG2BGR + COLOR_BGR2GRAY) and observed exactly as ObserveImage observes the decoded images,
+  // synchronous or pipelined.  OdomCheck comes first: a gated frame is not parsed.  A file the host refuses (malformed or
+  // unsupported header, another size, above the queue's byte cap) books nothing: false, last_status() says why.  A file
+  // the DEVICE refuses (broken PNG data, a JPEG stream that breaks off at a missing restart marker) is observed as an
+  // all-zero image -- a node without features (defined deviation, include/vsf.h).  refused_frames() counts such frames
+  // as they are booked and never goes back; last_status() reads VSF_ERR_INVALID_ARG right after that booking only, i.e. in
+  // synchronous mode -- a pipelined Frontend books frames inside later calls, whose own status follows at once, so there
+  // the counter is the way to learn of it.  The host keeps no copy of such a frame's pixels: with debug_images_ on,
+  // getDebugImages() / getDebugStereoImages() hold canvases drawn on the GPU from the DECODED (and demosaiced) images.
+  bool ObserveCompressedImage(const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
+                              bool bayer_rggb8, double time);
   void ObserveOdometry(const Vector3f& translation, const Quaternionf& rotation, double timestamp);
   void GetSLAMProblem(slam_types::SLAMProblem* problem) const;
   int GetNumPoses();
@@ -137,6 +150,8 @@ class Frontend {
 
   // Additions (not in the reference): error reporting instead of abort, and read access for tests.
   vsf_status last_status() const { return last_status_; }
+  // Frames booked so far whose compressed file the DEVICE refused (observed as an all-zero image); sticky.
+  uint64_t refused_frames() const { return refused_frames_; }
   // true (default): ObserveImage is one GPU submission (vsf_observe_stereo); false: one C-ABI call per reference call
   // (vsf_extract_pair, vsf_get_matches, ...) with the reference's host steps in between.  Same results; choose before
   // the first ObserveImage.
@@ -202,6 +217,13 @@ class Frontend {
                          slam_types::VisionFactor* matches_out = nullptr);
   bool EnsureContext(int width, int height);
   bool ObserveImageFused(const Image& left_image, const Image& right_image);
+  struct FramePayload {  // what a frame brings to the queue: two raw images at `step`, or two compressed files
+    const uint8_t* left = nullptr;
+    const uint8_t* right = nullptr;
+    size_t step = 0, left_bytes = 0, right_bytes = 0;
+    bool compressed = false, bayer = false;
+  };
+  bool ObserveFused(int width, int height, const FramePayload& fp);
   void FinishNode(const Frame& curr_frame, const std::vector<slam_types::VisionFeature>& features);
   // A frame the GPU is still working on, with the odometry its ObserveImage call saw (cc:444-458 reads it at the END of
   // the call; between submit and collect the driver may already have delivered the next pose).
@@ -254,6 +276,7 @@ class Frontend {
   vsf_ctx* ctx_;
   int device_;
   vsf_status last_status_;
+  uint64_t refused_frames_ = 0;
 };
 
 }  // namespace slam
