@@ -472,6 +472,19 @@ vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on);
 /* A collected frame's debug images inside the pinned debug ring (NULL where the frame has none); valid under the rule of
  * vsf_observe_collect_view (until `depth` further frames have been submitted). */
 vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match);
+/* The debug images as JPEG FILES (an addition the reference does not have; its publish loop would put them into
+ * sensor_msgs/CompressedImage): quality 1 .. 100 switches it on, 0 (the default) off.  Needs vsf_observe_set_debug_images on and
+ * follows its rules (only before the queue's first frame or after vsf_observe_reset).  With it on each batch's tail encodes the
+ * canvases it has just drawn as vsf_jpeg_encode_batch_dev does -- the files are what cv::imencode(".jpg") writes for the raw
+ * canvases -- and only the files go home, into a pinned ring of depth slots of vsf_jpeg_encode_capacity(2w, h, 3) +
+ * vsf_jpeg_encode_capacity(w, h, 3) bytes; the raw canvases stay on the device and vsf_observe_debug_view returns
+ * VSF_ERR_INVALID_ARG.  Results (header words 14 / 15 included) are those of vsf_observe_set_debug_images alone.  Off: launches,
+ * results and cost are exactly those without the call (vsf_observe_stats value 14 counts what the path launched). */
+vsf_status vsf_observe_set_debug_jpeg(vsf_ctx* ctx, int quality);
+/* A collected frame's two files inside that ring (NULL / 0 where the frame has no such image); lifetime as
+ * vsf_observe_debug_view.  VSF_ERR_CAPACITY if a file did not fit its slot (the bound of vsf_jpeg_encode_capacity rules it out). */
+vsf_status vsf_observe_debug_jpeg_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                                       const uint8_t** match, size_t* match_bytes);
 
 /* ---------------- Host checks of the compressed path (no context, no device) ----------------
  * What vsf_observe_submit_compressed computes and checks on the host, callable on their own so that tests without a GPU --
@@ -575,7 +588,33 @@ vsf_status vsf_bayer_bg_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, in
                                           size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst,
                                           size_t dst_image_stride, size_t dst_row_stride);
 
+/* The way OUT of the device for pixels: cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) as OpenCV 3.2 drives libjpeg
+ * (the reference's own instance: src/test/bag_extract.cc:90) for n equally sized images resident in HBM -- baseline, the
+ * standard tables of jpeg_set_quality(quality, TRUE), ISLOW forward DCT, the standard Huffman tables, no restart interval, a
+ * JFIF 1.01 APP0.  channels 1: one component.  channels 3: B G R in, YCbCr with 2x2 chroma subsampling out.  The FILES equal
+ * libjpeg's byte for byte.  Any width / height in 1 .. 65535 whatever the context's geometry; an image whose worst-case file
+ * (vsf_jpeg_encode_capacity) exceeds 2^31 - 1 bytes returns VSF_ERR_UNSUPPORTED.  quality 1 .. 100, 0 = 95.
+ * Image i is read at d_src + i * src_image_stride, rows src_row_stride >= width * channels bytes apart (no alignment rule;
+ * bytes between rows are never read into a file); its file is written at d_out + i * out_stride and its size to d_out_bytes[i]
+ * (DEVICE memory).  A file that does not fit out_stride sets d_out_bytes[i] = -1 and makes the next vsf_sync return
+ * VSF_ERR_CAPACITY; nothing is written outside a slot, and out_stride >= vsf_jpeg_encode_capacity() never overflows.
+ * Asynchronous on the context's stream; scratch grows without waiting for the GPU, as for the decoders. */
+size_t vsf_jpeg_encode_capacity(int width, int height, int channels); /* no context; worst case incl. stuffing; 0: bad arguments */
+vsf_status vsf_jpeg_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int channels,
+                                     size_t src_image_stride, size_t src_row_stride, int quality, uint8_t* d_out,
+                                     size_t out_stride, int32_t* d_out_bytes);
+/* The same with HOST pointers, synchronous.  out_bytes[i] = -1 and VSF_ERR_CAPACITY when file i does not fit out_stride (the
+ * other files are delivered). */
+vsf_status vsf_jpeg_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int channels,
+                           size_t src_image_stride, size_t src_row_stride, int quality, uint8_t* out, size_t out_stride,
+                           int32_t* out_bytes);
+
 /* ---------------- introspection for kernel-level parity tests and the roofline model ---------------- */
+
+/* The encoder's host half alone: every byte from SOI to the end of the SOS header (<= 640).  *n_bytes is set even when cap is
+ * short (VSF_ERR_CAPACITY).  No context, no device. */
+vsf_status vsf_debug_jpeg_encode_header(int width, int height, int channels, int quality, uint8_t* out, size_t cap,
+                                        size_t* n_bytes);
 
 /* Test hook for the error plumbing: the next entry point that launches returns VSF_ERR_HIP (vsf_last_hip_error == code),
  * as if one of its event records / waits had failed; the call after that works again. */

@@ -35,7 +35,14 @@ GEOMETRY = {
     "geometry_msgs/Quaternion": "float64 x\nfloat64 y\nfloat64 z\nfloat64 w\n",
 }
 KNOWN = {"geometry_msgs/Point": "4a842b65f413084dc2b10fb484ea7f17", "geometry_msgs/Vector3": "4a842b65f413084dc2b10fb484ea7f17",
-         "geometry_msgs/Quaternion": "a779879fadf0160734f906b8c19c7004"}
+         "geometry_msgs/Quaternion": "a779879fadf0160734f906b8c19c7004",
+         "std_msgs/Header": "2176decaecbce78abc3b96ef049fabed", "sensor_msgs/CompressedImage": "8f7a12909da2c9d3332d540a0977563f"}
+# The one message of another package the host serialises: sensor_msgs/CompressedImage (the debug images as JPEG files), with the
+# std_msgs/Header it starts with.  Field lists of ROS-1's common_msgs / std_msgs; not part of table() (the package's own nine).
+EXTERNAL = {
+    "std_msgs/Header": "uint32 seq\ntime stamp\nstring frame_id\n",
+    "sensor_msgs/CompressedImage": "Header header\nstring format\nuint8[] data\n",
+}
 NAMES = ["CameraExtrinsics", "CameraIntrinsics", "FeatureMatch", "OdometryFactor", "RobotPose", "SLAMNode", "SLAMProblem",
          "VisionFactor", "VisionFeature"]
 
@@ -43,6 +50,8 @@ NAMES = ["CameraExtrinsics", "CameraIntrinsics", "FeatureMatch", "OdometryFactor
 def msg_text(full_name: str) -> str:
     if full_name in GEOMETRY:
         return GEOMETRY[full_name]
+    if full_name in EXTERNAL:
+        return EXTERNAL[full_name]
     pkg, name = full_name.split("/")
     assert pkg == PACKAGE, full_name
     return MESSAGES[name] + "\n"
@@ -80,11 +89,18 @@ def table() -> dict:
     return {n: md5("%s/%s" % (PACKAGE, n)) for n in NAMES}
 
 
+def compressed_image_md5() -> str:
+    """md5sum of sensor_msgs/CompressedImage (slam_to_ros.h: kCompressedImageMd5)."""
+    table()
+    return md5("sensor_msgs/CompressedImage")
+
+
 if __name__ == "__main__":
     t = table()
     if "--header" in sys.argv[1:]:
         for n in NAMES:
             print('constexpr const char* kMd5%s = "%s";' % (n, t[n]))
+        print('constexpr const char* kCompressedImageMd5 = "%s";' % compressed_image_md5())
     else:
         for n in NAMES:
             print("%s  %s/%s" % (t[n], PACKAGE, n))

@@ -42,6 +42,7 @@ EXPORTS = [
     "vsf_observe_submit_compressed", "vsf_observe_stereo_compressed", "vsf_observe_set_compressed_cap",
     "vsf_observe_default_compressed_cap", "vsf_observe_compressed_slot_bytes", "vsf_observe_compressed_ring_bytes",
     "vsf_compressed_image_size", "vsf_observe_probe_compressed",
+    "vsf_observe_set_debug_jpeg", "vsf_observe_debug_jpeg_view", "vsf_jpeg_encode_capacity", "vsf_jpeg_encode_batch_dev", "vsf_jpeg_encode", "vsf_debug_jpeg_encode_header",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -101,6 +102,21 @@ class VsfError(RuntimeError):
 _lib = None
 
 
+def jpeg_encode_capacity(width: int, height: int, channels: int) -> int:
+    """Bytes that hold the JPEG file of any width x height x channels image (vsf_jpeg_encode_capacity)."""
+    return int(lib().vsf_jpeg_encode_capacity(width, height, channels))
+
+
+def jpeg_encode_header(width: int, height: int, channels: int, quality: int = 0) -> bytes:
+    """The encoder's host half: SOI .. SOS header."""
+    buf = np.zeros(640, np.uint8)
+    n = C.c_size_t()
+    st = lib().vsf_debug_jpeg_encode_header(width, height, channels, quality, buf.ctypes.data_as(C.c_void_p), 640, C.byref(n))
+    if st != VSF_OK:
+        raise VsfError(st, "vsf_debug_jpeg_encode_header")
+    return buf[:n.value].tobytes()
+
+
 def lib() -> C.CDLL:
     """Loads libvsf_hip.so; raises (loudly) if it has not been built -- there is no fallback path."""
     global _lib
@@ -153,6 +169,11 @@ def lib() -> C.CDLL:
         L.vsf_remove_ambig_stereo_batch_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.c_float, vp, vp, vp, vp, vp, vp]
         L.vsf_feature_matches_batch_dev.argtypes = [vp, vp, vp, sz, vp, vp, i32, C.c_float, vp, vp]
         L.vsf_bayer_bg_to_gray_batch_dev.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_jpeg_encode_capacity.argtypes = [i32, i32, i32]
+        L.vsf_jpeg_encode_capacity.restype = sz
+        L.vsf_jpeg_encode_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, i32, vp, sz, vp]
+        L.vsf_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, i32, vp, sz, vp]
+        L.vsf_debug_jpeg_encode_header.argtypes = [i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
         L.vsf_stereo_residuals_batch_dev.argtypes = [vp, vp, vp, vp, i32, vp, vp]
         L.vsf_stereo_thresholds_dev.argtypes = [vp, vp, i32, vp, vp]
         L.vsf_stereo_filter_batch_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
@@ -188,6 +209,8 @@ def lib() -> C.CDLL:
         L.vsf_observe_probe_compressed.argtypes = [vp, sz, i32, i32, sz, i32, ip]
         L.vsf_observe_set_debug_images.argtypes = [vp, i32]
         L.vsf_observe_debug_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
+        L.vsf_observe_set_debug_jpeg.argtypes = [vp, i32]
+        L.vsf_observe_debug_jpeg_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
         L.vsf_draw_canvases_dev.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
         L.vsf_draw_canvases.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
         L.vsf_jpeg_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
@@ -538,10 +561,10 @@ class Context:
 
     def observe_stats(self) -> dict:
         """vsf_observe_stats by name."""
-        v = np.zeros(14, np.int64)
-        self._check(lib().vsf_observe_stats(self._h, _p(v), 14), "vsf_observe_stats")
+        v = np.zeros(15, np.int64)
+        self._check(lib().vsf_observe_stats(self._h, _p(v), 15), "vsf_observe_stats")
         names = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
-                 "wait_ns", "compressed", "ingest_commands", "compressed_bytes")
+                 "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands")
         return {k: int(x) for k, x in zip(names, v)}
 
     def debug_jpeg_serial(self, on: bool):
@@ -614,6 +637,25 @@ class Context:
         if st != VSF_OK and st not in allow_status:
             raise VsfError(st, "vsf_imdecode_gray_batch", lib().vsf_last_hip_error(self._h))
         return st
+
+    def jpeg_encode_batch_dev(self, d_src: int, n_images: int, width: int, height: int, channels: int, src_image_stride: int,
+                              src_row_stride: int, quality: int, d_out: int, out_stride: int, d_out_bytes: int):
+        """cv::imencode(".jpg") of images resident in HBM: file i at d_out + i * out_stride, its size in d_out_bytes[i]."""
+        self._check(lib().vsf_jpeg_encode_batch_dev(self._h, _p(d_src), n_images, width, height, channels, src_image_stride,
+                                                    src_row_stride, quality, _p(d_out), out_stride, _p(d_out_bytes)),
+                    "vsf_jpeg_encode_batch_dev")
+
+    def jpeg_encode(self, images, quality: int = 0, out_stride: int | None = None):
+        """cv::imencode(".jpg", img, quality) of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
+        imgs = np.ascontiguousarray(np.stack([np.asarray(i) for i in images]), dtype=np.uint8)
+        n, h, w = imgs.shape[:3]
+        ch = 1 if imgs.ndim == 3 else imgs.shape[3]
+        stride = jpeg_encode_capacity(w, h, ch) if out_stride is None else out_stride
+        out = np.zeros((n, stride), np.uint8)
+        nbytes = np.zeros(n, np.int32)
+        self._check(lib().vsf_jpeg_encode(self._h, _p(imgs), n, w, h, ch, w * h * ch, w * ch, quality, _p(out), stride,
+                                          _p(nbytes)), "vsf_jpeg_encode")
+        return [out[i, :nbytes[i]].tobytes() for i in range(n)]
 
     def bayer_bg_to_gray_batch_dev(self, d_src: int, n_images: int, width: int, height: int, src_image_stride: int,
                                    src_row_stride: int, d_dst: int, dst_image_stride: int, dst_row_stride: int):

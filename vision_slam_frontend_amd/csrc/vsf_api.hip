@@ -587,6 +587,8 @@ void vsf_destroy(vsf_ctx* ctx) {
   hipFree(ctx->png_filtered);
   hipFree(ctx->png_file_status);
   hipFree(ctx->jp_clean);
+  hipFree(ctx->je_scratch);
+  hipFree(ctx->je_buf);
   hipFree(ctx->jp_coef);
   for (int i = 0; i < 2; i++) {
     if (ctx->jp_host[i]) hipHostFree(ctx->jp_host[i]);

@@ -171,6 +171,17 @@ struct vsf_ctx {
     uint8_t* h_dbg = nullptr;
     uint32_t* h_col = nullptr;
     int64_t col_ring = 0, col_generated = 0, col_retired = 0;
+    // vsf_observe_set_debug_jpeg: the canvases stay on the device; each batch's tail encodes them (k_jpeg_enc.hip) into device
+    // slots and a kernel carries the FILES into the pinned ring h_jpg [depth][jpg_slot].  A slot: i32 stereo bytes, i32 match
+    // bytes, then (16-byte aligned) the stereo file at jpg_off[0] and the match file at jpg_off[1], each with room for
+    // vsf_jpeg_encode_capacity() bytes.  h_dbg does not exist then.
+    int dbg_jpeg = 0;                 // quality the queue was built with (0: raw canvases)
+    size_t jpg_off[2] = {0, 0}, jpg_cap[2] = {0, 0}, jpg_slot = 0;
+    uint8_t* d_jpg = nullptr;         // [bmax][jpg_slot]
+    int32_t* d_jpg_n = nullptr;       // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
+    uint8_t* jpg_scratch = nullptr;   // the encoder's scratch for bmax stereo canvases
+    uint8_t* h_jpg = nullptr;
+    int64_t stat_jpeg_commands = 0;   // launches the compressed debug path issued (vsf_observe_stats)
     int depth = 0;      // frames that may be submitted and not collected
     int bmax = 0;       // frames per batch at most
     int ring = 0;       // descriptor sets [0, ring): the kept left frames (frame g in set g % ring); [ring, ring + bmax): the
@@ -229,6 +240,7 @@ struct vsf_ctx {
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
+  int ob_debug_jpeg = 0;  // vsf_observe_set_debug_jpeg: ... and hands them out as JPEG files of this quality (0: raw)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // vsf_draw_canvases(_dev) (k_draw.hip): per-pixel winners (all zero between calls: the resolve clears what it read),
   // the canvas table (device, and its host image until the upload has left: dr_uploaded), the host call's staging
@@ -257,6 +269,10 @@ struct vsf_ctx {
   size_t jp_clean_cap = 0;
   int16_t* jp_coef = nullptr;    // ... and the luminance coefficients of the batch
   size_t jp_coef_cap = 0;
+  uint8_t* je_scratch = nullptr;  // vsf_jpeg_encode_batch_dev: coefficients, bit positions, the scans before stuffing
+  size_t je_scratch_cap = 0;
+  uint8_t* je_buf = nullptr;      // vsf_jpeg_encode (host pointers): images | files | byte counts on the device
+  size_t je_buf_cap = 0;
   uint8_t* mh_desc = nullptr;  // host-API descriptor staging: 2 sets
   int32_t* mh_counts = nullptr;
   vsf_dmatch* mh_matches = nullptr;

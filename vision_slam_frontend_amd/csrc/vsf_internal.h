@@ -345,6 +345,18 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off
                             int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags, int status_stride = 0);
 // prog_serial: progressive files scan after scan in one wave; d_prog_flags [n_prog]: scratch of the pipelined form
 // status_stride (both decoders): 0 = every file reports into *d_status; 1 = file i into d_status[i] (the ObserveImage queue)
+// k_jpeg_enc.hip: the baseline JPEG encoder (cv::imencode(".jpg")).  d_scratch: vsf_jpeg_enc_scratch_bytes() bytes, 16-byte aligned.
+// out_cap: bytes a file may take of its slot (0: all out_stride of them).
+size_t vsf_jpeg_enc_scratch_bytes(int n, int width, int height, int channels, size_t out_stride);
+void vsf_launch_jpeg_encode(const uint8_t* d_src, int n, int width, int height, int channels, size_t src_image_stride,
+                            size_t src_row_stride, int quality, void* d_scratch, uint8_t* d_out, size_t out_stride,
+                            int32_t* d_out_bytes, int32_t* d_status, hipStream_t s, size_t out_cap = 0);
+// The queue's compressed debug images: file i (d_bytes[i] bytes at d_files + i * file_stride; nothing when negative) goes to
+// h_ring + ((slot0 + i) % depth) * slot_stride + file_off and its size to the i32 at that slot + 4 * which.  16 bytes per lane.
+// A frame whose result header (results + frames[i].out_slot * result_stride, word 14) lacks bit `which` has no such image: size 0.
+void vsf_launch_jpeg_files_home(const uint8_t* d_files, size_t file_stride, const int32_t* d_bytes, int n, uint8_t* h_ring,
+                                size_t slot_stride, size_t file_off, int which, int slot0, int depth, const VsfObserveFrame* frames,
+                                const uint8_t* results, size_t result_stride, hipStream_t s);
 // The queue's ingest finish (k_ingest.hip): every image of [0, n) whose status word carries bit 1 (its decoder refused the
 // data) becomes all zero, `rows` rows of `pitch` bytes.
 void vsf_launch_ingest_finish(uint8_t* d_img, size_t image_stride, int pitch, int rows, const int32_t* d_status, int n,

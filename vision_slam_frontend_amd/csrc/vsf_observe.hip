@@ -226,6 +226,10 @@ void free_observe(vsf_ctx* ctx) {
   hipFree(o.dbg_prev_kp);
   hipFree(o.dbg_ints);
   if (o.h_dbg) hipHostFree(o.h_dbg);
+  hipFree(o.d_jpg);
+  hipFree(o.d_jpg_n);
+  hipFree(o.jpg_scratch);
+  if (o.h_jpg) hipHostFree(o.h_jpg);
   if (o.h_col) hipHostFree(o.h_col);
   for (vsf_ctx::ObserveBatch& b : o.batch) {
     hipFree(b.d_img);
@@ -255,7 +259,8 @@ void launcher_thread(vsf_ctx* ctx);
 
 vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug) return VSF_OK;
+  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.dbg_jpeg == (ctx->ob_debug ? ctx->ob_debug_jpeg : 0))
+    return VSF_OK;
   sync_all_streams(ctx);
   float thr_state = 10000.0f;  // cc:353
   if (o.floats) VSF_HIP(hipMemcpy(&thr_state, o.floats + 2 * o.bmax + 1, sizeof(float), hipMemcpyDeviceToHost));
@@ -266,6 +271,7 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.bmax = std::min(o.depth, frames_cap);
   o.frame_life = frame_life;
   o.debug = ctx->ob_debug;
+  o.dbg_jpeg = o.debug ? ctx->ob_debug_jpeg : 0;
   o.ring = frame_life + o.bmax;
   o.max_pairs = o.bmax * (frame_life + 1);
   const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)o.ring + B;
@@ -305,7 +311,23 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
     VSF_HIP(hipMalloc((void**)&o.dbg_prev_kp, K * sizeof(vsf_keypoint)));
     VSF_HIP(hipMalloc((void**)&o.dbg_ints, 16));
     VSF_HIP(hipMemset(o.dbg_ints, 0, 16));
-    VSF_HIP(hipHostMalloc((void**)&o.h_dbg, (size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
+    if (o.dbg_jpeg) {  // the files leave, not the canvases: a pinned ring sized by the encoder's bound
+      const int w = ctx->p.width, h = ctx->p.height;
+      o.jpg_cap[0] = (vsf_jpeg_encode_capacity(2 * w, h, 3) + 15) & ~(size_t)15;
+      o.jpg_cap[1] = (vsf_jpeg_encode_capacity(w, h, 3) + 15) & ~(size_t)15;
+      if (o.jpg_cap[0] > 0x7FFFFFF0u) return VSF_ERR_UNSUPPORTED;
+      o.jpg_off[0] = 16;
+      o.jpg_off[1] = 16 + o.jpg_cap[0];
+      o.jpg_slot = (16 + o.jpg_cap[0] + o.jpg_cap[1] + 255) & ~(size_t)255;
+      VSF_HIP(hipMalloc((void**)&o.d_jpg, B * o.jpg_slot));
+      VSF_HIP(hipMalloc((void**)&o.d_jpg_n, (2 * B + 1) * sizeof(int32_t)));  // (+ the encoder's status word: a file that does
+      // not fit leaves its count at -1, which is what the view reports)
+      VSF_HIP(hipMemset(o.d_jpg_n, 0, (2 * B + 1) * sizeof(int32_t)));
+      VSF_HIP(hipMalloc((void**)&o.jpg_scratch, vsf_jpeg_enc_scratch_bytes((int)B, 2 * w, h, 3, o.jpg_cap[0])));
+      VSF_HIP(hipHostMalloc((void**)&o.h_jpg, (size_t)o.depth * o.jpg_slot, hipHostMallocMapped));
+    } else {
+      VSF_HIP(hipHostMalloc((void**)&o.h_dbg, (size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
+    }
     VSF_HIP(hipHostMalloc((void**)&o.h_col, (size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
   }
   for (vsf_ctx::ObserveBatch& b : o.batch) {
@@ -657,7 +679,7 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   if (o.debug) {
     // ---- the debug images (slam_frontend.cc:74-115, 167-171, 458-466) of every frame, drawn in the batch's tail from what
     // it holds in HBM, then into the frames' slots of the pinned debug ring (one copy, two when the slots wrap) ----
-    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 6);
+    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, o.dbg_jpeg ? 14 : 6);  // (4 kernels + 2 copies, or 4 + 2 x (4 encode + 1 carry))
     VsfObserveDebugArgs d;
     d.n_frames = n;
     d.max_rows = Kc;
@@ -685,11 +707,26 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
     d.out_stride = o.out_stride;
     vsf_launch_observe_debug(d, s_tail);
     const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
-    VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
-                           hipMemcpyDeviceToHost, s_tail));
-    if (first < n)
-      VSF_HIP(hipMemcpyAsync(o.h_dbg, o.dbg_canvas + (size_t)first * o.dbg_stride, (size_t)(n - first) * o.dbg_stride,
+    if (o.dbg_jpeg) {
+      // cv::imencode(".jpg") of the canvases just drawn, stereo then match (two sizes: two encodes), into the batch's device
+      // slots; then only the files' bytes cross to the pinned ring
+      const int w = ctx->p.width, h = ctx->p.height;
+      for (int which = 0; which < 2; which++) {
+        const int iw = which ? w : 2 * w;
+        vsf_launch_jpeg_encode(o.dbg_canvas + (which ? (size_t)6 * w * h : 0), n, iw, h, 3, o.dbg_stride, (size_t)3 * iw, o.dbg_jpeg,
+                               o.jpg_scratch, o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax,
+                               o.d_jpg_n + 2 * (size_t)o.bmax, s_tail, o.jpg_cap[which]);
+        vsf_launch_jpeg_files_home(o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax, n, o.h_jpg, o.jpg_slot,
+                                   o.jpg_off[which], which, slot0, o.depth, M.frames, o.h_out, o.out_stride, s_tail);
+      }
+      o.stat_jpeg_commands += 10;
+    } else {
+      VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
                              hipMemcpyDeviceToHost, s_tail));
+      if (first < n)
+        VSF_HIP(hipMemcpyAsync(o.h_dbg, o.dbg_canvas + (size_t)first * o.dbg_stride, (size_t)(n - first) * o.dbg_stride,
+                               hipMemcpyDeviceToHost, s_tail));
+    }
   }
   VSF_HIP(hipEventRecord(b.ev_done, s_tail));
   b.used = true;
@@ -828,13 +865,51 @@ vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** 
   *stereo = *match = nullptr;
   const vsf_ctx::Observe& o = ctx->ob;
   // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_collect_view)
-  if (!o.ready || !o.debug || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
-    return VSF_ERR_INVALID_ARG;
+  if (!o.ready || !o.debug || o.dbg_jpeg || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+    return VSF_ERR_INVALID_ARG;  // (with vsf_observe_set_debug_jpeg the raw canvases never leave the device)
   const int slot = (int)(ticket % o.depth);
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
   const uint8_t* base = o.h_dbg + (size_t)slot * o.dbg_stride;
   if (flags & 1) *stereo = base;
   if (flags & 2) *match = base + (size_t)6 * ctx->p.width * ctx->p.height;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_set_debug_jpeg(vsf_ctx* ctx, int quality) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || quality < 0 || quality > 100) return VSF_ERR_INVALID_ARG;
+  if (quality == ctx->ob_debug_jpeg) return VSF_OK;
+  if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
+  // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
+  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
+  if (ctx->ob.ready) stop_observe_threads(ctx);
+  ctx->ob_debug_jpeg = quality;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_debug_jpeg_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                                       const uint8_t** match, size_t* match_bytes) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !stereo || !stereo_bytes || !match || !match_bytes) return VSF_ERR_INVALID_ARG;
+  *stereo = *match = nullptr;
+  *stereo_bytes = *match_bytes = 0;
+  const vsf_ctx::Observe& o = ctx->ob;
+  if (!o.ready || !o.debug || !o.dbg_jpeg || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+    return VSF_ERR_INVALID_ARG;
+  const int slot = (int)(ticket % o.depth);
+  const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
+  const uint8_t* base = o.h_jpg + (size_t)slot * o.jpg_slot;
+  const int32_t* n = reinterpret_cast<const int32_t*>(base);
+  // (cannot happen while vsf_jpeg_encode_capacity is the bound it claims to be: a file that did not fit its slot)
+  if (((flags & 1) && n[0] < 0) || ((flags & 2) && n[1] < 0)) return VSF_ERR_CAPACITY;
+  if ((flags & 1) && n[0] > 0) {
+    *stereo = base + o.jpg_off[0];
+    *stereo_bytes = (size_t)n[0];
+  }
+  if ((flags & 2) && n[1] > 0) {
+    *match = base + o.jpg_off[1];
+    *match_bytes = (size_t)n[1];
+  }
   return VSF_OK;
 }
 
@@ -864,10 +939,11 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob_cap;
   cmp_bytes += o.ing_clean_cap + o.ing_coef_cap + o.ing_filtered_cap +
                ((size_t)o.ing_flags_cap + (size_t)o.ing_file_status_cap) * sizeof(int32_t);
-  const int64_t v[14] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
+  const int64_t v[15] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns,
-                         o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes};
-  for (int i = 0; i < n && i < 14; i++) out[i] = v[i];
+                         o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes,
+                         o.stat_jpeg_commands};
+  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
   return VSF_OK;
 }
 

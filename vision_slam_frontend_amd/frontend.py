@@ -66,6 +66,10 @@ def lib() -> C.CDLL:
         L.vsfh_set_debug_images.restype = None
         L.vsfh_num_debug_images.argtypes = [vp, i32]
         L.vsfh_debug_image.argtypes = [vp, i32, i32, vp, sz, vp]
+        L.vsfh_set_debug_jpeg_quality.argtypes = [vp, i32]
+        L.vsfh_set_debug_jpeg_quality.restype = None
+        L.vsfh_debug_image_compressed.argtypes = [vp, i32, vp, sz]
+        L.vsfh_debug_image_compressed.restype = sz
         _lib = L
     return _lib
 
@@ -83,12 +87,15 @@ def default_calibration() -> capi.VsfCalibration:
 
 class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
-                 best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False):
+                 best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
+                 debug_jpeg_quality: int = 0):
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
         if debug_images:  # FrontendConfig::debug_images_ (the reference's default is on, slam_frontend.cc:552)
             lib().vsfh_set_debug_images(self._h, 1)
+        if debug_jpeg_quality:  # FrontendConfig::debug_jpeg_quality_: the queued modes keep JPEG files instead of raw images
+            lib().vsfh_set_debug_jpeg_quality(self._h, debug_jpeg_quality)
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend")
@@ -143,6 +150,15 @@ class Frontend:
     def debug_images(self, stereo: bool = False):
         """getDebugImages() (stereo: getDebugStereoImages()) as rows x cols x 3 arrays, bytes in OpenCV's B, G, R order."""
         return [self._debug_image(stereo, i) for i in range(lib().vsfh_num_debug_images(self._h, int(stereo)))]
+
+    def last_debug_image_compressed(self, stereo: bool = False):
+        """GetLastDebugImageCompressed() (stereo: GetLastDebugStereoImageCompressed()) as bytes; None when there is none."""
+        n = lib().vsfh_debug_image_compressed(self._h, int(stereo), None, 0)
+        if not n:
+            return None
+        out = np.zeros(n, np.uint8)
+        lib().vsfh_debug_image_compressed(self._h, int(stereo), _p(out), n)
+        return out.tobytes()
 
     def last_debug_image(self, stereo: bool = False):
         """GetLastDebugImage() (stereo: GetLastDebugStereoImage()); None for the reference's empty cv::Mat."""

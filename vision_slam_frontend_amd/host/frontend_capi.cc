@@ -166,6 +166,15 @@ int vsfh_debug_image(void* f, int stereo, int i, uint8_t* out, size_t cap, int r
   return 1;
 }
 
+void vsfh_set_debug_jpeg_quality(void* f, int quality) { static_cast<Frontend*>(f)->set_debug_jpeg_quality(quality); }
+// GetLastDebugImageCompressed / GetLastDebugStereoImageCompressed: the file's size (0: none); min(size, cap) bytes into out.
+size_t vsfh_debug_image_compressed(void* f, int stereo, uint8_t* out, size_t cap) {
+  Frontend* fe = static_cast<Frontend*>(f);
+  const Frontend::CompressedView v = stereo ? fe->GetLastDebugStereoImageCompressed() : fe->GetLastDebugImageCompressed();
+  if (out && v.size) std::memcpy(out, v.data, v.size < cap ? v.size : cap);
+  return v.size;
+}
+
 void vsfh_frontend_destroy(void* f) { delete static_cast<Frontend*>(f); }
 
 void vsfh_observe_odometry(void* f, const float t[3], const float q_wxyz[4], double ts) {

@@ -122,6 +122,7 @@ FrontendConfig::FrontendConfig() {
   // reference: true (cc:552; quirk Q10: it retains every image forever).  Off here so that nothing is drawn or kept unless
   // asked for; on, the images are the reference's byte for byte (drawn on the GPU, csrc/k_draw.hip).
   debug_images_ = false;
+  debug_jpeg_quality_ = 0;
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
   descriptor_extract_type_ = DescriptorExtractorType::ORB;
   best_percent_ = 0.3f;
@@ -273,6 +274,8 @@ bool Frontend::EnsureContext(int width, int height) {
   if (last_status_ == VSF_OK) last_status_ = vsf_observe_configure(ctx_, ctx_depth_, min_batch_, 0);
   // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
   if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
+  if (last_status_ == VSF_OK && config_.debug_images_ && config_.debug_jpeg_quality_ > 0)
+    last_status_ = vsf_observe_set_debug_jpeg(ctx_, config_.debug_jpeg_quality_);
   pending_.assign((size_t)ctx_depth_, PendingFrame());
   pending_head_ = pending_count_ = 0;
   return last_status_ == VSF_OK;
@@ -680,7 +683,17 @@ bool Frontend::RetireOldest() {
     right_temp_frame.frame_ID_ = curr_frame_ID_;
     book(right_temp_frame, &curr_frame, pair_bytes[n_pairs - 1], npairs[n_pairs - 1], nullptr);
   }
-  if (config_.debug_images_) {  // drawn in the batch's tail (vsf_observe_set_debug_images); kept, as the reference keeps them
+  if (config_.debug_images_ && config_.debug_jpeg_quality_ > 0) {  // encoded in the batch's tail (vsf_observe_set_debug_jpeg)
+    const uint8_t *stereo = nullptr, *match = nullptr;
+    size_t stereo_bytes = 0, match_bytes = 0;
+    const vsf_status ds = vsf_observe_debug_jpeg_view(ctx_, pf.ticket, &stereo, &stereo_bytes, &match, &match_bytes);
+    if (ds != VSF_OK) {
+      last_status_ = ds;
+      return false;
+    }
+    if (stereo) debug_stereo_files_.emplace_back(stereo, stereo + stereo_bytes);
+    if (match) debug_files_.emplace_back(match, match + match_bytes);
+  } else if (config_.debug_images_) {  // drawn in the batch's tail (vsf_observe_set_debug_images); kept, as the reference keeps them
     const uint8_t *stereo = nullptr, *match = nullptr;
     const vsf_status ds = vsf_observe_debug_view(ctx_, pf.ticket, &stereo, &match);
     if (ds != VSF_OK) {
@@ -813,6 +826,29 @@ void Frontend::set_debug_images(bool on) {
   }
   config_.debug_images_ = on;
   if (ctx_) last_status_ = vsf_observe_set_debug_images(ctx_, on ? 1 : 0);
+}
+
+void Frontend::set_debug_jpeg_quality(int quality) {
+  if (!nodes_.empty() || pending_count_ > 0 || quality < 0 || quality > 100) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  config_.debug_jpeg_quality_ = quality;
+  if (ctx_ && (config_.debug_images_ || quality == 0)) last_status_ = vsf_observe_set_debug_jpeg(ctx_, quality);
+}
+
+Frontend::CompressedView Frontend::GetLastDebugImageCompressed() {
+  Flush();
+  CompressedView v;
+  if (!debug_files_.empty()) v.data = debug_files_.back().data(), v.size = debug_files_.back().size();
+  return v;
+}
+
+Frontend::CompressedView Frontend::GetLastDebugStereoImageCompressed() {
+  Flush();
+  CompressedView v;
+  if (!debug_stereo_files_.empty()) v.data = debug_stereo_files_.back().data(), v.size = debug_stereo_files_.back().size();
+  return v;
 }
 
 std::vector<Image> Frontend::getDebugImages() {

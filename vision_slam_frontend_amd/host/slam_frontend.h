@@ -73,6 +73,10 @@ struct FrontendConfig {
   enum class DescriptorExtractorType { AKAZE, ORB, BRISK, SURF, SIFT, FREAK };
   FrontendConfig();
   bool debug_images_;
+  // An addition the reference does not have: 1 .. 100 makes the queued modes keep the debug images as JPEG files of that quality
+  // (what cv::imencode(".jpg") writes for them; vsf_observe_set_debug_jpeg) INSTEAD of the raw images -- the raw getters below
+  // then return nothing.  0 (the default): raw images.  Ignored in per-call mode.
+  int debug_jpeg_quality_;
   DescriptorExtractorType descriptor_extract_type_;
   float best_percent_;
   float nn_match_ratio_;
@@ -147,6 +151,14 @@ class Frontend {
   Image GetLastDebugImage();
   Image GetLastDebugStereoImage();
   std::vector<Image> getDebugStereoImages();
+  // The newest match / stereo image as a JPEG file (config.debug_jpeg_quality_ > 0, queued modes): the payload of a
+  // sensor_msgs/CompressedImage with format "jpeg" (slam_to_ros.h).  {nullptr, 0} when there is none.  Valid while the object lives.
+  struct CompressedView {
+    const uint8_t* data = nullptr;
+    size_t size = 0;
+  };
+  CompressedView GetLastDebugImageCompressed();
+  CompressedView GetLastDebugStereoImageCompressed();
 
   // Additions (not in the reference): error reporting instead of abort, and read access for tests.
   vsf_status last_status() const { return last_status_; }
@@ -167,6 +179,7 @@ class Frontend {
   void set_pipelined(bool on) { pipelined_ = on; }
   // config.debug_images_ after construction (before the first ObserveImage; later calls fail with VSF_ERR_INVALID_ARG).
   void set_debug_images(bool on);
+  void set_debug_jpeg_quality(int quality);  // config.debug_jpeg_quality_, under the same rule
   // Frames ObserveImage may leave in the queue when pipelined (1..1024, default 256) and the most frames one batch carries
   // (default 128; the context's extraction buffers are sized for it: ~25 MB of HBM per 640x480 frame; the queue's staging
   // and result rings are pinned host memory: depth x (two images + vsf_observe_capacity)).  Measured on an MI355X at
@@ -265,6 +278,7 @@ class Frontend {
   // The reference keeps this in a file-static shared by all instances (cc:353, quirk Q3); here it is per object.
   float stereo_ambig_constraint_;
   std::vector<OwnedImage> debug_images_, debug_stereo_images_;  // cc h:202-203: kept for the object's lifetime
+  std::vector<std::vector<uint8_t>> debug_files_, debug_stereo_files_;  // ... or their JPEG files (debug_jpeg_quality_)
   bool fused_;
   bool pipelined_;
   int depth_ = 256, batch_frames_ = 128, min_batch_ = 0;

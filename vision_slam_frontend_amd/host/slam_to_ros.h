@@ -28,6 +28,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "slam_types.h"
@@ -43,6 +44,10 @@ constexpr const char* kMd5SLAMNode = "0e51780741a149812c832d6ae619d556";
 constexpr const char* kMd5SLAMProblem = "a5ec5d26ada8532dd747269f672dd5f8";
 constexpr const char* kMd5VisionFactor = "da3820cf3e135bcd0b601cacc8cf0809";
 constexpr const char* kMd5VisionFeature = "9cccef6835ecad8ee3bfb40a17ba67fb";
+
+// sensor_msgs/CompressedImage (another package's message: the debug images as JPEG files, Frontend::GetLastDebugImageCompressed),
+// computed by the same tool from ROS-1's field lists (std_msgs/Header header, string format, uint8[] data).
+constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 
 class Writer {
  public:
@@ -190,6 +195,57 @@ inline void SerializeSLAMProblem(const slam_types::SLAMProblem& p, std::vector<u
   for (const auto& c : p.vision_factors) Write(&w, c);
   w.u32((uint32_t)p.odometry_factors.size());
   for (const auto& o : p.odometry_factors) Write(&w, o);
+}
+
+// One sensor_msgs/CompressedImage with format "jpeg" (what image_transport's compressed publisher sends for a JPEG file):
+//   Header   uint32 seq, time stamp (uint32 secs, uint32 nsecs), string frame_id (uint32 length + bytes)
+//   string format, uint8[] data (uint32 length + bytes)                                  24 + |frame_id| + |format| + n B
+inline void SerializeCompressedImage(uint32_t seq, uint32_t stamp_secs, uint32_t stamp_nsecs, const std::string& frame_id,
+                                     const uint8_t* file, size_t file_bytes, std::vector<uint8_t>* out,
+                                     const std::string& format = "jpeg") {
+  out->clear();
+  out->reserve(24 + frame_id.size() + format.size() + file_bytes);
+  Writer w(out);
+  w.u32(seq);
+  w.u32(stamp_secs);
+  w.u32(stamp_nsecs);
+  w.u32((uint32_t)frame_id.size());
+  out->insert(out->end(), frame_id.begin(), frame_id.end());
+  w.u32((uint32_t)format.size());
+  out->insert(out->end(), format.begin(), format.end());
+  w.u32((uint32_t)file_bytes);
+  out->insert(out->end(), file, file + file_bytes);
+}
+
+// The way back (a subscriber's view of the payload): false when the payload is not one whole message.
+struct CompressedImageView {
+  uint32_t seq = 0, stamp_secs = 0, stamp_nsecs = 0;
+  std::string frame_id, format;
+  const uint8_t* data = nullptr;
+  size_t size = 0;
+};
+inline bool ParseCompressedImage(const uint8_t* msg, size_t n, CompressedImageView* v) {
+  size_t p = 0;
+  auto u32 = [&](uint32_t* x) {
+    if (n - p < 4) return false;
+    std::memcpy(x, msg + p, 4);
+    p += 4;
+    return true;
+  };
+  auto str = [&](std::string* s) {
+    uint32_t len;
+    if (!u32(&len) || n - p < len) return false;
+    s->assign(reinterpret_cast<const char*>(msg + p), len);
+    p += len;
+    return true;
+  };
+  uint32_t len;
+  if (!u32(&v->seq) || !u32(&v->stamp_secs) || !u32(&v->stamp_nsecs) || !str(&v->frame_id) || !str(&v->format) || !u32(&len) ||
+      n - p != len)
+    return false;
+  v->data = msg + p;
+  v->size = len;
+  return true;
 }
 
 inline size_t SerializedSize(const slam_types::SLAMProblem& p) {
