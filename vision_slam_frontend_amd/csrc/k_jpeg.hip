@@ -1528,16 +1528,29 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(const DevImage* __restric
   }
 }
 
-}  // namespace
-
 // Bytes of the parallel decoder's stream scratch: the clean streams in the layout of the upload's stream part, then
 // their segment-major copies.
-size_t vsf_jpeg_clean_bytes(size_t stream_bytes, int n_par) {
+size_t clean_bytes(size_t stream_bytes, int n_par) {
   const size_t linear = (stream_bytes + 64 + 255) & ~(size_t)255;
   return n_par > 0 ? 2 * linear + (size_t)n_par * kTransSlack : linear;
 }
 
-size_t vsf_jpeg_prog_huff_bytes(int n_tables) { return (size_t)n_tables * sizeof(DevHuffLite); }
+// Bytes of one file's slot in the coefficient buffer: every luminance block of the largest padded image, written whole.
+size_t coef_slot_bytes(const VsfJpegPlan& p) { return (size_t)p.max_luma_blocks * 64 * sizeof(int16_t); }
+
+}  // namespace
+
+// The scratch of one upload.  Files without restart intervals (what a camera driver writes) take the self-synchronising
+// parallel decode: it needs the de-stuffed streams and, as the progressive files do, the luminance coefficients in HBM.  The
+// expanded Huffman tables of progressive scans live behind the coefficients.
+VsfDecodeNeed vsf_jpeg_scratch_need(const VsfJpegPlan& p) {
+  VsfDecodeNeed need;
+  if (p.n_par > 0) need.clean = clean_bytes(p.total - p.off_stream, p.n_par);
+  if (p.n_par + p.n_prog > 0)
+    need.coef = (size_t)(p.n_par + p.n_prog) * coef_slot_bytes(p) + (size_t)p.n_prog_huff * sizeof(DevHuffLite);
+  need.flags = (size_t)p.n_prog * sizeof(int32_t);
+  return need;
+}
 
 // The parallel decoder's static + dynamic LDS exceed the default 64 KB for colour files: raised (checked) at vsf_create.
 hipError_t vsf_prepare_jpeg_kernels(int lds_limit) {
@@ -1547,48 +1560,51 @@ hipError_t vsf_prepare_jpeg_kernels(int lds_limit) {
 }
 
 // Both decoders over one upload: the files without restart intervals (n_par of them, listed first in the index array
-// at off_index) take the self-synchronising parallel decode, the others the one-wave-per-image decode.  d_clean has
-// vsf_jpeg_clean_bytes(total - off_stream, n_par) bytes, d_coef holds n_par * coef_stride bytes (coef_stride = 128 * luminance blocks of the
-// largest padded image): every luminance block is written whole.
-void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off_index, size_t off_tables, size_t off_scans,
-                            size_t off_prog_huff, size_t off_stream, size_t total, int n_par, int n_prog, int n_prog_huff,
-                            void* d_prog_huff, int n_ser, int max_luma_blocks, int max_slots, int width, int height,
-                            uint8_t* d_clean,
-                            int16_t* d_coef, size_t coef_stride, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
-                            int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags, int status_stride) {
-  const DevImage* images = reinterpret_cast<const DevImage*>(d_blob + off_images);
-  const DevTables* tables = reinterpret_cast<const DevTables*>(d_blob + off_tables);
-  const uint32_t* index = reinterpret_cast<const uint32_t*>(d_blob + off_index);
+// at off_index) take the self-synchronising parallel decode, the progressive ones follow, the others take the
+// one-wave-per-image decode.  `scratch` holds what vsf_jpeg_scratch_need(p) asks for.
+void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, int width, int height,
+                            const VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
+                            int32_t* d_status, int status_stride, bool prog_serial, hipStream_t s) {
+  const int n_par = p.n_par, n_prog = p.n_prog, n_ser = n - n_par - n_prog;
+  const size_t coef_stride = coef_slot_bytes(p);
+  int16_t* d_coef = scratch.coef;
+  DevHuffLite* d_prog_huff = reinterpret_cast<DevHuffLite*>(reinterpret_cast<uint8_t*>(d_coef) + (size_t)(n_par + n_prog) * coef_stride);
+  const DevImage* images = reinterpret_cast<const DevImage*>(d_blob + p.off_images);
+  const DevTables* tables = reinterpret_cast<const DevTables*>(d_blob + p.off_tables);
+  const uint32_t* index = reinterpret_cast<const uint32_t*>(d_blob + p.off_index);
+  const DevScan* scans = reinterpret_cast<const DevScan*>(d_blob + p.off_scans);
+  const uint8_t* stream = d_blob + p.off_stream;
+  const size_t stream_bytes = p.total - p.off_stream;
   if (n_par > 0) {
     // (static + dynamic LDS exceed 64 KB for colour files: vsf_prepare_jpeg_kernels raised the limit at vsf_create)
-    hipLaunchKernelGGL(jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads), (size_t)max_slots * sizeof(DevHuff), s, images, index, tables, d_blob + off_stream,
-                       reinterpret_cast<uint32_t*>(d_clean),
-                       reinterpret_cast<uint32_t*>(d_clean + vsf_jpeg_clean_bytes(total - off_stream, 0)), d_coef, coef_stride,
-                       max_slots, d_status, status_stride);
+    hipLaunchKernelGGL(jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads), (size_t)p.max_slots * sizeof(DevHuff), s, images, index, tables, stream,
+                       reinterpret_cast<uint32_t*>(scratch.clean),
+                       reinterpret_cast<uint32_t*>(scratch.clean + clean_bytes(stream_bytes, 0)), d_coef, coef_stride,
+                       p.max_slots, d_status, status_stride);
   }
   if (n_prog > 0) {  // progressive files: their slots of the coefficient buffer follow the parallel decoder's
-    if (n_prog_huff > 0)
-      hipLaunchKernelGGL(jpeg_expand_huff_kernel, dim3(n_prog_huff), dim3(64), 0, s,
-                         reinterpret_cast<const DevHuffSrc*>(d_blob + off_prog_huff), static_cast<DevHuffLite*>(d_prog_huff));
+    if (p.n_prog_huff > 0)
+      hipLaunchKernelGGL(jpeg_expand_huff_kernel, dim3(p.n_prog_huff), dim3(64), 0, s,
+                         reinterpret_cast<const DevHuffSrc*>(d_blob + p.off_prog_huff), d_prog_huff);
     const int32_t* only = nullptr;
     // The pipelined form pays while the CUs' scalar units have slots left: 256 files per call 7.1 k images/s against 3.7 k
     // scan after scan, 512 files 11.5 against 7.1 k, 768 files 14.9 against 10.3 k; from ~1000 files on the one-wave form
     // fills the scalar units by itself (1024: 13.1 / 13.3 k, 1536: 12.1 / 15.8 k, 2048: 13.5 / 16.7 k).
-    if (!prog_serial && d_prog_flags && n_prog <= kProgPipeMaxFiles) {
-      hipLaunchKernelGGL(jpeg_prog_pipe_kernel, dim3(n_prog), dim3(64 * kProgWaves), 0, s, images, index + n_par,
-                         reinterpret_cast<const DevScan*>(d_blob + off_scans), static_cast<const DevHuffLite*>(d_prog_huff),
-                         d_blob + off_stream, d_coef, coef_stride, n_par, width, height, d_prog_flags);
-      only = d_prog_flags;  // (the one-wave kernel below then repeats the files that kernel flagged, and no others)
+    if (!prog_serial && scratch.flags && n_prog <= kProgPipeMaxFiles) {
+      hipLaunchKernelGGL(jpeg_prog_pipe_kernel, dim3(n_prog), dim3(64 * kProgWaves), 0, s, images, index + n_par, scans,
+                         static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, width, height,
+                         scratch.flags);
+      only = scratch.flags;  // (the one-wave kernel below then repeats the files that kernel flagged, and no others)
     }
-    hipLaunchKernelGGL(jpeg_prog_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par,
-                       reinterpret_cast<const DevScan*>(d_blob + off_scans), static_cast<const DevHuffLite*>(d_prog_huff),
-                       d_blob + off_stream, d_coef, coef_stride, n_par, width, height, d_status, status_stride, only);
+    hipLaunchKernelGGL(jpeg_prog_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par, scans,
+                       static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, width, height, d_status,
+                       status_stride, only);
   }
   if (n_par + n_prog > 0)
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((max_luma_blocks + 7) / 8, n_par + n_prog), dim3(64), 0, s, images, index, tables,
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((p.max_luma_blocks + 7) / 8, n_par + n_prog), dim3(64), 0, s, images, index, tables,
                        d_coef, coef_stride, width, height, d_dst, dst_image_stride, dst_pitch);
   if (n_ser > 0)
-    hipLaunchKernelGGL(jpeg_gray_kernel, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, d_blob + off_stream,
-                       (uint32_t)((total - off_stream) & ~(size_t)3), width, height, d_dst, dst_image_stride, dst_pitch,
+    hipLaunchKernelGGL(jpeg_gray_kernel, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, stream,
+                       (uint32_t)(stream_bytes & ~(size_t)3), width, height, d_dst, dst_image_stride, dst_pitch,
                        d_status, status_stride);
 }

@@ -1367,17 +1367,26 @@ __global__ __launch_bounds__(64) void png_unfilter_rgb_kernel(PngArgs a) {
 
 }  // namespace
 
-void vsf_launch_png_decode(const uint8_t* d_blob, size_t off_images, size_t off_pieces, size_t off_tables, size_t off_stream, int n, int width, int height,
-                           uint8_t* d_filtered, size_t filtered_stride, int32_t* d_file_status, uint8_t* d_dst,
-                           size_t dst_image_stride, int dst_pitch, int32_t* d_status, bool any_general, bool any_rgb, hipStream_t s, int status_stride) {
+VsfDecodeNeed vsf_png_scratch_need(const VsfPngPlan& p, int n) {
+  VsfDecodeNeed need;
+  need.filtered = p.filtered_stride * (size_t)n;
+  need.file_status = (size_t)n * sizeof(int32_t);
+  return need;
+}
+
+// Inflate, then the filters: the gray kernel always, the palette / interlace and the colour kernels when the run has such files.
+// `scratch` holds what vsf_png_scratch_need(p, n) asks for.
+void vsf_launch_png_decode(const uint8_t* d_blob, const VsfPngPlan& p, int n, int width, int height,
+                           const VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
+                           int32_t* d_status, int status_stride, hipStream_t s) {
   PngArgs a;
   a.blob = d_blob;
-  a.off_images = off_images;
-  a.off_pieces = off_pieces;
-  a.off_tables = off_tables;
-  a.off_stream = off_stream;
-  a.filtered = d_filtered;
-  a.filtered_stride = filtered_stride;
+  a.off_images = p.off_images;
+  a.off_pieces = p.off_pieces;
+  a.off_tables = p.off_tables;
+  a.off_stream = p.off_stream;
+  a.filtered = scratch.filtered;
+  a.filtered_stride = p.filtered_stride;
   a.width = width;
   a.height = height;
   a.dst = d_dst;
@@ -1385,11 +1394,11 @@ void vsf_launch_png_decode(const uint8_t* d_blob, size_t off_images, size_t off_
   a.dst_pitch = dst_pitch;
   a.status = d_status;
   a.status_stride = status_stride;
-  a.file_status = d_file_status;
+  a.file_status = scratch.file_status;
   hipLaunchKernelGGL(png_inflate_kernel, dim3(n), dim3(64), 0, s, a);
   hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(64), 0, s, a);
-  if (any_general) hipLaunchKernelGGL(png_unfilter_general_kernel, dim3(n), dim3(64), 0, s, a);
-  if (any_rgb) hipLaunchKernelGGL(png_unfilter_rgb_kernel, dim3(n), dim3(64), 0, s, a);
+  if (p.any_general) hipLaunchKernelGGL(png_unfilter_general_kernel, dim3(n), dim3(64), 0, s, a);
+  if (p.any_rgb) hipLaunchKernelGGL(png_unfilter_rgb_kernel, dim3(n), dim3(64), 0, s, a);
 }
 
 #ifdef VSF_PNG_STATS

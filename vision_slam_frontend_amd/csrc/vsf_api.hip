@@ -583,18 +583,10 @@ void vsf_destroy(vsf_ctx* ctx) {
   hipFree(ctx->dr_canv);
   hipFree(ctx->dr_buf);
   if (ctx->dr_uploaded) hipEventDestroy(ctx->dr_uploaded);
-  hipFree(ctx->jp_flags);
-  hipFree(ctx->png_filtered);
-  hipFree(ctx->png_file_status);
-  hipFree(ctx->jp_clean);
   hipFree(ctx->je_scratch);
   hipFree(ctx->je_buf);
-  hipFree(ctx->jp_coef);
-  for (int i = 0; i < 2; i++) {
-    if (ctx->jp_host[i]) hipHostFree(ctx->jp_host[i]);
-    hipFree(ctx->jp_dev[i]);
-    if (ctx->jp_copied[i]) hipEventDestroy(ctx->jp_copied[i]);
-  }
+  free_decode_buffers(ctx->ingest_scratch);
+  for (VsfStaging& stage : ctx->ingest_stage) free_decode_buffers(stage);
   free_retired(ctx);
   hipFree(ctx->v_pairs);
   hipFree(ctx->v_npairs);

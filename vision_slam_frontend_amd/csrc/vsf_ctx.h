@@ -138,10 +138,9 @@ struct vsf_ctx {
     int32_t* nmatches = nullptr;     // [bmax]
     int32_t* status = nullptr;       // [2 bmax] a status word per image
     ObserveBatchMeta* h_meta = nullptr;
-    // compressed frames: the batch's ONE upload (every run's headers / tables / entropy-coded or IDAT bytes), pinned + device
-    uint8_t* h_blob = nullptr;
-    uint8_t* d_blob = nullptr;
-    size_t blob_cap = 0;
+    // compressed frames: the batch's ONE upload (every run's headers / tables / entropy-coded or IDAT bytes); free once the
+    // slot's previous batch has left the GPU (ev_done)
+    VsfStaging blob;
     hipEvent_t ev_uploaded = nullptr, ev_extracted = nullptr, ev_done = nullptr;
     bool used = false;               // ev_done has been recorded at least once
     hipStream_t done_stream = nullptr;  // the stream its tail ran on
@@ -150,7 +149,7 @@ struct vsf_ctx {
     vsf_calibration calib;
     float best_percent = 0.f;
     int batch = -1;  // batch slot it was launched in, -1 while it waits
-    uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, 1 a JPEG file, 2 a PNG file in h_cmp
+    uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, else VSF_FILE_JPEG / VSF_FILE_PNG: a file in h_cmp
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
     bool bayer = false;          // compressed frames: the decoded images are bayer_rggb8 mosaics
   };
@@ -209,16 +208,7 @@ struct vsf_ctx {
     uint8_t* h_cmp = nullptr;       // pinned [depth][2][cmp_slot] the files as submitted
     size_t cmp_cap = 0, cmp_slot = 0;  // bytes a file may have / bytes of its slot (vsf_observe_compressed_slot_bytes)
     uint8_t* d_bayer = nullptr;     // [2 bmax] images at the staging pitch: the decoded mosaics of a Bayer batch
-    uint8_t* ing_clean = nullptr;   // the JPEG decoders' scratch (as vsf_ctx::jp_clean / jp_coef / jp_flags) ...
-    size_t ing_clean_cap = 0;
-    int16_t* ing_coef = nullptr;
-    size_t ing_coef_cap = 0;
-    int32_t* ing_flags = nullptr;
-    int ing_flags_cap = 0;
-    uint8_t* ing_filtered = nullptr;  // ... and the PNG decoder's (png_filtered / png_file_status)
-    size_t ing_filtered_cap = 0;
-    int32_t* ing_file_status = nullptr;
-    int ing_file_status_cap = 0;
+    VsfDecodeScratch ing_scratch;   // the decoders' scratch on the copy stream
     int64_t stat_compressed = 0;    // compressed frames launched
     int64_t stat_ingest_commands = 0;  // copy commands + launches the compressed path issued
     size_t out_cap = 0, out_stride = 0;
@@ -252,23 +242,12 @@ struct vsf_ctx {
   hipEvent_t dr_uploaded = nullptr;
   uint8_t* dr_buf = nullptr;
   size_t dr_buf_cap = 0;
-  // vsf_jpeg_decode_gray_batch: pinned staging + device copy of the packed headers / tables / entropy-coded segments
-  // (two sets, used alternately: the host fills one while the previous call's upload / decode still use the other)
-  int32_t* jp_flags = nullptr;  // [jp_flags_cap] per progressive file of a call: damaged, decode again scan after scan
-  int jp_flags_cap = 0;
-  uint8_t* jp_host[2] = {nullptr, nullptr};
-  uint8_t* jp_dev[2] = {nullptr, nullptr};
-  size_t jp_cap[2] = {0, 0};
-  hipEvent_t jp_copied[2] = {nullptr, nullptr};  // the last upload out of jp_host[i] has finished
-  int jp_flip = 0;
-  uint8_t* png_filtered = nullptr;  // PNG: the inflated scanlines of a batch
-  size_t png_filtered_cap = 0;
-  int32_t* png_file_status = nullptr;
-  int png_file_status_cap = 0;
-  uint8_t* jp_clean = nullptr;   // parallel decode: the de-stuffed streams (layout of the upload's stream part)
-  size_t jp_clean_cap = 0;
-  int16_t* jp_coef = nullptr;    // ... and the luminance coefficients of the batch
-  size_t jp_coef_cap = 0;
+  // vsf_jpeg_decode_gray_batch / vsf_png_decode_gray_batch: two staging pairs, used alternately (the host fills one while the
+  // previous call's upload / decode still use the other; `uploaded`: the last upload out of the pair has finished), and the
+  // decoders' scratch on the context's stream
+  VsfStaging ingest_stage[2];
+  int ingest_flip = 0;
+  VsfDecodeScratch ingest_scratch;
   uint8_t* je_scratch = nullptr;  // vsf_jpeg_encode_batch_dev: coefficients, bit positions, the scans before stuffing
   size_t je_scratch_cap = 0;
   uint8_t* je_buf = nullptr;      // vsf_jpeg_encode (host pointers): images | files | byte counts on the device
@@ -344,6 +323,17 @@ vsf_status grow_scratch(vsf_ctx* ctx, T*& ptr, size_t bytes) {
   return VSF_OK;
 }
 void free_retired(vsf_ctx* ctx);  // (callers have waited for every stream of the context)
+// vsf_ingest.hip: the ONE way compressed files reach the device and are decoded there.  Files [0, n) of `kinds` (VSF_FILE_*;
+// VSF_FILE_NONE: not a file, its image is left alone) are planned run by run of one format, `stage` and `scratch` are grown to
+// the largest need without waiting for the GPU (a quarter of headroom; what is outgrown is retired), every run is filled at
+// its offset of the staging pair, ONE upload goes out on `s` and each run's decoder is launched behind it: image i at
+// d_dst + i * dst_image_stride, file i's damage in d_status[i * status_stride].  *n_runs (optional): the runs launched.
+// Which staging pair is free is the caller's business (VsfStaging::uploaded).  The caller checks for launch errors.
+vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width,
+                       int height, VsfStaging& stage, VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride,
+                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs = nullptr);
+void free_decode_buffers(VsfStaging& stage);  // (the GPU has left them)
+void free_decode_buffers(VsfDecodeScratch& scratch);
 vsf_status ensure_match_buffers(vsf_ctx* ctx, int pairs, int rows);
 vsf_status ensure_match_host_staging(vsf_ctx* ctx, int rows);  // (host-pointer, synchronous entry points only)
 vsf_status ensure_residual_buffers(vsf_ctx* ctx, int n_frames);

@@ -1,11 +1,59 @@
-// vsf_ingest_host.cc -- what vsf_observe_submit_compressed does with a payload before anything is booked: the staging
-// ring's sizes, the format by the file's first bytes (as cv::imdecode's findDecoder does), the per-file byte cap and the
-// decoder's own host checks (vsf_jpeg_plan / vsf_png_plan of the ONE file: every marker, table and chunk length).  The
-// bytes are UNTRUSTED (slam_frontend_main.cc:98-100 hands cv::imdecode whatever the topic carried).  Plain C++, no HIP call:
-// the same translation unit is part of the sanitizer build (make asan) and needs no device.
+// vsf_ingest_host.cc -- the host half of "decode these files on the device", shared by the C ABI's decoders and the
+// ObserveImage queue: the format by the file's first bytes (as cv::imdecode's findDecoder does), the runs of one format in a
+// list of files, the plan of ONE upload for all of them (vsf_jpeg_plan / vsf_png_plan per run: every marker, table and chunk
+// length) and its fill.  And what vsf_observe_submit_compressed does with a payload before anything is booked: the staging
+// ring's sizes, the per-file byte cap and the same plan for the ONE file.  The bytes are UNTRUSTED (slam_frontend_main.cc:98-100
+// hands cv::imdecode whatever the topic carried).  Plain C++, no HIP call: the same translation unit is part of the sanitizer
+// build (make asan) and needs no device.
 #include <cstring>
 
 #include "vsf_internal.h"
+#include "vsf_png_host.h"
+
+int vsf_file_kind(const uint8_t* file, size_t nbytes) {
+  if (!file) return VSF_FILE_NONE;
+  if (nbytes >= 8 && std::memcmp(file, vsf_png::kSignature, 8) == 0) return VSF_FILE_PNG;
+  if (nbytes >= 3 && file[0] == 0xFF && file[1] == 0xD8 && file[2] == 0xFF) return VSF_FILE_JPEG;  // (SOI + a marker)
+  return VSF_FILE_NONE;  // (imdecode's other formats -- BMP, TIFF, WebP ... -- are not built)
+}
+
+int vsf_run_end(const uint8_t* kinds, int n, int i0) {
+  int i1 = i0 + 1;
+  while (i1 < n && kinds[i1] == kinds[i0]) ++i1;
+  return i1;
+}
+
+// Every run of JPEG or PNG files among files [0, n) planned as one upload of its own, the uploads one after the other at
+// 256-byte-aligned offsets of ONE blob of out->total bytes.  The first refusal of a decoder's host half is returned as it is.
+vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
+                         bool force_serial, VsfDecodeRuns* out) {
+  out->runs.clear();
+  out->total = 0;
+  for (int i0 = 0, i1; i0 < n; i0 = i1) {
+    i1 = vsf_run_end(kinds, n, i0);
+    if (kinds[i0] == VSF_FILE_NONE) continue;
+    out->runs.emplace_back();
+    VsfDecodeRun& r = out->runs.back();
+    r.i0 = i0;
+    r.n = i1 - i0;
+    r.kind = kinds[i0];
+    r.off = (out->total + 255) & ~(size_t)255;
+    const vsf_status st = r.kind == VSF_FILE_JPEG ? vsf_jpeg_plan(files + i0, nbytes + i0, r.n, width, height, force_serial, &r.jp)
+                                                  : vsf_png_plan(files + i0, nbytes + i0, r.n, width, height, &r.pp);
+    if (st != VSF_OK) return st;
+    out->total = r.off + (r.kind == VSF_FILE_JPEG ? r.jp.total : r.pp.total);
+  }
+  return VSF_OK;
+}
+
+void vsf_fill_runs(const VsfDecodeRuns& plan, const uint8_t* const* files, uint8_t* dst) {
+  for (const VsfDecodeRun& r : plan.runs) {
+    if (r.kind == VSF_FILE_JPEG)
+      vsf_jpeg_fill(r.jp, files + r.i0, r.n, dst + r.off);
+    else
+      vsf_png_fill(r.pp, files + r.i0, r.n, dst + r.off);
+  }
+}
 
 extern "C" {
 
@@ -29,15 +77,15 @@ size_t vsf_observe_compressed_ring_bytes(int depth, size_t cap_per_image) {
 // Width and height as the file's header states them (PNG: IHDR; JPEG: the first SOF0 / SOF1 / SOF2 segment); nothing else
 // of the file is looked at or promised -- the submit's checks follow.
 vsf_status vsf_compressed_image_size(const uint8_t* file, size_t nbytes, int* width, int* height) {
-  static const uint8_t kPng[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
   if (!file || !width || !height) return VSF_ERR_INVALID_ARG;
   *width = *height = 0;
   uint32_t w = 0, h = 0;
-  if (nbytes >= 8 && std::memcmp(file, kPng, 8) == 0) {
+  const int kind = vsf_file_kind(file, nbytes);
+  if (kind == VSF_FILE_PNG) {
     if (nbytes < 24 || std::memcmp(file + 12, "IHDR", 4) != 0) return VSF_ERR_INVALID_ARG;
     w = ((uint32_t)file[16] << 24) | ((uint32_t)file[17] << 16) | ((uint32_t)file[18] << 8) | file[19];
     h = ((uint32_t)file[20] << 24) | ((uint32_t)file[21] << 16) | ((uint32_t)file[22] << 8) | file[23];
-  } else if (nbytes >= 3 && file[0] == 0xFF && file[1] == 0xD8 && file[2] == 0xFF) {
+  } else if (kind == VSF_FILE_JPEG) {
     size_t pos = 2;
     while (pos + 4 <= nbytes) {
       if (file[pos] != 0xFF) return VSF_ERR_INVALID_ARG;
@@ -67,27 +115,14 @@ vsf_status vsf_compressed_image_size(const uint8_t* file, size_t nbytes, int* wi
 
 vsf_status vsf_observe_probe_compressed(const uint8_t* file, size_t nbytes, int width, int height, size_t cap_per_image,
                                         int force_serial, int* kind) {
-  static const uint8_t kPng[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-  if (kind) *kind = 0;
+  if (kind) *kind = VSF_FILE_NONE;
   if (!file || width < 1 || height < 1 || width > 65535 || height > 65535) return VSF_ERR_INVALID_ARG;
-  int k = 0;
-  if (nbytes >= 8 && std::memcmp(file, kPng, 8) == 0)
-    k = 2;
-  else if (nbytes >= 3 && file[0] == 0xFF && file[1] == 0xD8 && file[2] == 0xFF)
-    k = 1;
-  if (k == 0) return VSF_ERR_UNSUPPORTED;  // (imdecode's other formats -- BMP, TIFF, WebP ... -- are not built)
+  const uint8_t k = (uint8_t)vsf_file_kind(file, nbytes);
+  if (k == VSF_FILE_NONE) return VSF_ERR_UNSUPPORTED;
   if (nbytes > cap_per_image || nbytes > 0x40000000u) return VSF_ERR_CAPACITY;
-  const uint8_t* files[1] = {file};
-  const size_t sizes[1] = {nbytes};
-  vsf_status st;
-  if (k == 1) {
-    if (nbytes < 4) return VSF_ERR_INVALID_ARG;
-    VsfJpegPlan plan;
-    st = vsf_jpeg_plan(files, sizes, 1, width, height, force_serial != 0, &plan);
-  } else {
-    VsfPngPlan plan;
-    st = vsf_png_plan(files, sizes, 1, width, height, &plan);
-  }
+  if (k == VSF_FILE_JPEG && nbytes < 4) return VSF_ERR_INVALID_ARG;
+  VsfDecodeRuns plan;
+  const vsf_status st = vsf_plan_runs(&file, &nbytes, &k, 1, width, height, force_serial != 0, &plan);
   if (st == VSF_OK && kind) *kind = k;
   return st;
 }

@@ -332,19 +332,59 @@ struct VsfPngPlan {  // layout of one upload: [image descriptors | ends of the I
 vsf_status vsf_png_plan(const uint8_t* const* png, const size_t* nbytes, int n, int width, int height, VsfPngPlan* plan);
 void vsf_png_fill(const VsfPngPlan& plan, const uint8_t* const* png, int n, uint8_t* dst);
 #endif
-void vsf_launch_png_decode(const uint8_t* d_blob, size_t off_images, size_t off_pieces, size_t off_tables, size_t off_stream, int n, int width, int height,
-                           uint8_t* d_filtered, size_t filtered_stride, int32_t* d_file_status, uint8_t* d_dst,
-                           size_t dst_image_stride, int dst_pitch, int32_t* d_status, bool any_general, bool any_rgb, hipStream_t s, int status_stride = 0);
-size_t vsf_jpeg_clean_bytes(size_t stream_bytes, int n_par);
-size_t vsf_jpeg_prog_huff_bytes(int n_tables);  // device scratch for the expanded tables of progressive scans
-void vsf_launch_jpeg_decode(const uint8_t* d_blob, size_t off_images, size_t off_index, size_t off_tables, size_t off_scans,
-                            size_t off_prog_huff, size_t off_stream, size_t total, int n_par, int n_prog, int n_prog_huff,
-                            void* d_prog_huff, int n_ser, int max_luma_blocks, int max_slots, int width, int height,
-                            uint8_t* d_clean,
-                            int16_t* d_coef, size_t coef_stride, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
-                            int32_t* d_status, hipStream_t s, bool prog_serial, int32_t* d_prog_flags, int status_stride = 0);
-// prog_serial: progressive files scan after scan in one wave; d_prog_flags [n_prog]: scratch of the pipelined form
-// status_stride (both decoders): 0 = every file reports into *d_status; 1 = file i into d_status[i] (the ObserveImage queue)
+// ---- one decode path for compressed payloads (the C ABI's decoders and the ObserveImage queue) ----
+// What the decode kernels of ONE stream need beside the upload.  Grown by decode_runs (vsf_ingest.hip), never shrunk; the
+// capacities are bytes.
+struct VsfDecodeScratch {
+  uint8_t* clean = nullptr;        // JPEG, parallel decode: the de-stuffed streams and their segment-major copies
+  int16_t* coef = nullptr;         // JPEG: luminance coefficients, then the expanded Huffman tables of progressive scans
+  int32_t* flags = nullptr;        // JPEG: per progressive file "damaged: decode again scan after scan"
+  uint8_t* filtered = nullptr;     // PNG: the inflated scanlines
+  int32_t* file_status = nullptr;  // PNG: per file, what its inflate made of the stream
+  size_t clean_cap = 0, coef_cap = 0, flags_cap = 0, filtered_cap = 0, file_status_cap = 0;
+  size_t bytes() const { return clean_cap + coef_cap + flags_cap + filtered_cap + file_status_cap; }
+};
+struct VsfDecodeNeed {  // bytes of each; the needs of several runs on one stream combine by maximum
+  size_t clean = 0, coef = 0, flags = 0, filtered = 0, file_status = 0;
+};
+// Pinned staging + its device copy for ONE upload.  `uploaded` (optional): recorded behind the upload, and waited for before
+// the host writes the pair again -- an owner that knows the pair to be free by other means leaves it null.
+struct VsfStaging {
+  uint8_t* h = nullptr;
+  uint8_t* d = nullptr;
+  size_t cap = 0;
+  hipEvent_t uploaded = nullptr;
+};
+// Each launcher owns everything derived from its plan: offsets into the upload, strides and positions inside the scratch,
+// which kernels a run takes.  `n` files of width x height land at d_dst + i * dst_image_stride.
+// status_stride: 0 = every file reports into *d_status; 1 = file i into d_status[i] (the ObserveImage queue).
+// prog_serial: progressive files scan after scan in one wave (otherwise the pipelined form up to its file limit).
+VsfDecodeNeed vsf_jpeg_scratch_need(const VsfJpegPlan& plan);
+VsfDecodeNeed vsf_png_scratch_need(const VsfPngPlan& plan, int n);
+void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& plan, int n, int width, int height,
+                            const VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
+                            int32_t* d_status, int status_stride, bool prog_serial, hipStream_t s);
+void vsf_launch_png_decode(const uint8_t* d_blob, const VsfPngPlan& plan, int n, int width, int height,
+                           const VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
+                           int32_t* d_status, int status_stride, hipStream_t s);
+
+// vsf_ingest_host.cc (plain C++, no HIP call): what a list of files is, and the host half of decoding it.
+enum { VSF_FILE_NONE = 0, VSF_FILE_JPEG = 1, VSF_FILE_PNG = 2 };  // (ObserveFrame::kind: 0 is the raw frame there)
+int vsf_file_kind(const uint8_t* file, size_t nbytes);  // by the first bytes, as cv::imdecode's findDecoder tells them apart
+int vsf_run_end(const uint8_t* kinds, int n, int i0);   // one past the last file of the run of one kind that starts at i0
+struct VsfDecodeRun {  // files [i0, i0 + n) of one format; its upload starts `off` bytes (a multiple of 256) into the blob
+  int i0 = 0, n = 0, kind = VSF_FILE_NONE;
+  size_t off = 0;
+  VsfJpegPlan jp;  // (the one of `kind`)
+  VsfPngPlan pp;
+};
+struct VsfDecodeRuns {
+  std::vector<VsfDecodeRun> runs;  // in file order; files of kind VSF_FILE_NONE belong to none
+  size_t total = 0;                // bytes of the ONE upload
+};
+vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
+                         bool force_serial, VsfDecodeRuns* out);
+void vsf_fill_runs(const VsfDecodeRuns& plan, const uint8_t* const* files, uint8_t* dst);
 // k_jpeg_enc.hip: the baseline JPEG encoder (cv::imencode(".jpg")).  d_scratch: vsf_jpeg_enc_scratch_bytes() bytes, 16-byte aligned.
 // out_cap: bytes a file may take of its slot (0: all out_stride of them).
 size_t vsf_jpeg_enc_scratch_bytes(int n, int width, int height, int channels, size_t out_stride);

@@ -214,11 +214,7 @@ void free_observe(vsf_ctx* ctx) {
   if (o.h_out) hipHostFree(o.h_out);
   if (o.h_cmp) hipHostFree(o.h_cmp);
   hipFree(o.d_bayer);
-  hipFree(o.ing_clean);
-  hipFree(o.ing_coef);
-  hipFree(o.ing_flags);
-  hipFree(o.ing_filtered);
-  hipFree(o.ing_file_status);
+  free_decode_buffers(o.ing_scratch);
   hipFree(o.dbg_canvas);
   hipFree(o.dbg_win);
   hipFree(o.dbg_ops);
@@ -240,8 +236,7 @@ void free_observe(vsf_ctx* ctx) {
     hipFree(b.nmatches);
     hipFree(b.status);
     if (b.h_meta) hipHostFree(b.h_meta);
-    if (b.h_blob) hipHostFree(b.h_blob);
-    hipFree(b.d_blob);
+    free_decode_buffers(b.blob);
     if (b.ev_uploaded) hipEventDestroy(b.ev_uploaded);
     if (b.ev_extracted) hipEventDestroy(b.ev_extracted);
     if (b.ev_done) hipEventDestroy(b.ev_done);
@@ -391,131 +386,37 @@ vsf_status ensure_compressed(vsf_ctx* ctx, bool bayer) {
   return VSF_OK;
 }
 
-// A scratch buffer of the queue's decoders grown without waiting for the GPU (grow_scratch: the outgrown one is retired).
-template <class T, class N>
-vsf_status grow_ingest(vsf_ctx* ctx, T*& ptr, N& cap, size_t need, size_t unit) {
-  if (need <= (size_t)cap * unit) return VSF_OK;
-  const size_t want = need + need / 4;
-  const vsf_status st = grow_scratch(ctx, ptr, want);
-  if (st != VSF_OK) return st;
-  cap = (N)(want / unit);
-  return VSF_OK;
-}
-
-// The compressed frames of batch [t0, t0 + n): the host half of the decoders over every run of one format among the
-// batch's 2n images (as vsf_imdecode_gray_batch walks a list of files), ONE upload for all of them, the decode kernels on
-// `s` with a status word per image (b.status: damage lands on its own image), BayerBG -> gray for bayer_rggb8 frames, and
-// the ingest finish: an image its decoder refused becomes all zero.  Raw frames of the batch have been copied already.
+// The compressed frames of batch [t0, t0 + n): the batch's 2n images go through decode_runs (vsf_ingest.hip) on `s` -- ONE
+// upload for every run of one format among them, a status word per image (b.status: damage lands on its own image) --, then
+// BayerBG -> gray for bayer_rggb8 frames, and the ingest finish: an image its decoder refused becomes all zero.  Raw frames of
+// the batch have been copied already.
 vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s) {
   vsf_ctx::Observe& o = ctx->ob;
   const int w = ctx->p.width, h = ctx->p.height, N = 2 * n;
   const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
   std::vector<const uint8_t*> files((size_t)N);
   std::vector<size_t> sizes((size_t)N);
-  std::vector<int> kind((size_t)N);
+  std::vector<uint8_t> kinds((size_t)N);
   for (int i = 0; i < N; i++) {
     const int slot = (int)((t0 + i / 2) % o.depth);
     const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
-    kind[i] = fr.kind[i & 1];
+    kinds[i] = fr.kind[i & 1];
     files[i] = o.h_cmp + ((size_t)slot * 2 + (size_t)(i & 1)) * o.cmp_slot;
     sizes[i] = fr.nbytes[i & 1];
   }
-  struct Run {
-    int i0, n, kind;
-    size_t off;
-    VsfJpegPlan jp;
-    VsfPngPlan pp;
-  };
-  std::vector<Run> runs;
-  size_t total = 0, clean_need = 0, coef_need = 0, filtered_need = 0;
-  int flags_need = 0, png_need = 0;
-  for (int i0 = 0; i0 < N;) {
-    int i1 = i0 + 1;
-    while (i1 < N && kind[i1] == kind[i0]) ++i1;
-    if (kind[i0] != 0) {
-      runs.emplace_back();
-      Run& r = runs.back();
-      r.i0 = i0;
-      r.n = i1 - i0;
-      r.kind = kind[i0];
-      r.off = total;
-      vsf_status st;
-      if (r.kind == 1) {
-        st = vsf_jpeg_plan(files.data() + i0, sizes.data() + i0, r.n, w, h, ctx->tuning.jpeg_serial != 0, &r.jp);
-        if (st != VSF_OK) return st;  // (every file passed this at its submit)
-        total += (r.jp.total + 255) & ~(size_t)255;
-        if (r.jp.n_par + r.jp.n_prog > 0) {
-          const size_t coef_stride = (size_t)r.jp.max_luma_blocks * 64 * sizeof(int16_t);
-          if (r.jp.n_par > 0) clean_need = std::max(clean_need, vsf_jpeg_clean_bytes(r.jp.total - r.jp.off_stream, r.jp.n_par));
-          coef_need = std::max(coef_need, (size_t)(r.jp.n_par + r.jp.n_prog) * coef_stride + vsf_jpeg_prog_huff_bytes(r.jp.n_prog_huff));
-        }
-        flags_need = std::max(flags_need, r.jp.n_prog);
-      } else {
-        st = vsf_png_plan(files.data() + i0, sizes.data() + i0, r.n, w, h, &r.pp);
-        if (st != VSF_OK) return st;
-        total += (r.pp.total + 255) & ~(size_t)255;
-        filtered_need = std::max(filtered_need, r.pp.filtered_stride * (size_t)r.n);
-        png_need = std::max(png_need, r.n);
-      }
-    }
-    i0 = i1;
-  }
-  if (runs.empty()) return VSF_OK;
-  if (total > b.blob_cap) {  // (no wait: the slot's previous batch has left the GPU, but hipFree would wait for the device)
-    const size_t cap = total + total / 4 + 4096;
-    void *host = nullptr, *dev = nullptr;
-    VSF_HIP(hipHostMalloc(&host, cap, hipHostMallocDefault));
-    if (hipMalloc(&dev, cap) != hipSuccess) {
-      hipHostFree(host);
-      (void)hipGetLastError();
-      return VSF_ERR_HIP;
-    }
-    if (b.h_blob) ctx->retired_host.push_back(b.h_blob);
-    if (b.d_blob) ctx->retired.push_back(b.d_blob);
-    b.h_blob = static_cast<uint8_t*>(host);
-    b.d_blob = static_cast<uint8_t*>(dev);
-    b.blob_cap = cap;
-  }
-  vsf_status st = grow_ingest(ctx, o.ing_clean, o.ing_clean_cap, clean_need, 1);
-  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_coef, o.ing_coef_cap, coef_need, 1);
-  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_flags, o.ing_flags_cap, (size_t)flags_need * sizeof(int32_t), sizeof(int32_t));
-  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_filtered, o.ing_filtered_cap, filtered_need, 1);
-  if (st == VSF_OK) st = grow_ingest(ctx, o.ing_file_status, o.ing_file_status_cap, (size_t)png_need * sizeof(int32_t), sizeof(int32_t));
-  if (st != VSF_OK) return st;
-  for (const Run& r : runs) {
-    if (r.kind == 1)
-      vsf_jpeg_fill(r.jp, files.data() + r.i0, r.n, b.h_blob + r.off);
-    else
-      vsf_png_fill(r.pp, files.data() + r.i0, r.n, b.h_blob + r.off);
-  }
-  VSF_HIP(hipMemcpyAsync(b.d_blob, b.h_blob, total, hipMemcpyHostToDevice, s));
-  // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
-  o.stat_ingest_commands += 2 + (int64_t)runs.size() + (bayer ? 1 : 0);
-  uint8_t* dst = bayer ? o.d_bayer : b.d_img;
   const size_t stride = ctx->st_img_stride;
   const int pitch = (int)ctx->st_img_pitch;
-  for (const Run& r : runs) {
-    const uint8_t* blob = b.d_blob + r.off;
-    uint8_t* d = dst + (size_t)r.i0 * stride;
-    if (r.kind == 1) {
-      const VsfJpegPlan& p = r.jp;
-      const size_t coef_stride = (size_t)p.max_luma_blocks * 64 * sizeof(int16_t);
-      vsf_launch_jpeg_decode(blob, p.off_images, p.off_index, p.off_tables, p.off_scans, p.off_prog_huff, p.off_stream, p.total,
-                             p.n_par, p.n_prog, p.n_prog_huff,
-                             reinterpret_cast<uint8_t*>(o.ing_coef) + (size_t)(p.n_par + p.n_prog) * coef_stride,
-                             r.n - p.n_par - p.n_prog, p.max_luma_blocks, p.max_slots, w, h, o.ing_clean, o.ing_coef, coef_stride, d,
-                             stride, pitch, b.status + r.i0, s, ctx->tuning.jpeg_serial != 0, o.ing_flags, 1);
-    } else {
-      const VsfPngPlan& p = r.pp;
-      vsf_launch_png_decode(blob, p.off_images, p.off_pieces, p.off_tables, p.off_stream, r.n, w, h, o.ing_filtered,
-                            p.filtered_stride, o.ing_file_status, d, stride, pitch, b.status + r.i0, p.any_general, p.any_rgb, s,
-                            1);
-    }
-  }
+  int runs = 0;
+  // (every file passed the decoders' host half at its submit; b.blob is free: the slot's previous batch has left the GPU)
+  const vsf_status st = decode_runs(ctx, files.data(), sizes.data(), kinds.data(), N, w, h, b.blob, o.ing_scratch,
+                                    bayer ? o.d_bayer : b.d_img, stride, pitch, b.status, 1, s, &runs);
+  if (st != VSF_OK || runs == 0) return st;
   // bayer_rggb8 (slam_frontend_main.cc:101-109): every image of such a batch is a decoded mosaic
   if (bayer) vsf_launch_bayer_bg_gray(o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
   vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
-  for (int f = 0; f < n; f++) o.stat_compressed += kind[2 * f] != 0;
+  // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
+  o.stat_ingest_commands += 2 + runs + (bayer ? 1 : 0);
+  for (int f = 0; f < n; f++) o.stat_compressed += kinds[2 * f] != VSF_FILE_NONE;
   return VSF_OK;
 }
 
@@ -936,9 +837,8 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   // every byte the compressed path owns: 0 until the first compressed frame
   size_t cmp_bytes = o.h_cmp ? vsf_observe_compressed_ring_bytes(o.depth, o.cmp_cap) : 0;
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
-  for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob_cap;
-  cmp_bytes += o.ing_clean_cap + o.ing_coef_cap + o.ing_filtered_cap +
-               ((size_t)o.ing_flags_cap + (size_t)o.ing_file_status_cap) * sizeof(int32_t);
+  for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
+  cmp_bytes += o.ing_scratch.bytes();
   const int64_t v[15] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns,
                          o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes,

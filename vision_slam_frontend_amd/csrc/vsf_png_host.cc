@@ -61,8 +61,6 @@ uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {  // slicing by
 
 uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
-const uint8_t kSignature[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-
 struct Piece {
   uint32_t off, len;
 };

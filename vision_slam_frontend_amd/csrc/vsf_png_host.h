@@ -7,6 +7,8 @@
 
 namespace vsf_png {
 
+constexpr uint8_t kSignature[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};  // the first bytes of every PNG file
+
 struct DevImage {
   uint32_t stream_off;   // the zlib stream (the IDAT payloads in file order) inside the packed stream buffer, 4-byte aligned
   uint32_t stream_len;
