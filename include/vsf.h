@@ -485,6 +485,19 @@ vsf_status vsf_observe_set_debug_jpeg(vsf_ctx* ctx, int quality);
  * vsf_observe_debug_view.  VSF_ERR_CAPACITY if a file did not fit its slot (the bound of vsf_jpeg_encode_capacity rules it out). */
 vsf_status vsf_observe_debug_jpeg_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
                                        const uint8_t** match, size_t* match_bytes);
+/* The debug images as PNG FILES, lossless: on != 0 switches it on.  The rules of vsf_observe_set_debug_jpeg word for word (needs
+ * vsf_observe_set_debug_images; only before the queue's first frame or after vsf_observe_reset): each batch's tail encodes the
+ * canvases it has just drawn as vsf_png_encode_batch_dev does -- the files are what cv::imencode(".png") writes for the raw
+ * canvases, so every byte of a canvas survives -- and only the files go home, into a pinned ring of depth slots of
+ * vsf_png_encode_capacity(2w, h, 3) + vsf_png_encode_capacity(w, h, 3) bytes; the raw canvases stay on the device and
+ * vsf_observe_debug_view returns VSF_ERR_INVALID_ARG.  Mutually exclusive with the JPEG form: whichever is asked for second
+ * returns VSF_ERR_INVALID_ARG.  Results (header words 14 / 15 included) are those of vsf_observe_set_debug_images alone.  Off:
+ * launches, results and cost are exactly those without the call (vsf_observe_stats value 14 counts what either path launched). */
+vsf_status vsf_observe_set_debug_png(vsf_ctx* ctx, int on);
+/* A collected frame's two PNG files inside that ring (NULL / 0 where the frame has no such image); lifetime as
+ * vsf_observe_debug_view.  VSF_ERR_CAPACITY if a file did not fit its slot (the bound of vsf_png_encode_capacity rules it out). */
+vsf_status vsf_observe_debug_png_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                                      const uint8_t** match, size_t* match_bytes);
 
 /* ---------------- Host checks of the compressed path (no context, no device) ----------------
  * What vsf_observe_submit_compressed computes and checks on the host, callable on their own so that tests without a GPU --
@@ -609,7 +622,36 @@ vsf_status vsf_jpeg_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int w
                            size_t src_image_stride, size_t src_row_stride, int quality, uint8_t* out, size_t out_stride,
                            int32_t* out_bytes);
 
+/* The lossless way out: cv::imencode(".png", img) without parameters as OpenCV 3.2 drives libpng 1.6 and zlib 1.2.11 (filter Sub,
+ * compression level 1, strategy Z_RLE, png_set_bgr) for n equally sized images resident in HBM -- 8 bits, no interlace, IDAT
+ * chunks of 8192 bytes.  channels 1: gray, colour type 0.  channels 3: B G R in memory, colour type 2 (R G B) in the file.  The
+ * FILES equal libpng's byte for byte, the window bits of small images and the filter type 0 of images one pixel wide included.
+ * Any width / height in 1 .. 65535 whatever the context's geometry; an image whose worst-case file (vsf_png_encode_capacity)
+ * exceeds 2^31 - 1 bytes returns VSF_ERR_UNSUPPORTED.
+ * Image i is read at d_src + i * src_image_stride, rows src_row_stride >= width * channels bytes apart (no alignment rule;
+ * bytes between rows are never read); its file is written at d_out + i * out_stride and its size to d_out_bytes[i] (DEVICE
+ * memory).  A file that does not fit out_stride sets d_out_bytes[i] = -1 and makes the next vsf_sync return VSF_ERR_CAPACITY;
+ * nothing is written outside a slot, and out_stride >= vsf_png_encode_capacity() never overflows.
+ * Asynchronous on the context's stream; scratch grows without waiting for the GPU, as for the decoders. */
+size_t vsf_png_encode_capacity(int width, int height, int channels); /* no context; every block stored + chunk framing; 0: bad arguments */
+vsf_status vsf_png_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int channels,
+                                    size_t src_image_stride, size_t src_row_stride, uint8_t* d_out, size_t out_stride,
+                                    int32_t* d_out_bytes);
+/* The same with HOST pointers, synchronous.  out_bytes[i] = -1 and VSF_ERR_CAPACITY when file i does not fit out_stride (the
+ * other files are delivered). */
+vsf_status vsf_png_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int channels,
+                          size_t src_image_stride, size_t src_row_stride, uint8_t* out, size_t out_stride, int32_t* out_bytes);
+
 /* ---------------- introspection for kernel-level parity tests and the roofline model ---------------- */
+
+/* The PNG encoder's host half alone: the signature and the IHDR chunk (33 bytes), then the two header bytes of the zlib stream
+ * (which follow the first IDAT's length and type in a file) -- 35 bytes.  *n_bytes is set even when cap is short
+ * (VSF_ERR_CAPACITY).  No context, no device. */
+vsf_status vsf_debug_png_encode_header(int width, int height, int channels, uint8_t* out, size_t cap, size_t* n_bytes);
+/* The whole PNG encoder on the CPU, serially, from the same per-block code the kernels run: what tests without a GPU compare with
+ * the real library.  VSF_ERR_CAPACITY when the file does not fit cap.  No context, no device. */
+vsf_status vsf_debug_png_encode_cpu(const uint8_t* src, int width, int height, int channels, size_t src_row_stride, uint8_t* out,
+                                    size_t cap, size_t* n_bytes);
 
 /* The encoder's host half alone: every byte from SOI to the end of the SOS header (<= 640).  *n_bytes is set even when cap is
  * short (VSF_ERR_CAPACITY).  No context, no device. */

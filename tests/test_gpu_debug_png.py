@@ -1,0 +1,178 @@
+"""vsf_observe_set_debug_png: the queue's debug images leave as PNG files, lossless.  Every frame's two files must be what
+cv::imencode(".png") -- the system's libpng driven as OpenCV 3.2 drives it, tests/png_enc_ref.py -- writes for the RAW canvases
+an identical run with vsf_observe_set_debug_images alone returns (and decode back to them); every result byte (header words
+14 / 15 included) is unchanged; a frame without an image has no file; the JPEG and PNG switches refuse each other; with the
+switch off nothing more is launched than without the call.  Then the same bytes through slam::Frontend in queued mode."""
+import sys
+import zlib
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import png_enc_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+if not ref.available():
+    pytest.skip("libpng16.so.16 cannot be loaded", allow_module_level=True)
+
+W, H, NF, LIFE, SEED = 320, 240, 500, 3, 11
+F_RECT = np.float32([0, 0, 0, 0, 0, -1, 0, 1, 0])
+
+
+@pytest.fixture(scope="module")
+def frames():
+    from vision_slam_frontend_amd import synth
+    sc = synth.Scene(W, H)
+    fr = [(sc.render(f, 0), sc.render(f, 1)) for f in range(5)]
+    fr[2] = (fr[2][0], np.zeros_like(fr[2][1]))  # an empty right image: no stereo match, so no stereo image for this frame
+    return fr
+
+
+def _run(frames, depth, images, png):
+    """png: None = the call is never made.  -> (results, raw canvases or files per frame, stats)"""
+    from vision_slam_frontend_amd import capi, frontend
+    calib = frontend.default_calibration().set("fundamental", F_RECT.reshape(9))
+    L = capi.lib()
+    with capi.Context(capi.default_params(W, H, max_images=2 * depth, nfeatures=NF), device=0) as ctx:
+        ctx.observe_configure(depth=depth)
+        ctx.profile_enable(True)  # (the per-stage launch counts of vsf_profile_read)
+        # the stereo lines' colours come from the process's rand(), drawn at submit: seeded once the context exists (the HIP
+        # runtime's own start-up, which the first context of a process triggers, does not leave rand() where it was)
+        assert ctx.sync() == capi.VSF_OK
+        C.CDLL("libc.so.6").srand(SEED)
+        if images:
+            assert L.vsf_observe_set_debug_images(ctx._h, 1) == capi.VSF_OK
+        if png is not None:
+            assert L.vsf_observe_set_debug_png(ctx._h, png) == capi.VSF_OK
+        cap = L.vsf_observe_capacity(ctx._h, LIFE)
+        outs, pics = [], []
+        for g0 in range(0, len(frames), depth):
+            tickets = []
+            for left, right in frames[g0:g0 + depth]:
+                t = C.c_int64()
+                assert L.vsf_observe_submit(ctx._h, left.ctypes.data, right.ctypes.data, W, H, W, C.byref(calib), C.c_float(0.3),
+                                            LIFE, C.byref(t)) == capi.VSF_OK
+                tickets.append(t.value)
+            for t in tickets:
+                buf = np.zeros(cap, np.uint8)
+                n = C.c_size_t()
+                assert L.vsf_observe_collect(ctx._h, t, buf.ctypes.data, cap, C.byref(n)) == capi.VSF_OK
+                outs.append(buf[:n.value].copy())
+            for t in tickets:
+                s_, m_, sn, mn = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+                if png:
+                    assert L.vsf_observe_debug_png_view(ctx._h, t, C.byref(s_), C.byref(sn), C.byref(m_), C.byref(mn)) == capi.VSF_OK
+                    assert bool(s_.value) == (sn.value > 0) and bool(m_.value) == (mn.value > 0)
+                    pics.append((C.string_at(s_.value, sn.value) if s_.value else None,
+                                 C.string_at(m_.value, mn.value) if m_.value else None))
+                    assert L.vsf_observe_debug_view(ctx._h, t, C.byref(s_), C.byref(m_)) == capi.VSF_ERR_INVALID_ARG
+                    assert L.vsf_observe_debug_jpeg_view(ctx._h, t, C.byref(s_), C.byref(sn), C.byref(m_),
+                                                         C.byref(mn)) == capi.VSF_ERR_INVALID_ARG
+                elif images:
+                    assert L.vsf_observe_debug_view(ctx._h, t, C.byref(s_), C.byref(m_)) == capi.VSF_OK
+                    pics.append((np.frombuffer(C.string_at(s_.value, 6 * W * H), np.uint8).reshape(H, 2 * W, 3) if s_.value else None,
+                                 np.frombuffer(C.string_at(m_.value, 3 * W * H), np.uint8).reshape(H, W, 3) if m_.value else None))
+                    assert L.vsf_observe_debug_png_view(ctx._h, t, C.byref(s_), C.byref(sn), C.byref(m_),
+                                                        C.byref(mn)) == capi.VSF_ERR_INVALID_ARG
+        if png:  # the window holds frames: the switch no longer moves
+            assert L.vsf_observe_set_debug_png(ctx._h, 0) == capi.VSF_ERR_INVALID_ARG
+        stats = ctx.observe_stats()
+        stats["launches"] = {k: v[1] for k, v in ctx.profile_read().items()}
+        return outs, pics, stats
+
+
+def _pixels(png, w):
+    """The canvas a PNG file of this encoder holds: inflate, undo Sub, R G B -> B G R."""
+    raw = np.frombuffer(zlib.decompress(ref.idat(png)), np.uint8).reshape(H, 1 + 3 * w)
+    assert (raw[:, 0] == 1).all()
+    return np.cumsum(raw[:, 1:].reshape(H, w, 3).astype(np.int64), axis=1).astype(np.uint8)[:, :, ::-1]
+
+
+@pytest.mark.parametrize("depth", [1, 4, 32])
+def test_files_equal_the_reference_encode_of_the_raw_canvases(frames, depth):
+    raw_out, canvases, raw_stats = _run(frames, depth, True, None)
+    png_out, files, stats = _run(frames, depth, True, 1)
+    assert len(files) == len(canvases) == len(frames)
+    # the shape of the raw run: the first frame has no match image, the frame with the empty right image no stereo image (nor has
+    # the one behind it: its threshold is the NaN of a frame without stereo matches) -- and the others have both
+    assert canvases[0][1] is None and canvases[2][0] is None
+    assert canvases[0][0] is not None and canvases[4][0] is not None and all(c[1] is not None for c in canvases[1:])
+    for i, ((cs, cm), (fs, fm)) in enumerate(zip(canvases, files)):
+        assert (fs is None) == (cs is None) and (fm is None) == (cm is None), i  # NULL / 0 where a frame has no image
+        if cs is not None:
+            assert fs == ref.imencode(cs), "stereo file of frame %d" % i
+            assert np.array_equal(_pixels(fs, 2 * W), cs)  # lossless: every byte of the canvas
+        if cm is not None:
+            assert fm == ref.imencode(cm), "match file of frame %d" % i
+            assert np.array_equal(_pixels(fm, W), cm)
+    for a, b in zip(raw_out, png_out):  # header words 14 / 15 and every other result byte
+        assert a.tobytes() == b.tobytes()
+    # twenty launches per batch (two encodes of nine, two carries) on top of the raw run's, which in turn has two copy commands
+    # per batch that this one has not
+    assert stats["debug_jpeg_commands"] == 20 * stats["batches"] > 0
+    assert sum(stats["launches"].values()) == sum(raw_stats["launches"].values()) + 18 * stats["batches"]
+
+
+def test_the_jpeg_and_png_switches_refuse_each_other():
+    from vision_slam_frontend_amd import capi
+    L = capi.lib()
+    with capi.Context(capi.default_params(W, H, max_images=2, nfeatures=NF), device=0) as ctx:
+        assert L.vsf_observe_set_debug_png(ctx._h, 1) == capi.VSF_ERR_INVALID_ARG  # nobody draws the images
+        assert L.vsf_observe_set_debug_png(ctx._h, 0) == capi.VSF_OK
+        assert L.vsf_observe_set_debug_images(ctx._h, 1) == capi.VSF_OK
+        assert L.vsf_observe_set_debug_png(ctx._h, 1) == capi.VSF_OK
+        assert L.vsf_observe_set_debug_jpeg(ctx._h, 95) == capi.VSF_ERR_INVALID_ARG  # the second request
+        assert L.vsf_observe_set_debug_jpeg(ctx._h, 0) == capi.VSF_OK
+        assert L.vsf_observe_set_debug_png(ctx._h, 0) == capi.VSF_OK
+        assert L.vsf_observe_set_debug_jpeg(ctx._h, 95) == capi.VSF_OK
+        assert L.vsf_observe_set_debug_png(ctx._h, 1) == capi.VSF_ERR_INVALID_ARG    # ... and the other way round
+        assert L.vsf_observe_set_debug_png(ctx._h, 0) == capi.VSF_OK
+
+
+def test_the_switch_costs_nothing_when_off(frames):
+    counted = ("frames", "batches", "max_batch", "solo", "forced", "depth", "bmax", "compressed", "ingest_commands",
+               "compressed_bytes", "debug_jpeg_commands", "launches")  # launches: per stage, as vsf_profile_read counts them
+    for images in (False, True):
+        out_a, pics_a, st_a = _run(frames, 4, images, None)   # the parent's behaviour: the call is never made
+        out_b, pics_b, st_b = _run(frames, 4, images, 0)      # ... and made with 0
+        assert {k: st_a[k] for k in counted} == {k: st_b[k] for k in counted} and st_b["debug_jpeg_commands"] == 0
+        assert [o.tobytes() for o in out_a] == [o.tobytes() for o in out_b]
+        for (sa, ma), (sb, mb) in zip(pics_a, pics_b):
+            assert (sa is None) == (sb is None) and (ma is None) == (mb is None)
+            assert sa is None or np.array_equal(sa, sb)
+            assert ma is None or np.array_equal(ma, mb)
+
+
+def test_frontend_hands_out_the_same_files_in_queued_mode(frames):
+    from vision_slam_frontend_amd import frontend
+    _, canvases, _ = _run(frames, 4, True, None)
+    C.CDLL("libc.so.6").srand(SEED)
+    fe = frontend.Frontend(W, H, nfeatures=NF, fundamental=F_RECT, frame_life=LIFE, debug_images=True, debug_png=True)
+    fe.set_pipelined(True)
+    fe.set_queue(depth=4)
+    q = np.array([1, 0, 0, 0], np.float32)
+    fe.observe_odometry([0, 0, 0], q, 1.0)
+    assert fe.last_debug_image_compressed() is None and fe.last_debug_image_compressed(stereo=True) is None
+    assert fe.last_debug_image_format() is None
+    for f, (left, right) in enumerate(frames):
+        fe.observe_odometry([0.3 * (f + 1), 0, 0], q, 10.0 + f)
+        assert fe.observe_image(left, right) is True
+    assert fe.num_poses == len(frames)
+    assert fe.last_debug_image_compressed() == ref.imencode(canvases[-1][1])
+    assert fe.last_debug_image_compressed(stereo=True) == ref.imencode(canvases[-1][0])
+    assert fe.last_debug_image_format() == "png" and fe.last_debug_image_format(stereo=True) == "png"
+    fe.close()
+
+
+def test_frontend_refuses_both_forms_at_once():
+    from vision_slam_frontend_amd import capi, frontend
+    with pytest.raises(capi.VsfError):
+        frontend.Frontend(W, H, nfeatures=NF, fundamental=F_RECT, frame_life=LIFE, debug_images=True, debug_jpeg_quality=95,
+                          debug_png=True)

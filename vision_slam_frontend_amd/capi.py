@@ -43,6 +43,7 @@ EXPORTS = [
     "vsf_observe_default_compressed_cap", "vsf_observe_compressed_slot_bytes", "vsf_observe_compressed_ring_bytes",
     "vsf_compressed_image_size", "vsf_observe_probe_compressed",
     "vsf_observe_set_debug_jpeg", "vsf_observe_debug_jpeg_view", "vsf_jpeg_encode_capacity", "vsf_jpeg_encode_batch_dev", "vsf_jpeg_encode", "vsf_debug_jpeg_encode_header",
+    "vsf_png_encode_capacity", "vsf_png_encode_batch_dev", "vsf_png_encode", "vsf_debug_png_encode_header", "vsf_debug_png_encode_cpu", "vsf_observe_set_debug_png", "vsf_observe_debug_png_view",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -117,6 +118,35 @@ def jpeg_encode_header(width: int, height: int, channels: int, quality: int = 0)
     return buf[:n.value].tobytes()
 
 
+def png_encode_capacity(width: int, height: int, channels: int) -> int:
+    """Bytes that hold the PNG file of any width x height x channels image (vsf_png_encode_capacity)."""
+    return int(lib().vsf_png_encode_capacity(width, height, channels))
+
+
+def png_encode_header(width: int, height: int, channels: int) -> bytes:
+    """The PNG encoder's host half: signature + IHDR (33 bytes), then the zlib stream's two header bytes."""
+    buf = np.zeros(64, np.uint8)
+    n = C.c_size_t()
+    st = lib().vsf_debug_png_encode_header(width, height, channels, buf.ctypes.data_as(C.c_void_p), 64, C.byref(n))
+    if st != VSF_OK:
+        raise VsfError(st, "vsf_debug_png_encode_header")
+    return buf[:n.value].tobytes()
+
+
+def png_encode_cpu(img) -> bytes:
+    """cv::imencode(".png", img) by the encoder's CPU model (vsf_debug_png_encode_cpu): (h, w) gray or (h, w, 3) BGR uint8."""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w = img.shape[:2]
+    ch = 1 if img.ndim == 2 else img.shape[2]
+    cap = png_encode_capacity(w, h, ch)
+    out = np.zeros(cap, np.uint8)
+    n = C.c_size_t()
+    st = lib().vsf_debug_png_encode_cpu(_p(img), w, h, ch, w * ch, _p(out), cap, C.byref(n))
+    if st != VSF_OK:
+        raise VsfError(st, "vsf_debug_png_encode_cpu")
+    return out[:n.value].tobytes()
+
+
 def lib() -> C.CDLL:
     """Loads libvsf_hip.so; raises (loudly) if it has not been built -- there is no fallback path."""
     global _lib
@@ -174,6 +204,12 @@ def lib() -> C.CDLL:
         L.vsf_jpeg_encode_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, i32, vp, sz, vp]
         L.vsf_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, i32, vp, sz, vp]
         L.vsf_debug_jpeg_encode_header.argtypes = [i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
+        L.vsf_png_encode_capacity.argtypes = [i32, i32, i32]
+        L.vsf_png_encode_capacity.restype = sz
+        L.vsf_png_encode_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, vp]
+        L.vsf_png_encode.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, vp]
+        L.vsf_debug_png_encode_header.argtypes = [i32, i32, i32, vp, sz, C.POINTER(sz)]
+        L.vsf_debug_png_encode_cpu.argtypes = [vp, i32, i32, i32, sz, vp, sz, C.POINTER(sz)]
         L.vsf_stereo_residuals_batch_dev.argtypes = [vp, vp, vp, vp, i32, vp, vp]
         L.vsf_stereo_thresholds_dev.argtypes = [vp, vp, i32, vp, vp]
         L.vsf_stereo_filter_batch_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
@@ -211,6 +247,8 @@ def lib() -> C.CDLL:
         L.vsf_observe_debug_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
         L.vsf_observe_set_debug_jpeg.argtypes = [vp, i32]
         L.vsf_observe_debug_jpeg_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
+        L.vsf_observe_set_debug_png.argtypes = [vp, i32]
+        L.vsf_observe_debug_png_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
         L.vsf_draw_canvases_dev.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
         L.vsf_draw_canvases.argtypes = [vp, C.POINTER(VsfDrawCanvas), i32, vp, i32]
         L.vsf_jpeg_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
@@ -655,6 +693,25 @@ class Context:
         nbytes = np.zeros(n, np.int32)
         self._check(lib().vsf_jpeg_encode(self._h, _p(imgs), n, w, h, ch, w * h * ch, w * ch, quality, _p(out), stride,
                                           _p(nbytes)), "vsf_jpeg_encode")
+        return [out[i, :nbytes[i]].tobytes() for i in range(n)]
+
+    def png_encode_batch_dev(self, d_src: int, n_images: int, width: int, height: int, channels: int, src_image_stride: int,
+                             src_row_stride: int, d_out: int, out_stride: int, d_out_bytes: int):
+        """cv::imencode(".png") of images resident in HBM: file i at d_out + i * out_stride, its size in d_out_bytes[i]."""
+        self._check(lib().vsf_png_encode_batch_dev(self._h, _p(d_src), n_images, width, height, channels, src_image_stride,
+                                                   src_row_stride, _p(d_out), out_stride, _p(d_out_bytes)),
+                    "vsf_png_encode_batch_dev")
+
+    def png_encode(self, images, out_stride: int | None = None):
+        """cv::imencode(".png", img) of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
+        imgs = np.ascontiguousarray(np.stack([np.asarray(i) for i in images]), dtype=np.uint8)
+        n, h, w = imgs.shape[:3]
+        ch = 1 if imgs.ndim == 3 else imgs.shape[3]
+        stride = png_encode_capacity(w, h, ch) if out_stride is None else out_stride
+        out = np.zeros((n, stride), np.uint8)
+        nbytes = np.zeros(n, np.int32)
+        self._check(lib().vsf_png_encode(self._h, _p(imgs), n, w, h, ch, w * h * ch, w * ch, _p(out), stride, _p(nbytes)),
+                    "vsf_png_encode")
         return [out[i, :nbytes[i]].tobytes() for i in range(n)]
 
     def bayer_bg_to_gray_batch_dev(self, d_src: int, n_images: int, width: int, height: int, src_image_stride: int,

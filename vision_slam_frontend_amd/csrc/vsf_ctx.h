@@ -175,6 +175,7 @@ struct vsf_ctx {
     // bytes, then (16-byte aligned) the stereo file at jpg_off[0] and the match file at jpg_off[1], each with room for
     // vsf_jpeg_encode_capacity() bytes.  h_dbg does not exist then.
     int dbg_jpeg = 0;                 // quality the queue was built with (0: raw canvases)
+    bool dbg_png = false;             // vsf_observe_set_debug_png: the files are PNG (k_png_enc.hip); same ring, slots by its bound
     size_t jpg_off[2] = {0, 0}, jpg_cap[2] = {0, 0}, jpg_slot = 0;
     uint8_t* d_jpg = nullptr;         // [bmax][jpg_slot]
     int32_t* d_jpg_n = nullptr;       // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
@@ -230,6 +231,7 @@ struct vsf_ctx {
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
+  bool ob_debug_png = false;  // vsf_observe_set_debug_png: ... as PNG files (never together with the JPEG form)
   int ob_debug_jpeg = 0;  // vsf_observe_set_debug_jpeg: ... and hands them out as JPEG files of this quality (0: raw)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // vsf_draw_canvases(_dev) (k_draw.hip): per-pixel winners (all zero between calls: the resolve clears what it read),
@@ -252,6 +254,10 @@ struct vsf_ctx {
   size_t je_scratch_cap = 0;
   uint8_t* je_buf = nullptr;      // vsf_jpeg_encode (host pointers): images | files | byte counts on the device
   size_t je_buf_cap = 0;
+  uint8_t* pe_scratch = nullptr;  // vsf_png_encode_batch_dev: filtered bytes, symbols, block plans, the zlib streams
+  size_t pe_scratch_cap = 0;
+  uint8_t* pe_buf = nullptr;      // vsf_png_encode (host pointers): images | files | byte counts on the device
+  size_t pe_buf_cap = 0;
   uint8_t* mh_desc = nullptr;  // host-API descriptor staging: 2 sets
   int32_t* mh_counts = nullptr;
   vsf_dmatch* mh_matches = nullptr;

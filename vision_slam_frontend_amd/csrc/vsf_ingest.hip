@@ -269,4 +269,69 @@ vsf_status vsf_jpeg_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int w
   return st;
 }
 
+// cv::imencode(".png", img) for a batch of equally sized images (k_png_enc.hip): the way out
+// of the device for pixels, as the decoders above are the way in.  Asynchronous on the context's stream.
+vsf_status vsf_png_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int channels,
+                                     size_t src_image_stride, size_t src_row_stride, uint8_t* d_out,
+                                     size_t out_stride, int32_t* d_out_bytes) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !d_src || !d_out || !d_out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 ||
+      width > 65535 || height > 65535 || (channels != 1 && channels != 3))
+    return VSF_ERR_INVALID_ARG;
+  if (src_row_stride < (size_t)width * (size_t)channels || src_image_stride < src_row_stride * (size_t)height || out_stride < 1 ||
+      ((uintptr_t)d_out_bytes & 3))
+    return VSF_ERR_INVALID_ARG;
+  // the byte count of a file is an int32, the byte index of the kernels a u32
+  if (vsf_png_encode_capacity(width, height, channels) > 0x7FFFFFFFu) return VSF_ERR_UNSUPPORTED;
+  VSF_HIP(hipSetDevice(ctx->device));
+  const size_t need = vsf_png_enc_scratch_need(n_images, width, height, channels, out_stride);
+  if (need > ctx->pe_scratch_cap) {  // (no wait: the outgrown buffer is retired)
+    const vsf_status gs = grow_scratch(ctx, ctx->pe_scratch, need + need / 4);
+    if (gs != VSF_OK) return gs;
+    ctx->pe_scratch_cap = need + need / 4;
+  }
+  vsf_launch_png_encode(d_src, n_images, width, height, channels, src_image_stride, src_row_stride,
+                         ctx->pe_scratch, d_out, out_stride, d_out_bytes, ctx->d_status, ctx->stream);
+  VSF_STICKY();
+  return VSF_OK;
+}
+
+// The same for host pointers, synchronous: images up, files and byte counts back.  out_bytes[i] = -1 and VSF_ERR_CAPACITY for a
+// file that does not fit out_stride.
+vsf_status vsf_png_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int channels,
+                           size_t src_image_stride, size_t src_row_stride, uint8_t* out, size_t out_stride,
+                           int32_t* out_bytes) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !src || !out || !out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 65535 ||
+      height > 65535 || (channels != 1 && channels != 3) || out_stride < 1)
+    return VSF_ERR_INVALID_ARG;
+  const size_t row = (size_t)width * (size_t)channels;
+  if (src_row_stride < row || src_image_stride < src_row_stride * (size_t)height) return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // device staging: images (packed rows) | files | byte counts
+  const size_t img_bytes = (row * (size_t)height + 15) & ~(size_t)15, files_bytes = ((size_t)n_images * out_stride + 15) & ~(size_t)15;
+  const size_t need = (size_t)n_images * (img_bytes + sizeof(int32_t)) + files_bytes;
+  if (need > ctx->pe_buf_cap) {
+    const vsf_status gs = grow_scratch(ctx, ctx->pe_buf, need);
+    if (gs != VSF_OK) return gs;
+    ctx->pe_buf_cap = need;
+  }
+  uint8_t* d_img = ctx->pe_buf;
+  uint8_t* d_files = d_img + (size_t)n_images * img_bytes;
+  int32_t* d_bytes = reinterpret_cast<int32_t*>(d_files + files_bytes);
+  for (int i = 0; i < n_images; i++)
+    VSF_HIP(hipMemcpy2DAsync(d_img + (size_t)i * img_bytes, row, src + (size_t)i * src_image_stride, src_row_stride, row,
+                             (size_t)height, hipMemcpyHostToDevice, ctx->stream));
+  vsf_status st = vsf_png_encode_batch_dev(ctx, d_img, n_images, width, height, channels, img_bytes, row, d_files,
+                                            out_stride, d_bytes);
+  if (st != VSF_OK) return st;
+  VSF_HIP(hipMemcpyAsync(out_bytes, d_bytes, (size_t)n_images * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  st = check_status_word(ctx);  // synchronises
+  if (st != VSF_OK && st != VSF_ERR_CAPACITY) return st;
+  for (int i = 0; i < n_images; i++)
+    if (out_bytes[i] > 0)
+      VSF_HIP(hipMemcpy(out + (size_t)i * out_stride, d_files + (size_t)i * out_stride, (size_t)out_bytes[i], hipMemcpyDeviceToHost));
+  return st;
+}
+
 }  // extern "C"

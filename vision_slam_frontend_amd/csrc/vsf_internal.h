@@ -397,6 +397,11 @@ void vsf_launch_jpeg_encode(const uint8_t* d_src, int n, int width, int height, 
 void vsf_launch_jpeg_files_home(const uint8_t* d_files, size_t file_stride, const int32_t* d_bytes, int n, uint8_t* h_ring,
                                 size_t slot_stride, size_t file_off, int which, int slot0, int depth, const VsfObserveFrame* frames,
                                 const uint8_t* results, size_t result_stride, hipStream_t s);
+// k_png_enc.hip: the PNG encoder (cv::imencode(".png")).  d_scratch: vsf_png_enc_scratch_need() bytes, 64-byte aligned.  out_cap as above.
+size_t vsf_png_enc_scratch_need(int n, int width, int height, int channels, size_t out_stride);
+void vsf_launch_png_encode(const uint8_t* d_src, int n, int width, int height, int channels, size_t src_image_stride,
+                           size_t src_row_stride, void* d_scratch, uint8_t* d_out, size_t out_stride, int32_t* d_out_bytes,
+                           int32_t* d_status, hipStream_t s, size_t out_cap = 0);
 // The queue's ingest finish (k_ingest.hip): every image of [0, n) whose status word carries bit 1 (its decoder refused the
 // data) becomes all zero, `rows` rows of `pitch` bytes.
 void vsf_launch_ingest_finish(uint8_t* d_img, size_t image_stride, int pitch, int rows, const int32_t* d_status, int n,

@@ -254,7 +254,8 @@ void launcher_thread(vsf_ctx* ctx);
 
 vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.dbg_jpeg == (ctx->ob_debug ? ctx->ob_debug_jpeg : 0))
+  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.dbg_jpeg == (ctx->ob_debug ? ctx->ob_debug_jpeg : 0) &&
+      o.dbg_png == (ctx->ob_debug && ctx->ob_debug_png))
     return VSF_OK;
   sync_all_streams(ctx);
   float thr_state = 10000.0f;  // cc:353
@@ -267,6 +268,7 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.frame_life = frame_life;
   o.debug = ctx->ob_debug;
   o.dbg_jpeg = o.debug ? ctx->ob_debug_jpeg : 0;
+  o.dbg_png = o.debug && ctx->ob_debug_png;
   o.ring = frame_life + o.bmax;
   o.max_pairs = o.bmax * (frame_life + 1);
   const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)o.ring + B;
@@ -306,10 +308,10 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
     VSF_HIP(hipMalloc((void**)&o.dbg_prev_kp, K * sizeof(vsf_keypoint)));
     VSF_HIP(hipMalloc((void**)&o.dbg_ints, 16));
     VSF_HIP(hipMemset(o.dbg_ints, 0, 16));
-    if (o.dbg_jpeg) {  // the files leave, not the canvases: a pinned ring sized by the encoder's bound
+    if (o.dbg_jpeg || o.dbg_png) {  // the files leave, not the canvases: a pinned ring sized by the encoder's bound
       const int w = ctx->p.width, h = ctx->p.height;
-      o.jpg_cap[0] = (vsf_jpeg_encode_capacity(2 * w, h, 3) + 15) & ~(size_t)15;
-      o.jpg_cap[1] = (vsf_jpeg_encode_capacity(w, h, 3) + 15) & ~(size_t)15;
+      o.jpg_cap[0] = ((o.dbg_png ? vsf_png_encode_capacity(2 * w, h, 3) : vsf_jpeg_encode_capacity(2 * w, h, 3)) + 15) & ~(size_t)15;
+      o.jpg_cap[1] = ((o.dbg_png ? vsf_png_encode_capacity(w, h, 3) : vsf_jpeg_encode_capacity(w, h, 3)) + 15) & ~(size_t)15;
       if (o.jpg_cap[0] > 0x7FFFFFF0u) return VSF_ERR_UNSUPPORTED;
       o.jpg_off[0] = 16;
       o.jpg_off[1] = 16 + o.jpg_cap[0];
@@ -318,7 +320,8 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
       VSF_HIP(hipMalloc((void**)&o.d_jpg_n, (2 * B + 1) * sizeof(int32_t)));  // (+ the encoder's status word: a file that does
       // not fit leaves its count at -1, which is what the view reports)
       VSF_HIP(hipMemset(o.d_jpg_n, 0, (2 * B + 1) * sizeof(int32_t)));
-      VSF_HIP(hipMalloc((void**)&o.jpg_scratch, vsf_jpeg_enc_scratch_bytes((int)B, 2 * w, h, 3, o.jpg_cap[0])));
+      VSF_HIP(hipMalloc((void**)&o.jpg_scratch, o.dbg_png ? vsf_png_enc_scratch_need((int)B, 2 * w, h, 3, o.jpg_cap[0])
+                                                           : vsf_jpeg_enc_scratch_bytes((int)B, 2 * w, h, 3, o.jpg_cap[0])));
       VSF_HIP(hipHostMalloc((void**)&o.h_jpg, (size_t)o.depth * o.jpg_slot, hipHostMallocMapped));
     } else {
       VSF_HIP(hipHostMalloc((void**)&o.h_dbg, (size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
@@ -580,7 +583,7 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   if (o.debug) {
     // ---- the debug images (slam_frontend.cc:74-115, 167-171, 458-466) of every frame, drawn in the batch's tail from what
     // it holds in HBM, then into the frames' slots of the pinned debug ring (one copy, two when the slots wrap) ----
-    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, o.dbg_jpeg ? 14 : 6);  // (4 kernels + 2 copies, or 4 + 2 x (4 encode + 1 carry))
+    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, o.dbg_png ? 24 : o.dbg_jpeg ? 14 : 6);  // (4 kernels + 2 copies, or 4 + 2 x (4 or 9 encode + 1 carry))
     VsfObserveDebugArgs d;
     d.n_frames = n;
     d.max_rows = Kc;
@@ -608,19 +611,24 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
     d.out_stride = o.out_stride;
     vsf_launch_observe_debug(d, s_tail);
     const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
-    if (o.dbg_jpeg) {
-      // cv::imencode(".jpg") of the canvases just drawn, stereo then match (two sizes: two encodes), into the batch's device
+    if (o.dbg_jpeg || o.dbg_png) {
+      // cv::imencode(".jpg") / (".png") of the canvases just drawn, stereo then match (two sizes: two encodes), into the batch's device
       // slots; then only the files' bytes cross to the pinned ring
       const int w = ctx->p.width, h = ctx->p.height;
       for (int which = 0; which < 2; which++) {
         const int iw = which ? w : 2 * w;
-        vsf_launch_jpeg_encode(o.dbg_canvas + (which ? (size_t)6 * w * h : 0), n, iw, h, 3, o.dbg_stride, (size_t)3 * iw, o.dbg_jpeg,
-                               o.jpg_scratch, o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax,
-                               o.d_jpg_n + 2 * (size_t)o.bmax, s_tail, o.jpg_cap[which]);
+        if (o.dbg_png)
+          vsf_launch_png_encode(o.dbg_canvas + (which ? (size_t)6 * w * h : 0), n, iw, h, 3, o.dbg_stride, (size_t)3 * iw,
+                                o.jpg_scratch, o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax,
+                                o.d_jpg_n + 2 * (size_t)o.bmax, s_tail, o.jpg_cap[which]);
+        else
+          vsf_launch_jpeg_encode(o.dbg_canvas + (which ? (size_t)6 * w * h : 0), n, iw, h, 3, o.dbg_stride, (size_t)3 * iw, o.dbg_jpeg,
+                                 o.jpg_scratch, o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax,
+                                 o.d_jpg_n + 2 * (size_t)o.bmax, s_tail, o.jpg_cap[which]);
         vsf_launch_jpeg_files_home(o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax, n, o.h_jpg, o.jpg_slot,
                                    o.jpg_off[which], which, slot0, o.depth, M.frames, o.h_out, o.out_stride, s_tail);
       }
-      o.stat_jpeg_commands += 10;
+      o.stat_jpeg_commands += o.dbg_png ? 20 : 10;
     } else {
       VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
                              hipMemcpyDeviceToHost, s_tail));
@@ -766,8 +774,8 @@ vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** 
   *stereo = *match = nullptr;
   const vsf_ctx::Observe& o = ctx->ob;
   // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_collect_view)
-  if (!o.ready || !o.debug || o.dbg_jpeg || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
-    return VSF_ERR_INVALID_ARG;  // (with vsf_observe_set_debug_jpeg the raw canvases never leave the device)
+  if (!o.ready || !o.debug || o.dbg_jpeg || o.dbg_png || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+    return VSF_ERR_INVALID_ARG;  // (with vsf_observe_set_debug_jpeg / _png the raw canvases never leave the device)
   const int slot = (int)(ticket % o.depth);
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
   const uint8_t* base = o.h_dbg + (size_t)slot * o.dbg_stride;
@@ -781,6 +789,7 @@ vsf_status vsf_observe_set_debug_jpeg(vsf_ctx* ctx, int quality) {
   if (!ctx || quality < 0 || quality > 100) return VSF_ERR_INVALID_ARG;
   if (quality == ctx->ob_debug_jpeg) return VSF_OK;
   if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
+  if (quality != 0 && ctx->ob_debug_png) return VSF_ERR_INVALID_ARG;  // one form of file at a time
   // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
   if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
   if (ctx->ob.ready) stop_observe_threads(ctx);
@@ -788,14 +797,44 @@ vsf_status vsf_observe_set_debug_jpeg(vsf_ctx* ctx, int quality) {
   return VSF_OK;
 }
 
+namespace {
+// A collected frame's two files inside the pinned ring of files; png: which form the caller asks for.
+vsf_status debug_files_view(vsf_ctx* ctx, bool png, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                            const uint8_t** match, size_t* match_bytes);
+}  // namespace
+
 vsf_status vsf_observe_debug_jpeg_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
                                        const uint8_t** match, size_t* match_bytes) {
+  return debug_files_view(ctx, false, ticket, stereo, stereo_bytes, match, match_bytes);
+}
+
+vsf_status vsf_observe_set_debug_png(vsf_ctx* ctx, int on) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx) return VSF_ERR_INVALID_ARG;
+  if ((on != 0) == ctx->ob_debug_png) return VSF_OK;
+  if (on && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;      // files of images nobody draws
+  if (on && ctx->ob_debug_jpeg) return VSF_ERR_INVALID_ARG;  // one form of file at a time
+  // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
+  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
+  if (ctx->ob.ready) stop_observe_threads(ctx);
+  ctx->ob_debug_png = on != 0;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_debug_png_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                                      const uint8_t** match, size_t* match_bytes) {
+  return debug_files_view(ctx, true, ticket, stereo, stereo_bytes, match, match_bytes);
+}
+
+namespace {
+vsf_status debug_files_view(vsf_ctx* ctx, bool png, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                            const uint8_t** match, size_t* match_bytes) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || !stereo || !stereo_bytes || !match || !match_bytes) return VSF_ERR_INVALID_ARG;
   *stereo = *match = nullptr;
   *stereo_bytes = *match_bytes = 0;
   const vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready || !o.debug || !o.dbg_jpeg || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+  if (!o.ready || !o.debug || !(png ? o.dbg_png : o.dbg_jpeg != 0) || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
     return VSF_ERR_INVALID_ARG;
   const int slot = (int)(ticket % o.depth);
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
@@ -813,6 +852,7 @@ vsf_status vsf_observe_debug_jpeg_view(vsf_ctx* ctx, int64_t ticket, const uint8
   }
   return VSF_OK;
 }
+}  // namespace
 
 vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_flight) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)

@@ -68,6 +68,9 @@ def lib() -> C.CDLL:
         L.vsfh_debug_image.argtypes = [vp, i32, i32, vp, sz, vp]
         L.vsfh_set_debug_jpeg_quality.argtypes = [vp, i32]
         L.vsfh_set_debug_jpeg_quality.restype = None
+        L.vsfh_set_debug_png.argtypes = [vp, i32]
+        L.vsfh_set_debug_png.restype = None
+        L.vsfh_debug_image_compressed_format.argtypes = [vp, i32]
         L.vsfh_debug_image_compressed.argtypes = [vp, i32, vp, sz]
         L.vsfh_debug_image_compressed.restype = sz
         _lib = L
@@ -88,7 +91,7 @@ def default_calibration() -> capi.VsfCalibration:
 class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
-                 debug_jpeg_quality: int = 0):
+                 debug_jpeg_quality: int = 0, debug_png: bool = False):
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
@@ -96,6 +99,8 @@ class Frontend:
             lib().vsfh_set_debug_images(self._h, 1)
         if debug_jpeg_quality:  # FrontendConfig::debug_jpeg_quality_: the queued modes keep JPEG files instead of raw images
             lib().vsfh_set_debug_jpeg_quality(self._h, debug_jpeg_quality)
+        if debug_png:  # FrontendConfig::debug_png_: ... or PNG files, lossless (not together with the JPEG form)
+            lib().vsfh_set_debug_png(self._h, 1)
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend")
@@ -159,6 +164,10 @@ class Frontend:
         out = np.zeros(n, np.uint8)
         lib().vsfh_debug_image_compressed(self._h, int(stereo), _p(out), n)
         return out.tobytes()
+
+    def last_debug_image_format(self, stereo: bool = False):
+        """CompressedView::format of the same getters: "jpeg", "png" or None."""
+        return (None, "jpeg", "png")[lib().vsfh_debug_image_compressed_format(self._h, int(stereo))]
 
     def last_debug_image(self, stereo: bool = False):
         """GetLastDebugImage() (stereo: GetLastDebugStereoImage()); None for the reference's empty cv::Mat."""

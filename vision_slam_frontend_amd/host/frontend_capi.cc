@@ -167,6 +167,13 @@ int vsfh_debug_image(void* f, int stereo, int i, uint8_t* out, size_t cap, int r
 }
 
 void vsfh_set_debug_jpeg_quality(void* f, int quality) { static_cast<Frontend*>(f)->set_debug_jpeg_quality(quality); }
+void vsfh_set_debug_png(void* f, int on) { static_cast<Frontend*>(f)->set_debug_png(on != 0); }
+// The format of what vsfh_debug_image_compressed returns: 0 none, 1 "jpeg", 2 "png".
+int vsfh_debug_image_compressed_format(void* f, int stereo) {
+  Frontend* fe = static_cast<Frontend*>(f);
+  const Frontend::CompressedView v = stereo ? fe->GetLastDebugStereoImageCompressed() : fe->GetLastDebugImageCompressed();
+  return !v.format ? 0 : v.format[0] == 'p' ? 2 : 1;
+}
 // GetLastDebugImageCompressed / GetLastDebugStereoImageCompressed: the file's size (0: none); min(size, cap) bytes into out.
 size_t vsfh_debug_image_compressed(void* f, int stereo, uint8_t* out, size_t cap) {
   Frontend* fe = static_cast<Frontend*>(f);

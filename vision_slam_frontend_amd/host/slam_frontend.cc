@@ -123,6 +123,7 @@ FrontendConfig::FrontendConfig() {
   // asked for; on, the images are the reference's byte for byte (drawn on the GPU, csrc/k_draw.hip).
   debug_images_ = false;
   debug_jpeg_quality_ = 0;
+  debug_png_ = false;
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
   descriptor_extract_type_ = DescriptorExtractorType::ORB;
   best_percent_ = 0.3f;
@@ -276,6 +277,7 @@ bool Frontend::EnsureContext(int width, int height) {
   if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
   if (last_status_ == VSF_OK && config_.debug_images_ && config_.debug_jpeg_quality_ > 0)
     last_status_ = vsf_observe_set_debug_jpeg(ctx_, config_.debug_jpeg_quality_);
+  if (last_status_ == VSF_OK && config_.debug_images_ && config_.debug_png_) last_status_ = vsf_observe_set_debug_png(ctx_, 1);
   pending_.assign((size_t)ctx_depth_, PendingFrame());
   pending_head_ = pending_count_ = 0;
   return last_status_ == VSF_OK;
@@ -683,10 +685,13 @@ bool Frontend::RetireOldest() {
     right_temp_frame.frame_ID_ = curr_frame_ID_;
     book(right_temp_frame, &curr_frame, pair_bytes[n_pairs - 1], npairs[n_pairs - 1], nullptr);
   }
-  if (config_.debug_images_ && config_.debug_jpeg_quality_ > 0) {  // encoded in the batch's tail (vsf_observe_set_debug_jpeg)
+  if (config_.debug_images_ && (config_.debug_jpeg_quality_ > 0 || config_.debug_png_)) {
+    // encoded in the batch's tail (vsf_observe_set_debug_jpeg / vsf_observe_set_debug_png)
     const uint8_t *stereo = nullptr, *match = nullptr;
     size_t stereo_bytes = 0, match_bytes = 0;
-    const vsf_status ds = vsf_observe_debug_jpeg_view(ctx_, pf.ticket, &stereo, &stereo_bytes, &match, &match_bytes);
+    const vsf_status ds = config_.debug_png_
+                              ? vsf_observe_debug_png_view(ctx_, pf.ticket, &stereo, &stereo_bytes, &match, &match_bytes)
+                              : vsf_observe_debug_jpeg_view(ctx_, pf.ticket, &stereo, &stereo_bytes, &match, &match_bytes);
     if (ds != VSF_OK) {
       last_status_ = ds;
       return false;
@@ -829,7 +834,7 @@ void Frontend::set_debug_images(bool on) {
 }
 
 void Frontend::set_debug_jpeg_quality(int quality) {
-  if (!nodes_.empty() || pending_count_ > 0 || quality < 0 || quality > 100) {
+  if (!nodes_.empty() || pending_count_ > 0 || quality < 0 || quality > 100 || (quality > 0 && config_.debug_png_)) {
     last_status_ = VSF_ERR_INVALID_ARG;
     return;
   }
@@ -837,17 +842,29 @@ void Frontend::set_debug_jpeg_quality(int quality) {
   if (ctx_ && (config_.debug_images_ || quality == 0)) last_status_ = vsf_observe_set_debug_jpeg(ctx_, quality);
 }
 
+void Frontend::set_debug_png(bool on) {
+  if (!nodes_.empty() || pending_count_ > 0 || (on && config_.debug_jpeg_quality_ > 0)) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  config_.debug_png_ = on;
+  if (ctx_ && (config_.debug_images_ || !on)) last_status_ = vsf_observe_set_debug_png(ctx_, on ? 1 : 0);
+}
+
 Frontend::CompressedView Frontend::GetLastDebugImageCompressed() {
   Flush();
   CompressedView v;
-  if (!debug_files_.empty()) v.data = debug_files_.back().data(), v.size = debug_files_.back().size();
+  if (!debug_files_.empty())
+    v.data = debug_files_.back().data(), v.size = debug_files_.back().size(), v.format = config_.debug_png_ ? "png" : "jpeg";
   return v;
 }
 
 Frontend::CompressedView Frontend::GetLastDebugStereoImageCompressed() {
   Flush();
   CompressedView v;
-  if (!debug_stereo_files_.empty()) v.data = debug_stereo_files_.back().data(), v.size = debug_stereo_files_.back().size();
+  if (!debug_stereo_files_.empty())
+    v.data = debug_stereo_files_.back().data(), v.size = debug_stereo_files_.back().size(),
+    v.format = config_.debug_png_ ? "png" : "jpeg";
   return v;
 }
 

@@ -77,6 +77,10 @@ struct FrontendConfig {
   // (what cv::imencode(".jpg") writes for them; vsf_observe_set_debug_jpeg) INSTEAD of the raw images -- the raw getters below
   // then return nothing.  0 (the default): raw images.  Ignored in per-call mode.
   int debug_jpeg_quality_;
+  // The same, lossless: the queued modes keep the debug images as PNG files (what cv::imencode(".png") writes for them;
+  // vsf_observe_set_debug_png).  Off by default; ignored in per-call mode; not together with debug_jpeg_quality_ (the second of
+  // the two to be asked for is refused with VSF_ERR_INVALID_ARG).
+  bool debug_png_;
   DescriptorExtractorType descriptor_extract_type_;
   float best_percent_;
   float nn_match_ratio_;
@@ -151,11 +155,13 @@ class Frontend {
   Image GetLastDebugImage();
   Image GetLastDebugStereoImage();
   std::vector<Image> getDebugStereoImages();
-  // The newest match / stereo image as a JPEG file (config.debug_jpeg_quality_ > 0, queued modes): the payload of a
-  // sensor_msgs/CompressedImage with format "jpeg" (slam_to_ros.h).  {nullptr, 0} when there is none.  Valid while the object lives.
+  // The newest match / stereo image as a JPEG file (config.debug_jpeg_quality_ > 0) or a PNG file (config.debug_png_), queued
+  // modes: the payload of a sensor_msgs/CompressedImage whose format string is `format` ("jpeg" / "png", slam_to_ros.h).
+  // {nullptr, 0, nullptr} when there is none.  Valid while the object lives.
   struct CompressedView {
     const uint8_t* data = nullptr;
     size_t size = 0;
+    const char* format = nullptr;
   };
   CompressedView GetLastDebugImageCompressed();
   CompressedView GetLastDebugStereoImageCompressed();
@@ -180,6 +186,7 @@ class Frontend {
   // config.debug_images_ after construction (before the first ObserveImage; later calls fail with VSF_ERR_INVALID_ARG).
   void set_debug_images(bool on);
   void set_debug_jpeg_quality(int quality);  // config.debug_jpeg_quality_, under the same rule
+  void set_debug_png(bool on);               // config.debug_png_, under the same rule
   // Frames ObserveImage may leave in the queue when pipelined (1..1024, default 256) and the most frames one batch carries
   // (default 128; the context's extraction buffers are sized for it: ~25 MB of HBM per 640x480 frame; the queue's staging
   // and result rings are pinned host memory: depth x (two images + vsf_observe_capacity)).  Measured on an MI355X at
@@ -278,7 +285,7 @@ class Frontend {
   // The reference keeps this in a file-static shared by all instances (cc:353, quirk Q3); here it is per object.
   float stereo_ambig_constraint_;
   std::vector<OwnedImage> debug_images_, debug_stereo_images_;  // cc h:202-203: kept for the object's lifetime
-  std::vector<std::vector<uint8_t>> debug_files_, debug_stereo_files_;  // ... or their JPEG files (debug_jpeg_quality_)
+  std::vector<std::vector<uint8_t>> debug_files_, debug_stereo_files_;  // ... or their JPEG / PNG files (debug_jpeg_quality_ / debug_png_)
   bool fused_;
   bool pipelined_;
   int depth_ = 256, batch_frames_ = 128, min_batch_ = 0;

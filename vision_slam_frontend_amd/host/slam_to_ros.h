@@ -49,6 +49,9 @@ constexpr const char* kMd5VisionFeature = "9cccef6835ecad8ee3bfb40a17ba67fb";
 // computed by the same tool from ROS-1's field lists (std_msgs/Header header, string format, uint8[] data).
 constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 
+constexpr const char* kCompressedFormatJpeg = "jpeg";
+constexpr const char* kCompressedFormatPng = "png";
+
 class Writer {
  public:
   explicit Writer(std::vector<uint8_t>* out) : out_(out) {}
@@ -197,7 +200,8 @@ inline void SerializeSLAMProblem(const slam_types::SLAMProblem& p, std::vector<u
   for (const auto& o : p.odometry_factors) Write(&w, o);
 }
 
-// One sensor_msgs/CompressedImage with format "jpeg" (what image_transport's compressed publisher sends for a JPEG file):
+// One sensor_msgs/CompressedImage with format "jpeg" (what image_transport's compressed publisher sends for a JPEG file); pass
+// kCompressedFormatPng (Frontend::CompressedView::format says which) for a PNG file, image_transport's lossless setting:
 //   Header   uint32 seq, time stamp (uint32 secs, uint32 nsecs), string frame_id (uint32 length + bytes)
 //   string format, uint8[] data (uint32 length + bytes)                                  24 + |frame_id| + |format| + n B
 inline void SerializeCompressedImage(uint32_t seq, uint32_t stamp_secs, uint32_t stamp_nsecs, const std::string& frame_id,
