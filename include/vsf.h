@@ -95,7 +95,10 @@ typedef struct vsf_ctx vsf_ctx;
 
 /* Fills *p with the reference literals for the given image size and batch capacity. */
 vsf_status vsf_params_default(vsf_params* p, int width, int height, int max_images);
-/* ratio as the reference stores it: a float widened to double. Sets ratio_num / ratio_shift. */
+/* ratio as the reference stores it: a float widened to double. Sets ratio_num / ratio_shift (lowest terms: ratio_num odd
+ * or ratio_shift 0).  VSF_ERR_INVALID_ARG, with *p left unchanged, for a float that is not finite, not inside (0, 256),
+ * or needs more than 31 fractional bits (ratio_shift <= 31): 0.001f == 8 589 935 / 2^33 is refused, 2^-31 is the
+ * smallest power of two accepted. */
 vsf_status vsf_params_set_ratio(vsf_params* p, float nn_match_ratio);
 
 vsf_status vsf_create(const vsf_params* p, int device, vsf_ctx** out);
