@@ -22,70 +22,17 @@ torch = pytest.importorskip("torch")
 if not ref.available():
     pytest.skip("libpng16.so.16 cannot be loaded", allow_module_level=True)
 
-W, H, NF, LIFE, SEED = 320, 240, 500, 3, 11
-F_RECT = np.float32([0, 0, 0, 0, 0, -1, 0, 1, 0])
+from debug_files_run import F_RECT, H, LIFE, NF, SEED, W, make_frames, run  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def frames():
-    from vision_slam_frontend_amd import synth
-    sc = synth.Scene(W, H)
-    fr = [(sc.render(f, 0), sc.render(f, 1)) for f in range(5)]
-    fr[2] = (fr[2][0], np.zeros_like(fr[2][1]))  # an empty right image: no stereo match, so no stereo image for this frame
-    return fr
+    return make_frames()
 
 
 def _run(frames, depth, images, png):
     """png: None = the call is never made.  -> (results, raw canvases or files per frame, stats)"""
-    from vision_slam_frontend_amd import capi, frontend
-    calib = frontend.default_calibration().set("fundamental", F_RECT.reshape(9))
-    L = capi.lib()
-    with capi.Context(capi.default_params(W, H, max_images=2 * depth, nfeatures=NF), device=0) as ctx:
-        ctx.observe_configure(depth=depth)
-        ctx.profile_enable(True)  # (the per-stage launch counts of vsf_profile_read)
-        # the stereo lines' colours come from the process's rand(), drawn at submit: seeded once the context exists (the HIP
-        # runtime's own start-up, which the first context of a process triggers, does not leave rand() where it was)
-        assert ctx.sync() == capi.VSF_OK
-        C.CDLL("libc.so.6").srand(SEED)
-        if images:
-            assert L.vsf_observe_set_debug_images(ctx._h, 1) == capi.VSF_OK
-        if png is not None:
-            assert L.vsf_observe_set_debug_png(ctx._h, png) == capi.VSF_OK
-        cap = L.vsf_observe_capacity(ctx._h, LIFE)
-        outs, pics = [], []
-        for g0 in range(0, len(frames), depth):
-            tickets = []
-            for left, right in frames[g0:g0 + depth]:
-                t = C.c_int64()
-                assert L.vsf_observe_submit(ctx._h, left.ctypes.data, right.ctypes.data, W, H, W, C.byref(calib), C.c_float(0.3),
-                                            LIFE, C.byref(t)) == capi.VSF_OK
-                tickets.append(t.value)
-            for t in tickets:
-                buf = np.zeros(cap, np.uint8)
-                n = C.c_size_t()
-                assert L.vsf_observe_collect(ctx._h, t, buf.ctypes.data, cap, C.byref(n)) == capi.VSF_OK
-                outs.append(buf[:n.value].copy())
-            for t in tickets:
-                s_, m_, sn, mn = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
-                if png:
-                    assert L.vsf_observe_debug_png_view(ctx._h, t, C.byref(s_), C.byref(sn), C.byref(m_), C.byref(mn)) == capi.VSF_OK
-                    assert bool(s_.value) == (sn.value > 0) and bool(m_.value) == (mn.value > 0)
-                    pics.append((C.string_at(s_.value, sn.value) if s_.value else None,
-                                 C.string_at(m_.value, mn.value) if m_.value else None))
-                    assert L.vsf_observe_debug_view(ctx._h, t, C.byref(s_), C.byref(m_)) == capi.VSF_ERR_INVALID_ARG
-                    assert L.vsf_observe_debug_jpeg_view(ctx._h, t, C.byref(s_), C.byref(sn), C.byref(m_),
-                                                         C.byref(mn)) == capi.VSF_ERR_INVALID_ARG
-                elif images:
-                    assert L.vsf_observe_debug_view(ctx._h, t, C.byref(s_), C.byref(m_)) == capi.VSF_OK
-                    pics.append((np.frombuffer(C.string_at(s_.value, 6 * W * H), np.uint8).reshape(H, 2 * W, 3) if s_.value else None,
-                                 np.frombuffer(C.string_at(m_.value, 3 * W * H), np.uint8).reshape(H, W, 3) if m_.value else None))
-                    assert L.vsf_observe_debug_png_view(ctx._h, t, C.byref(s_), C.byref(sn), C.byref(m_),
-                                                        C.byref(mn)) == capi.VSF_ERR_INVALID_ARG
-        if png:  # the window holds frames: the switch no longer moves
-            assert L.vsf_observe_set_debug_png(ctx._h, 0) == capi.VSF_ERR_INVALID_ARG
-        stats = ctx.observe_stats()
-        stats["launches"] = {k: v[1] for k, v in ctx.profile_read().items()}
-        return outs, pics, stats
+    return run(frames, depth, images, "png", png)
 
 
 def _pixels(png, w):

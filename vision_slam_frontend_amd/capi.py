@@ -676,43 +676,45 @@ class Context:
             raise VsfError(st, "vsf_imdecode_gray_batch", lib().vsf_last_hip_error(self._h))
         return st
 
-    def jpeg_encode_batch_dev(self, d_src: int, n_images: int, width: int, height: int, channels: int, src_image_stride: int,
-                              src_row_stride: int, quality: int, d_out: int, out_stride: int, d_out_bytes: int):
-        """cv::imencode(".jpg") of images resident in HBM: file i at d_out + i * out_stride, its size in d_out_bytes[i]."""
-        self._check(lib().vsf_jpeg_encode_batch_dev(self._h, _p(d_src), n_images, width, height, channels, src_image_stride,
-                                                    src_row_stride, quality, _p(d_out), out_stride, _p(d_out_bytes)),
-                    "vsf_jpeg_encode_batch_dev")
+    def _encode_batch_dev(self, fmt: str, quality: tuple, d_src, n_images, width, height, channels, src_image_stride, src_row_stride,
+                          d_out, out_stride, d_out_bytes):
+        """vsf_<fmt>_encode_batch_dev; `quality`: the arguments between the strides and d_out ((quality,) for JPEG, () for PNG)."""
+        name = "vsf_%s_encode_batch_dev" % fmt
+        self._check(getattr(lib(), name)(self._h, _p(d_src), n_images, width, height, channels, src_image_stride, src_row_stride,
+                                         *quality, _p(d_out), out_stride, _p(d_out_bytes)), name)
 
-    def jpeg_encode(self, images, quality: int = 0, out_stride: int | None = None):
-        """cv::imencode(".jpg", img, quality) of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
+    def _encode(self, fmt: str, quality: tuple, images, out_stride):
+        """vsf_<fmt>_encode of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
         imgs = np.ascontiguousarray(np.stack([np.asarray(i) for i in images]), dtype=np.uint8)
         n, h, w = imgs.shape[:3]
         ch = 1 if imgs.ndim == 3 else imgs.shape[3]
-        stride = jpeg_encode_capacity(w, h, ch) if out_stride is None else out_stride
+        name = "vsf_%s_encode" % fmt
+        stride = int(getattr(lib(), name + "_capacity")(w, h, ch)) if out_stride is None else out_stride
         out = np.zeros((n, stride), np.uint8)
         nbytes = np.zeros(n, np.int32)
-        self._check(lib().vsf_jpeg_encode(self._h, _p(imgs), n, w, h, ch, w * h * ch, w * ch, quality, _p(out), stride,
-                                          _p(nbytes)), "vsf_jpeg_encode")
+        self._check(getattr(lib(), name)(self._h, _p(imgs), n, w, h, ch, w * h * ch, w * ch, *quality, _p(out), stride, _p(nbytes)),
+                    name)
         return [out[i, :nbytes[i]].tobytes() for i in range(n)]
+
+    def jpeg_encode_batch_dev(self, d_src: int, n_images: int, width: int, height: int, channels: int, src_image_stride: int,
+                              src_row_stride: int, quality: int, d_out: int, out_stride: int, d_out_bytes: int):
+        """cv::imencode(".jpg") of images resident in HBM: file i at d_out + i * out_stride, its size in d_out_bytes[i]."""
+        self._encode_batch_dev("jpeg", (quality,), d_src, n_images, width, height, channels, src_image_stride, src_row_stride, d_out,
+                               out_stride, d_out_bytes)
+
+    def jpeg_encode(self, images, quality: int = 0, out_stride: int | None = None):
+        """cv::imencode(".jpg", img, quality) of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
+        return self._encode("jpeg", (quality,), images, out_stride)
 
     def png_encode_batch_dev(self, d_src: int, n_images: int, width: int, height: int, channels: int, src_image_stride: int,
                              src_row_stride: int, d_out: int, out_stride: int, d_out_bytes: int):
         """cv::imencode(".png") of images resident in HBM: file i at d_out + i * out_stride, its size in d_out_bytes[i]."""
-        self._check(lib().vsf_png_encode_batch_dev(self._h, _p(d_src), n_images, width, height, channels, src_image_stride,
-                                                   src_row_stride, _p(d_out), out_stride, _p(d_out_bytes)),
-                    "vsf_png_encode_batch_dev")
+        self._encode_batch_dev("png", (), d_src, n_images, width, height, channels, src_image_stride, src_row_stride, d_out, out_stride,
+                               d_out_bytes)
 
     def png_encode(self, images, out_stride: int | None = None):
         """cv::imencode(".png", img) of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
-        imgs = np.ascontiguousarray(np.stack([np.asarray(i) for i in images]), dtype=np.uint8)
-        n, h, w = imgs.shape[:3]
-        ch = 1 if imgs.ndim == 3 else imgs.shape[3]
-        stride = png_encode_capacity(w, h, ch) if out_stride is None else out_stride
-        out = np.zeros((n, stride), np.uint8)
-        nbytes = np.zeros(n, np.int32)
-        self._check(lib().vsf_png_encode(self._h, _p(imgs), n, w, h, ch, w * h * ch, w * ch, _p(out), stride, _p(nbytes)),
-                    "vsf_png_encode")
-        return [out[i, :nbytes[i]].tobytes() for i in range(n)]
+        return self._encode("png", (), images, out_stride)
 
     def bayer_bg_to_gray_batch_dev(self, d_src: int, n_images: int, width: int, height: int, src_image_stride: int,
                                    src_row_stride: int, d_dst: int, dst_image_stride: int, dst_row_stride: int):

@@ -616,6 +616,25 @@ __global__ __launch_bounds__(256) void observe_pack_kernel(VsfObserveArgs a) {
   for (uint32_t w = blockIdx.x * 256u + threadIdx.x; w < words; w += gridDim.x * 256u) dst[w] = src[w];
 }
 
+constexpr int kThreads = 256;  // of files_home_kernel: the queue's debug files go home; it knows nothing of their format
+__global__ __launch_bounds__(kThreads) void files_home_kernel(const uint8_t* __restrict__ files, size_t file_stride,
+                                                              const int32_t* __restrict__ nbytes, uint8_t* __restrict__ ring,
+                                                              size_t slot_stride, size_t file_off, int which, int slot0, int depth,
+                                                              const VsfObserveFrame* __restrict__ frames,
+                                                              const uint8_t* __restrict__ results, size_t result_stride) {
+  const int i = blockIdx.y;
+  // header word 14 of the frame's result (written by the drawing kernels in front of this one): bit `which` says whether the frame
+  // has this image at all; a frame without it sends nothing home (its canvas holds whatever an earlier batch left there)
+  const uint32_t flags = reinterpret_cast<const uint32_t*>(results + (size_t)frames[i].out_slot * result_stride)[14];
+  const int32_t n = (flags >> which) & 1u ? nbytes[i] : 0;
+  uint8_t* slot = ring + (size_t)((slot0 + i) % depth) * slot_stride;
+  if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int32_t*>(slot)[which] = n;
+  const size_t vecs = n > 0 ? ((size_t)n + 15) / 16 : 0;  // (both sides are 16-byte aligned and padded)
+  const uint4* src = reinterpret_cast<const uint4*>(files + (size_t)i * file_stride);
+  uint4* dst = reinterpret_cast<uint4*>(slot + file_off);
+  for (size_t v = (size_t)blockIdx.x * kThreads + threadIdx.x; v < vecs; v += (size_t)gridDim.x * kThreads) dst[v] = src[v];
+}
+
 }  // namespace
 
 void vsf_launch_stereo_residuals(const vsf_keypoint* d_kp, const vsf_dmatch* d_matches, const int32_t* d_nmatches,
@@ -693,4 +712,11 @@ hipError_t vsf_prepare_sort_kernels(int lds_limit) {
 void vsf_launch_observe_pack(const VsfObserveArgs& a, int max_pairs_per_frame, hipStream_t s) {
   // sections: 0 VisionFeature, 1 cv::KeyPoint, 2 descriptors, 3.. one per pair; up to 16 chunks of workgroups each; z = frame
   hipLaunchKernelGGL(observe_pack_kernel, dim3(a.n_frames > 8 ? 4 : 16, 3 + max_pairs_per_frame, a.n_frames), dim3(256), 0, s, a);
+}
+
+void vsf_launch_files_home(const uint8_t* d_files, size_t file_stride, const int32_t* d_bytes, int n, uint8_t* h_ring,
+                           size_t slot_stride, size_t file_off, int which, int slot0, int depth, const VsfObserveFrame* frames,
+                           const uint8_t* results, size_t result_stride, hipStream_t s) {
+  hipLaunchKernelGGL(files_home_kernel, dim3(16, (unsigned)n), dim3(kThreads), 0, s, d_files, file_stride, d_bytes, h_ring,
+                     slot_stride, file_off, which, slot0, depth, frames, results, result_stride);
 }

@@ -410,51 +410,38 @@ __global__ __launch_bounds__(kThreads) void jpeg_enc_stuff_kernel(VsfJpegEncHead
   }
 }
 
-__global__ __launch_bounds__(kThreads) void jpeg_files_home_kernel(const uint8_t* __restrict__ files, size_t file_stride,
-                                                                   const int32_t* __restrict__ nbytes, uint8_t* __restrict__ ring,
-                                                                   size_t slot_stride, size_t file_off, int which, int slot0, int depth,
-                                                                   const VsfObserveFrame* __restrict__ frames,
-                                                                   const uint8_t* __restrict__ results, size_t result_stride) {
-  const int i = blockIdx.y;
-  // header word 14 of the frame's result (written by the drawing kernels in front of this one): bit `which` says whether the frame
-  // has this image at all; a frame without it sends nothing home (its canvas holds whatever an earlier batch left there)
-  const uint32_t flags = reinterpret_cast<const uint32_t*>(results + (size_t)frames[i].out_slot * result_stride)[14];
-  const int32_t n = (flags >> which) & 1u ? nbytes[i] : 0;
-  uint8_t* slot = ring + (size_t)((slot0 + i) % depth) * slot_stride;
-  if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int32_t*>(slot)[which] = n;
-  const size_t vecs = n > 0 ? ((size_t)n + 15) / 16 : 0;  // (both sides are 16-byte aligned and padded)
-  const uint4* src = reinterpret_cast<const uint4*>(files + (size_t)i * file_stride);
-  uint4* dst = reinterpret_cast<uint4*>(slot + file_off);
-  for (size_t v = (size_t)blockIdx.x * kThreads + threadIdx.x; v < vecs; v += (size_t)gridDim.x * kThreads) dst[v] = src[v];
+// Where everything sits in the scratch of a job: coefficients | bit offsets | totals | AC bits | streams, each part a multiple of
+// 16 bytes.  The ONE statement of it: the need and the launcher both read it.
+struct JeLayout {
+  size_t blocks;         // of the whole batch
+  size_t stream_stride;  // bytes between the images' scans before stuffing: the worst case or what a file may take, whichever is less
+  size_t off_bit_off, off_tot_bits, off_ac_bits, off_stream, total;  // (the coefficients start at 0)
+};
+
+JeLayout layout(const VsfEncodeJob& job) {
+  JeLayout L;
+  const size_t per_image = vsf_jpeg_enc_blocks(job.width, job.height, job.channels), worst = per_image * VSF_JPEG_ENC_BLOCK_BYTES;
+  L.blocks = per_image * (size_t)job.n;
+  L.stream_stride = ((worst < job.cap() ? worst : job.cap()) + 16 + 15) & ~(size_t)15;
+  L.off_bit_off = L.blocks * 128;
+  L.off_tot_bits = L.off_bit_off + ((L.blocks * 8 + 15) & ~(size_t)15);
+  L.off_ac_bits = L.off_tot_bits + (((size_t)job.n * 8 + 15) & ~(size_t)15);
+  L.off_stream = L.off_ac_bits + ((L.blocks * 4 + 15) & ~(size_t)15);
+  L.total = L.off_stream + (size_t)job.n * L.stream_stride;
+  return L;
 }
 
 }  // namespace
 
-void vsf_launch_jpeg_files_home(const uint8_t* d_files, size_t file_stride, const int32_t* d_bytes, int n, uint8_t* h_ring,
-                                size_t slot_stride, size_t file_off, int which, int slot0, int depth, const VsfObserveFrame* frames,
-                                const uint8_t* results, size_t result_stride, hipStream_t s) {
-  hipLaunchKernelGGL(jpeg_files_home_kernel, dim3(16, (unsigned)n), dim3(kThreads), 0, s, d_files, file_stride, d_bytes, h_ring,
-                     slot_stride, file_off, which, slot0, depth, frames, results, result_stride);
-}
+size_t vsf_jpeg_enc_scratch_need(const VsfEncodeJob& job) { return layout(job).total; }
 
-size_t vsf_jpeg_enc_stream_stride(int width, int height, int channels, size_t out_stride) {
-  const size_t worst = vsf_jpeg_enc_blocks(width, height, channels) * VSF_JPEG_ENC_BLOCK_BYTES;
-  return ((worst < out_stride ? worst : out_stride) + 16 + 15) & ~(size_t)15;
-}
+int vsf_jpeg_enc_launches() { return 4; }  // (dct, scan, pack, stuff: the launches below)
 
-size_t vsf_jpeg_enc_scratch_bytes(int n, int width, int height, int channels, size_t out_stride) {
-  const size_t blocks = vsf_jpeg_enc_blocks(width, height, channels) * (size_t)n;
-  // coefficients | bit offsets | totals | AC bits | streams (each part a multiple of 16 bytes)
-  return blocks * 128 + ((blocks * 8 + 15) & ~(size_t)15) + (((size_t)n * 8 + 15) & ~(size_t)15) + ((blocks * 4 + 15) & ~(size_t)15) +
-         (size_t)n * vsf_jpeg_enc_stream_stride(width, height, channels, out_stride);
-}
-
-void vsf_launch_jpeg_encode(const uint8_t* d_src, int n, int width, int height, int channels, size_t src_image_stride,
-                            size_t src_row_stride, int quality, void* d_scratch, uint8_t* d_out, size_t out_stride,
-                            int32_t* d_out_bytes, int32_t* d_status, hipStream_t s, size_t out_cap) {
-  if (out_cap == 0 || out_cap > out_stride) out_cap = out_stride;
+void vsf_jpeg_enc_launch(const VsfEncodeJob& job, const uint8_t* d_src, void* d_scratch, uint8_t* d_out, int32_t* d_out_bytes,
+                         int32_t* d_status, hipStream_t s) {
+  const size_t out_cap = job.cap();
   VsfJpegEncTables tab;
-  vsf_jpeg_enc_quant(quality, tab.quant);
+  vsf_jpeg_enc_quant(job.quality, tab.quant);
   vsf_jpeg_enc_codes(&tab);
   for (int t = 0; t < 2; t++)
     for (int i = 0; i < 64; i++) {
@@ -462,33 +449,24 @@ void vsf_launch_jpeg_encode(const uint8_t* d_src, int n, int width, int height, 
       tab.recip[t][i] = (uint32_t)(((1ull << 32) + q - 1) / q);
     }
   VsfJpegEncHeader hdr;
-  hdr.len = vsf_jpeg_enc_header(width, height, channels, quality, hdr.bytes);
-  EncGeom g;
-  g.n = n;
-  g.w = width;
-  g.h = height;
-  g.channels = channels;
-  g.bw = channels == 3 ? (width + 15) / 16 : (width + 7) / 8;
-  g.bh = channels == 3 ? (height + 15) / 16 : (height + 7) / 8;
-  g.blocks = (uint32_t)vsf_jpeg_enc_blocks(width, height, channels);
-  g.src_image_stride = src_image_stride;
-  g.src_row_stride = src_row_stride;
-  const size_t blocks = (size_t)g.blocks * (size_t)n, stream_stride = vsf_jpeg_enc_stream_stride(width, height, channels, out_cap);
+  hdr.len = vsf_jpeg_enc_header(job.width, job.height, job.channels, job.quality, hdr.bytes);
+  const bool mcu16 = job.channels == 3;  // (EncGeom: blocks across / down, or 16x16 MCUs)
+  const EncGeom g{job.n, job.width, job.height, job.channels, mcu16 ? (job.width + 15) / 16 : (job.width + 7) / 8,
+                  mcu16 ? (job.height + 15) / 16 : (job.height + 7) / 8, (uint32_t)vsf_jpeg_enc_blocks(job.width, job.height, job.channels),
+                  job.src_image_stride, job.src_row_stride};
+  const JeLayout L = layout(job);
   uint8_t* p = static_cast<uint8_t*>(d_scratch);
   int16_t* coef = reinterpret_cast<int16_t*>(p);
-  p += blocks * 128;
-  uint64_t* bit_off = reinterpret_cast<uint64_t*>(p);
-  p += (blocks * 8 + 15) & ~(size_t)15;
-  uint64_t* tot_bits = reinterpret_cast<uint64_t*>(p);
-  p += ((size_t)n * 8 + 15) & ~(size_t)15;
-  uint32_t* ac_bits = reinterpret_cast<uint32_t*>(p);
-  p += (blocks * 4 + 15) & ~(size_t)15;
-  uint32_t* stream = reinterpret_cast<uint32_t*>(p);
-  const dim3 per_block((g.blocks + kThreads - 1) / kThreads, (unsigned)n);
+  uint64_t* bit_off = reinterpret_cast<uint64_t*>(p + L.off_bit_off);
+  uint64_t* tot_bits = reinterpret_cast<uint64_t*>(p + L.off_tot_bits);
+  uint32_t* ac_bits = reinterpret_cast<uint32_t*>(p + L.off_ac_bits);
+  uint32_t* stream = reinterpret_cast<uint32_t*>(p + L.off_stream);
+  const dim3 per_block((g.blocks + kThreads - 1) / kThreads, (unsigned)job.n), per_image((unsigned)job.n);
   hipLaunchKernelGGL(jpeg_enc_dct_kernel, per_block, dim3(kThreads), 0, s, d_src, g, tab, coef, ac_bits);
-  hipLaunchKernelGGL(jpeg_enc_scan_kernel, dim3((unsigned)n), dim3(kThreads), 0, s, g, tab, coef, ac_bits, bit_off, tot_bits, stream,
-                     stream_stride, hdr.len, out_cap, d_out_bytes, d_status);
-  hipLaunchKernelGGL(jpeg_enc_pack_kernel, per_block, dim3(kThreads), 0, s, g, tab, coef, bit_off, stream, stream_stride, d_out_bytes);
-  hipLaunchKernelGGL(jpeg_enc_stuff_kernel, dim3((unsigned)n), dim3(kThreads), 0, s, hdr, tot_bits,
-                     reinterpret_cast<const uint8_t*>(stream), stream_stride, d_out, out_stride, out_cap, d_out_bytes, d_status);
+  hipLaunchKernelGGL(jpeg_enc_scan_kernel, per_image, dim3(kThreads), 0, s, g, tab, coef, ac_bits, bit_off, tot_bits, stream,
+                     L.stream_stride, hdr.len, out_cap, d_out_bytes, d_status);
+  hipLaunchKernelGGL(jpeg_enc_pack_kernel, per_block, dim3(kThreads), 0, s, g, tab, coef, bit_off, stream, L.stream_stride, d_out_bytes);
+  hipLaunchKernelGGL(jpeg_enc_stuff_kernel, per_image, dim3(kThreads), 0, s, hdr, tot_bits, reinterpret_cast<const uint8_t*>(stream),
+                     L.stream_stride, d_out, job.out_stride, out_cap, d_out_bytes, d_status);
 }
+

@@ -514,23 +514,23 @@ struct PeLayout {
   size_t total;
 };
 
-PeLayout layout(int n, int width, int height, int channels, size_t src_image_stride, size_t src_row_stride, size_t out_cap) {
+PeLayout layout(const VsfEncodeJob& job) {
   PeLayout L;
   PeGeom& g = L.g;
-  g.n = n;
-  g.w = width;
-  g.h = height;
-  g.channels = channels;
-  g.rowbytes1 = (uint32_t)width * (uint32_t)channels + 1u;
-  g.nf = (uint32_t)vsf_png_enc_filtered_bytes(width, height, channels);
+  g.n = job.n;
+  g.w = job.width;
+  g.h = job.height;
+  g.channels = job.channels;
+  g.rowbytes1 = (uint32_t)job.width * (uint32_t)job.channels + 1u;
+  g.nf = (uint32_t)vsf_png_enc_filtered_bytes(job.width, job.height, job.channels);
   g.tiles = (g.nf + kTile - 1) / kTile;
   g.max_blocks = g.nf / kBlockSyms + 1;
-  g.src_image_stride = src_image_stride;
-  g.src_row_stride = src_row_stride;
+  g.src_image_stride = job.src_image_stride;
+  g.src_row_stride = job.src_row_stride;
   g.f_stride = (size_t)g.tiles * kTile + kTile;
   const size_t worst = (size_t)vsf_png_enc_stream_bound(g.nf);
-  g.stream_stride = align_up((worst < out_cap ? worst : out_cap) + 16, 16);
-  const size_t N = (size_t)n;
+  g.stream_stride = align_up((worst < job.cap() ? worst : job.cap()) + 16, 16);
+  const size_t N = (size_t)job.n;
   const size_t sizes[13] = {N * g.f_stride,
                             N * g.tiles * 4,
                             N * g.tiles * 4,
@@ -555,15 +555,15 @@ PeLayout layout(int n, int width, int height, int channels, size_t src_image_str
 
 }  // namespace
 
-size_t vsf_png_enc_scratch_need(int n, int width, int height, int channels, size_t out_stride) {
-  return layout(n, width, height, channels, 0, 0, out_stride).total;
-}
+size_t vsf_png_enc_scratch_need(const VsfEncodeJob& job) { return layout(job).total; }
 
-void vsf_launch_png_encode(const uint8_t* d_src, int n, int width, int height, int channels, size_t src_image_stride,
-                           size_t src_row_stride, void* d_scratch, uint8_t* d_out, size_t out_stride, int32_t* d_out_bytes,
-                           int32_t* d_status, hipStream_t s, size_t out_cap) {
-  if (out_cap == 0 || out_cap > out_stride) out_cap = out_stride;
-  const PeLayout L = layout(n, width, height, channels, src_image_stride, src_row_stride, out_cap);
+int vsf_png_enc_launches() { return 9; }  // (filter .. file: the launches below)
+
+void vsf_png_enc_launch(const VsfEncodeJob& job, const uint8_t* d_src, void* d_scratch, uint8_t* d_out, int32_t* d_out_bytes,
+                        int32_t* d_status, hipStream_t s) {
+  const size_t out_cap = job.cap();
+  const int n = job.n;
+  const PeLayout L = layout(job);
   const PeGeom& g = L.g;
   uint8_t* p = static_cast<uint8_t*>(d_scratch);
   PeBufs b;
@@ -581,7 +581,7 @@ void vsf_launch_png_encode(const uint8_t* d_src, int n, int width, int height, i
   b.z_bytes = reinterpret_cast<uint32_t*>(p + L.off[11]);
   b.stream = reinterpret_cast<uint32_t*>(p + L.off[12]);
   VsfPngEncConsts k;
-  vsf_png_enc_consts(width, height, channels, &k);
+  vsf_png_enc_consts(job.width, job.height, job.channels, &k);
   const dim3 per_tile((g.tiles + kThreads - 1) / kThreads, (unsigned)n), per_image((unsigned)n), per_block(g.max_blocks, (unsigned)n);
   hipLaunchKernelGGL(png_enc_filter_kernel, per_tile, dim3(kThreads), 0, s, d_src, g, k.filter, b);
   hipLaunchKernelGGL(png_enc_runs_kernel, per_image, dim3(kThreads), 0, s, g, b);
@@ -591,5 +591,6 @@ void vsf_launch_png_encode(const uint8_t* d_src, int n, int width, int height, i
   hipLaunchKernelGGL(png_enc_plan_kernel, per_block, dim3(64), 0, s, g, b);
   hipLaunchKernelGGL(png_enc_place_kernel, per_image, dim3(kThreads), 0, s, g, b, k, out_cap, d_out_bytes, d_status);
   hipLaunchKernelGGL(png_enc_write_kernel, per_block, dim3(kThreads), 0, s, g, b, d_out_bytes);
-  hipLaunchKernelGGL(png_enc_file_kernel, per_image, dim3(kThreads), 0, s, g, b, k, d_out, out_stride, out_cap, d_out_bytes);
+  hipLaunchKernelGGL(png_enc_file_kernel, per_image, dim3(kThreads), 0, s, g, b, k, d_out, job.out_stride, out_cap, d_out_bytes);
 }
+

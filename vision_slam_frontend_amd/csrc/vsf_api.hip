@@ -583,10 +583,8 @@ void vsf_destroy(vsf_ctx* ctx) {
   hipFree(ctx->dr_canv);
   hipFree(ctx->dr_buf);
   if (ctx->dr_uploaded) hipEventDestroy(ctx->dr_uploaded);
-  hipFree(ctx->je_scratch);
-  hipFree(ctx->je_buf);
-  hipFree(ctx->pe_scratch);
-  hipFree(ctx->pe_buf);
+  hipFree(ctx->encode.scratch);
+  hipFree(ctx->encode.staging);
   free_decode_buffers(ctx->ingest_scratch);
   for (VsfStaging& stage : ctx->ingest_stage) free_decode_buffers(stage);
   free_retired(ctx);

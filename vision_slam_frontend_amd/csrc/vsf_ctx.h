@@ -153,6 +153,11 @@ struct vsf_ctx {
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
     bool bayer = false;          // compressed frames: the decoded images are bayer_rggb8 mosaics
   };
+  struct DebugForm {  // how the queue's debug images leave: raw canvases, or files of ONE kind
+    int kind = VSF_FILE_NONE;  // VSF_FILE_JPEG / VSF_FILE_PNG
+    int quality = 0;           // JPEG: 1 .. 100; PNG: 1
+    bool operator==(const DebugForm& o) const { return kind == o.kind && quality == o.quality; }
+  };
   struct Observe {
     bool ready = false;
     int frame_life = 0;
@@ -170,18 +175,19 @@ struct vsf_ctx {
     uint8_t* h_dbg = nullptr;
     uint32_t* h_col = nullptr;
     int64_t col_ring = 0, col_generated = 0, col_retired = 0;
-    // vsf_observe_set_debug_jpeg: the canvases stay on the device; each batch's tail encodes them (k_jpeg_enc.hip) into device
-    // slots and a kernel carries the FILES into the pinned ring h_jpg [depth][jpg_slot].  A slot: i32 stereo bytes, i32 match
-    // bytes, then (16-byte aligned) the stereo file at jpg_off[0] and the match file at jpg_off[1], each with room for
-    // vsf_jpeg_encode_capacity() bytes.  h_dbg does not exist then.
-    int dbg_jpeg = 0;                 // quality the queue was built with (0: raw canvases)
-    bool dbg_png = false;             // vsf_observe_set_debug_png: the files are PNG (k_png_enc.hip); same ring, slots by its bound
-    size_t jpg_off[2] = {0, 0}, jpg_cap[2] = {0, 0}, jpg_slot = 0;
-    uint8_t* d_jpg = nullptr;         // [bmax][jpg_slot]
-    int32_t* d_jpg_n = nullptr;       // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
-    uint8_t* jpg_scratch = nullptr;   // the encoder's scratch for bmax stereo canvases
-    uint8_t* h_jpg = nullptr;
-    int64_t stat_jpeg_commands = 0;   // launches the compressed debug path issued (vsf_observe_stats)
+    // vsf_observe_set_debug_jpeg / _png: the canvases stay on the device; each batch's tail encodes them (k_jpeg_enc.hip /
+    // k_png_enc.hip) into device slots and a kernel carries the FILES into the pinned ring h_ring [depth][slot].  A slot: i32 stereo
+    // bytes, i32 match bytes, then (16-byte aligned) the stereo file at off[0] and the match file at off[1], each with room for
+    // cap[] = vsf_encode_capacity() bytes.  h_dbg does not exist then.
+    struct DebugFiles {
+      DebugForm form;                // what the queue was built with (kind 0: raw canvases, nothing below exists)
+      size_t off[2] = {0, 0}, cap[2] = {0, 0}, slot = 0;
+      uint8_t* d_slots = nullptr;    // [bmax][slot]
+      int32_t* d_bytes = nullptr;    // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
+      uint8_t* d_scratch = nullptr;  // the encoder's scratch for bmax canvases of either size
+      uint8_t* h_ring = nullptr;
+      int64_t stat_commands = 0;     // launches the compressed debug path issued (vsf_observe_stats)
+    } files;
     int depth = 0;      // frames that may be submitted and not collected
     int bmax = 0;       // frames per batch at most
     int ring = 0;       // descriptor sets [0, ring): the kept left frames (frame g in set g % ring); [ring, ring + bmax): the
@@ -231,8 +237,7 @@ struct vsf_ctx {
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
-  bool ob_debug_png = false;  // vsf_observe_set_debug_png: ... as PNG files (never together with the JPEG form)
-  int ob_debug_jpeg = 0;  // vsf_observe_set_debug_jpeg: ... and hands them out as JPEG files of this quality (0: raw)
+  DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // vsf_draw_canvases(_dev) (k_draw.hip): per-pixel winners (all zero between calls: the resolve clears what it read),
   // the canvas table (device, and its host image until the upload has left: dr_uploaded), the host call's staging
@@ -250,14 +255,7 @@ struct vsf_ctx {
   VsfStaging ingest_stage[2];
   int ingest_flip = 0;
   VsfDecodeScratch ingest_scratch;
-  uint8_t* je_scratch = nullptr;  // vsf_jpeg_encode_batch_dev: coefficients, bit positions, the scans before stuffing
-  size_t je_scratch_cap = 0;
-  uint8_t* je_buf = nullptr;      // vsf_jpeg_encode (host pointers): images | files | byte counts on the device
-  size_t je_buf_cap = 0;
-  uint8_t* pe_scratch = nullptr;  // vsf_png_encode_batch_dev: filtered bytes, symbols, block plans, the zlib streams
-  size_t pe_scratch_cap = 0;
-  uint8_t* pe_buf = nullptr;      // vsf_png_encode (host pointers): images | files | byte counts on the device
-  size_t pe_buf_cap = 0;
+  VsfEncodeScratch encode;  // vsf_jpeg_encode* / vsf_png_encode*
   uint8_t* mh_desc = nullptr;  // host-API descriptor staging: 2 sets
   int32_t* mh_counts = nullptr;
   vsf_dmatch* mh_matches = nullptr;

@@ -15,7 +15,7 @@ using namespace vsfi;
 
 namespace {
 
-// One policy for everything a decode outgrows: a quarter of headroom, and no wait for the GPU -- the outgrown buffer is
+// One policy for everything a decode or an encode outgrows: a quarter of headroom, and no wait for the GPU -- the outgrown buffer is
 // retired (an upload or a decode already queued may still be using it) and released by the next vsf_sync, like every other
 // scratch a *_dev call outgrows.
 template <class T>
@@ -77,6 +77,61 @@ vsf_status decode_gray_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* f
   ctx->ingest_flip ^= 1;
   VSF_STICKY();
   return record_ingest_done(ctx);  // (a pipelined extract waits for its images, as after the Bayer step)
+}
+
+// ---- the ONE way pixels leave the device as files: vsf_jpeg_encode* and vsf_png_encode* are argument adapters of these two ----
+bool encode_job_ok(const VsfEncodeJob& j) {  // what both forms of the call refuse as VSF_ERR_INVALID_ARG
+  return j.n >= 1 && j.n <= 65535 && j.width >= 1 && j.height >= 1 && j.width <= 65535 && j.height <= 65535 &&
+         (j.channels == 1 || j.channels == 3) && j.quality >= 0 && j.quality <= 100 && j.out_stride >= 1 &&
+         j.src_row_stride >= (size_t)j.width * (size_t)j.channels && j.src_image_stride >= j.src_row_stride * (size_t)j.height;
+}
+
+vsf_status encode_batch_dev(vsf_ctx* ctx, VsfEncodeJob job, const uint8_t* d_src, uint8_t* d_out, int32_t* d_out_bytes) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !d_src || !d_out || !d_out_bytes || !encode_job_ok(job) || ((uintptr_t)d_out_bytes & 3)) return VSF_ERR_INVALID_ARG;
+  // the byte count of a file is an int32, the block / byte index of the kernels a u32
+  if (vsf_encode_capacity(job.kind, job.width, job.height, job.channels) > 0x7FFFFFFFu) return VSF_ERR_UNSUPPORTED;
+  VSF_HIP(hipSetDevice(ctx->device));
+  if (job.quality == 0) job.quality = 95;
+  VsfEncodeScratch& e = ctx->encode;
+  const vsf_status gs = grow_decode_scratch(ctx, e.scratch, e.scratch_cap, vsf_encode_scratch_need(job));  // (no wait)
+  if (gs != VSF_OK) return gs;
+  vsf_launch_encode(job, d_src, e.scratch, d_out, d_out_bytes, ctx->d_status, ctx->stream);
+  VSF_STICKY();
+  return VSF_OK;
+}
+
+vsf_status encode_host(vsf_ctx* ctx, VsfEncodeJob job, const uint8_t* src, uint8_t* out, int32_t* out_bytes) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !src || !out || !out_bytes || !encode_job_ok(job)) return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // device staging: images (packed rows) | files | byte counts
+  const size_t row = (size_t)job.width * (size_t)job.channels, n = (size_t)job.n;
+  const size_t img_bytes = (row * (size_t)job.height + 15) & ~(size_t)15, files_bytes = (n * job.out_stride + 15) & ~(size_t)15;
+  const size_t need = n * (img_bytes + sizeof(int32_t)) + files_bytes;
+  VsfEncodeScratch& e = ctx->encode;
+  if (need > e.staging_cap) {
+    const vsf_status gs = grow_scratch(ctx, e.staging, need);
+    if (gs != VSF_OK) return gs;
+    e.staging_cap = need;
+  }
+  uint8_t* d_img = e.staging;
+  uint8_t* d_files = d_img + n * img_bytes;
+  int32_t* d_bytes = reinterpret_cast<int32_t*>(d_files + files_bytes);
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(d_img + i * img_bytes, row, src + i * job.src_image_stride, job.src_row_stride, row, (size_t)job.height,
+                             hipMemcpyHostToDevice, ctx->stream));
+  job.src_image_stride = img_bytes;
+  job.src_row_stride = row;
+  vsf_status st = encode_batch_dev(ctx, job, d_img, d_files, d_bytes);
+  if (st != VSF_OK) return st;
+  VSF_HIP(hipMemcpyAsync(out_bytes, d_bytes, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  st = check_status_word(ctx);  // synchronises
+  if (st != VSF_OK && st != VSF_ERR_CAPACITY) return st;
+  for (size_t i = 0; i < n; i++)
+    if (out_bytes[i] > 0)
+      VSF_HIP(hipMemcpy(out + i * job.out_stride, d_files + i * job.out_stride, (size_t)out_bytes[i], hipMemcpyDeviceToHost));
+  return st;
 }
 
 }  // namespace
@@ -204,31 +259,22 @@ vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, co
   return VSF_OK;
 }
 
-// cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) for a batch of equally sized images (k_jpeg_enc.hip): the way out
-// of the device for pixels, as the decoders above are the way in.  Asynchronous on the context's stream.
+// cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) / cv::imencode(".png", img) for a batch of equally sized images
+// (k_jpeg_enc.hip, k_png_enc.hip): the way out of the device for pixels, as the decoders above are the way in.  Asynchronous on the
+// context's stream.
+// (a job as the caller gave it: quality 0 = 95, and a PNG job carries 0; out_cap 0: a file may take all of its slot)
 vsf_status vsf_jpeg_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int channels,
                                      size_t src_image_stride, size_t src_row_stride, int quality, uint8_t* d_out,
                                      size_t out_stride, int32_t* d_out_bytes) {
-  VsfErrorScope scope_(ctx);
-  if (!ctx || !d_src || !d_out || !d_out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 ||
-      width > 65535 || height > 65535 || (channels != 1 && channels != 3) || quality < 0 || quality > 100)
-    return VSF_ERR_INVALID_ARG;
-  if (src_row_stride < (size_t)width * (size_t)channels || src_image_stride < src_row_stride * (size_t)height || out_stride < 1 ||
-      ((uintptr_t)d_out_bytes & 3))
-    return VSF_ERR_INVALID_ARG;
-  // the byte count of a file is an int32, the block index of the kernels a u32
-  if (vsf_jpeg_encode_capacity(width, height, channels) > 0x7FFFFFFFu) return VSF_ERR_UNSUPPORTED;
-  VSF_HIP(hipSetDevice(ctx->device));
-  const size_t need = vsf_jpeg_enc_scratch_bytes(n_images, width, height, channels, out_stride);
-  if (need > ctx->je_scratch_cap) {  // (no wait: the outgrown buffer is retired)
-    const vsf_status gs = grow_scratch(ctx, ctx->je_scratch, need + need / 4);
-    if (gs != VSF_OK) return gs;
-    ctx->je_scratch_cap = need + need / 4;
-  }
-  vsf_launch_jpeg_encode(d_src, n_images, width, height, channels, src_image_stride, src_row_stride, quality ? quality : 95,
-                         ctx->je_scratch, d_out, out_stride, d_out_bytes, ctx->d_status, ctx->stream);
-  VSF_STICKY();
-  return VSF_OK;
+  return encode_batch_dev(ctx, {VSF_FILE_JPEG, n_images, width, height, channels, src_image_stride, src_row_stride, quality, out_stride, 0},
+                          d_src, d_out, d_out_bytes);
+}
+
+vsf_status vsf_png_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int channels,
+                                    size_t src_image_stride, size_t src_row_stride, uint8_t* d_out, size_t out_stride,
+                                    int32_t* d_out_bytes) {
+  return encode_batch_dev(ctx, {VSF_FILE_PNG, n_images, width, height, channels, src_image_stride, src_row_stride, 0, out_stride, 0},
+                          d_src, d_out, d_out_bytes);
 }
 
 // The same for host pointers, synchronous: images up, files and byte counts back.  out_bytes[i] = -1 and VSF_ERR_CAPACITY for a
@@ -236,102 +282,14 @@ vsf_status vsf_jpeg_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_i
 vsf_status vsf_jpeg_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int channels,
                            size_t src_image_stride, size_t src_row_stride, int quality, uint8_t* out, size_t out_stride,
                            int32_t* out_bytes) {
-  VsfErrorScope scope_(ctx);
-  if (!ctx || !src || !out || !out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 65535 ||
-      height > 65535 || (channels != 1 && channels != 3) || out_stride < 1 || quality < 0 || quality > 100)
-    return VSF_ERR_INVALID_ARG;
-  const size_t row = (size_t)width * (size_t)channels;
-  if (src_row_stride < row || src_image_stride < src_row_stride * (size_t)height) return VSF_ERR_INVALID_ARG;
-  VSF_HIP(hipSetDevice(ctx->device));
-  // device staging: images (packed rows) | files | byte counts
-  const size_t img_bytes = (row * (size_t)height + 15) & ~(size_t)15, files_bytes = ((size_t)n_images * out_stride + 15) & ~(size_t)15;
-  const size_t need = (size_t)n_images * (img_bytes + sizeof(int32_t)) + files_bytes;
-  if (need > ctx->je_buf_cap) {
-    const vsf_status gs = grow_scratch(ctx, ctx->je_buf, need);
-    if (gs != VSF_OK) return gs;
-    ctx->je_buf_cap = need;
-  }
-  uint8_t* d_img = ctx->je_buf;
-  uint8_t* d_files = d_img + (size_t)n_images * img_bytes;
-  int32_t* d_bytes = reinterpret_cast<int32_t*>(d_files + files_bytes);
-  for (int i = 0; i < n_images; i++)
-    VSF_HIP(hipMemcpy2DAsync(d_img + (size_t)i * img_bytes, row, src + (size_t)i * src_image_stride, src_row_stride, row,
-                             (size_t)height, hipMemcpyHostToDevice, ctx->stream));
-  vsf_status st = vsf_jpeg_encode_batch_dev(ctx, d_img, n_images, width, height, channels, img_bytes, row, quality, d_files,
-                                            out_stride, d_bytes);
-  if (st != VSF_OK) return st;
-  VSF_HIP(hipMemcpyAsync(out_bytes, d_bytes, (size_t)n_images * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  st = check_status_word(ctx);  // synchronises
-  if (st != VSF_OK && st != VSF_ERR_CAPACITY) return st;
-  for (int i = 0; i < n_images; i++)
-    if (out_bytes[i] > 0)
-      VSF_HIP(hipMemcpy(out + (size_t)i * out_stride, d_files + (size_t)i * out_stride, (size_t)out_bytes[i], hipMemcpyDeviceToHost));
-  return st;
+  return encode_host(ctx, {VSF_FILE_JPEG, n_images, width, height, channels, src_image_stride, src_row_stride, quality, out_stride, 0},
+                     src, out, out_bytes);
 }
 
-// cv::imencode(".png", img) for a batch of equally sized images (k_png_enc.hip): the way out
-// of the device for pixels, as the decoders above are the way in.  Asynchronous on the context's stream.
-vsf_status vsf_png_encode_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int channels,
-                                     size_t src_image_stride, size_t src_row_stride, uint8_t* d_out,
-                                     size_t out_stride, int32_t* d_out_bytes) {
-  VsfErrorScope scope_(ctx);
-  if (!ctx || !d_src || !d_out || !d_out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 ||
-      width > 65535 || height > 65535 || (channels != 1 && channels != 3))
-    return VSF_ERR_INVALID_ARG;
-  if (src_row_stride < (size_t)width * (size_t)channels || src_image_stride < src_row_stride * (size_t)height || out_stride < 1 ||
-      ((uintptr_t)d_out_bytes & 3))
-    return VSF_ERR_INVALID_ARG;
-  // the byte count of a file is an int32, the byte index of the kernels a u32
-  if (vsf_png_encode_capacity(width, height, channels) > 0x7FFFFFFFu) return VSF_ERR_UNSUPPORTED;
-  VSF_HIP(hipSetDevice(ctx->device));
-  const size_t need = vsf_png_enc_scratch_need(n_images, width, height, channels, out_stride);
-  if (need > ctx->pe_scratch_cap) {  // (no wait: the outgrown buffer is retired)
-    const vsf_status gs = grow_scratch(ctx, ctx->pe_scratch, need + need / 4);
-    if (gs != VSF_OK) return gs;
-    ctx->pe_scratch_cap = need + need / 4;
-  }
-  vsf_launch_png_encode(d_src, n_images, width, height, channels, src_image_stride, src_row_stride,
-                         ctx->pe_scratch, d_out, out_stride, d_out_bytes, ctx->d_status, ctx->stream);
-  VSF_STICKY();
-  return VSF_OK;
-}
-
-// The same for host pointers, synchronous: images up, files and byte counts back.  out_bytes[i] = -1 and VSF_ERR_CAPACITY for a
-// file that does not fit out_stride.
 vsf_status vsf_png_encode(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int channels,
-                           size_t src_image_stride, size_t src_row_stride, uint8_t* out, size_t out_stride,
-                           int32_t* out_bytes) {
-  VsfErrorScope scope_(ctx);
-  if (!ctx || !src || !out || !out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 65535 ||
-      height > 65535 || (channels != 1 && channels != 3) || out_stride < 1)
-    return VSF_ERR_INVALID_ARG;
-  const size_t row = (size_t)width * (size_t)channels;
-  if (src_row_stride < row || src_image_stride < src_row_stride * (size_t)height) return VSF_ERR_INVALID_ARG;
-  VSF_HIP(hipSetDevice(ctx->device));
-  // device staging: images (packed rows) | files | byte counts
-  const size_t img_bytes = (row * (size_t)height + 15) & ~(size_t)15, files_bytes = ((size_t)n_images * out_stride + 15) & ~(size_t)15;
-  const size_t need = (size_t)n_images * (img_bytes + sizeof(int32_t)) + files_bytes;
-  if (need > ctx->pe_buf_cap) {
-    const vsf_status gs = grow_scratch(ctx, ctx->pe_buf, need);
-    if (gs != VSF_OK) return gs;
-    ctx->pe_buf_cap = need;
-  }
-  uint8_t* d_img = ctx->pe_buf;
-  uint8_t* d_files = d_img + (size_t)n_images * img_bytes;
-  int32_t* d_bytes = reinterpret_cast<int32_t*>(d_files + files_bytes);
-  for (int i = 0; i < n_images; i++)
-    VSF_HIP(hipMemcpy2DAsync(d_img + (size_t)i * img_bytes, row, src + (size_t)i * src_image_stride, src_row_stride, row,
-                             (size_t)height, hipMemcpyHostToDevice, ctx->stream));
-  vsf_status st = vsf_png_encode_batch_dev(ctx, d_img, n_images, width, height, channels, img_bytes, row, d_files,
-                                            out_stride, d_bytes);
-  if (st != VSF_OK) return st;
-  VSF_HIP(hipMemcpyAsync(out_bytes, d_bytes, (size_t)n_images * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  st = check_status_word(ctx);  // synchronises
-  if (st != VSF_OK && st != VSF_ERR_CAPACITY) return st;
-  for (int i = 0; i < n_images; i++)
-    if (out_bytes[i] > 0)
-      VSF_HIP(hipMemcpy(out + (size_t)i * out_stride, d_files + (size_t)i * out_stride, (size_t)out_bytes[i], hipMemcpyDeviceToHost));
-  return st;
+                          size_t src_image_stride, size_t src_row_stride, uint8_t* out, size_t out_stride, int32_t* out_bytes) {
+  return encode_host(ctx, {VSF_FILE_PNG, n_images, width, height, channels, src_image_stride, src_row_stride, 0, out_stride, 0}, src,
+                     out, out_bytes);
 }
 
 }  // extern "C"

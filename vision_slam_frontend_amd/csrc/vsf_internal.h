@@ -385,23 +385,52 @@ struct VsfDecodeRuns {
 vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
                          bool force_serial, VsfDecodeRuns* out);
 void vsf_fill_runs(const VsfDecodeRuns& plan, const uint8_t* const* files, uint8_t* dst);
-// k_jpeg_enc.hip: the baseline JPEG encoder (cv::imencode(".jpg")).  d_scratch: vsf_jpeg_enc_scratch_bytes() bytes, 16-byte aligned.
-// out_cap: bytes a file may take of its slot (0: all out_stride of them).
-size_t vsf_jpeg_enc_scratch_bytes(int n, int width, int height, int channels, size_t out_stride);
-void vsf_launch_jpeg_encode(const uint8_t* d_src, int n, int width, int height, int channels, size_t src_image_stride,
-                            size_t src_row_stride, int quality, void* d_scratch, uint8_t* d_out, size_t out_stride,
-                            int32_t* d_out_bytes, int32_t* d_status, hipStream_t s, size_t out_cap = 0);
-// The queue's compressed debug images: file i (d_bytes[i] bytes at d_files + i * file_stride; nothing when negative) goes to
+// ---- one encode path for JPEG / PNG files (the C ABI's encoders and the ObserveImage queue's debug files) ----
+// cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) / cv::imencode(".png", img) of n equally sized images: image i
+// at d_src + i * src_image_stride, its file at d_out + i * out_stride and the file's size in d_out_bytes[i].
+struct VsfEncodeJob {
+  int kind = VSF_FILE_NONE;  // VSF_FILE_JPEG / VSF_FILE_PNG
+  int n = 0, width = 0, height = 0, channels = 0;
+  size_t src_image_stride = 0, src_row_stride = 0;
+  int quality = 0;     // JPEG: 1 .. 100; PNG: ignored
+  size_t out_stride = 0;
+  size_t out_cap = 0;  // bytes a file may take of its slot (0: all out_stride of them)
+  size_t cap() const { return out_cap == 0 || out_cap > out_stride ? out_stride : out_cap; }
+};
+// What each format brings (k_jpeg_enc.hip, k_png_enc.hip): the launches its launcher issues -- stated beside that launcher --,
+// the scratch a job needs (16- / 64-byte aligned; it reads the SAME layout and the same cap() as the launcher, so a buffer
+// sized for a job holds that job) and the launcher itself, asynchronous on `s`.
+int vsf_jpeg_enc_launches();
+size_t vsf_jpeg_enc_scratch_need(const VsfEncodeJob& job);
+void vsf_jpeg_enc_launch(const VsfEncodeJob& job, const uint8_t* d_src, void* d_scratch, uint8_t* d_out, int32_t* d_out_bytes,
+                         int32_t* d_status, hipStream_t s);
+int vsf_png_enc_launches();
+size_t vsf_png_enc_scratch_need(const VsfEncodeJob& job);
+void vsf_png_enc_launch(const VsfEncodeJob& job, const uint8_t* d_src, void* d_scratch, uint8_t* d_out, int32_t* d_out_bytes,
+                        int32_t* d_status, hipStream_t s);
+inline size_t vsf_encode_capacity(int kind, int w, int h, int ch) {
+  return kind == VSF_FILE_PNG ? vsf_png_encode_capacity(w, h, ch) : vsf_jpeg_encode_capacity(w, h, ch);
+}
+inline int vsf_encode_launches(int kind) { return kind == VSF_FILE_PNG ? vsf_png_enc_launches() : vsf_jpeg_enc_launches(); }
+inline size_t vsf_encode_scratch_need(const VsfEncodeJob& j) { return j.kind == VSF_FILE_PNG ? vsf_png_enc_scratch_need(j) : vsf_jpeg_enc_scratch_need(j); }
+inline void vsf_launch_encode(const VsfEncodeJob& j, const uint8_t* d_src, void* d_scratch, uint8_t* d_out, int32_t* d_out_bytes,
+                              int32_t* d_status, hipStream_t s) {
+  (j.kind == VSF_FILE_PNG ? vsf_png_enc_launch : vsf_jpeg_enc_launch)(j, d_src, d_scratch, d_out, d_out_bytes, d_status, s);
+}
+// What the encode calls of ONE context need: both encoders launch only on the context's stream, one call after the other, so
+// they share one scratch and one staging buffer.  A call that needs more takes a new allocation without waiting (grow_scratch
+// retires the outgrown buffer, which an encode already queued may still be using, until the next vsf_sync).  Bytes; never shrunk.
+struct VsfEncodeScratch {
+  uint8_t* scratch = nullptr;  // *_encode_batch_dev: the encoder's work buffers (a quarter of headroom when it grows)
+  uint8_t* staging = nullptr;  // the host-pointer calls: images | files | byte counts on the device (grown to the need)
+  size_t scratch_cap = 0, staging_cap = 0;
+};
+// The queue's debug files (k_frontend.hip): file i (d_bytes[i] bytes at d_files + i * file_stride; nothing when negative) goes to
 // h_ring + ((slot0 + i) % depth) * slot_stride + file_off and its size to the i32 at that slot + 4 * which.  16 bytes per lane.
 // A frame whose result header (results + frames[i].out_slot * result_stride, word 14) lacks bit `which` has no such image: size 0.
-void vsf_launch_jpeg_files_home(const uint8_t* d_files, size_t file_stride, const int32_t* d_bytes, int n, uint8_t* h_ring,
-                                size_t slot_stride, size_t file_off, int which, int slot0, int depth, const VsfObserveFrame* frames,
-                                const uint8_t* results, size_t result_stride, hipStream_t s);
-// k_png_enc.hip: the PNG encoder (cv::imencode(".png")).  d_scratch: vsf_png_enc_scratch_need() bytes, 64-byte aligned.  out_cap as above.
-size_t vsf_png_enc_scratch_need(int n, int width, int height, int channels, size_t out_stride);
-void vsf_launch_png_encode(const uint8_t* d_src, int n, int width, int height, int channels, size_t src_image_stride,
-                           size_t src_row_stride, void* d_scratch, uint8_t* d_out, size_t out_stride, int32_t* d_out_bytes,
-                           int32_t* d_status, hipStream_t s, size_t out_cap = 0);
+void vsf_launch_files_home(const uint8_t* d_files, size_t file_stride, const int32_t* d_bytes, int n, uint8_t* h_ring,
+                           size_t slot_stride, size_t file_off, int which, int slot0, int depth, const VsfObserveFrame* frames,
+                           const uint8_t* results, size_t result_stride, hipStream_t s);
 // The queue's ingest finish (k_ingest.hip): every image of [0, n) whose status word carries bit 1 (its decoder refused the
 // data) becomes all zero, `rows` rows of `pitch` bytes.
 void vsf_launch_ingest_finish(uint8_t* d_img, size_t image_stride, int pitch, int rows, const int32_t* d_status, int n,

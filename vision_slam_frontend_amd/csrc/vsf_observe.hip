@@ -222,10 +222,10 @@ void free_observe(vsf_ctx* ctx) {
   hipFree(o.dbg_prev_kp);
   hipFree(o.dbg_ints);
   if (o.h_dbg) hipHostFree(o.h_dbg);
-  hipFree(o.d_jpg);
-  hipFree(o.d_jpg_n);
-  hipFree(o.jpg_scratch);
-  if (o.h_jpg) hipHostFree(o.h_jpg);
+  hipFree(o.files.d_slots);
+  hipFree(o.files.d_bytes);
+  hipFree(o.files.d_scratch);
+  if (o.files.h_ring) hipHostFree(o.files.h_ring);
   if (o.h_col) hipHostFree(o.h_col);
   for (vsf_ctx::ObserveBatch& b : o.batch) {
     hipFree(b.d_img);
@@ -252,11 +252,44 @@ namespace {
 
 void launcher_thread(vsf_ctx* ctx);
 
+// The encode of a batch's n stereo canvases (which = 0: 2w x h) or match canvases (1: w x h) into the device slots: the ONE
+// description the scratch is sized by and the tail launches with.
+VsfEncodeJob debug_files_job(const vsf_ctx* ctx, int which, int n) {
+  const vsf_ctx::Observe& o = ctx->ob;
+  const int w = which ? ctx->p.width : 2 * ctx->p.width;
+  return {o.files.form.kind, n, w, ctx->p.height, 3, o.dbg_stride, (size_t)3 * w, o.files.form.quality, o.files.slot, o.files.cap[which]};
+}
+
+// A slot of the ring of files: i32 stereo bytes, i32 match bytes, then (16-byte aligned) room for the encoder's bound of each.
+void debug_files_slot_layout(vsf_ctx::Observe::DebugFiles& f, int w, int h) {
+  for (int which = 0; which < 2; which++)
+    f.cap[which] = (vsf_encode_capacity(f.form.kind, which ? w : 2 * w, h, 3) + 15) & ~(size_t)15;
+  f.off[0] = 16;
+  f.off[1] = 16 + f.cap[0];
+  f.slot = (16 + f.cap[0] + f.cap[1] + 255) & ~(size_t)255;
+}
+
+// The files leave, not the canvases: device slots, the encoder's scratch and a pinned ring sized by the encoder's bound.
+vsf_status alloc_debug_files(vsf_ctx* ctx) {
+  vsf_ctx::Observe& o = ctx->ob;
+  vsf_ctx::Observe::DebugFiles& f = o.files;
+  const size_t B = (size_t)o.bmax;
+  debug_files_slot_layout(f, ctx->p.width, ctx->p.height);
+  if (f.cap[0] > 0x7FFFFFF0u) return VSF_ERR_UNSUPPORTED;
+  VSF_HIP(hipMalloc((void**)&f.d_slots, B * f.slot));
+  // (+ the encoder's status word: a file that does not fit leaves its count at -1, which is what the view reports)
+  VSF_HIP(hipMalloc((void**)&f.d_bytes, (2 * B + 1) * sizeof(int32_t)));
+  VSF_HIP(hipMemset(f.d_bytes, 0, (2 * B + 1) * sizeof(int32_t)));
+  VSF_HIP(hipMalloc((void**)&f.d_scratch, std::max(vsf_encode_scratch_need(debug_files_job(ctx, 0, o.bmax)),
+                                                   vsf_encode_scratch_need(debug_files_job(ctx, 1, o.bmax)))));
+  VSF_HIP(hipHostMalloc((void**)&f.h_ring, (size_t)o.depth * f.slot, hipHostMallocMapped));
+  return VSF_OK;
+}
+
 vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.dbg_jpeg == (ctx->ob_debug ? ctx->ob_debug_jpeg : 0) &&
-      o.dbg_png == (ctx->ob_debug && ctx->ob_debug_png))
-    return VSF_OK;
+  const vsf_ctx::DebugForm form = ctx->ob_debug ? ctx->ob_debug_form : vsf_ctx::DebugForm();
+  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.files.form == form) return VSF_OK;
   sync_all_streams(ctx);
   float thr_state = 10000.0f;  // cc:353
   if (o.floats) VSF_HIP(hipMemcpy(&thr_state, o.floats + 2 * o.bmax + 1, sizeof(float), hipMemcpyDeviceToHost));
@@ -267,8 +300,7 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.bmax = std::min(o.depth, frames_cap);
   o.frame_life = frame_life;
   o.debug = ctx->ob_debug;
-  o.dbg_jpeg = o.debug ? ctx->ob_debug_jpeg : 0;
-  o.dbg_png = o.debug && ctx->ob_debug_png;
+  o.files.form = form;
   o.ring = frame_life + o.bmax;
   o.max_pairs = o.bmax * (frame_life + 1);
   const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)o.ring + B;
@@ -308,21 +340,9 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
     VSF_HIP(hipMalloc((void**)&o.dbg_prev_kp, K * sizeof(vsf_keypoint)));
     VSF_HIP(hipMalloc((void**)&o.dbg_ints, 16));
     VSF_HIP(hipMemset(o.dbg_ints, 0, 16));
-    if (o.dbg_jpeg || o.dbg_png) {  // the files leave, not the canvases: a pinned ring sized by the encoder's bound
-      const int w = ctx->p.width, h = ctx->p.height;
-      o.jpg_cap[0] = ((o.dbg_png ? vsf_png_encode_capacity(2 * w, h, 3) : vsf_jpeg_encode_capacity(2 * w, h, 3)) + 15) & ~(size_t)15;
-      o.jpg_cap[1] = ((o.dbg_png ? vsf_png_encode_capacity(w, h, 3) : vsf_jpeg_encode_capacity(w, h, 3)) + 15) & ~(size_t)15;
-      if (o.jpg_cap[0] > 0x7FFFFFF0u) return VSF_ERR_UNSUPPORTED;
-      o.jpg_off[0] = 16;
-      o.jpg_off[1] = 16 + o.jpg_cap[0];
-      o.jpg_slot = (16 + o.jpg_cap[0] + o.jpg_cap[1] + 255) & ~(size_t)255;
-      VSF_HIP(hipMalloc((void**)&o.d_jpg, B * o.jpg_slot));
-      VSF_HIP(hipMalloc((void**)&o.d_jpg_n, (2 * B + 1) * sizeof(int32_t)));  // (+ the encoder's status word: a file that does
-      // not fit leaves its count at -1, which is what the view reports)
-      VSF_HIP(hipMemset(o.d_jpg_n, 0, (2 * B + 1) * sizeof(int32_t)));
-      VSF_HIP(hipMalloc((void**)&o.jpg_scratch, o.dbg_png ? vsf_png_enc_scratch_need((int)B, 2 * w, h, 3, o.jpg_cap[0])
-                                                           : vsf_jpeg_enc_scratch_bytes((int)B, 2 * w, h, 3, o.jpg_cap[0])));
-      VSF_HIP(hipHostMalloc((void**)&o.h_jpg, (size_t)o.depth * o.jpg_slot, hipHostMallocMapped));
+    if (form.kind) {
+      const vsf_status st = alloc_debug_files(ctx);
+      if (st != VSF_OK) return st;
     } else {
       VSF_HIP(hipHostMalloc((void**)&o.h_dbg, (size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
     }
@@ -429,6 +449,42 @@ int batches_on_gpu(vsf_ctx* ctx) {  // launched and not finished (a query costs 
     if (b.used && hipEventQuery(b.ev_done) != hipSuccess) n++;
   (void)hipGetLastError();  // (hipErrorNotReady is not an error)
   return n;
+}
+
+// The debug images (slam_frontend.cc:74-115, 167-171, 458-466) of batch [t0, t0 + n), drawn in its tail from what it holds in HBM; then
+// the canvases go into the frames' slots of the pinned debug ring (one copy, two when the slots wrap), or their files into the ring of files.
+vsf_status launch_debug_images(vsf_ctx* ctx, const vsf_ctx::ObserveBatch& b, const MetaView& M, int64_t t0, int n, hipStream_t s_tail) {
+  vsf_ctx::Observe& o = ctx->ob;
+  vsf_ctx::Observe::DebugFiles& fl = o.files;
+  // per canvas size (stereo, match): one copy command, or the encoder's launches + the kernel that carries the files home
+  const int per_size = fl.form.kind ? vsf_encode_launches(fl.form.kind) + 1 : 1;
+  StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 4 + 2 * per_size);  // (4: the drawing kernels)
+  // (in the order of the struct's fields; o.ints: the filtered frames' counts, o.dbg_ints: the colour cursor, then the kept frame's count)
+  const VsfObserveDebugArgs d{n, ctx->p.max_keypoints, ctx->p.width, ctx->p.height, b.d_img, ctx->st_img_stride, ctx->st_img_pitch,
+                              o.kpf, o.ints, o.pairs, o.npairs, M.frames, o.dbg_prev_kp, reinterpret_cast<int32_t*>(o.dbg_ints + 1),
+                              o.h_col, o.col_ring, o.dbg_ints, o.dbg_ops, o.dbg_table, o.dbg_canvas, o.dbg_stride, o.dbg_win,
+                              o.h_out, o.out_stride};
+  vsf_launch_observe_debug(d, s_tail);
+  const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
+  if (fl.form.kind) {
+    // cv::imencode(".jpg") / (".png") of the canvases just drawn, stereo then match (two sizes: two encodes), into the batch's
+    // device slots; then only the files' bytes cross to the pinned ring
+    for (int which = 0; which < 2; which++) {
+      int32_t* d_bytes = fl.d_bytes + (size_t)which * o.bmax;
+      vsf_launch_encode(debug_files_job(ctx, which, n), o.dbg_canvas + (which ? (size_t)6 * d.width * d.height : 0), fl.d_scratch,
+                        fl.d_slots + fl.off[which], d_bytes, fl.d_bytes + 2 * (size_t)o.bmax, s_tail);
+      vsf_launch_files_home(fl.d_slots + fl.off[which], fl.slot, d_bytes, n, fl.h_ring, fl.slot, fl.off[which], which, slot0, o.depth,
+                            M.frames, o.h_out, o.out_stride, s_tail);
+    }
+    fl.stat_commands += 2 * per_size;
+  } else {
+    VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
+                           hipMemcpyDeviceToHost, s_tail));
+    if (first < n)
+      VSF_HIP(hipMemcpyAsync(o.h_dbg, o.dbg_canvas + (size_t)first * o.dbg_stride, (size_t)(n - first) * o.dbg_stride,
+                             hipMemcpyDeviceToHost, s_tail));
+  }
+  return VSF_OK;
 }
 
 // Queues frames [t0, t0 + n) -- they wait in consecutive staging slots -- as one batch.
@@ -581,61 +637,8 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
     vsf_launch_observe_pack(a, max_pairs_per_frame, s_tail);
   }
   if (o.debug) {
-    // ---- the debug images (slam_frontend.cc:74-115, 167-171, 458-466) of every frame, drawn in the batch's tail from what
-    // it holds in HBM, then into the frames' slots of the pinned debug ring (one copy, two when the slots wrap) ----
-    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, o.dbg_png ? 24 : o.dbg_jpeg ? 14 : 6);  // (4 kernels + 2 copies, or 4 + 2 x (4 or 9 encode + 1 carry))
-    VsfObserveDebugArgs d;
-    d.n_frames = n;
-    d.max_rows = Kc;
-    d.width = ctx->p.width;
-    d.height = ctx->p.height;
-    d.images = b.d_img;
-    d.image_stride = ctx->st_img_stride;
-    d.image_pitch = ctx->st_img_pitch;
-    d.kp_f = o.kpf;
-    d.counts_f = counts_f;
-    d.pairs = o.pairs;
-    d.npairs = o.npairs;
-    d.frames = M.frames;
-    d.prev_kp = o.dbg_prev_kp;
-    d.prev_n = reinterpret_cast<int32_t*>(o.dbg_ints + 1);
-    d.colours = o.h_col;
-    d.colour_ring = o.col_ring;
-    d.colour_cursor = o.dbg_ints;
-    d.ops = o.dbg_ops;
-    d.canvases = o.dbg_table;
-    d.canvas = o.dbg_canvas;
-    d.canvas_stride = o.dbg_stride;
-    d.winners = o.dbg_win;
-    d.out = o.h_out;
-    d.out_stride = o.out_stride;
-    vsf_launch_observe_debug(d, s_tail);
-    const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
-    if (o.dbg_jpeg || o.dbg_png) {
-      // cv::imencode(".jpg") / (".png") of the canvases just drawn, stereo then match (two sizes: two encodes), into the batch's device
-      // slots; then only the files' bytes cross to the pinned ring
-      const int w = ctx->p.width, h = ctx->p.height;
-      for (int which = 0; which < 2; which++) {
-        const int iw = which ? w : 2 * w;
-        if (o.dbg_png)
-          vsf_launch_png_encode(o.dbg_canvas + (which ? (size_t)6 * w * h : 0), n, iw, h, 3, o.dbg_stride, (size_t)3 * iw,
-                                o.jpg_scratch, o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax,
-                                o.d_jpg_n + 2 * (size_t)o.bmax, s_tail, o.jpg_cap[which]);
-        else
-          vsf_launch_jpeg_encode(o.dbg_canvas + (which ? (size_t)6 * w * h : 0), n, iw, h, 3, o.dbg_stride, (size_t)3 * iw, o.dbg_jpeg,
-                                 o.jpg_scratch, o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax,
-                                 o.d_jpg_n + 2 * (size_t)o.bmax, s_tail, o.jpg_cap[which]);
-        vsf_launch_jpeg_files_home(o.d_jpg + o.jpg_off[which], o.jpg_slot, o.d_jpg_n + (size_t)which * o.bmax, n, o.h_jpg, o.jpg_slot,
-                                   o.jpg_off[which], which, slot0, o.depth, M.frames, o.h_out, o.out_stride, s_tail);
-      }
-      o.stat_jpeg_commands += o.dbg_png ? 20 : 10;
-    } else {
-      VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
-                             hipMemcpyDeviceToHost, s_tail));
-      if (first < n)
-        VSF_HIP(hipMemcpyAsync(o.h_dbg, o.dbg_canvas + (size_t)first * o.dbg_stride, (size_t)(n - first) * o.dbg_stride,
-                               hipMemcpyDeviceToHost, s_tail));
-    }
+    const vsf_status st = launch_debug_images(ctx, b, M, t0, n, s_tail);
+    if (st != VSF_OK) return st;
   }
   VSF_HIP(hipEventRecord(b.ev_done, s_tail));
   b.used = true;
@@ -736,6 +739,47 @@ void launcher_thread(vsf_ctx* ctx) {
   }
 }
 
+// vsf_observe_set_debug_jpeg / _png: quality != 0 asks for files of `kind`, 0 takes that request back.
+vsf_status set_debug_form(vsf_ctx* ctx, int kind, int quality) {
+  vsf_ctx::DebugForm& f = ctx->ob_debug_form;
+  if (quality == (f.kind == kind ? f.quality : 0)) return VSF_OK;
+  if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
+  if (quality != 0 && f.kind != VSF_FILE_NONE && f.kind != kind) return VSF_ERR_INVALID_ARG;  // one form of file at a time
+  // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
+  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
+  if (ctx->ob.ready) stop_observe_threads(ctx);
+  f.kind = quality ? kind : VSF_FILE_NONE;
+  f.quality = quality;
+  return VSF_OK;
+}
+
+// A collected frame's two files inside the pinned ring of files; kind: which form the caller asks for.
+vsf_status debug_files_view(vsf_ctx* ctx, int kind, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
+                            const uint8_t** match, size_t* match_bytes) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !stereo || !stereo_bytes || !match || !match_bytes) return VSF_ERR_INVALID_ARG;
+  *stereo = *match = nullptr;
+  *stereo_bytes = *match_bytes = 0;
+  const vsf_ctx::Observe& o = ctx->ob;
+  if (!o.ready || !o.debug || o.files.form.kind != kind || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+    return VSF_ERR_INVALID_ARG;
+  const int slot = (int)(ticket % o.depth);
+  const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
+  const uint8_t* base = o.files.h_ring + (size_t)slot * o.files.slot;
+  const int32_t* n = reinterpret_cast<const int32_t*>(base);
+  // (cannot happen while vsf_encode_capacity is the bound it claims to be: a file that did not fit its slot)
+  if (((flags & 1) && n[0] < 0) || ((flags & 2) && n[1] < 0)) return VSF_ERR_CAPACITY;
+  if ((flags & 1) && n[0] > 0) {
+    *stereo = base + o.files.off[0];
+    *stereo_bytes = (size_t)n[0];
+  }
+  if ((flags & 2) && n[1] > 0) {
+    *match = base + o.files.off[1];
+    *match_bytes = (size_t)n[1];
+  }
+  return VSF_OK;
+}
+
 }  // namespace
 
 // Every entry point of the context except the queue's own comes through here (VsfErrorScope): what waits in the queue
@@ -774,7 +818,7 @@ vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** 
   *stereo = *match = nullptr;
   const vsf_ctx::Observe& o = ctx->ob;
   // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_collect_view)
-  if (!o.ready || !o.debug || o.dbg_jpeg || o.dbg_png || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+  if (!o.ready || !o.debug || o.files.form.kind || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
     return VSF_ERR_INVALID_ARG;  // (with vsf_observe_set_debug_jpeg / _png the raw canvases never leave the device)
   const int slot = (int)(ticket % o.depth);
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
@@ -787,72 +831,24 @@ vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** 
 vsf_status vsf_observe_set_debug_jpeg(vsf_ctx* ctx, int quality) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || quality < 0 || quality > 100) return VSF_ERR_INVALID_ARG;
-  if (quality == ctx->ob_debug_jpeg) return VSF_OK;
-  if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
-  if (quality != 0 && ctx->ob_debug_png) return VSF_ERR_INVALID_ARG;  // one form of file at a time
-  // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
-  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
-  if (ctx->ob.ready) stop_observe_threads(ctx);
-  ctx->ob_debug_jpeg = quality;
-  return VSF_OK;
+  return set_debug_form(ctx, VSF_FILE_JPEG, quality);
 }
-
-namespace {
-// A collected frame's two files inside the pinned ring of files; png: which form the caller asks for.
-vsf_status debug_files_view(vsf_ctx* ctx, bool png, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
-                            const uint8_t** match, size_t* match_bytes);
-}  // namespace
 
 vsf_status vsf_observe_debug_jpeg_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
                                        const uint8_t** match, size_t* match_bytes) {
-  return debug_files_view(ctx, false, ticket, stereo, stereo_bytes, match, match_bytes);
+  return debug_files_view(ctx, VSF_FILE_JPEG, ticket, stereo, stereo_bytes, match, match_bytes);
 }
 
 vsf_status vsf_observe_set_debug_png(vsf_ctx* ctx, int on) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx) return VSF_ERR_INVALID_ARG;
-  if ((on != 0) == ctx->ob_debug_png) return VSF_OK;
-  if (on && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;      // files of images nobody draws
-  if (on && ctx->ob_debug_jpeg) return VSF_ERR_INVALID_ARG;  // one form of file at a time
-  // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
-  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
-  if (ctx->ob.ready) stop_observe_threads(ctx);
-  ctx->ob_debug_png = on != 0;
-  return VSF_OK;
+  return set_debug_form(ctx, VSF_FILE_PNG, on != 0);
 }
 
 vsf_status vsf_observe_debug_png_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
                                       const uint8_t** match, size_t* match_bytes) {
-  return debug_files_view(ctx, true, ticket, stereo, stereo_bytes, match, match_bytes);
+  return debug_files_view(ctx, VSF_FILE_PNG, ticket, stereo, stereo_bytes, match, match_bytes);
 }
-
-namespace {
-vsf_status debug_files_view(vsf_ctx* ctx, bool png, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
-                            const uint8_t** match, size_t* match_bytes) {
-  VsfErrorScope scope_(ctx, false);
-  if (!ctx || !stereo || !stereo_bytes || !match || !match_bytes) return VSF_ERR_INVALID_ARG;
-  *stereo = *match = nullptr;
-  *stereo_bytes = *match_bytes = 0;
-  const vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready || !o.debug || !(png ? o.dbg_png : o.dbg_jpeg != 0) || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
-    return VSF_ERR_INVALID_ARG;
-  const int slot = (int)(ticket % o.depth);
-  const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
-  const uint8_t* base = o.h_jpg + (size_t)slot * o.jpg_slot;
-  const int32_t* n = reinterpret_cast<const int32_t*>(base);
-  // (cannot happen while vsf_jpeg_encode_capacity is the bound it claims to be: a file that did not fit its slot)
-  if (((flags & 1) && n[0] < 0) || ((flags & 2) && n[1] < 0)) return VSF_ERR_CAPACITY;
-  if ((flags & 1) && n[0] > 0) {
-    *stereo = base + o.jpg_off[0];
-    *stereo_bytes = (size_t)n[0];
-  }
-  if ((flags & 2) && n[1] > 0) {
-    *match = base + o.jpg_off[1];
-    *match_bytes = (size_t)n[1];
-  }
-  return VSF_OK;
-}
-}  // namespace
 
 vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_flight) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
@@ -882,7 +878,7 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   const int64_t v[15] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns,
                          o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes,
-                         o.stat_jpeg_commands};
+                         o.files.stat_commands};
   for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
   return VSF_OK;
 }

@@ -275,9 +275,11 @@ bool Frontend::EnsureContext(int width, int height) {
   if (last_status_ == VSF_OK) last_status_ = vsf_observe_configure(ctx_, ctx_depth_, min_batch_, 0);
   // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
   if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
-  if (last_status_ == VSF_OK && config_.debug_images_ && config_.debug_jpeg_quality_ > 0)
+  // ... and leave as files when the configuration asks for one form of them (both: the second request is refused)
+  const int form = debug_file_form();
+  if (last_status_ == VSF_OK && config_.debug_images_ && (form & kFormJpeg))
     last_status_ = vsf_observe_set_debug_jpeg(ctx_, config_.debug_jpeg_quality_);
-  if (last_status_ == VSF_OK && config_.debug_images_ && config_.debug_png_) last_status_ = vsf_observe_set_debug_png(ctx_, 1);
+  if (last_status_ == VSF_OK && config_.debug_images_ && (form & kFormPng)) last_status_ = vsf_observe_set_debug_png(ctx_, 1);
   pending_.assign((size_t)ctx_depth_, PendingFrame());
   pending_head_ = pending_count_ = 0;
   return last_status_ == VSF_OK;
@@ -685,11 +687,11 @@ bool Frontend::RetireOldest() {
     right_temp_frame.frame_ID_ = curr_frame_ID_;
     book(right_temp_frame, &curr_frame, pair_bytes[n_pairs - 1], npairs[n_pairs - 1], nullptr);
   }
-  if (config_.debug_images_ && (config_.debug_jpeg_quality_ > 0 || config_.debug_png_)) {
+  if (config_.debug_images_ && debug_file_form() != kFormRaw) {
     // encoded in the batch's tail (vsf_observe_set_debug_jpeg / vsf_observe_set_debug_png)
     const uint8_t *stereo = nullptr, *match = nullptr;
     size_t stereo_bytes = 0, match_bytes = 0;
-    const vsf_status ds = config_.debug_png_
+    const vsf_status ds = (debug_file_form() & kFormPng)
                               ? vsf_observe_debug_png_view(ctx_, pf.ticket, &stereo, &stereo_bytes, &match, &match_bytes)
                               : vsf_observe_debug_jpeg_view(ctx_, pf.ticket, &stereo, &stereo_bytes, &match, &match_bytes);
     if (ds != VSF_OK) {
@@ -834,7 +836,7 @@ void Frontend::set_debug_images(bool on) {
 }
 
 void Frontend::set_debug_jpeg_quality(int quality) {
-  if (!nodes_.empty() || pending_count_ > 0 || quality < 0 || quality > 100 || (quality > 0 && config_.debug_png_)) {
+  if (!nodes_.empty() || pending_count_ > 0 || quality < 0 || quality > 100 || (quality > 0 && (debug_file_form() & kFormPng))) {
     last_status_ = VSF_ERR_INVALID_ARG;
     return;
   }
@@ -843,7 +845,7 @@ void Frontend::set_debug_jpeg_quality(int quality) {
 }
 
 void Frontend::set_debug_png(bool on) {
-  if (!nodes_.empty() || pending_count_ > 0 || (on && config_.debug_jpeg_quality_ > 0)) {
+  if (!nodes_.empty() || pending_count_ > 0 || (on && (debug_file_form() & kFormJpeg))) {
     last_status_ = VSF_ERR_INVALID_ARG;
     return;
   }
@@ -855,7 +857,7 @@ Frontend::CompressedView Frontend::GetLastDebugImageCompressed() {
   Flush();
   CompressedView v;
   if (!debug_files_.empty())
-    v.data = debug_files_.back().data(), v.size = debug_files_.back().size(), v.format = config_.debug_png_ ? "png" : "jpeg";
+    v.data = debug_files_.back().data(), v.size = debug_files_.back().size(), v.format = debug_file_format();
   return v;
 }
 
@@ -864,7 +866,7 @@ Frontend::CompressedView Frontend::GetLastDebugStereoImageCompressed() {
   CompressedView v;
   if (!debug_stereo_files_.empty())
     v.data = debug_stereo_files_.back().data(), v.size = debug_stereo_files_.back().size(),
-    v.format = config_.debug_png_ ? "png" : "jpeg";
+    v.format = debug_file_format();
   return v;
 }
 

@@ -236,6 +236,11 @@ class Frontend {
   void Calculate3DPoints(Frame* left_frame, Frame* right_frame, std::vector<Vector3f>* points,
                          slam_types::VisionFactor* matches_out = nullptr);
   bool EnsureContext(int width, int height);
+  // The form the queue's debug images leave in, as config_.debug_jpeg_quality_ / debug_png_ ask for it: raw images, or the bit of
+  // the one form of file (both bits only in a configuration the context refuses).  The ONE place that reads the pair.
+  enum { kFormRaw = 0, kFormJpeg = 1, kFormPng = 2 };
+  int debug_file_form() const { return (config_.debug_jpeg_quality_ > 0 ? kFormJpeg : 0) | (config_.debug_png_ ? kFormPng : 0); }
+  const char* debug_file_format() const { return (debug_file_form() & kFormPng) ? "png" : "jpeg"; }  // CompressedView::format
   bool ObserveImageFused(const Image& left_image, const Image& right_image);
   struct FramePayload {  // what a frame brings to the queue: two raw images at `step`, or two compressed files
     const uint8_t* left = nullptr;
