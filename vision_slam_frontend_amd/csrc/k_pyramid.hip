@@ -17,7 +17,8 @@
 // built by ONE launch, a 1024-thread workgroup per image with the levels ping-ponged through LDS.
 // pyramid_slab_kernel: a batch of one to four images (a frame) walks chains of levels per launch, the last level of a
 // chain cut into slabs whose workgroups never wait for each other (border rows are computed twice).
-// resize_march_kernel is the general fallback for levels that fail the R + 2 check.
+// resize_march_kernel is the general fallback for levels that fail the R + 2 check.  A band narrower than a wave has the
+// lane spans of its strips packed into full waves (strip_packed).
 #pragma clang fp contract(off)
 #include <algorithm>
 #include <cmath>
@@ -43,6 +44,10 @@ struct ResizeArgs {
   int dst_pitch, dw, dh;
   double scale_x, scale_y;  // cv::resize: 1. / ((double)dw / sw), 1. / ((double)dh / sh)
   int nstrips;
+  // packed last band (resize_strip_kernel; pk_waves == 0: every band is a wave per strip): columns [pk_x0, dw) of all
+  // strips laid end to end, pk_lanes lanes per strip, cut into pk_waves waves; pk_magic = floor(2^32 / pk_lanes) + 1
+  int pk_x0, pk_lanes, pk_waves;
+  uint32_t pk_magic;
 };
 
 template <int kStripRows>
@@ -164,10 +169,9 @@ struct StripRows {   // per strip: the R + 2 source-row windows and the lane-dis
   uint32_t ty_i0, ty_wts;
 };
 
-__device__ __forceinline__ StripX strip_setup(const ResizeArgs& a, int band) {
-  const int lane = threadIdx.x & 63;
+__device__ __forceinline__ StripX strip_setup_at(const ResizeArgs& a, int x4) {  // x4: the lane's first output column
   StripX c;
-  c.x4 = band * 256 + lane * 4;
+  c.x4 = x4;
   c.active = c.x4 < a.dw;
   auto xtap = [&](int dx) -> VsfTap {
     float fx = (float)((dx + 0.5) * a.scale_x - 0.5);
@@ -193,6 +197,9 @@ __device__ __forceinline__ StripX strip_setup(const ResizeArgs& a, int band) {
   c.s0 = selector(t0), c.s1 = selector(t1), c.s2 = selector(t2), c.s3 = selector(t3);
   c.q0 = weights(t0), c.q1 = weights(t1), c.q2 = weights(t2), c.q3 = weights(t3);
   return c;
+}
+__device__ __forceinline__ StripX strip_setup(const ResizeArgs& a, int band) {
+  return strip_setup_at(a, band * 256 + (int)(threadIdx.x & 63) * 4);
 }
 
 // LDS images of a level are reached through LDS-typed pointers where the compiler cannot see that for itself (an
@@ -312,11 +319,130 @@ __device__ __forceinline__ void resize_strip_unit(const ResizeArgs& a, int image
   strip_finish<R>(a, c, image, strip * R, a.dh, rows);
 }
 
+// Packed form of a strip, for a band narrower than a wave.  A strip of such a band is a span of `lanes` lanes (a lane is
+// four output columns, as above); the spans of all strips of the level lie end to end and a wave takes 64 consecutive
+// lanes of that sequence, whatever strips they belong to (neighbouring strips of one level of one image: same x taps per
+// column, same pitch, same source).  Nothing crosses lanes in the arithmetic, so a span may begin and end anywhere.
+// What was wave-uniform becomes per lane: the strip's first source row, the row addresses, the y weights and which two
+// of the R + 2 filtered rows an output row blends.  The y taps are still evaluated once per (strip, row): lane e takes
+// row e % R of the wave's (e / R)-th strip and a lane fetches its rows' taps with ds_bpermute, so a wave may touch at
+// most 64 / R strips (pack_lanes pads the span of a very narrow band until that holds).  The row pick is branch-free:
+// output row r always blends filtered row r + 1 -- as the lower tap when cv::resize's yofs has stepped past r, as the
+// upper tap otherwise -- with row r + 2 or row r, so the evaluating lane orders the two weights accordingly and flags
+// the step in the sign bit of one of them (v_mul_hi_u32_u24 reads 24 bits), and the lane selects ONE operand per pixel.
+__host__ __device__ inline int pack_lanes(int R, int lanes) {
+  const int ns = 64 / R;
+  for (int p = lanes; p < 64; p++) {
+    const int touched = (64 % p == 0) ? 64 / p : (63 + p - 1) / p + 1;  // strips a wave can reach (waves begin at 64 j)
+    if (touched <= ns) return p;
+  }
+  return 64;
+}
+// Packing pays where the waves it saves outweigh what a packed wave adds (per-lane addresses, tap fetch, operand
+// select): VALU instructions per wave, read off the compiled kernels (set-up + R rows)
+__host__ __device__ inline bool pack_pays(int R, int nstrips, int pk_waves) {
+  const long plain = R == 16 ? 763 : 467, packed = R == 16 ? 847 : 519;
+  return (long)pk_waves * packed < (long)nstrips * plain;
+}
+
+// strip: the lane's strip (lanes past the last strip repeat it and store nothing), s_lo: lane 0's (wave-uniform)
+template <int R, bool ALIGNED = false, class SP = const uint8_t*, class LP = uint8_t*>
+__device__ __forceinline__ void strip_packed(const ResizeArgs& a, const StripX& c, int image, int strip, int s_lo, SP S,
+                                             LP lcopy = nullptr, bool to_lds = false) {
+  const int lane = threadIdx.x & 63;
+  const int last = a.nstrips - 1;
+  const int sc = min(strip, last);
+  const bool live = c.active && strip <= last;
+  uint32_t ty_i0, wm, wo;  // of this lane's (strip, row): yofs; weight of filtered row r + 1; of the other row | step flag
+  {
+    const int r = lane & (R - 1);
+    const int dy = min(min(s_lo + lane / R, last) * R + r, a.dh - 1);
+    float fy = (float)((dy + 0.5) * a.scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy -= sy;
+    ty_i0 = (uint32_t)min(max(sy, 0), a.sh - 1);
+    const uint32_t b0 = (uint32_t)__float2int_rn((1.f - fy) * 2048) << 12, b1 = (uint32_t)__float2int_rn(fy * 2048) << 12;
+    const uint32_t first = (uint32_t)__builtin_amdgcn_ds_bpermute((lane & ~(R - 1)) * 4, (int)ty_i0);
+    const bool step = ty_i0 != first + (uint32_t)r;  // then the row's taps are first + r + 1 and first + r + 2
+    wm = step ? b0 : b1;
+    wo = step ? (b1 | 0x80000000u) : b0;
+  }
+  const int slot = (sc - s_lo) * (R * 4);  // (byte address of) the lane that evaluated this lane's row 0
+  const uint32_t first = (uint32_t)__builtin_amdgcn_ds_bpermute(slot, (int)ty_i0);
+  U8B v[R + 2];
+#pragma unroll
+  for (int k = 0; k < R + 2; k++) {
+    const uint32_t row = min(first + (uint32_t)k, (uint32_t)(a.sh - 1)) * (uint32_t)a.src_pitch;
+    if constexpr (ALIGNED) {  // (as in strip_issue_from)
+      const uint32_t b0 = row + (c.base & ~3u);
+      const uint32_t d0 = ld32(S + b0), d1 = ld32(S + (b0 + 4u)),
+                     d2 = ld32(S + (row + min((c.base & ~3u) + 8u, (uint32_t)a.src_pitch - 4u)));
+      v[k].lo = __builtin_amdgcn_alignbyte(d1, d0, c.base & 3u);
+      v[k].hi = __builtin_amdgcn_alignbyte(d2, d1, c.base & 3u);
+    } else {
+      v[k] = *reinterpret_cast<const U8B*>((const uint8_t*)S + (row + c.base));
+    }
+  }
+  struct H4 {
+    uint32_t a, b, c, d;
+  };
+  H4 H[R + 2];
+#pragma unroll
+  for (int k = 0; k < R + 2; k++) {
+    auto hsum = [&](uint32_t sel, uint32_t q) -> uint32_t {
+      return __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16, __builtin_amdgcn_perm(v[k].hi, v[k].lo, sel)),
+                                    __builtin_bit_cast(v2u16, q), 0u, false) & 0xFFFFF0u;
+    };
+    H[k].a = hsum(c.s0, c.q0);
+    H[k].b = hsum(c.s1, c.q1);
+    H[k].c = hsum(c.s2, c.q2);
+    H[k].d = hsum(c.s3, c.q3);
+  }
+  auto mulhi24 = [](uint32_t x, uint32_t y) -> uint32_t {
+    return (uint32_t)(((uint64_t)(x & 0xFFFFFFu) * (uint64_t)(y & 0xFFFFFFu)) >> 32);
+  };
+  uint8_t* D = a.dst + (size_t)image * a.dst_img_stride;
+  const int rlast = a.dh - last * R;  // rows of the level's last strip (wave-uniform)
+  const uint32_t d0 = (uint32_t)(sc * R) * (uint32_t)a.dst_pitch + (uint32_t)c.x4;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const uint32_t wmr = (uint32_t)__builtin_amdgcn_ds_bpermute(slot + 4 * r, (int)wm);
+    const uint32_t wor = (uint32_t)__builtin_amdgcn_ds_bpermute(slot + 4 * r, (int)wo);
+    const bool step = (int)wor < 0;
+    const uint32_t oa = step ? H[r + 2].a : H[r].a, ob = step ? H[r + 2].b : H[r].b;
+    const uint32_t oc = step ? H[r + 2].c : H[r].c, od = step ? H[r + 2].d : H[r].d;
+    const uint32_t ta = mulhi24(wmr, H[r + 1].a) + mulhi24(wor, oa) + 2u, tb = mulhi24(wmr, H[r + 1].b) + mulhi24(wor, ob) + 2u;
+    const uint32_t tc = mulhi24(wmr, H[r + 1].c) + mulhi24(wor, oc) + 2u, td = mulhi24(wmr, H[r + 1].d) + mulhi24(wor, od) + 2u;
+    const v2u16 lo = __builtin_bit_cast(v2u16, ta | (tb << 16)) >> (v2u16){2, 2};
+    const v2u16 hi = __builtin_bit_cast(v2u16, tc | (td << 16)) >> (v2u16){2, 2};
+    const uint32_t out = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u);
+    const uint32_t doff = d0 + (uint32_t)r * (uint32_t)a.dst_pitch;
+    if (live && (r < rlast || strip < last)) {  // (r < rlast is wave-uniform)
+      *reinterpret_cast<uint32_t*>(D + doff) = out;
+      if (to_lds) st32(lcopy + doff, out);
+    }
+  }
+}
+
 template <int R>
-__global__ __launch_bounds__(256) void resize_strip_kernel(ResizeArgs a) {
-  const int strip = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (strip >= a.nstrips) return;  // wave-uniform
-  resize_strip_unit<R>(a, blockIdx.y, strip, blockIdx.z);
+__device__ __forceinline__ void resize_packed_unit(const ResizeArgs& a, int image, int j) {
+  const uint32_t g = (uint32_t)j * 64u + (threadIdx.x & 63);  // the lane's place in the level's sequence of spans
+  const int strip = (int)__umulhi(g, a.pk_magic);             // g / pk_lanes (exact below 2^26)
+  const StripX c = strip_setup_at(a, a.pk_x0 + ((int)g - strip * a.pk_lanes) * 4);
+  strip_packed<R>(a, c, image, strip, __builtin_amdgcn_readfirstlane(strip), a.src + (size_t)image * a.src_img_stride);
+}
+
+// grid: (strips / 4, images, bands); with a packed last band (pk_waves > 0) the last z-slice counts packed waves
+// (eight waves per SIMD, as without the packed form: the compiler is held to 64 VGPRs)
+template <int R>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void resize_strip_kernel(ResizeArgs a) {
+  const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (a.pk_waves > 0 && blockIdx.z == gridDim.z - 1) {
+    if (unit < a.pk_waves) resize_packed_unit<R>(a, blockIdx.y, unit);
+    return;
+  }
+  if (unit >= a.nstrips) return;  // wave-uniform
+  resize_strip_unit<R>(a, blockIdx.y, unit, blockIdx.z);
 }
 
 // Image-major tail of the pyramid for large batches: the levels that are one band wide (w <= 256; 26 of the 49 at
@@ -356,6 +482,8 @@ __device__ __forceinline__ ResizeArgs tail_level_args(const PyramidArgs& p, int 
   a.scale_x = __builtin_bit_cast(double, ((unsigned long long)L.rscale_x[1] << 32) | L.rscale_x[0]);
   a.scale_y = __builtin_bit_cast(double, ((unsigned long long)L.rscale_y[1] << 32) | L.rscale_y[0]);
   a.nstrips = (L.h + 7) / 8;
+  a.pk_x0 = a.pk_lanes = a.pk_waves = 0;
+  a.pk_magic = 0;
   return a;
 }
 
@@ -390,13 +518,36 @@ __global__ __launch_bounds__(1024) void pyramid_image_kernel(PyramidArgs p) {
     uint8_t* lcopy = (l + 1 < p.nlevels) ? lvl[(l - p.l_begin) & 1] : nullptr;
     const uint8_t* lsrc = lvl[(l - p.l_begin + 1) & 1];
     const uint8_t* gsrc = a.src + (size_t)image * a.src_img_stride;
-    for (int strip = wave; strip < a.nstrips; strip += 16) {
-      StripRows<8> rows;
-      if (from_lds)  // (workgroup-uniform; two inlined copies so that the LDS one reads with ds_read_b64)
-        strip_issue_from<8, true>(a, c, lsrc, strip * 8, rows);
-      else
-        strip_issue_from<8>(a, c, gsrc, strip * 8, rows);
-      strip_finish<8>(a, c, image, strip * 8, a.dh, rows, lcopy, lcopy != nullptr);
+    // narrow levels: the strips' lane spans packed into full waves (strip_packed), where that saves instructions
+    const int pk_lanes = pack_lanes(8, (a.dw + 3) >> 2), pk_waves = (a.nstrips * pk_lanes + 63) >> 6;
+    if (pack_pays(8, a.nstrips, pk_waves)) {  // (workgroup-uniform)
+      const uint32_t magic = 0xFFFFFFFFu / (uint32_t)pk_lanes + 1u;
+      for (int j = wave; j < pk_waves; j += 16) {
+        const uint32_t g = (uint32_t)j * 64u + lane;
+        const int strip = (int)__umulhi(g, magic);
+        const int li = (int)g - strip * pk_lanes;
+        const uint32_t(*o)[64] = xs[l & 1];
+        StripX cp;
+        cp.s0 = o[0][li], cp.s1 = o[1][li], cp.s2 = o[2][li], cp.s3 = o[3][li];
+        cp.q0 = o[4][li], cp.q1 = o[5][li], cp.q2 = o[6][li], cp.q3 = o[7][li];
+        cp.base = o[8][li];
+        cp.x4 = li * 4;
+        cp.active = cp.x4 < a.dw;
+        const int s_lo = __builtin_amdgcn_readfirstlane(strip);
+        if (from_lds)
+          strip_packed<8, true>(a, cp, image, strip, s_lo, lsrc, lcopy, lcopy != nullptr);
+        else
+          strip_packed<8>(a, cp, image, strip, s_lo, gsrc, lcopy, lcopy != nullptr);
+      }
+    } else {
+      for (int strip = wave; strip < a.nstrips; strip += 16) {
+        StripRows<8> rows;
+        if (from_lds)  // (workgroup-uniform; two inlined copies so that the LDS one reads with ds_read_b64)
+          strip_issue_from<8, true>(a, c, lsrc, strip * 8, rows);
+        else
+          strip_issue_from<8>(a, c, gsrc, strip * 8, rows);
+        strip_finish<8>(a, c, image, strip * 8, a.dh, rows, lcopy, lcopy != nullptr);
+      }
     }
     if (wave == 0 && l + 1 < p.nlevels) publish(l + 1);
     __syncthreads();  // (waits for this wave's LDS writes; the HBM copy is not read in this kernel)
@@ -446,6 +597,8 @@ __device__ __forceinline__ ResizeArgs slab_level_args(const PyramidArgs& p, int 
   a.scale_x = __builtin_bit_cast(double, ((unsigned long long)L.rscale_x[1] << 32) | L.rscale_x[0]);
   a.scale_y = __builtin_bit_cast(double, ((unsigned long long)L.rscale_y[1] << 32) | L.rscale_y[0]);
   a.nstrips = (L.h + 7) / 8;
+  a.pk_x0 = a.pk_lanes = a.pk_waves = 0;
+  a.pk_magic = 0;
   return a;
 }
 
@@ -680,6 +833,18 @@ void vsf_launch_pyramid(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_lev
       if (L.resize_rows >= 8) {
         const int R = (large && L.resize_rows >= 16) ? 16 : 8;
         a.nstrips = (L.h + R - 1) / R;
+        // a last band narrower than a wave: its strips packed into full waves, where that saves instructions
+        a.pk_x0 = (L.w / 256) * 256;
+        a.pk_lanes = a.pk_waves = 0;
+        a.pk_magic = 0;
+        if (a.pk_x0 < L.w) {
+          const int lanes = pack_lanes(R, (L.w - a.pk_x0 + 3) / 4), waves = (a.nstrips * lanes + 63) / 64;
+          if (pack_pays(R, a.nstrips, waves)) {
+            a.pk_lanes = lanes;
+            a.pk_waves = waves;
+            a.pk_magic = 0xFFFFFFFFu / (uint32_t)lanes + 1u;
+          }
+        }
         const dim3 grid((a.nstrips + 3) / 4, n, nbands);
         if (R == 16)
           hipLaunchKernelGGL(resize_strip_kernel<16>, grid, block, 0, st[c], a);
@@ -689,6 +854,8 @@ void vsf_launch_pyramid(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_lev
       }
       const int rows = large ? 8 : 4;
       a.nstrips = (L.h + rows - 1) / rows;
+      a.pk_x0 = a.pk_lanes = a.pk_waves = 0;
+      a.pk_magic = 0;
       if (large)
         hipLaunchKernelGGL(resize_march_kernel<8>, dim3((a.nstrips + 3) / 4, n, nbands), dim3(256), 0, st[c], a);
       else
