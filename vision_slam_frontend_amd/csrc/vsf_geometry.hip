@@ -27,7 +27,6 @@ inline int cvCeilD(double v) {
   const int i = cvRoundD(v);
   return i + ((float)(i - v) < 0);
 }
-inline int16_t satShort(float v) { return (int16_t)std::min(std::max(cvRoundF(v), -32768), 32767); }
 
 }  // namespace
 
@@ -36,31 +35,9 @@ namespace vsfi {
 // cv::resize(INTER_LINEAR, 8u) coefficient tables for one level (source sw x sh -> dw x dh).
 void build_taps(int sw, int sh, int dw, int dh, std::vector<VsfTap>* xt, std::vector<VsfTap>* yt) {
   const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-  for (int dx = 0; dx < dw; dx++) {
-    float fx = (float)((dx + 0.5) * scale_x - 0.5);
-    int sx = cvFloorD(fx);
-    fx -= sx;
-    if (sx < 0) fx = 0, sx = 0;
-    if (sx >= sw - 1) fx = 0, sx = sw - 1;  // (also the dx >= xmax single-tap case: weight 2048 on S[sx])
-    VsfTap t;
-    t.i0 = (uint16_t)sx;
-    t.i1 = (uint16_t)std::min(sx + 1, sw - 1);
-    t.c0 = satShort((1.f - fx) * 2048);
-    t.c1 = satShort(fx * 2048);
-    xt->push_back(t);
-  }
+  for (int dx = 0; dx < dw; dx++) xt->push_back(resize_xtap(dx, scale_x, sw));
   while (xt->size() % 4) xt->push_back(VsfTap{0, 0, 0, 0});
-  for (int dy = 0; dy < dh; dy++) {
-    float fy = (float)((dy + 0.5) * scale_y - 0.5);
-    const int sy = cvFloorD(fy);
-    fy -= sy;
-    VsfTap t;
-    t.i0 = (uint16_t)std::min(std::max(sy, 0), sh - 1);
-    t.i1 = (uint16_t)std::min(std::max(sy + 1, 0), sh - 1);
-    t.c0 = satShort((1.f - fy) * 2048);
-    t.c1 = satShort(fy * 2048);
-    yt->push_back(t);
-  }
+  for (int dy = 0; dy < dh; dy++) yt->push_back(resize_ytap(dy, scale_y, sh));
 }
 
 // ORB umax table (features2d/orb.cpp computeKeyPoints) for the sanity check of the device constant.

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/vsf.h"
+#include "vsf_resize.h"  // VsfTap, the resize coefficient formula, the packing plan
 
 // FAST march kernel: a wave owns a band of 248 keypoint columns (lanes 1..62 x 4 px; lanes 0 and 63 carry the raw halo
 // pixels and score the ONE pixel next to the band -- lane 0's last, lane 63's first: their circles reach no further than
@@ -57,13 +58,6 @@ struct VsfLevel {
   int32_t resize_any8;     // 1: an 8-row strip starting at ANY row stays inside 10 consecutive source rows
   uint32_t rscale_x[2], rscale_y[2];  // bit patterns of cv::resize's double scale_x / scale_y from level - 1 (host-computed)
   uint32_t blur_tcol;      // matrix-core blur: index of this level's first pass-1 operand (4 per 64-column band) in the table
-};
-
-// Resize coefficients of one output column / row (cv::resize INTER_LINEAR 8u: xofs/ialpha resp. yofs/ibeta with the
-// out-of-range taps already clamped, weights kept); evaluated in place by k_pyramid.hip, tabulated on the host.
-struct VsfTap {
-  uint16_t i0, i1;  // source indices of the two taps
-  int16_t c0, c1;   // 11-bit fixed-point weights
 };
 
 // Candidate keypoint, 32 bit: score << 24 | y << 12 | x   (level coordinates, x,y < 4096)
