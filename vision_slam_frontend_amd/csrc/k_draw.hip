@@ -188,7 +188,7 @@ vsf_status draw_dev(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int n, const 
     ctx->dr_canv_cap = n;
   }
   // the table's host image is rewritten only after the previous call's upload has left it
-  if (!ctx->dr_uploaded) VSF_HIP(hipEventCreateWithFlags(&ctx->dr_uploaded, hipEventDisableTiming));
+  if (!ctx->dr_uploaded) VSF_HIP(ctx->dr_uploaded.alloc(hipEventDisableTiming));
   VSF_HIP(hipEventSynchronize(ctx->dr_uploaded));
   ctx->dr_canv_host.resize((size_t)n * sizeof(DrawCanvasDev));
   DrawCanvasDev* t = reinterpret_cast<DrawCanvasDev*>(ctx->dr_canv_host.data());
@@ -213,7 +213,7 @@ vsf_status draw_dev(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int n, const 
   }
   VSF_HIP(hipMemcpyAsync(ctx->dr_canv, t, (size_t)n * sizeof(DrawCanvasDev), hipMemcpyHostToDevice, ctx->stream));
   VSF_HIP(hipEventRecord(ctx->dr_uploaded, ctx->stream));
-  const DrawCanvasDev* dc = static_cast<const DrawCanvasDev*>(ctx->dr_canv);
+  const DrawCanvasDev* dc = static_cast<const DrawCanvasDev*>(ctx->dr_canv.get());
   if (max_ops > 0)
     hipLaunchKernelGGL(draw_raster_kernel, dim3((unsigned)((max_ops + 3) / 4), (unsigned)n), dim3(256), 0, ctx->stream, dc, d_ops);
   hipLaunchKernelGGL(draw_resolve_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, dc);
@@ -357,10 +357,8 @@ vsf_status vsf_draw_canvases(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int 
   }
   VSF_HIP(hipStreamSynchronize(ctx->stream));  // (the previous call's kernels may still read the staging buffer)
   if (total > ctx->dr_buf_cap) {
-    hipFree(ctx->dr_buf);
-    ctx->dr_buf = nullptr;
     ctx->dr_buf_cap = 0;
-    VSF_HIP(hipMalloc((void**)&ctx->dr_buf, total));
+    VSF_HIP(ctx->dr_buf.alloc(total));
     ctx->dr_buf_cap = total;
   }
   uint8_t* b = ctx->dr_buf;

@@ -1578,7 +1578,7 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
   if (n_par > 0) {
     // (static + dynamic LDS exceed 64 KB for colour files: vsf_prepare_jpeg_kernels raised the limit at vsf_create)
     hipLaunchKernelGGL(jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads), (size_t)p.max_slots * sizeof(DevHuff), s, images, index, tables, stream,
-                       reinterpret_cast<uint32_t*>(scratch.clean),
+                       reinterpret_cast<uint32_t*>(scratch.clean.get()),
                        reinterpret_cast<uint32_t*>(scratch.clean + clean_bytes(stream_bytes, 0)), d_coef, coef_stride,
                        p.max_slots, d_status, status_stride);
   }

@@ -19,58 +19,35 @@ thread_local int vsf_tls_hip_error = 0;
 namespace vsfi {
 
 vsf_status alloc_devset(vsf_ctx* ctx, const Geometry& G, DevSet* ds, bool orb, int n_images) {
-  VSF_HIP(upload(&ds->levels, G.levels));
-  VSF_HIP(upload(&ds->units, G.units));
-  VSF_HIP(upload(&ds->blur_mma_units, G.blur_mma_units));
-  VSF_HIP(upload(&ds->blur_mma_units_small, G.blur_mma_units_small));
-  VSF_HIP(upload(&ds->blur_tcol, G.blur_tcol));
-  VSF_HIP(upload(&ds->blur_tv, G.blur_tv));
-  VSF_HIP(upload(&ds->ic_table, build_ic_table()));
-  VsfDev& d = ds->d;
-  d.ic_table = ds->ic_table;
-  d.levels = ds->levels;
-  d.units = ds->units;
+  VSF_HIP(upload(ds->levels, G.levels));
+  VSF_HIP(upload(ds->units, G.units));
+  VSF_HIP(upload(ds->blur_mma_units, G.blur_mma_units));
+  VSF_HIP(upload(ds->blur_mma_units_small, G.blur_mma_units_small));
+  VSF_HIP(upload(ds->blur_tcol, G.blur_tcol));
+  VSF_HIP(upload(ds->blur_tv, G.blur_tv));
+  VSF_HIP(upload(ds->ic_table, build_ic_table()));
   const size_t n = (size_t)n_images;
   if (orb) {
-    VSF_HIP(hipMalloc((void**)&d.pyr, n * G.g.pyr_bytes));
-    VSF_HIP(hipMalloc((void**)&d.blur, n * G.g.pyr_bytes));
-    VSF_HIP(hipMalloc((void**)&d.scratch, n * 6 * G.g.cand_entries * sizeof(uint32_t)));
-    VSF_HIP(hipMalloc((void**)&d.lvlkp, n * G.g.lvlkp_entries * sizeof(VsfLevelKp)));
-    VSF_HIP(hipMalloc((void**)&d.lvl_count, n * G.g.nlevels * sizeof(int32_t)));
-    VSF_HIP(hipMemset(d.lvl_count, 0, n * G.g.nlevels * sizeof(int32_t)));
+    VSF_HIP(ds->pyr.alloc(n * G.g.pyr_bytes));
+    VSF_HIP(ds->blur.alloc(n * G.g.pyr_bytes));
+    VSF_HIP(ds->scratch.alloc(n * 6 * G.g.cand_entries * sizeof(uint32_t)));
+    VSF_HIP(ds->lvlkp.alloc(n * G.g.lvlkp_entries * sizeof(VsfLevelKp)));
+    VSF_HIP(ds->lvl_count.alloc(n * G.g.nlevels * sizeof(int32_t)));
+    VSF_HIP(hipMemset(ds->lvl_count, 0, n * G.g.nlevels * sizeof(int32_t)));
   }
-  VSF_HIP(hipMalloc((void**)&d.cand, n * G.g.cand_entries * sizeof(uint32_t)));
+  VSF_HIP(ds->cand.alloc(n * G.g.cand_entries * sizeof(uint32_t)));
   const size_t rs_bytes = n * (size_t)std::max(G.g.nunits, 1) * VSF_FAST_RS_STRIDE * sizeof(uint16_t);
-  VSF_HIP(hipMalloc((void**)&d.rowstart, rs_bytes));
-  VSF_HIP(hipMemset(d.rowstart, 0, rs_bytes));
-  d.status = ctx->d_status;
-  d.tune = &ctx->tuning;
+  VSF_HIP(ds->rowstart.alloc(rs_bytes));
+  VSF_HIP(hipMemset(ds->rowstart, 0, rs_bytes));
+  // the view the launchers take (in the order of VsfDev's fields; status_stride 0: the context's one word)
+  ds->d = VsfDev{ds->levels, ds->units,     ds->pyr,       ds->blur,        ds->cand, ds->rowstart, ds->scratch,
+                 ds->lvlkp,  ds->ic_table,  ds->lvl_count, ctx->d_status,   0,        &ctx->tuning};
   ds->ready = true;
   return VSF_OK;
 }
 
-void free_devset(DevSet* ds) {
-  hipFree(ds->levels);
-  hipFree(ds->units);
-  hipFree(ds->blur_mma_units);
-  hipFree(ds->blur_mma_units_small);
-  hipFree(ds->blur_tcol);
-  hipFree(ds->blur_tv);
-  hipFree(ds->ic_table);
-  hipFree(ds->d.pyr);
-  hipFree(ds->d.blur);
-  hipFree(ds->d.scratch);
-  hipFree(ds->d.lvlkp);
-  hipFree(ds->d.lvl_count);
-  hipFree(ds->d.cand);
-  hipFree(ds->d.rowstart);
-  *ds = DevSet();
-}
-
 void free_retired(vsf_ctx* ctx) {  // (callers have waited for every stream of the context)
-  for (void* p : ctx->retired) hipFree(p);
   ctx->retired.clear();
-  for (void* p : ctx->retired_host) hipHostFree(p);
   ctx->retired_host.clear();
 }
 
@@ -91,8 +68,8 @@ vsf_status ensure_match_host_staging(vsf_ctx* ctx, int rows) {  // (host-pointer
   vsf_status st = grow_scratch(ctx, ctx->mh_desc, (size_t)2 * rows * VSF_DESC_BYTES);
   if (st == VSF_OK) st = grow_scratch(ctx, ctx->mh_matches, (size_t)rows * sizeof(vsf_dmatch));
   if (st != VSF_OK) return st;
-  if (!ctx->mh_counts) VSF_HIP(hipMalloc((void**)&ctx->mh_counts, 2 * sizeof(int32_t)));
-  if (!ctx->mh_nmatches) VSF_HIP(hipMalloc((void**)&ctx->mh_nmatches, sizeof(int32_t)));
+  if (!ctx->mh_counts) VSF_HIP(ctx->mh_counts.alloc(2 * sizeof(int32_t)));
+  if (!ctx->mh_nmatches) VSF_HIP(ctx->mh_nmatches.alloc(sizeof(int32_t)));
   ctx->mh_rows = rows;
   return VSF_OK;
 }
@@ -382,10 +359,10 @@ vsf_status extract_async(vsf_ctx* ctx, const VsfImages& im, vsf_keypoint* d_kp, 
 // The second pyramid buffer and the events of cross-call pipelining (vsf_set_pipeline, the ObserveImage queue).
 vsf_status ensure_pipeline_buffers(vsf_ctx* ctx) {
   if (ctx->pyr_alt) return VSF_OK;
-  VSF_HIP(hipMalloc((void**)&ctx->pyr_alt, (size_t)ctx->p.max_images * ctx->orb.g.pyr_bytes));
-  VSF_HIP(hipEventCreateWithFlags(&ctx->ev_pyr_done, hipEventDisableTiming));
-  VSF_HIP(hipEventCreateWithFlags(&ctx->ev_fast_done, hipEventDisableTiming));
-  for (hipEvent_t& e : ctx->ev_pyr_free) VSF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  VSF_HIP(ctx->pyr_alt.alloc((size_t)ctx->p.max_images * ctx->orb.g.pyr_bytes));
+  VSF_HIP(ctx->ev_pyr_done.alloc(hipEventDisableTiming));
+  VSF_HIP(ctx->ev_fast_done.alloc(hipEventDisableTiming));
+  for (Event& e : ctx->ev_pyr_free) VSF_HIP(e.alloc(hipEventDisableTiming));
   return VSF_OK;
 }
 
@@ -482,25 +459,27 @@ vsf_status vsf_create(const vsf_params* p, int device, vsf_ctx** out) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->n_cus = cus;
   }
   if (!build_geometry(ctx->p, true, true, &ctx->orb)) return fail(VSF_ERR_INVALID_ARG);
-  if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(VSF_ERR_HIP);
+  if (ctx->own_stream.alloc(hipStreamNonBlocking) != hipSuccess) return fail(VSF_ERR_HIP);
   ctx->stream = ctx->own_stream;
-  if (hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->side.fork, hipEventDisableTiming) != hipSuccess)
+  vsf_ctx::SideOwner& so = ctx->side_own;
+  if (ctx->aux_stream.alloc(hipStreamNonBlocking) != hipSuccess ||
+      ctx->ev_fork.alloc(hipEventDisableTiming) != hipSuccess ||
+      ctx->ev_join.alloc(hipEventDisableTiming) != hipSuccess ||
+      so.fork.alloc(hipEventDisableTiming) != hipSuccess)
     return fail(VSF_ERR_HIP);
-  if (hipStreamCreateWithFlags(&ctx->blur_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_blur_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_blur_done, hipEventDisableTiming) != hipSuccess)
+  ctx->side.fork = so.fork;
+  if (ctx->blur_stream.alloc(hipStreamNonBlocking) != hipSuccess ||
+      ctx->ev_blur_fork.alloc(hipEventDisableTiming) != hipSuccess ||
+      ctx->ev_blur_done.alloc(hipEventDisableTiming) != hipSuccess)
     return fail(VSF_ERR_HIP);
-  ctx->side.stream[0] = ctx->aux_stream;
   for (int i = 0; i < VSF_SIDE_STREAMS; i++) {
-    if (i > 0 && hipStreamCreateWithFlags(&ctx->side.stream[i], hipStreamNonBlocking) != hipSuccess)
-      return fail(VSF_ERR_HIP);
-    if (hipEventCreateWithFlags(&ctx->side.join[i], hipEventDisableTiming) != hipSuccess) return fail(VSF_ERR_HIP);
+    if (i > 0 && so.stream[i].alloc(hipStreamNonBlocking) != hipSuccess) return fail(VSF_ERR_HIP);
+    if (so.join[i].alloc(hipEventDisableTiming) != hipSuccess) return fail(VSF_ERR_HIP);
+    ctx->side.stream[i] = i > 0 ? so.stream[i].get() : ctx->aux_stream.get();
+    ctx->side.join[i] = so.join[i];
     ctx->side.n = i + 1;
   }
-  if (hipMalloc((void**)&ctx->d_status, 4 * sizeof(int32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
+  if (ctx->d_status.alloc(4 * sizeof(int32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
   if (hipMemset(ctx->d_status, 0, 4 * sizeof(int32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
   {
     // Three kernels ask for more dynamic LDS than the default 64 KB (the parallel sort of GetFeatureMatches, the slab
@@ -524,19 +503,18 @@ vsf_status vsf_create(const vsf_params* p, int device, vsf_ctx** out) {
       ctx->tuning.jpeg_serial = 1;
     }
   }
-  if (hipMalloc((void**)&ctx->fast_cells, 2 * sizeof(uint32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
-  if (hipHostMalloc((void**)&ctx->h_status, sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-    return fail(VSF_ERR_HIP);
+  if (ctx->fast_cells.alloc(2 * sizeof(uint32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
+  if (ctx->h_status.alloc(sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return fail(VSF_ERR_HIP);
   vsf_status st = alloc_devset(ctx, ctx->orb, &ctx->dorb, true, ctx->p.max_images);
   if (st != VSF_OK) return fail(st);
   // staging buffers of the host-pointer API (one image / one set of outputs per image slot)
   ctx->st_img_pitch = (size_t)align_up(ctx->p.width, 64);
   ctx->st_img_stride = ctx->st_img_pitch * (size_t)ctx->p.height;
   const size_t n = (size_t)ctx->p.max_images, K = (size_t)ctx->p.max_keypoints;
-  if (hipMalloc((void**)&ctx->st_img, n * ctx->st_img_stride) != hipSuccess ||
-      hipMalloc((void**)&ctx->st_kp, n * K * sizeof(vsf_keypoint)) != hipSuccess ||
-      hipMalloc((void**)&ctx->st_desc, n * K * VSF_DESC_BYTES) != hipSuccess ||
-      hipMalloc((void**)&ctx->st_counts, n * sizeof(int32_t)) != hipSuccess)
+  if (ctx->st_img.alloc(n * ctx->st_img_stride) != hipSuccess ||
+      ctx->st_kp.alloc(n * K * sizeof(vsf_keypoint)) != hipSuccess ||
+      ctx->st_desc.alloc(n * K * VSF_DESC_BYTES) != hipSuccess ||
+      ctx->st_counts.alloc(n * sizeof(int32_t)) != hipSuccess)
     return fail(VSF_ERR_HIP);
   // scratch of the batched *_dev calls for whole batches of this context (vsf_reserve sizes it for others)
   if (reserve_scratch(ctx, std::max(1, ctx->p.max_images / 2), std::max(1, ctx->p.max_images / 2)) != VSF_OK)
@@ -551,72 +529,9 @@ void vsf_destroy(vsf_ctx* ctx) {
   hipSetDevice(ctx->device);
   stop_observe_threads(ctx);  // (the queue's launcher may be in the middle of a batch)
   // every stream the context ever launched on -- the slots' streams of frames still in flight included: their kernels
-  // write device buffers and pinned host memory that is freed below
+  // write device buffers and pinned host memory that the owners in vsf_ctx release with it
   sync_all_streams(ctx);
   vsf_tls_hip_error = 0;
-  if (ctx->ev_pyr_done) {
-    hipEventDestroy(ctx->ev_pyr_done);
-    hipEventDestroy(ctx->ev_fast_done);
-    for (hipEvent_t e : ctx->ev_pyr_free) hipEventDestroy(e);
-  }
-  if (ctx->ev_ingest_done) hipEventDestroy(ctx->ev_ingest_done);
-  hipFree(ctx->pyr_alt);
-  free_devset(&ctx->dorb);
-  free_devset(&ctx->dfast);
-  hipFree(ctx->d_status);
-  hipFree(ctx->fast_cells);
-  for (hipEvent_t e : ctx->fast_tune.ev)
-    if (e) hipEventDestroy(e);
-  if (ctx->h_status) hipHostFree(ctx->h_status);
-  hipFree(ctx->st_img);
-  hipFree(ctx->st_kp);
-  hipFree(ctx->st_desc);
-  hipFree(ctx->st_counts);
-  hipFree(ctx->m_idx2);
-  hipFree(ctx->m_dist2);
-  hipFree(ctx->f_residual);
-  hipFree(ctx->t_matches);
-  hipFree(ctx->t_nmatches);
-  hipFree(ctx->t_sortkeys);
-  free_observe(ctx);
-  hipFree(ctx->dr_win);
-  hipFree(ctx->dr_canv);
-  hipFree(ctx->dr_buf);
-  if (ctx->dr_uploaded) hipEventDestroy(ctx->dr_uploaded);
-  hipFree(ctx->encode.scratch);
-  hipFree(ctx->encode.staging);
-  free_decode_buffers(ctx->ingest_scratch);
-  for (VsfStaging& stage : ctx->ingest_stage) free_decode_buffers(stage);
-  free_retired(ctx);
-  hipFree(ctx->v_pairs);
-  hipFree(ctx->v_npairs);
-  hipFree(ctx->v_sets);
-  hipFree(ctx->pk_offsets);
-  hipFree(ctx->mm_desc);
-  hipFree(ctx->mm_counts);
-  hipFree(ctx->mm_matches);
-  hipFree(ctx->mm_nmatches);
-  hipFree(ctx->mh_desc);
-  hipFree(ctx->mh_counts);
-  hipFree(ctx->mh_matches);
-  hipFree(ctx->mh_nmatches);
-  for (hipEvent_t e : ctx->ev_pool) hipEventDestroy(e);
-  if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
-  if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-  if (ctx->side.fork) hipEventDestroy(ctx->side.fork);
-  for (int i = 0; i < VSF_SIDE_STREAMS; i++) {
-    if (ctx->side.join[i]) hipEventDestroy(ctx->side.join[i]);
-    if (i > 0 && ctx->side.stream[i]) {
-      hipStreamSynchronize(ctx->side.stream[i]);
-      hipStreamDestroy(ctx->side.stream[i]);
-    }
-  }
-  if (ctx->aux_stream) hipStreamDestroy(ctx->aux_stream);
-  if (ctx->pipe_stream) hipStreamDestroy(ctx->pipe_stream);
-  if (ctx->blur_stream) hipStreamDestroy(ctx->blur_stream);
-  if (ctx->ev_blur_fork) hipEventDestroy(ctx->ev_blur_fork);
-  if (ctx->ev_blur_done) hipEventDestroy(ctx->ev_blur_done);
-  if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
   delete ctx;
 }
 
@@ -739,14 +654,12 @@ vsf_status vsf_set_pipeline(vsf_ctx* ctx, int on) {
   VSF_HIP(hipStreamSynchronize(ctx->aux_stream));  // (the pipelined pyramid chain runs there ...
   if (ctx->pipe_stream) VSF_HIP(hipStreamSynchronize(ctx->pipe_stream));  // ... or on a stream of its own priority)
   if (on && ctx->tuning.pipe_priority != ctx->pipe_stream_priority) {
-    if (ctx->pipe_stream) VSF_HIP(hipStreamDestroy(ctx->pipe_stream));
-    ctx->pipe_stream = nullptr;
+    ctx->pipe_stream.reset();
     ctx->pipe_stream_priority = 0;
     if (ctx->tuning.pipe_priority != 0) {
       int least = 0, greatest = 0;
       VSF_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      VSF_HIP(hipStreamCreateWithPriority(&ctx->pipe_stream, hipStreamNonBlocking,
-                                          ctx->tuning.pipe_priority > 0 ? least : greatest));
+      VSF_HIP(ctx->pipe_stream.alloc(hipStreamNonBlocking, ctx->tuning.pipe_priority > 0 ? least : greatest));
       ctx->pipe_stream_priority = ctx->tuning.pipe_priority;
     }
   }
@@ -765,6 +678,7 @@ vsf_status vsf_sync(vsf_ctx* ctx) {
   if (!ctx) return VSF_ERR_INVALID_ARG;
   const vsf_status st = check_status_word(ctx);
   if (!ctx->retired.empty() || !ctx->retired_host.empty()) {  // scratch a *_dev call outgrew: nothing can be using it once every stream is idle
+    VSF_HIP(hipSetDevice(ctx->device));  // (owners release on the context's device, like every other path that frees)
     sync_all_streams(ctx);
     free_retired(ctx);
   }

@@ -44,8 +44,8 @@ vsf_status vsf_tune_fast_resident(vsf_ctx* ctx, const uint8_t* d_imgs, int n_ima
   T.choice = 0;
   // batches the blur does not run beside have one form only
   if (!(ctx->blur_overlap && n_images >= 32 && ctx->blur_stream && ctx->lanes == 1)) return VSF_OK;
-  for (hipEvent_t& e : T.ev)
-    if (!e) VSF_HIP(hipEventCreate(&e));
+  for (Event& e : T.ev)
+    if (!e) VSF_HIP(e.alloc(hipEventDefault));
   const VsfImages im{d_imgs, image_stride, row_stride, n_images};
   sync_all_streams(ctx);  // nothing of an earlier call beside the timed runs
   std::vector<float> ms[2];

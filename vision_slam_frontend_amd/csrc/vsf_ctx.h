@@ -7,6 +7,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "vsf_internal.h"
@@ -26,15 +27,20 @@ struct Geometry {
   int blur_bias = 0;
 };
 
-struct DevSet {  // device copies of one Geometry + its work buffers
+struct DevSet {  // device copies of one Geometry + its work buffers: the owners, and the view `d` alloc_devset fills from them
   VsfDev d{};
-  VsfLevel* levels = nullptr;
-  uint32_t* units = nullptr;
-  uint32_t* blur_mma_units = nullptr;
-  uint32_t* blur_mma_units_small = nullptr;
-  uint4* blur_tcol = nullptr;
-  uint4* blur_tv = nullptr;
-  uint2* ic_table = nullptr;
+  vsfi::DevBuf<VsfLevel> levels;
+  vsfi::DevBuf<uint32_t> units;
+  vsfi::DevBuf<uint32_t> blur_mma_units;
+  vsfi::DevBuf<uint32_t> blur_mma_units_small;
+  vsfi::DevBuf<uint4> blur_tcol;
+  vsfi::DevBuf<uint4> blur_tv;
+  vsfi::DevBuf<uint2> ic_table;
+  vsfi::DevBuf<uint8_t> pyr, blur;
+  vsfi::DevBuf<uint32_t> scratch, cand;
+  vsfi::DevBuf<VsfLevelKp> lvlkp;
+  vsfi::DevBuf<int32_t> lvl_count;
+  vsfi::DevBuf<uint16_t> rowstart;
   bool ready = false;
 };
 
@@ -50,31 +56,38 @@ struct vsf_ctx {
   vsf_params p{};
   int device = 0;
   int n_cus = 256;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+  // Ownership: every stream the context creates is declared here, BEFORE the events recorded on it and the buffers
+  // its queued work touches -- members die in reverse order, so a stream outlives them.  `stream` is a view: own_stream or the
+  // caller's (vsf_set_stream).
+  vsfi::Stream own_stream;
+  hipStream_t stream = nullptr;
   // Second lane of the batched entry points: half of a batch runs on `stream`, the other half on `aux_stream`
   // (frames are independent), so latency-bound stages of one half overlap VALU-bound stages of the other.
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  vsfi::Stream aux_stream;
+  vsfi::Event ev_fork, ev_join;
   // the blur (matrix cores + memory) beside FAST (vector ALU) in batched calls: its own stream, forked after the pyramid
-  hipStream_t blur_stream = nullptr;
-  hipEvent_t ev_blur_fork = nullptr, ev_blur_done = nullptr;
+  vsfi::Stream blur_stream;
+  vsfi::Event ev_blur_fork, ev_blur_done;
+  struct SideOwner {  // what the view `side` points at; stream[0] stays empty: side.stream[0] is aux_stream
+    vsfi::Stream stream[VSF_SIDE_STREAMS];
+    vsfi::Event fork, join[VSF_SIDE_STREAMS];
+  } side_own;
   VsfSideStream side{};  // aux_stream, for the pyramid's second launch chain
   // Cross-call pipelining (vsf_set_pipeline): the pyramid of call k + 1 is built on side streams, into the other of
   // two pyramid buffers, while call k's later stages still run.
   bool pipeline = false;
-  hipStream_t pipe_stream = nullptr;  // the pipelined chain's own stream when VSF_OPT_PIPE_PRIORITY asks for a priority
+  vsfi::Stream pipe_stream;  // the pipelined chain's own stream when VSF_OPT_PIPE_PRIORITY asks for a priority
   int pipe_stream_priority = 0;
-  uint8_t* pyr_alt = nullptr;
   int pyr_flip = 0;
-  hipEvent_t ev_pyr_done = nullptr, ev_pyr_free[2] = {nullptr, nullptr}, ev_fast_done = nullptr;
+  vsfi::Event ev_pyr_done, ev_pyr_free[2], ev_fast_done;
   bool pyr_free_valid[2] = {false, false}, fast_done_valid = false;
   // A producer the library owns (the Bayer ingest) records this on the context's stream; a pipelined pyramid, which is
   // NOT ordered after that stream's earlier work, waits for it.
-  hipEvent_t ev_ingest_done = nullptr;
+  vsfi::Event ev_ingest_done;
   bool ingest_done_valid = false;
   // ... and ANY other producer hands over an event of its own (vsf_set_input_event): the next batched call -- its
   // pipelined pyramid included -- waits for it; one-shot.
-  hipEvent_t input_event = nullptr;
+  hipEvent_t input_event = nullptr;  // (the caller's: a view)
   const uint8_t* last_pyr = nullptr;
   int lanes = 1;  // 1 = everything on `stream` (default), 2 = two concurrent half batches (vsf_set_lanes)
   int blur_overlap = 1;  // the blur on blur_stream beside FAST / selection (vsf_set_blur_overlap)
@@ -83,67 +96,26 @@ struct vsf_ctx {
   VsfTuning tuning;        // vsf_set_option
   int last_hip = 0;
   int pending_hip = 0;  // an error noted during one of THIS context's calls that returned before checking (VsfErrorScope)
-  vsfi::Geometry orb, fast;
-  vsfi::DevSet dorb, dfast;
-  // Status words (bit 0: capacity overflow, bit 1: a JPEG stream broke off): word 0 belongs to the context's own stream
-  // (batched and host-pointer calls, vsf_sync), words 1..6 to the frames that may be in flight (vsf_observe_submit) --
-  // a frame's kernels run on its slot's stream beside another frame's, so each frame sets, copies and clears its own word.
-  int32_t* d_status = nullptr;     // [1 + VSF_OBSERVE_MAX_SLOTS]
-  uint32_t* fast_cells = nullptr;  // [2] cell counters of the resident FAST kernels (k_fast.hip)
-  struct FastTune {  // resident FAST or one workgroup per four cells: what vsf_tune_fast_resident measured, per batch size
-    int n = 0, choice = -1;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-  } fast_tune;
-  int32_t* h_status = nullptr;  // pinned
-  // staging for the host-pointer entry points
-  uint8_t* st_img = nullptr;
-  size_t st_img_pitch = 0, st_img_stride = 0;
-  vsf_keypoint* st_kp = nullptr;
-  uint8_t* st_desc = nullptr;
-  int32_t* st_counts = nullptr;
-  // matcher work buffers
-  int32_t* m_idx2 = nullptr;
-  int32_t* m_dist2 = nullptr;
-  int m_pairs = 0, m_rows = 0;
-  // f1 work buffers: residuals [frames][rows], F (9 floats), matches / counts / sort keys of the temporal pairs
-  float* f_residual = nullptr;
-  int f_frames = 0;
-  vsf_dmatch* t_matches = nullptr;
-  int32_t* t_nmatches = nullptr;
-  void* t_sortkeys = nullptr;
-  int t_pairs = 0;
-  // f2 work buffers: right->left pairs of every frame, their set indices, the pack kernel's offsets
-  uint64_t* v_pairs = nullptr;
-  int32_t* v_npairs = nullptr;
-  int32_t* v_sets = nullptr;   // [2][v_frames]: q_set = 2f + 1, t_set = 2f
-  int v_frames = 0;
-  uint32_t* pk_offsets = nullptr;
-  int pk_entries = 0;
-  // Scratch a *_dev call has outgrown.  Such a call takes a NEW allocation (hipMalloc does not wait for the GPU) and
-  // parks the old one here, because hipFree would wait for the whole device behind the caller's back; released by
-  // vsf_sync / vsf_reserve / vsf_destroy, when every stream of the context is known to be idle.
-  std::vector<void*> retired;
-  std::vector<void*> retired_host;  // ... and pinned host buffers (the ingest's staging)
   // The ObserveImage queue (vsf_observe.hip): frames wait in pinned staging and leave for the GPU in batches.
   static constexpr int kObserveBatchSlots = 4;
   struct ObserveLauncher;    // the queue's lock and its launcher thread
   struct ObserveCopyHelper;  // a host thread that takes half of a frame's staging copy while frames stream in
   struct ObserveBatchMeta;  // pinned, device-visible: read by the kernels over PCIe (no copy command)
   struct ObserveBatch {     // what one batch's extraction writes and its tail reads
-    uint8_t* d_img = nullptr;        // [2 bmax] images at the staging pitch
-    vsf_keypoint* kp_raw = nullptr;  // [2 bmax][K]
-    uint8_t* desc_raw = nullptr;     // [2 bmax][K][32]
-    int32_t* counts_raw = nullptr;   // [2 bmax]
-    vsf_dmatch* matches = nullptr;   // [bmax][K] raw stereo matches
-    int32_t* nmatches = nullptr;     // [bmax]
-    int32_t* status = nullptr;       // [2 bmax] a status word per image
-    ObserveBatchMeta* h_meta = nullptr;
+    vsfi::DevBuf<uint8_t> d_img;        // [2 bmax] images at the staging pitch
+    vsfi::DevBuf<vsf_keypoint> kp_raw;  // [2 bmax][K]
+    vsfi::DevBuf<uint8_t> desc_raw;     // [2 bmax][K][32]
+    vsfi::DevBuf<int32_t> counts_raw;   // [2 bmax]
+    vsfi::DevBuf<vsf_dmatch> matches;   // [bmax][K] raw stereo matches
+    vsfi::DevBuf<int32_t> nmatches;     // [bmax]
+    vsfi::DevBuf<int32_t> status;       // [2 bmax] a status word per image
+    vsfi::PinnedBuf<ObserveBatchMeta> h_meta;
     // compressed frames: the batch's ONE upload (every run's headers / tables / entropy-coded or IDAT bytes); free once the
     // slot's previous batch has left the GPU (ev_done)
     VsfStaging blob;
-    hipEvent_t ev_uploaded = nullptr, ev_extracted = nullptr, ev_done = nullptr;
+    vsfi::Event ev_uploaded, ev_extracted, ev_done;
     bool used = false;               // ev_done has been recorded at least once
-    hipStream_t done_stream = nullptr;  // the stream its tail ran on
+    hipStream_t done_stream = nullptr;  // the stream its tail ran on (a view)
   };
   struct ObserveFrame {  // per frame slot (ticket % depth), host side
     vsf_calibration calib;
@@ -159,21 +131,28 @@ struct vsf_ctx {
     bool operator==(const DebugForm& o) const { return kind == o.kind && quality == o.quality; }
   };
   struct Observe {
+    // (defined in vsf_observe.hip, where the two thread types are complete; `o = Observe()` releases everything a queue owns)
+    Observe();
+    ~Observe();
+    Observe& operator=(Observe&&) noexcept;
+    vsfi::Stream copy_stream, tail_stream;  // before everything their work touches
+    std::unique_ptr<ObserveLauncher> launcher;
+    std::unique_ptr<ObserveCopyHelper> copy_helper;
     bool ready = false;
     int frame_life = 0;
     bool debug = false;  // built with ob_debug: the batches' tails draw the debug images
     // debug images: device canvases [bmax][dbg_stride], winners [bmax][3 w h], operations [bmax][5 K], canvas table [2 bmax],
     // the newest kept frame's keypoints, {colour cursor (i64), its count}; pinned: the debug ring [depth][dbg_stride] and the
     // colour ring [col_ring] (colours drawn: col_generated, taken by collected frames: col_retired)
-    uint8_t* dbg_canvas = nullptr;
-    uint64_t* dbg_win = nullptr;
-    vsf_draw_op* dbg_ops = nullptr;
-    void* dbg_table = nullptr;
-    vsf_keypoint* dbg_prev_kp = nullptr;
-    int64_t* dbg_ints = nullptr;
+    vsfi::DevBuf<uint8_t> dbg_canvas;
+    vsfi::DevBuf<uint64_t> dbg_win;
+    vsfi::DevBuf<vsf_draw_op> dbg_ops;
+    vsfi::DevBuf<void> dbg_table;
+    vsfi::DevBuf<vsf_keypoint> dbg_prev_kp;
+    vsfi::DevBuf<int64_t> dbg_ints;
     size_t dbg_stride = 0;
-    uint8_t* h_dbg = nullptr;
-    uint32_t* h_col = nullptr;
+    vsfi::PinnedBuf<uint8_t> h_dbg;
+    vsfi::PinnedBuf<uint32_t> h_col;
     int64_t col_ring = 0, col_generated = 0, col_retired = 0;
     // vsf_observe_set_debug_jpeg / _png: the canvases stay on the device; each batch's tail encodes them (k_jpeg_enc.hip /
     // k_png_enc.hip) into device slots and a kernel carries the FILES into the pinned ring h_ring [depth][slot].  A slot: i32 stereo
@@ -182,10 +161,10 @@ struct vsf_ctx {
     struct DebugFiles {
       DebugForm form;                // what the queue was built with (kind 0: raw canvases, nothing below exists)
       size_t off[2] = {0, 0}, cap[2] = {0, 0}, slot = 0;
-      uint8_t* d_slots = nullptr;    // [bmax][slot]
-      int32_t* d_bytes = nullptr;    // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
-      uint8_t* d_scratch = nullptr;  // the encoder's scratch for bmax canvases of either size
-      uint8_t* h_ring = nullptr;
+      vsfi::DevBuf<uint8_t> d_slots;    // [bmax][slot]
+      vsfi::DevBuf<int32_t> d_bytes;    // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
+      vsfi::DevBuf<uint8_t> d_scratch;  // the encoder's scratch for bmax canvases of either size
+      vsfi::PinnedBuf<uint8_t> h_ring;
       int64_t stat_commands = 0;     // launches the compressed debug path issued (vsf_observe_stats)
     } files;
     int depth = 0;      // frames that may be submitted and not collected
@@ -193,37 +172,34 @@ struct vsf_ctx {
     int ring = 0;       // descriptor sets [0, ring): the kept left frames (frame g in set g % ring); [ring, ring + bmax): the
                         // right frames of the batch in the tail
     int max_pairs = 0;  // bmax * (frame_life + 1)
-    uint8_t* sets = nullptr;        // [ring + bmax][K][32]
-    int32_t* set_counts = nullptr;  // [ring + bmax]
+    vsfi::DevBuf<uint8_t> sets;        // [ring + bmax][K][32]
+    vsfi::DevBuf<int32_t> set_counts;  // [ring + bmax]
     // the tail's scratch exists once: tails run one after the other (they carry the threshold and the window)
-    float* residual = nullptr;      // [bmax][K]
-    float* floats = nullptr;        // means [bmax] | thr [bmax + 1] | thr_state
-    vsf_keypoint* kpf = nullptr;    // [2 bmax][K]
-    int32_t* ints = nullptr;        // counts_f [2 bmax] | nfeat [bmax] | npoints [bmax]
-    int32_t *ex_idx2 = nullptr, *ex_dist2 = nullptr;  // [bmax][K][2] the extraction side's matcher scratch
-    int32_t *t_idx2 = nullptr, *t_dist2 = nullptr;    // [max_pairs][K][2] the tail's
-    vsf_dmatch* t_matches = nullptr;                  // [max_pairs][K]
-    int32_t* t_nmatches = nullptr;
-    void* t_sortkeys = nullptr;
-    uint64_t* pairs = nullptr;      // [max_pairs][K][2]
-    int32_t* npairs = nullptr;
-    vsf_vision_feature* features = nullptr;  // [bmax][K]
-    uint8_t* h_img = nullptr;       // pinned [depth][2] images at the staging pitch
-    uint8_t* h_out = nullptr;       // pinned [depth][out_stride], written by observe_pack_kernel
+    vsfi::DevBuf<float> residual;      // [bmax][K]
+    vsfi::DevBuf<float> floats;        // means [bmax] | thr [bmax + 1] | thr_state
+    vsfi::DevBuf<vsf_keypoint> kpf;    // [2 bmax][K]
+    vsfi::DevBuf<int32_t> ints;        // counts_f [2 bmax] | nfeat [bmax] | npoints [bmax]
+    vsfi::DevBuf<int32_t> ex_idx2, ex_dist2;  // [bmax][K][2] the extraction side's matcher scratch
+    vsfi::DevBuf<int32_t> t_idx2, t_dist2;    // [max_pairs][K][2] the tail's
+    vsfi::DevBuf<vsf_dmatch> t_matches;                  // [max_pairs][K]
+    vsfi::DevBuf<int32_t> t_nmatches;
+    vsfi::DevBuf<void> t_sortkeys;
+    vsfi::DevBuf<uint64_t> pairs;      // [max_pairs][K][2]
+    vsfi::DevBuf<int32_t> npairs;
+    vsfi::DevBuf<vsf_vision_feature> features;  // [bmax][K]
+    vsfi::PinnedBuf<uint8_t> h_img;       // pinned [depth][2] images at the staging pitch
+    vsfi::PinnedBuf<uint8_t> h_out;       // pinned [depth][out_stride], written by observe_pack_kernel
     // vsf_observe_submit_compressed; nothing of this exists before the first compressed frame.  The files wait in a pinned
     // ring of their own; a batch's decode runs on the copy stream (one batch after the other: ONE set of decoder scratch)
-    uint8_t* h_cmp = nullptr;       // pinned [depth][2][cmp_slot] the files as submitted
+    vsfi::PinnedBuf<uint8_t> h_cmp;       // pinned [depth][2][cmp_slot] the files as submitted
     size_t cmp_cap = 0, cmp_slot = 0;  // bytes a file may have / bytes of its slot (vsf_observe_compressed_slot_bytes)
-    uint8_t* d_bayer = nullptr;     // [2 bmax] images at the staging pitch: the decoded mosaics of a Bayer batch
+    vsfi::DevBuf<uint8_t> d_bayer;     // [2 bmax] images at the staging pitch: the decoded mosaics of a Bayer batch
     VsfDecodeScratch ing_scratch;   // the decoders' scratch on the copy stream
     int64_t stat_compressed = 0;    // compressed frames launched
     int64_t stat_ingest_commands = 0;  // copy commands + launches the compressed path issued
     size_t out_cap = 0, out_stride = 0;
     ObserveBatch batch[kObserveBatchSlots];
     std::vector<ObserveFrame> frames;  // [depth]
-    hipStream_t copy_stream = nullptr, tail_stream = nullptr;
-    ObserveLauncher* launcher = nullptr;
-    ObserveCopyHelper* copy_helper = nullptr;
     int64_t next_ticket = 0;   // tickets issued
     int64_t next_launch = 0;   // first frame still waiting in staging
     int64_t next_collect = 0;  // oldest frame not collected
@@ -239,15 +215,58 @@ struct vsf_ctx {
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
+  // ---- buffers: every stream above, the queue's two included, outlives them ----
+  vsfi::DevBuf<uint8_t> pyr_alt;  // the other pyramid buffer of cross-call pipelining
+  vsfi::Geometry orb, fast;
+  vsfi::DevSet dorb, dfast;
+  // Status words (bit 0: capacity overflow, bit 1: a JPEG stream broke off): word 0 belongs to the context's own stream
+  // (batched and host-pointer calls, vsf_sync), words 1..6 to the frames that may be in flight (vsf_observe_submit) --
+  // a frame's kernels run on its slot's stream beside another frame's, so each frame sets, copies and clears its own word.
+  vsfi::DevBuf<int32_t> d_status;     // [1 + VSF_OBSERVE_MAX_SLOTS]
+  vsfi::DevBuf<uint32_t> fast_cells;  // [2] cell counters of the resident FAST kernels (k_fast.hip)
+  struct FastTune {  // resident FAST or one workgroup per four cells: what vsf_tune_fast_resident measured, per batch size
+    int n = 0, choice = -1;
+    vsfi::Event ev[2];
+  } fast_tune;
+  vsfi::PinnedBuf<int32_t> h_status;  // pinned
+  // staging for the host-pointer entry points
+  vsfi::DevBuf<uint8_t> st_img;
+  size_t st_img_pitch = 0, st_img_stride = 0;
+  vsfi::DevBuf<vsf_keypoint> st_kp;
+  vsfi::DevBuf<uint8_t> st_desc;
+  vsfi::DevBuf<int32_t> st_counts;
+  // matcher work buffers
+  vsfi::DevBuf<int32_t> m_idx2;
+  vsfi::DevBuf<int32_t> m_dist2;
+  int m_pairs = 0, m_rows = 0;
+  // f1 work buffers: residuals [frames][rows], F (9 floats), matches / counts / sort keys of the temporal pairs
+  vsfi::DevBuf<float> f_residual;
+  int f_frames = 0;
+  vsfi::DevBuf<vsf_dmatch> t_matches;
+  vsfi::DevBuf<int32_t> t_nmatches;
+  vsfi::DevBuf<void> t_sortkeys;
+  int t_pairs = 0;
+  // f2 work buffers: right->left pairs of every frame, their set indices, the pack kernel's offsets
+  vsfi::DevBuf<uint64_t> v_pairs;
+  vsfi::DevBuf<int32_t> v_npairs;
+  vsfi::DevBuf<int32_t> v_sets;   // [2][v_frames]: q_set = 2f + 1, t_set = 2f
+  int v_frames = 0;
+  vsfi::DevBuf<uint32_t> pk_offsets;
+  int pk_entries = 0;
+  // Scratch a *_dev call has outgrown.  Such a call takes a NEW allocation (hipMalloc does not wait for the GPU) and
+  // parks the old one here, because hipFree would wait for the whole device behind the caller's back; released by
+  // vsf_sync / vsf_reserve / vsf_destroy, when every stream of the context is known to be idle.
+  std::vector<vsfi::DevBuf<void>> retired;
+  std::vector<vsfi::PinnedBuf<void>> retired_host;  // ... and pinned host buffers (the ingest's staging)
   // vsf_draw_canvases(_dev) (k_draw.hip): per-pixel winners (all zero between calls: the resolve clears what it read),
   // the canvas table (device, and its host image until the upload has left: dr_uploaded), the host call's staging
-  uint64_t* dr_win = nullptr;
+  vsfi::DevBuf<uint64_t> dr_win;
   size_t dr_win_cap = 0;
-  void* dr_canv = nullptr;
+  vsfi::DevBuf<void> dr_canv;
   int dr_canv_cap = 0;
   std::vector<uint8_t> dr_canv_host;
-  hipEvent_t dr_uploaded = nullptr;
-  uint8_t* dr_buf = nullptr;
+  vsfi::Event dr_uploaded;
+  vsfi::DevBuf<uint8_t> dr_buf;
   size_t dr_buf_cap = 0;
   // vsf_jpeg_decode_gray_batch / vsf_png_decode_gray_batch: two staging pairs, used alternately (the host fills one while the
   // previous call's upload / decode still use the other; `uploaded`: the last upload out of the pair has finished), and the
@@ -256,23 +275,23 @@ struct vsf_ctx {
   int ingest_flip = 0;
   VsfDecodeScratch ingest_scratch;
   VsfEncodeScratch encode;  // vsf_jpeg_encode* / vsf_png_encode*
-  uint8_t* mh_desc = nullptr;  // host-API descriptor staging: 2 sets
-  int32_t* mh_counts = nullptr;
-  vsf_dmatch* mh_matches = nullptr;
-  int32_t* mh_nmatches = nullptr;
+  vsfi::DevBuf<uint8_t> mh_desc;  // host-API descriptor staging: 2 sets
+  vsfi::DevBuf<int32_t> mh_counts;
+  vsfi::DevBuf<vsf_dmatch> mh_matches;
+  vsfi::DevBuf<int32_t> mh_nmatches;
   int mh_rows = 0;
   // vsf_get_matches_multi staging: sets x rows descriptors, per-set counts / set indices / matches
-  uint8_t* mm_desc = nullptr;
-  int32_t* mm_counts = nullptr;  // [sets + 1] counts, then [sets] q_set, [sets] t_set
-  vsf_dmatch* mm_matches = nullptr;
-  int32_t* mm_nmatches = nullptr;
+  vsfi::DevBuf<uint8_t> mm_desc;
+  vsfi::DevBuf<int32_t> mm_counts;  // [sets + 1] counts, then [sets] q_set, [sets] t_set
+  vsfi::DevBuf<vsf_dmatch> mm_matches;
+  vsfi::DevBuf<int32_t> mm_nmatches;
   int mm_sets = 0, mm_rows = 0;
   VsfImages last_images{};
   bool last_valid = false;
   bool fast_nms = true;  // NMS mode the standalone-FAST geometry was built for
   // per-stage hipEvent profiling
   bool prof_on = false;
-  std::vector<hipEvent_t> ev_pool;  // pairs
+  std::vector<vsfi::Event> ev_pool;  // pairs
   std::vector<int> ev_stage;        // stage of pair i
   std::vector<int> ev_launches;
   size_t ev_used = 0;               // pairs in flight
@@ -306,24 +325,23 @@ struct vsf_ctx {
 namespace vsfi {
 
 template <class T>
-hipError_t upload(T** dst, const std::vector<T>& v) {
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T));
+hipError_t upload(DevBuf<T>& dst, const std::vector<T>& v) {
+  hipError_t e = dst.alloc(v.size() * sizeof(T));
   if (e != hipSuccess) return e;
-  return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+  return hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 vsf_status alloc_devset(vsf_ctx* ctx, const Geometry& G, DevSet* ds, bool orb, int n_images);
-void free_devset(DevSet* ds);
 
 // ---- scratch that follows the batch size of the *_dev calls ----
 // Sized at vsf_create for max_images / 2 frames and as many pairs, or by vsf_reserve.  A call that needs more never waits
 // for the GPU: grow_scratch() allocates anew and retires the old buffer (kernels already queued keep using it).
 template <class T>
-vsf_status grow_scratch(vsf_ctx* ctx, T*& ptr, size_t bytes) {
-  void* fresh = nullptr;
-  VSF_HIP(hipMalloc(&fresh, std::max<size_t>(bytes, 16)));
-  if (ptr) ctx->retired.push_back(static_cast<void*>(ptr));
-  ptr = static_cast<T*>(fresh);
+vsf_status grow_scratch(vsf_ctx* ctx, DevBuf<T>& buf, size_t bytes) {
+  DevBuf<T> fresh;
+  VSF_HIP(fresh.alloc(std::max<size_t>(bytes, 16)));
+  if (buf) ctx->retired.emplace_back(buf.release());
+  buf = std::move(fresh);
   return VSF_OK;
 }
 void free_retired(vsf_ctx* ctx);  // (callers have waited for every stream of the context)
@@ -336,8 +354,6 @@ void free_retired(vsf_ctx* ctx);  // (callers have waited for every stream of th
 vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width,
                        int height, VsfStaging& stage, VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride,
                        int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs = nullptr);
-void free_decode_buffers(VsfStaging& stage);  // (the GPU has left them)
-void free_decode_buffers(VsfDecodeScratch& scratch);
 vsf_status ensure_match_buffers(vsf_ctx* ctx, int pairs, int rows);
 vsf_status ensure_match_host_staging(vsf_ctx* ctx, int rows);  // (host-pointer, synchronous entry points only)
 vsf_status ensure_residual_buffers(vsf_ctx* ctx, int n_frames);
@@ -346,7 +362,7 @@ vsf_status ensure_vision_buffers(vsf_ctx* ctx, int n_frames);
 vsf_status ensure_pack_buffers(vsf_ctx* ctx, int n);
 vsf_status reserve_scratch(vsf_ctx* ctx, int n_frames, int n_pairs);
 vsf_status ensure_pipeline_buffers(vsf_ctx* ctx);
-void free_observe(vsf_ctx* ctx);          // vsf_observe.hip
+void free_observe(vsf_ctx* ctx);          // vsf_observe.hip: the queue's threads stop, then everything the queue owns goes
 void stop_observe_threads(vsf_ctx* ctx);  // ... before anything waits for the context's streams to drain
 
 vsf_status check_status_word(vsf_ctx* ctx);
@@ -367,9 +383,8 @@ struct StageTimer {  // records an event pair around one stage when profiling is
     }
     slot = ctx->ev_used++;
     while (ctx->ev_pool.size() < 2 * (slot + 1)) {
-      hipEvent_t e = nullptr;
-      vsf_note(hipEventCreate(&e));
-      ctx->ev_pool.push_back(e);
+      ctx->ev_pool.emplace_back();
+      vsf_note(ctx->ev_pool.back().alloc(hipEventDefault));
     }
     if (ctx->ev_stage.size() <= slot) {
       ctx->ev_stage.resize(slot + 1);

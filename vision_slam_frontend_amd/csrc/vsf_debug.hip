@@ -76,20 +76,17 @@ vsf_status vsf_debug_retain_best(vsf_ctx* ctx, uint32_t* key_bits, uint32_t* ids
   VSF_HIP(hipSetDevice(ctx->device));
   std::vector<uint2> h((size_t)std::max(n, 1));
   for (int i = 0; i < n; i++) h[i] = make_uint2(key_bits[i], ids[i]);
-  uint2* d = nullptr;
-  uint32_t* dt = nullptr;
-  int* dn = nullptr;
-  VSF_HIP(hipMalloc((void**)&d, h.size() * sizeof(uint2)));
-  VSF_HIP(hipMalloc((void**)&dt, 2 * h.size() * sizeof(uint32_t)));
-  VSF_HIP(hipMalloc((void**)&dn, sizeof(int)));
+  DevBuf<uint2> d;
+  DevBuf<uint32_t> dt;
+  DevBuf<int> dn;
+  VSF_HIP(d.alloc(h.size() * sizeof(uint2)));
+  VSF_HIP(dt.alloc(2 * h.size() * sizeof(uint32_t)));
+  VSF_HIP(dn.alloc(sizeof(int)));
   VSF_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(uint2), hipMemcpyHostToDevice));
   vsf_launch_retain_best_test(d, dt, n, n_points, use_lds, mode, dn, ctx->stream);
   hipError_t e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(h.data(), d, h.size() * sizeof(uint2), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(n_out, dn, sizeof(int), hipMemcpyDeviceToHost);
-  hipFree(d);
-  hipFree(dt);
-  hipFree(dn);
   if (e != hipSuccess) {
     ctx->last_hip = (int)e;
     return VSF_ERR_HIP;
@@ -108,15 +105,15 @@ vsf_status vsf_debug_sort_trim(vsf_ctx* ctx, const vsf_dmatch* matches, int n_li
     return VSF_ERR_INVALID_ARG;
   VSF_HIP(hipSetDevice(ctx->device));
   const size_t K = (size_t)ctx->p.max_keypoints;
-  vsf_dmatch* dm = nullptr;
-  int32_t *dn = nullptr, *dc = nullptr;
-  uint64_t* dp = nullptr;
-  void* dscratch = nullptr;
-  hipError_t e = hipMalloc((void**)&dm, (size_t)n_lists * K * sizeof(vsf_dmatch));
-  if (e == hipSuccess) e = hipMalloc((void**)&dn, (size_t)n_lists * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&dc, (size_t)n_lists * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&dp, (size_t)n_lists * K * 2 * sizeof(uint64_t));
-  if (e == hipSuccess) e = hipMalloc(&dscratch, (size_t)n_lists * K * 8);
+  DevBuf<vsf_dmatch> dm;
+  DevBuf<int32_t> dn, dc;
+  DevBuf<uint64_t> dp;
+  DevBuf<void> dscratch;
+  hipError_t e = dm.alloc((size_t)n_lists * K * sizeof(vsf_dmatch));
+  if (e == hipSuccess) e = dn.alloc((size_t)n_lists * sizeof(int32_t));
+  if (e == hipSuccess) e = dc.alloc((size_t)n_lists * sizeof(int32_t));
+  if (e == hipSuccess) e = dp.alloc((size_t)n_lists * K * 2 * sizeof(uint64_t));
+  if (e == hipSuccess) e = dscratch.alloc((size_t)n_lists * K * 8);
   std::vector<int32_t> hn((size_t)n_lists, n);
   if (e == hipSuccess) e = hipMemcpy(dn, hn.data(), hn.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   for (int i = 0; i < n_lists && e == hipSuccess && n > 0; i++)
@@ -130,11 +127,6 @@ vsf_status vsf_debug_sort_trim(vsf_ctx* ctx, const vsf_dmatch* matches, int n_li
   for (int i = 0; i < n_lists && e == hipSuccess && n > 0; i++)
     e = hipMemcpy(pairs_out + (size_t)i * n * 2, dp + (size_t)i * K * 2, (size_t)n * 2 * sizeof(uint64_t),
                   hipMemcpyDeviceToHost);
-  hipFree(dm);
-  hipFree(dn);
-  hipFree(dc);
-  hipFree(dp);
-  hipFree(dscratch);
   if (e != hipSuccess) {
     ctx->last_hip = (int)e;
     return VSF_ERR_HIP;

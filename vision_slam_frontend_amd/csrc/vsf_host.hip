@@ -97,7 +97,7 @@ vsf_status vsf_fast_detect(vsf_ctx* ctx, const uint8_t* img, int w, int h, size_
   // may be a corner, so that geometry is (re)built with full-density segments.
   if (!ctx->dfast.ready || ctx->fast_nms != want_nms) {
     VSF_HIP(hipStreamSynchronize(ctx->stream));
-    free_devset(&ctx->dfast);
+    ctx->dfast = DevSet();
     ctx->fast = Geometry();
     if (!build_geometry(ctx->p, false, want_nms, &ctx->fast)) return VSF_ERR_INVALID_ARG;
     vsf_status st0 = alloc_devset(ctx, ctx->fast, &ctx->dfast, false, 1);
@@ -111,10 +111,10 @@ vsf_status vsf_fast_detect(vsf_ctx* ctx, const uint8_t* img, int w, int h, size_
   const int kcap = ctx->p.max_keypoints;
   vsf_launch_fast(ctx->dfast.d, ctx->fast.g, im, threshold, want_nms ? 1 : 0, ctx->stream);
   vsf_keypoint* d_out = ctx->st_kp;
-  vsf_keypoint* big = nullptr;
+  DevBuf<vsf_keypoint> big;
   int outcap = kcap;
   if (cap > kcap) {
-    VSF_HIP(hipMalloc((void**)&big, (size_t)cap * sizeof(vsf_keypoint)));
+    VSF_HIP(big.alloc((size_t)cap * sizeof(vsf_keypoint)));
     d_out = big;
     outcap = cap;
   }
@@ -131,7 +131,6 @@ vsf_status vsf_fast_detect(vsf_ctx* ctx, const uint8_t* img, int w, int h, size_
     if (m > 0) e = hipMemcpy(kp_out, d_out, (size_t)m * sizeof(vsf_keypoint), hipMemcpyDeviceToHost);
     if (e == hipSuccess) st = n > m ? VSF_ERR_CAPACITY : VSF_OK;  // the status word only reflects `outcap`
   }
-  if (big) hipFree(big);
   if (e != hipSuccess) {
     ctx->last_hip = (int)e;
     return VSF_ERR_HIP;
@@ -198,19 +197,11 @@ vsf_status vsf_get_matches_multi(vsf_ctx* ctx, const uint8_t* const* q, const in
   if (n_sets > ctx->mm_sets || rows > ctx->mm_rows) {
     const int S = std::max(n_sets, ctx->mm_sets), R = std::max(rows, ctx->mm_rows);
     VSF_HIP(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->mm_desc);
-    hipFree(ctx->mm_counts);
-    hipFree(ctx->mm_matches);
-    hipFree(ctx->mm_nmatches);
-    ctx->mm_desc = nullptr;
-    ctx->mm_counts = nullptr;
-    ctx->mm_matches = nullptr;
-    ctx->mm_nmatches = nullptr;
     ctx->mm_sets = ctx->mm_rows = 0;
-    VSF_HIP(hipMalloc((void**)&ctx->mm_desc, (size_t)(S + 1) * R * VSF_DESC_BYTES));
-    VSF_HIP(hipMalloc((void**)&ctx->mm_counts, (size_t)(3 * S + 1) * sizeof(int32_t)));
-    VSF_HIP(hipMalloc((void**)&ctx->mm_matches, (size_t)S * R * sizeof(vsf_dmatch)));
-    VSF_HIP(hipMalloc((void**)&ctx->mm_nmatches, (size_t)S * sizeof(int32_t)));
+    VSF_HIP(ctx->mm_desc.alloc((size_t)(S + 1) * R * VSF_DESC_BYTES));
+    VSF_HIP(ctx->mm_counts.alloc((size_t)(3 * S + 1) * sizeof(int32_t)));
+    VSF_HIP(ctx->mm_matches.alloc((size_t)S * R * sizeof(vsf_dmatch)));
+    VSF_HIP(ctx->mm_nmatches.alloc((size_t)S * sizeof(int32_t)));
     ctx->mm_sets = S;
     ctx->mm_rows = R;
   }

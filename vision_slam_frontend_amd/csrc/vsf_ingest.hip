@@ -19,7 +19,7 @@ namespace {
 // retired (an upload or a decode already queued may still be using it) and released by the next vsf_sync, like every other
 // scratch a *_dev call outgrows.
 template <class T>
-vsf_status grow_decode_scratch(vsf_ctx* ctx, T*& ptr, size_t& cap, size_t need) {
+vsf_status grow_decode_scratch(vsf_ctx* ctx, DevBuf<T>& ptr, size_t& cap, size_t need) {
   if (need <= cap) return VSF_OK;
   const size_t want = need + need / 4;
   const vsf_status st = grow_scratch(ctx, ptr, want);
@@ -29,24 +29,24 @@ vsf_status grow_decode_scratch(vsf_ctx* ctx, T*& ptr, size_t& cap, size_t need) 
 
 vsf_status grow_staging(vsf_ctx* ctx, VsfStaging& stage, size_t need) {
   const size_t cap = need + need / 4 + 4096;
-  void *host = nullptr, *dev = nullptr;
-  VSF_HIP(hipHostMalloc(&host, cap, hipHostMallocDefault));
-  if (hipMalloc(&dev, cap) != hipSuccess) {
-    hipHostFree(host);
+  PinnedBuf<uint8_t> host;
+  DevBuf<uint8_t> dev;
+  VSF_HIP(host.alloc(cap, hipHostMallocDefault));
+  if (dev.alloc(cap) != hipSuccess) {
     (void)hipGetLastError();
     return VSF_ERR_HIP;
   }
-  if (stage.h) ctx->retired_host.push_back(stage.h);
-  if (stage.d) ctx->retired.push_back(stage.d);
-  stage.h = static_cast<uint8_t*>(host);
-  stage.d = static_cast<uint8_t*>(dev);
+  if (stage.h) ctx->retired_host.emplace_back(stage.h.release());
+  if (stage.d) ctx->retired.emplace_back(stage.d.release());
+  stage.h = std::move(host);
+  stage.d = std::move(dev);
   stage.cap = cap;
   return VSF_OK;
 }
 
 // a pipelined extract that follows (vsf_set_pipeline) builds its pyramid off this stream: give it something to wait for
 vsf_status record_ingest_done(vsf_ctx* ctx) {
-  if (!ctx->ev_ingest_done) VSF_HIP(hipEventCreateWithFlags(&ctx->ev_ingest_done, hipEventDisableTiming));
+  if (!ctx->ev_ingest_done) VSF_HIP(ctx->ev_ingest_done.alloc(hipEventDisableTiming));
   VSF_HIP(hipEventRecord(ctx->ev_ingest_done, ctx->stream));
   ctx->ingest_done_valid = true;
   return VSF_OK;
@@ -69,7 +69,7 @@ vsf_status decode_gray_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* f
   // the staging pair the call before the previous one used: its upload has left it long ago (the previous call's upload and
   // decode are what may still be running, out of the OTHER pair)
   VsfStaging& stage = ctx->ingest_stage[ctx->ingest_flip];
-  if (!stage.uploaded) VSF_HIP(hipEventCreateWithFlags(&stage.uploaded, hipEventDisableTiming));
+  if (!stage.uploaded) VSF_HIP(stage.uploaded.alloc(hipEventDisableTiming));
   const std::vector<uint8_t> kinds((size_t)n_images, kind);
   const vsf_status st = decode_runs(ctx, files, nbytes, kinds.data(), n_images, width, height, stage, ctx->ingest_scratch, d_dst,
                                     dst_image_stride, (int)dst_row_stride, ctx->d_status, 0, ctx->stream);
@@ -180,22 +180,6 @@ vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* 
   }
   if (n_runs) *n_runs = (int)plan.runs.size();
   return VSF_OK;
-}
-
-void free_decode_buffers(VsfStaging& stage) {
-  if (stage.h) hipHostFree(stage.h);
-  hipFree(stage.d);
-  if (stage.uploaded) hipEventDestroy(stage.uploaded);
-  stage = VsfStaging();
-}
-
-void free_decode_buffers(VsfDecodeScratch& scratch) {
-  hipFree(scratch.clean);
-  hipFree(scratch.coef);
-  hipFree(scratch.flags);
-  hipFree(scratch.filtered);
-  hipFree(scratch.file_status);
-  scratch = VsfDecodeScratch();
 }
 
 }  // namespace vsfi

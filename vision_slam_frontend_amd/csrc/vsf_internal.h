@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/vsf.h"
+#include "vsf_own.h"     // DevBuf, PinnedBuf, Event, Stream
 #include "vsf_resize.h"  // VsfTap, the resize coefficient formula, the packing plan
 
 // FAST march kernel: a wave owns a band of 248 keypoint columns (lanes 1..62 x 4 px; lanes 0 and 63 carry the raw halo
@@ -330,11 +331,11 @@ void vsf_png_fill(const VsfPngPlan& plan, const uint8_t* const* png, int n, uint
 // What the decode kernels of ONE stream need beside the upload.  Grown by decode_runs (vsf_ingest.hip), never shrunk; the
 // capacities are bytes.
 struct VsfDecodeScratch {
-  uint8_t* clean = nullptr;        // JPEG, parallel decode: the de-stuffed streams and their segment-major copies
-  int16_t* coef = nullptr;         // JPEG: luminance coefficients, then the expanded Huffman tables of progressive scans
-  int32_t* flags = nullptr;        // JPEG: per progressive file "damaged: decode again scan after scan"
-  uint8_t* filtered = nullptr;     // PNG: the inflated scanlines
-  int32_t* file_status = nullptr;  // PNG: per file, what its inflate made of the stream
+  vsfi::DevBuf<uint8_t> clean;        // JPEG, parallel decode: the de-stuffed streams and their segment-major copies
+  vsfi::DevBuf<int16_t> coef;         // JPEG: luminance coefficients, then the expanded Huffman tables of progressive scans
+  vsfi::DevBuf<int32_t> flags;        // JPEG: per progressive file "damaged: decode again scan after scan"
+  vsfi::DevBuf<uint8_t> filtered;     // PNG: the inflated scanlines
+  vsfi::DevBuf<int32_t> file_status;  // PNG: per file, what its inflate made of the stream
   size_t clean_cap = 0, coef_cap = 0, flags_cap = 0, filtered_cap = 0, file_status_cap = 0;
   size_t bytes() const { return clean_cap + coef_cap + flags_cap + filtered_cap + file_status_cap; }
 };
@@ -344,10 +345,10 @@ struct VsfDecodeNeed {  // bytes of each; the needs of several runs on one strea
 // Pinned staging + its device copy for ONE upload.  `uploaded` (optional): recorded behind the upload, and waited for before
 // the host writes the pair again -- an owner that knows the pair to be free by other means leaves it null.
 struct VsfStaging {
-  uint8_t* h = nullptr;
-  uint8_t* d = nullptr;
+  vsfi::PinnedBuf<uint8_t> h;
+  vsfi::DevBuf<uint8_t> d;
   size_t cap = 0;
-  hipEvent_t uploaded = nullptr;
+  vsfi::Event uploaded;
 };
 // Each launcher owns everything derived from its plan: offsets into the upload, strides and positions inside the scratch,
 // which kernels a run takes.  `n` files of width x height land at d_dst + i * dst_image_stride.
@@ -415,8 +416,8 @@ inline void vsf_launch_encode(const VsfEncodeJob& j, const uint8_t* d_src, void*
 // they share one scratch and one staging buffer.  A call that needs more takes a new allocation without waiting (grow_scratch
 // retires the outgrown buffer, which an encode already queued may still be using, until the next vsf_sync).  Bytes; never shrunk.
 struct VsfEncodeScratch {
-  uint8_t* scratch = nullptr;  // *_encode_batch_dev: the encoder's work buffers (a quarter of headroom when it grows)
-  uint8_t* staging = nullptr;  // the host-pointer calls: images | files | byte counts on the device (grown to the need)
+  vsfi::DevBuf<uint8_t> scratch;  // *_encode_batch_dev: the encoder's work buffers (a quarter of headroom when it grows)
+  vsfi::DevBuf<uint8_t> staging;  // the host-pointer calls: images | files | byte counts on the device (grown to the need)
   size_t scratch_cap = 0, staging_cap = 0;
 };
 // The queue's debug files (k_frontend.hip): file i (d_bytes[i] bytes at d_files + i * file_stride; nothing when negative) goes to

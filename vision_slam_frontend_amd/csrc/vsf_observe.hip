@@ -186,67 +186,24 @@ void stop_observe_threads(vsf_ctx* ctx) {
     o.launcher->th.join();
     o.launcher->has_thread = false;
   }
-  delete o.copy_helper;
-  o.copy_helper = nullptr;
+  o.copy_helper.reset();
 }
 
 void free_observe(vsf_ctx* ctx) {
   vsf_ctx::Observe& o = ctx->ob;
   stop_observe_threads(ctx);
-  delete o.launcher;
-  hipFree(o.sets);
-  hipFree(o.set_counts);
-  hipFree(o.residual);
-  hipFree(o.floats);
-  hipFree(o.kpf);
-  hipFree(o.ints);
-  hipFree(o.ex_idx2);
-  hipFree(o.ex_dist2);
-  hipFree(o.t_idx2);
-  hipFree(o.t_dist2);
-  hipFree(o.t_matches);
-  hipFree(o.t_nmatches);
-  hipFree(o.t_sortkeys);
-  hipFree(o.pairs);
-  hipFree(o.npairs);
-  hipFree(o.features);
-  if (o.h_img) hipHostFree(o.h_img);
-  if (o.h_out) hipHostFree(o.h_out);
-  if (o.h_cmp) hipHostFree(o.h_cmp);
-  hipFree(o.d_bayer);
-  free_decode_buffers(o.ing_scratch);
-  hipFree(o.dbg_canvas);
-  hipFree(o.dbg_win);
-  hipFree(o.dbg_ops);
-  hipFree(o.dbg_table);
-  hipFree(o.dbg_prev_kp);
-  hipFree(o.dbg_ints);
-  if (o.h_dbg) hipHostFree(o.h_dbg);
-  hipFree(o.files.d_slots);
-  hipFree(o.files.d_bytes);
-  hipFree(o.files.d_scratch);
-  if (o.files.h_ring) hipHostFree(o.files.h_ring);
-  if (o.h_col) hipHostFree(o.h_col);
-  for (vsf_ctx::ObserveBatch& b : o.batch) {
-    hipFree(b.d_img);
-    hipFree(b.kp_raw);
-    hipFree(b.desc_raw);
-    hipFree(b.counts_raw);
-    hipFree(b.matches);
-    hipFree(b.nmatches);
-    hipFree(b.status);
-    if (b.h_meta) hipHostFree(b.h_meta);
-    free_decode_buffers(b.blob);
-    if (b.ev_uploaded) hipEventDestroy(b.ev_uploaded);
-    if (b.ev_extracted) hipEventDestroy(b.ev_extracted);
-    if (b.ev_done) hipEventDestroy(b.ev_done);
-  }
-  if (o.copy_stream) hipStreamDestroy(o.copy_stream);
-  if (o.tail_stream) hipStreamDestroy(o.tail_stream);
+  // launch_batch publishes a batch slot's images as the context's last input (the vsf_debug_* level-0 reads): that view dies here
+  for (const vsf_ctx::ObserveBatch& b : o.batch)
+    if (b.d_img && ctx->last_images.base == b.d_img) ctx->last_valid = false;
   o = vsf_ctx::Observe();
 }
 
 }  // namespace vsfi
+
+// (here, where the two thread types are complete: the unique_ptr members need them)
+vsf_ctx::Observe::Observe() = default;
+vsf_ctx::Observe::~Observe() = default;
+vsf_ctx::Observe& vsf_ctx::Observe::operator=(Observe&&) noexcept = default;
 
 namespace {
 
@@ -276,13 +233,13 @@ vsf_status alloc_debug_files(vsf_ctx* ctx) {
   const size_t B = (size_t)o.bmax;
   debug_files_slot_layout(f, ctx->p.width, ctx->p.height);
   if (f.cap[0] > 0x7FFFFFF0u) return VSF_ERR_UNSUPPORTED;
-  VSF_HIP(hipMalloc((void**)&f.d_slots, B * f.slot));
+  VSF_HIP(f.d_slots.alloc(B * f.slot));
   // (+ the encoder's status word: a file that does not fit leaves its count at -1, which is what the view reports)
-  VSF_HIP(hipMalloc((void**)&f.d_bytes, (2 * B + 1) * sizeof(int32_t)));
+  VSF_HIP(f.d_bytes.alloc((2 * B + 1) * sizeof(int32_t)));
   VSF_HIP(hipMemset(f.d_bytes, 0, (2 * B + 1) * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&f.d_scratch, std::max(vsf_encode_scratch_need(debug_files_job(ctx, 0, o.bmax)),
+  VSF_HIP(f.d_scratch.alloc(std::max(vsf_encode_scratch_need(debug_files_job(ctx, 0, o.bmax)),
                                                    vsf_encode_scratch_need(debug_files_job(ctx, 1, o.bmax)))));
-  VSF_HIP(hipHostMalloc((void**)&f.h_ring, (size_t)o.depth * f.slot, hipHostMallocMapped));
+  VSF_HIP(f.h_ring.alloc((size_t)o.depth * f.slot, hipHostMallocMapped));
   return VSF_OK;
 }
 
@@ -304,82 +261,82 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.ring = frame_life + o.bmax;
   o.max_pairs = o.bmax * (frame_life + 1);
   const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)o.ring + B;
-  VSF_HIP(hipMalloc((void**)&o.sets, S * K * VSF_DESC_BYTES));
-  VSF_HIP(hipMalloc((void**)&o.set_counts, S * sizeof(int32_t)));
+  VSF_HIP(o.sets.alloc(S * K * VSF_DESC_BYTES));
+  VSF_HIP(o.set_counts.alloc(S * sizeof(int32_t)));
   VSF_HIP(hipMemset(o.set_counts, 0, S * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.residual, B * K * sizeof(float)));
-  VSF_HIP(hipMalloc((void**)&o.floats, (2 * B + 2) * sizeof(float)));
+  VSF_HIP(o.residual.alloc(B * K * sizeof(float)));
+  VSF_HIP(o.floats.alloc((2 * B + 2) * sizeof(float)));
   VSF_HIP(hipMemset(o.floats, 0, (2 * B + 2) * sizeof(float)));
   VSF_HIP(hipMemcpy(o.floats + 2 * B + 1, &thr_state, sizeof(float), hipMemcpyHostToDevice));
-  VSF_HIP(hipMalloc((void**)&o.kpf, 2 * B * K * sizeof(vsf_keypoint)));
-  VSF_HIP(hipMalloc((void**)&o.ints, 4 * B * sizeof(int32_t)));
+  VSF_HIP(o.kpf.alloc(2 * B * K * sizeof(vsf_keypoint)));
+  VSF_HIP(o.ints.alloc(4 * B * sizeof(int32_t)));
   VSF_HIP(hipMemset(o.ints, 0, 4 * B * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.ex_idx2, B * K * 2 * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.ex_dist2, B * K * 2 * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.t_idx2, P * K * 2 * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.t_dist2, P * K * 2 * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.t_matches, P * K * sizeof(vsf_dmatch)));
-  VSF_HIP(hipMalloc((void**)&o.t_nmatches, P * sizeof(int32_t)));
-  VSF_HIP(hipMalloc(&o.t_sortkeys, P * K * 8));
-  VSF_HIP(hipMalloc((void**)&o.pairs, P * K * 2 * sizeof(uint64_t)));
-  VSF_HIP(hipMalloc((void**)&o.npairs, P * sizeof(int32_t)));
-  VSF_HIP(hipMalloc((void**)&o.features, B * K * sizeof(vsf_vision_feature)));
+  VSF_HIP(o.ex_idx2.alloc(B * K * 2 * sizeof(int32_t)));
+  VSF_HIP(o.ex_dist2.alloc(B * K * 2 * sizeof(int32_t)));
+  VSF_HIP(o.t_idx2.alloc(P * K * 2 * sizeof(int32_t)));
+  VSF_HIP(o.t_dist2.alloc(P * K * 2 * sizeof(int32_t)));
+  VSF_HIP(o.t_matches.alloc(P * K * sizeof(vsf_dmatch)));
+  VSF_HIP(o.t_nmatches.alloc(P * sizeof(int32_t)));
+  VSF_HIP(o.t_sortkeys.alloc(P * K * 8));
+  VSF_HIP(o.pairs.alloc(P * K * 2 * sizeof(uint64_t)));
+  VSF_HIP(o.npairs.alloc(P * sizeof(int32_t)));
+  VSF_HIP(o.features.alloc(B * K * sizeof(vsf_vision_feature)));
   o.out_cap = vsf_observe_capacity(ctx, frame_life);
   o.out_stride = (o.out_cap + 255) & ~(size_t)255;
-  VSF_HIP(hipHostMalloc((void**)&o.h_img, (size_t)o.depth * 2 * ctx->st_img_stride, hipHostMallocMapped));
-  VSF_HIP(hipHostMalloc((void**)&o.h_out, (size_t)o.depth * o.out_stride, hipHostMallocMapped));
+  VSF_HIP(o.h_img.alloc((size_t)o.depth * 2 * ctx->st_img_stride, hipHostMallocMapped));
+  VSF_HIP(o.h_out.alloc((size_t)o.depth * o.out_stride, hipHostMallocMapped));
   if (o.debug) {  // vsf_observe_set_debug_images: canvases, winners, operations, the pinned debug ring and colour ring
     const size_t wh = (size_t)ctx->p.width * ctx->p.height;
     o.dbg_stride = (9 * wh + 255) & ~(size_t)255;  // stereo 2w x h x 3 | match w x h x 3
     o.col_ring = (int64_t)(o.depth + 1) * (int64_t)K;
-    VSF_HIP(hipMalloc((void**)&o.dbg_canvas, B * o.dbg_stride));
-    VSF_HIP(hipMalloc((void**)&o.dbg_win, B * 3 * wh * sizeof(uint64_t)));
+    VSF_HIP(o.dbg_canvas.alloc(B * o.dbg_stride));
+    VSF_HIP(o.dbg_win.alloc(B * 3 * wh * sizeof(uint64_t)));
     VSF_HIP(hipMemset(o.dbg_win, 0, B * 3 * wh * sizeof(uint64_t)));
-    VSF_HIP(hipMalloc((void**)&o.dbg_ops, B * 5 * K * sizeof(vsf_draw_op)));
-    VSF_HIP(hipMalloc(&o.dbg_table, 2 * B * 128));
-    VSF_HIP(hipMalloc((void**)&o.dbg_prev_kp, K * sizeof(vsf_keypoint)));
-    VSF_HIP(hipMalloc((void**)&o.dbg_ints, 16));
+    VSF_HIP(o.dbg_ops.alloc(B * 5 * K * sizeof(vsf_draw_op)));
+    VSF_HIP(o.dbg_table.alloc(2 * B * 128));
+    VSF_HIP(o.dbg_prev_kp.alloc(K * sizeof(vsf_keypoint)));
+    VSF_HIP(o.dbg_ints.alloc(16));
     VSF_HIP(hipMemset(o.dbg_ints, 0, 16));
     if (form.kind) {
       const vsf_status st = alloc_debug_files(ctx);
       if (st != VSF_OK) return st;
     } else {
-      VSF_HIP(hipHostMalloc((void**)&o.h_dbg, (size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
+      VSF_HIP(o.h_dbg.alloc((size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
     }
-    VSF_HIP(hipHostMalloc((void**)&o.h_col, (size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
+    VSF_HIP(o.h_col.alloc((size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
   }
   for (vsf_ctx::ObserveBatch& b : o.batch) {
-    VSF_HIP(hipMalloc((void**)&b.d_img, 2 * B * ctx->st_img_stride));
-    VSF_HIP(hipMalloc((void**)&b.kp_raw, 2 * B * K * sizeof(vsf_keypoint)));
-    VSF_HIP(hipMalloc((void**)&b.desc_raw, 2 * B * K * VSF_DESC_BYTES));
-    VSF_HIP(hipMalloc((void**)&b.counts_raw, 2 * B * sizeof(int32_t)));
-    VSF_HIP(hipMalloc((void**)&b.matches, B * K * sizeof(vsf_dmatch)));
-    VSF_HIP(hipMalloc((void**)&b.nmatches, B * sizeof(int32_t)));
-    VSF_HIP(hipMalloc((void**)&b.status, 2 * B * sizeof(int32_t)));
+    VSF_HIP(b.d_img.alloc(2 * B * ctx->st_img_stride));
+    VSF_HIP(b.kp_raw.alloc(2 * B * K * sizeof(vsf_keypoint)));
+    VSF_HIP(b.desc_raw.alloc(2 * B * K * VSF_DESC_BYTES));
+    VSF_HIP(b.counts_raw.alloc(2 * B * sizeof(int32_t)));
+    VSF_HIP(b.matches.alloc(B * K * sizeof(vsf_dmatch)));
+    VSF_HIP(b.nmatches.alloc(B * sizeof(int32_t)));
+    VSF_HIP(b.status.alloc(2 * B * sizeof(int32_t)));
     VSF_HIP(hipMemset(b.status, 0, 2 * B * sizeof(int32_t)));
-    VSF_HIP(hipHostMalloc((void**)&b.h_meta, meta_bytes(o.max_pairs, o.bmax), hipHostMallocMapped));
+    VSF_HIP(b.h_meta.alloc(meta_bytes(o.max_pairs, o.bmax), hipHostMallocMapped));
     std::memset(b.h_meta, 0, meta_bytes(o.max_pairs, o.bmax));
-    VSF_HIP(hipEventCreateWithFlags(&b.ev_uploaded, hipEventDisableTiming));
-    VSF_HIP(hipEventCreateWithFlags(&b.ev_extracted, hipEventDisableTiming));
-    VSF_HIP(hipEventCreateWithFlags(&b.ev_done, hipEventDisableTiming));
+    VSF_HIP(b.ev_uploaded.alloc(hipEventDisableTiming));
+    VSF_HIP(b.ev_extracted.alloc(hipEventDisableTiming));
+    VSF_HIP(b.ev_done.alloc(hipEventDisableTiming));
   }
   o.frames.assign((size_t)o.depth, vsf_ctx::ObserveFrame());
   // The tail rides a high-priority stream: it is short, latency-bound and what the host waits for; streams of different
   // priorities never share a hardware queue, so it runs beside the next batch's extraction instead of taking turns with it.
   int prio_lo = 0, prio_hi = 0;
   VSF_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-  VSF_HIP(hipStreamCreateWithPriority(&o.tail_stream, hipStreamNonBlocking, prio_hi));
+  VSF_HIP(o.tail_stream.alloc(hipStreamNonBlocking, prio_hi));
   // ... and the uploads the LOWEST: with the default priority the copy stream may land on the hardware queue of the
   // context's stream (HIP hands its few queues out round-robin) and the next batch's upload then waits for this batch's
   // extraction instead of running beside it -- which it did or did not from one context to the next (17 k or 27 k frames/s)
-  VSF_HIP(hipStreamCreateWithPriority(&o.copy_stream, hipStreamNonBlocking, prio_lo));
+  VSF_HIP(o.copy_stream.alloc(hipStreamNonBlocking, prio_lo));
   VSF_HIP(hipDeviceSynchronize());
-  o.launcher = new (std::nothrow) vsf_ctx::ObserveLauncher();
+  o.launcher.reset(new (std::nothrow) vsf_ctx::ObserveLauncher());
   if (!o.launcher) return VSF_ERR_INVALID_ARG;
   o.ready = true;
   // the two host threads of a deep queue: VSF_OPT_OBSERVE_THREAD (without it the caller launches everything) and
   // VSF_OPT_OBSERVE_COPY_THREAD (without it the caller stages both images)
-  if (o.depth >= 4 && ctx->tuning.observe_copy_thread) o.copy_helper = new (std::nothrow) vsf_ctx::ObserveCopyHelper();
+  if (o.depth >= 4 && ctx->tuning.observe_copy_thread) o.copy_helper.reset(new (std::nothrow) vsf_ctx::ObserveCopyHelper());
   if (o.depth >= 4 && ctx->tuning.observe_thread) {
     o.launcher->has_thread = true;
     o.launcher->th = std::thread(launcher_thread, ctx);
@@ -401,11 +358,11 @@ vsf_status ensure_compressed(vsf_ctx* ctx, bool bayer) {
     const size_t cap = compressed_cap(ctx);
     const size_t ring = vsf_observe_compressed_ring_bytes(o.depth, cap);
     if (ring == 0) return VSF_ERR_INVALID_ARG;
-    VSF_HIP(hipHostMalloc((void**)&o.h_cmp, ring, hipHostMallocDefault));
+    VSF_HIP(o.h_cmp.alloc(ring, hipHostMallocDefault));
     o.cmp_cap = cap;
     o.cmp_slot = vsf_observe_compressed_slot_bytes(cap);
   }
-  if (bayer && !o.d_bayer) VSF_HIP(hipMalloc((void**)&o.d_bayer, 2 * (size_t)o.bmax * ctx->st_img_stride));
+  if (bayer && !o.d_bayer) VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
   return VSF_OK;
 }
 
@@ -1018,8 +975,7 @@ vsf_status vsf_observe_set_compressed_cap(vsf_ctx* ctx, size_t cap_per_image) {
   vsf_ctx::Observe& o = ctx->ob;
   if (o.ready && o.next_collect != o.next_ticket) return VSF_ERR_INVALID_ARG;  // frames in the queue
   if (o.h_cmp) {  // (every frame has been collected: no upload reads the ring; a pinned buffer is retired, not freed)
-    ctx->retired_host.push_back(o.h_cmp);
-    o.h_cmp = nullptr;
+    ctx->retired_host.emplace_back(o.h_cmp.release());
     o.cmp_cap = o.cmp_slot = 0;
   }
   ctx->ob_cmp_cap = cap_per_image;
