@@ -387,7 +387,8 @@ vsf_status vsf_pack_outputs_dev(vsf_ctx* ctx, const vsf_vision_feature* d_featur
  * sends what waits in the queue, so nothing ever runs beside it).
  * Tickets are collected in the order they were issued; a submit beyond `depth` uncollected frames returns
  * VSF_ERR_INVALID_ARG.  Consecutive frames with different calibrations or best_percent never share a batch; frame_life
- * changes only while the queue is empty (the window starts over).
+ * changes only while the queue is empty (the window starts over).  These calls feed stream 0 of the queue's streams
+ * (vsf_observe_set_streams, below): with the default of one stream that is the whole queue.
  *
  * Result (little endian, *out_bytes bytes, at most vsf_observe_capacity()):
  *   u32 magic 'VSFO', n_pairs, nfeat, total_bytes, n_left, n_right (raw keypoints), n_stereo_matches, n_points,
@@ -454,12 +455,47 @@ vsf_status vsf_compressed_image_size(const uint8_t* file, size_t nbytes, int* wi
  * waits in staging or is on the GPU.  What a caller that books results as they come asks before each collect. */
 vsf_status vsf_observe_poll(vsf_ctx* ctx, int64_t ticket, int* ready);
 vsf_status vsf_observe_reset(vsf_ctx* ctx);
+/* STREAMS: several independent sequences of frames -- several cameras or robots on one GPU, several bags replayed at once --
+ * through ONE context and ONE queue.  Every stream has its own RemoveAmbigStereo threshold (10000 at first), its own temporal
+ * window of frame_life kept frames and its own calibration and best_percent; frames of different streams wait in the same
+ * queue and leave for the GPU in the same batch, so n cameras that have four frames waiting each fill a batch of 4 n instead
+ * of paying n batches' ~45 launches.  Each stream's results are, byte for byte, those of a context of its own fed that
+ * stream's frames alone (tests/test_gpu_observe_streams.py).
+ *   n_streams: 1 .. VSF_OBSERVE_MAX_STREAMS, 1 by default.  Before the first submit or while the queue is empty, like
+ * vsf_observe_configure; another value rebuilds the queue (every window and threshold starts over).
+ *   What one more stream costs in HBM: its ring of filtered descriptor sets and their counts,
+ *       (frame_life + bmax) x (32 x max_keypoints + 4) + 4 bytes,   bmax = min(depth, max_images / 2) frames per batch
+ * (2.4 MB at 2000 keypoints, frame_life 5, 32 frames per batch) -- against the ~25 MB per frame of extraction buffers and the
+ * tail's scratch that a context of its own would own again.  The pinned staging and result rings are the queue's: `depth`
+ * counts the uncollected frames of all streams together.
+ *   Tickets are global and are collected in the order they were issued, whatever the streams.  frame_life is one value per
+ * context.  The cut rule is per stream: a frame whose calibration or best_percent differs from the waiting frame of ITS OWN
+ * stream in front of it starts a new batch; frames of different streams may differ in both and share one.  Frames with
+ * different `bayer` never share a batch.
+ *   A stream outside [0, n_streams): VSF_ERR_INVALID_ARG, no ticket, the queue as it was.
+ *   Debug images are single-stream: vsf_observe_set_debug_images / _jpeg / _png with more than one stream return
+ * VSF_ERR_UNSUPPORTED, and so does vsf_observe_set_streams(> 1) while debug images are on (the match image needs each
+ * stream's previous frame, the stereo lines rand()'s colour sequence per stream). */
+#define VSF_OBSERVE_MAX_STREAMS 64
+vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams);
+vsf_status vsf_observe_submit_stream(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h,
+                                     size_t stride, const vsf_calibration* calib, float best_percent, int frame_life,
+                                     int64_t* ticket);
+vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes,
+                                                const uint8_t* right, size_t right_bytes, int bayer,
+                                                const vsf_calibration* calib, float best_percent, int frame_life,
+                                                int64_t* ticket);
+/* Forgets ONE stream's window and puts its threshold back to 10000: its next frame is the first frame of a fresh context.
+ * Legal while no frame of that stream is submitted and not collected (else VSF_ERR_INVALID_ARG); the other streams, frames
+ * in flight included, are untouched.  vsf_observe_reset stays "all streams" (and drops what waits). */
+vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream);
 /* What the queue did since it was built: out[0..n) of { frames launched, batches, largest batch, batches of one frame that
  * ran on one stream, launches forced by a collect or a change of parameters, launches that had to wait for a batch slot,
  * depth, frames per batch at most, then the host's nanoseconds inside staging copies, batch launches, waits for results,
  * compressed frames launched, copy commands + kernel launches the compressed path issued, bytes of every buffer the
  * compressed path owns (file ring, blobs, decoder scratch, mosaics) -- the last three are 0 for a queue that has only seen
- * raw frames }. */
+ * raw frames; [14] launches of the compressed debug images; [15] streams (vsf_observe_set_streams), [16] batches that
+ * carried frames of more than one stream }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,

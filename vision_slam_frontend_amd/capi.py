@@ -44,11 +44,16 @@ EXPORTS = [
     "vsf_compressed_image_size", "vsf_observe_probe_compressed",
     "vsf_observe_set_debug_jpeg", "vsf_observe_debug_jpeg_view", "vsf_jpeg_encode_capacity", "vsf_jpeg_encode_batch_dev", "vsf_jpeg_encode", "vsf_debug_jpeg_encode_header",
     "vsf_png_encode_capacity", "vsf_png_encode_batch_dev", "vsf_png_encode", "vsf_debug_png_encode_header", "vsf_debug_png_encode_cpu", "vsf_observe_set_debug_png", "vsf_observe_debug_png_view",
+    "vsf_observe_set_streams", "vsf_observe_submit_stream", "vsf_observe_submit_compressed_stream", "vsf_observe_reset_stream",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
  OPT_PIPE_AFTER_FAST, OPT_PIPE_PRIORITY, OPT_OBSERVE_THREAD, OPT_PYRAMID_TAIL_MIN, OPT_OBSERVE_COPY_THREAD) = range(11)
 STAGE_COUNT = 8
+# vsf_observe_stats' values, in order (include/vsf.h)
+OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
+                 "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands", "streams",
+                 "multi_stream_batches")
 
 
 class VsfParams(C.Structure):
@@ -230,6 +235,12 @@ def lib() -> C.CDLL:
         L.vsf_observe_stereo.argtypes = [vp, vp, vp, i32, i32, sz, C.POINTER(VsfCalibration), C.c_float, i32, vp, sz,
                                          C.POINTER(sz)]
         L.vsf_observe_reset.argtypes = [vp]
+        L.vsf_observe_set_streams.argtypes = [vp, i32]
+        L.vsf_observe_reset_stream.argtypes = [vp, i32]
+        L.vsf_observe_submit_stream.argtypes = [vp, i32, vp, vp, i32, i32, sz, C.POINTER(VsfCalibration), C.c_float, i32,
+                                                C.POINTER(C.c_int64)]
+        L.vsf_observe_submit_compressed_stream.argtypes = [vp, i32, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float,
+                                                           i32, C.POINTER(C.c_int64)]
         L.vsf_observe_submit_compressed.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32,
                                                     C.POINTER(C.c_int64)]
         L.vsf_observe_stereo_compressed.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32, vp,
@@ -549,6 +560,44 @@ class Context:
                     "vsf_observe_submit")
         return int(t.value)
 
+    def observe_set_streams(self, n_streams: int, allow_status=()) -> int:
+        """The queue takes frames of `n_streams` independent sequences (vsf_observe_set_streams); returns the status."""
+        st = lib().vsf_observe_set_streams(self._h, n_streams)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_set_streams", lib().vsf_last_hip_error(self._h))
+        return st
+
+    def observe_reset_stream(self, stream: int):
+        """Forgets one stream's window and threshold (vsf_observe_reset_stream)."""
+        self._check(lib().vsf_observe_reset_stream(self._h, stream), "vsf_observe_reset_stream")
+
+    def observe_submit_stream(self, stream: int, left: np.ndarray, right: np.ndarray, calib: VsfCalibration,
+                              best_percent: float = 0.3, frame_life: int = 10, allow_status=()):
+        """vsf_observe_submit_stream: queues one ObserveImage of sequence `stream`.  Returns the ticket -- or, with
+        `allow_status`, (status, ticket): a refused submit has ticket -1."""
+        left, right = _u8(left), _u8(right)
+        assert left.shape == right.shape and left.strides == right.strides
+        t = C.c_int64(-1)
+        st = lib().vsf_observe_submit_stream(self._h, stream, _p(left), _p(right), left.shape[1], left.shape[0],
+                                             left.strides[0], C.byref(calib), float(np.float32(best_percent)), frame_life,
+                                             C.byref(t))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_submit_stream", lib().vsf_last_hip_error(self._h))
+        return (st, int(t.value)) if allow_status else int(t.value)
+
+    def observe_submit_compressed_stream(self, stream: int, left: bytes, right: bytes, calib: VsfCalibration,
+                                         bayer: bool = False, best_percent: float = 0.3, frame_life: int = 10,
+                                         allow_status=()):
+        """vsf_observe_submit_compressed_stream; returns (status, ticket) like observe_submit_compressed."""
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        t = C.c_int64(-1)
+        st = lib().vsf_observe_submit_compressed_stream(self._h, stream, _p(lb), len(lb), _p(rb), len(rb), int(bool(bayer)),
+                                                        C.byref(calib), float(np.float32(best_percent)), frame_life,
+                                                        C.byref(t))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_submit_compressed_stream", lib().vsf_last_hip_error(self._h))
+        return st, int(t.value)
+
     def observe_collect(self, ticket: int, frame_life: int = 10) -> dict:
         """Waits for the frame of `ticket` (vsf_observe_collect) and returns its decoded result."""
         cap = int(lib().vsf_observe_capacity(self._h, frame_life))
@@ -599,11 +648,9 @@ class Context:
 
     def observe_stats(self) -> dict:
         """vsf_observe_stats by name."""
-        v = np.zeros(15, np.int64)
-        self._check(lib().vsf_observe_stats(self._h, _p(v), 15), "vsf_observe_stats")
-        names = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
-                 "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands")
-        return {k: int(x) for k, x in zip(names, v)}
+        v = np.zeros(len(OBSERVE_STATS), np.int64)
+        self._check(lib().vsf_observe_stats(self._h, _p(v), len(v)), "vsf_observe_stats")
+        return {k: int(x) for k, x in zip(OBSERVE_STATS, v)}
 
     def debug_jpeg_serial(self, on: bool):
         """Test hook: every JPEG file through the one-wave-per-image decoder (vsf_debug_jpeg_serial)."""

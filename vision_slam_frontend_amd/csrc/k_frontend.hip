@@ -34,11 +34,16 @@ __device__ __forceinline__ float dot3(int order, float a0, float b0, float a1, f
   return order ? (p0 + p1) + p2 : p0 + (p1 + p2);
 }
 
+// TABLE (the ObserveImage queue with frames of several streams in one batch): frame f's matrix is that of calibration
+// par[f].calib in the batch's table -- f is the workgroup's, so the loads are scalar.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void stereo_residual_kernel(const vsf_keypoint* __restrict__ kp,
                                                               const vsf_dmatch* __restrict__ matches,
                                                               const int32_t* __restrict__ nmatches, int max_rows,
                                                               const float* __restrict__ F,  // 9 floats, row major, or
                                                               VsfF9 Fv,  // NULL: the matrix by value (batched *_dev calls)
+                                                              const VsfObserveParam* __restrict__ par,     // TABLE: [frames]
+                                                              const vsf_calibration* __restrict__ calibs,  // TABLE
                                                               int order,  // vsf_params::residual_order
                                                               float* __restrict__ residual,  // [frames][max_rows]
                                                               float* __restrict__ mean,      // [frames], NaN if empty
@@ -54,6 +59,7 @@ __global__ __launch_bounds__(256) void stereo_residual_kernel(const vsf_keypoint
   float* res = residual + (size_t)f * max_rows;
   const bool in_lds = lds_rows >= max_rows;
   float Fm[9];
+  if (TABLE) F = calibs[par[f].calib].fundamental;
 #pragma unroll
   for (int i = 0; i < 9; i++) Fm[i] = F ? F[i] : Fv.v[i];
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -644,8 +650,17 @@ void vsf_launch_stereo_residuals(const vsf_keypoint* d_kp, const vsf_dmatch* d_m
   VsfF9 fv = {};
   if (h_F)  // the matrix rides in the kernel arguments: no copy command, no device buffer shared between calls
     for (int i = 0; i < 9; i++) fv.v[i] = h_F[i];
-  hipLaunchKernelGGL(stereo_residual_kernel, dim3(n_frames), dim3(256), (size_t)lds_rows * sizeof(float), s, d_kp,
-                     d_matches, d_nmatches, max_rows, h_F ? nullptr : d_F, fv, order, d_residual, d_mean, lds_rows);
+  hipLaunchKernelGGL(stereo_residual_kernel<false>, dim3(n_frames), dim3(256), (size_t)lds_rows * sizeof(float), s, d_kp,
+                     d_matches, d_nmatches, max_rows, h_F ? nullptr : d_F, fv, nullptr, nullptr, order, d_residual, d_mean,
+                     lds_rows);
+}
+
+void vsf_launch_stereo_residuals_table(const vsf_keypoint* d_kp, const vsf_dmatch* d_matches, const int32_t* d_nmatches,
+                                       int n_frames, int max_rows, const VsfObserveParam* d_par, const vsf_calibration* d_calibs,
+                                       int order, float* d_residual, float* d_mean, hipStream_t s) {
+  const int lds_rows = max_rows <= 16000 ? (max_rows + 3) & ~3 : 0;
+  hipLaunchKernelGGL(stereo_residual_kernel<true>, dim3(n_frames), dim3(256), (size_t)lds_rows * sizeof(float), s, d_kp,
+                     d_matches, d_nmatches, max_rows, nullptr, VsfF9{}, d_par, d_calibs, order, d_residual, d_mean, lds_rows);
 }
 
 void vsf_launch_stereo_filter_only(const vsf_keypoint* d_kp, const uint8_t* d_desc, const vsf_dmatch* d_matches,

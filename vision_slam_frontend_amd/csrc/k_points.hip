@@ -32,6 +32,18 @@ struct PointsArgs {
   int rows;         // 6 or 4
 };
 
+__host__ __device__ __forceinline__ PointsArgs points_args(const vsf_calibration& c) {
+  PointsArgs a;
+  for (int i = 0; i < 12; i++) {
+    a.P[0][i] = c.projection_left[i];
+    a.P[1][i] = c.projection_right[i];
+  }
+  for (int i = 0; i < 9; i++) a.K[i] = c.camera_matrix_left[i];
+  for (int i = 0; i < 5; i++) a.dist[i] = c.distortion_left[i];
+  a.rows = c.triangulate_rows == 4 ? 4 : 6;
+  return a;
+}
+
 __device__ __forceinline__ double lapack_hypot(double a, double b) {  // core/src/lapack.cpp hypot<_Tp>
   a = fabs(a);
   b = fabs(b);
@@ -122,11 +134,16 @@ __device__ __forceinline__ void smallest_right_singular_vector(double (&At)[4][6
   for (int k = 0; k < 4; k++) X[k] = best == 0 ? Vt[0][k] : best == 1 ? Vt[1][k] : best == 2 ? Vt[2][k] : Vt[3][k];
 }
 
+// TABLE (the ObserveImage queue with frames of several streams in one batch): frame f's calibration is entry par[f].calib of
+// the batch's table instead of the one in the kernel arguments -- f is the workgroup's, so the loads are scalar.
+template <bool TABLE>
 __global__ __launch_bounds__(64) void vision_features_kernel(const vsf_keypoint* __restrict__ kp,  // [2*frames][max_rows]
                                                               const int32_t* __restrict__ counts,   // [2*frames]
                                                               const uint64_t* __restrict__ pairs,   // [frames][max_rows][2]
                                                               const int32_t* __restrict__ npairs,   // [frames]
-                                                              int max_rows, PointsArgs a,
+                                                              int max_rows, PointsArgs a_by_value,
+                                                              const VsfObserveParam* __restrict__ par,     // TABLE: [frames]
+                                                              const vsf_calibration* __restrict__ calibs,  // TABLE
                                                               vsf_vision_feature* __restrict__ out,  // [frames][max_rows]
                                                               int32_t* __restrict__ nfeatures,       // [frames]
                                                               int32_t* __restrict__ npoints) {       // [frames] or null
@@ -139,6 +156,9 @@ __global__ __launch_bounds__(64) void vision_features_kernel(const vsf_keypoint*
     if (npoints) npoints[f] = m;
   }
   if (i >= n) return;
+  PointsArgs a_of_frame;
+  if (TABLE) a_of_frame = points_args(calibs[par[f].calib]);
+  const PointsArgs& a = TABLE ? a_of_frame : a_by_value;
   const vsf_keypoint* left = kp + (size_t)(2 * f) * max_rows;
   const vsf_keypoint* right = kp + (size_t)(2 * f + 1) * max_rows;
   vsf_vision_feature o;
@@ -288,6 +308,24 @@ __global__ void stereo_thresholds_kernel(const float* __restrict__ mean, int n, 
   }
 }
 
+// ---- the same for a batch that holds frames of several streams (the ObserveImage queue, vsf_observe_set_streams): every
+// stream's frames are taken in batch order against state[stream]; the streams side by side.  The lane of a stream's FIRST
+// frame in the batch hands its state over (it alone touches it): thr = state[stream], state[stream] = mean[tail] + 2 with
+// `tail` the stream's last frame in the batch; every other frame takes mean[prev] + 2 of the frame of its stream in front of
+// it -- ONE mean each, NaN included, so quirk Q3 holds per stream. ----
+__global__ void stereo_thresholds_streams_kernel(const float* __restrict__ mean, int n, const VsfObserveParam* __restrict__ par,
+                                                 float* __restrict__ state, float* __restrict__ thr) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const VsfObserveParam p = par[k];
+  if (p.prev < 0) {
+    thr[k] = state[p.stream];
+    state[p.stream] = mean[p.tail] + 2.0f;
+  } else {
+    thr[k] = mean[p.prev] + 2.0f;
+  }
+}
+
 // ---- the (query, train) set indices of Calculate3DPoints' right -> left matching: q[f] = 2f + 1, t[f] = 2f ----
 __global__ void fill_stereo_sets_kernel(int32_t* __restrict__ sets, int n) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -306,16 +344,16 @@ void vsf_launch_fill_stereo_sets(int32_t* d_sets, int n_frames, hipStream_t s) {
 void vsf_launch_vision_features(const vsf_keypoint* d_kp, const int32_t* d_counts, const uint64_t* d_pairs,
                                 const int32_t* d_npairs, int n_frames, int max_rows, const vsf_calibration& c,
                                 vsf_vision_feature* d_out, int32_t* d_nfeatures, int32_t* d_npoints, hipStream_t s) {
-  PointsArgs a;
-  for (int i = 0; i < 12; i++) {
-    a.P[0][i] = c.projection_left[i];
-    a.P[1][i] = c.projection_right[i];
-  }
-  for (int i = 0; i < 9; i++) a.K[i] = c.camera_matrix_left[i];
-  for (int i = 0; i < 5; i++) a.dist[i] = c.distortion_left[i];
-  a.rows = c.triangulate_rows == 4 ? 4 : 6;
-  hipLaunchKernelGGL(vision_features_kernel, dim3((max_rows + 63) / 64, n_frames), dim3(64), 0, s, d_kp, d_counts, d_pairs,
-                     d_npairs, max_rows, a, d_out, d_nfeatures, d_npoints);
+  hipLaunchKernelGGL(vision_features_kernel<false>, dim3((max_rows + 63) / 64, n_frames), dim3(64), 0, s, d_kp, d_counts,
+                     d_pairs, d_npairs, max_rows, points_args(c), nullptr, nullptr, d_out, d_nfeatures, d_npoints);
+}
+
+void vsf_launch_vision_features_table(const vsf_keypoint* d_kp, const int32_t* d_counts, const uint64_t* d_pairs,
+                                      const int32_t* d_npairs, int n_frames, int max_rows, const VsfObserveParam* d_par,
+                                      const vsf_calibration* d_calibs, vsf_vision_feature* d_out, int32_t* d_nfeatures,
+                                      int32_t* d_npoints, hipStream_t s) {
+  hipLaunchKernelGGL(vision_features_kernel<true>, dim3((max_rows + 63) / 64, n_frames), dim3(64), 0, s, d_kp, d_counts,
+                     d_pairs, d_npairs, max_rows, PointsArgs{}, d_par, d_calibs, d_out, d_nfeatures, d_npoints);
 }
 
 void vsf_launch_pack_outputs(const vsf_vision_feature* d_features, const int32_t* d_nfeatures, int n_frames,
@@ -330,4 +368,10 @@ void vsf_launch_pack_outputs(const vsf_vision_feature* d_features, const int32_t
 
 void vsf_launch_stereo_thresholds(const float* d_means, int n, float* d_state, float* d_thr, hipStream_t s) {
   hipLaunchKernelGGL(stereo_thresholds_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_means, n, d_state, d_thr);
+}
+
+void vsf_launch_stereo_thresholds_streams(const float* d_means, int n, const VsfObserveParam* d_par, float* d_state,
+                                          float* d_thr, hipStream_t s) {
+  hipLaunchKernelGGL(stereo_thresholds_streams_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_means, n, d_par, d_state,
+                     d_thr);
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "vsf_internal.h"
+#include "vsf_observe_plan.h"
 
 namespace vsfi {
 
@@ -124,6 +125,13 @@ struct vsf_ctx {
     uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, else VSF_FILE_JPEG / VSF_FILE_PNG: a file in h_cmp
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
     bool bayer = false;          // compressed frames: the decoded images are bayer_rggb8 mosaics
+    int stream = 0;              // vsf_observe_submit_stream: whose sequence it belongs to
+    int64_t k = 0;               // frames of its stream in front of it (since the queue was built or the stream reset)
+  };
+  struct ObserveStream {  // host side of one sequence of frames (vsf_observe_set_streams)
+    int64_t frames = 0;        // submitted since the queue was built or the stream was reset: the next frame's k
+    int64_t last_ticket = -1;  // its newest frame (the cut rule compares a frame with the one of ITS stream in front of it)
+    int uncollected = 0;       // submitted and not collected (vsf_observe_reset_stream wants 0)
   };
   struct DebugForm {  // how the queue's debug images leave: raw canvases, or files of ONE kind
     int kind = VSF_FILE_NONE;  // VSF_FILE_JPEG / VSF_FILE_PNG
@@ -169,14 +177,15 @@ struct vsf_ctx {
     } files;
     int depth = 0;      // frames that may be submitted and not collected
     int bmax = 0;       // frames per batch at most
-    int ring = 0;       // descriptor sets [0, ring): the kept left frames (frame g in set g % ring); [ring, ring + bmax): the
-                        // right frames of the batch in the tail
+    int n_streams = 1;  // vsf_observe_set_streams
+    int ring = 0;       // descriptor sets [s ring, (s + 1) ring): the kept left frames of stream s (its frame k in set
+                        // s ring + k % ring); [n_streams ring, n_streams ring + bmax): the right frames of the batch in the tail
     int max_pairs = 0;  // bmax * (frame_life + 1)
-    vsfi::DevBuf<uint8_t> sets;        // [ring + bmax][K][32]
-    vsfi::DevBuf<int32_t> set_counts;  // [ring + bmax]
+    vsfi::DevBuf<uint8_t> sets;        // [n_streams ring + bmax][K][32]
+    vsfi::DevBuf<int32_t> set_counts;  // [n_streams ring + bmax]
     // the tail's scratch exists once: tails run one after the other (they carry the threshold and the window)
     vsfi::DevBuf<float> residual;      // [bmax][K]
-    vsfi::DevBuf<float> floats;        // means [bmax] | thr [bmax + 1] | thr_state
+    vsfi::DevBuf<float> floats;        // means [bmax] | thr [bmax + 1] | thr_state [n_streams]
     vsfi::DevBuf<vsf_keypoint> kpf;    // [2 bmax][K]
     vsfi::DevBuf<int32_t> ints;        // counts_f [2 bmax] | nfeat [bmax] | npoints [bmax]
     vsfi::DevBuf<int32_t> ex_idx2, ex_dist2;  // [bmax][K][2] the extraction side's matcher scratch
@@ -200,6 +209,9 @@ struct vsf_ctx {
     size_t out_cap = 0, out_stride = 0;
     ObserveBatch batch[kObserveBatchSlots];
     std::vector<ObserveFrame> frames;  // [depth]
+    std::vector<ObserveStream> streams;  // [n_streams]
+    std::vector<vsfi::ObservePlanIn> plan_in;  // launch_batch's: the batch as vsf_observe_plan.h takes it ...
+    vsfi::ObservePlan plan;                    // ... and plans it (kept from batch to batch: no allocation per batch)
     int64_t next_ticket = 0;   // tickets issued
     int64_t next_launch = 0;   // first frame still waiting in staging
     int64_t next_collect = 0;  // oldest frame not collected
@@ -209,9 +221,11 @@ struct vsf_ctx {
     int last_batch = -1;       // slot of the batch launched last
     int64_t stat_frames = 0, stat_max_batch = 0, stat_solo = 0, stat_forced = 0, stat_slot_waits = 0;  // vsf_observe_stats
     int64_t stat_copy_ns = 0, stat_launch_ns = 0, stat_wait_ns = 0;  // host time in staging copies, launches, waits
+    int64_t stat_multi = 0;  // batches that carried frames of more than one stream
   } ob;
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
+  int ob_streams = 1;  // vsf_observe_set_streams
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)

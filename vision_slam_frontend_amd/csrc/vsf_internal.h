@@ -245,6 +245,22 @@ struct VsfObserveFrame {  // per frame of a batch; pinned host memory the kernel
   int32_t tp0;       // index of its first temporal pair in the batch's pair list (its right -> left pair is pair f)
   int32_t out_slot;  // result slot: out + out_slot * out_stride
 };
+// ... and its parameters where a batch holds frames of several streams (vsf_observe_set_streams), pinned as well
+struct VsfObserveParam {
+  int32_t stream;       // whose threshold state and window the frame belongs to
+  int32_t calib;        // index into the batch's table of distinct calibrations
+  float best_percent;   // of its temporal pairs (the pair list carries it per pair)
+  int32_t prev, tail;   // the threshold chain inside the batch (vsf_observe_plan.h)
+};
+void vsf_launch_stereo_residuals_table(const vsf_keypoint* d_kp, const vsf_dmatch* d_matches, const int32_t* d_nmatches,
+                                       int n_frames, int max_rows, const VsfObserveParam* d_par, const vsf_calibration* d_calibs,
+                                       int order, float* d_residual, float* d_mean, hipStream_t s);
+void vsf_launch_stereo_thresholds_streams(const float* d_means, int n, const VsfObserveParam* d_par, float* d_state,
+                                          float* d_thr, hipStream_t s);
+void vsf_launch_vision_features_table(const vsf_keypoint* d_kp, const int32_t* d_counts, const uint64_t* d_pairs,
+                                      const int32_t* d_npairs, int n_frames, int max_rows, const VsfObserveParam* d_par,
+                                      const vsf_calibration* d_calibs, vsf_vision_feature* d_out, int32_t* d_nfeatures,
+                                      int32_t* d_npoints, hipStream_t s);
 struct VsfObserveArgs {
   int n_frames, max_rows;
   const int32_t* counts_raw;          // [2n] keypoints of the left / right images

@@ -17,6 +17,11 @@
 // The kept frames' filtered descriptors live in a ring of descriptor sets in HBM (frame g in set g % ring); the pair list
 // of a batch addresses them by set index, so a frame matches against frames of earlier batches and of its own alike.
 // Results are those of one frame at a time, bit for bit (tests/test_gpu_observe.py).
+// STREAMS (vsf_observe_set_streams): the queue takes frames of several independent sequences -- several cameras on one GPU --
+// and frames of different streams leave in the same batch.  Everything that crosses frames exists per stream: a threshold
+// (thr_state[stream]), a ring of descriptor sets (frame k of stream s in set s ring + k % ring), the calibration (the batch's
+// pinned block carries a table of its distinct calibrations and an index per frame).  vsf_observe_plan.cc does the arithmetic;
+// each stream's results are those of a context of its own, byte for byte (tests/test_gpu_observe_streams.py).
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -137,7 +142,9 @@ struct vsf_ctx::ObserveLauncher {
 struct vsf_ctx::ObserveBatchMeta {
   int32_t n_frames, n_pairs;
   // followed by (offsets in int32 words from the start of the block, fixed by the queue's sizes):
-  //   q_set[max_pairs] | t_set[max_pairs] | best_percent[max_pairs] (float) | out_sets[2 bmax] | frames[bmax]
+  //   q_set[max_pairs] | t_set[max_pairs] | best_percent[max_pairs] (float) | out_sets[2 bmax] | frames[bmax] |
+  //   params[bmax] | calibs[bmax] -- the last two are written and read only by a batch that holds more than one stream or
+  //   more than one calibration
 };
 
 namespace {
@@ -148,10 +155,13 @@ struct MetaView {
   float* best_percent;
   int32_t* out_sets;
   VsfObserveFrame* frames;
+  VsfObserveParam* params;
+  vsf_calibration* calibs;
 };
 
 size_t meta_bytes(int max_pairs, int bmax) {
-  return 16 + (size_t)max_pairs * 12 + (size_t)bmax * 8 + (size_t)bmax * sizeof(VsfObserveFrame);
+  return 16 + (size_t)max_pairs * 12 + (size_t)bmax * 8 +
+         (size_t)bmax * (sizeof(VsfObserveFrame) + sizeof(VsfObserveParam) + sizeof(vsf_calibration));
 }
 
 MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
@@ -162,14 +172,14 @@ MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
   v.best_percent = reinterpret_cast<float*>(v.t_set + max_pairs);
   v.out_sets = reinterpret_cast<int32_t*>(v.best_percent + max_pairs);
   v.frames = reinterpret_cast<VsfObserveFrame*>(v.out_sets + 2 * bmax);
+  v.params = reinterpret_cast<VsfObserveParam*>(v.frames + bmax);
+  v.calibs = reinterpret_cast<vsf_calibration*>(v.params + bmax);
   return v;
 }
 
 inline int64_t now_ns() {
   return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-bool same_calibration(const vsf_calibration& a, const vsf_calibration& b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
 
 }  // namespace
 
@@ -248,9 +258,14 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   const vsf_ctx::DebugForm form = ctx->ob_debug ? ctx->ob_debug_form : vsf_ctx::DebugForm();
   if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.files.form == form) return VSF_OK;
   sync_all_streams(ctx);
-  float thr_state = 10000.0f;  // cc:353
-  if (o.floats) VSF_HIP(hipMemcpy(&thr_state, o.floats + 2 * o.bmax + 1, sizeof(float), hipMemcpyDeviceToHost));
+  const int NS = ctx->ob_streams;
+  std::vector<float> thr_state((size_t)NS, 10000.0f);  // cc:353, per stream
+  if (o.floats)
+    VSF_HIP(hipMemcpy(thr_state.data(), o.floats + 2 * o.bmax + 1, (size_t)std::min(NS, o.n_streams) * sizeof(float),
+                      hipMemcpyDeviceToHost));
   free_observe(ctx);
+  o.n_streams = NS;
+  o.streams.assign((size_t)NS, vsf_ctx::ObserveStream());
   const size_t K = (size_t)ctx->p.max_keypoints;
   const int frames_cap = std::max(1, ctx->p.max_images / 2);  // the extraction's own buffers hold max_images images
   o.depth = ctx->ob_depth > 0 ? ctx->ob_depth : frames_cap;
@@ -260,14 +275,15 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   o.files.form = form;
   o.ring = frame_life + o.bmax;
   o.max_pairs = o.bmax * (frame_life + 1);
-  const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)o.ring + B;
+  // (a batch may be one stream's frames alone: every stream's ring has room for frame_life + bmax sets)
+  const size_t B = (size_t)o.bmax, P = (size_t)o.max_pairs, S = (size_t)NS * o.ring + B;
   VSF_HIP(o.sets.alloc(S * K * VSF_DESC_BYTES));
   VSF_HIP(o.set_counts.alloc(S * sizeof(int32_t)));
   VSF_HIP(hipMemset(o.set_counts, 0, S * sizeof(int32_t)));
   VSF_HIP(o.residual.alloc(B * K * sizeof(float)));
-  VSF_HIP(o.floats.alloc((2 * B + 2) * sizeof(float)));
-  VSF_HIP(hipMemset(o.floats, 0, (2 * B + 2) * sizeof(float)));
-  VSF_HIP(hipMemcpy(o.floats + 2 * B + 1, &thr_state, sizeof(float), hipMemcpyHostToDevice));
+  VSF_HIP(o.floats.alloc((2 * B + 1 + NS) * sizeof(float)));
+  VSF_HIP(hipMemset(o.floats, 0, (2 * B + 1 + NS) * sizeof(float)));
+  VSF_HIP(hipMemcpy(o.floats + 2 * B + 1, thr_state.data(), (size_t)NS * sizeof(float), hipMemcpyHostToDevice));
   VSF_HIP(o.kpf.alloc(2 * B * K * sizeof(vsf_keypoint)));
   VSF_HIP(o.ints.alloc(4 * B * sizeof(int32_t)));
   VSF_HIP(hipMemset(o.ints, 0, 4 * B * sizeof(int32_t)));
@@ -459,7 +475,20 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   }
   const size_t K = (size_t)ctx->p.max_keypoints;
   const int Kc = (int)K, life = o.frame_life;
-  const vsf_ctx::ObserveFrame& f0 = o.frames[(size_t)(t0 % o.depth)];
+  // ---- the batch's plan, before anything is enqueued: a refused batch leaves nothing on the streams ----
+  // (vsf_observe_plan.cc: sets, pairs, the calibration table; the submit has cut the list where a stream's parameters change)
+  o.plan_in.resize((size_t)n);
+  for (int f = 0; f < n; f++) {
+    const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
+    o.plan_in[(size_t)f] = {fr.stream, fr.k, &fr.calib, fr.best_percent};
+  }
+  const ObservePlan& P = o.plan;
+  if (!observe_plan(o.plan_in.data(), n, o.n_streams, o.ring, life, &o.plan) || !P.cuts.empty() || P.n_pairs > o.max_pairs)
+    return VSF_ERR_INVALID_ARG;
+  const int n_pairs = P.n_pairs, max_pairs_per_frame = P.max_pairs_per_frame;
+  // one calibration: it rides in the kernel arguments; one stream: the chain of the lone sequence (both: today's launches)
+  const bool table = P.calibs.size() > 1, chains = P.n_streams_present > 1;
+  const vsf_calibration& calib0 = P.calibs[0];
   // solo: a lone frame with nothing else on the GPU runs on ONE stream from upload to result (no event hops in its chain);
   // otherwise copy, extraction and tail have a stream each, so that the next batch's upload and extraction run beside
   // this one's tail.
@@ -495,28 +524,17 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   }
   // ---- the batch's parameters, in pinned memory the kernels read directly ----
   const MetaView M = meta_view(b.h_meta, o.max_pairs, o.bmax);
-  int n_pairs = n, max_pairs_per_frame = 1;
   for (int f = 0; f < n; f++) {
-    const int64_t g = t0 + f;  // frames since the queue was built: frame g lives in set g % ring
-    const int n_past = (int)std::min<int64_t>(g, life), left_set = (int)(g % o.ring), right_set = o.ring + f;
-    M.out_sets[2 * f] = left_set;
-    M.out_sets[2 * f + 1] = right_set;
-    M.q_set[f] = right_set;  // Calculate3DPoints: GetFeatureMatches(right, left) with best_percent_ 1.0 (cc:129-132)
-    M.t_set[f] = left_set;
-    M.best_percent[f] = 1.0f;
-    VsfObserveFrame& fm = M.frames[f];
-    fm.left_set = left_set;
-    fm.n_past = n_past;
-    fm.tp0 = n_pairs;
-    fm.out_slot = (int)(g % o.depth);
-    for (int p = 0; p < n_past; p++) {  // oldest kept frame first: the order frame_list_ is walked in (cc:424)
-      M.q_set[n_pairs] = (int)((g - n_past + p) % o.ring);
-      M.t_set[n_pairs] = left_set;
-      M.best_percent[n_pairs] = f0.best_percent;
-      n_pairs++;
-    }
-    max_pairs_per_frame = std::max(max_pairs_per_frame, n_past + 1);
+    const ObservePlanFrame& pf = P.frames[(size_t)f];
+    M.out_sets[2 * f] = pf.left_set;
+    M.out_sets[2 * f + 1] = pf.right_set;
+    M.frames[f] = {pf.left_set, pf.n_past, pf.tp0, (int32_t)((t0 + f) % o.depth)};
+    if (table || chains) M.params[f] = {pf.stream, pf.calib, pf.best_percent, pf.prev, pf.tail};
   }
+  std::memcpy(M.q_set, P.q_set.data(), (size_t)n_pairs * sizeof(int32_t));
+  std::memcpy(M.t_set, P.t_set.data(), (size_t)n_pairs * sizeof(int32_t));
+  std::memcpy(M.best_percent, P.best_percent.data(), (size_t)n_pairs * sizeof(float));
+  if (table) std::memcpy(M.calibs, P.calibs.data(), P.calibs.size() * sizeof(vsf_calibration));
   b.h_meta->n_frames = n;
   b.h_meta->n_pairs = n_pairs;
   // ---- ExtractFeatures x 2 + GetMatches of every frame (cc:411-416) ----
@@ -538,17 +556,25 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   if (o.last_batch >= 0 && o.batch[o.last_batch].done_stream != s_tail)
     VSF_HIP(hipStreamWaitEvent(s_tail, o.batch[o.last_batch].ev_done, 0));
   // ---- RemoveAmbigStereo (cc:417): residuals, the threshold chain in frame order, the rebuilt frames ----
-  float *means = o.floats, *thr = o.floats + o.bmax, *thr_state = o.floats + 2 * o.bmax + 1;
+  float *means = o.floats, *thr = o.floats + o.bmax, *thr_state = o.floats + 2 * o.bmax + 1;  // thr_state[n_streams]
   int32_t *counts_f = o.ints, *nfeat = o.ints + 2 * o.bmax, *npoints = o.ints + 3 * o.bmax;
   {
     StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 3);
     // (a lone frame: the three steps in one launch)
-    if (n != 1 || !vsf_launch_stereo_one_frame(b.kp_raw, b.desc_raw, b.matches, b.nmatches, Kc, f0.calib.fundamental,
-                                               ctx->p.residual_order, means, thr, thr_state, o.kpf, o.sets, counts_f,
+    float* thr_state0 = thr_state + P.frames[0].stream;
+    if (n != 1 || !vsf_launch_stereo_one_frame(b.kp_raw, b.desc_raw, b.matches, b.nmatches, Kc, calib0.fundamental,
+                                               ctx->p.residual_order, means, thr, thr_state0, o.kpf, o.sets, counts_f,
                                                M.out_sets, o.set_counts, s_tail)) {
-      vsf_launch_stereo_residuals(b.kp_raw, b.matches, b.nmatches, n, Kc, nullptr, f0.calib.fundamental, ctx->p.residual_order,
-                                  o.residual, means, s_tail);
-      vsf_launch_stereo_thresholds(means, n, thr_state, thr, s_tail);
+      if (table)
+        vsf_launch_stereo_residuals_table(b.kp_raw, b.matches, b.nmatches, n, Kc, M.params, M.calibs, ctx->p.residual_order,
+                                          o.residual, means, s_tail);
+      else
+        vsf_launch_stereo_residuals(b.kp_raw, b.matches, b.nmatches, n, Kc, nullptr, calib0.fundamental, ctx->p.residual_order,
+                                    o.residual, means, s_tail);
+      if (chains)
+        vsf_launch_stereo_thresholds_streams(means, n, M.params, thr_state, thr, s_tail);
+      else
+        vsf_launch_stereo_thresholds(means, n, thr_state0, thr, s_tail);
       vsf_launch_stereo_filter_only(b.kp_raw, b.desc_raw, b.matches, b.nmatches, n, Kc, o.residual, thr, o.kpf, o.sets,
                                     counts_f, s_tail, M.out_sets, o.set_counts);
     }
@@ -567,10 +593,14 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   }
   {
     StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 3);
-    vsf_launch_sort_trim(o.t_matches, o.t_nmatches, n_pairs, Kc, f0.best_percent, M.best_percent, o.t_sortkeys, o.pairs,
+    vsf_launch_sort_trim(o.t_matches, o.t_nmatches, n_pairs, Kc, P.frames[0].best_percent, M.best_percent, o.t_sortkeys, o.pairs,
                          o.npairs, s_tail, false, ctx->tuning.lds_limit);
     // ---- Calculate3DPoints + VisionFeature + UndistortFeaturePoints (cc:437-443): pairs [0, n) are the right -> left ones ----
-    vsf_launch_vision_features(o.kpf, counts_f, o.pairs, o.npairs, n, Kc, f0.calib, o.features, nfeat, npoints, s_tail);
+    if (table)
+      vsf_launch_vision_features_table(o.kpf, counts_f, o.pairs, o.npairs, n, Kc, M.params, M.calibs, o.features, nfeat, npoints,
+                                       s_tail);
+    else
+      vsf_launch_vision_features(o.kpf, counts_f, o.pairs, o.npairs, n, Kc, calib0, o.features, nfeat, npoints, s_tail);
     // ---- one compact result per frame, into its slot of the pinned result ring ----
     VsfObserveArgs a;
     a.n_frames = n;
@@ -606,6 +636,7 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   o.stat_frames += n;
   o.stat_max_batch = std::max<int64_t>(o.stat_max_batch, n);
   if (solo) o.stat_solo++;
+  if (chains) o.stat_multi++;
   o.stat_launch_ns += now_ns() - t_begin;
   VSF_STICKY();
   return VSF_OK;
@@ -699,6 +730,7 @@ void launcher_thread(vsf_ctx* ctx) {
 // vsf_observe_set_debug_jpeg / _png: quality != 0 asks for files of `kind`, 0 takes that request back.
 vsf_status set_debug_form(vsf_ctx* ctx, int kind, int quality) {
   vsf_ctx::DebugForm& f = ctx->ob_debug_form;
+  if (quality != 0 && ctx->ob_streams > 1) return VSF_ERR_UNSUPPORTED;  // debug images are single-stream (include/vsf.h)
   if (quality == (f.kind == kind ? f.quality : 0)) return VSF_OK;
   if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
   if (quality != 0 && f.kind != VSF_FILE_NONE && f.kind != kind) return VSF_ERR_INVALID_ARG;  // one form of file at a time
@@ -761,6 +793,8 @@ size_t vsf_observe_capacity(const vsf_ctx* ctx, int frame_life) {
 vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx) return VSF_ERR_INVALID_ARG;
+  // single-stream: the match image needs each stream's previous frame and rand()'s colour sequence per stream
+  if (on != 0 && ctx->ob_streams > 1) return VSF_ERR_UNSUPPORTED;
   if ((on != 0) == ctx->ob_debug) return VSF_OK;
   // only before the window holds a frame: the next submit rebuilds the queue (ensure_observe carries the threshold)
   if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
@@ -824,6 +858,39 @@ vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_
   return VSF_OK;
 }
 
+vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams) {
+  VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
+  if (!ctx || n_streams < 1 || n_streams > VSF_OBSERVE_MAX_STREAMS) return VSF_ERR_INVALID_ARG;
+  if (n_streams > 1 && ctx->ob_debug) return VSF_ERR_UNSUPPORTED;  // (vsf_observe_set_debug_images: single-stream)
+  if (ctx->ob.ready && ctx->ob.next_collect != ctx->ob.next_ticket) return VSF_ERR_INVALID_ARG;  // frames in the queue
+  if (ctx->ob.ready && n_streams != ctx->ob_streams) {  // rebuilt by the next submit: every window and threshold starts over
+    VSF_HIP(hipSetDevice(ctx->device));
+    stop_observe_threads(ctx);
+    sync_all_streams(ctx);
+    free_observe(ctx);
+  }
+  ctx->ob_streams = n_streams;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream) {
+  VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  vsf_ctx::Observe& o = ctx->ob;
+  if (!o.ready) return VSF_OK;  // (nothing to forget)
+  vsf_ctx::ObserveStream& st = o.streams[(size_t)stream];
+  if (st.uncollected != 0) return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // Every frame of the stream has been collected: no kernel reads or writes its threshold any more (other streams' tails
+  // may be running: they touch their own).  Its window is forgotten by counting its frames from 0 again -- the next frame
+  // has no predecessor, and the sets fill in the same order as a fresh queue's.
+  const float thr = 10000.0f;  // cc:353
+  VSF_HIP(hipMemcpy(o.floats + 2 * o.bmax + 1 + stream, &thr, sizeof(float), hipMemcpyHostToDevice));
+  st.frames = 0;
+  st.last_ticket = -1;
+  return VSF_OK;
+}
+
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (!ctx || !out || n < 1) return VSF_ERR_INVALID_ARG;
   const vsf_ctx::Observe& o = ctx->ob;
@@ -832,11 +899,11 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[15] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
+  const int64_t v[17] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns,
                          o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes,
-                         o.files.stat_commands};
-  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
+                         o.files.stat_commands, (int64_t)ctx->ob_streams, o.stat_multi};
+  for (int i = 0; i < n && i < 17; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -852,10 +919,11 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx) {
 
 // Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
 // have passed vsf_observe_probe_compressed as kinds[0 / 1].
-static vsf_status observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
+static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
                                  const int* kinds, const size_t* nbytes, bool bayer, const vsf_calibration* calib,
                                  float best_percent, int frame_life, int64_t* ticket) {
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
+  if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6)
     return VSF_ERR_INVALID_ARG;
   VSF_HIP(hipSetDevice(ctx->device));
@@ -871,12 +939,18 @@ static vsf_status observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_
   vsf_ctx::ObserveLauncher& L = *o.launcher;
   const int slot = (int)(o.next_ticket % o.depth);
   {
-    // a batch shares one calibration and one best_percent: a frame that brings others sends what waits first
+    // a stream's frames of one batch share one calibration and one best_percent, a batch's frames `bayer`: a frame that
+    // brings others than the waiting frame of ITS stream in front of it sends what waits first
     std::unique_lock<std::mutex> lk(L.mu);
     if (L.status != VSF_OK) return L.status;
     if (o.next_launch < o.next_ticket) {
-      const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)((o.next_ticket - 1) % o.depth)];
-      if (w0.best_percent != best_percent || !same_calibration(w0.calib, *calib) || w0.bayer != bayer) {
+      bool cut = o.frames[(size_t)((o.next_ticket - 1) % o.depth)].bayer != bayer;
+      const int64_t mine = o.streams[(size_t)stream].last_ticket;
+      if (!cut && mine >= o.next_launch) {
+        const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
+        cut = observe_plan_must_cut(w0.calib, w0.best_percent, *calib, best_percent);
+      }
+      if (cut) {
         st = caller_pump(ctx, lk, true);
         if (st != VSF_OK) return st;
       }
@@ -924,8 +998,13 @@ static vsf_status observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_
   fr.calib = *calib;
   fr.best_percent = best_percent;
   fr.batch = -1;
+  vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
+  fr.stream = stream;
+  fr.k = mine.frames++;
+  mine.uncollected++;
   std::unique_lock<std::mutex> lk(L.mu);
   const bool was_empty = o.next_launch == o.next_ticket;
+  mine.last_ticket = o.next_ticket;
   *ticket = o.next_ticket++;
   o.last_submit_ns = now_ns();
   if (L.has_thread) {
@@ -939,24 +1018,38 @@ static vsf_status observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_
 
 vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
                               const vsf_calibration* calib, float best_percent, int frame_life, int64_t* ticket) {
+  return vsf_observe_submit_stream(ctx, 0, left, right, w, h, stride, calib, best_percent, frame_life, ticket);
+}
+
+vsf_status vsf_observe_submit_stream(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h,
+                                     size_t stride, const vsf_calibration* calib, float best_percent, int frame_life,
+                                     int64_t* ticket) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
       frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
     return VSF_ERR_INVALID_ARG;
   *ticket = -1;
   if (w != ctx->p.width || h != ctx->p.height || stride < (size_t)w || ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
-  return observe_submit(ctx, left, right, w, h, stride, nullptr, nullptr, false, calib, best_percent, frame_life, ticket);
+  return observe_submit(ctx, stream, left, right, w, h, stride, nullptr, nullptr, false, calib, best_percent, frame_life, ticket);
 }
 
 vsf_status vsf_observe_submit_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
                                          size_t right_bytes, int bayer, const vsf_calibration* calib, float best_percent,
                                          int frame_life, int64_t* ticket) {
+  return vsf_observe_submit_compressed_stream(ctx, 0, left, left_bytes, right, right_bytes, bayer, calib, best_percent,
+                                              frame_life, ticket);
+}
+
+vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes,
+                                                const uint8_t* right, size_t right_bytes, int bayer,
+                                                const vsf_calibration* calib, float best_percent, int frame_life,
+                                                int64_t* ticket) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
       frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
     return VSF_ERR_INVALID_ARG;
   *ticket = -1;
-  if (ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
+  if (ctx->p.max_images < 2 || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   // the decoders' host half, file by file: a refused file books nothing and leaves the queue as it was
   const size_t cap = compressed_cap(ctx);
   const size_t nbytes[2] = {left_bytes, right_bytes};
@@ -965,8 +1058,8 @@ vsf_status vsf_observe_submit_compressed(vsf_ctx* ctx, const uint8_t* left, size
   if (st == VSF_OK)
     st = vsf_observe_probe_compressed(right, right_bytes, ctx->p.width, ctx->p.height, cap, ctx->tuning.jpeg_serial, &kinds[1]);
   if (st != VSF_OK) return st;
-  return observe_submit(ctx, left, right, ctx->p.width, ctx->p.height, 0, kinds, nbytes, bayer != 0, calib, best_percent,
-                        frame_life, ticket);
+  return observe_submit(ctx, stream, left, right, ctx->p.width, ctx->p.height, 0, kinds, nbytes, bayer != 0, calib,
+                        best_percent, frame_life, ticket);
 }
 
 vsf_status vsf_observe_set_compressed_cap(vsf_ctx* ctx, size_t cap_per_image) {
@@ -1013,6 +1106,7 @@ static vsf_status observe_wait(vsf_ctx* ctx, int64_t ticket, const uint8_t** vie
   {
     std::unique_lock<std::mutex> lk(L.mu);
     o.next_collect = ticket + 1;
+    o.streams[(size_t)o.frames[(size_t)slot].stream].uncollected--;
     if (o.debug) o.col_retired += hdr[15];  // the colours this frame's stereo image took
     if (!L.has_thread) st = caller_pump(ctx, lk, false);  // (the GPU may have room again)
   }

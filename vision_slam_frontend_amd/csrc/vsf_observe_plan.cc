@@ -1,0 +1,79 @@
+// vsf_observe_plan.cc -- see vsf_observe_plan.h.  Plain C++: no device, no context.
+#include "vsf_observe_plan.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace vsfi {
+
+bool observe_plan_must_cut(const vsf_calibration& a_calib, float a_best_percent, const vsf_calibration& b_calib,
+                           float b_best_percent) {
+  return a_best_percent != b_best_percent || std::memcmp(&a_calib, &b_calib, sizeof(vsf_calibration)) != 0;
+}
+
+bool observe_plan(const ObservePlanIn* in, int n, int n_streams, int ring, int life, ObservePlan* plan) {
+  if (!in || !plan || n < 1 || n_streams < 1 || n_streams > VSF_OBSERVE_MAX_STREAMS || life < 0 || ring < life + 1) return false;
+  if ((int64_t)n_streams * ring + n > INT32_MAX) return false;
+  int last[VSF_OBSERVE_MAX_STREAMS];  // the stream's newest frame in the list so far, -1: none
+  std::fill(last, last + n_streams, -1);
+  plan->frames.resize((size_t)n);
+  plan->q_set.clear();
+  plan->t_set.clear();
+  plan->best_percent.clear();
+  plan->calibs.clear();
+  plan->cuts.clear();
+  plan->max_pairs_per_frame = 1;
+  plan->n_streams_present = 0;
+  for (int f = 0; f < n; f++) {
+    const ObservePlanIn& w = in[f];
+    if (w.stream < 0 || w.stream >= n_streams || w.k < 0 || !w.calib) return false;
+    ObservePlanFrame& fm = plan->frames[(size_t)f];
+    fm.left_set = w.stream * ring + (int32_t)(w.k % ring);
+    fm.right_set = n_streams * ring + f;
+    plan->q_set.push_back(fm.right_set);  // Calculate3DPoints: GetFeatureMatches(right, left) with best_percent_ 1.0 (cc:129-132)
+    plan->t_set.push_back(fm.left_set);
+    plan->best_percent.push_back(1.0f);
+  }
+  int n_pairs = n;
+  for (int f = 0; f < n; f++) {
+    const ObservePlanIn& w = in[f];
+    ObservePlanFrame& fm = plan->frames[(size_t)f];
+    fm.stream = w.stream;
+    fm.best_percent = w.best_percent;
+    fm.n_past = (int32_t)std::min<int64_t>(w.k, life);
+    fm.tp0 = n_pairs;
+    for (int p = 0; p < fm.n_past; p++) {  // oldest kept frame first: the order frame_list_ is walked in (cc:424)
+      plan->q_set.push_back(w.stream * ring + (int32_t)((w.k - fm.n_past + p) % ring));
+      plan->t_set.push_back(fm.left_set);
+      plan->best_percent.push_back(w.best_percent);
+      n_pairs++;
+    }
+    plan->max_pairs_per_frame = std::max(plan->max_pairs_per_frame, fm.n_past + 1);
+    // the threshold chain: every stream's frames in batch order
+    fm.prev = last[w.stream];
+    fm.tail = -1;
+    if (fm.prev < 0) {
+      plan->n_streams_present++;
+    } else {
+      const ObservePlanIn& a = in[fm.prev];
+      if (w.k != a.k + 1) return false;  // a stream's frames wait in the order they came
+      if (observe_plan_must_cut(*a.calib, a.best_percent, *w.calib, w.best_percent)) plan->cuts.push_back(f);
+    }
+    last[w.stream] = f;
+    // the calibration table: a stream's frames keep its entry; a stream's first frame searches the few there are
+    auto same = [&](size_t i) { return std::memcmp(&plan->calibs[i], w.calib, sizeof(vsf_calibration)) == 0; };
+    size_t c = fm.prev >= 0 ? (size_t)plan->frames[(size_t)fm.prev].calib : 0;
+    if (fm.prev < 0 || !same(c))
+      for (c = 0; c < plan->calibs.size() && !same(c);) c++;
+    if (c == plan->calibs.size()) plan->calibs.push_back(*w.calib);
+    fm.calib = (int32_t)c;
+  }
+  for (int f = 0; f < n; f++) {
+    ObservePlanFrame& fm = plan->frames[(size_t)f];
+    if (fm.prev < 0) fm.tail = last[fm.stream];
+  }
+  plan->n_pairs = n_pairs;
+  return true;
+}
+
+}  // namespace vsfi

@@ -73,6 +73,28 @@ def lib() -> C.CDLL:
         L.vsfh_debug_image_compressed_format.argtypes = [vp, i32]
         L.vsfh_debug_image_compressed.argtypes = [vp, i32, vp, sz]
         L.vsfh_debug_image_compressed.restype = sz
+        L.vsfh_group_create.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32]
+        L.vsfh_group_create.restype = vp
+        L.vsfh_group_destroy.argtypes = [vp]
+        L.vsfh_group_destroy.restype = None
+        L.vsfh_group_size.argtypes = [vp]
+        L.vsfh_group_member.argtypes = [vp, i32]
+        L.vsfh_group_member.restype = vp
+        L.vsfh_group_last_status.argtypes = [vp]
+        L.vsfh_group_set_pipelined.argtypes = [vp, i32]
+        L.vsfh_group_set_pipelined.restype = None
+        L.vsfh_group_set_queue.argtypes = [vp, i32, i32, i32]
+        L.vsfh_group_set_queue.restype = None
+        L.vsfh_group_set_queue_thread.argtypes = [vp, i32]
+        L.vsfh_group_set_queue_thread.restype = None
+        L.vsfh_group_flush.argtypes = [vp]
+        L.vsfh_group_observe_odometry.argtypes = [vp, i32, vp, vp, dbl]
+        L.vsfh_group_observe_odometry.restype = None
+        L.vsfh_group_observe_image.argtypes = [vp, i32, vp, vp, i32, i32, sz, dbl]
+        L.vsfh_group_observe_compressed_image.argtypes = [vp, i32, vp, sz, vp, sz, i32, dbl]
+        L.vsfh_group_queue_stats.argtypes = [vp, vp, i32]
+        L.vsfh_group_serialize_problem.argtypes = [vp, i32, vp, sz]
+        L.vsfh_group_serialize_problem.restype = sz
         _lib = L
     return _lib
 
@@ -292,3 +314,91 @@ class Frontend:
         if n < 0:
             raise IndexError(i)
         return fid.value, kp[:n].copy(), desc[:n].copy()
+
+
+class FrontendGroup:
+    """slam::FrontendGroup: several Frontend objects on ONE GPU context and ONE ObserveImage queue (member i is stream i of
+    vsf_observe_set_streams).  `fundamentals` and `best_percents` (optional) are per member; `members[i]` is member i as a
+    Frontend (owned by the group)."""
+
+    def __init__(self, width: int, height: int, fundamentals, nfeatures: int = 10000, device: int = 0, best_percents=None,
+                 frame_life: int = 0):
+        F = np.ascontiguousarray(fundamentals, np.float32).reshape(-1, 9)
+        n = len(F)
+        bp = None if best_percents is None else np.ascontiguousarray(best_percents, np.float32).reshape(n)
+        self._h = lib().vsfh_group_create(n, nfeatures, width, height, device, _p(F), _p(bp), frame_life)
+        st = lib().vsfh_group_last_status(self._h)
+        if st != capi.VSF_OK:
+            self.close()
+            raise capi.VsfError(st, "FrontendGroup")
+        self.members = []
+        for i in range(n):
+            m = Frontend.__new__(Frontend)
+            m._h = lib().vsfh_group_member(self._h, i)
+            m.cap = nfeatures + 256
+            m.close = lambda: None  # (the group owns its members)
+            self.members.append(m)
+
+    def __len__(self):
+        return len(self.members)
+
+    def set_pipelined(self, on: bool):
+        lib().vsfh_group_set_pipelined(self._h, int(on))
+
+    def set_queue(self, depth: int = 0, batch_frames: int = 0, min_batch: int = 0):
+        lib().vsfh_group_set_queue(self._h, int(depth), int(batch_frames), int(min_batch))
+
+    def set_queue_thread(self, on: bool):
+        lib().vsfh_group_set_queue_thread(self._h, int(on))
+
+    def _check(self, i: int, where: str, allow_status=()):
+        st = lib().vsfh_last_status(self.members[i]._h)
+        if st != capi.VSF_OK and st not in allow_status:
+            raise capi.VsfError(st, where)
+
+    def observe_odometry(self, i: int, translation, rotation_wxyz, timestamp: float):
+        t = np.ascontiguousarray(translation, np.float32)
+        q = np.ascontiguousarray(rotation_wxyz, np.float32)
+        lib().vsfh_group_observe_odometry(self._h, i, _p(t), _p(q), timestamp)
+
+    def observe_image(self, i: int, left: np.ndarray, right: np.ndarray, time: float = 0.0) -> bool:
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        assert left.shape == right.shape and left.ndim == 2
+        added = bool(lib().vsfh_group_observe_image(self._h, i, _p(left), _p(right), left.shape[1], left.shape[0],
+                                                    left.strides[0], time))
+        self._check(i, "FrontendGroup::ObserveImage")
+        return added
+
+    def observe_compressed_image(self, i: int, left: bytes, right: bytes, bayer_rggb8: bool = False, time: float = 0.0,
+                                 allow_status=()) -> bool:
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        added = bool(lib().vsfh_group_observe_compressed_image(self._h, i, _p(lb), len(lb), _p(rb), len(rb),
+                                                               int(bool(bayer_rggb8)), time))
+        self._check(i, "FrontendGroup::ObserveCompressedImage", allow_status)
+        return added
+
+    def serialize_problem(self, i: int) -> bytes:
+        """FrontendGroup::GetSLAMProblem(i) as ROS-1 wire bytes (books every frame in flight first)."""
+        n = lib().vsfh_group_serialize_problem(self._h, i, None, 0)
+        buf = np.zeros(max(n, 1), np.uint8)
+        lib().vsfh_group_serialize_problem(self._h, i, _p(buf), n)
+        return buf[:n].tobytes()
+
+    def flush(self) -> bool:
+        return bool(lib().vsfh_group_flush(self._h))
+
+    def queue_stats(self) -> dict:
+        """vsf_observe_stats of the group's context, by name (capi.Context.observe_stats)."""
+        v = np.zeros(len(capi.OBSERVE_STATS), np.int64)
+        st = lib().vsfh_group_queue_stats(self._h, _p(v), len(v))
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "vsf_observe_stats")
+        return {k: int(x) for k, x in zip(capi.OBSERVE_STATS, v)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vsfh_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()

@@ -184,6 +184,57 @@ size_t vsfh_debug_image_compressed(void* f, int stereo, uint8_t* out, size_t cap
 
 void vsfh_frontend_destroy(void* f) { delete static_cast<Frontend*>(f); }
 
+// slam::FrontendGroup: n members on one context.  Member i takes fundamental9[9 i ..] and best_percent[i] (<= 0: the
+// default); the rest as vsfh_frontend_create.  vsfh_group_member hands out
+// member i as a Frontend every vsfh_* call above takes (the group owns it: never vsfh_frontend_destroy).
+void* vsfh_group_create(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
+                        const float* best_percent, int frame_life) {
+  std::vector<FrontendConfig> cfgs((size_t)(n > 0 ? n : 0));
+  for (int i = 0; i < n; i++) {
+    FrontendConfig& cfg = cfgs[(size_t)i];
+    cfg.orb_nfeatures = nfeatures;
+    cfg.image_width = width;
+    cfg.image_height = height;
+    if (fundamental9) std::memcpy(cfg.fundamental.m, fundamental9 + 9 * i, 9 * sizeof(float));
+    if (best_percent && best_percent[i] > 0) cfg.best_percent_ = best_percent[i];
+    if (frame_life > 0) cfg.frame_life_ = (uint32_t)frame_life;
+  }
+  return new slam::FrontendGroup(cfgs, device);
+}
+void vsfh_group_destroy(void* g) { delete static_cast<slam::FrontendGroup*>(g); }
+int vsfh_group_size(void* g) { return static_cast<slam::FrontendGroup*>(g)->size(); }
+void* vsfh_group_member(void* g, int i) {
+  slam::FrontendGroup* gr = static_cast<slam::FrontendGroup*>(g);
+  return i >= 0 && i < gr->size() ? &gr->member(i) : nullptr;
+}
+int vsfh_group_last_status(void* g) { return (int)static_cast<slam::FrontendGroup*>(g)->last_status(); }
+void vsfh_group_set_pipelined(void* g, int on) { static_cast<slam::FrontendGroup*>(g)->set_pipelined(on != 0); }
+void vsfh_group_set_queue(void* g, int depth, int batch_frames, int min_batch) {
+  static_cast<slam::FrontendGroup*>(g)->set_queue(depth, batch_frames, min_batch);
+}
+void vsfh_group_set_queue_thread(void* g, int on) { static_cast<slam::FrontendGroup*>(g)->set_queue_thread(on != 0); }
+int vsfh_group_flush(void* g) { return static_cast<slam::FrontendGroup*>(g)->Flush() ? 1 : 0; }
+void vsfh_group_observe_odometry(void* g, int i, const float t[3], const float q_wxyz[4], double ts) {
+  static_cast<slam::FrontendGroup*>(g)->ObserveOdometry(i, slam::Vector3f(t[0], t[1], t[2]),
+                                                        slam::Quaternionf(q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3]), ts);
+}
+int vsfh_group_observe_image(void* g, int i, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, double time) {
+  return static_cast<slam::FrontendGroup*>(g)->ObserveImage(i, slam::Image(left, h, w, stride), slam::Image(right, h, w, stride), time)
+             ? 1
+             : 0;
+}
+int vsfh_group_observe_compressed_image(void* g, int i, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                        size_t right_bytes, int bayer_rggb8, double time) {
+  return static_cast<slam::FrontendGroup*>(g)->ObserveCompressedImage(i, left, left_bytes, right, right_bytes, bayer_rggb8 != 0, time)
+             ? 1
+             : 0;
+}
+// vsf_observe_stats of the group's context (out[0..n)).
+int vsfh_group_queue_stats(void* g, int64_t* out, int n) {
+  vsf_ctx* c = static_cast<slam::FrontendGroup*>(g)->context();
+  return c ? (int)vsf_observe_stats(c, out, n) : (int)VSF_ERR_INVALID_ARG;
+}
+
 void vsfh_observe_odometry(void* f, const float t[3], const float q_wxyz[4], double ts) {
   static_cast<Frontend*>(f)->ObserveOdometry(slam::Vector3f(t[0], t[1], t[2]),
                                              slam::Quaternionf(q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3]), ts);
@@ -307,6 +358,16 @@ void vsfh_serialize_calibration(void* f, uint8_t extrinsics48[48], uint8_t intri
 size_t vsfh_serialize_problem(void* f, uint8_t* out, size_t cap) {
   slam_types::SLAMProblem p;
   static_cast<Frontend*>(f)->GetSLAMProblem(&p);
+  std::vector<uint8_t> bytes;
+  slam_to_ros::SerializeSLAMProblem(p, &bytes);
+  if (out && cap) std::memcpy(out, bytes.data(), bytes.size() < cap ? bytes.size() : cap);
+  return bytes.size();
+}
+
+// FrontendGroup::GetSLAMProblem(i) as ROS-1 wire bytes (vsfh_serialize_problem's rules).
+size_t vsfh_group_serialize_problem(void* g, int i, uint8_t* out, size_t cap) {
+  slam_types::SLAMProblem p;
+  static_cast<slam::FrontendGroup*>(g)->GetSLAMProblem(i, &p);
   std::vector<uint8_t> bytes;
   slam_to_ros::SerializeSLAMProblem(p, &bytes);
   if (out && cap) std::memcpy(out, bytes.data(), bytes.size() < cap ? bytes.size() : cap);

@@ -223,6 +223,12 @@ Frame::Frame(const std::vector<vsf_keypoint>& keypoints, const std::vector<uint8
 Frontend::Frontend(const std::string& config_path) : Frontend(config_path, FrontendConfig(), 0) {}
 
 Frontend::Frontend(const std::string& /*config_path*/, const FrontendConfig& config, int device)
+    : Frontend(config, device, nullptr, 0) {
+  if (config_.image_width > 0 && config_.image_height > 0) EnsureContext(config_.image_width, config_.image_height);
+}
+
+// Everything but the context: a Frontend of its own builds it right away (above), a group builds ONE for all its members.
+Frontend::Frontend(const FrontendConfig& config, int device, FrontendGroup* group, int stream)
     : odom_initialized_(false),
       odom_timestamp_(0),
       config_(config),
@@ -231,22 +237,28 @@ Frontend::Frontend(const std::string& /*config_path*/, const FrontendConfig& con
       fused_(true),
       pipelined_(false),
       ctx_(nullptr),
+      group_(group),
+      stream_(stream),
+      owns_ctx_(stream == 0),
       device_(device),
       last_status_(VSF_OK) {
   if (config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::ORB &&
       config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::FREAK)
     last_status_ = VSF_ERR_UNSUPPORTED;  // the reference would build AKAZE / BRISK / SURF / SIFT here (cc:193-232)
-  if (config_.image_width > 0 && config_.image_height > 0) EnsureContext(config_.image_width, config_.image_height);
 }
 
 // Frames still in flight (pipelined mode) are dropped, not booked: nobody can read the problem any more.  vsf_destroy
 // waits for every stream of the context -- the slots' included -- before it frees what their kernels write.
 Frontend::~Frontend() {
   pending_count_ = 0;
-  vsf_destroy(ctx_);
+  if (owns_ctx_) vsf_destroy(ctx_);
 }
 
 bool Frontend::EnsureContext(int width, int height) {
+  return group_ ? group_->EnsureContext(width, height) : EnsureOwnContext(width, height, 1);
+}
+
+bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
   if (ctx_) {
     vsf_params p;
     vsf_get_params(ctx_, &p);
@@ -267,12 +279,14 @@ bool Frontend::EnsureContext(int width, int height) {
   if (last_status_ != VSF_OK) return false;
   last_status_ = vsf_create(&p, device_, &ctx_);
   if (last_status_ != VSF_OK) return false;
+  ctx_generation_++;
   ctx_depth_ = queue_depth();
   last_status_ = vsf_set_option(ctx_, VSF_OPT_OBSERVE_THREAD, queue_thread_ ? 1 : 0);
   if (last_status_ == VSF_OK) last_status_ = vsf_set_option(ctx_, VSF_OPT_OBSERVE_COPY_THREAD, copy_thread_ ? 1 : 0);
   for (const auto& ov : ctx_options_)
     if (last_status_ == VSF_OK) last_status_ = vsf_set_option(ctx_, ov.first, ov.second);
   if (last_status_ == VSF_OK) last_status_ = vsf_observe_configure(ctx_, ctx_depth_, min_batch_, 0);
+  if (last_status_ == VSF_OK && n_streams > 1) last_status_ = vsf_observe_set_streams(ctx_, n_streams);
   // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
   if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
   // ... and leave as files when the configuration asks for one form of them (both: the second request is refused)
@@ -582,15 +596,19 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   }
   const vsf_calibration calib = MakeCalibration(config_);
   // the queue must have room: when it is full, the oldest frame is collected and booked first
-  while ((int)pending_count_ >= queue_depth())
-    if (!RetireOldest()) return false;
+  // (a group member: the queue is the group's, and so is the order its frames are retired in)
+  auto in_flight = [this] { return group_ ? group_->in_flight() : pending_count_; };
+  auto retire = [this] { return group_ ? group_->RetireOldest() : RetireOldest(); };
+  while ((int)in_flight() >= queue_depth())
+    if (!retire()) return false;
   PendingFrame& pf = pending_[(pending_head_ + pending_count_) % pending_.size()];
   if (fp.compressed)  // (a file the host half of the decoders refuses: no ticket, nothing booked, the queue as it was)
-    last_status_ = vsf_observe_submit_compressed(ctx_, fp.left, fp.left_bytes, fp.right, fp.right_bytes, fp.bayer ? 1 : 0, &calib,
-                                                 config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
+    last_status_ = vsf_observe_submit_compressed_stream(ctx_, stream_, fp.left, fp.left_bytes, fp.right, fp.right_bytes,
+                                                        fp.bayer ? 1 : 0, &calib, config_.best_percent_,
+                                                        (int)config_.frame_life_, &pf.ticket);
   else
-    last_status_ = vsf_observe_submit(ctx_, fp.left, fp.right, width, height, fp.step, &calib, config_.best_percent_,
-                                      (int)config_.frame_life_, &pf.ticket);
+    last_status_ = vsf_observe_submit_stream(ctx_, stream_, fp.left, fp.right, width, height, fp.step, &calib,
+                                             config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
   if (last_status_ != VSF_OK) return false;
   pf.odom_translation = odom_translation_;
   pf.odom_rotation = odom_rotation_;
@@ -598,22 +616,25 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   pf.prev_odom_rotation = prev_odom_rotation_;
   pf.odom_timestamp = odom_timestamp_;
   pending_count_++;
+  if (group_) group_->submitted(stream_);
   // cc:457-458: the pose of this frame is what the NEXT call's OdomCheck compares with
   prev_odom_rotation_ = odom_rotation_;
   prev_odom_translation_ = odom_translation_;
-  if (!pipelined_) return RetireOldest();
+  if (!pipelined_) return retire();
   // results that are already there are booked now (no waiting, nothing sent early): at a camera's rate the problem stays a
   // frame or two behind instead of a queue's depth; when frames stream in faster than the GPU serves them this finds nothing
   // and the queue fills as before
-  while (pending_count_ > 1) {
+  while (in_flight() > 1) {
     int ready = 0;
-    if (vsf_observe_poll(ctx_, pending_[pending_head_].ticket, &ready) != VSF_OK || !ready) break;
-    if (!RetireOldest()) return false;
+    const int64_t oldest = group_ ? group_->oldest_ticket() : pending_[pending_head_].ticket;
+    if (vsf_observe_poll(ctx_, oldest, &ready) != VSF_OK || !ready) break;
+    if (!retire()) return false;
   }
   return true;
 }
 
 bool Frontend::Flush() {
+  if (group_) return group_->Flush();  // (tickets leave in the order they were issued, whichever member they belong to)
   while (pending_count_ > 0)
     if (!RetireOldest()) return false;
   return true;
@@ -966,6 +987,125 @@ void Frontend::DrawDebugImages(const uint8_t* left, const uint8_t* right, int w,
   if (last_status_ != VSF_OK) return;
   if (stereo) debug_stereo_images_.push_back(std::move(stereo_image));
   if (past_frame && temporal) debug_images_.push_back(std::move(match_image));
+}
+
+}  // namespace slam
+
+// ---- FrontendGroup ----
+namespace slam {
+
+FrontendGroup::FrontendGroup(const std::vector<FrontendConfig>& configs, int device) {
+  if (configs.empty() || configs.size() > (size_t)VSF_OBSERVE_MAX_STREAMS) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  const FrontendConfig& lead = configs[0];
+  for (const FrontendConfig& c : configs)  // debug images are single-stream: refused here, not by the context some calls later
+    if (configs.size() > 1 && (c.debug_images_ || c.debug_jpeg_quality_ != 0 || c.debug_png_)) {
+      last_status_ = VSF_ERR_UNSUPPORTED;
+      return;
+    }
+  for (const FrontendConfig& c : configs)  // what the one context is built with
+    if (c.orb_nfeatures != lead.orb_nfeatures || c.nn_match_ratio_ != lead.nn_match_ratio_ ||
+        c.residual_order != lead.residual_order || c.frame_life_ != lead.frame_life_ || c.image_width != lead.image_width ||
+        c.image_height != lead.image_height) {
+      last_status_ = VSF_ERR_INVALID_ARG;
+      return;
+    }
+  for (size_t i = 0; i < configs.size(); i++) {
+    members_.push_back(new Frontend(configs[i], device, this, (int)i));
+    if (last_status_ == VSF_OK) last_status_ = members_.back()->last_status_;
+  }
+  ready_ = true;
+  if (last_status_ == VSF_OK && lead.image_width > 0 && lead.image_height > 0) EnsureContext(lead.image_width, lead.image_height);
+}
+
+// (frames in flight are dropped, as a Frontend's are; the first member owns the context)
+FrontendGroup::~FrontendGroup() {
+  for (size_t i = members_.size(); i-- > 0;) delete members_[i];
+}
+
+// The queue is the group's: every member holds the same settings (a member's own setters come here).
+void FrontendGroup::set_pipelined(bool on) {
+  for (Frontend* m : members_) m->pipelined_ = on;
+}
+void FrontendGroup::set_queue(int depth, int batch_frames, int min_batch) {
+  for (Frontend* m : members_) {
+    if (depth > 0) m->depth_ = depth > 1024 ? 1024 : depth;
+    if (batch_frames > 0) m->batch_frames_ = batch_frames > 256 ? 256 : batch_frames;
+    if (min_batch >= 0) m->min_batch_ = min_batch;
+  }
+}
+void FrontendGroup::set_queue_thread(bool on) {
+  for (Frontend* m : members_) m->queue_thread_ = on;
+}
+
+// (the setters of slam_frontend.h that a group member hands to its group)
+void Frontend::set_pipelined(bool on) {
+  if (group_) return group_->set_pipelined(on);
+  pipelined_ = on;
+}
+void Frontend::set_queue_depth(int n) {
+  if (group_) return group_->set_queue(n < 1 ? 1 : n, 0, -1);
+  depth_ = n < 1 ? 1 : (n > 1024 ? 1024 : n);
+}
+void Frontend::set_batch_frames(int n) {
+  if (group_) return group_->set_queue(0, n < 1 ? 1 : n, -1);
+  batch_frames_ = n < 1 ? 1 : (n > 256 ? 256 : n);
+}
+void Frontend::set_min_batch(int n) {
+  if (group_) return group_->set_queue(0, 0, n < 0 ? 0 : n);
+  min_batch_ = n < 0 ? 0 : n;
+}
+void Frontend::set_queue_thread(bool on) {
+  if (group_) return group_->set_queue_thread(on);
+  queue_thread_ = on;
+}
+void Frontend::set_fused(bool on) {
+  if (!group_) fused_ = on;  // (a group's members observe through the queue: fused)
+}
+
+// The one context: built (or replaced: another image size, another queue) by the first member with a stream per member,
+// then shared.  A replaced context takes every frame in flight with it (booked first, in order, by the member's Flush).
+bool FrontendGroup::EnsureContext(int width, int height) {
+  if (!ready_) return true;  // (the members are still being constructed: the group's constructor calls again)
+  if (members_.empty() || last_status_ != VSF_OK) return false;
+  Frontend& lead = *members_[0];
+  vsf_ctx* const before = lead.ctx_;
+  const int generation = lead.ctx_generation_;
+  const bool ok = lead.EnsureOwnContext(width, height, size());
+  if (lead.ctx_ != before || lead.ctx_generation_ != generation) {
+    order_.clear();
+    for (Frontend* m : members_) {
+      m->ctx_ = lead.ctx_;
+      m->ctx_depth_ = lead.ctx_depth_;
+      m->pending_.assign((size_t)(lead.ctx_depth_ > 0 ? lead.ctx_depth_ : 1), Frontend::PendingFrame());
+      m->pending_head_ = m->pending_count_ = 0;
+    }
+  }
+  if (!ok)
+    for (Frontend* m : members_) m->last_status_ = lead.last_status_;
+  return ok;
+}
+
+int64_t FrontendGroup::oldest_ticket() const {
+  const Frontend& m = *members_[(size_t)order_.front()];
+  return m.pending_[m.pending_head_].ticket;
+}
+
+bool FrontendGroup::RetireOldest() {
+  if (in_flight() == 0) return true;
+  Frontend& m = *members_[(size_t)order_.front()];
+  order_.pop_front();
+  const bool ok = m.RetireOldest();
+  if (!ok) last_status_ = m.last_status_;
+  return ok;
+}
+
+bool FrontendGroup::Flush() {
+  while (in_flight() > 0)
+    if (!RetireOldest()) return false;
+  return true;
 }
 
 }  // namespace slam

@@ -11,6 +11,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <deque>
 #include <string>
 #include <utility>
 #include <vector>
@@ -119,6 +120,8 @@ class Frame {
   std::vector<uint8_t> descriptors_;  // keypoints_.size() x 32, row-major (cv::Mat CV_8U in the reference)
 };
 
+class FrontendGroup;
+
 class Frontend {
  public:
   // config_path is ignored exactly as in the reference (quirk Q1: FrontendConfig::Load is never defined).
@@ -173,7 +176,7 @@ class Frontend {
   // true (default): ObserveImage is one GPU submission (vsf_observe_stereo); false: one C-ABI call per reference call
   // (vsf_extract_pair, vsf_get_matches, ...) with the reference's host steps in between.  Same results; choose before
   // the first ObserveImage.
-  void set_fused(bool on) { fused_ = on; }
+  void set_fused(bool on);
   // ObserveImage's return value is OdomCheck's decision (cc:404-409): nothing in the reference's control flow needs a
   // frame's features before the next frame arrives.  With pipelining on (fused mode; choose before the first
   // ObserveImage) a call copies its frame into the GPU context's queue (vsf_observe_submit) and returns; frames that wait
@@ -182,7 +185,7 @@ class Frontend {
   // (queue_depth() frames later) or when anything reads the problem (GetSLAMProblem, GetNumPoses, the accessors below,
   // Flush).  Same nodes, factors and bytes as the
   // synchronous mode; a GPU failure then surfaces in last_status() some calls late.
-  void set_pipelined(bool on) { pipelined_ = on; }
+  void set_pipelined(bool on);
   // config.debug_images_ after construction (before the first ObserveImage; later calls fail with VSF_ERR_INVALID_ARG).
   void set_debug_images(bool on);
   void set_debug_jpeg_quality(int quality);  // config.debug_jpeg_quality_, under the same rule
@@ -191,16 +194,16 @@ class Frontend {
   // (default 128; the context's extraction buffers are sized for it: ~25 MB of HBM per 640x480 frame; the queue's staging
   // and result rings are pinned host memory: depth x (two images + vsf_observe_capacity)).  Measured on an MI355X at
   // 640x480 / 2000 features: depth 32 19 k frames/s, 64 25 k, 128 (64 per batch) 28 k, 256 (128 per batch) 32 k.
-  void set_queue_depth(int n) { depth_ = n < 1 ? 1 : (n > 1024 ? 1024 : n); }
+  void set_queue_depth(int n);
   void set_frames_in_flight(int n) { set_queue_depth(n); }  // (the name of rounds 3-5)
-  void set_batch_frames(int n) { batch_frames_ = n < 1 ? 1 : (n > 256 ? 256 : n); }
+  void set_batch_frames(int n);
   // While the GPU is busy, fewer waiting frames than this stay in the queue (0: a whole batch, or half the queue's depth
   // when that is less; 1: whatever waits leaves as soon as fewer than two batches are on the GPU).
-  void set_min_batch(int n) { min_batch_ = n < 0 ? 0 : n; }
+  void set_min_batch(int n);
   // The queue's host threads: the staging-copy helper (VSF_OPT_OBSERVE_COPY_THREAD, on by default) and the launcher
   // (VSF_OPT_OBSERVE_THREAD, off by default: with frames gathering into batches it only pays on a host whose launches
   // are what bounds the caller, and costs where depth = batch).
-  void set_queue_thread(bool on) { queue_thread_ = on; }
+  void set_queue_thread(bool on);
   void set_copy_thread(bool on) { copy_thread_ = on; }
   // Any vsf_option of the context (applied when it is created): launch choices only, results never depend on them.
   void set_context_option(int option, int value) { ctx_options_.push_back({option, value}); }
@@ -220,6 +223,9 @@ class Frontend {
   const std::vector<slam_types::OdometryFactor>& odometry_factors() const { Sync(); return odometry_factors_; }
 
  private:
+  friend class FrontendGroup;
+  // A member of a FrontendGroup: stream `stream` of the group's one context and queue.
+  Frontend(const FrontendConfig& config, int device, FrontendGroup* group, int stream);
   bool OdomCheck();
   bool ExtractFeatures(const Image& image, Frame* curr_frame);
   // The two ExtractFeatures calls of ObserveImage (cc:411-412) as one batch of two images (vsf_extract_pair).
@@ -235,7 +241,8 @@ class Frontend {
   void UndistortFeaturePoints(std::vector<slam_types::VisionFeature>* features);
   void Calculate3DPoints(Frame* left_frame, Frame* right_frame, std::vector<Vector3f>* points,
                          slam_types::VisionFactor* matches_out = nullptr);
-  bool EnsureContext(int width, int height);
+  bool EnsureContext(int width, int height);  // (a group member: the group's)
+  bool EnsureOwnContext(int width, int height, int n_streams);
   // The form the queue's debug images leave in, as config_.debug_jpeg_quality_ / debug_png_ ask for it: raw images, or the bit of
   // the one form of file (both bits only in a configuration the context refuses).  The ONE place that reads the pair.
   enum { kFormRaw = 0, kFormJpeg = 1, kFormPng = 2 };
@@ -299,10 +306,71 @@ class Frontend {
   std::vector<PendingFrame> pending_;  // a ring: pending_head_ is the oldest, pending_count_ frames wait
   size_t pending_head_ = 0, pending_count_ = 0;
   int ctx_depth_ = 0;
+  int ctx_generation_ = 0;  // contexts created so far (a replaced context may come back at the same address)
   vsf_ctx* ctx_;
+  FrontendGroup* group_ = nullptr;  // the group this object is a member of: ctx_ is then the group's (its first member owns it)
+  int stream_ = 0;                  // ... and this is its stream of the context's queue
+  bool owns_ctx_ = true;
   int device_;
   vsf_status last_status_;
   uint64_t refused_frames_ = 0;
+};
+
+// Several cameras, one GPU: N Frontend objects on ONE context and ONE ObserveImage queue, member i on stream i
+// (vsf_observe_set_streams).  Frames of different members wait in the same queue and leave for the GPU in the same batch, so
+// the members share the extraction buffers (~25 MB of HBM per frame of a batch) and a batch's ~45 launches.  Every member's
+// nodes, factors and bytes are those of a Frontend of its own fed the same calls (tests/test_gpu_frontend_group.py).
+//   The members' configurations may differ in everything a frame brings to the queue -- the calibration (intrinsics,
+// projections, fundamental), best_percent_, the odometry gates -- and must agree in what the context is built with:
+// orb_nfeatures, nn_match_ratio_, residual_order, frame_life_ and the image size (else last_status() of the group reads
+// VSF_ERR_INVALID_ARG and nothing is observed).  Members observe in fused mode (a member's set_fused does nothing).  Debug
+// images are not available in a group of more than one member: a configuration that asks for them (debug_images_,
+// debug_jpeg_quality_, debug_png_) is refused by the constructor with VSF_ERR_UNSUPPORTED.
+//   The queue is the group's: set_pipelined / set_queue / set_queue_thread below set every member alike, and the same
+// setters called on one member (set_pipelined, set_queue_depth, set_batch_frames, set_min_batch, set_queue_thread) are
+// handed to the group, so the members never disagree.  Context options and the copy thread are read from member(0).
+//   Tickets are retired in the order they were issued, whichever member they belong to, and each result is booked by the
+// member that submitted it with the odometry of ITS call.  Reading one member's problem books everything in flight.
+class FrontendGroup {
+ public:
+  explicit FrontendGroup(const std::vector<FrontendConfig>& configs, int device = 0);
+  ~FrontendGroup();
+  FrontendGroup(const FrontendGroup&) = delete;
+  FrontendGroup& operator=(const FrontendGroup&) = delete;
+
+  int size() const { return (int)members_.size(); }
+  Frontend& member(int i) { return *members_[(size_t)i]; }
+  void ObserveOdometry(int i, const Vector3f& translation, const Quaternionf& rotation, double timestamp) {
+    member(i).ObserveOdometry(translation, rotation, timestamp);
+  }
+  bool ObserveImage(int i, const Image& left_image, const Image& right_image, double time) {
+    return member(i).ObserveImage(left_image, right_image, time);
+  }
+  bool ObserveCompressedImage(int i, const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
+                              bool bayer_rggb8, double time) {
+    return member(i).ObserveCompressedImage(left, left_bytes, right, right_bytes, bayer_rggb8, time);
+  }
+  void GetSLAMProblem(int i, slam_types::SLAMProblem* problem) { member(i).GetSLAMProblem(problem); }
+  bool Flush();  // collects and books every frame still in flight, in ticket order; false if one of them failed
+  // As the Frontend's own (before the first image): the one queue of the group.
+  void set_pipelined(bool on);
+  void set_queue(int depth, int batch_frames, int min_batch);  // depth / batch_frames 0, min_batch < 0: as it is
+  void set_queue_thread(bool on);
+  vsf_status last_status() const { return last_status_; }
+  vsf_ctx* context() const { return members_.empty() ? nullptr : members_[0]->ctx_; }
+
+ private:
+  friend class Frontend;
+  bool EnsureContext(int width, int height);
+  bool RetireOldest();  // the oldest ticket, by the member it belongs to
+  size_t in_flight() const { return order_.size(); }
+  int64_t oldest_ticket() const;
+  void submitted(int stream) { order_.push_back(stream); }
+
+  std::vector<Frontend*> members_;
+  std::deque<int> order_;  // the members of the frames in flight, in ticket order
+  bool ready_ = false;  // every member is constructed
+  vsf_status last_status_ = VSF_OK;
 };
 
 }  // namespace slam
