@@ -12,6 +12,7 @@
 
 #include "vsf_internal.h"
 #include "vsf_observe_plan.h"
+#include "vsf_observe_queue.h"
 
 namespace vsfi {
 
@@ -99,8 +100,6 @@ struct vsf_ctx {
   int pending_hip = 0;  // an error noted during one of THIS context's calls that returned before checking (VsfErrorScope)
   // The ObserveImage queue (vsf_observe.hip): frames wait in pinned staging and leave for the GPU in batches.
   static constexpr int kObserveBatchSlots = 4;
-  struct ObserveLauncher;    // the queue's lock and its launcher thread
-  struct ObserveCopyHelper;  // a host thread that takes half of a frame's staging copy while frames stream in
   struct ObserveBatchMeta;  // pinned, device-visible: read by the kernels over PCIe (no copy command)
   struct ObserveBatch {     // what one batch's extraction writes and its tail reads
     vsfi::DevBuf<uint8_t> d_img;        // [2 bmax] images at the staging pitch
@@ -139,13 +138,12 @@ struct vsf_ctx {
     bool operator==(const DebugForm& o) const { return kind == o.kind && quality == o.quality; }
   };
   struct Observe {
-    // (defined in vsf_observe.hip, where the two thread types are complete; `o = Observe()` releases everything a queue owns)
-    Observe();
-    ~Observe();
-    Observe& operator=(Observe&&) noexcept;
+    // (`o = Observe()` releases everything a queue owns)
     vsfi::Stream copy_stream, tail_stream;  // before everything their work touches
-    std::unique_ptr<ObserveLauncher> launcher;
-    std::unique_ptr<ObserveCopyHelper> copy_helper;
+    // vsf_observe_queue.h: the tickets, the lock, who launches and when (there while `ready`); a host thread that takes half
+    // of a frame's staging copy while frames stream in.  (free_observe stops their threads before the buffers below go.)
+    std::unique_ptr<vsfi::ObserveQueue> queue;
+    std::unique_ptr<vsfi::ObserveCopyHelper> copy_helper;
     bool ready = false;
     int frame_life = 0;
     bool debug = false;  // built with ob_debug: the batches' tails draw the debug images
@@ -173,7 +171,6 @@ struct vsf_ctx {
       vsfi::DevBuf<int32_t> d_bytes;    // [2][bmax] the files' sizes: stereo, match; [1] the encoder's status word
       vsfi::DevBuf<uint8_t> d_scratch;  // the encoder's scratch for bmax canvases of either size
       vsfi::PinnedBuf<uint8_t> h_ring;
-      int64_t stat_commands = 0;     // launches the compressed debug path issued (vsf_observe_stats)
     } files;
     int depth = 0;      // frames that may be submitted and not collected
     int bmax = 0;       // frames per batch at most
@@ -204,24 +201,14 @@ struct vsf_ctx {
     size_t cmp_cap = 0, cmp_slot = 0;  // bytes a file may have / bytes of its slot (vsf_observe_compressed_slot_bytes)
     vsfi::DevBuf<uint8_t> d_bayer;     // [2 bmax] images at the staging pitch: the decoded mosaics of a Bayer batch
     VsfDecodeScratch ing_scratch;   // the decoders' scratch on the copy stream
-    int64_t stat_compressed = 0;    // compressed frames launched
-    int64_t stat_ingest_commands = 0;  // copy commands + launches the compressed path issued
     size_t out_cap = 0, out_stride = 0;
     ObserveBatch batch[kObserveBatchSlots];
     std::vector<ObserveFrame> frames;  // [depth]
     std::vector<ObserveStream> streams;  // [n_streams]
     std::vector<vsfi::ObservePlanIn> plan_in;  // launch_batch's: the batch as vsf_observe_plan.h takes it ...
     vsfi::ObservePlan plan;                    // ... and plans it (kept from batch to batch: no allocation per batch)
-    int64_t next_ticket = 0;   // tickets issued
-    int64_t next_launch = 0;   // first frame still waiting in staging
-    int64_t next_collect = 0;  // oldest frame not collected
-    int64_t batches = 0;       // batches launched
-    int64_t last_submit_ns = 0;  // when the last frame arrived
-    int rows_hint = 0;           // expected rows of a filtered frame (from the collected results; 0: unknown)
     int last_batch = -1;       // slot of the batch launched last
-    int64_t stat_frames = 0, stat_max_batch = 0, stat_solo = 0, stat_forced = 0, stat_slot_waits = 0;  // vsf_observe_stats
-    int64_t stat_copy_ns = 0, stat_launch_ns = 0, stat_wait_ns = 0;  // host time in staging copies, launches, waits
-    int64_t stat_multi = 0;  // batches that carried frames of more than one stream
+    int64_t stat_copy_ns = 0, stat_wait_ns = 0;  // the caller's time in staging copies and waits (vsf_observe_stats)
   } ob;
   // vsf_observe_configure (before the queue is built by the first submit; 0 = defaults)
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;

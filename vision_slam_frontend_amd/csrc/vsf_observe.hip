@@ -10,134 +10,35 @@
 //               result per frame written straight into pinned host memory.
 // A frame's launch-bound chain of ~30 small kernels costs the host 5.4 us per launch and the GPU a launch-to-launch latency
 // per kernel whatever the batch holds, so a batch of n frames costs little more than a batch of one until the chip is full.
-// When a batch leaves (batch_to_launch): when a whole batch waits; when `min_batch` frames wait (a whole batch by default while the queue holds two, else half the queue) and
+// When a batch leaves (vsf_observe_queue.cc batch_to_launch): when a whole batch waits; when `min_batch` frames wait (a whole batch by default while the queue holds two, else half the queue) and
 // fewer than `in_flight` batches are on the GPU; when the GPU is idle and no frame has arrived for 100 us; or when somebody
 // collects a frame that still waits (a lone frame: the synchronous call is a batch of one).  While the GPU is busy, frames
 // accumulate -- the batch size follows the caller's rate by itself.
 // The kept frames' filtered descriptors live in a ring of descriptor sets in HBM (frame g in set g % ring); the pair list
 // of a batch addresses them by set index, so a frame matches against frames of earlier batches and of its own alike.
 // Results are those of one frame at a time, bit for bit (tests/test_gpu_observe.py).
+// The host threads -- tickets, the lock, who launches and when, the staging copy's helper -- are plain C++ in
+// vsf_observe_queue.cc; this file is what touches HIP: it builds the queue's buffers, launches a batch, and hands the queue
+// that launch as a callable.
 // STREAMS (vsf_observe_set_streams): the queue takes frames of several independent sequences -- several cameras on one GPU --
 // and frames of different streams leave in the same batch.  Everything that crosses frames exists per stream: a threshold
 // (thr_state[stream]), a ring of descriptor sets (frame k of stream s in set s ring + k % ring), the calibration (the batch's
 // pinned block carries a table of its distinct calibrations and an index per frame).  vsf_observe_plan.cc does the arithmetic;
 // each stream's results are those of a context of its own, byte for byte (tests/test_gpu_observe_streams.py).
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <climits>
 #include <cmath>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
 #include <mutex>
 #include <new>
-#include <thread>
 #include <vector>
 
 #include "vsf_ctx.h"
 
 using namespace vsfi;
-
-// One row-wise copy of an image into the staging ring (rows at the device pitch): 5-12 us per 640x480 image on one core,
-// depending on the host (its memory, its neighbours).
-static void stage_image(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t src_pitch, size_t width, int rows) {
-  if (dst_pitch == src_pitch) {
-    std::memcpy(dst, src, (size_t)(rows - 1) * src_pitch + width);
-  } else {
-    for (int y = 0; y < rows; y++) std::memcpy(dst + (size_t)y * dst_pitch, src + (size_t)y * src_pitch, width);
-  }
-}
-
-// The staging copy is what a queued frame costs its caller once the launches have a thread of their own: 13 us per frame on
-// one box, 23 us on another (the same run: 31.5 k and 28.9 k frames/s -- on the second the caller never waits for the GPU).
-// While frames stream in (the previous one is still in the queue) a helper thread takes the right image: it spins for a job
-// while it is hot and goes to sleep 300 us after the last one, so a caller that submits and collects frame by frame never
-// meets it (a wake-up costs more than the copy saves).  It touches host memory only: no HIP call, no context state.
-struct vsf_ctx::ObserveCopyHelper {
-  struct Job {
-    uint8_t* dst;
-    const uint8_t* src;
-    size_t dst_pitch, src_pitch, width;
-    int rows;
-  };
-  std::thread th;
-  std::mutex m;
-  std::condition_variable cv;
-  std::atomic<int> state{0};  // 0 no job, 1 job posted, 2 job done
-  std::atomic<bool> hot{false}, stop{false};
-  bool wake = false;
-  Job job{};
-  ObserveCopyHelper() { th = std::thread([this] { run(); }); }
-  ~ObserveCopyHelper() {
-    {
-      std::lock_guard<std::mutex> g(m);
-      stop.store(true);
-    }
-    cv.notify_all();
-    th.join();
-  }
-  void run() {
-    using Clock = std::chrono::steady_clock;
-    while (!stop.load(std::memory_order_acquire)) {
-      hot.store(true, std::memory_order_release);
-      Clock::time_point last = Clock::now();
-      while (!stop.load(std::memory_order_relaxed)) {
-        if (state.load(std::memory_order_acquire) == 1) {
-          stage_image(job.dst, job.dst_pitch, job.src, job.src_pitch, job.width, job.rows);
-          state.store(2, std::memory_order_release);
-          last = Clock::now();
-        } else {
-          __builtin_ia32_pause();
-          if (Clock::now() - last > std::chrono::microseconds(300)) break;
-        }
-      }
-      hot.store(false, std::memory_order_release);
-      std::unique_lock<std::mutex> g(m);
-      // (a job posted between the last look and `hot = false` is still served: the wait's predicate sees it)
-      cv.wait(g, [this] { return stop.load() || wake || state.load(std::memory_order_acquire) == 1; });
-      wake = false;
-    }
-  }
-  // true: the helper took `j` (wait() must follow); false: it sleeps -- woken for the frames behind this one -- and the
-  // caller copies `j` itself.
-  bool post(const Job& j) {
-    if (!hot.load(std::memory_order_acquire)) {
-      {
-        std::lock_guard<std::mutex> g(m);
-        wake = true;
-      }
-      cv.notify_one();
-      return false;
-    }
-    job = j;
-    state.store(1, std::memory_order_release);
-    if (!hot.load(std::memory_order_acquire)) cv.notify_one();  // (it was on its way to sleep: the predicate serves the job)
-    return true;
-  }
-  void wait() {
-    while (state.load(std::memory_order_acquire) != 2) __builtin_ia32_pause();
-    state.store(0, std::memory_order_relaxed);
-  }
-};
-
-// Who launches.  A batch costs the host 0.1 ms (a lone frame) to 0.4 ms (the batched pyramid alone is 50-100 launches).
-// By default the caller launches, between two submits (4-5 us per frame at 64-128 frames per batch).  With
-// VSF_OPT_OBSERVE_THREAD a queue of depth >= 4 has a LAUNCHER thread instead: the caller stages frames and the thread sends
-// whatever the policy releases, polling the GPU's state while frames wait (measured slower wherever depth == batch size, the
-// same elsewhere: off by default).  The caller still launches by itself where waiting for the thread would cost more than it
-// saves: when it collects a frame that still waits (the synchronous call: submit, collect), and for every other entry
-// point of the context, which first sends everything that waits (VsfErrorScope -> vsf_ctx_enter), so that nothing else ever
-// runs beside the thread.  `launching` is the baton: whoever holds it is alone inside launch_batch.
-struct vsf_ctx::ObserveLauncher {
-  std::mutex mu;  // guards next_ticket / next_launch / next_collect, launching, stop, status
-  std::condition_variable cv_thread, cv_caller;
-  bool launching = false, stop = false, has_thread = false;
-  vsf_status status = VSF_OK;  // first failure of a launch: sticky until the queue is rebuilt
-  std::thread th;
-};
 
 struct vsf_ctx::ObserveBatchMeta {
   int32_t n_frames, n_pairs;
@@ -177,25 +78,13 @@ MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
   return v;
 }
 
-inline int64_t now_ns() {
-  return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 namespace vsfi {
 
 void stop_observe_threads(vsf_ctx* ctx) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.launcher && o.launcher->has_thread) {
-    {
-      std::lock_guard<std::mutex> g(o.launcher->mu);
-      o.launcher->stop = true;
-    }
-    o.launcher->cv_thread.notify_all();
-    o.launcher->th.join();
-    o.launcher->has_thread = false;
-  }
+  if (o.queue) o.queue->stop_thread();
   o.copy_helper.reset();
 }
 
@@ -210,14 +99,9 @@ void free_observe(vsf_ctx* ctx) {
 
 }  // namespace vsfi
 
-// (here, where the two thread types are complete: the unique_ptr members need them)
-vsf_ctx::Observe::Observe() = default;
-vsf_ctx::Observe::~Observe() = default;
-vsf_ctx::Observe& vsf_ctx::Observe::operator=(Observe&&) noexcept = default;
-
 namespace {
 
-void launcher_thread(vsf_ctx* ctx);
+ObserveGpu observe_gpu(vsf_ctx* ctx);
 
 // The encode of a batch's n stereo canvases (which = 0: 2w x h) or match canvases (1: w x h) into the device slots: the ONE
 // description the scratch is sized by and the tail launches with.
@@ -347,16 +231,13 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   // extraction instead of running beside it -- which it did or did not from one context to the next (17 k or 27 k frames/s)
   VSF_HIP(o.copy_stream.alloc(hipStreamNonBlocking, prio_lo));
   VSF_HIP(hipDeviceSynchronize());
-  o.launcher.reset(new (std::nothrow) vsf_ctx::ObserveLauncher());
-  if (!o.launcher) return VSF_ERR_INVALID_ARG;
+  o.queue.reset(new (std::nothrow) ObserveQueue({o.depth, o.bmax, ctx->ob_min_batch, ctx->ob_in_flight}, observe_gpu(ctx)));
+  if (!o.queue) return VSF_ERR_INVALID_ARG;
   o.ready = true;
   // the two host threads of a deep queue: VSF_OPT_OBSERVE_THREAD (without it the caller launches everything) and
   // VSF_OPT_OBSERVE_COPY_THREAD (without it the caller stages both images)
-  if (o.depth >= 4 && ctx->tuning.observe_copy_thread) o.copy_helper.reset(new (std::nothrow) vsf_ctx::ObserveCopyHelper());
-  if (o.depth >= 4 && ctx->tuning.observe_thread) {
-    o.launcher->has_thread = true;
-    o.launcher->th = std::thread(launcher_thread, ctx);
-  }
+  if (o.depth >= 4 && ctx->tuning.observe_copy_thread) o.copy_helper.reset(new (std::nothrow) ObserveCopyHelper());
+  if (o.depth >= 4 && ctx->tuning.observe_thread) o.queue->start_thread();
   return VSF_OK;
 }
 
@@ -411,8 +292,8 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   if (bayer) vsf_launch_bayer_bg_gray(o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
   vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
   // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
-  o.stat_ingest_commands += 2 + runs + (bayer ? 1 : 0);
-  for (int f = 0; f < n; f++) o.stat_compressed += kinds[2 * f] != VSF_FILE_NONE;
+  o.queue->stats.ingest_commands += 2 + runs + (bayer ? 1 : 0);
+  for (int f = 0; f < n; f++) o.queue->stats.compressed += kinds[2 * f] != VSF_FILE_NONE;
   return VSF_OK;
 }
 
@@ -449,7 +330,7 @@ vsf_status launch_debug_images(vsf_ctx* ctx, const vsf_ctx::ObserveBatch& b, con
       vsf_launch_files_home(fl.d_slots + fl.off[which], fl.slot, d_bytes, n, fl.h_ring, fl.slot, fl.off[which], which, slot0, o.depth,
                             M.frames, o.h_out, o.out_stride, s_tail);
     }
-    fl.stat_commands += 2 * per_size;
+    o.queue->stats.file_commands += 2 * per_size;
   } else {
     VSF_HIP(hipMemcpyAsync(o.h_dbg + (size_t)slot0 * o.dbg_stride, o.dbg_canvas, (size_t)first * o.dbg_stride,
                            hipMemcpyDeviceToHost, s_tail));
@@ -460,16 +341,17 @@ vsf_status launch_debug_images(vsf_ctx* ctx, const vsf_ctx::ObserveBatch& b, con
   return VSF_OK;
 }
 
-// Queues frames [t0, t0 + n) -- they wait in consecutive staging slots -- as one batch.
-vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
+// Queues frames [t0, t0 + n) -- they wait in consecutive staging slots -- as one batch.  The caller holds the queue's baton.
+vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hint) {
   vsf_ctx::Observe& o = ctx->ob;
+  ObserveLaunchStats& stats = o.queue->stats;
   const int64_t t_begin = now_ns();
-  const int bi = (int)(o.batches % vsf_ctx::kObserveBatchSlots);
+  const int bi = (int)(stats.batches % vsf_ctx::kObserveBatchSlots);
   vsf_ctx::ObserveBatch& b = o.batch[bi];
   // The slot's previous batch must have left the GPU: its kernels read the pinned parameter block that is rewritten below
   // (with `in_flight` batches on the GPU and four slots it has, long ago).
   if (b.used) {
-    if (hipEventQuery(b.ev_done) != hipSuccess) o.stat_slot_waits++;
+    if (hipEventQuery(b.ev_done) != hipSuccess) stats.slot_waits++;
     (void)hipGetLastError();
     VSF_HIP(hipEventSynchronize(b.ev_done));
   }
@@ -584,7 +466,7 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
     StageTimer t(ctx, s_tail, VSF_STAGE_KNN2, 1);
     // (rows_hint: what the caller's last collected frames held -- a filtered frame is a few hundred rows of the capacity)
     vsf_launch_knn2(o.sets, o.set_counts, K * VSF_DESC_BYTES, M.q_set, M.t_set, n_pairs, Kc, o.t_idx2, o.t_dist2, s_tail,
-                    o.rows_hint);
+                    rows_hint);
   }
   {
     StageTimer t(ctx, s_tail, VSF_STAGE_RATIO, 1);
@@ -632,99 +514,40 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo) {
   b.done_stream = s_tail;
   for (int f = 0; f < n; f++) o.frames[(size_t)((t0 + f) % o.depth)].batch = bi;
   o.last_batch = bi;
-  o.batches++;
-  o.stat_frames += n;
-  o.stat_max_batch = std::max<int64_t>(o.stat_max_batch, n);
-  if (solo) o.stat_solo++;
-  if (chains) o.stat_multi++;
-  o.stat_launch_ns += now_ns() - t_begin;
+  if (chains) stats.multi++;
+  stats.launch_ns += now_ns() - t_begin;
   VSF_STICKY();
   return VSF_OK;
 }
 
-// How many of the waiting frames leave now (0: none).  mu held, nobody launching.
-int batch_to_launch(vsf_ctx* ctx, bool force) {
-  vsf_ctx::Observe& o = ctx->ob;
-  const int pending = (int)(o.next_ticket - o.next_launch);
-  if (pending <= 0) return 0;
-  if (force || pending >= o.bmax) return std::min(pending, o.bmax);
-  // An idle GPU takes whatever waits.  A busy one is in no hurry: frames wait for company because a batch costs ~50-100
-  // launches whatever it carries (measured on the caller's thread: batches of 1-8 frames 14 k frames/s, of 32-64 frames
-  // 27 k).  How much company: in steady state a batch leaves the moment `min_batch` frames wait, so min_batch IS the batch
-  // size -- by default a whole batch when the queue is deep enough for the caller to fill the next one meanwhile (depth >= 2
-  // batches), else half the queue, so that staging and the GPU still overlap (tools/exp/min_batch.sh: depth 64 / 32 per
-  // batch 19.8 -> 25.0 k frames/s against half a batch, 128 / 64 27.9 -> 28.8 k, 256 / 128 32.0 -> 32.4 k; at depth =
-  // batch size half the queue is what it was).
-  // ... and "idle" must not be mistaken for "nobody is coming": while frames stream in (the last one arrived less than
-  // 100 us ago) even an idle GPU waits for min_batch of them.  Without that a GPU that once ran dry keeps being fed batches of
-  // a few frames, each gone before the next has gathered (measured: the same queue at 15 k or 32 k frames/s).
-  const int busy = batches_on_gpu(ctx);
-  const int min_batch = ctx->ob_min_batch > 0 ? std::min(ctx->ob_min_batch, o.bmax) : std::max(1, std::min(o.bmax, o.depth / 2));
-  if (busy < ctx->ob_in_flight && pending >= min_batch) return pending;
-  return (busy == 0 && now_ns() - o.last_submit_ns > 100000) ? pending : 0;
+// What the queue sees of the GPU (vsf_observe_queue.h).
+ObserveGpu observe_gpu(vsf_ctx* ctx) {
+  return {ctx,
+          [](void* c, int64_t t0, int n, bool solo, int rows_hint) {
+            return launch_batch(static_cast<vsf_ctx*>(c), t0, n, solo, rows_hint);
+          },
+          [](void* c) { return batches_on_gpu(static_cast<vsf_ctx*>(c)); },
+          [](void* c) { return hipSetDevice(static_cast<vsf_ctx*>(c)->device) == hipSuccess; }};
 }
 
-// One batch, by whoever holds the lock: takes the baton, launches outside the lock, publishes next_launch.
-vsf_status launch_one(vsf_ctx* ctx, std::unique_lock<std::mutex>& lk, int n) {
-  vsf_ctx::Observe& o = ctx->ob;
-  vsf_ctx::ObserveLauncher& L = *o.launcher;
-  const int64_t t0 = o.next_launch;
-  const bool solo = n == 1 && batches_on_gpu(ctx) == 0;
-  L.launching = true;
-  lk.unlock();
-  const vsf_status st = launch_batch(ctx, t0, n, solo);
-  lk.lock();
-  L.launching = false;
-  if (st == VSF_OK)
-    o.next_launch = t0 + n;
-  else if (L.status == VSF_OK)
-    L.status = st;
-  L.cv_caller.notify_all();
-  if (L.has_thread) L.cv_thread.notify_one();
-  return st;
+bool frames_in_queue(const vsf_ctx* ctx) { return ctx->ob.ready && ctx->ob.queue->next_collect != ctx->ob.queue->next_ticket; }
+
+// What a queue is built with changes only before its window holds a frame: the next submit rebuilds the queue
+// (ensure_observe carries the threshold).
+vsf_status retire_unused_queue(vsf_ctx* ctx) {
+  if (!ctx->ob.ready) return VSF_OK;
+  if (ctx->ob.queue->next_ticket != 0) return VSF_ERR_INVALID_ARG;
+  stop_observe_threads(ctx);
+  return VSF_OK;
 }
 
-// The caller's side.  force: everything that waits leaves now (somebody collects one of them, the parameters change, or
-// another entry point of the context is about to run); otherwise whatever the policy releases.  mu held on entry and exit.
-vsf_status caller_pump(vsf_ctx* ctx, std::unique_lock<std::mutex>& lk, bool force) {
-  vsf_ctx::Observe& o = ctx->ob;
-  vsf_ctx::ObserveLauncher& L = *o.launcher;
-  while (true) {
-    if (L.launching) {  // the thread is at it
-      if (!force) return VSF_OK;
-      L.cv_caller.wait(lk);
-      continue;
-    }
-    if (L.status != VSF_OK) return L.status;
-    const int n = batch_to_launch(ctx, force);
-    if (n == 0) return VSF_OK;
-    if (force) o.stat_forced++;
-    const vsf_status st = launch_one(ctx, lk, n);
-    if (st != VSF_OK) return st;
-  }
-}
-
-void launcher_thread(vsf_ctx* ctx) {
-  vsf_ctx::Observe& o = ctx->ob;
-  vsf_ctx::ObserveLauncher& L = *o.launcher;
-  if (hipSetDevice(ctx->device) != hipSuccess) {
-    std::lock_guard<std::mutex> g(L.mu);
-    L.status = VSF_ERR_HIP;
-    return;
-  }
-  std::unique_lock<std::mutex> lk(L.mu);
-  while (!L.stop) {
-    if (L.launching || L.status != VSF_OK || o.next_launch >= o.next_ticket) {
-      L.cv_thread.wait(lk);  // (a submit into an empty queue, the end of a launch and stop notify)
-      continue;
-    }
-    const int n = batch_to_launch(ctx, false);
-    if (n == 0) {  // frames wait for company or for the GPU: its state changes without a notification
-      L.cv_thread.wait_for(lk, std::chrono::microseconds(40));
-      continue;
-    }
-    (void)launch_one(ctx, lk, n);
-  }
+// The queue goes -- frames that still wait are dropped, the thresholds and the windows forgotten: the next submit builds another.
+vsf_status drop_queue(vsf_ctx* ctx) {
+  VSF_HIP(hipSetDevice(ctx->device));
+  stop_observe_threads(ctx);
+  sync_all_streams(ctx);
+  free_observe(ctx);
+  return VSF_OK;
 }
 
 // vsf_observe_set_debug_jpeg / _png: quality != 0 asks for files of `kind`, 0 takes that request back.
@@ -734,9 +557,8 @@ vsf_status set_debug_form(vsf_ctx* ctx, int kind, int quality) {
   if (quality == (f.kind == kind ? f.quality : 0)) return VSF_OK;
   if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
   if (quality != 0 && f.kind != VSF_FILE_NONE && f.kind != kind) return VSF_ERR_INVALID_ARG;  // one form of file at a time
-  // as vsf_observe_set_debug_images: only before the window holds a frame (the next submit rebuilds the queue)
-  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
-  if (ctx->ob.ready) stop_observe_threads(ctx);
+  const vsf_status st = retire_unused_queue(ctx);
+  if (st != VSF_OK) return st;
   f.kind = quality ? kind : VSF_FILE_NONE;
   f.quality = quality;
   return VSF_OK;
@@ -750,7 +572,7 @@ vsf_status debug_files_view(vsf_ctx* ctx, int kind, int64_t ticket, const uint8_
   *stereo = *match = nullptr;
   *stereo_bytes = *match_bytes = 0;
   const vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready || !o.debug || o.files.form.kind != kind || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+  if (!o.ready || !o.debug || o.files.form.kind != kind || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth)
     return VSF_ERR_INVALID_ARG;
   const int slot = (int)(ticket % o.depth);
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
@@ -775,11 +597,9 @@ vsf_status debug_files_view(vsf_ctx* ctx, int kind, int64_t ticket, const uint8_
 // leaves first and the launcher thread is idle afterwards -- it only wakes for frames that wait.
 void vsf_ctx_enter(vsf_ctx* ctx) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready || !o.launcher || !o.launcher->has_thread) return;
+  if (!o.ready || !o.queue->has_thread) return;
   if (hipSetDevice(ctx->device) != hipSuccess) return;
-  std::unique_lock<std::mutex> lk(o.launcher->mu);
-  (void)caller_pump(ctx, lk, true);
-  while (o.launcher->launching) o.launcher->cv_caller.wait(lk);
+  o.queue->drain();
 }
 
 extern "C" {
@@ -796,11 +616,9 @@ vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on) {
   // single-stream: the match image needs each stream's previous frame and rand()'s colour sequence per stream
   if (on != 0 && ctx->ob_streams > 1) return VSF_ERR_UNSUPPORTED;
   if ((on != 0) == ctx->ob_debug) return VSF_OK;
-  // only before the window holds a frame: the next submit rebuilds the queue (ensure_observe carries the threshold)
-  if (ctx->ob.ready && ctx->ob.next_ticket != 0) return VSF_ERR_INVALID_ARG;
-  if (ctx->ob.ready) stop_observe_threads(ctx);
-  ctx->ob_debug = on != 0;
-  return VSF_OK;
+  const vsf_status st = retire_unused_queue(ctx);
+  if (st == VSF_OK) ctx->ob_debug = on != 0;
+  return st;
 }
 
 vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match) {
@@ -809,7 +627,7 @@ vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** 
   *stereo = *match = nullptr;
   const vsf_ctx::Observe& o = ctx->ob;
   // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_collect_view)
-  if (!o.ready || !o.debug || o.files.form.kind || ticket < 0 || ticket >= o.next_collect || ticket < o.next_ticket - o.depth)
+  if (!o.ready || !o.debug || o.files.form.kind || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth)
     return VSF_ERR_INVALID_ARG;  // (with vsf_observe_set_debug_jpeg / _png the raw canvases never leave the device)
   const int slot = (int)(ticket % o.depth);
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
@@ -845,16 +663,19 @@ vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
   if (!ctx || depth < 0 || depth > 1024 || min_batch < 0 || in_flight < 0 || in_flight > vsf_ctx::kObserveBatchSlots - 1)
     return VSF_ERR_INVALID_ARG;
-  if (ctx->ob.ready && ctx->ob.next_collect != ctx->ob.next_ticket) return VSF_ERR_INVALID_ARG;  // frames in the queue
+  if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
   if (ctx->ob.ready && depth != ctx->ob_depth) {  // the queue is rebuilt by the next submit; the threshold and the window go
-    VSF_HIP(hipSetDevice(ctx->device));
-    stop_observe_threads(ctx);
-    sync_all_streams(ctx);
-    free_observe(ctx);
+    const vsf_status st = drop_queue(ctx);
+    if (st != VSF_OK) return st;
   }
   ctx->ob_depth = depth;
   ctx->ob_min_batch = min_batch;
   ctx->ob_in_flight = in_flight > 0 ? in_flight : 2;
+  if (ctx->ob.ready) {  // (a queue that stays follows at once)
+    std::lock_guard<std::mutex> g(ctx->ob.queue->mu);
+    ctx->ob.queue->sizes.min_batch = ctx->ob_min_batch;
+    ctx->ob.queue->sizes.in_flight = ctx->ob_in_flight;
+  }
   return VSF_OK;
 }
 
@@ -862,12 +683,10 @@ vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
   if (!ctx || n_streams < 1 || n_streams > VSF_OBSERVE_MAX_STREAMS) return VSF_ERR_INVALID_ARG;
   if (n_streams > 1 && ctx->ob_debug) return VSF_ERR_UNSUPPORTED;  // (vsf_observe_set_debug_images: single-stream)
-  if (ctx->ob.ready && ctx->ob.next_collect != ctx->ob.next_ticket) return VSF_ERR_INVALID_ARG;  // frames in the queue
+  if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
   if (ctx->ob.ready && n_streams != ctx->ob_streams) {  // rebuilt by the next submit: every window and threshold starts over
-    VSF_HIP(hipSetDevice(ctx->device));
-    stop_observe_threads(ctx);
-    sync_all_streams(ctx);
-    free_observe(ctx);
+    const vsf_status st = drop_queue(ctx);
+    if (st != VSF_OK) return st;
   }
   ctx->ob_streams = n_streams;
   return VSF_OK;
@@ -894,15 +713,19 @@ vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream) {
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (!ctx || !out || n < 1) return VSF_ERR_INVALID_ARG;
   const vsf_ctx::Observe& o = ctx->ob;
+  // (the launcher thread may be inside a batch: its counters and buffer sizes are read once it is out, under the queue's lock)
+  std::unique_lock<std::mutex> lk;
+  if (o.queue) lk = o.queue->lock_idle();
+  const ObserveLaunchStats s = o.queue ? o.queue->stats : ObserveLaunchStats();
   // every byte the compressed path owns: 0 until the first compressed frame
   size_t cmp_bytes = o.h_cmp ? vsf_observe_compressed_ring_bytes(o.depth, o.cmp_cap) : 0;
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[17] = {o.stat_frames, o.batches, o.stat_max_batch, o.stat_solo, o.stat_forced, o.stat_slot_waits,
-                         (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, o.stat_launch_ns, o.stat_wait_ns,
-                         o.stat_compressed, o.stat_ingest_commands, (int64_t)cmp_bytes,
-                         o.files.stat_commands, (int64_t)ctx->ob_streams, o.stat_multi};
+  const int64_t v[17] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+                         (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
+                         s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
+                         s.file_commands, (int64_t)ctx->ob_streams, s.multi};
   for (int i = 0; i < n && i < 17; i++) out[i] = v[i];
   return VSF_OK;
 }
@@ -910,11 +733,7 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
 vsf_status vsf_observe_reset(vsf_ctx* ctx) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx) return VSF_ERR_INVALID_ARG;
-  VSF_HIP(hipSetDevice(ctx->device));
-  stop_observe_threads(ctx);  // (frames that still wait are dropped)
-  sync_all_streams(ctx);
-  free_observe(ctx);
-  return VSF_OK;
+  return drop_queue(ctx);
 }
 
 // Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
@@ -930,28 +749,28 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   vsf_ctx::Observe& o = ctx->ob;
   // (re-sizing the window drops nothing that is still in the queue)
   if (o.ready && o.frame_life != frame_life) {
-    if (o.next_collect != o.next_ticket) return VSF_ERR_INVALID_ARG;
+    if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
     stop_observe_threads(ctx);
   }
   vsf_status st = ensure_observe(ctx, frame_life);
   if (st != VSF_OK) return st;
-  if (o.next_ticket - o.next_collect >= o.depth) return VSF_ERR_INVALID_ARG;  // collect the oldest frame first
-  vsf_ctx::ObserveLauncher& L = *o.launcher;
-  const int slot = (int)(o.next_ticket % o.depth);
+  ObserveQueue& q = *o.queue;
+  if (q.next_ticket - q.next_collect >= o.depth) return VSF_ERR_INVALID_ARG;  // collect the oldest frame first
+  const int slot = (int)(q.next_ticket % o.depth);
   {
     // a stream's frames of one batch share one calibration and one best_percent, a batch's frames `bayer`: a frame that
     // brings others than the waiting frame of ITS stream in front of it sends what waits first
-    std::unique_lock<std::mutex> lk(L.mu);
-    if (L.status != VSF_OK) return L.status;
-    if (o.next_launch < o.next_ticket) {
-      bool cut = o.frames[(size_t)((o.next_ticket - 1) % o.depth)].bayer != bayer;
+    std::unique_lock<std::mutex> lk(q.mu);
+    if (q.status != VSF_OK) return q.status;
+    if (q.next_launch < q.next_ticket) {
+      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].bayer != bayer;
       const int64_t mine = o.streams[(size_t)stream].last_ticket;
-      if (!cut && mine >= o.next_launch) {
+      if (!cut && mine >= q.next_launch) {
         const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
         cut = observe_plan_must_cut(w0.calib, w0.best_percent, *calib, best_percent);
       }
       if (cut) {
-        st = caller_pump(ctx, lk, true);
+        st = q.caller_pump(lk, true);
         if (st != VSF_OK) return st;
       }
     }
@@ -962,7 +781,7 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     // the stereo lines' colours, cv::Scalar(rand() % 255, rand() % 255, rand() % 255) (cc:95) in the reference's order --
     // GCC evaluates the three calls right to left: the first is channel 2 -- drawn ahead: enough for every frame in the queue
     // (a frame takes at most max_keypoints); the device takes them in frame order from its cursor
-    const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (o.next_ticket + 1 - o.next_collect) * K;
+    const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + 1 - q.next_collect) * K;
     for (; o.col_generated < want; o.col_generated++) {
       const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
       o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
@@ -979,15 +798,15 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     std::memcpy(h_cmp, left, nbytes[0]);
     std::memcpy(h_cmp + o.cmp_slot, right, nbytes[1]);
   } else {
-  uint8_t* h_img = o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
-  const vsf_ctx::ObserveCopyHelper::Job jr{h_img + ctx->st_img_stride, right, ctx->st_img_pitch, stride, (size_t)w, h};
-  // frames are streaming in (the previous one is still in the queue): the helper thread takes the right image
-  const bool helped = o.copy_helper && o.next_ticket > o.next_collect && o.copy_helper->post(jr);
-  stage_image(h_img, ctx->st_img_pitch, left, stride, (size_t)w, h);
-  if (helped)
-    o.copy_helper->wait();
-  else
-    stage_image(jr.dst, jr.dst_pitch, jr.src, jr.src_pitch, jr.width, jr.rows);
+    uint8_t* h_img = o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
+    const ObserveCopyHelper::Job jr{h_img + ctx->st_img_stride, right, ctx->st_img_pitch, stride, (size_t)w, h};
+    // frames are streaming in (the previous one is still in the queue): the helper thread takes the right image
+    const bool helped = o.copy_helper && q.next_ticket > q.next_collect && o.copy_helper->post(jr);
+    stage_image(h_img, ctx->st_img_pitch, left, stride, (size_t)w, h);
+    if (helped)
+      o.copy_helper->wait();
+    else
+      stage_image(jr.dst, jr.dst_pitch, jr.src, jr.src_pitch, jr.width, jr.rows);
   }
   o.stat_copy_ns += now_ns() - t_copy;
   for (int k = 0; k < 2; k++) {
@@ -1002,18 +821,8 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   fr.stream = stream;
   fr.k = mine.frames++;
   mine.uncollected++;
-  std::unique_lock<std::mutex> lk(L.mu);
-  const bool was_empty = o.next_launch == o.next_ticket;
-  mine.last_ticket = o.next_ticket;
-  *ticket = o.next_ticket++;
-  o.last_submit_ns = now_ns();
-  if (L.has_thread) {
-    // the thread launches: it sleeps while nothing waits and polls while something does.  (A caller that collects right
-    // away launches the frame itself there -- waking the thread would cost more than the launch.)
-    if (was_empty) L.cv_thread.notify_one();
-    return VSF_OK;
-  }
-  return caller_pump(ctx, lk, false);
+  mine.last_ticket = q.next_ticket;
+  return q.submit(ticket);
 }
 
 vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
@@ -1066,7 +875,7 @@ vsf_status vsf_observe_set_compressed_cap(vsf_ctx* ctx, size_t cap_per_image) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
   if (!ctx || (cap_per_image != 0 && vsf_observe_compressed_slot_bytes(cap_per_image) == 0)) return VSF_ERR_INVALID_ARG;
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.ready && o.next_collect != o.next_ticket) return VSF_ERR_INVALID_ARG;  // frames in the queue
+  if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
   if (o.h_cmp) {  // (every frame has been collected: no upload reads the ring; a pinned buffer is retired, not freed)
     ctx->retired_host.emplace_back(o.h_cmp.release());
     o.cmp_cap = o.cmp_slot = 0;
@@ -1081,39 +890,25 @@ static vsf_status observe_wait(vsf_ctx* ctx, int64_t ticket, const uint8_t** vie
   vsf_ctx::Observe& o = ctx->ob;
   *bytes = 0;
   // frames leave in the order they entered (the host's bookkeeping is sequential)
-  if (!o.ready || ticket < 0 || ticket != o.next_collect || ticket >= o.next_ticket) return VSF_ERR_INVALID_ARG;
+  if (!o.ready || ticket < 0 || ticket != o.queue->next_collect || ticket >= o.queue->next_ticket) return VSF_ERR_INVALID_ARG;
   VSF_HIP(hipSetDevice(ctx->device));
-  vsf_ctx::ObserveLauncher& L = *o.launcher;
   const int slot = (int)(ticket % o.depth);
-  const vsf_ctx::ObserveBatch* b = nullptr;
-  {
-    std::unique_lock<std::mutex> lk(L.mu);
-    if (ticket >= o.next_launch) {  // it still waits in staging: everything that waits leaves now
-      const vsf_status st = caller_pump(ctx, lk, true);
-      if (st != VSF_OK) return st;
-    }
-    if (ticket >= o.next_launch) return L.status != VSF_OK ? L.status : VSF_ERR_HIP;
-    b = &o.batch[o.frames[(size_t)slot].batch];
-  }
+  vsf_status st = o.queue->release(ticket);  // (if it still waits in staging, everything that waits leaves now)
+  if (st != VSF_OK) return st;
+  const vsf_ctx::ObserveBatch& b = o.batch[o.frames[(size_t)slot].batch];
   {
     const int64_t t_wait = now_ns();
-    VSF_HIP(hipEventSynchronize(b->ev_done));
+    VSF_HIP(hipEventSynchronize(b.ev_done));
     o.stat_wait_ns += now_ns() - t_wait;
   }
   const uint8_t* res = o.h_out + (size_t)slot * o.out_stride;
   const uint32_t* hdr = reinterpret_cast<const uint32_t*>(res);
-  vsf_status st = VSF_OK;
-  {
-    std::unique_lock<std::mutex> lk(L.mu);
-    o.next_collect = ticket + 1;
-    o.streams[(size_t)o.frames[(size_t)slot].stream].uncollected--;
-    if (o.debug) o.col_retired += hdr[15];  // the colours this frame's stereo image took
-    if (!L.has_thread) st = caller_pump(ctx, lk, false);  // (the GPU may have room again)
-  }
-  if (hdr[0] != 0x4F465356u) return VSF_ERR_HIP;
+  const bool whole = hdr[0] == 0x4F465356u;
+  o.streams[(size_t)o.frames[(size_t)slot].stream].uncollected--;
+  if (o.debug) o.col_retired += hdr[15];  // the colours this frame's stereo image took
+  st = o.queue->collected(ticket, whole ? (int)hdr[2] : -1);  // (hdr[2]: the filtered frame's rows)
+  if (!whole) return VSF_ERR_HIP;
   const_cast<uint32_t*>(hdr)[0] = 0;  // (the slot's next frame must write its own)
-  // the filtered frames' size, for the matcher's launch choice: the largest of the last few frames with room to grow
-  o.rows_hint = std::max((int)hdr[2] * 2 + 64, o.rows_hint - o.rows_hint / 8);
   *view = res;
   *bytes = hdr[3];
   if (st != VSF_OK) return st;
@@ -1127,11 +922,11 @@ vsf_status vsf_observe_poll(vsf_ctx* ctx, int64_t ticket, int* ready) {
   if (!ctx || !ready) return VSF_ERR_INVALID_ARG;
   *ready = 0;
   vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready || ticket < o.next_collect || ticket >= o.next_ticket) return VSF_ERR_INVALID_ARG;
+  if (!o.ready || ticket < o.queue->next_collect || ticket >= o.queue->next_ticket) return VSF_ERR_INVALID_ARG;
   const vsf_ctx::ObserveBatch* b = nullptr;
   {
-    std::lock_guard<std::mutex> g(o.launcher->mu);
-    if (ticket >= o.next_launch) return o.launcher->status;  // it still waits in staging (nothing is forced)
+    std::lock_guard<std::mutex> g(o.queue->mu);
+    if (ticket >= o.queue->next_launch) return o.queue->status;  // it still waits in staging (nothing is forced)
     b = &o.batch[o.frames[(size_t)(ticket % o.depth)].batch];
   }
   VSF_HIP(hipSetDevice(ctx->device));
