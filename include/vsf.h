@@ -179,7 +179,14 @@ typedef enum {
                                  * even when that fills less than three quarters of the chip; 0: never */
   VSF_OPT_OBSERVE_COPY_THREAD = 10, /* 1 (default): while frames stream into an ObserveImage queue of depth >= 4 a second host thread
                                      * takes the right image's staging copy; 0: the caller copies both.  Read when the queue is built */
-  VSF_OPT_COUNT = 11
+  VSF_OPT_FAST_EARLY_LEVELS = 11, /* pipelined calls (vsf_set_pipeline): n > 0 = FAST on the full-width cells of pyramid levels
+                                   * 0 .. n - 1 is a launch of its own that starts from inside the call's pyramid chain, as soon as
+                                   * level n - 1 exists, beside the previous call's selection and descriptors; the rest of FAST
+                                   * follows the pyramid as before.  0: one FAST pass; default 12.  Clamped to the levels that have such a
+                                   * cell; read by every call, so it may change between two calls */
+  VSF_OPT_FAST_EARLY_FORM = 12,   /* that early launch as a grid of one workgroup per four cells (0) or as one resident
+                                   * workgroup per CU with 1 .. 3 waves per SIMD; default 0 */
+  VSF_OPT_COUNT = 13
 } vsf_option;
 vsf_status vsf_set_option(vsf_ctx* ctx, int option, int value);
 vsf_status vsf_get_option(const vsf_ctx* ctx, int option, int* value);

@@ -1,0 +1,88 @@
+"""Where FAST's list of full cells is cut for VSF_OPT_FAST_EARLY_LEVELS (csrc/vsf_fast_split.h, one plain function the host
+and this test share), on the CPU: tests/cpp/test_fast_split.cc checks it for every number of early levels against the
+work lists the library itself builds (vsf_debug_fast_work, no device needed) for 640x480, 1920x1080 and the 352x160 of
+tests/test_gpu_fast_split.py -- the head holds exactly the full-width cells of the early levels, n_early(0) == 0, n_early
+is monotone -- and once more as a stand-alone program under AddressSanitizer / UBSan."""
+import ctypes as C
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+SRC = ROOT / "tests" / "cpp" / "test_fast_split.cc"
+SHAPES = [(640, 480), (1920, 1080), (352, 160), (160, 120)]
+
+
+@pytest.fixture(scope="module")
+def capi():
+    sys.path.insert(0, str(ROOT))
+    import __graft_entry__ as g
+    from vision_slam_frontend_amd import capi
+    if not capi.LIB_PATH.exists():
+        g.build()
+    return capi
+
+
+@pytest.fixture(scope="module")
+def lists(capi, tmp_path_factory):
+    lines = [str(len(SHAPES))]
+    for w, h in SHAPES:
+        p = capi.default_params(w, h)
+        cap = 1 << 20
+        words = np.zeros(cap, np.uint32)
+        levels = np.zeros((64, 10), np.int32)
+        nw, nf = C.c_int(), C.c_int()
+        st = capi.lib().vsf_debug_fast_work(C.byref(p), 1, 1, words.ctypes.data, cap, C.byref(nw), C.byref(nf),
+                                            levels.ctypes.data, 64)
+        assert st == capi.VSF_OK
+        lines.append("%d %d %d %d" % (w, h, p.nlevels, nf.value))
+        for lv in levels[:p.nlevels]:  # w, h, x_lo, x_hi, y_lo, y_hi, fast_a0, nbands, nstrips, unit0
+            lines.append(" ".join(str(int(v)) for v in lv[2:9]))
+        lines.append(" ".join(str(int(v)) for v in words[:nf.value]))
+    path = tmp_path_factory.mktemp("fast_split") / "work_lists.txt"
+    path.write_text("\n".join(lines) + "\n")
+    return path
+
+
+def test_shapes_are_what_the_gpu_test_needs(capi):
+    """640x480: 235 full cells in levels 0..19, 102 of them in levels 0..3; 352x160: three levels with a full cell and two
+    strips; 160x120: none."""
+    def full_by_level(w, h):
+        p = capi.default_params(w, h)
+        words = np.zeros(1 << 20, np.uint32)
+        levels = np.zeros((64, 10), np.int32)
+        nw, nf = C.c_int(), C.c_int()
+        assert capi.lib().vsf_debug_fast_work(C.byref(p), 1, 1, words.ctypes.data, 1 << 20, C.byref(nw), C.byref(nf),
+                                              levels.ctypes.data, 64) == capi.VSF_OK
+        out = {}
+        for wd in words[:nf.value]:
+            l, b = int(wd >> 24), int((wd >> 16) & 0xFF)
+            _, _, x_lo, x_hi, _, _, a0 = (int(v) for v in levels[l][:7])
+            if (min(x_hi, a0 + 248 * (b + 1)) - (a0 + 248 * b) + 3) // 4 + 2 >= 64:
+                out[l] = out.get(l, 0) + 1
+        return out, levels
+    vga, _ = full_by_level(640, 480)
+    assert sum(vga.values()) == 235 and max(vga) == 19 and sum(v for l, v in vga.items() if l < 4) == 102
+    small, lv = full_by_level(352, 160)
+    assert len(small) >= 3 and all(int(lv[l][8]) >= 2 for l in small)
+    assert full_by_level(160, 120)[0] == {}
+
+
+def test_cut_for_every_number_of_early_levels(lists, tmp_path):
+    exe = tmp_path / "test_fast_split"
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-o", str(exe), str(SRC)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    p = subprocess.run([str(exe), str(lists)], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and p.stdout.startswith("ok %d shapes" % len(SHAPES)), (p.stdout[-2000:], p.stderr[-2000:])
+
+
+def test_cut_under_sanitizers(lists, tmp_path):
+    exe = tmp_path / "test_fast_split_san"
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
+                        str(SRC)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    p = subprocess.run([str(exe), str(lists)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and p.stdout.startswith("ok "), (p.stdout[-2000:], p.stderr[-2000:])

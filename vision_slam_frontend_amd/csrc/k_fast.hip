@@ -29,6 +29,7 @@
 // Output per unit: a candidate segment in unit-local raster order + the start offset of every row, which
 // vsf_gather.h merges into the level's global raster order.
 #include "vsf_gather.h"
+#include <algorithm>
 #include <cstdlib>
 
 #include "vsf_internal.h"
@@ -480,21 +481,23 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
   }
 }
 
+// (`first`: the launch walks work items [first, first + nwork) -- the list of full cells may be cut in two,
+// vsf_fast_split.h; 0 for the packed items)
 template <bool PACK, bool NMS>
-__global__ __launch_bounds__(256) void fast_march_kernel(FastArgs a, int nwork) {
+__global__ __launch_bounds__(256) void fast_march_kernel(FastArgs a, int first, int nwork) {
   const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (item >= nwork) return;  // wave-uniform
-  fast_march_body<PACK, NMS>(a, item, blockIdx.y);
+  fast_march_body<PACK, NMS>(a, first + item, blockIdx.y);
 }
 
 // Full cells and the packed items in ONE launch, for batches that leave the chip nearly empty: there a launch lasts as
 // long as one cell's march, and two launches in a row last twice that.
 template <bool NMS>
-__global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int nfull, int npack) {
+__global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int first, int nfull, int npack) {
   const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (item >= nfull + npack) return;  // wave-uniform
   if (item < nfull)
-    fast_march_body<false, NMS>(a, item, blockIdx.y);
+    fast_march_body<false, NMS>(a, first + item, blockIdx.y);
   else
     fast_march_body<true, NMS>(a, item - nfull, blockIdx.y);
 }
@@ -506,7 +509,8 @@ __global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int nf
 // SIMD's registers to the kernel beside it.  Alone, FAST reaches 93 % of the vector ALU's issue rate with five waves per
 // SIMD, the same with four, 92 % of that with three and 76 % with two (occupancy sweep, NOTES.md section 6).
 template <bool PACK, bool NMS>
-__global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, int nwork, int nimages, uint32_t* next_cell) {
+__global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, int first, int nwork, int nimages,
+                                                                  uint32_t* next_cell) {
   // cells are handed out through a counter (zeroed by the launcher): a wave slowed down by its neighbours takes fewer
   const int total = nwork * nimages;
   while (true) {  // (wave-uniform; the counter passes `total` for every wave)
@@ -525,7 +529,7 @@ __global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, i
     const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
     if (u >= (uint32_t)total) break;
     const int image = (int)u / nwork, cell = (int)u - image * nwork;
-    fast_march_body<PACK, NMS>(a, cell, image);
+    fast_march_body<PACK, NMS>(a, first + cell, image);
   }
 }
 
@@ -565,7 +569,12 @@ __global__ __launch_bounds__(256) void fast_emit_kernel(const VsfLevel* __restri
 }  // namespace
 
 void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int threshold, int nms, hipStream_t s,
-                     int resident_waves_per_simd, int n_cus, uint32_t* d_cell_counters) {
+                     int resident_waves_per_simd, int n_cus, uint32_t* d_cell_counters, int part, int n_early) {
+  // the work of this launch: full cells [f0, f0 + nf) and np packed items
+  n_early = std::min(std::max(n_early, 0), g.nwork_full);
+  const int f0 = part == VSF_FAST_LATE ? n_early : 0;
+  const int nf = part == VSF_FAST_EARLY ? n_early : g.nwork_full - f0;
+  const int np = part == VSF_FAST_EARLY ? 0 : g.nwork_pack;
   FastArgs a;
   a.levels = d.levels;
   a.units = d.units;
@@ -582,32 +591,32 @@ void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int
   a.threshold = threshold;
   a.nms = nms;
   if (resident_waves_per_simd > 0 && resident_waves_per_simd <= 4 && nms && d_cell_counters) {
-    vsf_note(hipMemsetAsync(d_cell_counters, 0, 2 * sizeof(uint32_t), s));
+    // (an early part runs on another stream than the late part of the call before it: a counter of its own)
+    uint32_t* cnt = part == VSF_FAST_EARLY ? d_cell_counters + 2 : d_cell_counters;
+    vsf_note(hipMemsetAsync(cnt, 0, (part == VSF_FAST_EARLY ? 1 : 2) * sizeof(uint32_t), s));
     const dim3 block(256 * resident_waves_per_simd);
-    if (g.nwork_full > 0)
-      hipLaunchKernelGGL((fast_march_resident_kernel<false, true>), dim3(n_cus), block, 0, s, a, g.nwork_full, im.n,
-                         d_cell_counters);
-    if (g.nwork_pack > 0)
-      hipLaunchKernelGGL((fast_march_resident_kernel<true, true>), dim3(n_cus), block, 0, s, a, g.nwork_pack, im.n,
-                         d_cell_counters + 1);
+    if (nf > 0)
+      hipLaunchKernelGGL((fast_march_resident_kernel<false, true>), dim3(n_cus), block, 0, s, a, f0, nf, im.n, cnt);
+    if (np > 0)
+      hipLaunchKernelGGL((fast_march_resident_kernel<true, true>), dim3(n_cus), block, 0, s, a, 0, np, im.n, cnt + 1);
     return;
   }
-  const dim3 gf((g.nwork_full + 3) / 4, im.n), gp((g.nwork_pack + 3) / 4, im.n);
+  const dim3 gf((nf + 3) / 4, im.n), gp((np + 3) / 4, im.n);
   const int both_max = d.tune ? d.tune->fast_both_max : 16;
-  if (im.n <= both_max && g.nwork_full > 0 && g.nwork_pack > 0) {
-    const dim3 gb((g.nwork_full + g.nwork_pack + 3) / 4, im.n);
+  if (im.n <= both_max && nf > 0 && np > 0) {
+    const dim3 gb((nf + np + 3) / 4, im.n);
     if (nms)
-      hipLaunchKernelGGL((fast_march_both_kernel<true>), gb, dim3(256), 0, s, a, g.nwork_full, g.nwork_pack);
+      hipLaunchKernelGGL((fast_march_both_kernel<true>), gb, dim3(256), 0, s, a, f0, nf, np);
     else
-      hipLaunchKernelGGL((fast_march_both_kernel<false>), gb, dim3(256), 0, s, a, g.nwork_full, g.nwork_pack);
+      hipLaunchKernelGGL((fast_march_both_kernel<false>), gb, dim3(256), 0, s, a, f0, nf, np);
     return;
   }
   if (nms) {
-    if (g.nwork_full > 0) hipLaunchKernelGGL((fast_march_kernel<false, true>), gf, dim3(256), 0, s, a, g.nwork_full);
-    if (g.nwork_pack > 0) hipLaunchKernelGGL((fast_march_kernel<true, true>), gp, dim3(256), 0, s, a, g.nwork_pack);
+    if (nf > 0) hipLaunchKernelGGL((fast_march_kernel<false, true>), gf, dim3(256), 0, s, a, f0, nf);
+    if (np > 0) hipLaunchKernelGGL((fast_march_kernel<true, true>), gp, dim3(256), 0, s, a, 0, np);
   } else {
-    if (g.nwork_full > 0) hipLaunchKernelGGL((fast_march_kernel<false, false>), gf, dim3(256), 0, s, a, g.nwork_full);
-    if (g.nwork_pack > 0) hipLaunchKernelGGL((fast_march_kernel<true, false>), gp, dim3(256), 0, s, a, g.nwork_pack);
+    if (nf > 0) hipLaunchKernelGGL((fast_march_kernel<false, false>), gf, dim3(256), 0, s, a, f0, nf);
+    if (np > 0) hipLaunchKernelGGL((fast_march_kernel<true, false>), gp, dim3(256), 0, s, a, 0, np);
   }
 }
 

@@ -652,10 +652,13 @@ int choose_l_tail(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, c
 // dependent launches is issued once per half of the batch, on two streams, interleaved: the small levels are bound by the
 // latency of a launch's dependency chain (~5 us each), not by throughput, and two chains run in the time of one.
 // (two chains: with four the host's launch rate, ~4 us per launch, becomes the limit: 0.56 -> 0.94 ms measured)
+// `hook` (one chain only): called behind the launch of level hook->level, in front of the first launch for level 0.
 void launch_level_chains(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, const VsfImages& im, hipStream_t s,
-                         const VsfSideStream* side, int l_tail) {
+                         const VsfSideStream* side, int l_tail, const VsfPyramidHook* hook) {
   const PyramidArgs p = pyramid_args(d, g, im, 1, l_tail);
   const int nchains = (side && side->n > 0 && im.n >= 2) ? 2 : 1;
+  if (nchains > 1) hook = nullptr;  // (a level is complete on two streams then)
+  if (hook && hook->level <= 0) hook->fn(hook->arg, s);
   hipStream_t st[VSF_SIDE_STREAMS + 1] = {s};
   for (int c = 1; c < nchains; c++) st[c] = side->stream[c - 1];
   if (nchains > 1) {
@@ -693,6 +696,7 @@ void launch_level_chains(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_le
       else
         hipLaunchKernelGGL(resize_march_kernel<4>, grid, dim3(256), 0, st[c], a);
     }
+    if (hook && hook->level == l) hook->fn(hook->arg, s);
   }
   for (int c = 1; c < nchains; c++) {
     vsf_note(hipEventRecord(side->join[c - 1], st[c]));
@@ -709,12 +713,14 @@ hipError_t vsf_prepare_pyramid_kernels(int lds_limit) {
 }
 
 void vsf_launch_pyramid(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, const VsfImages& im,
-                        hipStream_t s, const VsfSideStream* side) {
+                        hipStream_t s, const VsfSideStream* side, const VsfPyramidHook* hook) {
   const int few_max = d.tune ? d.tune->pyramid_few : 16;
   const bool few = side && im.n <= few_max;
   if (few && g.nlevels > 1 && launch_slab_chains(d, g, h_levels, im, s)) return;
+  // (a hook comes with side == NULL: neither the slab chains above nor the image-major tail below are taken, every level
+  // up to the last is a launch of the one chain)
   const int l_tail = choose_l_tail(d, g, h_levels, im, side, few);
-  launch_level_chains(d, g, h_levels, im, s, side, l_tail);
+  launch_level_chains(d, g, h_levels, im, s, side, l_tail, hook);
   if (l_tail < g.nlevels)
     hipLaunchKernelGGL(pyramid_image_kernel, dim3(im.n), dim3(1024), 0, s, pyramid_args(d, g, im, l_tail, g.nlevels));
 }

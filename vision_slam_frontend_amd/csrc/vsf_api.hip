@@ -186,6 +186,24 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
                 uint8_t* d_desc, int32_t* d_counts, bool inputs_complete, const VsfSideStream* own_side, int32_t* status,
                 int status_stride) {
   const VsfGeom& g = ctx->orb.g;
+  const bool pipe = ctx->pipeline && inputs_complete && ctx->lanes == 1 && st == ctx->stream && i0 == 0;
+  // VSF_OPT_FAST_EARLY_LEVELS (read here, per call): the full cells of levels < early_levels -- the head [0, n_early) of the
+  // work list, vsf_fast_split.h -- are scored by a launch of their own on blur_stream, which starts as soon as the chain
+  // below has produced level early_levels - 1 and so runs beside the PREVIOUS call's selection and descriptors, whose
+  // kernels wait on latency and leave vector-ALU issue slots unused.  Pipelined calls only; never the tune call.
+  const int early_levels = pipe && ctx->cand_alt && ctx->blur_stream && ctx->fast_force < 0
+                               ? std::min(ctx->tuning.fast_early_levels, g.fast_split_levels)
+                               : 0;
+  const int n_early = early_levels > 0 ? vsf_fast_n_early(ctx->orb.levels.data(), g.nlevels, early_levels) : 0;
+  // Such a call takes the other pair of candidate buffers: its early part writes them while the previous call's selection
+  // may still read its own.  (A call without an early part stays on the pair the last call used: its FAST follows that
+  // call's selection on this stream.  Every pipelined call records the release of the pair it read, so the option may change
+  // from call to call.)
+  if (n_early > 0) {
+    ctx->cand_flip ^= 1;
+    ctx->dorb.d.cand = ctx->cand_flip ? ctx->cand_alt.get() : ctx->dorb.cand.get();
+    ctx->dorb.d.rowstart = ctx->cand_flip ? ctx->rowstart_alt.get() : ctx->dorb.rowstart.get();
+  }
   VsfDev d = shifted(ctx->dorb.d, g, i0);
   if (status) {
     d.status = status;
@@ -195,7 +213,6 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
   im.base += (size_t)i0 * im.image_stride;
   im.n = n;
   const size_t K = (size_t)ctx->p.max_keypoints;
-  const bool pipe = ctx->pipeline && inputs_complete && ctx->lanes == 1 && st == ctx->stream && i0 == 0;
   if (pipe) {
     // The pyramid depends on the input images only.  The caller promised they are complete (vsf_set_pipeline), so the
     // chain goes onto the pipe streams WITHOUT being ordered after this stream's earlier work and overlaps the previous
@@ -214,10 +231,39 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
     if (ctx->ingest_done_valid) vsf_note(hipStreamWaitEvent(ps, ctx->ev_ingest_done, 0));
     // ... nor before the caller's own producer has finished them (vsf_set_input_event)
     if (ctx->input_event) vsf_note(hipStreamWaitEvent(ps, ctx->input_event, 0));
+    struct Early {
+      vsf_ctx* ctx;
+      const VsfDev* d;
+      const VsfImages* im;
+      int n_early;
+      bool fired;
+    } early{ctx, &d, &im, n_early, false};
+    // behind the launch of level early_levels - 1 (ps has waited for the inputs by then: level 0 needs no more than that)
+    const VsfPyramidHook hook{early_levels - 1,
+                              [](void* arg, hipStream_t chain) {
+                                Early& e = *static_cast<Early*>(arg);
+                                vsf_ctx* c = e.ctx;
+                                hipStream_t es = c->blur_stream;
+                                e.fired = true;
+                                vsf_note(hipEventRecord(c->ev_early_go, chain));
+                                vsf_note(hipStreamWaitEvent(es, c->ev_early_go, 0));
+                                // ... and not before the selection that last read this pair of buffers is through
+                                if (c->cand_free_valid[c->cand_flip])
+                                  vsf_note(hipStreamWaitEvent(es, c->ev_cand_free[c->cand_flip], 0));
+                                {
+                                  // (0 launches: the step's launch count stays what the one-pass FAST reports)
+                                  StageTimer t(c, es, VSF_STAGE_FAST, 0);
+                                  vsf_launch_fast(*e.d, c->orb.g, *e.im, c->p.fast_threshold, 1, es, c->tuning.fast_early_form,
+                                                  c->n_cus, c->fast_cells, VSF_FAST_EARLY, e.n_early);
+                                }
+                                vsf_note(hipEventRecord(c->ev_early_done, es));
+                              },
+                              &early};
     {
       StageTimer t(ctx, ps, VSF_STAGE_PYRAMID, g.nlevels - 1);
-      vsf_launch_pyramid(d, g, ctx->orb.levels.data(), im, ps, nullptr);
+      vsf_launch_pyramid(d, g, ctx->orb.levels.data(), im, ps, nullptr, n_early > 0 ? &hook : nullptr);
     }
+    if (n_early > 0 && !early.fired) hook.fn(&early, ps);  // (no launch of the chain made that level: behind all of it)
     vsf_note(hipEventRecord(ctx->ev_pyr_done, ps));
     vsf_note(hipStreamWaitEvent(st, ctx->ev_pyr_done, 0));
   } else {
@@ -237,6 +283,11 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
   // forked from INSIDE the pyramid's launch chain as soon as their levels exist (the chain's dependent launches stretch from
   // 1.28 to 1.8-2.2 ms beside the blur's memory traffic, 7.37-7.46 ms per step against 7.31); the first 3 / 6 / 10 / 16
   // levels blurred in line in front of FAST and only the rest beside it (7.25-7.36: noise).
+  // Measured and KEPT (NOTES.md, "FAST: the wide levels start beside the previous call"): FAST on the full cells of the
+  // first 12 levels as a grid launch from inside the next call's pyramid chain (5.81-5.94 -> 5.63-5.73 ms per 256-frame
+  // step).  Left out: fewer levels (1 / 2 / 4 / 8: 5.81 / 5.84 / 5.73 / 5.66 ms) or all 20 (5.67); that early part as a
+  // resident launch of one, two or three waves per SIMD (5.72-5.95: it does not finish before the pyramid does, and the
+  // late part waits for it).
   const bool beside_ok = ctx->blur_overlap && im.n >= 32 && ctx->blur_stream;
   // With the blur beside it FAST can run as ONE resident workgroup per CU (k_fast.hip): three waves per SIMD keep 92 % of
   // its own rate and leave the other 224 of a SIMD's 512 registers -- which a grid of one workgroup per four cells fills
@@ -273,10 +324,12 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
     launch_blur(ctx->blur_stream);
     vsf_note(hipEventRecord(ctx->ev_blur_done, ctx->blur_stream));
   };
-  if (blur_beside) fork_blur();
+  if (blur_beside) fork_blur();  // (on blur_stream behind the early FAST part: stream order)
+  if (n_early > 0) vsf_note(hipStreamWaitEvent(st, ctx->ev_early_done, 0));
   {
     StageTimer t(ctx, st, VSF_STAGE_FAST, 1);
-    vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, st, blur_beside ? resident : 0, ctx->n_cus, ctx->fast_cells);
+    vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, st, blur_beside ? resident : 0, ctx->n_cus, ctx->fast_cells,
+                    n_early > 0 ? VSF_FAST_LATE : VSF_FAST_ALL, n_early);
   }
   if (pipe) {
     vsf_note(hipEventRecord(ctx->ev_fast_done, st));
@@ -285,6 +338,10 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
   {
     StageTimer t(ctx, st, VSF_STAGE_SELECT, 1);
     vsf_launch_select(d, g, ctx->orb.levels.data(), im, st);
+  }
+  if (pipe && ctx->cand_alt) {  // the last reader of this pair of candidate buffers is queued
+    vsf_note(hipEventRecord(ctx->ev_cand_free[ctx->cand_flip], st));
+    ctx->cand_free_valid[ctx->cand_flip] = true;
   }
   if (blur_beside)
     vsf_note(hipStreamWaitEvent(st, ctx->ev_blur_done, 0));
@@ -360,6 +417,16 @@ vsf_status extract_async(vsf_ctx* ctx, const VsfImages& im, vsf_keypoint* d_kp, 
 vsf_status ensure_pipeline_buffers(vsf_ctx* ctx) {
   if (ctx->pyr_alt) return VSF_OK;
   VSF_HIP(ctx->pyr_alt.alloc((size_t)ctx->p.max_images * ctx->orb.g.pyr_bytes));
+  {
+    const size_t n = (size_t)ctx->p.max_images;
+    const size_t rs_bytes = n * (size_t)std::max(ctx->orb.g.nunits, 1) * VSF_FAST_RS_STRIDE * sizeof(uint16_t);
+    VSF_HIP(ctx->cand_alt.alloc(n * ctx->orb.g.cand_entries * sizeof(uint32_t)));
+    VSF_HIP(ctx->rowstart_alt.alloc(rs_bytes));
+    VSF_HIP(hipMemset(ctx->rowstart_alt, 0, rs_bytes));
+    for (Event& e : ctx->ev_cand_free) VSF_HIP(e.alloc(hipEventDisableTiming));
+    VSF_HIP(ctx->ev_early_go.alloc(hipEventDisableTiming));
+    VSF_HIP(ctx->ev_early_done.alloc(hipEventDisableTiming));
+  }
   VSF_HIP(ctx->ev_pyr_done.alloc(hipEventDisableTiming));
   VSF_HIP(ctx->ev_fast_done.alloc(hipEventDisableTiming));
   for (Event& e : ctx->ev_pyr_free) VSF_HIP(e.alloc(hipEventDisableTiming));
@@ -503,7 +570,7 @@ vsf_status vsf_create(const vsf_params* p, int device, vsf_ctx** out) {
       ctx->tuning.jpeg_serial = 1;
     }
   }
-  if (ctx->fast_cells.alloc(2 * sizeof(uint32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
+  if (ctx->fast_cells.alloc(3 * sizeof(uint32_t)) != hipSuccess) return fail(VSF_ERR_HIP);
   if (ctx->h_status.alloc(sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return fail(VSF_ERR_HIP);
   vsf_status st = alloc_devset(ctx, ctx->orb, &ctx->dorb, true, ctx->p.max_images);
   if (st != VSF_OK) return fail(st);
@@ -598,6 +665,14 @@ vsf_status vsf_set_option(vsf_ctx* ctx, int option, int value) {
     case VSF_OPT_SELECT_WIDE: t.select_wide = value != 0; break;
     case VSF_OPT_SELECT_BIG_CLASS: t.select_big_class = value != 0; break;
     case VSF_OPT_PIPE_AFTER_FAST: t.pipe_after_fast = value != 0; break;
+    case VSF_OPT_FAST_EARLY_LEVELS:  // (read by each call: clamped there to the levels that have a full cell)
+      if (value < 0 || value > VSF_MAX_LEVELS) return VSF_ERR_INVALID_ARG;
+      t.fast_early_levels = value;
+      break;
+    case VSF_OPT_FAST_EARLY_FORM:
+      if (value < 0 || value > 3) return VSF_ERR_INVALID_ARG;
+      t.fast_early_form = value;
+      break;
     case VSF_OPT_OBSERVE_THREAD: t.observe_thread = value != 0; break;  // (read when the queue is built)
     case VSF_OPT_OBSERVE_COPY_THREAD: t.observe_copy_thread = value != 0; break;
     case VSF_OPT_PIPE_PRIORITY:
@@ -634,6 +709,8 @@ vsf_status vsf_get_option(const vsf_ctx* ctx, int option, int* value) {
     case VSF_OPT_SELECT_WIDE: *value = t.select_wide; break;
     case VSF_OPT_SELECT_BIG_CLASS: *value = t.select_big_class; break;
     case VSF_OPT_PIPE_AFTER_FAST: *value = t.pipe_after_fast; break;
+    case VSF_OPT_FAST_EARLY_LEVELS: *value = t.fast_early_levels; break;
+    case VSF_OPT_FAST_EARLY_FORM: *value = t.fast_early_form; break;
     case VSF_OPT_OBSERVE_THREAD: *value = t.observe_thread; break;
     case VSF_OPT_OBSERVE_COPY_THREAD: *value = t.observe_copy_thread; break;
     case VSF_OPT_PIPE_PRIORITY: *value = t.pipe_priority; break;
@@ -669,6 +746,7 @@ vsf_status vsf_set_pipeline(vsf_ctx* ctx, int on) {
   }
   ctx->pipeline = on != 0;
   ctx->pyr_free_valid[0] = ctx->pyr_free_valid[1] = false;
+  ctx->cand_free_valid[0] = ctx->cand_free_valid[1] = false;
   ctx->fast_done_valid = false;
   return VSF_OK;
 }

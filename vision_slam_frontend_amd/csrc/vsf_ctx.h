@@ -83,6 +83,13 @@ struct vsf_ctx {
   int pyr_flip = 0;
   vsfi::Event ev_pyr_done, ev_pyr_free[2], ev_fast_done;
   bool pyr_free_valid[2] = {false, false}, fast_done_valid = false;
+  // ... and FAST on the full cells of its first levels (VSF_OPT_FAST_EARLY_LEVELS) starts from inside that chain, on
+  // blur_stream: it writes the candidate buffers while call k's selection still reads its own, so a call with an early
+  // part takes the other of two pairs (cand_flip: the pair dorb.d.cand / .rowstart point at -- what the LAST call used, and
+  // what every other path and the debug hooks use).  ev_cand_free[i]: behind the pipelined selection that last read pair i.
+  int cand_flip = 0;
+  vsfi::Event ev_cand_free[2], ev_early_go, ev_early_done;
+  bool cand_free_valid[2] = {false, false};
   // A producer the library owns (the Bayer ingest) records this on the context's stream; a pipelined pyramid, which is
   // NOT ordered after that stream's earlier work, waits for it.
   vsfi::Event ev_ingest_done;
@@ -218,13 +225,15 @@ struct vsf_ctx {
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----
   vsfi::DevBuf<uint8_t> pyr_alt;  // the other pyramid buffer of cross-call pipelining
+  vsfi::DevBuf<uint32_t> cand_alt;      // ... and the other pair of FAST's candidate segments and row-start tables
+  vsfi::DevBuf<uint16_t> rowstart_alt;  //     (pair 0 is dorb.cand / dorb.rowstart)
   vsfi::Geometry orb, fast;
   vsfi::DevSet dorb, dfast;
   // Status words (bit 0: capacity overflow, bit 1: a JPEG stream broke off): word 0 belongs to the context's own stream
   // (batched and host-pointer calls, vsf_sync), words 1..6 to the frames that may be in flight (vsf_observe_submit) --
   // a frame's kernels run on its slot's stream beside another frame's, so each frame sets, copies and clears its own word.
   vsfi::DevBuf<int32_t> d_status;     // [1 + VSF_OBSERVE_MAX_SLOTS]
-  vsfi::DevBuf<uint32_t> fast_cells;  // [2] cell counters of the resident FAST kernels (k_fast.hip)
+  vsfi::DevBuf<uint32_t> fast_cells;  // [3] cell counters of the resident FAST kernels (k_fast.hip): full, packed, early part
   struct FastTune {  // resident FAST or one workgroup per four cells: what vsf_tune_fast_resident measured, per batch size
     int n = 0, choice = -1;
     vsfi::Event ev[2];

@@ -208,8 +208,7 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
     // work items: a full-width cell is one wave; a narrower one (ceil(cols / 4) + 2 lanes) is packed with others
     for (int s = 0; s < L.nstrips; s++)
       for (int b = 0; b < L.nbands; b++) {
-        const int bx0 = L.fast_a0 + VSF_FAST_BAND_COLS * b;
-        const int lanes = (std::min(L.x_hi, bx0 + VSF_FAST_BAND_COLS) - bx0 + 3) / 4 + 2;
+        const int lanes = vsf_fast_cell_lanes(L.fast_a0, L.x_hi, b);
         const int rows = std::min(VSF_FAST_STRIP_ROWS, L.y_hi - (L.y_lo + VSF_FAST_STRIP_ROWS * s));
         if (lanes < 64)
           narrow.push_back(Narrow{rows, lanes, l, b, s});
@@ -228,6 +227,9 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
   }
   G.g.cand_entries = std::max(cand, 1u);
   G.g.nunits = ncells;
+  // the full cells so far are in level order: vsf_fast_split.h cuts this part of the list, and counts it by itself
+  G.g.fast_split_levels = vsf_fast_split_levels(G.levels.data(), nlevels);
+  if (vsf_fast_n_early(G.levels.data(), nlevels, nlevels) != (int)G.units.size()) return false;
   // Narrow cells into waves: deterministic first fit, tallest and widest first, so that cells of equal row count share a
   // wave.  A wave reads one image buffer (level 0 is the input image, levels >= 1 the pyramid), so those never mix.  A cell
   // left alone in its wave stays a one-cell item (the full form, which needs no per-lane bookkeeping).

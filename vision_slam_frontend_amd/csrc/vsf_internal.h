@@ -9,6 +9,7 @@
 
 #include "../../include/vsf.h"
 #include "vsf_own.h"     // DevBuf, PinnedBuf, Event, Stream
+#include "vsf_fast_split.h"  // which FAST cells are full waves, and where their list is cut by level
 #include "vsf_resize.h"  // VsfTap, the resize coefficient formula, the packing plan
 
 // FAST march kernel: a wave owns a band of 248 keypoint columns (lanes 1..62 x 4 px; lanes 0 and 63 carry the raw halo
@@ -25,6 +26,8 @@
 #define VSF_FAST_PACK_WORDS (4 + 2 * VSF_FAST_PACK_SEGS)
 #define VSF_FAST_STRIP_ROWS 32
 #define VSF_FAST_RS_STRIDE (VSF_FAST_STRIP_ROWS + 2)  // u16 row-start table per unit (SR + 1 used)
+static_assert(VSF_FAST_SPLIT_BAND_COLS == VSF_FAST_BAND_COLS && VSF_FAST_SPLIT_STRIP_ROWS == VSF_FAST_STRIP_ROWS,
+              "vsf_fast_split.h states the cell size for itself");
 #define VSF_BLUR_MMA_ROWS 26     // output rows per step of the matrix-core blur (32 loaded rows - 2 x 3 halo rows)
 #define VSF_BLUR_MMA_STEPS 16    // double steps (52 rows) per unit: a workgroup walks this many blocks down its band pair
 #define VSF_BLUR_MMA_STEPS_SMALL 2  // ... for batches below 32 images
@@ -82,6 +85,7 @@ struct VsfGeom {
   uint32_t cand_entries;    // one image's candidate buffer (u32 entries)
   int nunits;               // FAST cells (32-row strip x 240-column band) per image
   int nwork_full, nwork_pack;  // FAST work items: waves covering one cell / packed items of narrow cells
+  int fast_split_levels;       // levels 0 .. this - 1 have full cells: the most VSF_OPT_FAST_EARLY_LEVELS can mean (vsf_fast_split.h)
   int lvlkp_entries;        // one image's level-keypoint buffer (VsfLevelKp entries)
   uint64_t pyramid_pixels;
 };
@@ -94,6 +98,10 @@ struct VsfTuning {
   int pipe_priority = 0;     // VSF_OPT_PIPE_PRIORITY: stream priority of the pipelined pyramid chain (0 normal, 1 lowest, -1 highest)
   int pipe_after_fast = 1;   // VSF_OPT_PIPE_AFTER_FAST: the pipelined pyramid of call k + 1 starts behind call k's FAST (1) or at once (0)
   int select_big_class = 1;  // VSF_OPT_SELECT_BIG_CLASS: 1 = the widest levels of a batch take the 9 216-entry class
+  int fast_early_levels = 12;  // VSF_OPT_FAST_EARLY_LEVELS: a pipelined call starts FAST on the full cells of this many levels from
+                               // inside its pyramid chain, beside the previous call's selection / descriptors (0: one FAST pass;
+                               // 12, as a grid: NOTES.md "FAST: the wide levels start beside the previous call")
+  int fast_early_form = 0;    // VSF_OPT_FAST_EARLY_FORM: that early launch as a grid (0) or resident with 1..3 waves per SIMD
   int jpeg_serial = 0;     // 1: every file through the one-wave-per-image decoder (set when the parallel decoder's LDS is refused)
   int pyramid_few = 16;    // VSF_OPT_PYRAMID_FEW: largest batch (images) that takes the slab kernel for every level
   int pyramid_chain = 8;   // VSF_OPT_PYRAMID_CHAIN: levels per slab launch (0: keep the per-level launches)
@@ -176,11 +184,23 @@ struct VsfSideStream {
 };
 void vsf_launch_bayer_bg_gray(const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch,
                               uint8_t* d_dst, size_t dst_image_stride, int dst_pitch, hipStream_t s);
+// `hook` (single chain only, side == NULL): called once, right behind the launch that produces level hook->level (0: before
+// the first launch) -- the caller records an event there and starts work on the levels that exist by then.
+struct VsfPyramidHook {
+  int level;
+  void (*fn)(void* arg, hipStream_t s);
+  void* arg;
+};
 void vsf_launch_pyramid(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, const VsfImages& im,
-                        hipStream_t s, const VsfSideStream* side);
+                        hipStream_t s, const VsfSideStream* side, const VsfPyramidHook* hook = nullptr);
 // threshold: FAST threshold; nms == 0 keeps every corner (standalone FAST only).
+// d_cell_counters: [3] for the resident forms: full cells, packed items, full cells of an early part.
+// part / n_early: VSF_FAST_ALL = every work item; VSF_FAST_EARLY = full cells [0, n_early) only; VSF_FAST_LATE = the full cells
+// from n_early on and every packed item (the two parts together are the whole list: vsf_fast_split.h).
+enum { VSF_FAST_ALL = 0, VSF_FAST_EARLY = 1, VSF_FAST_LATE = 2 };
 void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int threshold, int nms, hipStream_t s,
-                     int resident_waves_per_simd = 0, int n_cus = 0, uint32_t* d_cell_counters = nullptr);
+                     int resident_waves_per_simd = 0, int n_cus = 0, uint32_t* d_cell_counters = nullptr,
+                     int part = VSF_FAST_ALL, int n_early = 0);
 void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, const VsfImages& im,
                        hipStream_t s);
 void vsf_launch_retain_best_test(uint2* d_data, uint32_t* d_tables, int n, int n_points, int use_lds, int mode,
