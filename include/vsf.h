@@ -496,13 +496,54 @@ vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const 
  * Legal while no frame of that stream is submitted and not collected (else VSF_ERR_INVALID_ARG); the other streams, frames
  * in flight included, are untouched.  vsf_observe_reset stays "all streams" (and drops what waits). */
 vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream);
+/* Frames that ALREADY LIVE IN DEVICE MEMORY -- a tensor of the caller's framework, the output of vsf_imdecode_gray_batch /
+ * vsf_bayer_bg_to_gray_batch_dev on the caller's own stream, a camera SDK's or video decoder's buffer, the caller's own
+ * preprocessing kernel -- enter the queue without crossing to the host: what vsf_set_input_event is to the batched calls.
+ *   frames[0 .. n) are n CONSECUTIVE frames of queue stream `stream`, oldest first; tickets[i] is frame i's (consecutive).
+ * Each image is width x height bytes (the context's size) at ANY base address and ANY pitch >= width; left and right are
+ * independent of each other.  pixfmt: VSF_PIX_MONO8, or VSF_PIX_BAYER_RGGB8 -- mosaics that go through
+ * COLOR_BayerBG2BGR + COLOR_BGR2GRAY on the device, as the compressed frames' `bayer` does (frames with different `bayer`
+ * never share a batch).
+ *   ORDERING: the call is stream-ordered on `producer_stream` (a hipStream_t; NULL = the default stream), like
+ * hipMemcpyAsync.  The images may still be being produced by work queued earlier on that stream, and they may be
+ * overwritten by work queued on that stream after the call returns.  The call never waits for the GPU.
+ *   What it does: ONE kernel launch on the producer's stream copies the 2 n images into the frames' slots of a device ring
+ * (vsf_observe_device_ring_bytes(depth) bytes of HBM, built by the first such call) and an event recorded behind it is
+ * what the batch's copy stream waits for; when the batch leaves, its device frames go from the ring into the batch's image
+ * buffer in one copy command per contiguous run of them (two where the run wraps the ring), beside the raw frames' upload
+ * and the decoders' output.  The kernel reads only aligned 4-byte words that hold at least one pixel of the image: a row
+ * may end on the last byte of its allocation.  Everything behind that -- cut rules, tickets, collect / poll / view,
+ * reset / reset_stream, debug images and their files -- is as for raw frames, and so are the results, byte for byte.
+ *   THE CALLER'S PROMISE, as with vsf_set_stream: the pointers are device memory of the context's device and
+ * producer_stream is a stream of that device that is not being captured into a graph.  Neither is checked.
+ *   A refused call issues no ticket, books nothing and launches nothing.  VSF_ERR_INVALID_ARG: a null pointer (ctx, frames,
+ * an image, calib, tickets), n < 1, n larger than the free slots (depth - frames submitted and not collected), a pitch
+ * smaller than the width, a stream outside [0, n_streams), an unknown pixfmt -- and whatever vsf_observe_submit refuses
+ * (triangulate_rows, another frame_life while frames wait, a queue whose launch failed; VSF_ERR_UNSUPPORTED for
+ * max_keypoints >= 65536). */
+typedef struct {
+  const void* left;
+  const void* right;
+  size_t left_pitch, right_pitch;
+} vsf_dev_frame;
+enum { VSF_PIX_MONO8 = 0, VSF_PIX_BAYER_RGGB8 = 1 };
+vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame* frames, int n, int pixfmt,
+                                  void* producer_stream, const vsf_calibration* calib, float best_percent, int frame_life,
+                                  int64_t* tickets);
+/* HBM the device ring takes in a queue of `depth` frames (0: the depth vsf_observe_configure set, or its default):
+ * depth x 2 images at the staging pitch (width rounded up to 64) -- 157 MB at depth 256 and 640 x 480.  0 for a depth outside
+ * [0, 1024].  No device work. */
+size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth);
 /* What the queue did since it was built: out[0..n) of { frames launched, batches, largest batch, batches of one frame that
  * ran on one stream, launches forced by a collect or a change of parameters, launches that had to wait for a batch slot,
  * depth, frames per batch at most, then the host's nanoseconds inside staging copies, batch launches, waits for results,
  * compressed frames launched, copy commands + kernel launches the compressed path issued, bytes of every buffer the
  * compressed path owns (file ring, blobs, decoder scratch, mosaics) -- the last three are 0 for a queue that has only seen
  * raw frames; [14] launches of the compressed debug images; [15] streams (vsf_observe_set_streams), [16] batches that
- * carried frames of more than one stream }. */
+ * carried frames of more than one stream; [17] device frames launched (vsf_observe_submit_dev), [18] kernel launches and
+ * copy commands the device path issued (a submit's one launch, a batch's copies out of the ring, its demosaic where no
+ * compressed frame brings one), [19] bytes of the device ring -- the last three are 0 for a queue that has seen no device
+ * frame }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,

@@ -45,6 +45,7 @@ EXPORTS = [
     "vsf_observe_set_debug_jpeg", "vsf_observe_debug_jpeg_view", "vsf_jpeg_encode_capacity", "vsf_jpeg_encode_batch_dev", "vsf_jpeg_encode", "vsf_debug_jpeg_encode_header",
     "vsf_png_encode_capacity", "vsf_png_encode_batch_dev", "vsf_png_encode", "vsf_debug_png_encode_header", "vsf_debug_png_encode_cpu", "vsf_observe_set_debug_png", "vsf_observe_debug_png_view",
     "vsf_observe_set_streams", "vsf_observe_submit_stream", "vsf_observe_submit_compressed_stream", "vsf_observe_reset_stream",
+    "vsf_observe_submit_dev", "vsf_observe_device_ring_bytes",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -54,7 +55,9 @@ STAGE_COUNT = 8
 # vsf_observe_stats' values, in order (include/vsf.h)
 OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
                  "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands", "streams",
-                 "multi_stream_batches")
+                 "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes")
+# vsf_observe_submit_dev's pixel formats (include/vsf.h)
+PIX_MONO8, PIX_BAYER_RGGB8 = 0, 1
 
 
 class VsfParams(C.Structure):
@@ -88,6 +91,26 @@ class VsfCalibration(C.Structure):
 DRAW_CIRCLE, DRAW_LINE = 0, 1
 DRAW_OP_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("bgr", "u1", (4,))])
 assert DRAW_OP_DTYPE.itemsize == 24
+
+
+class VsfDevFrame(C.Structure):
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("left_pitch", C.c_size_t), ("right_pitch", C.c_size_t)]
+
+
+def device_image(t, width: int, height: int, device: int):
+    """(address, pitch) of a 2-D uint8 tensor of height x width on GPU `device` whose rows are dense (stride(1) == 1; any
+    stride(0) >= width): what vsf_observe_submit_dev takes.  ValueError for anything else -- before any call into the library."""
+    if not (hasattr(t, "data_ptr") and hasattr(t, "stride") and hasattr(t, "is_cuda")):
+        raise ValueError("a device image is a torch tensor, not %s" % type(t).__name__)
+    if str(t.dtype) != "torch.uint8":
+        raise ValueError("a device image is torch.uint8, not %s" % t.dtype)
+    if not t.is_cuda or (t.device.index or 0) != device:
+        raise ValueError("a device image lives on GPU %d, not on %s" % (device, t.device))
+    if t.dim() != 2 or tuple(t.shape) != (height, width):
+        raise ValueError("a device image is %d x %d, not %s" % (height, width, tuple(t.shape)))
+    if t.stride(1) != 1 or (height > 1 and t.stride(0) < width):
+        raise ValueError("a device image has dense rows (stride(1) == 1, stride(0) >= width), not strides %s" % (tuple(t.stride()),))
+    return int(t.data_ptr()), int(t.stride(0)) if height > 1 else max(int(t.stride(0)), width)
 
 
 class VsfDrawCanvas(C.Structure):
@@ -242,6 +265,10 @@ def lib() -> C.CDLL:
                                                 C.POINTER(C.c_int64)]
         L.vsf_observe_submit_compressed_stream.argtypes = [vp, i32, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float,
                                                            i32, C.POINTER(C.c_int64)]
+        L.vsf_observe_submit_dev.argtypes = [vp, i32, C.POINTER(VsfDevFrame), i32, i32, vp, C.POINTER(VsfCalibration), C.c_float,
+                                             i32, C.POINTER(C.c_int64)]
+        L.vsf_observe_device_ring_bytes.argtypes = [vp, i32]
+        L.vsf_observe_device_ring_bytes.restype = sz
         L.vsf_observe_submit_compressed.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32,
                                                     C.POINTER(C.c_int64)]
         L.vsf_observe_stereo_compressed.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32, vp,
@@ -598,6 +625,37 @@ class Context:
         if st != VSF_OK and st not in allow_status:
             raise VsfError(st, "vsf_observe_submit_compressed_stream", lib().vsf_last_hip_error(self._h))
         return st, int(t.value)
+
+    def observe_submit_dev(self, frames, calib: VsfCalibration, stream: int = 0, pixfmt: int = PIX_MONO8,
+                           producer_stream: int | None = None, best_percent: float = 0.3, frame_life: int = 10,
+                           allow_status=()):
+        """vsf_observe_submit_dev: queues len(frames) consecutive frames of sequence `stream` that already live in device
+        memory, stream-ordered on `producer_stream` (a hipStream_t as an integer; None: torch.cuda.current_stream() of the
+        context's device).  A frame is a pair (left, right) of 2-D torch.uint8 tensors on the context's device (device_image:
+        ValueError otherwise, before the library is called), or four integers (left address, left pitch, right address,
+        right pitch).  Returns the tickets -- or, with `allow_status`, (status, tickets): a refused call's are all -1."""
+        p = self.params
+        arr = (VsfDevFrame * max(len(frames), 1))()
+        for i, f in enumerate(frames):
+            if len(f) == 2:
+                (lp, ls), (rp, rs) = (device_image(t, p.width, p.height, self.device) for t in f)
+            else:
+                lp, ls, rp, rs = (int(v) for v in f)
+            arr[i] = VsfDevFrame(lp, rp, ls, rs)
+        if producer_stream is None:
+            import torch
+            producer_stream = torch.cuda.current_stream(self.device).cuda_stream
+        tickets = (C.c_int64 * max(len(frames), 1))(*([-1] * max(len(frames), 1)))
+        st = lib().vsf_observe_submit_dev(self._h, stream, arr, len(frames), pixfmt, C.c_void_p(producer_stream or None),
+                                          C.byref(calib), float(np.float32(best_percent)), frame_life, tickets)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_submit_dev", lib().vsf_last_hip_error(self._h))
+        out = [int(t) for t in tickets[:len(frames)]]
+        return (st, out) if allow_status else out
+
+    def observe_device_ring_bytes(self, depth: int = 0) -> int:
+        """HBM the queue's device ring takes at `depth` (vsf_observe_device_ring_bytes; no device work)."""
+        return int(lib().vsf_observe_device_ring_bytes(self._h, depth))
 
     def observe_collect(self, ticket: int, frame_life: int = 10) -> dict:
         """Waits for the frame of `ticket` (vsf_observe_collect) and returns its decoded result."""

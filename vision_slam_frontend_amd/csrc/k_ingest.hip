@@ -167,7 +167,81 @@ __global__ __launch_bounds__(256) void ingest_finish_kernel(uint8_t* __restrict_
   for (uint32_t i = threadIdx.x; i < dwords; i += 256u) out[i] = 0u;
 }
 
+// vsf_observe_submit_dev: a call's 2 n images, wherever they lie in device memory, into their slots of the queue's device
+// ring -- ONE launch on the producer's stream.  The destination is the staging layout (rows at a multiple of 64 bytes), so
+// a lane owns 16 destination bytes and writes them with one aligned 16-byte store.  The source has any base address and any
+// pitch: a lane reads the (up to five) ALIGNED dwords that hold its 16 bytes and funnel-shifts them (v_alignbyte_b32) by
+// the address's low two bits.  A dword is read only if it holds at least one pixel of the lane's row -- an aligned dword
+// never straddles a page, so a row that ends on the last byte of an allocation is read to that byte and no further --;
+// what is not read counts as zero, and the columns >= w of the last 16-byte piece are written as zero.
+// A workgroup walks kIngestRows rows of one image as a flat list of 16-byte pieces, four per lane in flight (20 dword
+// loads) before the first store, so a wave lives through several memory round trips (cf. bayer_bg_gray_kernel above).
+struct IngestRingArgs {
+  uint8_t* ring;
+  size_t image_stride;
+  int dst_pitch, w, h, slot0, depth;
+  const VsfIngestSrc* table;
+  VsfIngestSrc inl[VSF_INGEST_INLINE];
+};
+
+constexpr int kIngestRows = 32, kIngestUnroll = 4;
+
+__global__ __launch_bounds__(256) void ingest_ring_kernel(IngestRingArgs a) {
+  const int image = blockIdx.y, side = image & 1;
+  int slot = a.slot0 + (image >> 1);
+  if (slot >= a.depth) slot -= a.depth;
+  const VsfIngestSrc s = a.table ? a.table[2 * slot + side] : a.inl[image];
+  uint8_t* dst = a.ring + ((size_t)slot * 2 + (size_t)side) * a.image_stride;
+  const int cpr = (a.w + 15) >> 4;  // 16-byte pieces per row
+  const int y0 = blockIdx.x * kIngestRows, rows = min(kIngestRows, a.h - y0);
+  const int items = rows * cpr;
+  for (int i0 = threadIdx.x; i0 < items; i0 += 256 * kIngestUnroll) {
+    uint32_t d[kIngestUnroll][5], sh[kIngestUnroll];
+#pragma unroll
+    for (int u = 0; u < kIngestUnroll; u++) {
+      const int i = i0 + 256 * u;
+      sh[u] = 0;
+#pragma unroll
+      for (int k = 0; k < 5; k++) d[u][k] = 0u;
+      if (i < items) {
+        const int r = i / cpr, c = i - r * cpr;
+        const uintptr_t row = (uintptr_t)s.src + (size_t)(y0 + r) * s.pitch, row_end = row + (uintptr_t)a.w;
+        const uintptr_t addr = row + 16u * (uintptr_t)c;  // (< row_end: c < cpr)
+        sh[u] = (uint32_t)(addr & 3u);
+        const uintptr_t base = addr - sh[u];  // (>= row - 3: inside the dword of the row's first pixel)
+#pragma unroll
+        for (int k = 0; k < 5; k++)
+          if (base + 4u * k < row_end) d[u][k] = *reinterpret_cast<const uint32_t*>(base + 4u * k);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kIngestUnroll; u++) {
+      const int i = i0 + 256 * u;
+      if (i < items) {
+        const int r = i / cpr, c = i - r * cpr;
+        uint32_t o[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int left = a.w - (16 * c + 4 * j);  // pixels of the row from this dword's first byte on
+          const uint32_t keep = left >= 4 ? 0xFFFFFFFFu : left <= 0 ? 0u : (1u << (8 * left)) - 1u;
+          o[j] = __builtin_amdgcn_alignbyte(d[u][j + 1], d[u][j], sh[u]) & keep;
+        }
+        *reinterpret_cast<uint4*>(dst + (size_t)(y0 + r) * a.dst_pitch + 16 * c) = make_uint4(o[0], o[1], o[2], o[3]);
+      }
+    }
+  }
+}
+
 }  // namespace
+
+void vsf_launch_ingest_ring(uint8_t* d_ring, size_t image_stride, int dst_pitch, int w, int h, int slot0, int depth, int n_frames,
+                            const VsfIngestSrc* inl, const VsfIngestSrc* table, hipStream_t s) {
+  if (n_frames < 1 || w < 1 || h < 1) return;
+  IngestRingArgs a{d_ring, image_stride, dst_pitch, w, h, slot0, depth, table, {}};
+  if (!table)
+    for (int i = 0; i < 2 * n_frames && i < VSF_INGEST_INLINE; i++) a.inl[i] = inl[i];
+  hipLaunchKernelGGL(ingest_ring_kernel, dim3((h + kIngestRows - 1) / kIngestRows, 2 * n_frames), dim3(256), 0, s, a);
+}
 
 void vsf_launch_bayer_bg_gray(const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch,
                               uint8_t* d_dst, size_t dst_image_stride, int dst_pitch, hipStream_t s) {

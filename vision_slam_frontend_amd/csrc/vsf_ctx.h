@@ -128,9 +128,12 @@ struct vsf_ctx {
     vsf_calibration calib;
     float best_percent = 0.f;
     int batch = -1;  // batch slot it was launched in, -1 while it waits
-    uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, else VSF_FILE_JPEG / VSF_FILE_PNG: a file in h_cmp
+    uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, VSF_FILE_JPEG / VSF_FILE_PNG: a file in h_cmp,
+                                 // kObserveKindDevice (both): the images are in the slot of the device ring d_ring
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
-    bool bayer = false;          // compressed frames: the decoded images are bayer_rggb8 mosaics
+    bool bayer = false;          // compressed and device frames: the (decoded) images are bayer_rggb8 mosaics
+    int dev_event = -1;          // device frames: the slot whose event in dev_ev follows the copy into the ring ...
+    hipStream_t dev_stream = nullptr;  // ... and the producer's stream it was recorded on (a view)
     int stream = 0;              // vsf_observe_submit_stream: whose sequence it belongs to
     int64_t k = 0;               // frames of its stream in front of it (since the queue was built or the stream reset)
   };
@@ -208,6 +211,15 @@ struct vsf_ctx {
     size_t cmp_cap = 0, cmp_slot = 0;  // bytes a file may have / bytes of its slot (vsf_observe_compressed_slot_bytes)
     vsfi::DevBuf<uint8_t> d_bayer;     // [2 bmax] images at the staging pitch: the decoded mosaics of a Bayer batch
     VsfDecodeScratch ing_scratch;   // the decoders' scratch on the copy stream
+    // vsf_observe_submit_dev; nothing of this exists before the first device frame.  The frames wait in a DEVICE ring in the
+    // staging ring's layout; the submit's one launch on the producer's stream fills their slots and records the event of the
+    // call's last slot behind it; the batch's copy stream waits for that event and moves the slots into the batch's images.
+    vsfi::DevBuf<uint8_t> d_ring;            // [depth][2] images at the staging pitch
+    vsfi::PinnedBuf<VsfIngestSrc> h_dev_src;  // pinned [depth][2]: where a long call's images are (read by its launch)
+    std::vector<vsfi::Event> dev_ev;         // [depth]
+    std::vector<uint8_t> run_kinds;          // launch_batch's: the batch's kinds as observe_batch_runs takes them ...
+    std::vector<vsfi::ObserveRun> runs;      // ... and splits them
+    int64_t stat_dev_commands = 0;           // the caller's share of vsf_observe_stats value 18 (the submits' launches)
     size_t out_cap = 0, out_stride = 0;
     ObserveBatch batch[kObserveBatchSlots];
     std::vector<ObserveFrame> frames;  // [depth]

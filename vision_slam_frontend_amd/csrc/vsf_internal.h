@@ -466,5 +466,17 @@ void vsf_launch_files_home(const uint8_t* d_files, size_t file_stride, const int
 // data) becomes all zero, `rows` rows of `pitch` bytes.
 void vsf_launch_ingest_finish(uint8_t* d_img, size_t image_stride, int pitch, int rows, const int32_t* d_status, int n,
                               hipStream_t s);
+// vsf_observe_submit_dev (k_ingest.hip): ONE launch copies a call's 2 n device-resident images -- any base address, any
+// pitch >= w -- into the slots (slot0 + f) % depth, f = 0 .. n - 1, of the queue's device ring (left, right per slot;
+// image_stride bytes each, rows at dst_pitch, a multiple of 16 >= (w + 15) & ~15 with h * dst_pitch <= image_stride).
+// Where an image comes from: up to VSF_INGEST_INLINE images ride in the kernel arguments (`inl`, by image); a longer call
+// names `table`, device-visible pinned memory indexed by 2 * slot + side, which must stay as it is until the kernel has run.
+struct VsfIngestSrc {
+  const uint8_t* src;
+  size_t pitch;
+};
+#define VSF_INGEST_INLINE 8
+void vsf_launch_ingest_ring(uint8_t* d_ring, size_t image_stride, int dst_pitch, int w, int h, int slot0, int depth, int n_frames,
+                            const VsfIngestSrc* inl, const VsfIngestSrc* table, hipStream_t s);
 
 #endif  // VSF_INTERNAL_H_

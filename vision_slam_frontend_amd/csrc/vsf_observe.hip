@@ -91,6 +91,10 @@ void stop_observe_threads(vsf_ctx* ctx) {
 void free_observe(vsf_ctx* ctx) {
   vsf_ctx::Observe& o = ctx->ob;
   stop_observe_threads(ctx);
+  // the device ring is written on the PRODUCERS' streams (vsf_observe_submit_dev), which sync_all_streams does not know: the
+  // events recorded behind those launches say when they are done with it
+  for (const Event& e : o.dev_ev)
+    if (e) (void)hipEventSynchronize(e);
   // launch_batch publishes a batch slot's images as the context's last input (the vsf_debug_* level-0 reads): that view dies here
   for (const vsf_ctx::ObserveBatch& b : o.batch)
     if (b.d_img && ctx->last_images.base == b.d_img) ctx->last_valid = false;
@@ -263,6 +267,54 @@ vsf_status ensure_compressed(vsf_ctx* ctx, bool bayer) {
   return VSF_OK;
 }
 
+// The device ring, its table of sources and its events: built by the first device frame -- a queue that never sees one owns
+// none of this (vsf_observe_device_ring_bytes says what it costs).
+vsf_status ensure_device_ring(vsf_ctx* ctx, bool bayer) {
+  vsf_ctx::Observe& o = ctx->ob;
+  if (!o.d_ring) {
+    const size_t bytes = vsf_observe_device_ring_bytes(ctx, o.depth);
+    if (bytes == 0) return VSF_ERR_INVALID_ARG;
+    std::vector<Event> ev((size_t)o.depth);
+    for (Event& e : ev) VSF_HIP(e.alloc(hipEventDisableTiming));
+    VSF_HIP(o.h_dev_src.alloc((size_t)o.depth * 2 * sizeof(VsfIngestSrc), hipHostMallocMapped));
+    VSF_HIP(o.d_ring.alloc(bytes));
+    o.dev_ev = std::move(ev);
+  }
+  if (bayer && !o.d_bayer) VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
+  return VSF_OK;
+}
+
+// The device frames of batch [t0, t0 + n) (o.runs): the copy stream waits for the launches that filled their slots -- for
+// the newest event of every stretch of frames that came over one producer stream: it is behind the others --, then ONE copy
+// command per run takes the slots into the batch's images (into the mosaics' buffer for a Bayer batch).
+vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, bool bayer, bool demosaic, hipStream_t s) {
+  vsf_ctx::Observe& o = ctx->ob;
+  ObserveLaunchStats& stats = o.queue->stats;
+  const vsf_ctx::ObserveFrame* last = nullptr;
+  for (int f = 0; f <= n; f++) {
+    const vsf_ctx::ObserveFrame* fr = f < n ? &o.frames[(size_t)((t0 + f) % o.depth)] : nullptr;
+    if (fr && fr->kind[0] != kObserveKindDevice) continue;
+    if (last && (!fr || fr->dev_stream != last->dev_stream)) VSF_HIP(hipStreamWaitEvent(s, o.dev_ev[(size_t)last->dev_event], 0));
+    last = fr;
+  }
+  const size_t frame_bytes = 2 * ctx->st_img_stride;
+  uint8_t* dst = bayer ? o.d_bayer.get() : b.d_img.get();
+  for (const ObserveRun& r : o.runs) {
+    if (r.cls != kObserveRunDevice) continue;
+    VSF_HIP(hipMemcpyAsync(dst + (size_t)r.f0 * frame_bytes, o.d_ring + (size_t)r.slot0 * frame_bytes, (size_t)r.n * frame_bytes,
+                           hipMemcpyDeviceToDevice, s));
+    stats.device_commands++;
+    stats.device_frames += r.n;
+  }
+  // (a Bayer batch that also holds compressed frames is demosaiced once, behind its decoders: ingest_batch)
+  if (demosaic) {
+    vsf_launch_bayer_bg_gray(o.d_bayer, 2 * n, ctx->p.width, ctx->p.height, ctx->st_img_stride, (int)ctx->st_img_pitch, b.d_img,
+                             ctx->st_img_stride, (int)ctx->st_img_pitch, s);
+    stats.device_commands++;
+  }
+  return VSF_OK;
+}
+
 // The compressed frames of batch [t0, t0 + n): the batch's 2n images go through decode_runs (vsf_ingest.hip) on `s` -- ONE
 // upload for every run of one format among them, a status word per image (b.status: damage lands on its own image) --, then
 // BayerBG -> gray for bayer_rggb8 frames, and the ingest finish: an image its decoder refused becomes all zero.  Raw frames of
@@ -277,7 +329,7 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   for (int i = 0; i < N; i++) {
     const int slot = (int)((t0 + i / 2) % o.depth);
     const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
-    kinds[i] = fr.kind[i & 1];
+    kinds[i] = fr.kind[i & 1] == kObserveKindDevice ? (uint8_t)VSF_FILE_NONE : fr.kind[i & 1];  // (in the ring: not a file)
     files[i] = o.h_cmp + ((size_t)slot * 2 + (size_t)(i & 1)) * o.cmp_slot;
     sizes[i] = fr.nbytes[i & 1];
   }
@@ -374,11 +426,17 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   // solo: a lone frame with nothing else on the GPU runs on ONE stream from upload to result (no event hops in its chain);
   // otherwise copy, extraction and tail have a stream each, so that the next batch's upload and extraction run beside
   // this one's tail.
-  bool any_raw = false, any_cmp = false;
+  bool any_raw = false, any_cmp = false, any_dev = false;
   for (int f = 0; f < n; f++) {
-    const bool c = o.frames[(size_t)((t0 + f) % o.depth)].kind[0] != 0;
-    any_cmp |= c;
-    any_raw |= !c;
+    const uint8_t kind = o.frames[(size_t)((t0 + f) % o.depth)].kind[0];
+    any_raw |= kind == 0;
+    any_dev |= kind == kObserveKindDevice;
+    any_cmp |= kind != 0 && kind != kObserveKindDevice;
+  }
+  if (any_dev) {  // (vsf_observe_plan.cc: the runs of device frames, cut where the ring wraps)
+    o.run_kinds.resize((size_t)n);
+    for (int f = 0; f < n; f++) o.run_kinds[(size_t)f] = o.frames[(size_t)((t0 + f) % o.depth)].kind[0];
+    if (!observe_batch_runs(o.run_kinds.data(), n, t0, o.depth, &o.runs)) return VSF_ERR_INVALID_ARG;
   }
   // (compressed frames are decoded on the copy stream whatever else runs: the decoders' scratch exists once, for that stream)
   hipStream_t s_copy = solo && !any_cmp ? ctx->stream : o.copy_stream, s_ex = ctx->stream,
@@ -394,6 +452,12 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
     if (any_raw && first < n)
       VSF_HIP(hipMemcpyAsync(b.d_img + (size_t)first * frame_bytes, o.h_img, (size_t)(n - first) * frame_bytes,
                              hipMemcpyHostToDevice, s_copy));
+    // ---- device frames: out of the device ring, behind the launches that put them there ----
+    if (any_dev) {
+      const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
+      const vsf_status st = ingest_device_runs(ctx, b, t0, n, bayer, bayer && !any_cmp, s_copy);
+      if (st != VSF_OK) return st;
+    }
     // ---- compressed frames: one more copy command for their files, the decoders, the ingest finish ----
     if (any_cmp) {
       const vsf_status st = ingest_batch(ctx, b, t0, n, s_copy);
@@ -722,11 +786,13 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[17] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+  const int64_t v[20] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
-                         s.file_commands, (int64_t)ctx->ob_streams, s.multi};
-  for (int i = 0; i < n && i < 17; i++) out[i] = v[i];
+                         s.file_commands, (int64_t)ctx->ob_streams, s.multi,
+                         s.device_frames, s.device_commands + o.stat_dev_commands,
+                         (int64_t)(o.d_ring ? vsf_observe_device_ring_bytes(ctx, o.depth) : 0)};
+  for (int i = 0; i < n && i < 20; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -869,6 +935,109 @@ vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const 
   if (st != VSF_OK) return st;
   return observe_submit(ctx, stream, left, right, ctx->p.width, ctx->p.height, 0, kinds, nbytes, bayer != 0, calib,
                         best_percent, frame_life, ticket);
+}
+
+size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth) {
+  if (!ctx || depth < 0 || depth > 1024) return 0;
+  if (depth == 0) depth = ctx->ob_depth > 0 ? ctx->ob_depth : std::max(1, ctx->p.max_images / 2);
+  return (size_t)depth * 2 * ctx->st_img_stride;
+}
+
+// Frames that are in device memory already.  The order of things: every refusal; the queue (built by the first submit of any
+// kind); what waits and may not share a batch with these frames leaves; the ring; ONE launch on the producer's stream and
+// the event behind it; only then the frames' records and their tickets, one by one -- a batch may leave between two of them,
+// and takes the frames that have theirs.
+vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame* frames, int n, int pixfmt, void* producer_stream,
+                                  const vsf_calibration* calib, float best_percent, int frame_life, int64_t* tickets) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !frames || !calib || !tickets || n < 1 || !(best_percent >= 0.f) || frame_life < 0 ||
+      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
+    return VSF_ERR_INVALID_ARG;
+  for (int i = 0; i < n; i++) tickets[i] = -1;
+  if (pixfmt != VSF_PIX_MONO8 && pixfmt != VSF_PIX_BAYER_RGGB8) return VSF_ERR_INVALID_ARG;
+  if (ctx->p.max_images < 2 || n > 1024) return VSF_ERR_INVALID_ARG;
+  const size_t w = (size_t)ctx->p.width;
+  for (int i = 0; i < n; i++)
+    if (!frames[i].left || !frames[i].right || frames[i].left_pitch < w || frames[i].right_pitch < w) return VSF_ERR_INVALID_ARG;
+  if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
+  if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6) return VSF_ERR_INVALID_ARG;
+  const bool bayer = pixfmt == VSF_PIX_BAYER_RGGB8;
+  hipStream_t producer = static_cast<hipStream_t>(producer_stream);
+  VSF_HIP(hipSetDevice(ctx->device));
+  vsf_ctx::Observe& o = ctx->ob;
+  if (o.ready && o.frame_life != frame_life) {  // (re-sizing the window drops nothing that is still in the queue)
+    if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
+    stop_observe_threads(ctx);
+  }
+  vsf_status st = ensure_observe(ctx, frame_life);
+  if (st != VSF_OK) return st;
+  ObserveQueue& q = *o.queue;
+  ObserveSpan span;  // (next_ticket and next_collect are the caller's own: nobody else writes them)
+  if (!observe_submit_span(q.next_ticket, q.next_collect, o.depth, n, &span)) return VSF_ERR_INVALID_ARG;
+  {
+    // the cut rule of observe_submit, once: the call's frames share everything it looks at
+    std::unique_lock<std::mutex> lk(q.mu);
+    if (q.status != VSF_OK) return q.status;
+    if (q.next_launch < q.next_ticket) {
+      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].bayer != bayer;
+      const int64_t mine = o.streams[(size_t)stream].last_ticket;
+      if (!cut && mine >= q.next_launch) {
+        const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
+        cut = observe_plan_must_cut(w0.calib, w0.best_percent, *calib, best_percent);
+      }
+      if (cut) {
+        st = q.caller_pump(lk, true);
+        if (st != VSF_OK) return st;
+      }
+    }
+  }
+  st = ensure_device_ring(ctx, bayer);
+  if (st != VSF_OK) return st;
+  if (o.debug) {  // the stereo lines' colours, drawn ahead for every frame of the call (observe_submit)
+    const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + n - q.next_collect) * K;
+    for (; o.col_generated < want; o.col_generated++) {
+      const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
+      o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
+    }
+  }
+  // ---- ONE launch on the producer's stream: the 2 n images into the frames' slots of the ring (the slots' previous frames
+  // have been collected: the copies out of them are long done), and the event the batch's copy stream will wait for ----
+  const int64_t t_copy = now_ns();
+  VsfIngestSrc inl[VSF_INGEST_INLINE];
+  const bool by_table = 2 * n > VSF_INGEST_INLINE;
+  for (int i = 0; i < n; i++) {
+    const int slot = (span.slot0 + i) % o.depth;
+    VsfIngestSrc* e = by_table ? o.h_dev_src + 2 * (size_t)slot : inl + 2 * i;
+    e[0] = {static_cast<const uint8_t*>(frames[i].left), frames[i].left_pitch};
+    e[1] = {static_cast<const uint8_t*>(frames[i].right), frames[i].right_pitch};
+  }
+  vsf_launch_ingest_ring(o.d_ring, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.width, ctx->p.height, span.slot0, o.depth, n,
+                         inl, by_table ? o.h_dev_src.get() : nullptr, producer);
+  const int ev_slot = (span.slot0 + n - 1) % o.depth;
+  VSF_HIP(hipEventRecord(o.dev_ev[(size_t)ev_slot], producer));
+  VSF_STICKY();
+  o.stat_dev_commands++;
+  o.stat_copy_ns += now_ns() - t_copy;
+  for (int i = 0; i < n; i++) {
+    vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((span.slot0 + i) % o.depth)];
+    fr.kind[0] = fr.kind[1] = kObserveKindDevice;
+    fr.nbytes[0] = fr.nbytes[1] = 0u;
+    fr.bayer = bayer;
+    fr.dev_event = ev_slot;
+    fr.dev_stream = producer;
+    fr.calib = *calib;
+    fr.best_percent = best_percent;
+    fr.batch = -1;
+    vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
+    fr.stream = stream;
+    fr.k = mine.frames++;
+    mine.uncollected++;
+    mine.last_ticket = q.next_ticket;
+    st = q.submit(&tickets[i]);
+    if (st != VSF_OK) return st;
+  }
+  return VSF_OK;
 }
 
 vsf_status vsf_observe_set_compressed_cap(vsf_ctx* ctx, size_t cap_per_image) {

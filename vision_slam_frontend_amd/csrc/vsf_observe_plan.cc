@@ -76,4 +76,30 @@ bool observe_plan(const ObservePlanIn* in, int n, int n_streams, int ring, int l
   return true;
 }
 
+bool observe_submit_span(int64_t next_ticket, int64_t next_collect, int depth, int n, ObserveSpan* span) {
+  if (!span || depth < 1 || depth > 1024 || next_collect < 0 || next_ticket < next_collect || next_ticket - next_collect > depth)
+    return false;
+  const int free_slots = depth - (int)(next_ticket - next_collect);
+  if (n < 1 || n > free_slots) return false;
+  const int slot0 = (int)(next_ticket % depth), first = std::min(n, depth - slot0);
+  *span = {slot0, first, n - first};
+  return true;
+}
+
+bool observe_batch_runs(const uint8_t* kinds, int n, int64_t t0, int depth, std::vector<ObserveRun>* runs) {
+  if (!kinds || !runs || depth < 1 || n < 1 || n > depth || t0 < 0) return false;
+  runs->clear();
+  int slot = (int)(t0 % depth);
+  for (int f = 0; f < n; f++) {
+    if (kinds[f] > kObserveKindDevice) return false;
+    const int cls = kinds[f] == 0 ? kObserveRunRaw : kinds[f] == kObserveKindDevice ? kObserveRunDevice : kObserveRunCompressed;
+    if (f == 0 || slot == 0 || runs->back().cls != cls)
+      runs->push_back({cls, f, 1, slot});
+    else
+      runs->back().n++;
+    if (++slot == depth) slot = 0;
+  }
+  return true;
+}
+
 }  // namespace vsfi

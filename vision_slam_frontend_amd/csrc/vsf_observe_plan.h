@@ -60,6 +60,34 @@ bool observe_plan_must_cut(const vsf_calibration& a_calib, float a_best_percent,
 // storage).  false: an argument is out of range (a stream outside [0, n_streams), k < 0, ring < life + 1, ...).
 bool observe_plan(const ObservePlanIn* in, int n, int n_streams, int ring, int life, ObservePlan* plan);
 
+// ---- frames that already live in device memory (vsf_observe_submit_dev) ----
+// Such frames wait in a DEVICE ring of `depth` slots in the staging ring's layout (ticket t in slot t % depth), beside the
+// raw frames' pinned ring and the compressed frames' ring of files.
+
+// ObserveFrame::kind of a device frame (0 raw, VSF_FILE_JPEG = 1, VSF_FILE_PNG = 2 are the others).
+enum { kObserveKindDevice = 3 };
+
+// One call's n consecutive frames: slots [slot0, slot0 + first), then [0, second) when they wrap the ring.
+struct ObserveSpan {
+  int slot0, first, second;
+};
+// false -- and *span untouched -- unless 1 <= n <= depth - (next_ticket - next_collect): a call never takes a slot whose
+// frame has not been collected.
+bool observe_submit_span(int64_t next_ticket, int64_t next_collect, int depth, int n, ObserveSpan* span);
+
+// A batch's frames [t0, t0 + n) by where their images come from: a run is a stretch of frames of one class whose slots are
+// contiguous in the rings -- what ONE copy command can carry.
+enum { kObserveRunRaw = 0, kObserveRunCompressed = 1, kObserveRunDevice = 2 };
+struct ObserveRun {
+  int cls;    // kObserveRun*
+  int f0, n;  // frames [f0, f0 + n) of the batch
+  int slot0;  // the ring slot of frame f0; slot0 + n <= depth
+};
+// kinds[f]: ObserveFrame::kind of the batch's frame f.  Runs come in frame order and are maximal: a new one starts where the
+// class changes or the ring wraps (at most once: n <= depth).  false: an argument is out of range; `runs` keeps its storage
+// from batch to batch.
+bool observe_batch_runs(const uint8_t* kinds, int n, int64_t t0, int depth, std::vector<ObserveRun>* runs);
+
 }  // namespace vsfi
 
 #endif  // VSF_OBSERVE_PLAN_H_

@@ -28,6 +28,8 @@ def lib() -> C.CDLL:
         L.vsfh_observe_odometry.argtypes = [vp, vp, vp, dbl]
         L.vsfh_observe_image.argtypes = [vp, vp, vp, i32, i32, sz, dbl]
         L.vsfh_observe_compressed_image.argtypes = [vp, vp, sz, vp, sz, i32, dbl]
+        L.vsfh_observe_device_image.argtypes = [vp, vp, sz, vp, sz, vp, dbl, i32]
+        L.vsfh_group_observe_device_image.argtypes = [vp, i32, vp, sz, vp, sz, vp, dbl, i32]
         L.vsfh_last_status.argtypes = [vp]
         L.vsfh_refused_frames.argtypes = [vp]
         L.vsfh_refused_frames.restype = C.c_uint64
@@ -103,6 +105,17 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _device_frame(left, right, width: int, height: int, device: int, stream):
+    """What vsfh_observe_device_image takes of two tensors: (left address, left pitch, right address, right pitch, stream).
+    ValueError -- before any call into the library -- for a tensor that is not height x width torch.uint8 with dense rows on
+    GPU `device`; stream None: torch.cuda.current_stream() of that device, else a torch stream or a hipStream_t as an integer."""
+    (lp, ls), (rp, rs) = capi.device_image(left, width, height, device), capi.device_image(right, width, height, device)
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(device)
+    return lp, ls, rp, rs, C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
+
+
 def default_calibration() -> capi.VsfCalibration:
     """FrontendConfig()'s stereo calibration (the reference's hard-coded constants, slam_frontend.cc:565-644)."""
     c = capi.VsfCalibration()
@@ -117,6 +130,7 @@ class Frontend:
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
+        self.size, self.device = (width, height), device
         if debug_images:  # FrontendConfig::debug_images_ (the reference's default is on, slam_frontend.cc:552)
             lib().vsfh_set_debug_images(self._h, 1)
         if debug_jpeg_quality:  # FrontendConfig::debug_jpeg_quality_: the queued modes keep JPEG files instead of raw images
@@ -220,6 +234,18 @@ class Frontend:
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend::ObserveImage")
+        return added
+
+    def observe_device_image(self, left, right, time: float = 0.0, bayer_rggb8: bool = False, stream=None) -> bool:
+        """Frontend::ObserveDeviceImage: the frame as two 2-D torch.uint8 tensors that already live on the Frontend's GPU
+        (stride(1) == 1, any stride(0)), stream-ordered on `stream` (None: torch.cuda.current_stream()): they may still be
+        being written by work queued on that stream, and may be overwritten by work queued on it afterwards.  A tensor of
+        another dtype, device, size or inner stride raises ValueError before the library is called."""
+        lp, ls, rp, rs, s = _device_frame(left, right, self.size[0], self.size[1], self.device, stream)
+        added = bool(lib().vsfh_observe_device_image(self._h, lp, ls, rp, rs, s, time, int(bool(bayer_rggb8))))
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "Frontend::ObserveDeviceImage")
         return added
 
     def observe_compressed_image(self, left: bytes, right: bytes, bayer_rggb8: bool = False, time: float = 0.0,
@@ -336,6 +362,7 @@ class FrontendGroup:
             m = Frontend.__new__(Frontend)
             m._h = lib().vsfh_group_member(self._h, i)
             m.cap = nfeatures + 256
+            m.size, m.device = (width, height), device
             m.close = lambda: None  # (the group owns its members)
             self.members.append(m)
 
@@ -367,6 +394,14 @@ class FrontendGroup:
         added = bool(lib().vsfh_group_observe_image(self._h, i, _p(left), _p(right), left.shape[1], left.shape[0],
                                                     left.strides[0], time))
         self._check(i, "FrontendGroup::ObserveImage")
+        return added
+
+    def observe_device_image(self, i: int, left, right, time: float = 0.0, bayer_rggb8: bool = False, stream=None) -> bool:
+        """FrontendGroup::ObserveDeviceImage(i, ...): Frontend.observe_device_image for member i."""
+        m = self.members[i]
+        lp, ls, rp, rs, s = _device_frame(left, right, m.size[0], m.size[1], m.device, stream)
+        added = bool(lib().vsfh_group_observe_device_image(self._h, i, lp, ls, rp, rs, s, time, int(bool(bayer_rggb8))))
+        self._check(i, "FrontendGroup::ObserveDeviceImage")
         return added
 
     def observe_compressed_image(self, i: int, left: bytes, right: bytes, bayer_rggb8: bool = False, time: float = 0.0,

@@ -229,6 +229,13 @@ int vsfh_group_observe_compressed_image(void* g, int i, const uint8_t* left, siz
              ? 1
              : 0;
 }
+int vsfh_group_observe_device_image(void* g, int i, const void* left, size_t left_pitch, const void* right, size_t right_pitch,
+                                    void* hip_stream, double time, int bayer_rggb8) {
+  return static_cast<slam::FrontendGroup*>(g)->ObserveDeviceImage(i, left, left_pitch, right, right_pitch, hip_stream, time,
+                                                                   bayer_rggb8 != 0)
+             ? 1
+             : 0;
+}
 // vsf_observe_stats of the group's context (out[0..n)).
 int vsfh_group_queue_stats(void* g, int64_t* out, int n) {
   vsf_ctx* c = static_cast<slam::FrontendGroup*>(g)->context();
@@ -249,6 +256,11 @@ int vsfh_observe_image(void* f, const uint8_t* left, const uint8_t* right, int w
 int vsfh_observe_compressed_image(void* f, const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
                                   int bayer_rggb8, double time) {
   return static_cast<Frontend*>(f)->ObserveCompressedImage(left, left_bytes, right, right_bytes, bayer_rggb8 != 0, time) ? 1 : 0;
+}
+
+int vsfh_observe_device_image(void* f, const void* left, size_t left_pitch, const void* right, size_t right_pitch,
+                              void* hip_stream, double time, int bayer_rggb8) {
+  return static_cast<Frontend*>(f)->ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time, bayer_rggb8 != 0) ? 1 : 0;
 }
 
 unsigned long long vsfh_refused_frames(void* f) { return static_cast<Frontend*>(f)->refused_frames(); }

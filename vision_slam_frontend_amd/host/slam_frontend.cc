@@ -602,7 +602,11 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   while ((int)in_flight() >= queue_depth())
     if (!retire()) return false;
   PendingFrame& pf = pending_[(pending_head_ + pending_count_) % pending_.size()];
-  if (fp.compressed)  // (a file the host half of the decoders refuses: no ticket, nothing booked, the queue as it was)
+  if (fp.device) {  // (already in HBM: one launch on the producer's stream, no staging copy, no upload)
+    const vsf_dev_frame df{fp.left, fp.right, fp.left_bytes, fp.right_bytes};
+    last_status_ = vsf_observe_submit_dev(ctx_, stream_, &df, 1, fp.bayer ? VSF_PIX_BAYER_RGGB8 : VSF_PIX_MONO8, fp.hip_stream,
+                                          &calib, config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
+  } else if (fp.compressed)  // (a file the host half of the decoders refuses: no ticket, nothing booked, the queue as it was)
     last_status_ = vsf_observe_submit_compressed_stream(ctx_, stream_, fp.left, fp.left_bytes, fp.right, fp.right_bytes,
                                                         fp.bayer ? 1 : 0, &calib, config_.best_percent_,
                                                         (int)config_.frame_life_, &pf.ticket);
@@ -797,6 +801,37 @@ bool Frontend::ObserveCompressedImage(const uint8_t* left, size_t left_bytes, co
   fp.right_bytes = right_bytes;
   fp.compressed = true;
   fp.bayer = bayer_rggb8;
+  return ObserveFused(width, height, fp);
+}
+
+// cc:400-472 for a frame that is in device memory already.
+bool Frontend::ObserveDeviceImage(const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
+                                  double /*time*/, bool bayer_rggb8) {
+  if (!OdomCheck()) return false;
+  if (!fused_ || config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::ORB ||
+      config_.orb_nfeatures + 256 >= 65536 || config_.frame_life_ < 1 || config_.frame_life_ + 1 > 64) {
+    last_status_ = VSF_ERR_UNSUPPORTED;  // device frames exist in the queue only
+    return false;
+  }
+  int width = config_.image_width, height = config_.image_height;
+  if (ctx_) {
+    vsf_params p;
+    vsf_get_params(ctx_, &p);
+    width = p.width;
+    height = p.height;
+  }
+  if (!left || !right || width < 1 || height < 1) {  // (a pointer says nothing about a size: the configuration must)
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return false;
+  }
+  FramePayload fp;
+  fp.left = static_cast<const uint8_t*>(left);
+  fp.right = static_cast<const uint8_t*>(right);
+  fp.left_bytes = left_pitch;
+  fp.right_bytes = right_pitch;
+  fp.device = true;
+  fp.bayer = bayer_rggb8;
+  fp.hip_stream = hip_stream;
   return ObserveFused(width, height, fp);
 }
 

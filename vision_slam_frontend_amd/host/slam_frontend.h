@@ -146,6 +146,15 @@ class Frontend {
   // getDebugImages() / getDebugStereoImages() hold canvases drawn on the GPU from the DECODED (and demosaiced) images.
   bool ObserveCompressedImage(const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
                               bool bayer_rggb8, double time);
+  // The same frame when it ALREADY LIVES IN DEVICE MEMORY (a tensor, a decoder's or camera SDK's buffer, the caller's own
+  // kernel's output): two images of the context's size (config.image_width x image_height, or whatever earlier frames
+  // were) on the context's device, any base address, any pitch >= width, stream-ordered on `hip_stream` (a hipStream_t;
+  // NULL: the default stream) like hipMemcpyAsync -- the images may still be being produced by work queued on that stream
+  // and may be overwritten by work queued on it after the call (vsf_observe_submit_dev).  bayer_rggb8: the images are
+  // mosaics (COLOR_BayerBG2BGR + COLOR_BGR2GRAY on the device).  OdomCheck and the bookkeeping are ObserveImage's;
+  // synchronous or pipelined; the problem is the one ObserveImage builds from the same pixels, byte for byte.
+  bool ObserveDeviceImage(const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
+                          double time, bool bayer_rggb8 = false);
   void ObserveOdometry(const Vector3f& translation, const Quaternionf& rotation, double timestamp);
   void GetSLAMProblem(slam_types::SLAMProblem* problem) const;
   int GetNumPoses();
@@ -249,11 +258,13 @@ class Frontend {
   int debug_file_form() const { return (config_.debug_jpeg_quality_ > 0 ? kFormJpeg : 0) | (config_.debug_png_ ? kFormPng : 0); }
   const char* debug_file_format() const { return (debug_file_form() & kFormPng) ? "png" : "jpeg"; }  // CompressedView::format
   bool ObserveImageFused(const Image& left_image, const Image& right_image);
-  struct FramePayload {  // what a frame brings to the queue: two raw images at `step`, or two compressed files
+  struct FramePayload {  // what a frame brings to the queue: two raw images at `step`, two compressed files, or two
+                         // images in device memory at left_bytes / right_bytes per row, ordered on `hip_stream`
     const uint8_t* left = nullptr;
     const uint8_t* right = nullptr;
     size_t step = 0, left_bytes = 0, right_bytes = 0;
-    bool compressed = false, bayer = false;
+    bool compressed = false, bayer = false, device = false;
+    void* hip_stream = nullptr;
   };
   bool ObserveFused(int width, int height, const FramePayload& fp);
   void FinishNode(const Frame& curr_frame, const std::vector<slam_types::VisionFeature>& features);
@@ -345,6 +356,10 @@ class FrontendGroup {
   }
   bool ObserveImage(int i, const Image& left_image, const Image& right_image, double time) {
     return member(i).ObserveImage(left_image, right_image, time);
+  }
+  bool ObserveDeviceImage(int i, const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
+                          double time, bool bayer_rggb8 = false) {
+    return member(i).ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time, bayer_rggb8);
   }
   bool ObserveCompressedImage(int i, const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
                               bool bayer_rggb8, double time) {
