@@ -359,6 +359,32 @@ vsf_status vsf_vision_features_batch_dev(vsf_ctx* ctx, const vsf_calibration* ca
                                          const uint8_t* d_desc, const int32_t* d_counts, int n_frames,
                                          vsf_vision_feature* d_features, int32_t* d_nfeatures, int32_t* d_npoints);
 
+/* ---------------- The RViz point cloud of the reference's driver (slam_frontend_main.cc:155-173, 194-225) ----------------
+ * slam_types::RobotPose as the driver's PublishVisualization reads it from a SLAMNode: Translation3f(loc) * Quaternionf. */
+typedef struct {
+  float loc[3];
+  float quat_xyzw[4];
+} vsf_pose;
+/* AddFeaturePoints for n_frames frames whose vsf_vision_feature records are in device memory (the layouts of
+ * vsf_vision_features_batch_dev's d_features / d_nfeatures).  Frame f keeps, IN FEATURE ORDER, every feature whose point3d
+ * has three finite coordinates, (double)z > 0.1, (double)norm > 0.5 and (double)norm < 20.0 -- norm the float sqrtf of the
+ * float sum of squares, as Vector3f::norm() -- and writes M_f * point3d widened to double, three consecutive doubles per point
+ * (the body of a geometry_msgs/Point[]): d_points [n_frames][max_keypoints][3], d_npoints [n_frames].  M_f =
+ * (Translation(poses[f].loc) * poses[f].quat) * cam_to_robot, evaluated in float; `poses` (n_frames of them) and cam_to_robot
+ * (3 x 4 row-major: config.left_cam_to_robot) are HOST memory, read before the call returns.  Nothing is written behind
+ * d_npoints[f] points of a frame.  The zero points of quirk Q5 have norm 0 and fall out by the predicate.  Rounding and
+ * summation order: vision_slam_frontend_amd/csrc/vsf_world_points.h, which the host mirror's AddFeaturePoints includes as well
+ * -- the two agree bit for bit.  Deterministic (no atomics); asynchronous on the context's stream like every *_dev call. */
+vsf_status vsf_world_points_batch_dev(vsf_ctx* ctx, const vsf_vision_feature* d_features, const int32_t* d_nfeatures,
+                                      int n_frames, const vsf_pose* poses, const float cam_to_robot[12], double* d_points,
+                                      int32_t* d_npoints);
+
+/* The same for ONE frame whose records are in HOST memory, synchronous (upload, the kernel, download): what the host
+ * Frontend's per-call mode runs once per node.  points_out holds `cap` points of three doubles; *n_out = points kept
+ * (VSF_ERR_CAPACITY and nothing copied if that is more than cap; n_features above max_keypoints likewise). */
+vsf_status vsf_world_points(vsf_ctx* ctx, const vsf_vision_feature* features, int n_features, const vsf_pose* pose,
+                            const float cam_to_robot[12], double* points_out, int cap, int* n_out);
+
 /* Compact output payload of a batch (what a rank sends to rank 0): counts first, then records sized by the counts.
  *   u32 magic 'VSF1', n_frames, n_pairs, total_bytes | u32 nfeatures[n_frames] | u32 npairs[n_pairs] |
  *   vsf_vision_feature x sum(nfeatures), frame after frame | vsf_feature_match x sum(npairs), pair after pair
@@ -543,7 +569,7 @@ size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth);
  * carried frames of more than one stream; [17] device frames launched (vsf_observe_submit_dev), [18] kernel launches and
  * copy commands the device path issued (a submit's one launch, a batch's copies out of the ring, its demosaic where no
  * compressed frame brings one), [19] bytes of the device ring -- the last three are 0 for a queue that has seen no device
- * frame }. */
+ * frame; [20] .. [22] the point cloud's (vsf_observe_set_world_points) }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,
@@ -585,6 +611,31 @@ vsf_status vsf_observe_set_debug_png(vsf_ctx* ctx, int on);
  * vsf_observe_debug_view.  VSF_ERR_CAPACITY if a file did not fit its slot (the bound of vsf_png_encode_capacity rules it out). */
 vsf_status vsf_observe_debug_png_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
                                       const uint8_t** match, size_t* match_bytes);
+
+/* The queue's point cloud: with the switch on, every batch's tail also runs vsf_world_points_batch_dev's kernel over the
+ * VisionFeature records it has just made -- ONE more launch per batch, which writes each frame's points and their count
+ * straight into the frame's slot of a pinned ring of points (depth x max_keypoints x 24 bytes, built only when the switch is
+ * on; like the result ring it is written by the kernel itself, so no copy command and no host wait are added).  A node's pose
+ * never changes once it is booked, so what the caller keeps is append-only: the concatenation of the collected frames' views.
+ *   cam_to_robot: 3 x 4 row-major, config.left_cam_to_robot; read when `on` is not 0 (it may be NULL otherwise).
+ *   Callable before the queue's first frame or after vsf_observe_reset, like vsf_observe_set_debug_images (the queue is then
+ * rebuilt with the thresholds carried over); VSF_ERR_INVALID_ARG once the queue has issued a ticket.  The same switch with the
+ * same matrix again changes nothing and is always accepted.
+ *   Off (the default): results, launches, copies and their cost are exactly those without the call.  On or off, the result
+ * record of vsf_observe_collect and vsf_observe_capacity are byte for byte the same.
+ *   vsf_observe_stats values [20] frames whose points were launched, [21] kernel launches + copy commands of this path (one
+ * per batch), [22] bytes of the ring of points and its counts: all 0 while the switch is off. */
+vsf_status vsf_observe_set_world_points(vsf_ctx* ctx, int on, const float* cam_to_robot);
+/* The pose the frames submitted AFTERWARDS on queue stream `stream` carry -- what Frontend::ObserveOdometry is to
+ * ObserveImage.  Sticky; identity (loc 0, quaternion 0 0 0 1) at first; captured by each of the five submit calls when it is
+ * made, so it may change between any two frames.  vsf_observe_reset_stream puts that stream's pose back to identity,
+ * vsf_observe_reset every stream's.  Host bookkeeping only: it never waits, sends nothing, and is legal at any time, also with
+ * the switch off (the pose is then never read).  loc: 3 floats, quat_xyzw: 4 floats. */
+vsf_status vsf_observe_set_pose(vsf_ctx* ctx, int stream, const float* loc, const float* quat_xyzw);
+/* A collected frame's points inside the pinned ring: *xyz points at *n points of three doubles (NULL where n is 0); lifetime
+ * and ticket rules of vsf_observe_debug_view (collected, and fewer than `depth` frames submitted since).
+ * VSF_ERR_INVALID_ARG with the switch off. */
+vsf_status vsf_observe_world_points_view(vsf_ctx* ctx, int64_t ticket, const double** xyz, int32_t* n);
 
 /* ---------------- Host checks of the compressed path (no context, no device) ----------------
  * What vsf_observe_submit_compressed computes and checks on the host, callable on their own so that tests without a GPU --

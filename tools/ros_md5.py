@@ -33,15 +33,28 @@ GEOMETRY = {
     "geometry_msgs/Point": "float64 x\nfloat64 y\nfloat64 z\n",
     "geometry_msgs/Vector3": "float64 x\nfloat64 y\nfloat64 z\n",
     "geometry_msgs/Quaternion": "float64 x\nfloat64 y\nfloat64 z\nfloat64 w\n",
+    "geometry_msgs/Pose": "Point position\nQuaternion orientation\n",
 }
 KNOWN = {"geometry_msgs/Point": "4a842b65f413084dc2b10fb484ea7f17", "geometry_msgs/Vector3": "4a842b65f413084dc2b10fb484ea7f17",
          "geometry_msgs/Quaternion": "a779879fadf0160734f906b8c19c7004",
-         "std_msgs/Header": "2176decaecbce78abc3b96ef049fabed", "sensor_msgs/CompressedImage": "8f7a12909da2c9d3332d540a0977563f"}
+         "std_msgs/Header": "2176decaecbce78abc3b96ef049fabed", "sensor_msgs/CompressedImage": "8f7a12909da2c9d3332d540a0977563f",
+         "geometry_msgs/Pose": "e45d45a5a1ce597b249e23fb30fc871f", "std_msgs/ColorRGBA": "a29a96539573343b1310c73607334b00"}
 # The one message of another package the host serialises: sensor_msgs/CompressedImage (the debug images as JPEG files), with the
 # std_msgs/Header it starts with.  Field lists of ROS-1's common_msgs / std_msgs; not part of table() (the package's own nine).
 EXTERNAL = {
     "std_msgs/Header": "uint32 seq\ntime stamp\nstring frame_id\n",
     "sensor_msgs/CompressedImage": "Header header\nstring format\nuint8[] data\n",
+    # ... and the two the driver's PublishVisualization sends to RViz (host/slam_visualization.h, slam_to_ros.h SerializeMarker /
+    # SerializeMarkerArray): visualization_msgs/Marker as ROS-1 ships it since DELETEALL was added (Jade), and MarkerArray
+    "std_msgs/ColorRGBA": "float32 r\nfloat32 g\nfloat32 b\nfloat32 a\n",
+    "visualization_msgs/Marker": (
+        "uint8 ARROW=0\nuint8 CUBE=1\nuint8 SPHERE=2\nuint8 CYLINDER=3\nuint8 LINE_STRIP=4\nuint8 LINE_LIST=5\nuint8 CUBE_LIST=6\n"
+        "uint8 SPHERE_LIST=7\nuint8 POINTS=8\nuint8 TEXT_VIEW_FACING=9\nuint8 MESH_RESOURCE=10\nuint8 TRIANGLE_LIST=11\n"
+        "uint8 ADD=0\nuint8 MODIFY=0\nuint8 DELETE=2\nuint8 DELETEALL=3\n"
+        "Header header\nstring ns\nint32 id\nint32 type\nint32 action\ngeometry_msgs/Pose pose\ngeometry_msgs/Vector3 scale\n"
+        "std_msgs/ColorRGBA color\nduration lifetime\nbool frame_locked\ngeometry_msgs/Point[] points\n"
+        "std_msgs/ColorRGBA[] colors\nstring text\nstring mesh_resource\nbool mesh_use_embedded_materials\n"),
+    "visualization_msgs/MarkerArray": "Marker[] markers\n",
 }
 NAMES = ["CameraExtrinsics", "CameraIntrinsics", "FeatureMatch", "OdometryFactor", "RobotPose", "SLAMNode", "SLAMProblem",
          "VisionFactor", "VisionFeature"]
@@ -89,6 +102,12 @@ def table() -> dict:
     return {n: md5("%s/%s" % (PACKAGE, n)) for n in NAMES}
 
 
+def marker_md5s() -> tuple:
+    """md5sums of visualization_msgs/Marker and MarkerArray (slam_to_ros.h: kMarkerMd5, kMarkerArrayMd5)."""
+    table()
+    return md5("visualization_msgs/Marker"), md5("visualization_msgs/MarkerArray")
+
+
 def compressed_image_md5() -> str:
     """md5sum of sensor_msgs/CompressedImage (slam_to_ros.h: kCompressedImageMd5)."""
     table()
@@ -101,6 +120,7 @@ if __name__ == "__main__":
         for n in NAMES:
             print('constexpr const char* kMd5%s = "%s";' % (n, t[n]))
         print('constexpr const char* kCompressedImageMd5 = "%s";' % compressed_image_md5())
+        print('constexpr const char* kMarkerMd5 = "%s";\nconstexpr const char* kMarkerArrayMd5 = "%s";' % marker_md5s())
     else:
         for n in NAMES:
             print("%s  %s/%s" % (t[n], PACKAGE, n))

@@ -46,6 +46,8 @@ EXPORTS = [
     "vsf_png_encode_capacity", "vsf_png_encode_batch_dev", "vsf_png_encode", "vsf_debug_png_encode_header", "vsf_debug_png_encode_cpu", "vsf_observe_set_debug_png", "vsf_observe_debug_png_view",
     "vsf_observe_set_streams", "vsf_observe_submit_stream", "vsf_observe_submit_compressed_stream", "vsf_observe_reset_stream",
     "vsf_observe_submit_dev", "vsf_observe_device_ring_bytes",
+    "vsf_world_points_batch_dev", "vsf_world_points", "vsf_observe_set_world_points", "vsf_observe_set_pose",
+    "vsf_observe_world_points_view",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -55,7 +57,8 @@ STAGE_COUNT = 8
 # vsf_observe_stats' values, in order (include/vsf.h)
 OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
                  "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands", "streams",
-                 "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes")
+                 "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes",
+                 "world_points_frames", "world_points_commands", "world_points_ring_bytes")
 # vsf_observe_submit_dev's pixel formats (include/vsf.h)
 PIX_MONO8, PIX_BAYER_RGGB8 = 0, 1
 
@@ -243,6 +246,11 @@ def lib() -> C.CDLL:
         L.vsf_stereo_thresholds_dev.argtypes = [vp, vp, i32, vp, vp]
         L.vsf_stereo_filter_batch_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.vsf_vision_features_batch_dev.argtypes = [vp, C.POINTER(VsfCalibration), vp, vp, vp, i32, vp, vp, vp]
+        L.vsf_world_points_batch_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+        L.vsf_world_points.argtypes = [vp, vp, i32, vp, vp, vp, i32, ip]
+        L.vsf_observe_set_world_points.argtypes = [vp, i32, vp]
+        L.vsf_observe_set_pose.argtypes = [vp, i32, vp, vp]
+        L.vsf_observe_world_points_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(i32)]
         L.vsf_packed_outputs_capacity.argtypes = [vp, i32, i32]
         L.vsf_packed_outputs_capacity.restype = sz
         L.vsf_pack_outputs_dev.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, sz]
@@ -552,6 +560,51 @@ class Context:
         self._check(lib().vsf_vision_features_batch_dev(self._h, C.byref(calib), _p(d_kp), _p(d_desc), _p(d_counts),
                                                         n_frames, _p(d_features), _p(d_nfeatures), _p(d_npoints)),
                     "vsf_vision_features_batch_dev")
+
+    def world_points_batch_dev(self, d_features: int, d_nfeatures: int, n_frames: int, poses, cam_to_robot, d_points: int,
+                               d_npoints: int):
+        """AddFeaturePoints of n_frames frames on the device (vsf_world_points_batch_dev).  poses: (n_frames, 7) float32
+        rows of loc xyz + quaternion xyzw (vsf_pose); cam_to_robot: 3 x 4 float32, row-major."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(n_frames, 7)
+        c = np.ascontiguousarray(cam_to_robot, np.float32).reshape(12)
+        self._check(lib().vsf_world_points_batch_dev(self._h, _p(d_features), _p(d_nfeatures), n_frames, _p(poses), _p(c),
+                                                     _p(d_points), _p(d_npoints)), "vsf_world_points_batch_dev")
+
+    def world_points(self, features: np.ndarray, pose, cam_to_robot) -> np.ndarray:
+        """The same for one frame's VISION_FEATURE_DTYPE records in host memory (vsf_world_points): the (n, 3) float64 points."""
+        f = np.ascontiguousarray(features, VISION_FEATURE_DTYPE)
+        pose = np.ascontiguousarray(pose, np.float32).reshape(7)
+        c = np.ascontiguousarray(cam_to_robot, np.float32).reshape(12)
+        out = np.zeros((max(len(f), 1), 3), np.float64)
+        n = C.c_int(0)
+        self._check(lib().vsf_world_points(self._h, _p(f), len(f), _p(pose), _p(c), _p(out), len(f), C.byref(n)), "vsf_world_points")
+        return out[:n.value].copy()
+
+    def observe_set_world_points(self, on: bool, cam_to_robot=None, allow_status=()) -> int:
+        """The queue's point cloud (vsf_observe_set_world_points); cam_to_robot: 3 x 4 float32, row-major.  Returns the status."""
+        c = None if cam_to_robot is None else np.ascontiguousarray(cam_to_robot, np.float32).reshape(12)
+        st = lib().vsf_observe_set_world_points(self._h, int(bool(on)), _p(c) if c is not None else None)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_set_world_points", lib().vsf_last_hip_error(self._h))
+        return st
+
+    def observe_set_pose(self, stream: int, loc, quat_xyzw):
+        """The pose the frames submitted afterwards on `stream` carry (vsf_observe_set_pose)."""
+        l = np.ascontiguousarray(loc, np.float32).reshape(3)
+        q = np.ascontiguousarray(quat_xyzw, np.float32).reshape(4)
+        self._check(lib().vsf_observe_set_pose(self._h, stream, _p(l), _p(q)), "vsf_observe_set_pose")
+
+    def observe_world_points(self, ticket: int, allow_status=()):
+        """A collected frame's points (vsf_observe_world_points_view), copied: an (n, 3) float64 array -- or, with
+        `allow_status`, (status, array)."""
+        ptr, n = C.c_void_p(), C.c_int32(0)
+        st = lib().vsf_observe_world_points_view(self._h, C.c_int64(ticket), C.byref(ptr), C.byref(n))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_world_points_view", lib().vsf_last_hip_error(self._h))
+        pts = np.zeros((0, 3), np.float64)
+        if st == VSF_OK and n.value > 0:
+            pts = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_double)), shape=(n.value, 3)).copy()
+        return (st, pts) if allow_status else pts
 
     def packed_outputs_capacity(self, n_frames: int, n_pairs: int) -> int:
         return int(lib().vsf_packed_outputs_capacity(self._h, n_frames, n_pairs))

@@ -516,6 +516,7 @@ vsf_status vsf_create(const vsf_params* p, int device, vsf_ctx** out) {
   ctx->p = *p;
   if (ctx->p.max_keypoints <= 0) ctx->p.max_keypoints = ctx->p.nfeatures + 256;
   ctx->device = device;
+  for (vsf_pose& pose : ctx->ob_pose) pose = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 1.f}};  // vsf_observe_set_pose: identity at first
   auto fail = [&](vsf_status s) {
     vsf_destroy(ctx);
     return s;

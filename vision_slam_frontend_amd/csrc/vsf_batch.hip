@@ -227,6 +227,28 @@ vsf_status vsf_vision_features_batch_dev(vsf_ctx* ctx, const vsf_calibration* ca
   return VSF_OK;
 }
 
+vsf_status vsf_world_points_batch_dev(vsf_ctx* ctx, const vsf_vision_feature* d_features, const int32_t* d_nfeatures,
+                                      int n_frames, const vsf_pose* poses, const float cam_to_robot[12], double* d_points,
+                                      int32_t* d_npoints) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !d_features || !d_nfeatures || n_frames < 1 || !poses || !cam_to_robot || !d_points || !d_npoints ||
+      ((uintptr_t)d_points & 7))
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // M_f of every frame on the host (vsf_world_points.h: the same statements the CPU restatement runs), handed over in the
+  // kernel arguments: no copy command, no scratch, nothing that could wait
+  for (int f0 = 0; f0 < n_frames; f0 += VSF_WORLD_CHUNK) {
+    const int n = std::min(VSF_WORLD_CHUNK, n_frames - f0);
+    VsfWorldTransforms tf;
+    for (int f = 0; f < n; f++) tf.m[f] = vsfwp::camera_to_world(poses[f0 + f].loc, poses[f0 + f].quat_xyzw, cam_to_robot);
+    for (int f = n; f < VSF_WORLD_CHUNK; f++) tf.m[f] = vsfwp::Affine{};
+    StageTimer t(ctx, ctx->stream, VSF_STAGE_TAIL, 1);
+    vsf_launch_world_points(d_features, d_nfeatures, f0, n, ctx->p.max_keypoints, tf, d_points, d_npoints, ctx->stream);
+  }
+  VSF_STICKY();
+  return VSF_OK;
+}
+
 size_t vsf_packed_outputs_capacity(const vsf_ctx* ctx, int n_frames, int n_pairs) {
   if (!ctx || n_frames < 0 || n_pairs < 0) return 0;
   const size_t K = (size_t)ctx->p.max_keypoints;

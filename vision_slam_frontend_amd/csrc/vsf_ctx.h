@@ -136,6 +136,7 @@ struct vsf_ctx {
     hipStream_t dev_stream = nullptr;  // ... and the producer's stream it was recorded on (a view)
     int stream = 0;              // vsf_observe_submit_stream: whose sequence it belongs to
     int64_t k = 0;               // frames of its stream in front of it (since the queue was built or the stream reset)
+    vsf_pose pose{};             // vsf_observe_set_pose: what its stream's pose was when it was submitted (read with `cloud`)
   };
   struct ObserveStream {  // host side of one sequence of frames (vsf_observe_set_streams)
     int64_t frames = 0;        // submitted since the queue was built or the stream was reset: the next frame's k
@@ -157,6 +158,12 @@ struct vsf_ctx {
     bool ready = false;
     int frame_life = 0;
     bool debug = false;  // built with ob_debug: the batches' tails draw the debug images
+    // vsf_observe_set_world_points: built with ob_cloud -- the batches' tails run k_cloud.hip's kernel, which writes each frame's
+    // points and their count into the frame's slot of these pinned rings (nothing of this exists with the switch off)
+    bool cloud = false;
+    float cam_to_robot[12] = {0};
+    vsfi::PinnedBuf<double> h_wp;     // pinned [depth][K][3]
+    vsfi::PinnedBuf<int32_t> h_wp_n;  // pinned [depth]
     // debug images: device canvases [bmax][dbg_stride], winners [bmax][3 w h], operations [bmax][5 K], canvas table [2 bmax],
     // the newest kept frame's keypoints, {colour cursor (i64), its count}; pinned: the debug ring [depth][dbg_stride] and the
     // colour ring [col_ring] (colours drawn: col_generated, taken by collected frames: col_retired)
@@ -233,6 +240,9 @@ struct vsf_ctx {
   int ob_depth = 0, ob_min_batch = 0, ob_in_flight = 2;
   int ob_streams = 1;  // vsf_observe_set_streams
   bool ob_debug = false;  // vsf_observe_set_debug_images: the queue draws the debug images
+  bool ob_cloud = false;   // vsf_observe_set_world_points: the queue makes the point cloud ...
+  float ob_cam_to_robot[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};  // ... with this left_cam_to_robot (3 x 4 row-major)
+  vsf_pose ob_pose[VSF_OBSERVE_MAX_STREAMS];  // vsf_observe_set_pose: each stream's sticky pose (identity: vsf_create)
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----
@@ -308,6 +318,7 @@ struct vsf_ctx {
   vsfi::DevBuf<vsf_dmatch> mm_matches;
   vsfi::DevBuf<int32_t> mm_nmatches;
   int mm_sets = 0, mm_rows = 0;
+  vsfi::DevBuf<uint8_t> wp_buf;  // vsf_world_points (host pointers): one frame's records | its points | {nfeatures, npoints}
   VsfImages last_images{};
   bool last_valid = false;
   bool fast_nms = true;  // NMS mode the standalone-FAST geometry was built for

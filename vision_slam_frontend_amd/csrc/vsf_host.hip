@@ -248,6 +248,39 @@ vsf_status vsf_get_matches_multi(vsf_ctx* ctx, const uint8_t* const* q, const in
   return st;
 }
 
+// vsf_world_points_batch_dev for ONE frame whose records are in host memory (what the host Frontend's per-call mode runs
+// once per node): upload, the kernel, download, wait.
+vsf_status vsf_world_points(vsf_ctx* ctx, const vsf_vision_feature* features, int n_features, const vsf_pose* pose,
+                            const float cam_to_robot[12], double* points_out, int cap, int* n_out) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || n_features < 0 || (n_features > 0 && !features) || !pose || !cam_to_robot || !n_out || cap < 0 ||
+      (cap > 0 && !points_out))
+    return VSF_ERR_INVALID_ARG;
+  *n_out = 0;
+  const size_t K = (size_t)ctx->p.max_keypoints;
+  if ((size_t)n_features > K) return VSF_ERR_CAPACITY;
+  VSF_HIP(hipSetDevice(ctx->device));
+  const size_t off_points = (K * sizeof(vsf_vision_feature) + 15) & ~(size_t)15, off_ints = off_points + K * 3 * sizeof(double);
+  if (!ctx->wp_buf) VSF_HIP(ctx->wp_buf.alloc(off_ints + 16));
+  vsf_vision_feature* d_features = reinterpret_cast<vsf_vision_feature*>(ctx->wp_buf.get());
+  double* d_points = reinterpret_cast<double*>(ctx->wp_buf + off_points);
+  int32_t* d_ints = reinterpret_cast<int32_t*>(ctx->wp_buf + off_ints);
+  const int32_t nf = n_features;
+  if (n_features > 0)
+    VSF_HIP(hipMemcpyAsync(d_features, features, (size_t)n_features * sizeof(vsf_vision_feature), hipMemcpyHostToDevice, ctx->stream));
+  VSF_HIP(hipMemcpyAsync(d_ints, &nf, sizeof(nf), hipMemcpyHostToDevice, ctx->stream));
+  const vsf_status st = vsf_world_points_batch_dev(ctx, d_features, d_ints, 1, pose, cam_to_robot, d_points, d_ints + 1);
+  if (st != VSF_OK) return st;
+  int32_t n = 0;
+  VSF_HIP(hipMemcpyAsync(&n, d_ints + 1, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+  VSF_HIP(hipStreamSynchronize(ctx->stream));
+  if (n < 0 || n > n_features) return VSF_ERR_HIP;
+  *n_out = n;
+  if (n > cap) return VSF_ERR_CAPACITY;
+  if (n > 0) VSF_HIP(hipMemcpy(points_out, d_points, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return VSF_OK;
+}
+
 vsf_status vsf_knn2_hamming(vsf_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx2,
                             int32_t* dist2) {
   VsfErrorScope scope_(ctx);

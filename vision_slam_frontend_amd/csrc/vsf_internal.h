@@ -10,6 +10,7 @@
 #include "../../include/vsf.h"
 #include "vsf_own.h"     // DevBuf, PinnedBuf, Event, Stream
 #include "vsf_fast_split.h"  // which FAST cells are full waves, and where their list is cut by level
+#include "vsf_world_points.h"  // the point cloud's arithmetic, shared with the host's AddFeaturePoints
 #include "vsf_resize.h"  // VsfTap, the resize coefficient formula, the packing plan
 
 // FAST march kernel: a wave owns a band of 248 keypoint columns (lanes 1..62 x 4 px; lanes 0 and 63 carry the raw halo
@@ -281,6 +282,19 @@ void vsf_launch_vision_features_table(const vsf_keypoint* d_kp, const int32_t* d
                                       const int32_t* d_npairs, int n_frames, int max_rows, const VsfObserveParam* d_par,
                                       const vsf_calibration* d_calibs, vsf_vision_feature* d_out, int32_t* d_nfeatures,
                                       int32_t* d_npoints, hipStream_t s);
+// The RViz point cloud (k_cloud.hip; arithmetic: vsf_world_points.h): per frame the features that pass AddFeaturePoints'
+// predicate, in feature order, as M_f * point3d in three doubles.  The stand-alone call carries up to VSF_WORLD_CHUNK
+// transforms in the kernel arguments (frames [f0, f0 + n_frames), frame f to slot f); the queue's batch reads them from its
+// pinned block and writes frame f's points and count into slot frames[f].out_slot of pinned rings.
+#define VSF_WORLD_CHUNK 64
+struct VsfWorldTransforms {
+  vsfwp::Affine m[VSF_WORLD_CHUNK];
+};
+void vsf_launch_world_points(const vsf_vision_feature* d_features, const int32_t* d_nfeatures, int f0, int n_frames, int max_rows,
+                             const VsfWorldTransforms& tf, double* d_points, int32_t* d_npoints, hipStream_t s);
+void vsf_launch_world_points_table(const vsf_vision_feature* d_features, const int32_t* d_nfeatures, int n_frames, int max_rows,
+                                   const vsfwp::Affine* tf, const VsfObserveFrame* frames, double* points, int32_t* npoints,
+                                   hipStream_t s);
 struct VsfObserveArgs {
   int n_frames, max_rows;
   const int32_t* counts_raw;          // [2n] keypoints of the left / right images

@@ -45,7 +45,7 @@ struct vsf_ctx::ObserveBatchMeta {
   // followed by (offsets in int32 words from the start of the block, fixed by the queue's sizes):
   //   q_set[max_pairs] | t_set[max_pairs] | best_percent[max_pairs] (float) | out_sets[2 bmax] | frames[bmax] |
   //   params[bmax] | calibs[bmax] -- the last two are written and read only by a batch that holds more than one stream or
-  //   more than one calibration
+  //   more than one calibration -- | transforms[bmax]: M_f of every frame, written and read only with the point cloud on
 };
 
 namespace {
@@ -58,11 +58,12 @@ struct MetaView {
   VsfObserveFrame* frames;
   VsfObserveParam* params;
   vsf_calibration* calibs;
+  vsfwp::Affine* transforms;
 };
 
 size_t meta_bytes(int max_pairs, int bmax) {
   return 16 + (size_t)max_pairs * 12 + (size_t)bmax * 8 +
-         (size_t)bmax * (sizeof(VsfObserveFrame) + sizeof(VsfObserveParam) + sizeof(vsf_calibration));
+         (size_t)bmax * (sizeof(VsfObserveFrame) + sizeof(VsfObserveParam) + sizeof(vsf_calibration) + sizeof(vsfwp::Affine));
 }
 
 MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
@@ -75,6 +76,7 @@ MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
   v.frames = reinterpret_cast<VsfObserveFrame*>(v.out_sets + 2 * bmax);
   v.params = reinterpret_cast<VsfObserveParam*>(v.frames + bmax);
   v.calibs = reinterpret_cast<vsf_calibration*>(v.params + bmax);
+  v.transforms = reinterpret_cast<vsfwp::Affine*>(v.calibs + bmax);
   return v;
 }
 
@@ -144,7 +146,9 @@ vsf_status alloc_debug_files(vsf_ctx* ctx) {
 vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   vsf_ctx::Observe& o = ctx->ob;
   const vsf_ctx::DebugForm form = ctx->ob_debug ? ctx->ob_debug_form : vsf_ctx::DebugForm();
-  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.files.form == form) return VSF_OK;
+  if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.files.form == form && o.cloud == ctx->ob_cloud &&
+      (!o.cloud || std::memcmp(o.cam_to_robot, ctx->ob_cam_to_robot, sizeof(o.cam_to_robot)) == 0))
+    return VSF_OK;
   sync_all_streams(ctx);
   const int NS = ctx->ob_streams;
   std::vector<float> thr_state((size_t)NS, 10000.0f);  // cc:353, per stream
@@ -208,6 +212,13 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
       VSF_HIP(o.h_dbg.alloc((size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
     }
     VSF_HIP(o.h_col.alloc((size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
+  }
+  o.cloud = ctx->ob_cloud;
+  if (o.cloud) {  // vsf_observe_set_world_points: the pinned ring of points and its counts, written by the tail's kernel
+    std::memcpy(o.cam_to_robot, ctx->ob_cam_to_robot, sizeof(o.cam_to_robot));
+    VSF_HIP(o.h_wp.alloc((size_t)o.depth * K * 3 * sizeof(double), hipHostMallocMapped));
+    VSF_HIP(o.h_wp_n.alloc((size_t)o.depth * sizeof(int32_t), hipHostMallocMapped));
+    std::memset(o.h_wp_n, 0, (size_t)o.depth * sizeof(int32_t));
   }
   for (vsf_ctx::ObserveBatch& b : o.batch) {
     VSF_HIP(b.d_img.alloc(2 * B * ctx->st_img_stride));
@@ -481,6 +492,11 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   std::memcpy(M.t_set, P.t_set.data(), (size_t)n_pairs * sizeof(int32_t));
   std::memcpy(M.best_percent, P.best_percent.data(), (size_t)n_pairs * sizeof(float));
   if (table) std::memcpy(M.calibs, P.calibs.data(), P.calibs.size() * sizeof(vsf_calibration));
+  if (o.cloud)  // M_f = (Translation(loc) * quat) * cam_to_robot of every frame, from the pose it was submitted with
+    for (int f = 0; f < n; f++) {
+      const vsf_pose& pose = o.frames[(size_t)((t0 + f) % o.depth)].pose;
+      M.transforms[f] = vsfwp::camera_to_world(pose.loc, pose.quat_xyzw, o.cam_to_robot);
+    }
   b.h_meta->n_frames = n;
   b.h_meta->n_pairs = n_pairs;
   // ---- ExtractFeatures x 2 + GetMatches of every frame (cc:411-416) ----
@@ -569,6 +585,14 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
     a.out_cap = (uint32_t)std::min<size_t>(o.out_cap, 0xFFFFFFF0u);
     vsf_launch_observe_pack(a, max_pairs_per_frame, s_tail);
   }
+  if (o.cloud) {
+    // ---- the point cloud (main.cc:155-173): ONE launch over the records just made; each frame's points and their count land
+    // in its slot of the pinned rings, as the result does (no copy command) ----
+    StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 1);
+    vsf_launch_world_points_table(o.features, nfeat, n, Kc, M.transforms, M.frames, o.h_wp, o.h_wp_n, s_tail);
+    stats.cloud_commands++;
+    stats.cloud_frames += n;
+  }
   if (o.debug) {
     const vsf_status st = launch_debug_images(ctx, b, M, t0, n, s_tail);
     if (st != VSF_OK) return st;
@@ -593,6 +617,8 @@ ObserveGpu observe_gpu(vsf_ctx* ctx) {
           [](void* c) { return batches_on_gpu(static_cast<vsf_ctx*>(c)); },
           [](void* c) { return hipSetDevice(static_cast<vsf_ctx*>(c)->device) == hipSuccess; }};
 }
+
+vsf_pose identity_pose() { return {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 1.f}}; }
 
 bool frames_in_queue(const vsf_ctx* ctx) { return ctx->ob.ready && ctx->ob.queue->next_collect != ctx->ob.queue->next_ticket; }
 
@@ -685,6 +711,44 @@ vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on) {
   return st;
 }
 
+vsf_status vsf_observe_set_world_points(vsf_ctx* ctx, int on, const float* cam_to_robot) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || (on != 0 && !cam_to_robot)) return VSF_ERR_INVALID_ARG;
+  if ((on != 0) == ctx->ob_cloud &&
+      (on == 0 || std::memcmp(cam_to_robot, ctx->ob_cam_to_robot, sizeof(ctx->ob_cam_to_robot)) == 0))
+    return VSF_OK;
+  const vsf_status st = retire_unused_queue(ctx);
+  if (st != VSF_OK) return st;
+  ctx->ob_cloud = on != 0;
+  if (on != 0) std::memcpy(ctx->ob_cam_to_robot, cam_to_robot, sizeof(ctx->ob_cam_to_robot));
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_set_pose(vsf_ctx* ctx, int stream, const float* loc, const float* quat_xyzw) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams || !loc || !quat_xyzw) return VSF_ERR_INVALID_ARG;
+  vsf_pose& p = ctx->ob_pose[stream];
+  for (int i = 0; i < 3; i++) p.loc[i] = loc[i];
+  for (int i = 0; i < 4; i++) p.quat_xyzw[i] = quat_xyzw[i];
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_world_points_view(vsf_ctx* ctx, int64_t ticket, const double** xyz, int32_t* n) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !xyz || !n) return VSF_ERR_INVALID_ARG;
+  *xyz = nullptr;
+  *n = 0;
+  const vsf_ctx::Observe& o = ctx->ob;
+  // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_debug_view)
+  if (!o.ready || !o.cloud || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth)
+    return VSF_ERR_INVALID_ARG;
+  const int slot = (int)(ticket % o.depth);
+  const int32_t count = std::min(std::max(o.h_wp_n[slot], 0), ctx->p.max_keypoints);
+  *n = count;
+  if (count > 0) *xyz = o.h_wp + (size_t)slot * ctx->p.max_keypoints * 3;
+  return VSF_OK;
+}
+
 vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || !stereo || !match) return VSF_ERR_INVALID_ARG;
@@ -760,9 +824,10 @@ vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
   if (!ctx || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready) return VSF_OK;  // (nothing to forget)
+  if (o.ready && o.streams[(size_t)stream].uncollected != 0) return VSF_ERR_INVALID_ARG;
+  ctx->ob_pose[stream] = identity_pose();  // (vsf_observe_set_pose: captured by the frames already submitted, all collected)
+  if (!o.ready) return VSF_OK;  // (nothing else to forget)
   vsf_ctx::ObserveStream& st = o.streams[(size_t)stream];
-  if (st.uncollected != 0) return VSF_ERR_INVALID_ARG;
   VSF_HIP(hipSetDevice(ctx->device));
   // Every frame of the stream has been collected: no kernel reads or writes its threshold any more (other streams' tails
   // may be running: they touch their own).  Its window is forgotten by counting its frames from 0 again -- the next frame
@@ -786,19 +851,22 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[20] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+  const int64_t v[23] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
                          s.file_commands, (int64_t)ctx->ob_streams, s.multi,
                          s.device_frames, s.device_commands + o.stat_dev_commands,
-                         (int64_t)(o.d_ring ? vsf_observe_device_ring_bytes(ctx, o.depth) : 0)};
-  for (int i = 0; i < n && i < 20; i++) out[i] = v[i];
+                         (int64_t)(o.d_ring ? vsf_observe_device_ring_bytes(ctx, o.depth) : 0),
+                         s.cloud_frames, s.cloud_commands,
+                         (int64_t)(o.h_wp ? (size_t)o.depth * ((size_t)ctx->p.max_keypoints * 3 * sizeof(double) + sizeof(int32_t)) : 0)};
+  for (int i = 0; i < n && i < 23; i++) out[i] = v[i];
   return VSF_OK;
 }
 
 vsf_status vsf_observe_reset(vsf_ctx* ctx) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx) return VSF_ERR_INVALID_ARG;
+  for (vsf_pose& p : ctx->ob_pose) p = identity_pose();
   return drop_queue(ctx);
 }
 
@@ -882,6 +950,7 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   fr.bayer = bayer;
   fr.calib = *calib;
   fr.best_percent = best_percent;
+  fr.pose = ctx->ob_pose[stream];
   fr.batch = -1;
   vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
   fr.stream = stream;
@@ -1028,6 +1097,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     fr.dev_stream = producer;
     fr.calib = *calib;
     fr.best_percent = best_percent;
+    fr.pose = ctx->ob_pose[stream];
     fr.batch = -1;
     vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
     fr.stream = stream;

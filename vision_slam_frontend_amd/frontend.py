@@ -97,6 +97,20 @@ def lib() -> C.CDLL:
         L.vsfh_group_queue_stats.argtypes = [vp, vp, i32]
         L.vsfh_group_serialize_problem.argtypes = [vp, i32, vp, sz]
         L.vsfh_group_serialize_problem.restype = sz
+        L.vsfh_set_projections.argtypes = [vp, vp, vp]
+        L.vsfh_set_projections.restype = None
+        L.vsfh_set_visualization.argtypes = [vp, i32]
+        L.vsfh_set_visualization.restype = None
+        L.vsfh_group_set_visualization.argtypes = [vp, i32]
+        L.vsfh_group_set_visualization.restype = None
+        L.vsfh_visualization_points.argtypes = [vp, i32, i32, vp, sz]
+        L.vsfh_visualization_points.restype = C.c_longlong
+        L.vsfh_serialize_visualization.argtypes = [vp, i32, i32, vp, sz]
+        L.vsfh_serialize_visualization.restype = sz
+        L.vsfh_add_feature_points.argtypes = [vp, vp, vp, vp, i32, vp]
+        L.vsfh_time_visualization.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_longlong)]
+        L.vsfh_time_visualization.restype = dbl
+        L.vsfh_queue_stats.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
 
@@ -116,6 +130,18 @@ def _device_frame(left, right, width: int, height: int, device: int, stream):
     return lp, ls, rp, rs, C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
 
 
+def add_feature_points(cam_to_robot, loc, quat_xyzw, point3d) -> np.ndarray:
+    """The CPU restatement of the point cloud (host/slam_visualization.h AddFeaturePoints, the reference's
+    slam_frontend_main.cc:155-173) on ONE node with the given pose and features: the kept points, (n, 3) float64.  No GPU."""
+    c = np.ascontiguousarray(cam_to_robot, np.float32).reshape(12)
+    l = np.ascontiguousarray(loc, np.float32).reshape(3)
+    q = np.ascontiguousarray(quat_xyzw, np.float32).reshape(4)
+    p = np.ascontiguousarray(point3d, np.float32).reshape(-1, 3)
+    out = np.zeros((max(len(p), 1), 3), np.float64)
+    n = lib().vsfh_add_feature_points(_p(c), _p(l), _p(q), _p(p), len(p), _p(out))
+    return out[:n].copy()
+
+
 def default_calibration() -> capi.VsfCalibration:
     """FrontendConfig()'s stereo calibration (the reference's hard-coded constants, slam_frontend.cc:565-644)."""
     c = capi.VsfCalibration()
@@ -126,7 +152,7 @@ def default_calibration() -> capi.VsfCalibration:
 class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
-                 debug_jpeg_quality: int = 0, debug_png: bool = False):
+                 debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False):
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
@@ -137,6 +163,8 @@ class Frontend:
             lib().vsfh_set_debug_jpeg_quality(self._h, debug_jpeg_quality)
         if debug_png:  # FrontendConfig::debug_png_: ... or PNG files, lossless (not together with the JPEG form)
             lib().vsfh_set_debug_png(self._h, 1)
+        if visualization:  # FrontendConfig::visualization_: the point cloud and pose graph of Frontend::GetVisualization
+            lib().vsfh_set_visualization(self._h, 1)
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend")
@@ -325,6 +353,63 @@ class Frontend:
         lib().vsfh_serialize_calibration(self._h, _p(e), _p(k))
         return e.tobytes(), k.tobytes()
 
+    def set_projections(self, left, right):
+        """FrontendConfig::projection_left / projection_right (3 x 4, row-major) before the first image: another stereo rig
+        than the reference's hard-coded one."""
+        l = np.ascontiguousarray(left, np.float32).reshape(12)
+        r = np.ascontiguousarray(right, np.float32).reshape(12)
+        lib().vsfh_set_projections(self._h, _p(l), _p(r))
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "Frontend::set_projections")
+
+    def visualization(self, host: bool = False):
+        """Frontend::GetVisualization: what the reference's driver publishes to RViz after every pose, for the frames booked
+        so far (it does NOT flush the queue; complete after flush()).  Returns (cloud, nodes, odometry, vision): the point
+        cloud as an (n, 3) float64 array, one point per node, and the two end points of every odometry / vision factor's line
+        as (m, 2, 3) arrays.  host=True: the same computed on the CPU from the whole problem, as the reference's driver does
+        (GetSLAMProblem + AddFeaturePoints / AddPoseGraph; that flushes)."""
+        out = []
+        for which in (3, 0, 1, 2):
+            n = lib().vsfh_visualization_points(self._h, int(host), which, None, 0)
+            if n < 0:
+                raise capi.VsfError(lib().vsfh_last_status(self._h), "Frontend::GetVisualization")
+            a = np.zeros((max(n, 1), 3), np.float64)
+            n = min(n, lib().vsfh_visualization_points(self._h, int(host), which, _p(a), len(a)))
+            out.append(a[:n].copy())
+        return out[0], out[1], out[2].reshape(-1, 2, 3), out[3].reshape(-1, 2, 3)
+
+    def serialize_visualization(self, host: bool = False):
+        """ROS-1 payloads of the two messages the driver publishes (host/slam_to_ros.h): the visualization_msgs/MarkerArray of
+        slam_frontend/pose_graph and the visualization_msgs/Marker of slam_frontend/points."""
+        out = []
+        for which in (0, 1):
+            n = lib().vsfh_serialize_visualization(self._h, int(host), which, None, 0)
+            if n == 0:
+                raise capi.VsfError(lib().vsfh_last_status(self._h), "Frontend::GetVisualization")
+            buf = np.zeros(n, np.uint8)
+            n = min(n, lib().vsfh_serialize_visualization(self._h, int(host), which, _p(buf), n))
+            out.append(buf[:n].tobytes())
+        return tuple(out)
+
+    def time_visualization(self, frames: np.ndarray, n_frames: int, warm: int = 32, host: bool = False, publish_every: int = 1):
+        """The driver's loop with the visualization asked for after every node (vsfh_time_visualization): (frames/s, points)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        pts = C.c_longlong(0)
+        fps = lib().vsfh_time_visualization(self._h, _p(frames), frames.shape[0], frames.shape[3], frames.shape[2], int(n_frames),
+                                            int(warm), int(host), int(publish_every), C.byref(pts))
+        if fps < 0:
+            raise capi.VsfError(lib().vsfh_last_status(self._h), "Frontend::GetVisualization (time_visualization)")
+        return fps, int(pts.value)
+
+    def queue_stats(self) -> dict:
+        """vsf_observe_stats of the object's context, by name (capi.Context.observe_stats)."""
+        v = np.zeros(len(capi.OBSERVE_STATS), np.int64)
+        st = lib().vsfh_queue_stats(self._h, _p(v), len(v))
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "vsf_observe_stats")
+        return {k: int(x) for k, x in zip(capi.OBSERVE_STATS, v)}
+
     def serialize_problem(self) -> bytes:
         """ROS-1 wire bytes of vision_slam_frontend/SLAMProblem for everything observed so far (host/slam_to_ros.h)."""
         n = lib().vsfh_serialize_problem(self._h, None, 0)
@@ -377,6 +462,12 @@ class FrontendGroup:
 
     def set_queue_thread(self, on: bool):
         lib().vsfh_group_set_queue_thread(self._h, int(on))
+
+    def set_visualization(self, on: bool):
+        """Every member's FrontendConfig::visualization_ (before the first image); members[i].visualization() reads member i's."""
+        lib().vsfh_group_set_visualization(self._h, int(on))
+        for i in range(len(self.members)):
+            self._check(i, "FrontendGroup::set_visualization")
 
     def _check(self, i: int, where: str, allow_status=()):
         st = lib().vsfh_last_status(self.members[i]._h)

@@ -182,6 +182,114 @@ size_t vsfh_debug_image_compressed(void* f, int stereo, uint8_t* out, size_t cap
   return v.size;
 }
 
+// ---- what the driver publishes to RViz (slam_visualization.h, Frontend::GetVisualization) ----
+void vsfh_set_projections(void* f, const float left12[12], const float right12[12]) {
+  static_cast<Frontend*>(f)->set_projections(left12, right12);
+}
+void vsfh_set_visualization(void* f, int on) { static_cast<Frontend*>(f)->set_visualization(on != 0); }
+void vsfh_group_set_visualization(void* g, int on) {
+  slam::FrontendGroup* gr = static_cast<slam::FrontendGroup*>(g);
+  for (int i = 0; i < gr->size(); i++) gr->member(i).set_visualization(on != 0);
+}
+
+namespace {
+// host != 0: PublishVisualization's markers computed on the CPU from the whole problem, as the reference's driver does
+// (GetSLAMProblem -- which flushes -- then AddFeaturePoints / AddPoseGraph); else Frontend::GetVisualization.
+bool get_visualization(Frontend* fe, int host, slam::Visualization* v) {
+  if (!host) return fe->GetVisualization(v);
+  slam_types::SLAMProblem problem;
+  fe->GetSLAMProblem(&problem);
+  float cam_to_robot[12];
+  slam::CamToRobot(fe->GetConfig(), cam_to_robot);
+  slam_visualization::BuildVisualization(cam_to_robot, problem, v);
+  return true;
+}
+const slam_visualization::Marker& marker_of(const slam::Visualization& v, int which) {
+  return which == 0 ? v.nodes : which == 1 ? v.odometry : which == 2 ? v.vision : v.vision_points;
+}
+}  // namespace
+
+// Points of marker `which` (0 nodes, 1 odometry lines, 2 vision lines, 3 the cloud): the count, or -1; min(count, cap) points
+// of three doubles into out.
+long long vsfh_visualization_points(void* f, int host, int which, double* out, size_t cap) {
+  slam::Visualization v;
+  if (which < 0 || which > 3 || !get_visualization(static_cast<Frontend*>(f), host, &v)) return -1;
+  const slam_visualization::Marker& m = marker_of(v, which);
+  const size_t n = m.points.size() < cap ? m.points.size() : cap;
+  if (out && n) std::memcpy(out, m.points.data(), n * sizeof(slam_visualization::Point));
+  return (long long)m.points.size();
+}
+// ROS-1 wire bytes of what the driver publishes: which = 0 the MarkerArray of slam_frontend/pose_graph (nodes, odometry, vision),
+// 1 the Marker of slam_frontend/points (the cloud).  The payload size (0 on failure); min(size, cap) bytes into out.
+size_t vsfh_serialize_visualization(void* f, int host, int which, uint8_t* out, size_t cap) {
+  slam::Visualization v;
+  if (!get_visualization(static_cast<Frontend*>(f), host, &v)) return 0;
+  std::vector<uint8_t> bytes;
+  if (which == 0)
+    slam_to_ros::SerializeMarkerArray(v.PoseGraph(), &bytes);
+  else
+    slam_to_ros::SerializeMarker(v.vision_points, &bytes);
+  if (out && cap) std::memcpy(out, bytes.data(), bytes.size() < cap ? bytes.size() : cap);
+  return bytes.size();
+}
+// The CPU restatement alone, no Frontend and no GPU: slam_visualization::AddFeaturePoints on a problem of ONE node with pose
+// (loc xyz, quaternion xyzw) and n features whose point3d are point3d[3 i ..].  Returns the points kept; out holds 3 n doubles.
+int vsfh_add_feature_points(const float cam_to_robot[12], const float loc[3], const float quat_xyzw[4], const float* point3d, int n,
+                            double* out) {
+  slam_types::SLAMProblem problem;
+  problem.nodes.resize(1);
+  slam_types::SLAMNode& node = problem.nodes[0];
+  node.pose = slam_types::RobotPose(slam::Vector3f(loc[0], loc[1], loc[2]),
+                                    slam::Quaternionf(quat_xyzw[3], quat_xyzw[0], quat_xyzw[1], quat_xyzw[2]));
+  for (int i = 0; i < n; i++)
+    node.features.push_back(slam_types::VisionFeature((uint64_t)i, slam::Vector2f(),
+                                                      slam::Vector3f(point3d[3 * i], point3d[3 * i + 1], point3d[3 * i + 2])));
+  slam_visualization::Marker m;
+  slam_visualization::InitializeMarker(slam_visualization::Marker::POINTS, slam_visualization::Color4f::kWhite(), 0.025f, 0.025f,
+                                       0.025f, &m);
+  slam_visualization::AddFeaturePoints(cam_to_robot, problem, &m);
+  if (!m.points.empty()) std::memcpy(out, m.points.data(), m.points.size() * sizeof(slam_visualization::Point));
+  return (int)m.points.size();
+}
+
+// The driver's loop of vsfh_time_sequence with the visualization asked for after EVERY node (slam_frontend_main.cc:319-325).
+// host == 0: Frontend::GetVisualization into one Visualization object kept across the loop (it only appends; the queue is not
+// flushed); host != 0: GetSLAMProblem + AddFeaturePoints / AddPoseGraph over the whole problem per node, as the reference does.
+// Either way the two messages are serialised every `publish_every`-th node (0: never).  Returns the steady frames per second;
+// *points: the cloud's size at the end; < 0 on failure.
+double vsfh_time_visualization(void* f, const uint8_t* frames, int n_src, int w, int h, int n_frames, int warm, int host,
+                               int publish_every, long long* points) {
+  using Clock = std::chrono::steady_clock;
+  Frontend* fe = static_cast<Frontend*>(f);
+  const slam::Quaternionf q(1, 0, 0, 0);
+  const int first = fe->GetNumPoses();
+  if (first == 0) fe->ObserveOdometry(slam::Vector3f(0, 0, 0), q, 0.0);
+  slam::Visualization v;
+  std::vector<uint8_t> bytes;
+  Clock::time_point t0 = Clock::now();
+  for (int k = 0; k < n_frames; k++) {
+    if (k == warm) {
+      fe->Flush();
+      t0 = Clock::now();
+    }
+    const uint8_t* l = frames + (size_t)(k % n_src) * 2 * w * h;
+    fe->ObserveOdometry(slam::Vector3f(0.3f * (first + k + 1), 0, 0), q, 1.0 + first + k);
+    const bool added = fe->ObserveImage(slam::Image(l, h, w, (size_t)w), slam::Image(l + (size_t)w * h, h, w, (size_t)w),
+                                        1.0 + first + k);
+    if (!added || fe->last_status() != VSF_OK) return -1.0;
+    if (!get_visualization(fe, host, &v)) return -1.0;
+    if (publish_every > 0 && (k + 1) % publish_every == 0) {
+      slam_to_ros::SerializeMarkerArray(v.PoseGraph(), &bytes);
+      slam_to_ros::SerializeMarker(v.vision_points, &bytes);
+    }
+  }
+  if (!fe->Flush() || !get_visualization(fe, host, &v)) return -1.0;
+  const double wall = std::chrono::duration<double>(Clock::now() - t0).count();
+  if (points) *points = (long long)v.vision_points.points.size();
+  const int n = n_frames - warm;
+  return n > 0 && wall > 0 ? n / wall : 0.0;
+}
+
 void vsfh_frontend_destroy(void* f) { delete static_cast<Frontend*>(f); }
 
 // slam::FrontendGroup: n members on one context.  Member i takes fundamental9[9 i ..] and best_percent[i] (<= 0: the
@@ -235,6 +343,11 @@ int vsfh_group_observe_device_image(void* g, int i, const void* left, size_t lef
                                                                    bayer_rggb8 != 0)
              ? 1
              : 0;
+}
+// vsf_observe_stats of a Frontend's context (out[0..n)).
+int vsfh_queue_stats(void* f, int64_t* out, int n) {
+  vsf_ctx* c = static_cast<Frontend*>(f)->context();
+  return c ? (int)vsf_observe_stats(c, out, n) : (int)VSF_ERR_INVALID_ARG;
 }
 // vsf_observe_stats of the group's context (out[0..n)).
 int vsfh_group_queue_stats(void* g, int64_t* out, int n) {

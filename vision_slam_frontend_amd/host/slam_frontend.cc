@@ -124,6 +124,7 @@ FrontendConfig::FrontendConfig() {
   debug_images_ = false;
   debug_jpeg_quality_ = 0;
   debug_png_ = false;
+  visualization_ = false;
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
   descriptor_extract_type_ = DescriptorExtractorType::ORB;
   best_percent_ = 0.3f;
@@ -193,6 +194,15 @@ FrontendConfig::FrontendConfig() {
   const float c[9] = {0.0f, -A[2], A[1], A[2], 0.0f, -A[0], -A[1], A[0], 0.0f};
   std::memcpy(C.m, c, sizeof(c));
   fundamental = Mul(Mul(Mul(Transpose(Inverse(K_right)), rotation), Transpose(K_left)), C);
+}
+
+void CamToRobot(const FrontendConfig& config, float out[12]) {
+  const Affine3f& a = config.left_cam_to_robot;
+  const float t[3] = {a.translation_.x(), a.translation_.y(), a.translation_.z()};
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) out[4 * r + c] = a.linear_(r, c);
+    out[4 * r + 3] = t[r];
+  }
 }
 
 vsf_calibration MakeCalibration(const FrontendConfig& config) {
@@ -294,6 +304,12 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
   if (last_status_ == VSF_OK && config_.debug_images_ && (form & kFormJpeg))
     last_status_ = vsf_observe_set_debug_jpeg(ctx_, config_.debug_jpeg_quality_);
   if (last_status_ == VSF_OK && config_.debug_images_ && (form & kFormPng)) last_status_ = vsf_observe_set_debug_png(ctx_, 1);
+  // the point cloud of GetVisualization: one more launch in every batch's tail (vsf_observe_set_world_points)
+  if (last_status_ == VSF_OK && config_.visualization_) {
+    float cam_to_robot[12];
+    CamToRobot(config_, cam_to_robot);
+    last_status_ = vsf_observe_set_world_points(ctx_, 1, cam_to_robot);
+  }
   pending_.assign((size_t)ctx_depth_, PendingFrame());
   pending_head_ = pending_count_ = 0;
   return last_status_ == VSF_OK;
@@ -602,6 +618,7 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   while ((int)in_flight() >= queue_depth())
     if (!retire()) return false;
   PendingFrame& pf = pending_[(pending_head_ + pending_count_) % pending_.size()];
+  if (config_.visualization_ && !SetQueuePose()) return false;
   if (fp.device) {  // (already in HBM: one launch on the producer's stream, no staging copy, no upload)
     const vsf_dev_frame df{fp.left, fp.right, fp.left_bytes, fp.right_bytes};
     last_status_ = vsf_observe_submit_dev(ctx_, stream_, &df, 1, fp.bayer ? VSF_PIX_BAYER_RGGB8 : VSF_PIX_MONO8, fp.hip_stream,
@@ -628,13 +645,107 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   // results that are already there are booked now (no waiting, nothing sent early): at a camera's rate the problem stays a
   // frame or two behind instead of a queue's depth; when frames stream in faster than the GPU serves them this finds nothing
   // and the queue fills as before
-  while (in_flight() > 1) {
+  return BookFinished();
+}
+
+// Books, oldest first, the frames whose results are already there (vsf_observe_poll: no wait, nothing sent early); the newest
+// frame always stays in flight.  What ObserveFused does behind every submit, and all GetVisualization does to the queue.
+bool Frontend::BookFinished() {
+  auto in_flight = [this] { return group_ ? group_->in_flight() : pending_count_; };
+  while (ctx_ && in_flight() > 1) {
     int ready = 0;
     const int64_t oldest = group_ ? group_->oldest_ticket() : pending_[pending_head_].ticket;
     if (vsf_observe_poll(ctx_, oldest, &ready) != VSF_OK || !ready) break;
-    if (!retire()) return false;
+    if (!(group_ ? group_->RetireOldest() : RetireOldest())) return false;
   }
   return true;
+}
+
+// The pose of the node this frame becomes (cc:444-447, the expressions of RetireOldest / FinishNode on the odometry this call
+// sees), handed to the queue so that the batch's tail can place the frame's points in the world.
+bool Frontend::SetQueuePose() {
+  const Vector3f loc = init_odom_rotation_.inverse() * (odom_translation_ - init_odom_translation_);
+  const Quaternionf angle = odom_rotation_ * init_odom_rotation_.inverse();
+  const float l[3] = {loc.x(), loc.y(), loc.z()}, q[4] = {angle.x(), angle.y(), angle.z(), angle.w()};
+  last_status_ = vsf_observe_set_pose(ctx_, stream_, l, q);
+  return last_status_ == VSF_OK;
+}
+
+void Frontend::BookVisualization(size_t first_vision_factor, const double* xyz, int n) {
+  const SLAMNode& node = nodes_.back();
+  viz_nodes_.push_back(slam_visualization::StdPoint(node.pose.loc));
+  if (node.node_idx > 0 && !odometry_factors_.empty()) {  // (the factor booked with this node: pose_i = node_idx - 1)
+    const OdometryFactor& f = odometry_factors_.back();
+    viz_odometry_.push_back(slam_visualization::StdPoint(nodes_[f.pose_i].pose.loc));
+    viz_odometry_.push_back(slam_visualization::StdPoint(nodes_[f.pose_j].pose.loc));
+  }
+  for (size_t i = first_vision_factor; i < vision_factors_.size(); i++) {
+    const VisionFactor& f = vision_factors_[i];
+    viz_vision_.push_back(slam_visualization::StdPoint(nodes_[f.pose_idx_initial].pose.loc));
+    viz_vision_.push_back(slam_visualization::StdPoint(nodes_[f.pose_idx_current].pose.loc));
+  }
+  if (n > 0) cloud_.insert(cloud_.end(), xyz, xyz + (size_t)3 * n);
+}
+
+bool Frontend::GetVisualization(Visualization* out) {
+  if (!out || !config_.visualization_) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return false;
+  }
+  if (pipelined_ && !BookFinished()) return false;
+  using slam_visualization::ColorRGBA;
+  using slam_visualization::Marker;
+  using slam_visualization::Point;
+  const size_t n_cloud = cloud_.size() / 3;
+  if (out->source != this || out->nodes.points.size() > viz_nodes_.size() || out->odometry.points.size() > viz_odometry_.size() ||
+      out->vision.points.size() > viz_vision_.size() || out->vision_points.points.size() > n_cloud) {
+    slam_visualization::InitializeVisualization(out);
+    out->source = this;
+  }
+  auto append = [](Marker* m, const Point* all, size_t n, const slam_visualization::Color4f& colour) {
+    const size_t have = m->points.size();
+    if (have == n) return;
+    m->points.insert(m->points.end(), all + have, all + n);
+    m->colors.resize(n, slam_visualization::StdColor(colour));
+  };
+  append(&out->nodes, viz_nodes_.data(), viz_nodes_.size(), slam_visualization::Color4f::kRed());
+  append(&out->odometry, viz_odometry_.data(), viz_odometry_.size(), slam_visualization::Color4f::kGreen());
+  append(&out->vision, viz_vision_.data(), viz_vision_.size(), slam_visualization::Color4f::kBlue());
+  // (Point is three doubles without padding: the cloud's doubles ARE its points)
+  static_assert(sizeof(Point) == 3 * sizeof(double), "the cloud is appended as Points");
+  {
+    Marker* m = &out->vision_points;
+    const size_t have = m->points.size();
+    if (have < n_cloud) {
+      m->points.resize(n_cloud);
+      std::memcpy(static_cast<void*>(m->points.data() + have), cloud_.data() + 3 * have, (n_cloud - have) * sizeof(Point));
+      m->colors.resize(n_cloud, slam_visualization::StdColor(slam_visualization::CloudColor()));
+    }
+  }
+  return true;
+}
+
+void Frontend::set_projections(const float left[12], const float right[12]) {
+  if (!left || !right || !nodes_.empty() || pending_count_ > 0) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  std::memcpy(config_.projection_left, left, sizeof(config_.projection_left));
+  std::memcpy(config_.projection_right, right, sizeof(config_.projection_right));
+}
+
+void Frontend::set_visualization(bool on) {
+  // (before the first ObserveImage, like set_debug_images: the cloud and the nodes must start together)
+  if (!nodes_.empty() || pending_count_ > 0) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  config_.visualization_ = on;
+  if (ctx_) {
+    float cam_to_robot[12];
+    CamToRobot(config_, cam_to_robot);
+    last_status_ = vsf_observe_set_world_points(ctx_, on ? 1 : 0, cam_to_robot);
+  }
 }
 
 bool Frontend::Flush() {
@@ -702,6 +813,7 @@ bool Frontend::RetireOldest() {
       }
     }
   };
+  const size_t first_vision_factor = vision_factors_.size();
   for (int p = 0; p + 1 < n_pairs; p++) {  // the temporal loop, cc:424-434
     std::vector<FeatureMatch> pairs;
     book(frame_list_[p], &curr_frame, pair_bytes[p], npairs[p], &pairs);
@@ -755,6 +867,16 @@ bool Frontend::RetireOldest() {
     const Vector3f translation = pf.prev_odom_rotation.inverse() * (pf.odom_translation - pf.prev_odom_translation);
     const Quaternionf rotation(pf.odom_rotation * pf.prev_odom_rotation.inverse());
     odometry_factors_.push_back(OdometryFactor(curr_frame_ID_ - 1, curr_frame_ID_, translation, rotation));
+  }
+  if (config_.visualization_) {  // the node's points, made in the batch's tail (vsf_observe_set_world_points)
+    const double* xyz = nullptr;
+    int32_t n_points = 0;
+    const vsf_status vs = vsf_observe_world_points_view(ctx_, pf.ticket, &xyz, &n_points);
+    if (vs != VSF_OK) {
+      last_status_ = vs;
+      return false;
+    }
+    BookVisualization(first_vision_factor, xyz, n_points);
   }
   curr_frame_ID_++;
   if (frame_list_.size() >= config_.frame_life_ && !frame_list_.empty()) frame_list_.erase(frame_list_.begin());
@@ -847,6 +969,7 @@ bool Frontend::ObserveImage(const Image& left_image, const Image& right_image, d
   if (!ExtractFeaturesPair(left_image, right_image, &curr_frame, &right_temp_frame)) return false;
   const std::vector<vsf_dmatch> stereo_matches = GetMatches(curr_frame, right_temp_frame, config_.nn_match_ratio_);
   RemoveAmbigStereo(&curr_frame, &right_temp_frame, stereo_matches);
+  const size_t first_vision_factor = vision_factors_.size();
   GetFeatureMatchesAll(&frame_list_, &curr_frame, &vision_factors_);
   std::vector<Vector3f> points;
   VisionFactor stereo;
@@ -868,6 +991,25 @@ bool Frontend::ObserveImage(const Image& left_image, const Image& right_image, d
   }
   UndistortFeaturePoints(&features);
   FinishNode(curr_frame, features);
+  if (config_.visualization_) {  // the node's points: one vsf_world_points call (the kernel the queue's batches run)
+    const SLAMNode& node = nodes_.back();
+    std::vector<vsf_vision_feature> records(features.size());
+    for (size_t i = 0; i < features.size(); i++) {
+      const VisionFeature& f = features[i];
+      records[i] = {(uint32_t)f.feature_idx, (uint32_t)(f.feature_idx >> 32), {f.pixel.x(), f.pixel.y()},
+                    {f.point3d.x(), f.point3d.y(), f.point3d.z()}};
+    }
+    const vsf_pose pose = {{node.pose.loc.x(), node.pose.loc.y(), node.pose.loc.z()},
+                           {node.pose.angle.x(), node.pose.angle.y(), node.pose.angle.z(), node.pose.angle.w()}};
+    float cam_to_robot[12];
+    CamToRobot(config_, cam_to_robot);
+    std::vector<double> xyz(3 * records.size());
+    int n_points = 0;
+    last_status_ = vsf_world_points(ctx_, records.data(), (int)records.size(), &pose, cam_to_robot, xyz.data(), (int)records.size(),
+                                    &n_points);
+    if (last_status_ != VSF_OK) return false;
+    BookVisualization(first_vision_factor, xyz.data(), n_points);
+  }
   return true;
 }
 
@@ -1043,7 +1185,8 @@ FrontendGroup::FrontendGroup(const std::vector<FrontendConfig>& configs, int dev
   for (const FrontendConfig& c : configs)  // what the one context is built with
     if (c.orb_nfeatures != lead.orb_nfeatures || c.nn_match_ratio_ != lead.nn_match_ratio_ ||
         c.residual_order != lead.residual_order || c.frame_life_ != lead.frame_life_ || c.image_width != lead.image_width ||
-        c.image_height != lead.image_height) {
+        c.image_height != lead.image_height || c.visualization_ != lead.visualization_ ||
+        (c.visualization_ && std::memcmp(&c.left_cam_to_robot, &lead.left_cam_to_robot, sizeof(Affine3f)) != 0)) {
       last_status_ = VSF_ERR_INVALID_ARG;
       return;
     }

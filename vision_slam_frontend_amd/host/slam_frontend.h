@@ -18,6 +18,7 @@
 
 #include "../../include/vsf.h"
 #include "slam_types.h"
+#include "slam_visualization.h"
 
 namespace slam {
 
@@ -82,6 +83,10 @@ struct FrontendConfig {
   // vsf_observe_set_debug_png).  Off by default; ignored in per-call mode; not together with debug_jpeg_quality_ (the second of
   // the two to be asked for is refused with VSF_ERR_INVALID_ARG).
   bool debug_png_;
+  // An addition: the object also builds what the reference's driver publishes to RViz after every pose (PublishVisualization,
+  // slam_frontend_main.cc:194-225) -- the point cloud on the GPU, inside the queue's batches, the pose graph while nodes and
+  // factors are booked -- for Frontend::GetVisualization.  Off by default: nothing is launched, copied or kept for it.
+  bool visualization_;
   DescriptorExtractorType descriptor_extract_type_;
   float best_percent_;
   float nn_match_ratio_;
@@ -107,6 +112,17 @@ struct FrontendConfig {
 
 // FrontendConfig's stereo calibration in the layout of the C ABI (include/vsf.h vsf_calibration).
 vsf_calibration MakeCalibration(const FrontendConfig& config);
+// config.left_cam_to_robot as the 3 x 4 row-major matrix the point cloud's calls take.
+void CamToRobot(const FrontendConfig& config, float out[12]);
+
+using slam_visualization::Visualization;
+// The driver's AddFeaturePoints with its own signature (slam_frontend_main.cc:155-157): the CPU restatement of the cloud.
+inline void AddFeaturePoints(const FrontendConfig& config, const slam_types::SLAMProblem& problem,
+                             slam_visualization::Marker* marker_ptr) {
+  float c[12];
+  CamToRobot(config, c);
+  slam_visualization::AddFeaturePoints(c, problem, marker_ptr);
+}
 
 // src/slam_frontend.h:100-114
 class Frame {
@@ -159,6 +175,24 @@ class Frontend {
   void GetSLAMProblem(slam_types::SLAMProblem* problem) const;
   int GetNumPoses();
   FrontendConfig GetConfig() { return config_; }
+  // The four markers of the driver's PublishVisualization (slam_frontend_main.cc:194-225) for the frames BOOKED SO FAR, with
+  // config.visualization_ on (else false and VSF_ERR_INVALID_ARG): nodes (id 0, POINTS), odometry factors (1, LINE_LIST),
+  // vision factors (2, LINE_LIST), the point cloud (3, POINTS, colours (1, 1, 1, 0.2)), frame "map".
+  //   Unlike GetSLAMProblem and the accessors below this call does NOT flush the queue: it first books the frames whose
+  // results are already there -- it never waits for the GPU and sends nothing early -- and reports those, so a driver that asks
+  // after every node keeps the queue's batches whole.  After Flush() it is complete: every observed frame is in it, and the
+  // markers are, byte for byte, those of the synchronous modes and of slam_visualization::BuildVisualization on the problem.
+  //   The pose graph is host bookkeeping made while nodes and factors are booked; the cloud is the concatenation of the
+  // booked frames' device-made points (vsf_observe_set_world_points; per-call mode: one vsf_world_points per node).  A node's
+  // pose never changes once booked, so everything here only grows: handing the SAME Visualization object in again appends
+  // what is new (its markers must not have been edited in between); any other object is filled from scratch.
+  bool GetVisualization(Visualization* out);
+  void set_visualization(bool on);  // config.visualization_, under the rule of set_debug_images
+  // config.projection_left / projection_right (3 x 4 row-major) after construction, under the same rule: a stereo rig other than
+  // the reference's hard-coded one (cc:595-611) -- what Calculate3DPoints triangulates with.
+  void set_projections(const float left[12], const float right[12]);
+  // The cloud as the object keeps it: three doubles per point, booked frames in order (valid until the next call that books).
+  const std::vector<double>& visualization_cloud() const { return cloud_; }
   // cc:474-495.  With config.debug_images_ on, every node keeps a match image (CreateMatchDebugImage, cc:100-115; from the
   // second node on) and a stereo image (CreateStereoDebugImage, cc:74-98; unless the node has no stereo match, cc:131-133)
   // for the object's lifetime.  Like GetNumPoses these book the frames still in flight first; the views point into memory
@@ -268,6 +302,11 @@ class Frontend {
   };
   bool ObserveFused(int width, int height, const FramePayload& fp);
   void FinishNode(const Frame& curr_frame, const std::vector<slam_types::VisionFeature>& features);
+  // visualization_: the newest node and the factors booked with it (vision factors from index `first_vision_factor`) join the
+  // pose-graph lists; points [xyz, xyz + 3 n) -- the node's, made on the device -- join the cloud.
+  void BookVisualization(size_t first_vision_factor, const double* xyz, int n);
+  bool SetQueuePose();  // the pose the next node will carry, handed to the queue before its frame is submitted
+  bool BookFinished();  // books the frames whose results are already there: never waits, sends nothing early
   // A frame the GPU is still working on, with the odometry its ObserveImage call saw (cc:444-458 reads it at the END of
   // the call; between submit and collect the driver may already have delivered the next pose).
   struct PendingFrame {
@@ -309,6 +348,9 @@ class Frontend {
   float stereo_ambig_constraint_;
   std::vector<OwnedImage> debug_images_, debug_stereo_images_;  // cc h:202-203: kept for the object's lifetime
   std::vector<std::vector<uint8_t>> debug_files_, debug_stereo_files_;  // ... or their JPEG / PNG files (debug_jpeg_quality_ / debug_png_)
+  // visualization_: the pose graph as points (one per node; two per factor) and the cloud (three doubles per point)
+  std::vector<slam_visualization::Point> viz_nodes_, viz_odometry_, viz_vision_;
+  std::vector<double> cloud_;
   bool fused_;
   bool pipelined_;
   int depth_ = 256, batch_frames_ = 128, min_batch_ = 0;
@@ -333,7 +375,8 @@ class Frontend {
 // nodes, factors and bytes are those of a Frontend of its own fed the same calls (tests/test_gpu_frontend_group.py).
 //   The members' configurations may differ in everything a frame brings to the queue -- the calibration (intrinsics,
 // projections, fundamental), best_percent_, the odometry gates -- and must agree in what the context is built with:
-// orb_nfeatures, nn_match_ratio_, residual_order, frame_life_ and the image size (else last_status() of the group reads
+// orb_nfeatures, nn_match_ratio_, residual_order, frame_life_, visualization_ (with it, left_cam_to_robot: the queue places
+// every stream's points with ONE camera-to-robot transform) and the image size (else last_status() of the group reads
 // VSF_ERR_INVALID_ARG and nothing is observed).  Members observe in fused mode (a member's set_fused does nothing).  Debug
 // images are not available in a group of more than one member: a configuration that asks for them (debug_images_,
 // debug_jpeg_quality_, debug_png_) is refused by the constructor with VSF_ERR_UNSUPPORTED.

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "slam_types.h"
+#include "slam_visualization.h"
 
 namespace slam_to_ros {
 
@@ -49,6 +50,14 @@ constexpr const char* kMd5VisionFeature = "9cccef6835ecad8ee3bfb40a17ba67fb";
 // computed by the same tool from ROS-1's field lists (std_msgs/Header header, string format, uint8[] data).
 constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 
+// visualization_msgs/Marker and /MarkerArray (what the driver's PublishVisualization sends to RViz: SerializeMarker /
+// SerializeMarkerArray below), by the same tool from ROS-1's field and constant lists (tools/ros_md5.py: EXTERNAL; the Marker
+// that has DELETEALL, i.e. Jade and later).  No ROS exists here to confirm them against `rosmsg md5` -- like the ten sums
+// above they rest on the tool, which reproduces the sums it knows (geometry_msgs/Point, Vector3, Quaternion, Pose,
+// std_msgs/Header, ColorRGBA, sensor_msgs/CompressedImage).
+constexpr const char* kMarkerMd5 = "4048c9de2a16f4ae8e0538085ebf1b97";
+constexpr const char* kMarkerArrayMd5 = "d155b9ce5188fbaf89745847fd5882d7";
+
 constexpr const char* kCompressedFormatJpeg = "jpeg";
 constexpr const char* kCompressedFormatPng = "png";
 
@@ -58,6 +67,16 @@ class Writer {
   void u32(uint32_t v) { raw(&v, 4); }
   void u64(uint64_t v) { raw(&v, 8); }
   void f64(double v) { raw(&v, 8); }
+  void i32(int32_t v) { raw(&v, 4); }
+  void f32(float v) { raw(&v, 4); }
+  void u8(uint8_t v) { raw(&v, 1); }
+  void str(const std::string& s) {  // string: uint32 length + bytes
+    u32((uint32_t)s.size());
+    bytes(s.data(), s.size());
+  }
+  void bytes(const void* p, size_t n) {
+    if (n != 0) raw(p, n);
+  }
 
  private:
   void raw(const void* p, size_t n) {  // host is little endian (x86-64), as is the wire
@@ -250,6 +269,68 @@ inline bool ParseCompressedImage(const uint8_t* msg, size_t n, CompressedImageVi
   v->data = msg + p;
   v->size = len;
   return true;
+}
+
+// One visualization_msgs/Marker in ROS-1 wire format:
+//   Header (uint32 seq, time stamp, string frame_id), string ns, int32 id, type, action, Pose (Point + Quaternion: 7 float64),
+//   Vector3 scale, ColorRGBA color (4 float32), duration lifetime (2 int32), bool frame_locked (1 byte), Point[] points,
+//   ColorRGBA[] colors, string text, string mesh_resource, bool mesh_use_embedded_materials
+//                                   154 + |frame_id| + |ns| + 24 points + 16 colors + |text| + |mesh_resource| B
+// The points array -- the cloud: the one part that grows -- is written with ONE memcpy (slam_visualization.h: Point is three
+// float64 without padding, the host is little endian as the wire is); the colours likewise.
+inline size_t SerializedSize(const slam_visualization::Marker& m) {
+  return 154 + m.header.frame_id.size() + m.ns.size() + 24 * m.points.size() + 16 * m.colors.size() + m.text.size() +
+         m.mesh_resource.size();
+}
+inline void Write(Writer* w, const slam_visualization::Marker& m) {
+  w->u32(m.header.seq);
+  w->u32(m.header.stamp_secs);
+  w->u32(m.header.stamp_nsecs);
+  w->str(m.header.frame_id);
+  w->str(m.ns);
+  w->i32(m.id);
+  w->i32(m.type);
+  w->i32(m.action);
+  w->f64(m.pose.position.x);
+  w->f64(m.pose.position.y);
+  w->f64(m.pose.position.z);
+  w->f64(m.pose.orientation.x);
+  w->f64(m.pose.orientation.y);
+  w->f64(m.pose.orientation.z);
+  w->f64(m.pose.orientation.w);
+  w->f64(m.scale.x);
+  w->f64(m.scale.y);
+  w->f64(m.scale.z);
+  w->f32(m.color.r);
+  w->f32(m.color.g);
+  w->f32(m.color.b);
+  w->f32(m.color.a);
+  w->i32(m.lifetime_secs);
+  w->i32(m.lifetime_nsecs);
+  w->u8(m.frame_locked ? 1 : 0);
+  w->u32((uint32_t)m.points.size());
+  w->bytes(m.points.data(), m.points.size() * sizeof(slam_visualization::Point));
+  w->u32((uint32_t)m.colors.size());
+  w->bytes(m.colors.data(), m.colors.size() * sizeof(slam_visualization::ColorRGBA));
+  w->str(m.text);
+  w->str(m.mesh_resource);
+  w->u8(m.mesh_use_embedded_materials ? 1 : 0);
+}
+inline void SerializeMarker(const slam_visualization::Marker& m, std::vector<uint8_t>* out) {
+  out->clear();
+  out->reserve(SerializedSize(m));
+  Writer w(out);
+  Write(&w, m);
+}
+// visualization_msgs/MarkerArray: Marker[] markers.
+inline void SerializeMarkerArray(const slam_visualization::MarkerArray& a, std::vector<uint8_t>* out) {
+  out->clear();
+  size_t n = 4;
+  for (const auto& m : a.markers) n += SerializedSize(m);
+  out->reserve(n);
+  Writer w(out);
+  w.u32((uint32_t)a.markers.size());
+  for (const auto& m : a.markers) Write(&w, m);
 }
 
 inline size_t SerializedSize(const slam_types::SLAMProblem& p) {
