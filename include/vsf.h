@@ -518,6 +518,33 @@ vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const 
                                                 const uint8_t* right, size_t right_bytes, int bayer,
                                                 const vsf_calibration* calib, float best_percent, int frame_life,
                                                 int64_t* ticket);
+/* The same frames read as cv::imdecode(msg.data, IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8) reads them (reduce = 2, 4, 8; reduce = 1
+ * is vsf_observe_submit_compressed_stream with bayer = 0): JPEG files of up to `reduce` times the context's size a side, decoded
+ * inside the batch by libjpeg's reduced inverse DCTs (vsf_imdecode_reduced_gray_batch) straight to the context's size.  Every
+ * rule of vsf_observe_submit_compressed_stream holds, with the size rule applied per file: a file of W x H is taken when
+ * ceil(W / reduce) x ceil(H / reduce) (vsf_reduced_size) is the context's size -- VSF_ERR_INVALID_ARG otherwise, and for a
+ * reduce outside {1, 2, 4, 8}; a PNG file with reduce > 1 is VSF_ERR_UNSUPPORTED (cv::imdecode would decode it whole and call
+ * cv::resize, which is not built here).  A file the host refuses issues no ticket and leaves the queue as it was; a file the
+ * device refuses fails its own ticket through status word 13, as for full-size files.  The byte cap
+ * (vsf_observe_set_compressed_cap) applies to the file as it is: files of a larger camera usually need a larger cap than the
+ * default of the context's size.
+ *   There is no `bayer` argument: a mosaic cannot be reduced in the DCT domain (the reduced image of a mosaic is not the
+ * mosaic of the reduced image); bayer_rggb8 topics stay at full size through the calls above.
+ *   THE CALIBRATION IS THE CALLER'S, FOR THE REDUCED IMAGE.  The library scales nothing: K, the distortion terms and the
+ * fundamental matrix handed in must describe the ceil(W / reduce) x ceil(H / reduce) image the extraction sees.
+ *   BATCHING: frames of different `reduce` -- and full-size compressed frames and raw frames -- SHARE a batch and its one
+ * upload; inside the upload a decode run ends where the format or the denominator changes.  Results do not depend on it: each
+ * frame's result is, byte for byte, that of vsf_observe_submit on the images the library decodes.
+ *   vsf_observe_stats value [23] counts the frames launched with reduce > 1. */
+vsf_status vsf_observe_submit_compressed_reduced(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes,
+                                                 const uint8_t* right, size_t right_bytes, int reduce,
+                                                 const vsf_calibration* calib, float best_percent, int frame_life,
+                                                 int64_t* ticket);
+/* submit (stream 0) + collect of one such frame, as vsf_observe_stereo_compressed is for full-size files. */
+vsf_status vsf_observe_stereo_compressed_reduced(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                                 size_t right_bytes, int reduce, const vsf_calibration* calib,
+                                                 float best_percent, int frame_life, uint8_t* out, size_t cap,
+                                                 size_t* out_bytes);
 /* Forgets ONE stream's window and puts its threshold back to 10000: its next frame is the first frame of a fresh context.
  * Legal while no frame of that stream is submitted and not collected (else VSF_ERR_INVALID_ARG); the other streams, frames
  * in flight included, are untouched.  vsf_observe_reset stays "all streams" (and drops what waits). */
@@ -569,7 +596,8 @@ size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth);
  * carried frames of more than one stream; [17] device frames launched (vsf_observe_submit_dev), [18] kernel launches and
  * copy commands the device path issued (a submit's one launch, a batch's copies out of the ring, its demosaic where no
  * compressed frame brings one), [19] bytes of the device ring -- the last three are 0 for a queue that has seen no device
- * frame; [20] .. [22] the point cloud's (vsf_observe_set_world_points) }. */
+ * frame; [20] .. [22] the point cloud's (vsf_observe_set_world_points); [23] frames launched at a reduced size
+ * (vsf_observe_submit_compressed_reduced with reduce > 1) }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,
@@ -650,6 +678,11 @@ size_t vsf_observe_compressed_ring_bytes(int depth, size_t cap_per_image);
  * changes the plan that is laid out, never what is refused. */
 vsf_status vsf_observe_probe_compressed(const uint8_t* file, size_t nbytes, int width, int height, size_t cap_per_image,
                                         int force_serial, int* kind);
+/* The same for vsf_observe_submit_compressed_reduced: width x height is the context's size, the file must reduce to it
+ * (VSF_ERR_INVALID_ARG otherwise, and for a reduce outside {1, 2, 4, 8}); a PNG file with reduce > 1 is VSF_ERR_UNSUPPORTED.
+ * The cap applies to the file as it is. */
+vsf_status vsf_observe_probe_compressed_reduced(const uint8_t* file, size_t nbytes, int reduce, int width, int height,
+                                                size_t cap_per_image, int force_serial, int* kind);
 
 /* ---------------- Debug images: cv::circle / cv::line onto GRAY2BGR canvases (slam_frontend.cc:74-115) ----------------
  * Each canvas is GRAY2BGR of one grey image, or of two side by side (cv::hconcat), 3 bytes per pixel, with its slice of the
@@ -728,6 +761,27 @@ vsf_status vsf_png_decode_gray_batch(vsf_ctx* ctx, const uint8_t* const* png, co
 vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images,
                                    int width, int height, uint8_t* d_dst, size_t dst_image_stride,
                                    size_t dst_row_stride);
+
+/* The siblings of that flag: cv::imdecode(data, cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8) for reduce = 2, 4, 8.  For a JPEG
+ * file OpenCV sets libjpeg's scale_num / scale_denom = 1 / reduce, and libjpeg decodes with its reduced inverse DCTs
+ * (jidctred.c: 4 x 4, 2 x 2 or 1 x 1 pixels per block of coefficients) -- no resize runs -- to
+ *     ceil(W / reduce) x ceil(H / reduce)   pixels (vsf_reduced_size).
+ * `width` and `height` are that OUTPUT size: a file of W x H is accepted when it reduces to exactly width x height, so files
+ * that differ below the denominator (127 x 95 and 128 x 96 at reduce 2) share a call; any other size is VSF_ERR_INVALID_ARG
+ * for that file (nothing is launched).  Entropy decoding, restart handling and every refusal are those of
+ * vsf_jpeg_decode_gray_batch; only the inverse DCT and what it stores differ.  Bit for bit what the library gives
+ * (tests/jpeg_ref_reduced.py).  reduce = 1 IS vsf_imdecode_gray_batch; a reduce other than 1, 2, 4, 8 returns
+ * VSF_ERR_INVALID_ARG and launches nothing (libjpeg's other N / 8 scales are not what imdecode asks for).
+ * A PNG file with reduce > 1 returns VSF_ERR_UNSUPPORTED: cv::imdecode decodes a PNG at full size and then calls cv::resize,
+ * which is not built here.  Destination and asynchronous contract as for vsf_jpeg_decode_gray_batch. */
+vsf_status vsf_imdecode_reduced_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images,
+                                           int reduce, int width, int height, uint8_t* d_dst, size_t dst_image_stride,
+                                           size_t dst_row_stride);
+/* The size an image of w x h has after IMREAD_REDUCED_GRAYSCALE_<reduce>: *rw = ceil(w / reduce), *rh = ceil(h / reduce)
+ * (libjpeg's jpeg_calc_output_dimensions); reduce in {1, 2, 4, 8}, w, h >= 1, else VSF_ERR_INVALID_ARG and 0 x 0.  With
+ * vsf_compressed_image_size -- which keeps reporting the FILE's own size -- it sizes a context for a stream of reduced
+ * files.  No context, no device. */
+vsf_status vsf_reduced_size(int w, int h, int reduce, int* rw, int* rh);
 
 /* SURVEY section 8(f) row f4, the part behind cv::imdecode: DecodeImage's cvtColor(COLOR_BayerBG2BGR) +
  * cvtColor(COLOR_BGR2GRAY) (slam_frontend_main.cc:101-106) for n 8-bit mosaics of width x height resident in HBM, in

@@ -48,6 +48,8 @@ EXPORTS = [
     "vsf_observe_submit_dev", "vsf_observe_device_ring_bytes",
     "vsf_world_points_batch_dev", "vsf_world_points", "vsf_observe_set_world_points", "vsf_observe_set_pose",
     "vsf_observe_world_points_view",
+    "vsf_imdecode_reduced_gray_batch", "vsf_reduced_size", "vsf_observe_probe_compressed_reduced",
+    "vsf_observe_submit_compressed_reduced", "vsf_observe_stereo_compressed_reduced",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -58,7 +60,7 @@ STAGE_COUNT = 8
 OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
                  "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands", "streams",
                  "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes",
-                 "world_points_frames", "world_points_commands", "world_points_ring_bytes")
+                 "world_points_frames", "world_points_commands", "world_points_ring_bytes", "reduced_frames")
 # vsf_observe_submit_dev's pixel formats (include/vsf.h)
 PIX_MONO8, PIX_BAYER_RGGB8 = 0, 1
 
@@ -133,6 +135,23 @@ class VsfError(RuntimeError):
 
 
 _lib = None
+
+
+def reduced_size(width: int, height: int, reduce: int):
+    """vsf_reduced_size: (status, width, height) of a width x height image after IMREAD_REDUCED_GRAYSCALE_<reduce>
+    (ceil(width / reduce), ceil(height / reduce); reduce in 1, 2, 4, 8).  No context, no device."""
+    w, h = C.c_int(0), C.c_int(0)
+    st = lib().vsf_reduced_size(width, height, reduce, C.byref(w), C.byref(h))
+    return st, int(w.value), int(h.value)
+
+
+def probe_compressed_reduced(data: bytes, reduce: int, width: int, height: int, cap_per_image: int, force_serial: bool = False):
+    """vsf_observe_probe_compressed_reduced: (status, kind) -- what a reduced submit makes of ONE payload on the host."""
+    b = np.frombuffer(bytes(data), np.uint8)
+    kind = C.c_int(0)
+    st = lib().vsf_observe_probe_compressed_reduced(_p(b), len(b), reduce, width, height, cap_per_image, int(force_serial),
+                                                    C.byref(kind))
+    return st, int(kind.value)
 
 
 def jpeg_encode_capacity(width: int, height: int, channels: int) -> int:
@@ -301,6 +320,13 @@ def lib() -> C.CDLL:
         L.vsf_jpeg_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_png_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_imdecode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
+        L.vsf_imdecode_reduced_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, sz, sz]
+        L.vsf_reduced_size.argtypes = [i32, i32, i32, ip, ip]
+        L.vsf_observe_probe_compressed_reduced.argtypes = [vp, sz, i32, i32, i32, sz, i32, ip]
+        L.vsf_observe_submit_compressed_reduced.argtypes = [vp, i32, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float,
+                                                            i32, C.POINTER(C.c_int64)]
+        L.vsf_observe_stereo_compressed_reduced.argtypes = [vp, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32,
+                                                            vp, sz, C.POINTER(sz)]
         L.vsf_debug_level_image.argtypes = [vp, i32, i32, i32, vp, sz]
         L.vsf_debug_fast_candidates.argtypes = [vp, i32, i32, vp, i32, ip]
         L.vsf_debug_fast_work.argtypes = [vp, i32, i32, vp, i32, ip, ip, vp, i32]
@@ -743,6 +769,31 @@ class Context:
                                                         _p(buf), cap, C.byref(n)), "vsf_observe_stereo_compressed")
         return decode_observation(buf[:n.value])
 
+    def observe_submit_compressed_reduced(self, left: bytes, right: bytes, calib: VsfCalibration, reduce: int, stream: int = 0,
+                                          best_percent: float = 0.3, frame_life: int = 10, allow_status=()):
+        """vsf_observe_submit_compressed_reduced: one ObserveImage given as two JPEG payloads read as
+        cv::imdecode(IMREAD_REDUCED_GRAYSCALE_<reduce>) reads them (files of up to `reduce` times the context's size a side;
+        the calibration is the caller's, for the reduced image).  Returns (status, ticket) like observe_submit_compressed."""
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        t = C.c_int64(-1)
+        st = lib().vsf_observe_submit_compressed_reduced(self._h, stream, _p(lb), len(lb), _p(rb), len(rb), reduce, C.byref(calib),
+                                                         float(np.float32(best_percent)), frame_life, C.byref(t))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_submit_compressed_reduced", lib().vsf_last_hip_error(self._h))
+        return st, int(t.value)
+
+    def observe_stereo_compressed_reduced(self, left: bytes, right: bytes, calib: VsfCalibration, reduce: int,
+                                          best_percent: float = 0.3, frame_life: int = 10) -> dict:
+        """vsf_observe_stereo_compressed_reduced: submit + collect of one such frame."""
+        lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
+        cap = int(lib().vsf_observe_capacity(self._h, frame_life))
+        buf = np.zeros(max(cap, 64), np.uint8)
+        n = C.c_size_t()
+        self._check(lib().vsf_observe_stereo_compressed_reduced(self._h, _p(lb), len(lb), _p(rb), len(rb), reduce, C.byref(calib),
+                                                                float(np.float32(best_percent)), frame_life, _p(buf), cap,
+                                                                C.byref(n)), "vsf_observe_stereo_compressed_reduced")
+        return decode_observation(buf[:n.value])
+
     def observe_collect_bytes(self, ticket: int, frame_life: int = 10, allow_status=()):
         """vsf_observe_collect as (status, the result's bytes): what the tests compare byte for byte.  Header word 13
         (bytes 52..56) is the decoder status of a compressed frame (include/vsf.h)."""
@@ -833,6 +884,20 @@ class Context:
                                            _p(d_dst), dst_image_stride, dst_row_stride)
         if st != VSF_OK and st not in allow_status:
             raise VsfError(st, "vsf_imdecode_gray_batch", lib().vsf_last_hip_error(self._h))
+        return st
+
+    def imdecode_reduced_gray_batch(self, files, reduce: int, width: int, height: int, d_dst: int, dst_image_stride: int,
+                                    dst_row_stride: int, allow_status=()):
+        """cv::imdecode(IMREAD_REDUCED_GRAYSCALE_<reduce>) of JPEG payloads (vsf_imdecode_reduced_gray_batch): width x height
+        is the OUTPUT size, ceil(W / reduce) x ceil(H / reduce) of every file; reduce = 1 is imdecode_gray_batch."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        sizes = (C.c_size_t * n)(*[len(b) for b in bufs])
+        st = lib().vsf_imdecode_reduced_gray_batch(self._h, C.cast(ptrs, C.c_void_p), C.cast(sizes, C.c_void_p), n, reduce, width,
+                                                   height, _p(d_dst), dst_image_stride, dst_row_stride)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_imdecode_reduced_gray_batch", lib().vsf_last_hip_error(self._h))
         return st
 
     def _encode_batch_dev(self, fmt: str, quality: tuple, d_src, n_images, width, height, channels, src_image_stride, src_row_stride,

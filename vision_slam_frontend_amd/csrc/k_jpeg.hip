@@ -29,6 +29,12 @@
 // Sequential files whose components come in several scans take that kernel too (a scan then decodes a block whole).
 // Arithmetic / 12-bit / lossless files and progressive files whose scans stop short of full precision are refused
 // (VSF_ERR_UNSUPPORTED).
+//
+// REDUCED SIZES (cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8: libjpeg at scale 1/2, 1/4, 1/8).  Nothing in front of the inverse
+// DCT changes; the plan's `reduce` = D > 1 swaps the IDCT for jidctred.c's 4 x 4, 2 x 2 or 1 x 1 form (vsf_jpeg_idct_reduced.h,
+// shared with a CPU test program) in both places it lives: jpeg_gray_kernel<D> and jpeg_idct_reduced_kernel<D>.  The image is
+// ceil(W / D) x ceil(H / D), a block gives 8 / D x 8 / D pixels at its origin / D, the last block of a row or column is
+// cropped.  Checked bit for bit against the system's libjpeg at those scales (tests/test_gpu_jpeg_reduced.py).
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -38,6 +44,7 @@
 
 #include "vsf_internal.h"
 #include "vsf_jpeg_host.h"
+#include "vsf_jpeg_idct_reduced.h"
 
 using namespace vsf_jpeg;
 
@@ -327,7 +334,43 @@ __device__ __forceinline__ void idct8_descaled(const int32_t d[8], int32_t out[8
   }
 }
 
-// `index`: the images (positions in `images` and in the destination) this launch decodes, one per workgroup
+// The reduced forms' stores in the one-wave decoder, wave-wide (every lane calls it).  A lane holds S = 8 / D pixels of one
+// row of one block (`val`, first pixel in the low byte) for (x, y) of the reduced image; M = 4 / S lanes make a dword of that
+// row.  The blocks parked in LDS come in MCU order, so the lanes that complete a lane's dword are looked for where they usually
+// are -- the next M - 1 lanes -- and taken when they hold the very next pixels of the same row: that lane then writes the whole
+// dword and the others nothing.  Whoever finds no such company (the end of a row, a group of blocks that starts in the middle
+// of a dword, 1 x 1 MCUs stacked by a sampling factor) writes its own bytes.
+template <int S, int M>
+__device__ __forceinline__ void store_reduced_packed(uint8_t* __restrict__ out, int pitch, int width, int lane, int x, int y,
+                                                     uint32_t val, bool valid) {
+  bool lead = valid && (x & 3) == 0 && x + 4 <= width;
+  uint32_t word = val;
+#pragma unroll
+  for (int j = 1; j < M; j++) {
+    const int xj = __shfl_down(x, j, 64), yj = __shfl_down(y, j, 64);
+    const uint32_t vj = __shfl_down(val, j, 64);
+    const bool okj = __shfl_down((int)valid, j, 64) != 0 && lane + j < 64;
+    lead = lead && okj && xj == x + j * S && yj == y;
+    word |= vj << (8 * S * j);
+  }
+  bool covered = false;  // the lane (x & 3) / S in front of this one writes this lane's pixels with its dword
+#pragma unroll
+  for (int j = 1; j < M; j++) {
+    const bool lj = __shfl_up((int)lead, j, 64) != 0 && lane >= j;
+    if ((x & 3) == j * S) covered = lj;
+  }
+  if (!valid || covered) return;
+  uint8_t* p = out + (size_t)y * pitch + x;
+  if (lead) {
+    *reinterpret_cast<uint32_t*>(p) = word;  // (x % 4 == 0, base and pitch are multiples of 4)
+  } else {
+    for (int k = 0; k < S && x + k < width; k++) p[k] = (uint8_t)(val >> (8 * k));
+  }
+}
+
+// `index`: the images (positions in `images` and in the destination) this launch decodes, one per workgroup.
+// D: the denominator of the output size (IMREAD_REDUCED_GRAYSCALE_D; 1 = full size); width, height: the OUTPUT size.
+template <int D>
 __global__ __launch_bounds__(64) void jpeg_gray_kernel(const DevImage* __restrict__ images,
                                                         const uint32_t* __restrict__ index,
                                                         const DevTables* __restrict__ tables,
@@ -420,38 +463,70 @@ __global__ __launch_bounds__(64) void jpeg_gray_kernel(const DevImage* __restric
     const bool done = mcu >= nmcu || broken;
     __syncthreads();
     // ---- dequantise + IDCT of the parked blocks: 8 blocks x 8 columns, then 8 blocks x 8 rows, per round ----
-    for (int b0 = 0; b0 < count; b0 += 8) {
-      const int b = b0 + (lane >> 3), i = lane & 7;
-      if (b < count) {
-        int32_t d[8], r[8];
+    if constexpr (D == 1) {
+      for (int b0 = 0; b0 < count; b0 += 8) {
+        const int b = b0 + (lane >> 3), i = lane & 7;
+        if (b < count) {
+          int32_t d[8], r[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) d[k] = (int32_t)s_coef[b][8 * k + i] * (int32_t)s_qt[8 * k + i];
-        idct8_descaled(d, r, 11);  // DESCALE(., CONST_BITS - PASS1_BITS)
+          for (int k = 0; k < 8; k++) d[k] = (int32_t)s_coef[b][8 * k + i] * (int32_t)s_qt[8 * k + i];
+          idct8_descaled(d, r, 11);  // DESCALE(., CONST_BITS - PASS1_BITS)
 #pragma unroll
-        for (int k = 0; k < 8; k++) s_ws[b][8 * k + i] = r[k];
-      }
-      __syncthreads();
-      if (b < count) {
-        int32_t d[8], r[8];
+          for (int k = 0; k < 8; k++) s_ws[b][8 * k + i] = r[k];
+        }
+        __syncthreads();
+        if (b < count) {
+          int32_t d[8], r[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) d[k] = s_ws[b][8 * i + k];
-        idct8_descaled(d, r, 18);  // DESCALE(., 13 + 2 + 3)
-        const int x0 = s_dest[b] & 0xFFFF, y = (s_dest[b] >> 16) + i;
-        if (y < height && x0 < width) {
-          uint8_t px[8];
+          for (int k = 0; k < 8; k++) d[k] = s_ws[b][8 * i + k];
+          idct8_descaled(d, r, 18);  // DESCALE(., 13 + 2 + 3)
+          const int x0 = s_dest[b] & 0xFFFF, y = (s_dest[b] >> 16) + i;
+          if (y < height && x0 < width) {
+            uint8_t px[8];
 #pragma unroll
-          for (int k = 0; k < 8; k++) px[k] = range_limit(r[k]);
-          uint8_t* row = out + (size_t)y * dst_pitch + x0;
-          if (x0 + 8 <= width) {
-            uint32_t lo, hi;
-            memcpy(&lo, px, 4);
-            memcpy(&hi, px + 4, 4);
-            reinterpret_cast<uint32_t*>(row)[0] = lo;  // (x0 % 8 == 0, base and pitch are multiples of 4)
-            reinterpret_cast<uint32_t*>(row)[1] = hi;
-          } else {
-            for (int k = 0; k < 8 && x0 + k < width; k++) row[k] = px[k];
+            for (int k = 0; k < 8; k++) px[k] = range_limit(r[k]);
+            uint8_t* row = out + (size_t)y * dst_pitch + x0;
+            if (x0 + 8 <= width) {
+              uint32_t lo, hi;
+              memcpy(&lo, px, 4);
+              memcpy(&hi, px + 4, 4);
+              reinterpret_cast<uint32_t*>(row)[0] = lo;  // (x0 % 8 == 0, base and pitch are multiples of 4)
+              reinterpret_cast<uint32_t*>(row)[1] = hi;
+            } else {
+              for (int k = 0; k < 8 && x0 + k < width; k++) row[k] = px[k];
+            }
           }
         }
+        __syncthreads();
+      }
+    } else {
+      // ---- the reduced forms (vsf_jpeg_idct_reduced.h): pass 1 over (block, column the form reads), pass 2 with lane =
+      // row x 16 + block; a block gives S x S pixels at its origin / D ----
+      constexpr int S = 8 / D, M = D / 2;
+      if constexpr (D != 8) {
+        constexpr int C = D == 2 ? 8 : 5;  // column slots per block (4 x 4: column 4 idles; 2 x 2: columns 0, 1, 3, 5, 7)
+        for (int t = lane; t < count * C; t += 64) {
+          const int b = t / C, j = t - b * C, col = D == 2 ? j : (j < 2 ? j : 2 * j - 1);
+          if (vsf_idct::used_column<D>(col)) vsf_idct::pass1_column<D>(s_coef[b], s_qt, col, s_ws[b]);
+        }
+        __syncthreads();
+      }
+      {
+        const int b = lane & 15, r = lane >> 4;
+        const bool mine = b < count && r < S;
+        uint32_t val = 0;
+        int x = 0, y = 0;
+        if (mine) {
+          uint8_t px[4] = {0, 0, 0, 0};
+          if constexpr (D == 8)
+            px[0] = vsf_idct::red1(vsf_idct::dequant(s_coef[b][0], s_qt[0]));
+          else
+            vsf_idct::pass2_row<D>(&s_ws[b][8 * r], px);
+          memcpy(&val, px, 4);
+          x = (s_dest[b] & 0xFFFF) / D;
+          y = (s_dest[b] >> 16) / D + r;
+        }
+        store_reduced_packed<S, M>(out, dst_pitch, width, lane, x, y, val, mine && y < height && x < width);
       }
       __syncthreads();
     }
@@ -1528,6 +1603,76 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(const DevImage* __restric
   }
 }
 
+// The same for the reduced forms (vsf_jpeg_idct_reduced.h), D = 2, 4, 8: width x height is the OUTPUT size, a block gives
+// S x S pixels, S = 8 / D.  The design question is the stores, not the arithmetic: a block's row is 4, 2 or 1 byte wide.  So the
+// work is cut by the OUTPUT, not by the coefficient buffer's MCU order: a UNIT is one dword of S consecutive rows -- the
+// M = D / 2 blocks side by side that fill it -- units are numbered along a block row and then down, and a wave takes U
+// consecutive units.  In the storing pass a lane is (row, unit) with the unit in the low bits, so consecutive lanes write
+// consecutive dwords of one row (64, 128 or 256 bytes before the row changes), as the full-size kernel's rows are dwords.
+// Where a unit's blocks lie in the coefficient buffer follows from the frame's sampling factors (4:2:0 / 4:2:2 MCUs).  The
+// blocks of the padded grid beyond the image are never read; the last dword of a row is written byte by byte up to width.
+template <int D>
+__global__ __launch_bounds__(64) void jpeg_idct_reduced_kernel(const DevImage* __restrict__ images,
+                                                                const uint32_t* __restrict__ index,
+                                                                const DevTables* __restrict__ tables,
+                                                                const int16_t* __restrict__ coef_all, size_t coef_stride,
+                                                                int width, int height, uint8_t* __restrict__ dst,
+                                                                size_t dst_image_stride, int dst_pitch) {
+  constexpr int S = 8 / D, M = D / 2;
+  constexpr int U = D == 2 ? 16 : (D == 4 ? 32 : 64);  // units per wave: U x S = 64 lanes store at once
+  constexpr int NBLK = U * M;                          // blocks per wave: 16, 64, 256
+  __shared__ int32_t s_ws[D == 8 ? 8 : NBLK * S * 8];
+  const uint32_t image = index[blockIdx.y];
+  const DevImage& im = images[image];
+  const int h0 = im.h[0], v0 = im.v[0], lum = h0 * v0, mcus_x = im.mcus_x;
+  const int grid_w = mcus_x * h0, grid_h = im.mcus_y * v0;         // the padded block grid of this file
+  const int vbw = (width + S - 1) / S, vbh = (height + S - 1) / S;  // blocks with pixels inside the image
+  const int upr = (vbw + M - 1) / M, units = upr * vbh;
+  const int lane = threadIdx.x, u0 = blockIdx.x * U;
+  const int16_t* coef = coef_all + (size_t)blockIdx.y * (coef_stride / sizeof(int16_t));
+  const uint16_t* qt = tables[im.tables].qt_luma;
+  // block `blk` of this wave (unit u0 + blk / M, its blk % M-th block): its coefficients, or null where there is none
+  auto block_at = [&](int blk) -> const int16_t* {
+    const int u = u0 + blk / M;
+    if (u >= units) return nullptr;
+    const int by = u / upr, bx = (u - by * upr) * M + blk % M;
+    if (bx >= vbw || bx >= grid_w || by >= grid_h) return nullptr;
+    const int my = by / v0, cy = by - my * v0, mx = bx / h0, cx = bx - mx * h0;
+    return coef + ((size_t)(my * mcus_x + mx) * lum + cy * h0 + cx) * 64;
+  };
+  if constexpr (D != 8) {
+    constexpr int C = D == 2 ? 8 : 5;  // column slots per block (4 x 4: column 4 idles; 2 x 2: columns 0, 1, 3, 5, 7)
+    for (int t = lane; t < NBLK * C; t += 64) {
+      const int blk = t / C, j = t - blk * C, col = D == 2 ? j : (j < 2 ? j : 2 * j - 1);
+      const int16_t* c = block_at(blk);
+      if (c && vsf_idct::used_column<D>(col)) vsf_idct::pass1_column<D>(c, qt, col, s_ws + blk * S * 8);
+    }
+    __syncthreads();
+  }
+  const int unit = lane % U, r = lane / U, u = u0 + unit;
+  if (u >= units) return;
+  const int by = u / upr, x0 = (u - by * upr) * 4, y = by * S + r;
+  if (y >= height) return;
+  uint8_t px[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < M; j++) {
+    const int16_t* c = block_at(unit * M + j);
+    if (!c) continue;
+    if constexpr (D == 8)
+      px[j] = vsf_idct::red1(vsf_idct::dequant(c[0], qt[0]));
+    else
+      vsf_idct::pass2_row<D>(s_ws + ((unit * M + j) * S + r) * 8, px + j * S);
+  }
+  uint8_t* row = dst + (size_t)image * dst_image_stride + (size_t)y * dst_pitch + x0;
+  if (x0 + 4 <= width) {
+    uint32_t w;
+    memcpy(&w, px, 4);
+    *reinterpret_cast<uint32_t*>(row) = w;  // (x0 % 4 == 0, base and pitch are multiples of 4)
+  } else {
+    for (int k = 0; k < 4 && x0 + k < width; k++) row[k] = px[k];
+  }
+}
+
 // Bytes of the parallel decoder's stream scratch: the clean streams in the layout of the upload's stream part, then
 // their segment-major copies.
 size_t clean_bytes(size_t stream_bytes, int n_par) {
@@ -1561,7 +1706,9 @@ hipError_t vsf_prepare_jpeg_kernels(int lds_limit) {
 
 // Both decoders over one upload: the files without restart intervals (n_par of them, listed first in the index array
 // at off_index) take the self-synchronising parallel decode, the progressive ones follow, the others take the
-// one-wave-per-image decode.  `scratch` holds what vsf_jpeg_scratch_need(p) asks for.
+// one-wave-per-image decode.  `scratch` holds what vsf_jpeg_scratch_need(p) asks for.  width x height is the OUTPUT size:
+// with p.reduce = d > 1 the files are up to d times that a side and the reduced IDCTs write ceil(W / d) x ceil(H / d) pixels;
+// the entropy decoders and the coefficient buffer are the same (d = 1: the launches below are what they always were).
 void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, int width, int height,
                             const VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
                             int32_t* d_status, int status_stride, bool prog_serial, hipStream_t s) {
@@ -1575,6 +1722,10 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
   const DevScan* scans = reinterpret_cast<const DevScan*>(d_blob + p.off_scans);
   const uint8_t* stream = d_blob + p.off_stream;
   const size_t stream_bytes = p.total - p.off_stream;
+  const int d = p.reduce;
+  // what the progressive kernels derive a component's block grid from: ceil(d * width / 8) == ceil(W / 8) for every file
+  // width W with ceil(W / d) == width, so one value serves a batch of files that differ below the denominator
+  const int file_w = width * d, file_h = height * d;
   if (n_par > 0) {
     // (static + dynamic LDS exceed 64 KB for colour files: vsf_prepare_jpeg_kernels raised the limit at vsf_create)
     hipLaunchKernelGGL(jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads), (size_t)p.max_slots * sizeof(DevHuff), s, images, index, tables, stream,
@@ -1592,19 +1743,29 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
     // fills the scalar units by itself (1024: 13.1 / 13.3 k, 1536: 12.1 / 15.8 k, 2048: 13.5 / 16.7 k).
     if (!prog_serial && scratch.flags && n_prog <= kProgPipeMaxFiles) {
       hipLaunchKernelGGL(jpeg_prog_pipe_kernel, dim3(n_prog), dim3(64 * kProgWaves), 0, s, images, index + n_par, scans,
-                         static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, width, height,
+                         static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, file_w, file_h,
                          scratch.flags);
       only = scratch.flags;  // (the one-wave kernel below then repeats the files that kernel flagged, and no others)
     }
     hipLaunchKernelGGL(jpeg_prog_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par, scans,
-                       static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, width, height, d_status,
+                       static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, file_w, file_h, d_status,
                        status_stride, only);
   }
-  if (n_par + n_prog > 0)
+  if (n_par + n_prog > 0 && d == 1)
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((p.max_luma_blocks + 7) / 8, n_par + n_prog), dim3(64), 0, s, images, index, tables,
                        d_coef, coef_stride, width, height, d_dst, dst_image_stride, dst_pitch);
-  if (n_ser > 0)
-    hipLaunchKernelGGL(jpeg_gray_kernel, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, stream,
+  if (n_par + n_prog > 0 && d > 1) {  // units of the OUTPUT (see jpeg_idct_reduced_kernel): one dword x 8 / d rows each
+    const int side = 8 / d, per_dword = d / 2, per_wave = d == 2 ? 16 : (d == 4 ? 32 : 64);
+    const int vbw = (width + side - 1) / side, vbh = (height + side - 1) / side;
+    const unsigned waves = (unsigned)(((size_t)((vbw + per_dword - 1) / per_dword) * vbh + per_wave - 1) / per_wave);
+    auto* k = d == 2 ? jpeg_idct_reduced_kernel<2> : (d == 4 ? jpeg_idct_reduced_kernel<4> : jpeg_idct_reduced_kernel<8>);
+    hipLaunchKernelGGL(k, dim3(waves, n_par + n_prog), dim3(64), 0, s, images, index, tables, static_cast<const int16_t*>(d_coef),
+                       coef_stride, width, height, d_dst, dst_image_stride, dst_pitch);
+  }
+  if (n_ser > 0) {
+    auto* k = d == 1 ? jpeg_gray_kernel<1> : (d == 2 ? jpeg_gray_kernel<2> : (d == 4 ? jpeg_gray_kernel<4> : jpeg_gray_kernel<8>));
+    hipLaunchKernelGGL(k, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, stream,
                        (uint32_t)(stream_bytes & ~(size_t)3), width, height, d_dst, dst_image_stride, dst_pitch,
                        d_status, status_stride);
+  }
 }

@@ -132,6 +132,7 @@ struct vsf_ctx {
                                  // kObserveKindDevice (both): the images are in the slot of the device ring d_ring
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
     bool bayer = false;          // compressed and device frames: the (decoded) images are bayer_rggb8 mosaics
+    uint8_t reduce = 1;          // compressed frames: both files decode at 1 / reduce (vsf_observe_submit_compressed_reduced)
     int dev_event = -1;          // device frames: the slot whose event in dev_ev follows the copy into the ring ...
     hipStream_t dev_stream = nullptr;  // ... and the producer's stream it was recorded on (a view)
     int stream = 0;              // vsf_observe_submit_stream: whose sequence it belongs to
@@ -384,9 +385,11 @@ void free_retired(vsf_ctx* ctx);  // (callers have waited for every stream of th
 // its offset of the staging pair, ONE upload goes out on `s` and each run's decoder is launched behind it: image i at
 // d_dst + i * dst_image_stride, file i's damage in d_status[i * status_stride].  *n_runs (optional): the runs launched.
 // Which staging pair is free is the caller's business (VsfStaging::uploaded).  The caller checks for launch errors.
+// reduces (optional): width x height is the OUTPUT size and file i decodes at 1 / reduces[i] (vsf_plan_runs).
 vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width,
                        int height, VsfStaging& stage, VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride,
-                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs = nullptr);
+                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs = nullptr,
+                       const uint8_t* reduces = nullptr);
 vsf_status ensure_match_buffers(vsf_ctx* ctx, int pairs, int rows);
 vsf_status ensure_match_host_staging(vsf_ctx* ctx, int rows);  // (host-pointer, synchronous entry points only)
 vsf_status ensure_residual_buffers(vsf_ctx* ctx, int n_frames);

@@ -54,8 +54,10 @@ vsf_status record_ingest_done(vsf_ctx* ctx) {
 
 // vsf_jpeg_decode_gray_batch / vsf_png_decode_gray_batch: n_images files of ONE format, asynchronous on the context's stream.
 vsf_status decode_gray_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* files, const size_t* nbytes, int n_images,
-                             int width, int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride) {
+                             int width, int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride,
+                             int reduce = 1) {
   VsfErrorScope scope_(ctx);
+  if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
   if (!ctx || !files || !nbytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 65535 ||
       height > 65535 || !d_dst)
     return VSF_ERR_INVALID_ARG;
@@ -70,9 +72,10 @@ vsf_status decode_gray_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* f
   // decode are what may still be running, out of the OTHER pair)
   VsfStaging& stage = ctx->ingest_stage[ctx->ingest_flip];
   if (!stage.uploaded) VSF_HIP(stage.uploaded.alloc(hipEventDisableTiming));
-  const std::vector<uint8_t> kinds((size_t)n_images, kind);
+  const std::vector<uint8_t> kinds((size_t)n_images, kind), reduces((size_t)n_images, (uint8_t)reduce);
   const vsf_status st = decode_runs(ctx, files, nbytes, kinds.data(), n_images, width, height, stage, ctx->ingest_scratch, d_dst,
-                                    dst_image_stride, (int)dst_row_stride, ctx->d_status, 0, ctx->stream);
+                                    dst_image_stride, (int)dst_row_stride, ctx->d_status, 0, ctx->stream, nullptr,
+                                    reduce > 1 ? reduces.data() : nullptr);
   if (st != VSF_OK) return st;  // (refused by the host half: nothing was uploaded or launched)
   ctx->ingest_flip ^= 1;
   VSF_STICKY();
@@ -140,11 +143,11 @@ namespace vsfi {
 
 vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width,
                        int height, VsfStaging& stage, VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride,
-                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs) {
+                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs, const uint8_t* reduces) {
   if (n_runs) *n_runs = 0;
   const bool serial = ctx->tuning.jpeg_serial != 0;
   VsfDecodeRuns plan;
-  vsf_status st = vsf_plan_runs(files, nbytes, kinds, n, width, height, serial, &plan);
+  vsf_status st = vsf_plan_runs(files, nbytes, kinds, n, width, height, serial, &plan, reduces);
   if (st != VSF_OK || plan.runs.empty()) return st;
   VsfDecodeNeed need;  // the runs decode one after the other on `s`: they share one scratch of the largest need
   for (const VsfDecodeRun& r : plan.runs) {
@@ -241,6 +244,24 @@ vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, co
     if (st != VSF_OK) return st;
   }
   return VSF_OK;
+}
+
+// cv::imdecode(data, IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8) for reduce = 2, 4, 8 (reduce = 1: vsf_imdecode_gray_batch): a JPEG
+// file of W x H is decoded by libjpeg's reduced inverse DCTs straight to ceil(W / reduce) x ceil(H / reduce) pixels -- width
+// x height here -- through the same upload-and-decode path.  A PNG file with reduce > 1 is VSF_ERR_UNSUPPORTED: cv::imdecode
+// decodes it at full size and calls cv::resize, which is not built here.
+vsf_status vsf_imdecode_reduced_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images,
+                                           int reduce, int width, int height, uint8_t* d_dst, size_t dst_image_stride,
+                                           size_t dst_row_stride) {
+  if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;  // (nothing is looked at, nothing launched)
+  if (reduce == 1) return vsf_imdecode_gray_batch(ctx, files, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride);
+  if (!ctx || !files || !nbytes || n_images < 1 || !d_dst) return VSF_ERR_INVALID_ARG;
+  for (int i = 0; i < n_images; i++) {  // (before anything is launched: a list with a PNG or an unknown file launches nothing)
+    const int kind = vsf_file_kind(files[i], nbytes[i]);
+    if (kind != VSF_FILE_JPEG) return VSF_ERR_UNSUPPORTED;
+  }
+  return decode_gray_batch(ctx, VSF_FILE_JPEG, files, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride,
+                           reduce);
 }
 
 // cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) / cv::imencode(".png", img) for a batch of equally sized images

@@ -25,20 +25,28 @@ int vsf_run_end(const uint8_t* kinds, int n, int i0) {
 
 // Every run of JPEG or PNG files among files [0, n) planned as one upload of its own, the uploads one after the other at
 // 256-byte-aligned offsets of ONE blob of out->total bytes.  The first refusal of a decoder's host half is returned as it is.
+// reduces[i] > 1: file i decodes at 1 / reduces[i] into width x height (JPEG only: imdecode would resize a PNG); a run is
+// files of one format AND one denominator.
 vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
-                         bool force_serial, VsfDecodeRuns* out) {
+                         bool force_serial, VsfDecodeRuns* out, const uint8_t* reduces) {
   out->runs.clear();
   out->total = 0;
   for (int i0 = 0, i1; i0 < n; i0 = i1) {
     i1 = vsf_run_end(kinds, n, i0);
     if (kinds[i0] == VSF_FILE_NONE) continue;
+    const int reduce = reduces ? reduces[i0] : 1;
+    if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
+    if (reduces)
+      for (int i = i0 + 1; i < i1; i++)
+        if (reduces[i] != reduces[i0]) i1 = i;
     out->runs.emplace_back();
     VsfDecodeRun& r = out->runs.back();
     r.i0 = i0;
     r.n = i1 - i0;
     r.kind = kinds[i0];
     r.off = (out->total + 255) & ~(size_t)255;
-    const vsf_status st = r.kind == VSF_FILE_JPEG ? vsf_jpeg_plan(files + i0, nbytes + i0, r.n, width, height, force_serial, &r.jp)
+    if (r.kind == VSF_FILE_PNG && reduce > 1) return VSF_ERR_UNSUPPORTED;
+    const vsf_status st = r.kind == VSF_FILE_JPEG ? vsf_jpeg_plan(files + i0, nbytes + i0, r.n, width, height, force_serial, &r.jp, reduce)
                                                   : vsf_png_plan(files + i0, nbytes + i0, r.n, width, height, &r.pp);
     if (st != VSF_OK) return st;
     out->total = r.off + (r.kind == VSF_FILE_JPEG ? r.jp.total : r.pp.total);
@@ -113,16 +121,34 @@ vsf_status vsf_compressed_image_size(const uint8_t* file, size_t nbytes, int* wi
   return VSF_OK;
 }
 
+// What libjpeg's jpeg_calc_output_dimensions makes of w x h at scale 1 / reduce -- the size cv::imdecode returns for
+// IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8 (reduce = 1: the size itself).
+vsf_status vsf_reduced_size(int w, int h, int reduce, int* rw, int* rh) {
+  if (rw) *rw = 0;
+  if (rh) *rh = 0;
+  if (!rw || !rh || w < 1 || h < 1 || !vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
+  *rw = (int)(((long long)w + reduce - 1) / reduce);
+  *rh = (int)(((long long)h + reduce - 1) / reduce);
+  return VSF_OK;
+}
+
 vsf_status vsf_observe_probe_compressed(const uint8_t* file, size_t nbytes, int width, int height, size_t cap_per_image,
                                         int force_serial, int* kind) {
+  return vsf_observe_probe_compressed_reduced(file, nbytes, 1, width, height, cap_per_image, force_serial, kind);
+}
+
+vsf_status vsf_observe_probe_compressed_reduced(const uint8_t* file, size_t nbytes, int reduce, int width, int height,
+                                                size_t cap_per_image, int force_serial, int* kind) {
   if (kind) *kind = VSF_FILE_NONE;
+  if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
   if (!file || width < 1 || height < 1 || width > 65535 || height > 65535) return VSF_ERR_INVALID_ARG;
   const uint8_t k = (uint8_t)vsf_file_kind(file, nbytes);
   if (k == VSF_FILE_NONE) return VSF_ERR_UNSUPPORTED;
   if (nbytes > cap_per_image || nbytes > 0x40000000u) return VSF_ERR_CAPACITY;
   if (k == VSF_FILE_JPEG && nbytes < 4) return VSF_ERR_INVALID_ARG;
   VsfDecodeRuns plan;
-  const vsf_status st = vsf_plan_runs(&file, &nbytes, &k, 1, width, height, force_serial != 0, &plan);
+  const uint8_t d = (uint8_t)reduce;
+  const vsf_status st = vsf_plan_runs(&file, &nbytes, &k, 1, width, height, force_serial != 0, &plan, &d);
   if (st == VSF_OK && kind) *kind = k;
   return st;
 }

@@ -358,9 +358,11 @@ struct VsfJpegPlan {  // layout of one upload: [image descriptors | decode order
   int n_prog_huff = 0;       // ... and the Huffman tables of their scans (expanded on the device)
   int max_luma_blocks = 0;   // luminance blocks of the (padded) image, largest over the batch
   int max_slots = 1;         // Huffman tables one file's scan uses, largest over the batch
+  int reduce = 1;            // the files are decoded at 1 / reduce (1, 2, 4, 8): IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8
 };
+// width x height: the OUTPUT size; a file of W x H is taken when ceil(W / reduce) == width and ceil(H / reduce) == height.
 vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n, int width, int height, bool force_serial,
-                         VsfJpegPlan* plan);
+                         VsfJpegPlan* plan, int reduce = 1);
 void vsf_jpeg_fill(const VsfJpegPlan& plan, const uint8_t* const* jpeg, int n, uint8_t* dst);
 #endif
 // k_png.hip / vsf_png_host.cc (row f4: cv::imdecode(IMREAD_GRAYSCALE) for grayscale PNG)
@@ -417,6 +419,8 @@ void vsf_launch_png_decode(const uint8_t* d_blob, const VsfPngPlan& plan, int n,
 enum { VSF_FILE_NONE = 0, VSF_FILE_JPEG = 1, VSF_FILE_PNG = 2 };  // (ObserveFrame::kind: 0 is the raw frame there)
 int vsf_file_kind(const uint8_t* file, size_t nbytes);  // by the first bytes, as cv::imdecode's findDecoder tells them apart
 int vsf_run_end(const uint8_t* kinds, int n, int i0);   // one past the last file of the run of one kind that starts at i0
+// The denominators a decode takes, stated ONCE: 1 (full size) and cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8.
+inline bool vsf_reduce_ok(int reduce) { return reduce == 1 || reduce == 2 || reduce == 4 || reduce == 8; }
 struct VsfDecodeRun {  // files [i0, i0 + n) of one format; its upload starts `off` bytes (a multiple of 256) into the blob
   int i0 = 0, n = 0, kind = VSF_FILE_NONE;
   size_t off = 0;
@@ -427,8 +431,12 @@ struct VsfDecodeRuns {
   std::vector<VsfDecodeRun> runs;  // in file order; files of kind VSF_FILE_NONE belong to none
   size_t total = 0;                // bytes of the ONE upload
 };
+// reduces (optional; null: 1 everywhere): file i decodes at 1 / reduces[i] into width x height -- a run also ends where the
+// denominator changes, so one upload carries files of several.  reduces[i] > 1 (2, 4, 8) with a PNG file is
+// VSF_ERR_UNSUPPORTED (cv::imdecode decodes a PNG at full size and calls cv::resize, which is not built here); a value
+// outside {1, 2, 4, 8} VSF_ERR_INVALID_ARG.
 vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
-                         bool force_serial, VsfDecodeRuns* out);
+                         bool force_serial, VsfDecodeRuns* out, const uint8_t* reduces = nullptr);
 void vsf_fill_runs(const VsfDecodeRuns& plan, const uint8_t* const* files, uint8_t* dst);
 // ---- one encode path for JPEG / PNG files (the C ABI's encoders and the ObserveImage queue's debug files) ----
 // cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) / cv::imencode(".png", img) of n equally sized images: image i

@@ -252,12 +252,15 @@ static bool baseline_tail_ok(const uint8_t* p, size_t n, int restart_interval, s
 
 // Parses one JPEG file; fills the image descriptor (without stream_off / tables) and the table set it needs.
 // Returns VSF_OK, VSF_ERR_INVALID_ARG (malformed, or not width x height) or VSF_ERR_UNSUPPORTED.
+// reduce = d > 1 (IMREAD_REDUCED_GRAYSCALE_d): width x height is the OUTPUT size, and the file's own W x H must reduce to it
+// as libjpeg's jpeg_calc_output_dimensions reduces it: ceil(W / d) x ceil(H / d).  Nothing else of the parse changes: the
+// descriptor's MCU grid is the file's.
 // Progressive files (SOF2, T.81 Annex G; libjpeg jdphuff.c): every scan that carries the luminance component is listed in
 // `prog` with the Huffman tables in force when it starts; scans of chroma alone are stepped over.  The progression must be
 // the orderly one (each scan continues where the last one over the same coefficients stopped) and must end with every
 // luminance coefficient at full precision: anything else libjpeg answers with an approximation, and is refused here.
-static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int height, DevImage* im, HostTableSet* tab,
-                             size_t* scan_begin, ProgFile* prog) {
+static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int height, int reduce, DevImage* im,
+                             HostTableSet* tab, size_t* scan_begin, ProgFile* prog) {
   if (!data || nbytes < 4 || data[0] != 0xFF || data[1] != 0xD8) return VSF_ERR_INVALID_ARG;
   uint16_t qt[4][64];
   bool qt_present[4] = {false, false, false, false};
@@ -436,7 +439,7 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
         vmax = std::max(vmax, cv[c]);
       }
       if (ncomp > 1 && (ch[0] != hmax || cv[0] != vmax)) return VSF_ERR_UNSUPPORTED;  // luminance would need upsampling
-      if (W != width || H != height) return VSF_ERR_INVALID_ARG;
+      if ((W + reduce - 1) / reduce != width || (H + reduce - 1) / reduce != height) return VSF_ERR_INVALID_ARG;
       const bool single = ncomp == 1;  // T.81 A.2.2: a one-component scan has one block per MCU
       const int mw = single ? 8 : 8 * hmax, mh = single ? 8 : 8 * vmax;
       if (!single && hmax * vmax > kGroupBlocks) return VSF_ERR_UNSUPPORTED;
@@ -475,7 +478,7 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
       vmax = std::max(vmax, cv[c]);
     }
     if (ch[0] != hmax || cv[0] != vmax) return VSF_ERR_UNSUPPORTED;  // luminance would need upsampling
-    if (W != width || H != height) return VSF_ERR_INVALID_ARG;
+    if ((W + reduce - 1) / reduce != width || (H + reduce - 1) / reduce != height) return VSF_ERR_INVALID_ARG;
     // the coefficient buffer is laid out as the frame's interleaved MCUs (what the IDCT kernel walks): for a gray frame that
     // is one block per MCU whatever its sampling factors say
     const bool single = ncomp == 1;
@@ -501,7 +504,9 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
 // distinct table sets (consecutive frames of a camera share theirs: compared with the previous file's first), packed
 // entropy-coded segments -- without touching the segments themselves.
 vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n, int width, int height, bool force_serial,
-                         VsfJpegPlan* plan) {
+                         VsfJpegPlan* plan, int reduce) {
+  if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
+  plan->reduce = reduce;
   std::vector<DevImage> images((size_t)n);
   std::vector<DevTables> tables;
   std::vector<HostTableSet> sets;
@@ -515,7 +520,7 @@ vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n
   size_t stream_bytes = 0;
   for (int i = 0; i < n; i++) {
     HostTableSet t;
-    const vsf_status st = parse_jpeg(jpeg[i], nbytes[i], width, height, &images[i], &t, &plan->scan_begin[i], &prog);
+    const vsf_status st = parse_jpeg(jpeg[i], nbytes[i], width, height, reduce, &images[i], &t, &plan->scan_begin[i], &prog);
     if (st != VSF_OK) return st;
     if (images[i].n_scans > 0) {
       images[i].first_scan = (uint32_t)scans.size();

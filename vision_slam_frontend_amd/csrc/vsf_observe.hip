@@ -336,11 +336,14 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
   std::vector<const uint8_t*> files((size_t)N);
   std::vector<size_t> sizes((size_t)N);
-  std::vector<uint8_t> kinds((size_t)N);
+  std::vector<uint8_t> kinds((size_t)N), reduces((size_t)N);
+  bool any_reduced = false;
   for (int i = 0; i < N; i++) {
     const int slot = (int)((t0 + i / 2) % o.depth);
     const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
     kinds[i] = fr.kind[i & 1] == kObserveKindDevice ? (uint8_t)VSF_FILE_NONE : fr.kind[i & 1];  // (in the ring: not a file)
+    reduces[i] = fr.reduce;  // (frames of different denominators share the batch and its ONE upload: a run ends where it changes)
+    any_reduced |= fr.reduce > 1;
     files[i] = o.h_cmp + ((size_t)slot * 2 + (size_t)(i & 1)) * o.cmp_slot;
     sizes[i] = fr.nbytes[i & 1];
   }
@@ -349,7 +352,8 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   int runs = 0;
   // (every file passed the decoders' host half at its submit; b.blob is free: the slot's previous batch has left the GPU)
   const vsf_status st = decode_runs(ctx, files.data(), sizes.data(), kinds.data(), N, w, h, b.blob, o.ing_scratch,
-                                    bayer ? o.d_bayer : b.d_img, stride, pitch, b.status, 1, s, &runs);
+                                    bayer ? o.d_bayer : b.d_img, stride, pitch, b.status, 1, s, &runs,
+                                    any_reduced ? reduces.data() : nullptr);
   if (st != VSF_OK || runs == 0) return st;
   // bayer_rggb8 (slam_frontend_main.cc:101-109): every image of such a batch is a decoded mosaic
   if (bayer) vsf_launch_bayer_bg_gray(o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
@@ -357,6 +361,7 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
   o.queue->stats.ingest_commands += 2 + runs + (bayer ? 1 : 0);
   for (int f = 0; f < n; f++) o.queue->stats.compressed += kinds[2 * f] != VSF_FILE_NONE;
+  for (int f = 0; f < n; f++) o.queue->stats.reduced += kinds[2 * f] != VSF_FILE_NONE && reduces[2 * f] > 1;
   return VSF_OK;
 }
 
@@ -851,15 +856,16 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[23] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+  const int64_t v[24] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
                          s.file_commands, (int64_t)ctx->ob_streams, s.multi,
                          s.device_frames, s.device_commands + o.stat_dev_commands,
                          (int64_t)(o.d_ring ? vsf_observe_device_ring_bytes(ctx, o.depth) : 0),
                          s.cloud_frames, s.cloud_commands,
-                         (int64_t)(o.h_wp ? (size_t)o.depth * ((size_t)ctx->p.max_keypoints * 3 * sizeof(double) + sizeof(int32_t)) : 0)};
-  for (int i = 0; i < n && i < 23; i++) out[i] = v[i];
+                         (int64_t)(o.h_wp ? (size_t)o.depth * ((size_t)ctx->p.max_keypoints * 3 * sizeof(double) + sizeof(int32_t)) : 0),
+                         s.reduced};
+  for (int i = 0; i < n && i < 24; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -871,10 +877,10 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx) {
 }
 
 // Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
-// have passed vsf_observe_probe_compressed as kinds[0 / 1].
+// have passed vsf_observe_probe_compressed_reduced as kinds[0 / 1] at 1 / reduce.
 static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
                                  const int* kinds, const size_t* nbytes, bool bayer, const vsf_calibration* calib,
-                                 float best_percent, int frame_life, int64_t* ticket) {
+                                 float best_percent, int frame_life, int64_t* ticket, int reduce = 1) {
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
   if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6)
@@ -948,6 +954,7 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     fr.nbytes[k] = kinds ? (uint32_t)nbytes[k] : 0u;
   }
   fr.bayer = bayer;
+  fr.reduce = (uint8_t)reduce;
   fr.calib = *calib;
   fr.best_percent = best_percent;
   fr.pose = ctx->ob_pose[stream];
@@ -984,10 +991,31 @@ vsf_status vsf_observe_submit_compressed(vsf_ctx* ctx, const uint8_t* left, size
                                               frame_life, ticket);
 }
 
+// Both compressed submits: the decoders' host half at 1 / reduce for the two files, then the frame's booking.
+static vsf_status observe_submit_files(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                       size_t right_bytes, int bayer, int reduce, const vsf_calibration* calib,
+                                       float best_percent, int frame_life, int64_t* ticket);
+
 vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes,
                                                 const uint8_t* right, size_t right_bytes, int bayer,
                                                 const vsf_calibration* calib, float best_percent, int frame_life,
                                                 int64_t* ticket) {
+  return observe_submit_files(ctx, stream, left, left_bytes, right, right_bytes, bayer, 1, calib, best_percent, frame_life, ticket);
+}
+
+// IMREAD_REDUCED_GRAYSCALE_<reduce> frames.  No `bayer`: a mosaic cannot be reduced in the DCT domain.
+vsf_status vsf_observe_submit_compressed_reduced(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes,
+                                                 const uint8_t* right, size_t right_bytes, int reduce,
+                                                 const vsf_calibration* calib, float best_percent, int frame_life,
+                                                 int64_t* ticket) {
+  if (ticket) *ticket = -1;
+  if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
+  return observe_submit_files(ctx, stream, left, left_bytes, right, right_bytes, 0, reduce, calib, best_percent, frame_life, ticket);
+}
+
+static vsf_status observe_submit_files(vsf_ctx* ctx, int stream, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                       size_t right_bytes, int bayer, int reduce, const vsf_calibration* calib,
+                                       float best_percent, int frame_life, int64_t* ticket) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
       frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
@@ -998,12 +1026,14 @@ vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const 
   const size_t cap = compressed_cap(ctx);
   const size_t nbytes[2] = {left_bytes, right_bytes};
   int kinds[2] = {0, 0};
-  vsf_status st = vsf_observe_probe_compressed(left, left_bytes, ctx->p.width, ctx->p.height, cap, ctx->tuning.jpeg_serial, &kinds[0]);
+  vsf_status st = vsf_observe_probe_compressed_reduced(left, left_bytes, reduce, ctx->p.width, ctx->p.height, cap,
+                                                       ctx->tuning.jpeg_serial, &kinds[0]);
   if (st == VSF_OK)
-    st = vsf_observe_probe_compressed(right, right_bytes, ctx->p.width, ctx->p.height, cap, ctx->tuning.jpeg_serial, &kinds[1]);
+    st = vsf_observe_probe_compressed_reduced(right, right_bytes, reduce, ctx->p.width, ctx->p.height, cap,
+                                              ctx->tuning.jpeg_serial, &kinds[1]);
   if (st != VSF_OK) return st;
   return observe_submit(ctx, stream, left, right, ctx->p.width, ctx->p.height, 0, kinds, nbytes, bayer != 0, calib,
-                        best_percent, frame_life, ticket);
+                        best_percent, frame_life, ticket, reduce);
 }
 
 size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth) {
@@ -1093,6 +1123,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     fr.kind[0] = fr.kind[1] = kObserveKindDevice;
     fr.nbytes[0] = fr.nbytes[1] = 0u;
     fr.bayer = bayer;
+    fr.reduce = 1;
     fr.dev_event = ev_slot;
     fr.dev_stream = producer;
     fr.calib = *calib;
@@ -1221,6 +1252,20 @@ vsf_status vsf_observe_stereo_compressed(vsf_ctx* ctx, const uint8_t* left, size
   int64_t ticket = -1;
   const vsf_status st =
       vsf_observe_submit_compressed(ctx, left, left_bytes, right, right_bytes, bayer, calib, best_percent, frame_life, &ticket);
+  if (st != VSF_OK) return st;
+  return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
+}
+
+vsf_status vsf_observe_stereo_compressed_reduced(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
+                                                 size_t right_bytes, int reduce, const vsf_calibration* calib,
+                                                 float best_percent, int frame_life, uint8_t* out, size_t cap,
+                                                 size_t* out_bytes) {
+  VsfErrorScope scope_(ctx, false);
+  if (!out || !out_bytes) return VSF_ERR_INVALID_ARG;
+  *out_bytes = 0;
+  int64_t ticket = -1;
+  const vsf_status st = vsf_observe_submit_compressed_reduced(ctx, 0, left, left_bytes, right, right_bytes, reduce, calib,
+                                                              best_percent, frame_life, &ticket);
   if (st != VSF_OK) return st;
   return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
 }

@@ -72,6 +72,10 @@ def lib() -> C.CDLL:
         L.vsfh_set_debug_jpeg_quality.restype = None
         L.vsfh_set_debug_png.argtypes = [vp, i32]
         L.vsfh_set_debug_png.restype = None
+        L.vsfh_set_imdecode_reduce.argtypes = [vp, i32]
+        L.vsfh_set_imdecode_reduce.restype = None
+        L.vsfh_set_compressed_cap.argtypes = [vp, sz]
+        L.vsfh_set_compressed_cap.restype = None
         L.vsfh_debug_image_compressed_format.argtypes = [vp, i32]
         L.vsfh_debug_image_compressed.argtypes = [vp, i32, vp, sz]
         L.vsfh_debug_image_compressed.restype = sz
@@ -152,7 +156,8 @@ def default_calibration() -> capi.VsfCalibration:
 class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
-                 debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False):
+                 debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False, imdecode_reduce: int = 1,
+                 compressed_cap: int = 0):
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
@@ -165,6 +170,10 @@ class Frontend:
             lib().vsfh_set_debug_png(self._h, 1)
         if visualization:  # FrontendConfig::visualization_: the point cloud and pose graph of Frontend::GetVisualization
             lib().vsfh_set_visualization(self._h, 1)
+        if imdecode_reduce != 1:  # FrontendConfig::imdecode_reduce_: IMREAD_REDUCED_GRAYSCALE_N; width x height is the reduced size
+            lib().vsfh_set_imdecode_reduce(self._h, int(imdecode_reduce))
+        if compressed_cap:  # FrontendConfig::compressed_cap_: bytes a payload may have (the default is sized by width x height)
+            lib().vsfh_set_compressed_cap(self._h, int(compressed_cap))
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend")
@@ -276,10 +285,30 @@ class Frontend:
             raise capi.VsfError(st, "Frontend::ObserveDeviceImage")
         return added
 
+    def set_imdecode_reduce(self, reduce: int):
+        """FrontendConfig::imdecode_reduce_: 1 (IMREAD_GRAYSCALE) or 2, 4, 8 (IMREAD_REDUCED_GRAYSCALE_N) for the compressed
+        frames observed from now on.  The calibration is the caller's, for the reduced image."""
+        lib().vsfh_set_imdecode_reduce(self._h, int(reduce))
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "Frontend::set_imdecode_reduce")
+
+    def set_compressed_cap(self, cap_per_image: int):
+        """FrontendConfig::compressed_cap_: bytes one compressed payload may have (0: width x height + 64 KB of the object's
+        image size -- the REDUCED size with imdecode_reduce > 1, so files of a larger camera usually need this).  Before the
+        first compressed frame or while no frame is in flight; a group member sets the group's."""
+        lib().vsfh_set_compressed_cap(self._h, int(cap_per_image))
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "Frontend::set_compressed_cap")
+
     def observe_compressed_image(self, left: bytes, right: bytes, bayer_rggb8: bool = False, time: float = 0.0,
-                                 allow_status=()) -> bool:
+                                 allow_status=(), reduce: int | None = None) -> bool:
         """Frontend::ObserveCompressedImage: the two CompressedImage payloads (JPEG or PNG) as they came; decoded on the GPU
-        inside the queue.  A status in `allow_status` (a refused file) is left for last_status instead of raising."""
+        inside the queue.  A status in `allow_status` (a refused file) is left for last_status instead of raising.
+        reduce: sets FrontendConfig::imdecode_reduce_ first (None: as it is)."""
+        if reduce is not None:
+            self.set_imdecode_reduce(reduce)
         lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
         added = bool(lib().vsfh_observe_compressed_image(self._h, _p(lb), len(lb), _p(rb), len(rb), int(bool(bayer_rggb8)),
                                                          time))
@@ -433,7 +462,7 @@ class FrontendGroup:
     Frontend (owned by the group)."""
 
     def __init__(self, width: int, height: int, fundamentals, nfeatures: int = 10000, device: int = 0, best_percents=None,
-                 frame_life: int = 0):
+                 frame_life: int = 0, imdecode_reduces=None, compressed_cap: int = 0):
         F = np.ascontiguousarray(fundamentals, np.float32).reshape(-1, 9)
         n = len(F)
         bp = None if best_percents is None else np.ascontiguousarray(best_percents, np.float32).reshape(n)
@@ -450,6 +479,10 @@ class FrontendGroup:
             m.size, m.device = (width, height), device
             m.close = lambda: None  # (the group owns its members)
             self.members.append(m)
+        for i, d in enumerate(imdecode_reduces or ()):  # per camera: FrontendConfig::imdecode_reduce_ of member i
+            self.members[i].set_imdecode_reduce(d)
+        if compressed_cap:  # the group's queue has ONE byte cap: size it for the largest camera's files
+            self.members[0].set_compressed_cap(compressed_cap)
 
     def __len__(self):
         return len(self.members)
@@ -496,7 +529,10 @@ class FrontendGroup:
         return added
 
     def observe_compressed_image(self, i: int, left: bytes, right: bytes, bayer_rggb8: bool = False, time: float = 0.0,
-                                 allow_status=()) -> bool:
+                                 allow_status=(), reduce: int | None = None) -> bool:
+        """reduce: member i's FrontendConfig::imdecode_reduce_ from this frame on (per camera; None: as it is)."""
+        if reduce is not None:
+            self.members[i].set_imdecode_reduce(reduce)
         lb, rb = np.frombuffer(bytes(left), np.uint8), np.frombuffer(bytes(right), np.uint8)
         added = bool(lib().vsfh_group_observe_compressed_image(self._h, i, _p(lb), len(lb), _p(rb), len(rb),
                                                                int(bool(bayer_rggb8)), time))

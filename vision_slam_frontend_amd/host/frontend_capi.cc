@@ -168,6 +168,10 @@ int vsfh_debug_image(void* f, int stereo, int i, uint8_t* out, size_t cap, int r
 
 void vsfh_set_debug_jpeg_quality(void* f, int quality) { static_cast<Frontend*>(f)->set_debug_jpeg_quality(quality); }
 void vsfh_set_debug_png(void* f, int on) { static_cast<Frontend*>(f)->set_debug_png(on != 0); }
+// FrontendConfig::imdecode_reduce_ (a group's member: the pointer vsfh_group_member returns)
+void vsfh_set_imdecode_reduce(void* f, int reduce) { static_cast<Frontend*>(f)->set_imdecode_reduce(reduce); }
+// FrontendConfig::compressed_cap_ (a group's member: the group's)
+void vsfh_set_compressed_cap(void* f, size_t cap_per_image) { static_cast<Frontend*>(f)->set_compressed_cap(cap_per_image); }
 // The format of what vsfh_debug_image_compressed returns: 0 none, 1 "jpeg", 2 "png".
 int vsfh_debug_image_compressed_format(void* f, int stereo) {
   Frontend* fe = static_cast<Frontend*>(f);

@@ -125,6 +125,8 @@ FrontendConfig::FrontendConfig() {
   debug_jpeg_quality_ = 0;
   debug_png_ = false;
   visualization_ = false;
+  imdecode_reduce_ = 1;  // IMREAD_GRAYSCALE, the reference's flag
+  compressed_cap_ = 0;   // the library's default: the context's width x height + 64 KB
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
   descriptor_extract_type_ = DescriptorExtractorType::ORB;
   best_percent_ = 0.3f;
@@ -297,6 +299,7 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
     if (last_status_ == VSF_OK) last_status_ = vsf_set_option(ctx_, ov.first, ov.second);
   if (last_status_ == VSF_OK) last_status_ = vsf_observe_configure(ctx_, ctx_depth_, min_batch_, 0);
   if (last_status_ == VSF_OK && n_streams > 1) last_status_ = vsf_observe_set_streams(ctx_, n_streams);
+  if (last_status_ == VSF_OK && config_.compressed_cap_ > 0) last_status_ = vsf_observe_set_compressed_cap(ctx_, config_.compressed_cap_);
   // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
   if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
   // ... and leave as files when the configuration asks for one form of them (both: the second request is refused)
@@ -623,7 +626,10 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
     const vsf_dev_frame df{fp.left, fp.right, fp.left_bytes, fp.right_bytes};
     last_status_ = vsf_observe_submit_dev(ctx_, stream_, &df, 1, fp.bayer ? VSF_PIX_BAYER_RGGB8 : VSF_PIX_MONO8, fp.hip_stream,
                                           &calib, config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
-  } else if (fp.compressed)  // (a file the host half of the decoders refuses: no ticket, nothing booked, the queue as it was)
+  } else if (fp.compressed && fp.reduce > 1)  // IMREAD_REDUCED_GRAYSCALE_N (refusals as below)
+    last_status_ = vsf_observe_submit_compressed_reduced(ctx_, stream_, fp.left, fp.left_bytes, fp.right, fp.right_bytes, fp.reduce,
+                                                         &calib, config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
+  else if (fp.compressed)  // (a file the host half of the decoders refuses: no ticket, nothing booked, the queue as it was)
     last_status_ = vsf_observe_submit_compressed_stream(ctx_, stream_, fp.left, fp.left_bytes, fp.right, fp.right_bytes,
                                                         fp.bayer ? 1 : 0, &calib, config_.best_percent_,
                                                         (int)config_.frame_life_, &pf.ticket);
@@ -897,6 +903,12 @@ void Frontend::FinishNode(const Frame& curr_frame, const std::vector<VisionFeatu
   frame_list_.push_back(curr_frame);
 }
 
+// The denominators the library takes are stated in the library: vsf_reduced_size refuses every other one.
+static bool ReduceOk(int reduce) {
+  int w = 0, h = 0;
+  return vsf_reduced_size(1, 1, reduce, &w, &h) == VSF_OK;
+}
+
 // slam_frontend_main.cc:98-133 + cc:400-472: the payloads of the two sensor_msgs::CompressedImage messages as they came.
 bool Frontend::ObserveCompressedImage(const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
                                       bool bayer_rggb8, double /*time*/) {
@@ -906,17 +918,24 @@ bool Frontend::ObserveCompressedImage(const uint8_t* left, size_t left_bytes, co
     last_status_ = VSF_ERR_UNSUPPORTED;  // compressed frames exist in the queue only
     return false;
   }
+  const int reduce = config_.imdecode_reduce_;
+  if (!ReduceOk(reduce) || (bayer_rggb8 && reduce > 1)) {
+    last_status_ = VSF_ERR_INVALID_ARG;  // (a mosaic cannot be reduced in the DCT domain: nothing is booked)
+    return false;
+  }
   int width = 0, height = 0;
   if (ctx_) {
     vsf_params p;
     vsf_get_params(ctx_, &p);
     width = p.width;
     height = p.height;
-  } else {  // the first frame sizes the context, as the first ObserveImage does
+  } else {  // the first frame sizes the context, as the first ObserveImage does: by what imdecode would return for it
     last_status_ = left && right ? vsf_compressed_image_size(left, left_bytes, &width, &height) : VSF_ERR_INVALID_ARG;
+    if (last_status_ == VSF_OK) last_status_ = vsf_reduced_size(width, height, reduce, &width, &height);
     if (last_status_ != VSF_OK) return false;
   }
   FramePayload fp;
+  fp.reduce = reduce;
   fp.left = left;
   fp.right = right;
   fp.left_bytes = left_bytes;
@@ -1040,6 +1059,19 @@ void Frontend::set_debug_jpeg_quality(int quality) {
   }
   config_.debug_jpeg_quality_ = quality;
   if (ctx_ && (config_.debug_images_ || quality == 0)) last_status_ = vsf_observe_set_debug_jpeg(ctx_, quality);
+}
+
+void Frontend::set_imdecode_reduce(int reduce) {
+  last_status_ = ReduceOk(reduce) ? VSF_OK : VSF_ERR_INVALID_ARG;
+  if (last_status_ == VSF_OK) config_.imdecode_reduce_ = reduce;
+}
+
+void Frontend::set_compressed_cap(size_t cap_per_image) {
+  if (group_) return group_->set_compressed_cap(cap_per_image);
+  config_.compressed_cap_ = cap_per_image;
+  // (a context that exists takes it now -- the queue must be empty, or not have seen a compressed frame yet; one that does not
+  // takes it when it is created)
+  last_status_ = ctx_ ? vsf_observe_set_compressed_cap(ctx_, cap_per_image) : VSF_OK;
 }
 
 void Frontend::set_debug_png(bool on) {
@@ -1216,6 +1248,13 @@ void FrontendGroup::set_queue(int depth, int batch_frames, int min_batch) {
 }
 void FrontendGroup::set_queue_thread(bool on) {
   for (Frontend* m : members_) m->queue_thread_ = on;
+}
+// (the byte cap is the queue's, and the queue is the group's: one value, whichever member asks for it)
+void FrontendGroup::set_compressed_cap(size_t cap_per_image) {
+  for (Frontend* m : members_) m->config_.compressed_cap_ = cap_per_image;
+  Frontend& lead = *members_[0];
+  const vsf_status st = lead.ctx_ ? vsf_observe_set_compressed_cap(lead.ctx_, cap_per_image) : VSF_OK;
+  for (Frontend* m : members_) m->last_status_ = st;
 }
 
 // (the setters of slam_frontend.h that a group member hands to its group)

@@ -87,6 +87,20 @@ struct FrontendConfig {
   // slam_frontend_main.cc:194-225) -- the point cloud on the GPU, inside the queue's batches, the pose graph while nodes and
   // factors are booked -- for Frontend::GetVisualization.  Off by default: nothing is launched, copied or kept for it.
   bool visualization_;
+  // An addition: which of cv::imdecode's flags ObserveCompressedImage mirrors.  1 (the default): IMREAD_GRAYSCALE, the
+  // reference's (slam_frontend_main.cc:100).  2, 4, 8: IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8 -- a JPEG payload of W x H is
+  // decoded by libjpeg's reduced inverse DCTs straight to ceil(W / N) x ceil(H / N) pixels (vsf_observe_submit_compressed_reduced),
+  // which is then the image size of the object.  The calibration in this configuration is the caller's, FOR THE REDUCED
+  // IMAGE: nothing is scaled.  PNG payloads are refused at N > 1 (VSF_ERR_UNSUPPORTED), and so are bayer_rggb8 frames
+  // (VSF_ERR_INVALID_ARG: a mosaic cannot be reduced in the DCT domain).  In a FrontendGroup it is per member: a 1280 x 960
+  // camera at 2 and a 640 x 480 camera at 1 share one 640 x 480 context.
+  int imdecode_reduce_;
+  // An addition: bytes one compressed payload may have (vsf_observe_set_compressed_cap), applied when the context is created.
+  // 0 (the default): the library's, width x height + 64 KB OF THE CONTEXT'S SIZE -- with imdecode_reduce_ > 1 that is the
+  // REDUCED size, and a camera's files of N times the side are usually larger: set this (vsf_observe_default_compressed_cap of
+  // the camera's own size is a good value), or the payloads are refused with VSF_ERR_CAPACITY.  One value per context: a
+  // FrontendGroup takes member 0's, and set_compressed_cap on any member sets the group's.
+  size_t compressed_cap_;
   DescriptorExtractorType descriptor_extract_type_;
   float best_percent_;
   float nn_match_ratio_;
@@ -233,6 +247,12 @@ class Frontend {
   void set_debug_images(bool on);
   void set_debug_jpeg_quality(int quality);  // config.debug_jpeg_quality_, under the same rule
   void set_debug_png(bool on);               // config.debug_png_, under the same rule
+  // config.imdecode_reduce_ (1, 2, 4, 8; anything else: VSF_ERR_INVALID_ARG and no change).  Legal at any time: it is read by
+  // each ObserveCompressedImage; the image size stays what the first frame made it.
+  void set_imdecode_reduce(int reduce);
+  // config.compressed_cap_.  Before the first compressed frame, or while no frame is in flight (vsf_observe_set_compressed_cap's
+  // rule; otherwise last_status() says VSF_ERR_INVALID_ARG and nothing changes on the device).
+  void set_compressed_cap(size_t cap_per_image);
   // Frames ObserveImage may leave in the queue when pipelined (1..1024, default 256) and the most frames one batch carries
   // (default 128; the context's extraction buffers are sized for it: ~25 MB of HBM per 640x480 frame; the queue's staging
   // and result rings are pinned host memory: depth x (two images + vsf_observe_capacity)).  Measured on an MI355X at
@@ -298,6 +318,7 @@ class Frontend {
     const uint8_t* right = nullptr;
     size_t step = 0, left_bytes = 0, right_bytes = 0;
     bool compressed = false, bayer = false, device = false;
+    int reduce = 1;  // compressed: config.imdecode_reduce_ at the call
     void* hip_stream = nullptr;
   };
   bool ObserveFused(int width, int height, const FramePayload& fp);
@@ -414,6 +435,7 @@ class FrontendGroup {
   void set_pipelined(bool on);
   void set_queue(int depth, int batch_frames, int min_batch);  // depth / batch_frames 0, min_batch < 0: as it is
   void set_queue_thread(bool on);
+  void set_compressed_cap(size_t cap_per_image);
   vsf_status last_status() const { return last_status_; }
   vsf_ctx* context() const { return members_.empty() ? nullptr : members_[0]->ctx_; }
 
