@@ -506,9 +506,10 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx);
  * stream in front of it starts a new batch; frames of different streams may differ in both and share one.  Frames with
  * different `bayer` never share a batch.
  *   A stream outside [0, n_streams): VSF_ERR_INVALID_ARG, no ticket, the queue as it was.
- *   Debug images are single-stream: vsf_observe_set_debug_images / _jpeg / _png with more than one stream return
- * VSF_ERR_UNSUPPORTED, and so does vsf_observe_set_streams(> 1) while debug images are on (the match image needs each
- * stream's previous frame, the stereo lines rand()'s colour sequence per stream). */
+ *   Debug images of several streams need vsf_observe_set_debug_seeds, which gives every stream rand()'s colour sequence of
+ * its own.  Without that call vsf_observe_set_debug_images / _jpeg / _png with more than one stream return
+ * VSF_ERR_UNSUPPORTED, and so does vsf_observe_set_streams(> 1) while debug images are on: the stereo lines' colours would
+ * come from ONE sequence, the process's rand(), whatever stream a frame belongs to. */
 #define VSF_OBSERVE_MAX_STREAMS 64
 vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams);
 vsf_status vsf_observe_submit_stream(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h,
@@ -597,7 +598,7 @@ size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth);
  * copy commands the device path issued (a submit's one launch, a batch's copies out of the ring, its demosaic where no
  * compressed frame brings one), [19] bytes of the device ring -- the last three are 0 for a queue that has seen no device
  * frame; [20] .. [22] the point cloud's (vsf_observe_set_world_points); [23] frames launched at a reduced size
- * (vsf_observe_submit_compressed_reduced with reduce > 1) }. */
+ * (vsf_observe_submit_compressed_reduced with reduce > 1); [24], [25] the colour generators' (vsf_observe_set_debug_seeds) }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,
@@ -610,6 +611,23 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
  * it took.  Off (the default): results, launches and their cost are exactly those without the switch.  It changes only
  * before the queue's first frame (or after vsf_observe_reset); the queue is then rebuilt with the threshold carried over. */
 vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on);
+/* A colour generator per stream, on the device: stream s takes the colours that srand(seeds[s]) followed by rand(), rand(),
+ * ... gives in glibc (csrc/vsf_glibc_random.h states the generator once, for the device and the host) -- in the reference's
+ * order, three calls per stereo pair, the first being channel 2, a frame taking clamp(pairs, 0, max_keypoints) of them.
+ * Seed 1 is a fresh process; seed 0 is 1, as in glibc.  The states live in device memory (31 words and a position per
+ * stream), seeded when the queue is built, by vsf_observe_reset, and by vsf_observe_reset_stream for that stream alone; in
+ * every batch's tail one more kernel -- one wave per stream present -- draws the colours of that stream's frames in
+ * submission order, carrying on where the stream's previous frame ended.  The process's rand() is never called, there is no
+ * pinned colour ring and the submitting thread draws nothing.  The match image's previous frame is kept per stream as well.
+ *   With seeds installed the three debug switches are accepted for any number of streams, and each stream's images, files
+ * and header words 14 / 15 are those of a one-stream context of its own after srand(seeds[s])
+ * (tests/test_gpu_observe_stream_debug.py).  One stream with a seed is legal: the old switch's bytes after srand(seed).
+ *   The order of use is: streams, seeds, switch.  n must be the number of streams; (NULL, 0) goes back to the process's
+ * rand().  Legal only while debug images are off and before the queue's first frame or after vsf_observe_reset; and with
+ * seeds installed vsf_observe_set_streams with another count is refused: VSF_ERR_INVALID_ARG each, the queue as it was.
+ *   Never called: statuses, bytes, launches and the use of rand() are exactly what they were.  vsf_observe_stats values
+ * [24] frames whose colours came from a stream's generator, [25] launches of the colour kernel: 0 without seeds. */
+vsf_status vsf_observe_set_debug_seeds(vsf_ctx* ctx, const uint32_t* seeds, int n);
 /* A collected frame's debug images inside the pinned debug ring (NULL where the frame has none); valid under the rule of
  * vsf_observe_collect_view (until `depth` further frames have been submitted). */
 vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** stereo, const uint8_t** match);
@@ -660,6 +678,12 @@ vsf_status vsf_observe_set_world_points(vsf_ctx* ctx, int on, const float* cam_t
  * vsf_observe_reset every stream's.  Host bookkeeping only: it never waits, sends nothing, and is legal at any time, also with
  * the switch off (the pose is then never read).  loc: 3 floats, quat_xyzw: 4 floats. */
 vsf_status vsf_observe_set_pose(vsf_ctx* ctx, int stream, const float* loc, const float* quat_xyzw);
+/* A stream's own left_cam_to_robot (3 x 4 row-major) in place of vsf_observe_set_world_points' -- two cameras on one robot
+ * never share one; m == NULL: the context's again.  Host bookkeeping like vsf_observe_set_pose: legal at any time, sticky,
+ * captured by each submit, read only with the point cloud on.  Extrinsics belong to the camera, not to the sequence: kept
+ * across vsf_observe_reset and vsf_observe_reset_stream, dropped when vsf_observe_set_streams changes the number of streams.
+ * A stream outside [0, n_streams): VSF_ERR_INVALID_ARG. */
+vsf_status vsf_observe_set_stream_cam_to_robot(vsf_ctx* ctx, int stream, const float* m);
 /* A collected frame's points inside the pinned ring: *xyz points at *n points of three doubles (NULL where n is 0); lifetime
  * and ticket rules of vsf_observe_debug_view (collected, and fewer than `depth` frames submitted since).
  * VSF_ERR_INVALID_ARG with the switch off. */

@@ -50,6 +50,7 @@ EXPORTS = [
     "vsf_observe_world_points_view",
     "vsf_imdecode_reduced_gray_batch", "vsf_reduced_size", "vsf_observe_probe_compressed_reduced",
     "vsf_observe_submit_compressed_reduced", "vsf_observe_stereo_compressed_reduced",
+    "vsf_observe_set_debug_seeds", "vsf_observe_set_stream_cam_to_robot",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -60,7 +61,8 @@ STAGE_COUNT = 8
 OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",
                  "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands", "streams",
                  "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes",
-                 "world_points_frames", "world_points_commands", "world_points_ring_bytes", "reduced_frames")
+                 "world_points_frames", "world_points_commands", "world_points_ring_bytes", "reduced_frames",
+                 "seeded_colour_frames", "colour_commands")
 # vsf_observe_submit_dev's pixel formats (include/vsf.h)
 PIX_MONO8, PIX_BAYER_RGGB8 = 0, 1
 
@@ -312,6 +314,8 @@ def lib() -> C.CDLL:
         L.vsf_observe_set_debug_images.argtypes = [vp, i32]
         L.vsf_observe_debug_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
         L.vsf_observe_set_debug_jpeg.argtypes = [vp, i32]
+        L.vsf_observe_set_debug_seeds.argtypes = [vp, vp, i32]
+        L.vsf_observe_set_stream_cam_to_robot.argtypes = [vp, i32, vp]
         L.vsf_observe_debug_jpeg_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
         L.vsf_observe_set_debug_png.argtypes = [vp, i32]
         L.vsf_observe_debug_png_view.argtypes = [vp, C.c_int64, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -619,6 +623,23 @@ class Context:
         l = np.ascontiguousarray(loc, np.float32).reshape(3)
         q = np.ascontiguousarray(quat_xyzw, np.float32).reshape(4)
         self._check(lib().vsf_observe_set_pose(self._h, stream, _p(l), _p(q)), "vsf_observe_set_pose")
+
+    def observe_set_debug_seeds(self, seeds, allow_status=()) -> int:
+        """A colour generator per stream (vsf_observe_set_debug_seeds): one seed per stream, None: the process's rand() again.
+        Returns the status."""
+        v = None if seeds is None else np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        st = lib().vsf_observe_set_debug_seeds(self._h, _p(v) if v is not None else None, 0 if v is None else len(v))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_set_debug_seeds", lib().vsf_last_hip_error(self._h))
+        return st
+
+    def observe_set_stream_cam_to_robot(self, stream: int, cam_to_robot=None, allow_status=()) -> int:
+        """A stream's own left_cam_to_robot, 3 x 4 float32 (vsf_observe_set_stream_cam_to_robot); None: the context's again."""
+        c = None if cam_to_robot is None else np.ascontiguousarray(cam_to_robot, np.float32).reshape(12)
+        st = lib().vsf_observe_set_stream_cam_to_robot(self._h, stream, _p(c) if c is not None else None)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_set_stream_cam_to_robot", lib().vsf_last_hip_error(self._h))
+        return st
 
     def observe_world_points(self, ticket: int, allow_status=()):
         """A collected frame's points (vsf_observe_world_points_view), copied: an (n, 3) float64 array -- or, with

@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "vsf_ctx.h"
+#include "vsf_glibc_random.h"
 
 using namespace vsfi;
 
@@ -221,6 +222,63 @@ vsf_status draw_dev(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int n, const 
   return VSF_OK;
 }
 
+// ---- the stereo lines' colours with a generator per stream (vsf_observe_set_debug_seeds) ----
+// One wave per frame of the batch; the wave of a stream's FIRST frame in the batch (params[f].prev < 0) walks that stream's
+// frames in submission order, every other wave leaves at once.  The chain is serial -- a draw needs the draw three before it
+// --, so every lane computes the same values and lane j keeps colour j of a block of 31 for one store.  The window of 31
+// words stays in registers: colours31 (vsf_glibc_random.h) names every word by a constant as long as the rear pointer is 0
+// when a block starts, so after each frame the window goes through LDS once, written at the rotated index and read back
+// in order.  A frame takes clamp(npairs, 0, K) colours whether or not its rows are valid (cc:95), as debug_ops_kernel reads them.
+__global__ __launch_bounds__(64) void debug_colours_kernel(VsfObserveDebugArgs a) {
+  __shared__ uint32_t s_win[32];
+  const int f0 = blockIdx.x, n = a.n_frames, K = a.max_rows, lane = (int)threadIdx.x;
+  const VsfObserveParam p0 = a.params[f0];
+  if (p0.prev >= 0) return;
+  uint32_t* st = a.rand_state + (size_t)p0.stream * 32;
+  {
+    const int rear = min(max((int)st[31], 0), vsfrand::kWords - 1);
+    if (lane < vsfrand::kWords) s_win[vsfrand::normalised_index(lane, rear)] = st[lane];
+  }
+  __syncthreads();
+  uint32_t r[vsfrand::kWords];
+#pragma unroll
+  for (int i = 0; i < vsfrand::kWords; i++) r[i] = s_win[i];
+  __syncthreads();
+  for (int g0 = f0 & ~63; g0 < n; g0 += 64) {
+    // the stream's frames among frames [g0, g0 + 64), as bits; walked lowest first: submission order
+    const int g = g0 + lane;
+    unsigned long long mine = __ballot(g >= f0 && g < n && a.params[min(g, n - 1)].stream == p0.stream);
+    while (mine) {
+      const int f = g0 + __ffsll((long long)mine) - 1;
+      mine &= mine - 1;
+      const int ns = min(max(a.npairs[f], 0), K);
+      uint32_t* out = a.stream_colours + (size_t)f * K;
+      for (int base = 0; base < ns; base += vsfrand::kWords) {
+        const int m = min(ns - base, vsfrand::kWords);
+        uint32_t keep = 0;
+        vsfrand::colours31(r, m, [&](int j, uint32_t c) { keep = lane == j ? c : keep; });
+        if (lane < m) out[base + lane] = keep;
+      }
+      const int rear = (int)((3 * (int64_t)ns) % vsfrand::kWords);
+      if (rear != 0) {  // (uniform) the window back to rear pointer 0
+        if (lane == 0) {
+#pragma unroll
+          for (int i = 0; i < vsfrand::kWords; i++) s_win[vsfrand::normalised_index(i, rear)] = r[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < vsfrand::kWords; i++) r[i] = s_win[i];
+        __syncthreads();
+      }
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < vsfrand::kWords; i++) st[i] = r[i];
+    st[31] = 0;
+  }
+}
+
 // ---- the ObserveImage queue's debug images (vsf_observe_set_debug_images): one block per frame of a batch ----
 // Stereo canvas 2f: cc:84-96 for every right -> left pair (pair f: initial = right row, current = left row), colours from
 // the host's ring at the frame's offset (the colour cursor + the stereo pairs of the frames before it in the batch); absent
@@ -231,7 +289,8 @@ __global__ __launch_bounds__(256) void debug_ops_kernel(VsfObserveDebugArgs a) {
   const int f = blockIdx.x, K = a.max_rows, w = a.width, h = a.height, tid = (int)threadIdx.x;
   const VsfObserveFrame fm = a.frames[f];
   const int ns = min(max(a.npairs[f], 0), K);
-  if (tid == 0) {
+  const bool per_stream = a.rand_state != nullptr;  // (vsf_observe_set_debug_seeds: the frame's colours are in stream_colours)
+  if (tid == 0 && !per_stream) {
     int64_t c = *a.colour_cursor;
     for (int g = 0; g < f; g++) c += min(max(a.npairs[g], 0), K);
     s_col = c;
@@ -244,7 +303,8 @@ __global__ __launch_bounds__(256) void debug_ops_kernel(VsfObserveDebugArgs a) {
   const uint64_t* sp = a.pairs + (size_t)f * K * 2;
   for (int i = tid; i < ns; i += 256) {
     const uint64_t ri = sp[2 * i], li = sp[2 * i + 1];
-    const uint32_t col = a.colours[(s_col + i) % a.colour_ring];  // (taken whether or not the rows are valid: cc:95)
+    // (taken whether or not the rows are valid: cc:95)
+    const uint32_t col = per_stream ? a.stream_colours[(size_t)f * K + i] : a.colours[(s_col + i) % a.colour_ring];
     vsf_draw_op* o = ops + 3 * i;
     if (ri >= (uint64_t)nr || li >= (uint64_t)nl) {
       o[0].kind = o[1].kind = o[2].kind = -1;  // (draws nothing)
@@ -260,8 +320,10 @@ __global__ __launch_bounds__(256) void debug_ops_kernel(VsfObserveDebugArgs a) {
   if (fm.n_past > 0) {
     const int p = fm.tp0 + fm.n_past - 1;
     nm = min(max(a.npairs[p], 0), K);
-    const vsf_keypoint* kp = f > 0 ? a.kp_f + (size_t)(2 * (f - 1)) * K : a.prev_kp;
-    const int np = f > 0 ? min(max(a.counts_f[2 * (f - 1)], 0), K) : min(max(*a.prev_n, 0), K);
+    // the newest kept frame: the frame of ITS stream in front of it in this batch, else what the stream kept from the last
+    const int pf = a.params ? a.params[f].prev : f - 1, ps = a.params ? a.params[f].stream : 0;
+    const vsf_keypoint* kp = pf >= 0 ? a.kp_f + (size_t)(2 * pf) * K : a.prev_kp + (size_t)ps * K;
+    const int np = min(max(pf >= 0 ? a.counts_f[2 * pf] : a.prev_n[ps], 0), K);
     const uint64_t* tp = a.pairs + (size_t)p * K * 2;
     for (int i = tid; i < nm; i += 256) {
       const uint64_t pi = tp[2 * i], ci = tp[2 * i + 1];
@@ -300,13 +362,23 @@ __global__ __launch_bounds__(256) void debug_ops_kernel(VsfObserveDebugArgs a) {
 }
 
 // after the batch: its newest frame's keypoints for the next batch's first match image; the colour cursor moves on
+// (with a generator per stream: block f, where frame f is the first of its stream in the batch, keeps the stream's LAST frame
+// of the batch -- params[f].tail -- in the stream's entry; a stream that is not in the batch keeps what it has)
 __global__ __launch_bounds__(256) void debug_finish_kernel(VsfObserveDebugArgs a) {
-  const int K = a.max_rows, last = a.n_frames - 1, tid = (int)threadIdx.x;
+  const int K = a.max_rows, tid = (int)threadIdx.x;
+  int last = a.n_frames - 1, stream = 0;
+  if (a.params) {
+    const VsfObserveParam p = a.params[blockIdx.x];
+    if (p.prev >= 0) return;
+    last = p.tail;
+    stream = p.stream;
+  }
   const int n = min(max(a.counts_f[2 * last], 0), K);
   const vsf_keypoint* src = a.kp_f + (size_t)(2 * last) * K;
-  for (int i = tid; i < n; i += 256) a.prev_kp[i] = src[i];
-  if (tid == 0) {
-    *a.prev_n = n;
+  vsf_keypoint* dst = a.prev_kp + (size_t)stream * K;
+  for (int i = tid; i < n; i += 256) dst[i] = src[i];
+  if (tid == 0) a.prev_n[stream] = n;
+  if (tid == 0 && !a.rand_state) {
     int64_t c = *a.colour_cursor;
     for (int g = 0; g < a.n_frames; g++) c += min(max(a.npairs[g], 0), K);
     *a.colour_cursor = c;
@@ -316,12 +388,13 @@ __global__ __launch_bounds__(256) void debug_finish_kernel(VsfObserveDebugArgs a
 }  // namespace
 
 void vsf_launch_observe_debug(const VsfObserveDebugArgs& a, hipStream_t s) {
+  if (a.rand_state) hipLaunchKernelGGL(debug_colours_kernel, dim3((unsigned)a.n_frames), dim3(64), 0, s, a);
   hipLaunchKernelGGL(debug_ops_kernel, dim3((unsigned)a.n_frames), dim3(256), 0, s, a);
   const DrawCanvasDev* dc = static_cast<const DrawCanvasDev*>(a.canvases);
   hipLaunchKernelGGL(draw_raster_kernel, dim3(32, (unsigned)(2 * a.n_frames)), dim3(256), 0, s, dc, a.ops);
   hipLaunchKernelGGL(draw_resolve_kernel, dim3((unsigned)((2 * a.width * a.height + 255) / 256), (unsigned)(2 * a.n_frames)),
                      dim3(256), 0, s, dc);
-  hipLaunchKernelGGL(debug_finish_kernel, dim3(1), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(debug_finish_kernel, dim3(a.params ? (unsigned)a.n_frames : 1u), dim3(256), 0, s, a);
 }
 
 extern "C" {

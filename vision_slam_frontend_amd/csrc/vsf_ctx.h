@@ -138,6 +138,7 @@ struct vsf_ctx {
     int stream = 0;              // vsf_observe_submit_stream: whose sequence it belongs to
     int64_t k = 0;               // frames of its stream in front of it (since the queue was built or the stream reset)
     vsf_pose pose{};             // vsf_observe_set_pose: what its stream's pose was when it was submitted (read with `cloud`)
+    float cam_to_robot[12] = {0};  // ... and its stream's left_cam_to_robot (vsf_observe_set_stream_cam_to_robot, or the context's)
   };
   struct ObserveStream {  // host side of one sequence of frames (vsf_observe_set_streams)
     int64_t frames = 0;        // submitted since the queue was built or the stream was reset: the next frame's k
@@ -172,8 +173,14 @@ struct vsf_ctx {
     vsfi::DevBuf<uint64_t> dbg_win;
     vsfi::DevBuf<vsf_draw_op> dbg_ops;
     vsfi::DevBuf<void> dbg_table;
-    vsfi::DevBuf<vsf_keypoint> dbg_prev_kp;
-    vsfi::DevBuf<int64_t> dbg_ints;
+    vsfi::DevBuf<vsf_keypoint> dbg_prev_kp;  // [n_streams][K]
+    vsfi::DevBuf<int64_t> dbg_ints;          // {colour cursor}, then i32 [n_streams]: the kept frames' counts
+    // vsf_observe_set_debug_seeds: built with ob_seeded -- each stream's generator (vsf_glibc_random.h) in device memory, the
+    // colours a batch's frames took from them; the pinned colour ring h_col does not exist then and rand() is never called
+    bool seeded = false;
+    std::vector<uint32_t> seeds;               // [n_streams] what the states were seeded with
+    vsfi::DevBuf<uint32_t> dbg_rand;           // [n_streams] vsfrand::State
+    vsfi::DevBuf<uint32_t> dbg_stream_colours; // [bmax][K]
     size_t dbg_stride = 0;
     vsfi::PinnedBuf<uint8_t> h_dbg;
     vsfi::PinnedBuf<uint32_t> h_col;
@@ -244,6 +251,12 @@ struct vsf_ctx {
   bool ob_cloud = false;   // vsf_observe_set_world_points: the queue makes the point cloud ...
   float ob_cam_to_robot[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};  // ... with this left_cam_to_robot (3 x 4 row-major)
   vsf_pose ob_pose[VSF_OBSERVE_MAX_STREAMS];  // vsf_observe_set_pose: each stream's sticky pose (identity: vsf_create)
+  // vsf_observe_set_debug_seeds: every stream draws its stereo lines' colours from a generator of its own (srand(seed), rand(), ...)
+  bool ob_seeded = false;
+  uint32_t ob_seeds[VSF_OBSERVE_MAX_STREAMS] = {0};
+  // vsf_observe_set_stream_cam_to_robot: a stream's own left_cam_to_robot in place of ob_cam_to_robot
+  bool ob_stream_c2r_set[VSF_OBSERVE_MAX_STREAMS] = {false};
+  float ob_stream_c2r[VSF_OBSERVE_MAX_STREAMS][12] = {{0}};
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----

@@ -320,6 +320,10 @@ void vsf_launch_observe_pack(const VsfObserveArgs& a, int max_pairs_per_frame, h
 // pairs, drawn into device canvases [n][stereo 2w x h x 3 | match w x h x 3]; then the newest frame's keypoints are kept for
 // the next batch and the colour cursor advances.  Header words 14 / 15 of each result: images present (bit 0 stereo, bit 1
 // match), colours used.
+// With a generator per stream (vsf_observe_set_debug_seeds: `rand_state` set) a kernel of its own runs first -- one wave per
+// stream present in the batch draws the colours of that stream's frames, in their order, from the stream's state in device
+// memory --, the stereo lines take them from `stream_colours`, and everything that crosses frames exists per stream: a frame's
+// newest kept frame is `params[f].prev` or prev_kp[its stream], and every stream present leaves its last frame there.
 struct VsfObserveDebugArgs {
   int n_frames, max_rows, width, height;
   const uint8_t* images;          // the batch's uploaded images: frame f left at 2f * image_stride, right one stride on
@@ -329,8 +333,8 @@ struct VsfObserveDebugArgs {
   const uint64_t* pairs;          // [pairs][max_rows][2]
   const int32_t* npairs;
   const VsfObserveFrame* frames;  // [n]
-  vsf_keypoint* prev_kp;          // [max_rows] the newest kept frame of earlier batches
-  int32_t* prev_n;
+  vsf_keypoint* prev_kp;          // [streams][max_rows] each stream's newest kept frame of earlier batches
+  int32_t* prev_n;                // [streams]
   const uint32_t* colours;        // pinned ring of packed b | g << 8 | r << 16, drawn from rand() by the host
   int64_t colour_ring;
   int64_t* colour_cursor;         // colours used by every frame launched before this batch
@@ -341,6 +345,9 @@ struct VsfObserveDebugArgs {
   uint64_t* winners;              // [n][3 w h], zero between batches
   uint8_t* out;                   // result ring: header words 14 / 15
   size_t out_stride;
+  const VsfObserveParam* params;  // [n] with a generator per stream (stream, prev, tail); nullptr: ONE stream, frame f - 1
+  uint32_t* rand_state;           // [streams] vsfrand::State (vsf_glibc_random.h), carried from batch to batch; nullptr: `colours`
+  uint32_t* stream_colours;       // [n][max_rows] packed colours the colour kernel writes and the operations read
 };
 void vsf_launch_observe_debug(const VsfObserveDebugArgs& a, hipStream_t s);
 

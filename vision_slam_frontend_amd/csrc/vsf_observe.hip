@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "vsf_ctx.h"
+#include "vsf_glibc_random.h"
 
 using namespace vsfi;
 
@@ -143,11 +144,23 @@ vsf_status alloc_debug_files(vsf_ctx* ctx) {
   return VSF_OK;
 }
 
+// vsf_observe_set_debug_seeds: streams [s0, s0 + n) start over -- srand(seed) -- in device memory.  (No kernel reads them: the
+// queue is being built, or every frame of the stream has been collected.)
+vsf_status upload_debug_generators(vsf_ctx* ctx, int s0, int n) {
+  vsf_ctx::Observe& o = ctx->ob;
+  std::vector<vsfrand::State> st((size_t)n);
+  for (int s = 0; s < n; s++) vsfrand::seed(st[(size_t)s], o.seeds[(size_t)(s0 + s)]);
+  VSF_HIP(hipMemcpy(o.dbg_rand + (size_t)s0 * 32, st.data(), (size_t)n * sizeof(vsfrand::State), hipMemcpyHostToDevice));
+  return VSF_OK;
+}
+
 vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   vsf_ctx::Observe& o = ctx->ob;
   const vsf_ctx::DebugForm form = ctx->ob_debug ? ctx->ob_debug_form : vsf_ctx::DebugForm();
+  const bool seeded = ctx->ob_debug && ctx->ob_seeded;  // (seeds without debug images: a queue as it always was)
   if (o.ready && o.frame_life == frame_life && o.debug == ctx->ob_debug && o.files.form == form && o.cloud == ctx->ob_cloud &&
-      (!o.cloud || std::memcmp(o.cam_to_robot, ctx->ob_cam_to_robot, sizeof(o.cam_to_robot)) == 0))
+      (!o.cloud || std::memcmp(o.cam_to_robot, ctx->ob_cam_to_robot, sizeof(o.cam_to_robot)) == 0) && o.seeded == seeded &&
+      (!seeded || std::equal(o.seeds.begin(), o.seeds.end(), ctx->ob_seeds)))
     return VSF_OK;
   sync_all_streams(ctx);
   const int NS = ctx->ob_streams;
@@ -202,16 +215,25 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
     VSF_HIP(hipMemset(o.dbg_win, 0, B * 3 * wh * sizeof(uint64_t)));
     VSF_HIP(o.dbg_ops.alloc(B * 5 * K * sizeof(vsf_draw_op)));
     VSF_HIP(o.dbg_table.alloc(2 * B * 128));
-    VSF_HIP(o.dbg_prev_kp.alloc(K * sizeof(vsf_keypoint)));
-    VSF_HIP(o.dbg_ints.alloc(16));
-    VSF_HIP(hipMemset(o.dbg_ints, 0, 16));
+    VSF_HIP(o.dbg_prev_kp.alloc((size_t)NS * K * sizeof(vsf_keypoint)));
+    VSF_HIP(o.dbg_ints.alloc(8 + (((size_t)NS * sizeof(int32_t) + 7) & ~(size_t)7)));
+    VSF_HIP(hipMemset(o.dbg_ints, 0, 8 + (((size_t)NS * sizeof(int32_t) + 7) & ~(size_t)7)));
     if (form.kind) {
       const vsf_status st = alloc_debug_files(ctx);
       if (st != VSF_OK) return st;
     } else {
       VSF_HIP(o.h_dbg.alloc((size_t)o.depth * o.dbg_stride, hipHostMallocMapped));
     }
-    VSF_HIP(o.h_col.alloc((size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
+    o.seeded = seeded;
+    if (seeded) {  // a generator per stream on the device: no colour ring, no rand()
+      o.seeds.assign(ctx->ob_seeds, ctx->ob_seeds + NS);
+      VSF_HIP(o.dbg_rand.alloc((size_t)NS * sizeof(vsfrand::State)));
+      VSF_HIP(o.dbg_stream_colours.alloc(B * K * sizeof(uint32_t)));
+      const vsf_status st = upload_debug_generators(ctx, 0, NS);
+      if (st != VSF_OK) return st;
+    } else {
+      VSF_HIP(o.h_col.alloc((size_t)o.col_ring * sizeof(uint32_t), hipHostMallocMapped));
+    }
   }
   o.cloud = ctx->ob_cloud;
   if (o.cloud) {  // vsf_observe_set_world_points: the pinned ring of points and its counts, written by the tail's kernel
@@ -380,13 +402,17 @@ vsf_status launch_debug_images(vsf_ctx* ctx, const vsf_ctx::ObserveBatch& b, con
   vsf_ctx::Observe::DebugFiles& fl = o.files;
   // per canvas size (stereo, match): one copy command, or the encoder's launches + the kernel that carries the files home
   const int per_size = fl.form.kind ? vsf_encode_launches(fl.form.kind) + 1 : 1;
-  StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 4 + 2 * per_size);  // (4: the drawing kernels)
+  StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 4 + (o.seeded ? 1 : 0) + 2 * per_size);  // (4: the drawing kernels; the colours')
   // (in the order of the struct's fields; o.ints: the filtered frames' counts, o.dbg_ints: the colour cursor, then the kept frame's count)
   const VsfObserveDebugArgs d{n, ctx->p.max_keypoints, ctx->p.width, ctx->p.height, b.d_img, ctx->st_img_stride, ctx->st_img_pitch,
                               o.kpf, o.ints, o.pairs, o.npairs, M.frames, o.dbg_prev_kp, reinterpret_cast<int32_t*>(o.dbg_ints + 1),
                               o.h_col, o.col_ring, o.dbg_ints, o.dbg_ops, o.dbg_table, o.dbg_canvas, o.dbg_stride, o.dbg_win,
-                              o.h_out, o.out_stride};
+                              o.h_out, o.out_stride, o.seeded ? M.params : nullptr, o.dbg_rand, o.dbg_stream_colours};
   vsf_launch_observe_debug(d, s_tail);
+  if (o.seeded) {
+    o.queue->stats.seeded_frames += n;
+    o.queue->stats.colour_commands++;
+  }
   const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
   if (fl.form.kind) {
     // cv::imencode(".jpg") / (".png") of the canvases just drawn, stereo then match (two sizes: two encodes), into the batch's
@@ -491,7 +517,7 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
     M.out_sets[2 * f] = pf.left_set;
     M.out_sets[2 * f + 1] = pf.right_set;
     M.frames[f] = {pf.left_set, pf.n_past, pf.tp0, (int32_t)((t0 + f) % o.depth)};
-    if (table || chains) M.params[f] = {pf.stream, pf.calib, pf.best_percent, pf.prev, pf.tail};
+    if (table || chains || o.seeded) M.params[f] = {pf.stream, pf.calib, pf.best_percent, pf.prev, pf.tail};
   }
   std::memcpy(M.q_set, P.q_set.data(), (size_t)n_pairs * sizeof(int32_t));
   std::memcpy(M.t_set, P.t_set.data(), (size_t)n_pairs * sizeof(int32_t));
@@ -499,8 +525,8 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   if (table) std::memcpy(M.calibs, P.calibs.data(), P.calibs.size() * sizeof(vsf_calibration));
   if (o.cloud)  // M_f = (Translation(loc) * quat) * cam_to_robot of every frame, from the pose it was submitted with
     for (int f = 0; f < n; f++) {
-      const vsf_pose& pose = o.frames[(size_t)((t0 + f) % o.depth)].pose;
-      M.transforms[f] = vsfwp::camera_to_world(pose.loc, pose.quat_xyzw, o.cam_to_robot);
+      const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
+      M.transforms[f] = vsfwp::camera_to_world(fr.pose.loc, fr.pose.quat_xyzw, fr.cam_to_robot);
     }
   b.h_meta->n_frames = n;
   b.h_meta->n_pairs = n_pairs;
@@ -648,7 +674,8 @@ vsf_status drop_queue(vsf_ctx* ctx) {
 // vsf_observe_set_debug_jpeg / _png: quality != 0 asks for files of `kind`, 0 takes that request back.
 vsf_status set_debug_form(vsf_ctx* ctx, int kind, int quality) {
   vsf_ctx::DebugForm& f = ctx->ob_debug_form;
-  if (quality != 0 && ctx->ob_streams > 1) return VSF_ERR_UNSUPPORTED;  // debug images are single-stream (include/vsf.h)
+  // (debug images of several streams need a generator per stream: vsf_observe_set_debug_seeds)
+  if (quality != 0 && ctx->ob_streams > 1 && !ctx->ob_seeded) return VSF_ERR_UNSUPPORTED;
   if (quality == (f.kind == kind ? f.quality : 0)) return VSF_OK;
   if (quality != 0 && !ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // files of images nobody draws
   if (quality != 0 && f.kind != VSF_FILE_NONE && f.kind != kind) return VSF_ERR_INVALID_ARG;  // one form of file at a time
@@ -708,8 +735,8 @@ size_t vsf_observe_capacity(const vsf_ctx* ctx, int frame_life) {
 vsf_status vsf_observe_set_debug_images(vsf_ctx* ctx, int on) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx) return VSF_ERR_INVALID_ARG;
-  // single-stream: the match image needs each stream's previous frame and rand()'s colour sequence per stream
-  if (on != 0 && ctx->ob_streams > 1) return VSF_ERR_UNSUPPORTED;
+  // several streams: rand()'s colour sequence must exist per stream (vsf_observe_set_debug_seeds); without it, refused
+  if (on != 0 && ctx->ob_streams > 1 && !ctx->ob_seeded) return VSF_ERR_UNSUPPORTED;
   if ((on != 0) == ctx->ob_debug) return VSF_OK;
   const vsf_status st = retire_unused_queue(ctx);
   if (st == VSF_OK) ctx->ob_debug = on != 0;
@@ -815,13 +842,37 @@ vsf_status vsf_observe_configure(vsf_ctx* ctx, int depth, int min_batch, int in_
 vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams) {
   VsfErrorScope scope_(ctx);  // (sends what waits; the launcher thread is idle afterwards)
   if (!ctx || n_streams < 1 || n_streams > VSF_OBSERVE_MAX_STREAMS) return VSF_ERR_INVALID_ARG;
-  if (n_streams > 1 && ctx->ob_debug) return VSF_ERR_UNSUPPORTED;  // (vsf_observe_set_debug_images: single-stream)
+  // (the seeds are one per stream: another count needs vsf_observe_set_debug_seeds first, with debug images off)
+  if (ctx->ob_seeded && n_streams != ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  if (n_streams > 1 && ctx->ob_debug && !ctx->ob_seeded) return VSF_ERR_UNSUPPORTED;  // (one stream without seeds)
   if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
   if (ctx->ob.ready && n_streams != ctx->ob_streams) {  // rebuilt by the next submit: every window and threshold starts over
     const vsf_status st = drop_queue(ctx);
     if (st != VSF_OK) return st;
   }
+  if (n_streams != ctx->ob_streams)  // (vsf_observe_set_stream_cam_to_robot: the streams are other cameras now)
+    for (bool& set : ctx->ob_stream_c2r_set) set = false;
   ctx->ob_streams = n_streams;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_set_debug_seeds(vsf_ctx* ctx, const uint32_t* seeds, int n) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || n < 0 || (n > 0 && !seeds) || (n == 0 && seeds)) return VSF_ERR_INVALID_ARG;
+  if (n != 0 && n != ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  if (ctx->ob_debug) return VSF_ERR_INVALID_ARG;  // the order of use: streams, seeds, switch
+  // (before the queue's first frame or after vsf_observe_reset; a queue built without debug images holds nothing of this)
+  if (ctx->ob.ready && ctx->ob.queue->next_ticket != 0) return VSF_ERR_INVALID_ARG;
+  ctx->ob_seeded = n != 0;
+  for (int s = 0; s < n; s++) ctx->ob_seeds[s] = seeds[s];
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_set_stream_cam_to_robot(vsf_ctx* ctx, int stream, const float* m) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  ctx->ob_stream_c2r_set[stream] = m != nullptr;
+  if (m) std::memcpy(ctx->ob_stream_c2r[stream], m, sizeof(ctx->ob_stream_c2r[stream]));
   return VSF_OK;
 }
 
@@ -839,6 +890,11 @@ vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream) {
   // has no predecessor, and the sets fill in the same order as a fresh queue's.
   const float thr = 10000.0f;  // cc:353
   VSF_HIP(hipMemcpy(o.floats + 2 * o.bmax + 1 + stream, &thr, sizeof(float), hipMemcpyHostToDevice));
+  if (o.debug && o.seeded) {  // its kept frame goes, its generator is seeded again
+    VSF_HIP(hipMemset(reinterpret_cast<int32_t*>(o.dbg_ints + 1) + stream, 0, sizeof(int32_t)));
+    const vsf_status sr = upload_debug_generators(ctx, stream, 1);
+    if (sr != VSF_OK) return sr;
+  }
   st.frames = 0;
   st.last_ticket = -1;
   return VSF_OK;
@@ -856,7 +912,7 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[24] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+  const int64_t v[26] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
                          s.file_commands, (int64_t)ctx->ob_streams, s.multi,
@@ -864,8 +920,8 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
                          (int64_t)(o.d_ring ? vsf_observe_device_ring_bytes(ctx, o.depth) : 0),
                          s.cloud_frames, s.cloud_commands,
                          (int64_t)(o.h_wp ? (size_t)o.depth * ((size_t)ctx->p.max_keypoints * 3 * sizeof(double) + sizeof(int32_t)) : 0),
-                         s.reduced};
-  for (int i = 0; i < n && i < 24; i++) out[i] = v[i];
+                         s.reduced, s.seeded_frames, s.colour_commands};
+  for (int i = 0; i < n && i < 26; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -874,6 +930,15 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx) {
   if (!ctx) return VSF_ERR_INVALID_ARG;
   for (vsf_pose& p : ctx->ob_pose) p = identity_pose();
   return drop_queue(ctx);
+}
+
+// What a frame takes from its stream when it is submitted, for the point cloud: the sticky pose (vsf_observe_set_pose) and, with
+// the cloud on, the stream's own left_cam_to_robot (vsf_observe_set_stream_cam_to_robot) or the one the queue was built with.
+static void capture_placement(const vsf_ctx* ctx, int stream, vsf_ctx::ObserveFrame& fr) {
+  fr.pose = ctx->ob_pose[stream];
+  if (ctx->ob.cloud)
+    std::memcpy(fr.cam_to_robot, ctx->ob_stream_c2r_set[stream] ? ctx->ob_stream_c2r[stream] : ctx->ob.cam_to_robot,
+                sizeof(fr.cam_to_robot));
 }
 
 // Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
@@ -917,7 +982,7 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   }
   // ---- the two images into the frame's slot of the pinned staging ring, rows at the device pitch (the slot's previous
   // frame has been collected: its upload is long done) ----
-  if (o.debug) {
+  if (o.debug && !o.seeded) {
     // the stereo lines' colours, cv::Scalar(rand() % 255, rand() % 255, rand() % 255) (cc:95) in the reference's order --
     // GCC evaluates the three calls right to left: the first is channel 2 -- drawn ahead: enough for every frame in the queue
     // (a frame takes at most max_keypoints); the device takes them in frame order from its cursor
@@ -957,7 +1022,7 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   fr.reduce = (uint8_t)reduce;
   fr.calib = *calib;
   fr.best_percent = best_percent;
-  fr.pose = ctx->ob_pose[stream];
+  capture_placement(ctx, stream, fr);
   fr.batch = -1;
   vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
   fr.stream = stream;
@@ -1093,7 +1158,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
   }
   st = ensure_device_ring(ctx, bayer);
   if (st != VSF_OK) return st;
-  if (o.debug) {  // the stereo lines' colours, drawn ahead for every frame of the call (observe_submit)
+  if (o.debug && !o.seeded) {  // the stereo lines' colours, drawn ahead for every frame of the call (observe_submit)
     const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + n - q.next_collect) * K;
     for (; o.col_generated < want; o.col_generated++) {
       const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
@@ -1128,7 +1193,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     fr.dev_stream = producer;
     fr.calib = *calib;
     fr.best_percent = best_percent;
-    fr.pose = ctx->ob_pose[stream];
+    capture_placement(ctx, stream, fr);
     fr.batch = -1;
     vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
     fr.stream = stream;
@@ -1175,7 +1240,7 @@ static vsf_status observe_wait(vsf_ctx* ctx, int64_t ticket, const uint8_t** vie
   const uint32_t* hdr = reinterpret_cast<const uint32_t*>(res);
   const bool whole = hdr[0] == 0x4F465356u;
   o.streams[(size_t)o.frames[(size_t)slot].stream].uncollected--;
-  if (o.debug) o.col_retired += hdr[15];  // the colours this frame's stereo image took
+  if (o.debug && !o.seeded) o.col_retired += hdr[15];  // the colours this frame's stereo image took
   st = o.queue->collected(ticket, whole ? (int)hdr[2] : -1);  // (hdr[2]: the filtered frame's rows)
   if (!whole) return VSF_ERR_HIP;
   const_cast<uint32_t*>(hdr)[0] = 0;  // (the slot's next frame must write its own)

@@ -72,6 +72,12 @@ def lib() -> C.CDLL:
         L.vsfh_set_debug_jpeg_quality.restype = None
         L.vsfh_set_debug_png.argtypes = [vp, i32]
         L.vsfh_set_debug_png.restype = None
+        L.vsfh_set_debug_colour_seed.argtypes = [vp, i32, C.c_uint32]
+        L.vsfh_set_debug_colour_seed.restype = None
+        L.vsfh_set_left_cam_to_robot.argtypes = [vp, vp]
+        L.vsfh_set_left_cam_to_robot.restype = None
+        L.vsfh_group_create_ex.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32]
+        L.vsfh_group_create_ex.restype = vp
         L.vsfh_set_imdecode_reduce.argtypes = [vp, i32]
         L.vsfh_set_imdecode_reduce.restype = None
         L.vsfh_set_compressed_cap.argtypes = [vp, sz]
@@ -157,17 +163,21 @@ class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False, imdecode_reduce: int = 1,
-                 compressed_cap: int = 0):
+                 compressed_cap: int = 0, debug_colour_seed=None, cam_to_robot=None):
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
         self.size, self.device = (width, height), device
+        if debug_colour_seed is not None:  # FrontendConfig::debug_colour_seeded_ / _seed_: the object's own rand(), before the switch
+            lib().vsfh_set_debug_colour_seed(self._h, 1, int(debug_colour_seed))
         if debug_images:  # FrontendConfig::debug_images_ (the reference's default is on, slam_frontend.cc:552)
             lib().vsfh_set_debug_images(self._h, 1)
         if debug_jpeg_quality:  # FrontendConfig::debug_jpeg_quality_: the queued modes keep JPEG files instead of raw images
             lib().vsfh_set_debug_jpeg_quality(self._h, debug_jpeg_quality)
         if debug_png:  # FrontendConfig::debug_png_: ... or PNG files, lossless (not together with the JPEG form)
             lib().vsfh_set_debug_png(self._h, 1)
+        if cam_to_robot is not None:  # FrontendConfig::left_cam_to_robot, 3 x 4 row-major
+            lib().vsfh_set_left_cam_to_robot(self._h, _p(np.ascontiguousarray(cam_to_robot, np.float32).reshape(12)))
         if visualization:  # FrontendConfig::visualization_: the point cloud and pose graph of Frontend::GetVisualization
             lib().vsfh_set_visualization(self._h, 1)
         if imdecode_reduce != 1:  # FrontendConfig::imdecode_reduce_: IMREAD_REDUCED_GRAYSCALE_N; width x height is the reduced size
@@ -459,14 +469,21 @@ class Frontend:
 class FrontendGroup:
     """slam::FrontendGroup: several Frontend objects on ONE GPU context and ONE ObserveImage queue (member i is stream i of
     vsf_observe_set_streams).  `fundamentals` and `best_percents` (optional) are per member; `members[i]` is member i as a
-    Frontend (owned by the group)."""
+    Frontend (owned by the group).  Debug images (`debug_images`, `debug_jpeg_quality`, `debug_png`: every member's) need
+    `debug_colour_seeds`, one per member, in a group of more than one; `cam_to_robots` (n x 3 x 4) gives every member its own
+    FrontendConfig::left_cam_to_robot, `visualization` switches every member's on."""
 
     def __init__(self, width: int, height: int, fundamentals, nfeatures: int = 10000, device: int = 0, best_percents=None,
-                 frame_life: int = 0, imdecode_reduces=None, compressed_cap: int = 0):
+                 frame_life: int = 0, imdecode_reduces=None, compressed_cap: int = 0, debug_images: bool = False,
+                 debug_jpeg_quality: int = 0, debug_png: bool = False, debug_colour_seeds=None, cam_to_robots=None,
+                 visualization: bool = False):
         F = np.ascontiguousarray(fundamentals, np.float32).reshape(-1, 9)
         n = len(F)
         bp = None if best_percents is None else np.ascontiguousarray(best_percents, np.float32).reshape(n)
-        self._h = lib().vsfh_group_create(n, nfeatures, width, height, device, _p(F), _p(bp), frame_life)
+        seeds = None if debug_colour_seeds is None else np.ascontiguousarray(debug_colour_seeds, np.uint32).reshape(n)
+        c2r = None if cam_to_robots is None else np.ascontiguousarray(cam_to_robots, np.float32).reshape(n, 12)
+        self._h = lib().vsfh_group_create_ex(n, nfeatures, width, height, device, _p(F), _p(bp), frame_life, int(debug_images),
+                                             int(debug_jpeg_quality), int(debug_png), _p(seeds), _p(c2r), int(visualization))
         st = lib().vsfh_group_last_status(self._h)
         if st != capi.VSF_OK:
             self.close()

@@ -168,6 +168,10 @@ int vsfh_debug_image(void* f, int stereo, int i, uint8_t* out, size_t cap, int r
 
 void vsfh_set_debug_jpeg_quality(void* f, int quality) { static_cast<Frontend*>(f)->set_debug_jpeg_quality(quality); }
 void vsfh_set_debug_png(void* f, int on) { static_cast<Frontend*>(f)->set_debug_png(on != 0); }
+// FrontendConfig::debug_colour_seeded_ / debug_colour_seed_: the stereo lines' colours from a generator the object owns
+void vsfh_set_debug_colour_seed(void* f, int seeded, uint32_t seed) {
+  static_cast<Frontend*>(f)->set_debug_colour_seed(seeded != 0, seed);
+}
 // FrontendConfig::imdecode_reduce_ (a group's member: the pointer vsfh_group_member returns)
 void vsfh_set_imdecode_reduce(void* f, int reduce) { static_cast<Frontend*>(f)->set_imdecode_reduce(reduce); }
 // FrontendConfig::compressed_cap_ (a group's member: the group's)
@@ -191,6 +195,7 @@ void vsfh_set_projections(void* f, const float left12[12], const float right12[1
   static_cast<Frontend*>(f)->set_projections(left12, right12);
 }
 void vsfh_set_visualization(void* f, int on) { static_cast<Frontend*>(f)->set_visualization(on != 0); }
+void vsfh_set_left_cam_to_robot(void* f, const float m12[12]) { static_cast<Frontend*>(f)->set_left_cam_to_robot(m12); }
 void vsfh_group_set_visualization(void* g, int on) {
   slam::FrontendGroup* gr = static_cast<slam::FrontendGroup*>(g);
   for (int i = 0; i < gr->size(); i++) gr->member(i).set_visualization(on != 0);
@@ -299,8 +304,13 @@ void vsfh_frontend_destroy(void* f) { delete static_cast<Frontend*>(f); }
 // slam::FrontendGroup: n members on one context.  Member i takes fundamental9[9 i ..] and best_percent[i] (<= 0: the
 // default); the rest as vsfh_frontend_create.  vsfh_group_member hands out
 // member i as a Frontend every vsfh_* call above takes (the group owns it: never vsfh_frontend_destroy).
-void* vsfh_group_create(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
-                        const float* best_percent, int frame_life) {
+// A group of n members: per member a fundamental matrix and (optional, > 0) a best_percent; then what a group must be BUILT
+// with: the debug images' switch and form (0 / 0 / 0: none), a colour seed per member (NULL: the process's rand() -- refused with
+// more than one member and debug images), a left_cam_to_robot per member (n x 12 floats, 3 x 4 row-major; NULL: the
+// reference's) and visualization_.
+void* vsfh_group_create_ex(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
+                           const float* best_percent, int frame_life, int debug_images, int debug_jpeg_quality, int debug_png,
+                           const uint32_t* colour_seeds, const float* cam_to_robots, int visualization) {
   std::vector<FrontendConfig> cfgs((size_t)(n > 0 ? n : 0));
   for (int i = 0; i < n; i++) {
     FrontendConfig& cfg = cfgs[(size_t)i];
@@ -310,8 +320,20 @@ void* vsfh_group_create(int n, int nfeatures, int width, int height, int device,
     if (fundamental9) std::memcpy(cfg.fundamental.m, fundamental9 + 9 * i, 9 * sizeof(float));
     if (best_percent && best_percent[i] > 0) cfg.best_percent_ = best_percent[i];
     if (frame_life > 0) cfg.frame_life_ = (uint32_t)frame_life;
+    cfg.debug_images_ = debug_images != 0;
+    cfg.debug_jpeg_quality_ = debug_jpeg_quality;
+    cfg.debug_png_ = debug_png != 0;
+    cfg.debug_colour_seeded_ = colour_seeds != nullptr;
+    if (colour_seeds) cfg.debug_colour_seed_ = colour_seeds[i];
+    cfg.visualization_ = visualization != 0;
+    if (cam_to_robots) cfg.left_cam_to_robot = slam::AffineFromRowMajor(cam_to_robots + 12 * i);
   }
   return new slam::FrontendGroup(cfgs, device);
+}
+// (the call as it was before the group took debug images and extrinsics)
+void* vsfh_group_create(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
+                        const float* best_percent, int frame_life) {
+  return vsfh_group_create_ex(n, nfeatures, width, height, device, fundamental9, best_percent, frame_life, 0, 0, 0, nullptr, nullptr, 0);
 }
 void vsfh_group_destroy(void* g) { delete static_cast<slam::FrontendGroup*>(g); }
 int vsfh_group_size(void* g) { return static_cast<slam::FrontendGroup*>(g)->size(); }

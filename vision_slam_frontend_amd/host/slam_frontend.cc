@@ -124,6 +124,8 @@ FrontendConfig::FrontendConfig() {
   debug_images_ = false;
   debug_jpeg_quality_ = 0;
   debug_png_ = false;
+  debug_colour_seeded_ = false;
+  debug_colour_seed_ = 1;
   visualization_ = false;
   imdecode_reduce_ = 1;  // IMREAD_GRAYSCALE, the reference's flag
   compressed_cap_ = 0;   // the library's default: the context's width x height + 64 KB
@@ -207,6 +209,13 @@ void CamToRobot(const FrontendConfig& config, float out[12]) {
   }
 }
 
+Affine3f AffineFromRowMajor(const float m[12]) {
+  Matrix3f R;
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) R(r, c) = m[4 * r + c];
+  return Affine3f(R, Vector3f(m[3], m[7], m[11]));
+}
+
 vsf_calibration MakeCalibration(const FrontendConfig& config) {
   vsf_calibration c;
   std::memset(&c, 0, sizeof(c));
@@ -254,6 +263,7 @@ Frontend::Frontend(const FrontendConfig& config, int device, FrontendGroup* grou
       owns_ctx_(stream == 0),
       device_(device),
       last_status_(VSF_OK) {
+  vsfrand::seed(colour_rng_, config_.debug_colour_seed_);
   if (config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::ORB &&
       config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::FREAK)
     last_status_ = VSF_ERR_UNSUPPORTED;  // the reference would build AKAZE / BRISK / SURF / SIFT here (cc:193-232)
@@ -300,22 +310,46 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
   if (last_status_ == VSF_OK) last_status_ = vsf_observe_configure(ctx_, ctx_depth_, min_batch_, 0);
   if (last_status_ == VSF_OK && n_streams > 1) last_status_ = vsf_observe_set_streams(ctx_, n_streams);
   if (last_status_ == VSF_OK && config_.compressed_cap_ > 0) last_status_ = vsf_observe_set_compressed_cap(ctx_, config_.compressed_cap_);
-  // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
-  if (last_status_ == VSF_OK && config_.debug_images_) last_status_ = vsf_observe_set_debug_images(ctx_, 1);
-  // ... and leave as files when the configuration asks for one form of them (both: the second request is refused)
-  const int form = debug_file_form();
-  if (last_status_ == VSF_OK && config_.debug_images_ && (form & kFormJpeg))
-    last_status_ = vsf_observe_set_debug_jpeg(ctx_, config_.debug_jpeg_quality_);
-  if (last_status_ == VSF_OK && config_.debug_images_ && (form & kFormPng)) last_status_ = vsf_observe_set_debug_png(ctx_, 1);
+  if (last_status_ == VSF_OK) last_status_ = ApplyDebugConfig(n_streams);
   // the point cloud of GetVisualization: one more launch in every batch's tail (vsf_observe_set_world_points)
   if (last_status_ == VSF_OK && config_.visualization_) {
     float cam_to_robot[12];
     CamToRobot(config_, cam_to_robot);
     last_status_ = vsf_observe_set_world_points(ctx_, 1, cam_to_robot);
   }
+  // ... placed with each camera's own left_cam_to_robot: a group's members are streams of this one queue
+  for (int i = 0; group_ && last_status_ == VSF_OK && i < n_streams; i++) {
+    float cam_to_robot[12];
+    CamToRobot(group_->members_[(size_t)i]->config_, cam_to_robot);
+    last_status_ = vsf_observe_set_stream_cam_to_robot(ctx_, i, cam_to_robot);
+  }
   pending_.assign((size_t)ctx_depth_, PendingFrame());
   pending_head_ = pending_count_ = 0;
   return last_status_ == VSF_OK;
+}
+
+vsf_status Frontend::ApplyDebugConfig(int n_streams) {
+  // (the seeds go in while the switch is off; the forms of file need it on: off in reverse order first -- all three are
+  // accepted without effect where nothing was on)
+  vsf_status st = vsf_observe_set_debug_png(ctx_, 0);
+  if (st == VSF_OK) st = vsf_observe_set_debug_jpeg(ctx_, 0);
+  if (st == VSF_OK) st = vsf_observe_set_debug_images(ctx_, 0);
+  if (st == VSF_OK) {
+    std::vector<uint32_t> seeds;
+    if (config_.debug_colour_seeded_)
+      for (int i = 0; i < n_streams; i++) seeds.push_back(group_ ? group_->members_[(size_t)i]->config_.debug_colour_seed_ : config_.debug_colour_seed_);
+    st = vsf_observe_set_debug_seeds(ctx_, seeds.empty() ? nullptr : seeds.data(), (int)seeds.size());
+    // (the queue's generators start at their seeds here: so does the object's own, which per-call mode draws from -- the modes
+    // agree across a replaced context too)
+    vsfrand::seed(colour_rng_, config_.debug_colour_seed_);
+  }
+  // the queue's results carry the right frame's filtered keypoints too (the stereo debug image draws them)
+  if (st == VSF_OK && config_.debug_images_) st = vsf_observe_set_debug_images(ctx_, 1);
+  // ... and leave as files when the configuration asks for one form of them (both: the second request is refused)
+  const int form = debug_file_form();
+  if (st == VSF_OK && config_.debug_images_ && (form & kFormJpeg)) st = vsf_observe_set_debug_jpeg(ctx_, config_.debug_jpeg_quality_);
+  if (st == VSF_OK && config_.debug_images_ && (form & kFormPng)) st = vsf_observe_set_debug_png(ctx_, 1);
+  return st;
 }
 
 // cc:250-263.  The reference copies the still-uninitialised odom_*_ into prev_odom_*_ on the first call (quirk
@@ -751,7 +785,19 @@ void Frontend::set_visualization(bool on) {
     float cam_to_robot[12];
     CamToRobot(config_, cam_to_robot);
     last_status_ = vsf_observe_set_world_points(ctx_, on ? 1 : 0, cam_to_robot);
+    // (a group's member: the switch is the queue's, the matrix its stream's own)
+    if (group_ && last_status_ == VSF_OK) last_status_ = vsf_observe_set_stream_cam_to_robot(ctx_, stream_, cam_to_robot);
   }
+}
+
+void Frontend::set_left_cam_to_robot(const float m[12]) {
+  if (!nodes_.empty() || pending_count_ > 0) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  config_.left_cam_to_robot = AffineFromRowMajor(m);
+  if (ctx_ && group_) last_status_ = vsf_observe_set_stream_cam_to_robot(ctx_, stream_, m);
+  if (ctx_ && !group_ && config_.visualization_) last_status_ = vsf_observe_set_world_points(ctx_, 1, m);
 }
 
 bool Frontend::Flush() {
@@ -1052,6 +1098,17 @@ void Frontend::set_debug_images(bool on) {
   if (ctx_) last_status_ = vsf_observe_set_debug_images(ctx_, on ? 1 : 0);
 }
 
+void Frontend::set_debug_colour_seed(bool seeded, uint32_t seed) {
+  if (!nodes_.empty() || pending_count_ > 0 || group_) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return;
+  }
+  config_.debug_colour_seeded_ = seeded;
+  config_.debug_colour_seed_ = seed;
+  vsfrand::seed(colour_rng_, seed);
+  if (ctx_) last_status_ = ApplyDebugConfig(1);
+}
+
 void Frontend::set_debug_jpeg_quality(int quality) {
   if (!nodes_.empty() || pending_count_ > 0 || quality < 0 || quality > 100 || (quality > 0 && (debug_file_form() & kFormPng))) {
     last_status_ = VSF_ERR_INVALID_ARG;
@@ -1134,7 +1191,8 @@ int CvRound(float v) { return (int)std::lrint(v); }  // cvRound: round half to e
 // own rand() stream, called in the reference's order.  The order in which those three calls run is unspecified in C++; GCC
 // evaluates the arguments of that constructor call right to left, so the FIRST draw is channel 2 (the byte the driver
 // labels R), the third is channel 0.  This choice follows the reference's usual build and is not pinned by a test against
-// it.
+// it.  With config_.debug_colour_seeded_ the three draws come from the object's own generator instead -- the same statement of
+// glibc's rand() the queue's colour kernel runs (csrc/vsf_glibc_random.h).
 void Frontend::DrawDebugImages(const uint8_t* left, const uint8_t* right, int w, int h, size_t pitch,
                                const Frame& curr_frame, const std::vector<vsf_keypoint>& right_keypoints,
                                const std::vector<FeatureMatch>* stereo, const Frame* past_frame,
@@ -1156,9 +1214,14 @@ void Frontend::DrawDebugImages(const uint8_t* left, const uint8_t* right, int w,
     vsf_draw_canvas c = {left, right, w, h, (int64_t)pitch, nullptr, (int64_t)6 * w, (int32_t)ops.size(), 0};
     for (const FeatureMatch& m : *stereo) {
       uint8_t bgr[3];  // (drawn for every pair, as cc:95 does: the colours keep the reference's sequence)
-      bgr[2] = (uint8_t)(rand() % 255);
-      bgr[1] = (uint8_t)(rand() % 255);
-      bgr[0] = (uint8_t)(rand() % 255);
+      if (config_.debug_colour_seeded_) {
+        const uint32_t c = vsfrand::next_colour(colour_rng_);
+        bgr[0] = (uint8_t)c, bgr[1] = (uint8_t)(c >> 8), bgr[2] = (uint8_t)(c >> 16);
+      } else {
+        bgr[2] = (uint8_t)(rand() % 255);
+        bgr[1] = (uint8_t)(rand() % 255);
+        bgr[0] = (uint8_t)(rand() % 255);
+      }
       if (m.feature_idx_current >= lk.size() || m.feature_idx_initial >= right_keypoints.size()) continue;
       const vsf_keypoint& l = lk[m.feature_idx_current];
       const vsf_keypoint& r = right_keypoints[m.feature_idx_initial];
@@ -1209,16 +1272,18 @@ FrontendGroup::FrontendGroup(const std::vector<FrontendConfig>& configs, int dev
     return;
   }
   const FrontendConfig& lead = configs[0];
-  for (const FrontendConfig& c : configs)  // debug images are single-stream: refused here, not by the context some calls later
-    if (configs.size() > 1 && (c.debug_images_ || c.debug_jpeg_quality_ != 0 || c.debug_png_)) {
+  // debug images of several streams need a colour generator per stream: refused here, not by the context some calls later
+  for (const FrontendConfig& c : configs)
+    if (configs.size() > 1 && (c.debug_images_ || c.debug_jpeg_quality_ != 0 || c.debug_png_) && !c.debug_colour_seeded_) {
       last_status_ = VSF_ERR_UNSUPPORTED;
       return;
     }
   for (const FrontendConfig& c : configs)  // what the one context is built with
     if (c.orb_nfeatures != lead.orb_nfeatures || c.nn_match_ratio_ != lead.nn_match_ratio_ ||
         c.residual_order != lead.residual_order || c.frame_life_ != lead.frame_life_ || c.image_width != lead.image_width ||
-        c.image_height != lead.image_height || c.visualization_ != lead.visualization_ ||
-        (c.visualization_ && std::memcmp(&c.left_cam_to_robot, &lead.left_cam_to_robot, sizeof(Affine3f)) != 0)) {
+        c.image_height != lead.image_height || c.visualization_ != lead.visualization_ || c.debug_images_ != lead.debug_images_ ||
+        c.debug_jpeg_quality_ != lead.debug_jpeg_quality_ || c.debug_png_ != lead.debug_png_ ||
+        c.debug_colour_seeded_ != lead.debug_colour_seeded_) {
       last_status_ = VSF_ERR_INVALID_ARG;
       return;
     }

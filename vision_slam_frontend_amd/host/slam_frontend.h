@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/vsf.h"
+#include "../csrc/vsf_glibc_random.h"  // glibc's rand(), shared with the queue's colour kernel
 #include "slam_types.h"
 #include "slam_visualization.h"
 
@@ -83,6 +84,14 @@ struct FrontendConfig {
   // vsf_observe_set_debug_png).  Off by default; ignored in per-call mode; not together with debug_jpeg_quality_ (the second of
   // the two to be asked for is refused with VSF_ERR_INVALID_ARG).
   bool debug_png_;
+  // An addition: where the stereo lines' colours (cc:95) come from.  false (the default): the process's rand(), as in the
+  // reference.  true: a generator the OBJECT owns -- srand(debug_colour_seed_), rand(), rand(), ... as glibc computes them
+  // (csrc/vsf_glibc_random.h) -- on the device in the queued modes (vsf_observe_set_debug_seeds), on the host in per-call mode;
+  // the process's rand() is then never called.  Seed 1 is what a fresh process draws.  A context that is replaced in the
+  // middle of a sequence (another image size, pipelining switched on) starts the sequence over, in every mode.  What a FrontendGroup's members need
+  // to have debug images at all: one sequence shared by several cameras would not be any camera's own.
+  bool debug_colour_seeded_;
+  uint32_t debug_colour_seed_;
   // An addition: the object also builds what the reference's driver publishes to RViz after every pose (PublishVisualization,
   // slam_frontend_main.cc:194-225) -- the point cloud on the GPU, inside the queue's batches, the pose graph while nodes and
   // factors are booked -- for Frontend::GetVisualization.  Off by default: nothing is launched, copied or kept for it.
@@ -126,8 +135,9 @@ struct FrontendConfig {
 
 // FrontendConfig's stereo calibration in the layout of the C ABI (include/vsf.h vsf_calibration).
 vsf_calibration MakeCalibration(const FrontendConfig& config);
-// config.left_cam_to_robot as the 3 x 4 row-major matrix the point cloud's calls take.
+// config.left_cam_to_robot as the 3 x 4 row-major matrix the point cloud's calls take, and such a matrix as the transform.
 void CamToRobot(const FrontendConfig& config, float out[12]);
+Affine3f AffineFromRowMajor(const float m[12]);
 
 using slam_visualization::Visualization;
 // The driver's AddFeaturePoints with its own signature (slam_frontend_main.cc:155-157): the CPU restatement of the cloud.
@@ -202,6 +212,8 @@ class Frontend {
   // what is new (its markers must not have been edited in between); any other object is filled from scratch.
   bool GetVisualization(Visualization* out);
   void set_visualization(bool on);  // config.visualization_, under the rule of set_debug_images
+  // config.left_cam_to_robot as a 3 x 4 row-major matrix, under the same rule (a group's member: its stream's own)
+  void set_left_cam_to_robot(const float m[12]);
   // config.projection_left / projection_right (3 x 4 row-major) after construction, under the same rule: a stereo rig other than
   // the reference's hard-coded one (cc:595-611) -- what Calculate3DPoints triangulates with.
   void set_projections(const float left[12], const float right[12]);
@@ -247,6 +259,9 @@ class Frontend {
   void set_debug_images(bool on);
   void set_debug_jpeg_quality(int quality);  // config.debug_jpeg_quality_, under the same rule
   void set_debug_png(bool on);               // config.debug_png_, under the same rule
+  // config.debug_colour_seeded_ / debug_colour_seed_, under the same rule; the generator starts over.  (A group's member: the
+  // seeds are the queue's and go in when the group is built -- VSF_ERR_INVALID_ARG.)
+  void set_debug_colour_seed(bool seeded, uint32_t seed);
   // config.imdecode_reduce_ (1, 2, 4, 8; anything else: VSF_ERR_INVALID_ARG and no change).  Legal at any time: it is read by
   // each ObserveCompressedImage; the image size stays what the first frame made it.
   void set_imdecode_reduce(int reduce);
@@ -306,6 +321,9 @@ class Frontend {
                          slam_types::VisionFactor* matches_out = nullptr);
   bool EnsureContext(int width, int height);  // (a group member: the group's)
   bool EnsureOwnContext(int width, int height, int n_streams);
+  // What the configuration asks of the queue's debug images, in the order the context takes it: everything off, the seeds
+  // (one per stream: a group's lead hands in every member's), the switch, the form of file.
+  vsf_status ApplyDebugConfig(int n_streams);
   // The form the queue's debug images leave in, as config_.debug_jpeg_quality_ / debug_png_ ask for it: raw images, or the bit of
   // the one form of file (both bits only in a configuration the context refuses).  The ONE place that reads the pair.
   enum { kFormRaw = 0, kFormJpeg = 1, kFormPng = 2 };
@@ -368,6 +386,7 @@ class Frontend {
   // The reference keeps this in a file-static shared by all instances (cc:353, quirk Q3); here it is per object.
   float stereo_ambig_constraint_;
   std::vector<OwnedImage> debug_images_, debug_stereo_images_;  // cc h:202-203: kept for the object's lifetime
+  vsfrand::State colour_rng_;  // per-call mode with config_.debug_colour_seeded_: the object's own rand()
   std::vector<std::vector<uint8_t>> debug_files_, debug_stereo_files_;  // ... or their JPEG / PNG files (debug_jpeg_quality_ / debug_png_)
   // visualization_: the pose graph as points (one per node; two per factor) and the cloud (three doubles per point)
   std::vector<slam_visualization::Point> viz_nodes_, viz_odometry_, viz_vision_;
@@ -396,11 +415,15 @@ class Frontend {
 // nodes, factors and bytes are those of a Frontend of its own fed the same calls (tests/test_gpu_frontend_group.py).
 //   The members' configurations may differ in everything a frame brings to the queue -- the calibration (intrinsics,
 // projections, fundamental), best_percent_, the odometry gates -- and must agree in what the context is built with:
-// orb_nfeatures, nn_match_ratio_, residual_order, frame_life_, visualization_ (with it, left_cam_to_robot: the queue places
-// every stream's points with ONE camera-to-robot transform) and the image size (else last_status() of the group reads
-// VSF_ERR_INVALID_ARG and nothing is observed).  Members observe in fused mode (a member's set_fused does nothing).  Debug
-// images are not available in a group of more than one member: a configuration that asks for them (debug_images_,
-// debug_jpeg_quality_, debug_png_) is refused by the constructor with VSF_ERR_UNSUPPORTED.
+// orb_nfeatures, nn_match_ratio_, residual_order, frame_life_, visualization_, the image size and -- the queue draws for every
+// stream or for none, in one form -- debug_images_, debug_jpeg_quality_, debug_png_ (else last_status() of the group reads
+// VSF_ERR_INVALID_ARG and nothing is observed).  left_cam_to_robot is per member: the group hands each member's matrix to its
+// stream (vsf_observe_set_stream_cam_to_robot), so two cameras on one robot keep two clouds.  Members observe in fused mode
+// (a member's set_fused does nothing).
+//   Debug images in a group of more than one member need debug_colour_seeded_ on EVERY member (each stream then draws its
+// colours from a generator of its own, vsf_observe_set_debug_seeds); a configuration that asks for debug images without it is
+// refused by the constructor with VSF_ERR_UNSUPPORTED.  With it every member's getDebugImages / getDebugStereoImages /
+// GetLast... / ...Compressed are those of a Frontend of its own (tests/test_gpu_frontend_group_debug.py).
 //   The queue is the group's: set_pipelined / set_queue / set_queue_thread below set every member alike, and the same
 // setters called on one member (set_pipelined, set_queue_depth, set_batch_frames, set_min_batch, set_queue_thread) are
 // handed to the group, so the members never disagree.  Context options and the copy thread are read from member(0).
