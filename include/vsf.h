@@ -525,7 +525,7 @@ vsf_status vsf_observe_submit_compressed_stream(vsf_ctx* ctx, int stream, const 
  * rule of vsf_observe_submit_compressed_stream holds, with the size rule applied per file: a file of W x H is taken when
  * ceil(W / reduce) x ceil(H / reduce) (vsf_reduced_size) is the context's size -- VSF_ERR_INVALID_ARG otherwise, and for a
  * reduce outside {1, 2, 4, 8}; a PNG file with reduce > 1 is VSF_ERR_UNSUPPORTED (cv::imdecode would decode it whole and call
- * cv::resize, which is not built here).  A file the host refuses issues no ticket and leaves the queue as it was; a file the
+ * cv::resize: that is a declared input size, vsf_observe_set_input_size, not this call).  A file the host refuses issues no ticket and leaves the queue as it was; a file the
  * device refuses fails its own ticket through status word 13, as for full-size files.  The byte cap
  * (vsf_observe_set_compressed_cap) applies to the file as it is: files of a larger camera usually need a larger cap than the
  * default of the context's size.
@@ -550,6 +550,40 @@ vsf_status vsf_observe_stereo_compressed_reduced(vsf_ctx* ctx, const uint8_t* le
  * Legal while no frame of that stream is submitted and not collected (else VSF_ERR_INVALID_ARG); the other streams, frames
  * in flight included, are untouched.  vsf_observe_reset stays "all streams" (and drops what waits). */
 vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream);
+/* A DECLARED INPUT SIZE per stream: the frames of `stream` arrive at width x height -- any size in 1 .. 32767 a side, larger or
+ * smaller than the context's, each axis by its own ratio -- and the queue brings them to the context's size with
+ * cv::resize(img, Size(ctx width, ctx height)) (INTER_LINEAR, vsf_resize_gray_batch_dev's kernel) on its copy stream, where
+ * decode and demosaic already run beside the previous batch's extraction.  From there on such a frame is a frame like any
+ * other: each result is, byte for byte, that of vsf_observe_submit on the resized images.  (0, 0): the context's size again.
+ *   Legal while no frame of that stream is submitted and not collected (else VSF_ERR_INVALID_ARG, the rule of
+ * vsf_observe_reset_stream); VSF_ERR_INVALID_ARG too for a stream outside [0, n_streams) or a side outside 1 .. 32767.  The
+ * size is kept across vsf_observe_reset and vsf_observe_reset_stream and dropped when vsf_observe_set_streams changes the
+ * number of streams.  A stream that was never told a size behaves exactly as without this call: same bytes, same launches.
+ *   What each submit takes on such a stream:
+ *     vsf_observe_submit_stream (vsf_observe_submit / vsf_observe_stereo for stream 0): w, h must be the declared size.
+ *     vsf_observe_submit_dev: the images have the declared size, at any base address and pitch >= its width.
+ *     vsf_observe_submit_compressed_stream: the FILE's own size must be the declared size; it is decoded whole (`bayer`:
+ *       demosaiced at that size), then resized -- cv::resize(DecodeImage(msg)).  For a PNG topic that is what
+ *       cv::imdecode(IMREAD_REDUCED_GRAYSCALE_N) does: declare the file's W x H on a context of (W / N) x (H / N), floor
+ *       division.  The byte cap stays sized by the context: raise it with vsf_observe_set_compressed_cap.
+ *     vsf_observe_submit_compressed_reduced: VSF_ERR_INVALID_ARG for reduce > 1 -- a reduced JPEG decode combined with a
+ *       declared size is not built.
+ *   A frame of another size than its stream's declared one is VSF_ERR_INVALID_ARG: no ticket, nothing booked or launched, the
+ * queue as it was.  A Bayer frame wider than 16384 is VSF_ERR_UNSUPPORTED (the demosaic's limit).
+ *   BATCHING: frames of streams with different declared sizes, and of streams with none, SHARE a batch; a batch issues one
+ * resize launch per run of consecutive frames of one size.  Results do not depend on it.
+ *   THE CALIBRATION IS THE CALLER'S, FOR THE RESIZED IMAGE: the library scales nothing.  Debug images are drawn from the
+ * resized images.
+ *   WHAT IT COSTS, built by the first frame that needs it and sized by the LARGEST declared size: an image's place is its
+ * height x (width rounded up to 64) bytes rounded up to 256, a slot two of them.  Raw host frames wait in a pinned ring of
+ * `depth` slots (629 MB at depth 256 and 1280 x 960 -- choose the depth accordingly) and are uploaded into one of four
+ * device buffers of bmax slots, which compressed frames are decoded into as well; device frames wait in a device ring of
+ * `depth` slots and are resized out of it without a copy.  Declaring a LARGER size later makes the next submit send what
+ * waits, wait for the device and rebuild these buffers.
+ *   vsf_observe_stats values [26] frames resized, [27] kernel launches and copy commands this path issued, [28] bytes of
+ * every buffer it owns -- all 0 for a queue that never saw a declared size -- and [29] batches whose frames came in at more
+ * than one size. */
+vsf_status vsf_observe_set_input_size(vsf_ctx* ctx, int stream, int width, int height);
 /* Frames that ALREADY LIVE IN DEVICE MEMORY -- a tensor of the caller's framework, the output of vsf_imdecode_gray_batch /
  * vsf_bayer_bg_to_gray_batch_dev on the caller's own stream, a camera SDK's or video decoder's buffer, the caller's own
  * preprocessing kernel -- enter the queue without crossing to the host: what vsf_set_input_event is to the batched calls.
@@ -797,7 +831,8 @@ vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, co
  * (tests/jpeg_ref_reduced.py).  reduce = 1 IS vsf_imdecode_gray_batch; a reduce other than 1, 2, 4, 8 returns
  * VSF_ERR_INVALID_ARG and launches nothing (libjpeg's other N / 8 scales are not what imdecode asks for).
  * A PNG file with reduce > 1 returns VSF_ERR_UNSUPPORTED: cv::imdecode decodes a PNG at full size and then calls cv::resize,
- * which is not built here.  Destination and asynchronous contract as for vsf_jpeg_decode_gray_batch. */
+ * which is another call: vsf_png_decode_gray_batch, then vsf_resize_gray_batch_dev to (W / reduce) x (H / reduce), floor
+ * division.  Destination and asynchronous contract as for vsf_jpeg_decode_gray_batch. */
 vsf_status vsf_imdecode_reduced_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images,
                                            int reduce, int width, int height, uint8_t* d_dst, size_t dst_image_stride,
                                            size_t dst_row_stride);
@@ -816,6 +851,32 @@ vsf_status vsf_reduced_size(int w, int h, int reduce, int* rw, int* rh);
 vsf_status vsf_bayer_bg_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height,
                                           size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst,
                                           size_t dst_image_stride, size_t dst_row_stride);
+
+/* cv::resize(src, dst, Size(dst_width, dst_height)) of OpenCV 3.2 with its default interpolation (INTER_LINEAR) on CV_8UC1,
+ * for n images resident in HBM, device to device, in ONE launch (k_resize.hip).  Independent of the context's own image
+ * size.  Bit for bit cv::resize's integers: the coefficients of csrc/vsf_resize.h (the pyramid's), HResizeLinear's and
+ * VResizeLinear's fixed-point passes; cv::resize's switch to INTER_AREA at an exact 2 x reduction in both axes is
+ * (a + b + c + d + 2) >> 2, which those integers give as well.
+ *   Any ratio per axis, independently: reduction, enlargement, or 1 (a copy).  Both sizes lie in 1 .. 32767 a side.  Image i
+ * at base + i * image_stride, rows row_stride bytes apart: ANY source base address, ANY pitch >= the width on either side
+ * (no alignment rule).  Bytes of a destination row beyond dst_width are not written.  A destination row that begins on a
+ * 4-byte boundary is written in dwords; one that does not (an odd pitch, or an odd base) is written byte by byte, four stores
+ * per lane where there was one: correct, and slower in stores -- give rows a pitch and base that are multiples of 4 where the
+ * rate matters (the queue's own destination is).  The source is read only in aligned
+ * 4-byte words that hold at least one pixel of the image: a row may end on the last byte of its allocation.
+ *   VSF_ERR_INVALID_ARG: a null pointer, n_images < 1, a size outside 1 .. 32767, a pitch below its width, with more than one
+ * image an image stride below (height - 1) * pitch + width; nothing is launched then.  Asynchronous on the context's stream like every *_dev call.
+ * Not built: other interpolations, colour or 16-bit images. */
+vsf_status vsf_resize_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int src_width, int src_height,
+                                     size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst, int dst_width,
+                                     int dst_height, size_t dst_image_stride, size_t dst_row_stride);
+
+/* The same for host pointers, synchronous: the images go up, are resized by the same kernel and come back (what a caller
+ * without a queue -- slam::Frontend's per-call mode with FrontendConfig::resize_width_ -- uses).  Same sizes, strides and
+ * refusals; the image strides are not looked at for n_images == 1. */
+vsf_status vsf_resize_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int src_width, int src_height, size_t src_image_stride,
+                           size_t src_row_stride, uint8_t* dst, int dst_width, int dst_height, size_t dst_image_stride,
+                           size_t dst_row_stride);
 
 /* The way OUT of the device for pixels: cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) as OpenCV 3.2 drives libjpeg
  * (the reference's own instance: src/test/bag_extract.cc:90) for n equally sized images resident in HBM -- baseline, the

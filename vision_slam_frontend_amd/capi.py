@@ -51,6 +51,7 @@ EXPORTS = [
     "vsf_imdecode_reduced_gray_batch", "vsf_reduced_size", "vsf_observe_probe_compressed_reduced",
     "vsf_observe_submit_compressed_reduced", "vsf_observe_stereo_compressed_reduced",
     "vsf_observe_set_debug_seeds", "vsf_observe_set_stream_cam_to_robot",
+    "vsf_resize_gray_batch_dev", "vsf_observe_set_input_size", "vsf_resize_gray",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -62,7 +63,8 @@ OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits
                  "wait_ns", "compressed", "ingest_commands", "compressed_bytes", "debug_jpeg_commands", "streams",
                  "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes",
                  "world_points_frames", "world_points_commands", "world_points_ring_bytes", "reduced_frames",
-                 "seeded_colour_frames", "colour_commands")
+                 "seeded_colour_frames", "colour_commands", "resized_frames", "resize_commands", "resize_bytes",
+                 "multi_size_batches")
 # vsf_observe_submit_dev's pixel formats (include/vsf.h)
 PIX_MONO8, PIX_BAYER_RGGB8 = 0, 1
 
@@ -290,6 +292,9 @@ def lib() -> C.CDLL:
         L.vsf_observe_reset.argtypes = [vp]
         L.vsf_observe_set_streams.argtypes = [vp, i32]
         L.vsf_observe_reset_stream.argtypes = [vp, i32]
+        L.vsf_observe_set_input_size.argtypes = [vp, i32, i32, i32]
+        L.vsf_resize_gray_batch_dev.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, i32, i32, sz, sz]
+        L.vsf_resize_gray.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, i32, i32, sz, sz]
         L.vsf_observe_submit_stream.argtypes = [vp, i32, vp, vp, i32, i32, sz, C.POINTER(VsfCalibration), C.c_float, i32,
                                                 C.POINTER(C.c_int64)]
         L.vsf_observe_submit_compressed_stream.argtypes = [vp, i32, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float,
@@ -382,6 +387,8 @@ class Context:
         self.params = VsfParams()
         lib().vsf_get_params(self._h, C.byref(self.params))
         self.device = device
+        self._input_sizes = {}  # observe_set_input_size: what observe_submit_dev checks its tensors against
+        self._n_streams = 1
 
     def close(self):
         if getattr(self, "_h", None):
@@ -693,11 +700,24 @@ class Context:
         st = lib().vsf_observe_set_streams(self._h, n_streams)
         if st != VSF_OK and st not in allow_status:
             raise VsfError(st, "vsf_observe_set_streams", lib().vsf_last_hip_error(self._h))
+        if st == VSF_OK and n_streams != self._n_streams:  # (another count drops the declared input sizes)
+            self._input_sizes = {}
+            self._n_streams = n_streams
         return st
 
     def observe_reset_stream(self, stream: int):
         """Forgets one stream's window and threshold (vsf_observe_reset_stream)."""
         self._check(lib().vsf_observe_reset_stream(self._h, stream), "vsf_observe_reset_stream")
+
+    def observe_set_input_size(self, stream: int, width: int, height: int, allow_status=()) -> int:
+        """The size the frames of `stream` arrive at (vsf_observe_set_input_size): the queue brings them to the context's size
+        with cv::resize on the device.  (0, 0): the context's size again.  Returns the status."""
+        st = lib().vsf_observe_set_input_size(self._h, stream, width, height)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_set_input_size", lib().vsf_last_hip_error(self._h))
+        if st == VSF_OK:
+            self._input_sizes[stream] = (width, height) if width or height else None
+        return st
 
     def observe_submit_stream(self, stream: int, left: np.ndarray, right: np.ndarray, calib: VsfCalibration,
                               best_percent: float = 0.3, frame_life: int = 10, allow_status=()):
@@ -735,10 +755,11 @@ class Context:
         ValueError otherwise, before the library is called), or four integers (left address, left pitch, right address,
         right pitch).  Returns the tickets -- or, with `allow_status`, (status, tickets): a refused call's are all -1."""
         p = self.params
+        w, h = self._input_sizes.get(stream) or (p.width, p.height)  # (observe_set_input_size)
         arr = (VsfDevFrame * max(len(frames), 1))()
         for i, f in enumerate(frames):
             if len(f) == 2:
-                (lp, ls), (rp, rs) = (device_image(t, p.width, p.height, self.device) for t in f)
+                (lp, ls), (rp, rs) = (device_image(t, w, h, self.device) for t in f)
             else:
                 lp, ls, rp, rs = (int(v) for v in f)
             arr[i] = VsfDevFrame(lp, rp, ls, rs)
@@ -960,6 +981,27 @@ class Context:
     def png_encode(self, images, out_stride: int | None = None):
         """cv::imencode(".png", img) of equally sized (h, w) gray or (h, w, 3) BGR uint8 images -> list of bytes."""
         return self._encode("png", (), images, out_stride)
+
+    def resize_gray_batch_dev(self, d_src: int, n_images: int, src_width: int, src_height: int, src_image_stride: int,
+                              src_row_stride: int, d_dst: int, dst_width: int, dst_height: int, dst_image_stride: int,
+                              dst_row_stride: int, allow_status=()) -> int:
+        """cv::resize (INTER_LINEAR, CV_8UC1) of images resident in HBM (vsf_resize_gray_batch_dev): any sizes in 1 .. 32767,
+        any base address, any pitch >= the width.  Asynchronous on the context's stream.  Returns the status."""
+        st = lib().vsf_resize_gray_batch_dev(self._h, _p(d_src), n_images, src_width, src_height, src_image_stride,
+                                             src_row_stride, _p(d_dst), dst_width, dst_height, dst_image_stride, dst_row_stride)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_resize_gray_batch_dev", lib().vsf_last_hip_error(self._h))
+        return st
+
+    def resize_gray(self, images, dst_width: int, dst_height: int) -> np.ndarray:
+        """cv::resize (INTER_LINEAR, CV_8UC1) of equally sized (h, w) uint8 images in host memory (vsf_resize_gray): an
+        (n, dst_height, dst_width) array."""
+        imgs = np.ascontiguousarray(np.stack([np.asarray(i) for i in images]), dtype=np.uint8)
+        n, h, w = imgs.shape
+        out = np.zeros((n, dst_height, dst_width), np.uint8)
+        self._check(lib().vsf_resize_gray(self._h, _p(imgs), n, w, h, w * h, w, _p(out), dst_width, dst_height,
+                                          dst_width * dst_height, dst_width), "vsf_resize_gray")
+        return out
 
     def bayer_bg_to_gray_batch_dev(self, d_src: int, n_images: int, width: int, height: int, src_image_stride: int,
                                    src_row_stride: int, d_dst: int, dst_image_stride: int, dst_row_stride: int):

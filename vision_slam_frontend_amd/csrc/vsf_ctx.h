@@ -120,6 +120,11 @@ struct vsf_ctx {
     // compressed frames: the batch's ONE upload (every run's headers / tables / entropy-coded or IDAT bytes); free once the
     // slot's previous batch has left the GPU (ev_done)
     VsfStaging blob;
+    // frames of a declared input size (vsf_observe_set_input_size): [bmax] big slots -- the raw host frames' upload and the
+    // compressed frames' decoded images, at the index the frame has in the batch -- and the upload of THEIR files (a staging
+    // pair of its own, with its event: a batch that holds compressed frames of several sizes decodes them size by size)
+    vsfi::DevBuf<uint8_t> d_in;
+    VsfStaging blob_in;
     vsfi::Event ev_uploaded, ev_extracted, ev_done;
     bool used = false;               // ev_done has been recorded at least once
     hipStream_t done_stream = nullptr;  // the stream its tail ran on (a view)
@@ -132,6 +137,7 @@ struct vsf_ctx {
                                  // kObserveKindDevice (both): the images are in the slot of the device ring d_ring
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
     bool bayer = false;          // compressed and device frames: the (decoded) images are bayer_rggb8 mosaics
+    int in_w = 0, in_h = 0;      // the size it was handed in at (vsf_observe_set_input_size), 0 x 0: the context's
     uint8_t reduce = 1;          // compressed frames: both files decode at 1 / reduce (vsf_observe_submit_compressed_reduced)
     int dev_event = -1;          // device frames: the slot whose event in dev_ev follows the copy into the ring ...
     hipStream_t dev_stream = nullptr;  // ... and the producer's stream it was recorded on (a view)
@@ -232,6 +238,18 @@ struct vsf_ctx {
     vsfi::DevBuf<uint8_t> d_ring;            // [depth][2] images at the staging pitch
     vsfi::PinnedBuf<VsfIngestSrc> h_dev_src;  // pinned [depth][2]: where a long call's images are (read by its launch)
     std::vector<vsfi::Event> dev_ev;         // [depth]
+    // vsf_observe_set_input_size; nothing of this exists before the first frame of a declared size.  Rings of big slots
+    // (vsf_observe_plan.h: 2 * in_half bytes, an image every in_half) beside the rings above: pinned for raw host frames, in
+    // HBM for device frames; the mosaics of a Bayer batch's resized frames, [bmax] big slots.
+    size_t in_half = 0;                       // what the buffers that exist were built for
+    vsfi::PinnedBuf<uint8_t> h_in;            // pinned [depth] big slots
+    vsfi::DevBuf<uint8_t> d_in_ring;          // [depth] big slots
+    vsfi::DevBuf<uint8_t> d_bayer_in;         // [bmax] big slots
+    std::vector<vsfi::ObserveResizeIn> resize_in;  // launch_batch's: the batch as observe_resize_plan takes it ...
+    vsfi::ObserveResizePlan resize_plan;           // ... and plans it
+    std::vector<const uint8_t*> rs_files;          // ingest_resized's: the batch's files, their sizes and kinds per decode
+    std::vector<size_t> rs_sizes;
+    std::vector<uint8_t> rs_kinds;
     std::vector<uint8_t> run_kinds;          // launch_batch's: the batch's kinds as observe_batch_runs takes them ...
     std::vector<vsfi::ObserveRun> runs;      // ... and splits them
     int64_t stat_dev_commands = 0;           // the caller's share of vsf_observe_stats value 18 (the submits' launches)
@@ -257,6 +275,9 @@ struct vsf_ctx {
   // vsf_observe_set_stream_cam_to_robot: a stream's own left_cam_to_robot in place of ob_cam_to_robot
   bool ob_stream_c2r_set[VSF_OBSERVE_MAX_STREAMS] = {false};
   float ob_stream_c2r[VSF_OBSERVE_MAX_STREAMS][12] = {{0}};
+  // vsf_observe_set_input_size: the size a stream's frames arrive at (0 x 0: the context's), brought to the context's by
+  // k_resize.hip inside the batch.  Kept across resets, dropped when vsf_observe_set_streams changes the count.
+  int ob_in_w[VSF_OBSERVE_MAX_STREAMS] = {0}, ob_in_h[VSF_OBSERVE_MAX_STREAMS] = {0};
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----

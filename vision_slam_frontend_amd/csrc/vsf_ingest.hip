@@ -208,6 +208,62 @@ vsf_status vsf_bayer_bg_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, in
   return record_ingest_done(ctx);
 }
 
+// cv::resize(src, dst, Size(dst_width, dst_height)), INTER_LINEAR on CV_8UC1 (k_resize.hip): what cv::imdecode's reduced
+// modes do to a PNG, and how a camera of another size than the context's gets in.
+vsf_status vsf_resize_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int src_width, int src_height,
+                                     size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst, int dst_width,
+                                     int dst_height, size_t dst_image_stride, size_t dst_row_stride) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !d_src || !d_dst || n_images < 1 || !vsf_resize_size_ok(src_width, src_height) ||
+      !vsf_resize_size_ok(dst_width, dst_height) || src_row_stride < (size_t)src_width || dst_row_stride < (size_t)dst_width)
+    return VSF_ERR_INVALID_ARG;
+  // (images may overlap their neighbours' padding, not their pixels; one image: the stride is not looked at)
+  if (n_images > 1 && (src_image_stride < (size_t)(src_height - 1) * src_row_stride + (size_t)src_width ||
+                       dst_image_stride < (size_t)(dst_height - 1) * dst_row_stride + (size_t)dst_width))
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  vsf_launch_resize_gray(d_src, n_images, src_width, src_height, src_image_stride, src_row_stride, d_dst, dst_width, dst_height,
+                         dst_image_stride, dst_row_stride, ctx->stream);
+  VSF_STICKY();
+  return record_ingest_done(ctx);
+}
+
+// ... for host pointers, synchronous: up, the kernel, down (device staging shared with the host-pointer encoders: both wait).
+vsf_status vsf_resize_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int src_width, int src_height, size_t src_image_stride,
+                           size_t src_row_stride, uint8_t* dst, int dst_width, int dst_height, size_t dst_image_stride,
+                           size_t dst_row_stride) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !src || !dst || n_images < 1 || n_images > 65535 || !vsf_resize_size_ok(src_width, src_height) ||
+      !vsf_resize_size_ok(dst_width, dst_height) || src_row_stride < (size_t)src_width || dst_row_stride < (size_t)dst_width)
+    return VSF_ERR_INVALID_ARG;
+  if (n_images > 1 && (src_image_stride < (size_t)(src_height - 1) * src_row_stride + (size_t)src_width ||
+                       dst_image_stride < (size_t)(dst_height - 1) * dst_row_stride + (size_t)dst_width))
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // device staging: sources (packed rows) | destinations (rows at a multiple of 4: dword stores)
+  const size_t n = (size_t)n_images, sp = (size_t)src_width, dp = ((size_t)dst_width + 3) & ~(size_t)3;
+  const size_t s_img = (sp * (size_t)src_height + 15) & ~(size_t)15, d_img = (dp * (size_t)dst_height + 15) & ~(size_t)15;
+  const size_t need = n * (s_img + d_img);
+  VsfEncodeScratch& e = ctx->encode;
+  if (need > e.staging_cap) {
+    const vsf_status gs = grow_scratch(ctx, e.staging, need);
+    if (gs != VSF_OK) return gs;
+    e.staging_cap = need;
+  }
+  uint8_t* d_src = e.staging;
+  uint8_t* d_dst = d_src + n * s_img;
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(d_src + i * s_img, sp, src + i * src_image_stride, src_row_stride, sp, (size_t)src_height,
+                             hipMemcpyHostToDevice, ctx->stream));
+  vsf_launch_resize_gray(d_src, n_images, src_width, src_height, s_img, sp, d_dst, dst_width, dst_height, d_img, dp, ctx->stream);
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(dst + i * dst_image_stride, dst_row_stride, d_dst + i * d_img, dp, (size_t)dst_width,
+                             (size_t)dst_height, hipMemcpyDeviceToHost, ctx->stream));
+  VSF_HIP(hipStreamSynchronize(ctx->stream));
+  VSF_STICKY();
+  return VSF_OK;
+}
+
 // cv::imdecode(IMREAD_GRAYSCALE) for JPEG files (slam_frontend_main.cc:99-100): markers and tables on the host, the entropy
 // decode and the IDCT on the device (k_jpeg.hip).
 vsf_status vsf_jpeg_decode_gray_batch(vsf_ctx* ctx, const uint8_t* const* jpeg, const size_t* nbytes, int n_images,
@@ -249,7 +305,7 @@ vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, co
 // cv::imdecode(data, IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8) for reduce = 2, 4, 8 (reduce = 1: vsf_imdecode_gray_batch): a JPEG
 // file of W x H is decoded by libjpeg's reduced inverse DCTs straight to ceil(W / reduce) x ceil(H / reduce) pixels -- width
 // x height here -- through the same upload-and-decode path.  A PNG file with reduce > 1 is VSF_ERR_UNSUPPORTED: cv::imdecode
-// decodes it at full size and calls cv::resize, which is not built here.
+// decodes it at full size and calls cv::resize: vsf_png_decode_gray_batch + vsf_resize_gray_batch_dev, not this call.
 vsf_status vsf_imdecode_reduced_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images,
                                            int reduce, int width, int height, uint8_t* d_dst, size_t dst_image_stride,
                                            size_t dst_row_stride) {

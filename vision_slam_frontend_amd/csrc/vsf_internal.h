@@ -428,6 +428,8 @@ int vsf_file_kind(const uint8_t* file, size_t nbytes);  // by the first bytes, a
 int vsf_run_end(const uint8_t* kinds, int n, int i0);   // one past the last file of the run of one kind that starts at i0
 // The denominators a decode takes, stated ONCE: 1 (full size) and cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8.
 inline bool vsf_reduce_ok(int reduce) { return reduce == 1 || reduce == 2 || reduce == 4 || reduce == 8; }
+// what cv::resize on the device takes on either side (vsf_resize_gray_batch_dev): VsfTap's 16-bit fields hold the taps
+inline bool vsf_resize_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= 32767 && h <= 32767; }
 struct VsfDecodeRun {  // files [i0, i0 + n) of one format; its upload starts `off` bytes (a multiple of 256) into the blob
   int i0 = 0, n = 0, kind = VSF_FILE_NONE;
   size_t off = 0;
@@ -507,5 +509,10 @@ struct VsfIngestSrc {
 #define VSF_INGEST_INLINE 8
 void vsf_launch_ingest_ring(uint8_t* d_ring, size_t image_stride, int dst_pitch, int w, int h, int slot0, int depth, int n_frames,
                             const VsfIngestSrc* inl, const VsfIngestSrc* table, hipStream_t s);
+
+// k_resize.hip: cv::resize (INTER_LINEAR, CV_8UC1) of n images of sw x sh into dw x dh, any base address and pitch on either
+// side; ONE launch (per 65535 images).  The caller has checked the sizes (1 .. 32767) and the pitches (>= the widths).
+void vsf_launch_resize_gray(const uint8_t* d_src, int n, int sw, int sh, size_t src_image_stride, size_t src_pitch, uint8_t* d_dst,
+                            int dw, int dh, size_t dst_image_stride, size_t dst_pitch, hipStream_t s);
 
 #endif  // VSF_INTERNAL_H_

@@ -302,18 +302,145 @@ vsf_status ensure_compressed(vsf_ctx* ctx, bool bayer) {
 
 // The device ring, its table of sources and its events: built by the first device frame -- a queue that never sees one owns
 // none of this (vsf_observe_device_ring_bytes says what it costs).
-vsf_status ensure_device_ring(vsf_ctx* ctx, bool bayer) {
+// (resized: the frames have a declared input size -- they wait in the ring of big slots, ensure_input, not in this one)
+vsf_status ensure_device_ring(vsf_ctx* ctx, bool bayer, bool resized = false) {
   vsf_ctx::Observe& o = ctx->ob;
-  if (!o.d_ring) {
-    const size_t bytes = vsf_observe_device_ring_bytes(ctx, o.depth);
-    if (bytes == 0) return VSF_ERR_INVALID_ARG;
+  if (o.dev_ev.empty()) {
     std::vector<Event> ev((size_t)o.depth);
     for (Event& e : ev) VSF_HIP(e.alloc(hipEventDisableTiming));
     VSF_HIP(o.h_dev_src.alloc((size_t)o.depth * 2 * sizeof(VsfIngestSrc), hipHostMallocMapped));
-    VSF_HIP(o.d_ring.alloc(bytes));
     o.dev_ev = std::move(ev);
   }
+  if (resized) return VSF_OK;
+  if (!o.d_ring) {
+    const size_t bytes = vsf_observe_device_ring_bytes(ctx, o.depth);
+    if (bytes == 0) return VSF_ERR_INVALID_ARG;
+    VSF_HIP(o.d_ring.alloc(bytes));
+  }
   if (bayer && !o.d_bayer) VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
+  return VSF_OK;
+}
+
+// ---- frames of a declared input size (vsf_observe_set_input_size) ----
+// The buffers of big slots (vsf_observe_plan.h), each built by the first frame that needs it -- a queue that never sees a
+// declared size owns none of this: the pinned ring raw host frames wait in, the device ring, the batches' own big slots (a
+// raw frame's upload, a compressed frame's decoded image), the mosaics of a Bayer batch.
+enum { kInHostRing = 1, kInDeviceRing = 2, kInBatch = 4, kInBayer = 8 };
+
+vsf_status ensure_input(vsf_ctx* ctx, int what) {
+  vsf_ctx::Observe& o = ctx->ob;
+  const size_t half = observe_input_half_bytes(ctx->ob_in_w, ctx->ob_in_h, ctx->ob_streams);
+  if (half == 0) return VSF_ERR_INVALID_ARG;
+  if (o.in_half != 0 && half > o.in_half) {
+    // A larger size has been declared since these were built, and frames of other streams may wait in them or be on their
+    // way out of them: what waits leaves, what left finishes, then they go (rare, and the one place the resize path waits).
+    ObserveQueue& q = *o.queue;
+    {
+      std::unique_lock<std::mutex> lk(q.mu);
+      if (q.status != VSF_OK) return q.status;
+      if (q.next_launch < q.next_ticket) {
+        const vsf_status st = q.caller_pump(lk, true);
+        if (st != VSF_OK) return st;
+      }
+    }
+    VSF_HIP(hipDeviceSynchronize());
+    if (o.h_in) ctx->retired_host.emplace_back(o.h_in.release());
+    o.d_in_ring = DevBuf<uint8_t>();
+    o.d_bayer_in = DevBuf<uint8_t>();
+    for (vsf_ctx::ObserveBatch& b : o.batch) b.d_in = DevBuf<uint8_t>();
+  }
+  o.in_half = std::max(o.in_half, half);
+  const size_t slot = 2 * o.in_half;
+  if ((what & kInHostRing) && !o.h_in) VSF_HIP(o.h_in.alloc((size_t)o.depth * slot, hipHostMallocDefault));
+  if ((what & kInDeviceRing) && !o.d_in_ring) VSF_HIP(o.d_in_ring.alloc((size_t)o.depth * slot));
+  if ((what & kInBayer) && !o.d_bayer_in) VSF_HIP(o.d_bayer_in.alloc((size_t)o.bmax * slot));
+  if (what & (kInBatch | kInBayer))
+    for (vsf_ctx::ObserveBatch& b : o.batch)
+      if (!b.d_in) VSF_HIP(b.d_in.alloc((size_t)o.bmax * slot));
+  return VSF_OK;
+}
+
+size_t input_bytes(const vsf_ctx* ctx) {  // vsf_observe_stats: every byte the resize path owns
+  const vsf_ctx::Observe& o = ctx->ob;
+  const size_t slot = 2 * o.in_half;
+  size_t bytes = (o.h_in ? (size_t)o.depth * slot : 0) + (o.d_in_ring ? (size_t)o.depth * slot : 0) +
+                 (o.d_bayer_in ? (size_t)o.bmax * slot : 0);
+  for (const vsf_ctx::ObserveBatch& b : o.batch) bytes += (b.d_in ? (size_t)o.bmax * slot : 0) + 2 * b.blob_in.cap;
+  return bytes;
+}
+
+// The batch's resized frames (o.resize_plan) on `s`: the raw host frames' uploads (ObserveUpload: one per stretch of them,
+// short gaps bridged) into the batch's big slots; the compressed frames' files decoded there at their own size, size by size; BayerBG -> gray at that
+// size for a Bayer batch; then ONE resize launch per run into the batch's images, where every other frame's pixels are
+// already (or, for a frame no kernel reads before, about to be) written.  *files: compressed frames were among them -- the
+// caller owes the batch its ingest finish.
+vsf_status ingest_resized(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s, bool* files) {
+  vsf_ctx::Observe& o = ctx->ob;
+  ObserveLaunchStats& stats = o.queue->stats;
+  const ObserveResizePlan& R = o.resize_plan;
+  const size_t half = o.in_half, slot = 2 * half;
+  const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
+  *files = false;
+  for (const ObserveUpload& u : R.uploads) {
+    VSF_HIP(hipMemcpyAsync(b.d_in + (size_t)u.f0 * slot, o.h_in + (size_t)u.slot0 * slot, (size_t)u.n * slot, hipMemcpyHostToDevice, s));
+    stats.resize_commands++;
+  }
+  // ---- cv::imdecode of the files, whole, at the size they have: a decode_runs per distinct size among them ----
+  const int N = 2 * n;
+  // (kept from batch to batch: no allocation on the launch path)
+  std::vector<const uint8_t*>& fl = o.rs_files;
+  std::vector<size_t>& sizes = o.rs_sizes;
+  std::vector<uint8_t>& kinds = o.rs_kinds;
+  fl.resize((size_t)N);
+  sizes.resize((size_t)N);
+  kinds.resize((size_t)N);
+  const auto is_file = [&](int f) {
+    const ObserveResizeIn& w = o.resize_in[(size_t)f];
+    return w.w != 0 && w.kind != 0 && w.kind != kObserveKindDevice;
+  };
+  int done[VSF_OBSERVE_MAX_STREAMS][2], n_done = 0;  // the sizes decoded so far: at most one per stream
+  for (int f0 = 0; f0 < n; f0++) {
+    const ObserveResizeIn lead = o.resize_in[(size_t)f0];
+    bool seen = !is_file(f0);  // (a size is decoded at the first frame that has it)
+    for (int q = 0; q < n_done && !seen; q++) seen = done[q][0] == lead.w && done[q][1] == lead.h;
+    if (seen || n_done == VSF_OBSERVE_MAX_STREAMS) continue;
+    done[n_done][0] = lead.w, done[n_done++][1] = lead.h;
+    std::fill(kinds.begin(), kinds.end(), (uint8_t)VSF_FILE_NONE);
+    for (int i = 0; i < N; i++) {
+      const int f = i / 2, fslot = (int)((t0 + f) % o.depth);
+      const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)fslot];
+      fl[(size_t)i] = o.h_cmp + ((size_t)fslot * 2 + (size_t)(i & 1)) * o.cmp_slot;
+      sizes[(size_t)i] = fr.nbytes[i & 1];
+      if (fr.in_w == lead.w && fr.in_h == lead.h && fr.kind[0] != 0 && fr.kind[0] != kObserveKindDevice) kinds[(size_t)i] = fr.kind[i & 1];
+    }
+    if (!b.blob_in.uploaded) VSF_HIP(b.blob_in.uploaded.alloc(hipEventDisableTiming));
+    int runs = 0;
+    const vsf_status st = decode_runs(ctx, fl.data(), sizes.data(), kinds.data(), N, lead.w, lead.h, b.blob_in, o.ing_scratch,
+                                      bayer ? o.d_bayer_in : b.d_in, half, (int)observe_input_pitch(lead.w), b.status, 1, s, &runs);
+    if (st != VSF_OK) return st;
+    stats.resize_commands += 1 + runs;  // (the upload, each run's decode)
+    *files = true;
+  }
+  const int cw = ctx->p.width, ch = ctx->p.height;
+  for (const ObserveResizeRun& r : R.runs) {
+    const int pitch = (int)observe_input_pitch(r.w);
+    uint8_t* staged = b.d_in + (size_t)r.f0 * slot;
+    const uint8_t* src = r.where == kObserveInDeviceRing ? o.d_in_ring + (size_t)r.src0 * slot : staged;
+    if (bayer) {  // the images are mosaics: where they lie -> the batch's big slots
+      const uint8_t* mosaic = r.where == kObserveInDeviceRing ? src : o.d_bayer_in + (size_t)r.f0 * slot;
+      vsf_launch_bayer_bg_gray(mosaic, 2 * r.n, r.w, r.h, half, pitch, staged, half, pitch, s);
+      stats.resize_commands++;
+      src = staged;
+    }
+    vsf_launch_resize_gray(src, 2 * r.n, r.w, r.h, half, (size_t)pitch, b.d_img + (size_t)r.f0 * 2 * ctx->st_img_stride, cw, ch,
+                           ctx->st_img_stride, ctx->st_img_pitch, s);
+    stats.resize_commands++;
+    stats.resized += r.n;
+    for (int f = r.f0; f < r.f0 + r.n; f++) {  // (what the frames also are)
+      stats.device_frames += o.resize_in[(size_t)f].kind == kObserveKindDevice;
+      stats.compressed += is_file(f);
+    }
+  }
   return VSF_OK;
 }
 
@@ -352,7 +479,8 @@ vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0
 // upload for every run of one format among them, a status word per image (b.status: damage lands on its own image) --, then
 // BayerBG -> gray for bayer_rggb8 frames, and the ingest finish: an image its decoder refused becomes all zero.  Raw frames of
 // the batch have been copied already.
-vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s) {
+// finish == false: frames of a declared input size follow (ingest_resized), and the finish behind them is the caller's.
+vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s, bool finish = true) {
   vsf_ctx::Observe& o = ctx->ob;
   const int w = ctx->p.width, h = ctx->p.height, N = 2 * n;
   const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
@@ -364,6 +492,7 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
     const int slot = (int)((t0 + i / 2) % o.depth);
     const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
     kinds[i] = fr.kind[i & 1] == kObserveKindDevice ? (uint8_t)VSF_FILE_NONE : fr.kind[i & 1];  // (in the ring: not a file)
+    if (o.in_half != 0 && fr.in_w != 0) kinds[i] = (uint8_t)VSF_FILE_NONE;  // (a file of another size: ingest_resized decodes it)
     reduces[i] = fr.reduce;  // (frames of different denominators share the batch and its ONE upload: a run ends where it changes)
     any_reduced |= fr.reduce > 1;
     files[i] = o.h_cmp + ((size_t)slot * 2 + (size_t)(i & 1)) * o.cmp_slot;
@@ -379,9 +508,9 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   if (st != VSF_OK || runs == 0) return st;
   // bayer_rggb8 (slam_frontend_main.cc:101-109): every image of such a batch is a decoded mosaic
   if (bayer) vsf_launch_bayer_bg_gray(o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
-  vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
+  if (finish) vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
   // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
-  o.queue->stats.ingest_commands += 2 + runs + (bayer ? 1 : 0);
+  o.queue->stats.ingest_commands += (finish ? 2 : 1) + runs + (bayer ? 1 : 0);
   for (int f = 0; f < n; f++) o.queue->stats.compressed += kinds[2 * f] != VSF_FILE_NONE;
   for (int f = 0; f < n; f++) o.queue->stats.reduced += kinds[2 * f] != VSF_FILE_NONE && reduces[2 * f] > 1;
   return VSF_OK;
@@ -468,20 +597,44 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   // solo: a lone frame with nothing else on the GPU runs on ONE stream from upload to result (no event hops in its chain);
   // otherwise copy, extraction and tail have a stream each, so that the next batch's upload and extraction run beside
   // this one's tail.
-  bool any_raw = false, any_cmp = false, any_dev = false;
+  // (any_*: frames of the context's size; rs_*: frames of a declared input size, which take the way of ingest_resized)
+  // (may_resize: the queue has seen a frame of a declared size -- until then no record's in_w is looked at or written)
+  const bool may_resize = o.in_half != 0;
+  bool any_raw = false, any_cmp = false, any_dev = false, rs_any = false, rs_cmp = false, rs_dev = false;
   for (int f = 0; f < n; f++) {
-    const uint8_t kind = o.frames[(size_t)((t0 + f) % o.depth)].kind[0];
-    any_raw |= kind == 0;
-    any_dev |= kind == kObserveKindDevice;
-    any_cmp |= kind != 0 && kind != kObserveKindDevice;
+    const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
+    const uint8_t kind = fr.kind[0];
+    const bool rs = may_resize && fr.in_w != 0, dev = kind == kObserveKindDevice, cmp = kind != 0 && !dev;
+    any_raw |= !rs && kind == 0;
+    any_dev |= !rs && dev;
+    any_cmp |= !rs && cmp;
+    rs_any |= rs;
+    rs_dev |= rs && dev;
+    rs_cmp |= rs && cmp;
   }
-  if (any_dev) {  // (vsf_observe_plan.cc: the runs of device frames, cut where the ring wraps)
+  if (any_dev || rs_dev) {  // (vsf_observe_plan.cc: the runs of device frames, cut where the ring wraps)
     o.run_kinds.resize((size_t)n);
     for (int f = 0; f < n; f++) o.run_kinds[(size_t)f] = o.frames[(size_t)((t0 + f) % o.depth)].kind[0];
+    // (a device frame of a declared size is not copied: k_resize.hip reads it where it lies, in the ring of big slots)
+    for (int f = 0; rs_dev && f < n; f++)
+      if (o.frames[(size_t)((t0 + f) % o.depth)].in_w != 0) o.run_kinds[(size_t)f] = 0;
     if (!observe_batch_runs(o.run_kinds.data(), n, t0, o.depth, &o.runs)) return VSF_ERR_INVALID_ARG;
   }
+  if (rs_any) {
+    o.resize_in.resize((size_t)n);
+    for (int f = 0; f < n; f++) {
+      const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
+      o.resize_in[(size_t)f] = {fr.in_w, fr.in_h, fr.kind[0]};
+    }
+    if (!observe_resize_plan(o.resize_in.data(), n, t0, o.depth, observe_upload_max_gap(2 * o.in_half), &o.resize_plan)) return VSF_ERR_INVALID_ARG;
+    for (int f = 1; f < n; f++)  // (vsf_observe_stats: a batch whose frames came in at more than one size)
+      if (o.resize_in[(size_t)f].w != o.resize_in[0].w || o.resize_in[(size_t)f].h != o.resize_in[0].h) {
+        stats.multi_size++;
+        break;
+      }
+  }
   // (compressed frames are decoded on the copy stream whatever else runs: the decoders' scratch exists once, for that stream)
-  hipStream_t s_copy = solo && !any_cmp ? ctx->stream : o.copy_stream, s_ex = ctx->stream,
+  hipStream_t s_copy = solo && !any_cmp && !rs_cmp ? ctx->stream : o.copy_stream, s_ex = ctx->stream,
               s_tail = solo ? ctx->stream : o.tail_stream;
   // ---- upload: ONE copy command (two when the frames wrap around the staging ring) ----
   {
@@ -495,15 +648,25 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
       VSF_HIP(hipMemcpyAsync(b.d_img + (size_t)first * frame_bytes, o.h_img, (size_t)(n - first) * frame_bytes,
                              hipMemcpyHostToDevice, s_copy));
     // ---- device frames: out of the device ring, behind the launches that put them there ----
-    if (any_dev) {
+    if (any_dev || rs_dev) {  // (rs_dev alone: the waits for the producers' events, no copy)
       const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
-      const vsf_status st = ingest_device_runs(ctx, b, t0, n, bayer, bayer && !any_cmp, s_copy);
+      const vsf_status st = ingest_device_runs(ctx, b, t0, n, bayer, bayer && any_dev && !any_cmp, s_copy);
       if (st != VSF_OK) return st;
     }
     // ---- compressed frames: one more copy command for their files, the decoders, the ingest finish ----
     if (any_cmp) {
-      const vsf_status st = ingest_batch(ctx, b, t0, n, s_copy);
+      const vsf_status st = ingest_batch(ctx, b, t0, n, s_copy, !rs_cmp);
       if (st != VSF_OK) return st;
+    }
+    // ---- frames of a declared input size: to the context's size, over whatever the steps above left in their places ----
+    if (rs_any) {
+      bool files = false;
+      const vsf_status st = ingest_resized(ctx, b, t0, n, s_copy, &files);
+      if (st != VSF_OK) return st;
+      if (files) {  // (an image its decoder refused becomes all zero, as in ingest_batch)
+        vsf_launch_ingest_finish(b.d_img, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.height, b.status, 2 * n, s_copy);
+        stats.resize_commands++;
+      }
     }
     if (s_copy != s_ex) {
       VSF_HIP(hipEventRecord(b.ev_uploaded, s_copy));
@@ -852,6 +1015,8 @@ vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams) {
   }
   if (n_streams != ctx->ob_streams)  // (vsf_observe_set_stream_cam_to_robot: the streams are other cameras now)
     for (bool& set : ctx->ob_stream_c2r_set) set = false;
+  if (n_streams != ctx->ob_streams)  // (vsf_observe_set_input_size: ... of other sizes)
+    for (int s = 0; s < VSF_OBSERVE_MAX_STREAMS; s++) ctx->ob_in_w[s] = ctx->ob_in_h[s] = 0;
   ctx->ob_streams = n_streams;
   return VSF_OK;
 }
@@ -873,6 +1038,17 @@ vsf_status vsf_observe_set_stream_cam_to_robot(vsf_ctx* ctx, int stream, const f
   if (!ctx || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   ctx->ob_stream_c2r_set[stream] = m != nullptr;
   if (m) std::memcpy(ctx->ob_stream_c2r[stream], m, sizeof(ctx->ob_stream_c2r[stream]));
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_set_input_size(vsf_ctx* ctx, int stream, int width, int height) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  if (!(width == 0 && height == 0) && !vsf_resize_size_ok(width, height)) return VSF_ERR_INVALID_ARG;
+  // (the rule of vsf_observe_reset_stream: no frame of the stream submitted and not collected)
+  if (ctx->ob.ready && ctx->ob.streams[(size_t)stream].uncollected != 0) return VSF_ERR_INVALID_ARG;
+  ctx->ob_in_w[stream] = width;
+  ctx->ob_in_h[stream] = height;
   return VSF_OK;
 }
 
@@ -912,7 +1088,7 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[26] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+  const int64_t v[30] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
                          s.file_commands, (int64_t)ctx->ob_streams, s.multi,
@@ -920,8 +1096,9 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
                          (int64_t)(o.d_ring ? vsf_observe_device_ring_bytes(ctx, o.depth) : 0),
                          s.cloud_frames, s.cloud_commands,
                          (int64_t)(o.h_wp ? (size_t)o.depth * ((size_t)ctx->p.max_keypoints * 3 * sizeof(double) + sizeof(int32_t)) : 0),
-                         s.reduced, s.seeded_frames, s.colour_commands};
-  for (int i = 0; i < n && i < 26; i++) out[i] = v[i];
+                         s.reduced, s.seeded_frames, s.colour_commands,
+                         s.resized, s.resize_commands, (int64_t)input_bytes(ctx), s.multi_size};
+  for (int i = 0; i < n && i < 30; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -993,6 +1170,12 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     }
   }
   vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
+  const bool resized = ctx->ob_in_w[stream] != 0;  // (w x h is the stream's declared size then: the callers have checked)
+  if (resized) {
+    if (bayer && w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
+    st = ensure_input(ctx, kinds ? (bayer ? kInBatch | kInBayer : kInBatch) : kInHostRing | kInBatch);
+    if (st != VSF_OK) return st;
+  }
   const int64_t t_copy = now_ns();
   if (kinds) {
     // ---- the two files into the frame's slots of the compressed ring (built by the first such frame) ----
@@ -1003,11 +1186,13 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     std::memcpy(h_cmp, left, nbytes[0]);
     std::memcpy(h_cmp + o.cmp_slot, right, nbytes[1]);
   } else {
-    uint8_t* h_img = o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
-    const ObserveCopyHelper::Job jr{h_img + ctx->st_img_stride, right, ctx->st_img_pitch, stride, (size_t)w, h};
+    // (a frame of a declared size: into its big slot of the pinned ring of such slots, rows at ITS width's pitch)
+    uint8_t* h_img = resized ? o.h_in + (size_t)slot * 2 * o.in_half : o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
+    const size_t h_stride = resized ? o.in_half : ctx->st_img_stride, h_pitch = resized ? observe_input_pitch(w) : ctx->st_img_pitch;
+    const ObserveCopyHelper::Job jr{h_img + h_stride, right, h_pitch, stride, (size_t)w, h};
     // frames are streaming in (the previous one is still in the queue): the helper thread takes the right image
     const bool helped = o.copy_helper && q.next_ticket > q.next_collect && o.copy_helper->post(jr);
-    stage_image(h_img, ctx->st_img_pitch, left, stride, (size_t)w, h);
+    stage_image(h_img, h_pitch, left, stride, (size_t)w, h);
     if (helped)
       o.copy_helper->wait();
     else
@@ -1020,6 +1205,10 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   }
   fr.bayer = bayer;
   fr.reduce = (uint8_t)reduce;
+  if (o.in_half != 0) {  // (a queue that has seen no declared size: the records' sizes are 0 x 0 and stay so)
+    fr.in_w = resized ? w : 0;
+    fr.in_h = resized ? h : 0;
+  }
   fr.calib = *calib;
   fr.best_percent = best_percent;
   capture_placement(ctx, stream, fr);
@@ -1045,7 +1234,12 @@ vsf_status vsf_observe_submit_stream(vsf_ctx* ctx, int stream, const uint8_t* le
       frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
     return VSF_ERR_INVALID_ARG;
   *ticket = -1;
-  if (w != ctx->p.width || h != ctx->p.height || stride < (size_t)w || ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
+  if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  // (the stream's declared size, vsf_observe_set_input_size, or the context's)
+  const bool declared = ctx->ob_in_w[stream] != 0;
+  if (w != (declared ? ctx->ob_in_w[stream] : ctx->p.width) || h != (declared ? ctx->ob_in_h[stream] : ctx->p.height) ||
+      stride < (size_t)w || ctx->p.max_images < 2)
+    return VSF_ERR_INVALID_ARG;
   return observe_submit(ctx, stream, left, right, w, h, stride, nullptr, nullptr, false, calib, best_percent, frame_life, ticket);
 }
 
@@ -1088,17 +1282,20 @@ static vsf_status observe_submit_files(vsf_ctx* ctx, int stream, const uint8_t* 
   *ticket = -1;
   if (ctx->p.max_images < 2 || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   // the decoders' host half, file by file: a refused file books nothing and leaves the queue as it was
+  // a stream with a declared size (vsf_observe_set_input_size): the FILE's size must be that one -- it is decoded whole and
+  // resized, cv::resize(DecodeImage(msg)); a reduced decode on top of that is not built
+  const bool declared = ctx->ob_in_w[stream] != 0;
+  if (declared && reduce != 1) return VSF_ERR_INVALID_ARG;
+  const int w = declared ? ctx->ob_in_w[stream] : ctx->p.width, h = declared ? ctx->ob_in_h[stream] : ctx->p.height;
   const size_t cap = compressed_cap(ctx);
   const size_t nbytes[2] = {left_bytes, right_bytes};
   int kinds[2] = {0, 0};
-  vsf_status st = vsf_observe_probe_compressed_reduced(left, left_bytes, reduce, ctx->p.width, ctx->p.height, cap,
-                                                       ctx->tuning.jpeg_serial, &kinds[0]);
+  vsf_status st = vsf_observe_probe_compressed_reduced(left, left_bytes, reduce, w, h, cap, ctx->tuning.jpeg_serial, &kinds[0]);
   if (st == VSF_OK)
-    st = vsf_observe_probe_compressed_reduced(right, right_bytes, reduce, ctx->p.width, ctx->p.height, cap,
-                                              ctx->tuning.jpeg_serial, &kinds[1]);
+    st = vsf_observe_probe_compressed_reduced(right, right_bytes, reduce, w, h, cap, ctx->tuning.jpeg_serial, &kinds[1]);
   if (st != VSF_OK) return st;
-  return observe_submit(ctx, stream, left, right, ctx->p.width, ctx->p.height, 0, kinds, nbytes, bayer != 0, calib,
-                        best_percent, frame_life, ticket, reduce);
+  return observe_submit(ctx, stream, left, right, w, h, 0, kinds, nbytes, bayer != 0, calib, best_percent, frame_life, ticket,
+                        reduce);
 }
 
 size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth) {
@@ -1120,11 +1317,15 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
   for (int i = 0; i < n; i++) tickets[i] = -1;
   if (pixfmt != VSF_PIX_MONO8 && pixfmt != VSF_PIX_BAYER_RGGB8) return VSF_ERR_INVALID_ARG;
   if (ctx->p.max_images < 2 || n > 1024) return VSF_ERR_INVALID_ARG;
-  const size_t w = (size_t)ctx->p.width;
+  if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  // (the images have the stream's declared size, vsf_observe_set_input_size, or the context's)
+  const bool resized = ctx->ob_in_w[stream] != 0;
+  const int in_w = resized ? ctx->ob_in_w[stream] : ctx->p.width, in_h = resized ? ctx->ob_in_h[stream] : ctx->p.height;
+  const size_t w = (size_t)in_w;
   for (int i = 0; i < n; i++)
     if (!frames[i].left || !frames[i].right || frames[i].left_pitch < w || frames[i].right_pitch < w) return VSF_ERR_INVALID_ARG;
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
-  if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  if (resized && pixfmt == VSF_PIX_BAYER_RGGB8 && in_w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6) return VSF_ERR_INVALID_ARG;
   const bool bayer = pixfmt == VSF_PIX_BAYER_RGGB8;
   hipStream_t producer = static_cast<hipStream_t>(producer_stream);
@@ -1156,7 +1357,8 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
       }
     }
   }
-  st = ensure_device_ring(ctx, bayer);
+  st = ensure_device_ring(ctx, bayer, resized);
+  if (st == VSF_OK && resized) st = ensure_input(ctx, bayer ? kInDeviceRing | kInBayer : kInDeviceRing);
   if (st != VSF_OK) return st;
   if (o.debug && !o.seeded) {  // the stereo lines' colours, drawn ahead for every frame of the call (observe_submit)
     const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + n - q.next_collect) * K;
@@ -1176,8 +1378,12 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     e[0] = {static_cast<const uint8_t*>(frames[i].left), frames[i].left_pitch};
     e[1] = {static_cast<const uint8_t*>(frames[i].right), frames[i].right_pitch};
   }
-  vsf_launch_ingest_ring(o.d_ring, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.width, ctx->p.height, span.slot0, o.depth, n,
-                         inl, by_table ? o.h_dev_src.get() : nullptr, producer);
+  if (resized)  // (into the ring of big slots, rows at the declared width's pitch: k_resize.hip reads them there)
+    vsf_launch_ingest_ring(o.d_in_ring, o.in_half, (int)observe_input_pitch(in_w), in_w, in_h, span.slot0, o.depth, n, inl,
+                           by_table ? o.h_dev_src.get() : nullptr, producer);
+  else
+    vsf_launch_ingest_ring(o.d_ring, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.width, ctx->p.height, span.slot0, o.depth, n,
+                           inl, by_table ? o.h_dev_src.get() : nullptr, producer);
   const int ev_slot = (span.slot0 + n - 1) % o.depth;
   VSF_HIP(hipEventRecord(o.dev_ev[(size_t)ev_slot], producer));
   VSF_STICKY();
@@ -1189,6 +1395,10 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     fr.nbytes[0] = fr.nbytes[1] = 0u;
     fr.bayer = bayer;
     fr.reduce = 1;
+    if (o.in_half != 0) {
+      fr.in_w = resized ? in_w : 0;
+      fr.in_h = resized ? in_h : 0;
+    }
     fr.dev_event = ev_slot;
     fr.dev_stream = producer;
     fr.calib = *calib;

@@ -102,4 +102,65 @@ bool observe_batch_runs(const uint8_t* kinds, int n, int64_t t0, int depth, std:
   return true;
 }
 
+size_t observe_input_pitch(int w) { return w >= 1 && w <= 32767 ? ((size_t)w + 63) & ~(size_t)63 : 0; }
+
+size_t observe_input_image_bytes(int w, int h) {
+  if (w < 1 || h < 1 || w > 32767 || h > 32767) return 0;
+  return (observe_input_pitch(w) * (size_t)h + 255) & ~(size_t)255;
+}
+
+size_t observe_input_half_bytes(const int* in_w, const int* in_h, int n_streams) {
+  if (!in_w || !in_h || n_streams < 1 || n_streams > VSF_OBSERVE_MAX_STREAMS) return 0;
+  size_t half = 0;
+  for (int s = 0; s < n_streams; s++)
+    if (in_w[s] != 0 || in_h[s] != 0) half = std::max(half, observe_input_image_bytes(in_w[s], in_h[s]));
+  return half;
+}
+
+size_t observe_input_ring_bytes(int depth, size_t half) {
+  if (depth < 1 || depth > 1024 || half == 0) return 0;
+  return (size_t)depth * 2 * half;
+}
+
+int observe_upload_max_gap(size_t slot_bytes) {
+  if (slot_bytes == 0) return 0;
+  const size_t gap = (size_t)kObserveCopyCommandUs * kObserveLinkBytesPerUs / slot_bytes;
+  return gap > 1024 ? 1024 : (int)gap;
+}
+
+bool observe_resize_plan(const ObserveResizeIn* in, int n, int64_t t0, int depth, int max_gap, ObserveResizePlan* plan) {
+  if (!in || !plan || depth < 1 || n < 1 || n > depth || t0 < 0 || max_gap < 0) return false;
+  plan->runs.clear();
+  plan->uploads.clear();
+  plan->n_resized = 0;
+  int raw_last = -1;  // the last raw resized frame so far: the end of uploads.back()
+  int slot = (int)(t0 % depth);
+  bool open = false;  // the frame in front is the last of runs.back()
+  for (int f = 0; f < n; f++, slot = slot + 1 == depth ? 0 : slot + 1) {
+    const ObserveResizeIn& w = in[f];
+    if (w.kind > kObserveKindDevice || w.w < 0 || w.h < 0 || (w.w == 0) != (w.h == 0)) return false;
+    if (w.w == 0) {
+      open = false;
+      continue;
+    }
+    plan->n_resized++;
+    const int where = w.kind == kObserveKindDevice ? kObserveInDeviceRing : kObserveInStaged;
+    if (w.kind == 0) {
+      // (the upload in front reaches this frame unless the gap is too long or the ring wrapped in between: slot <= gap then)
+      if (raw_last >= 0 && f - raw_last - 1 <= max_gap && slot > f - raw_last - 1)
+        plan->uploads.back().n = f - plan->uploads.back().f0 + 1;
+      else
+        plan->uploads.push_back({f, 1, slot});
+      raw_last = f;
+    }
+    const bool wraps = where == kObserveInDeviceRing && slot == 0;
+    if (open && !wraps && plan->runs.back().where == where && plan->runs.back().w == w.w && plan->runs.back().h == w.h)
+      plan->runs.back().n++;
+    else
+      plan->runs.push_back({where, f, 1, where == kObserveInDeviceRing ? slot : f, w.w, w.h});
+    open = true;
+  }
+  return true;
+}
+
 }  // namespace vsfi

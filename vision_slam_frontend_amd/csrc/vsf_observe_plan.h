@@ -88,6 +88,56 @@ struct ObserveRun {
 // from batch to batch.
 bool observe_batch_runs(const uint8_t* kinds, int n, int64_t t0, int depth, std::vector<ObserveRun>* runs);
 
+// ---- frames of another size than the context's (vsf_observe_set_input_size) ----
+// A stream with a declared size W x H hands in frames of that size; k_resize.hip brings them to the context's size inside the
+// batch.  Until then they wait in rings of their own, whose slots hold a frame of ANY declared size:
+//   an image of W x H has its rows observe_input_pitch(W) apart (W rounded up to 64, the staging rule) and takes
+//   observe_input_image_bytes(W, H) = pitch * H rounded up to 256 bytes;
+//   `half`, the place of one image, is the largest of these over the declared sizes; a slot is 2 * half: the left image at
+//   its start, the right one `half` behind it -- so the 2 n images of n consecutive slots lie `half` apart, whatever their
+//   size, and one resize launch takes them.
+size_t observe_input_pitch(int w);               // 0: w outside 1 .. 32767
+size_t observe_input_image_bytes(int w, int h);  // 0: a size outside 1 .. 32767
+// in_w[s], in_h[s]: stream s's declared size, 0 x 0: none.  0: no stream has one (or an argument is out of range).
+size_t observe_input_half_bytes(const int* in_w, const int* in_h, int n_streams);
+// A ring of `depth` such slots, 0 where there is none.
+size_t observe_input_ring_bytes(int depth, size_t half);
+
+// Where a batch's resized frames lie and what takes them to the batch's images.  A frame waits either STAGED -- raw host
+// frames in the pinned ring of big slots, uploaded into the batch's own buffer of big slots; compressed frames decoded into
+// that buffer: both at the index the frame has in the batch -- or in the DEVICE ring of big slots, at its ring slot.
+enum { kObserveInStaged = 0, kObserveInDeviceRing = 1 };
+struct ObserveResizeIn {  // a frame of the batch
+  int w, h;               // its declared size, 0 x 0: it is not resized
+  uint8_t kind;           // ObserveFrame::kind
+};
+struct ObserveResizeRun {  // ONE resize launch: 2 n images of w x h, `half` apart, from slot `src0` on
+  int where;               // kObserveIn*
+  int f0, n;               // frames [f0, f0 + n) of the batch
+  int src0;                // staged: f0; device ring: the ring slot of frame f0 (src0 + n <= depth)
+  int w, h;
+};
+struct ObserveUpload {  // ONE copy command out of the pinned ring of big slots: batch frames [f0, f0 + n), ring slots
+  int f0, n, slot0;     // [slot0, slot0 + n) (slot0 + n <= depth), into the batch's big slots [f0, f0 + n)
+};
+struct ObserveResizePlan {
+  std::vector<ObserveResizeRun> runs;  // in frame order, maximal: a run ends where the size or the place changes, or the ring wraps
+  // The raw host frames among them, as copy commands.  A copy command has a fixed cost whatever it carries, so slots that hold
+  // nothing of the raw resized frames are carried along where that is cheaper than a command of their own: a gap of up to
+  // `max_gap` such slots between two raw resized frames is bridged, a longer one ends the upload (max_gap = 0: nothing is
+  // carried along).  An upload also ends where the ring wraps.  Every upload begins and ends with a raw resized frame.
+  std::vector<ObserveUpload> uploads;
+  int n_resized = 0;
+};
+// The gap worth bridging for slots of `slot_bytes`: what a link of kObserveLinkBytesPerUs carries in the kObserveCopyCommandUs a
+// copy command costs by itself (NOTES.md: 180 us whatever it carries; 50 GB/s: 9 MB).  BOTH constants come from this
+// repository's earlier notes on the queue's first upload; neither was measured for this path.
+enum { kObserveCopyCommandUs = 180, kObserveLinkBytesPerUs = 50000 };
+int observe_upload_max_gap(size_t slot_bytes);
+// false: an argument is out of range (n > depth, a size with one side 0, a kind that does not exist, max_gap < 0); `plan`
+// keeps its storage.
+bool observe_resize_plan(const ObserveResizeIn* in, int n, int64_t t0, int depth, int max_gap, ObserveResizePlan* plan);
+
 }  // namespace vsfi
 
 #endif  // VSF_OBSERVE_PLAN_H_

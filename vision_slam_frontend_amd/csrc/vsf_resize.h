@@ -67,6 +67,22 @@ VSF_RESIZE_HD inline VsfTap resize_ytap(int dy, double scale_y, int sh) {
   return VsfTap{(uint16_t)w.i0, (uint16_t)w.i1, (int16_t)w.c0, (int16_t)w.c1};
 }
 
+// k_resize.hip (any source size into any destination size): a wave's 256 output columns [256 c, 256 c + 255] read the pixels
+// [i0(first), i1(last)] of a source row -- the taps grow with the column -- through the aligned dwords that hold them, and a
+// row may begin anywhere in its first dword.  The dwords the widest of a row's waves may need: what the launch sizes its
+// per-lane fetch by.
+inline int resize_span_dwords(int sw, int dw) {
+  const double scale_x = 1. / ((double)dw / sw);
+  int need = 0;
+  for (int xb = 0; xb < dw; xb += 256) {
+    const int xe = xb + 255 < dw - 1 ? xb + 255 : dw - 1;
+    const int bytes = (int)resize_xtap(xe, scale_x, sw).i1 - (int)resize_xtap(xb, scale_x, sw).i0 + 1;
+    const int dwords = (bytes + 3 + 3) >> 2;  // (+ 3: the first pixel in the last byte of its dword)
+    if (dwords > need) need = dwords;
+  }
+  return need;
+}
+
 // Packing plan of a band narrower than a wave.  A strip (R output rows) of such a band is a span of `lanes` lanes, a lane
 // being four output columns; the spans of the level's `nstrips` strips lie end to end and wave j takes lanes
 // [64 j, 64 j + 64) of that sequence, whatever strips they belong to.  A lane evaluates the y taps of one (strip, row) of

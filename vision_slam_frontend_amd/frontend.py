@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
         L.vsfh_group_create_ex.restype = vp
         L.vsfh_set_imdecode_reduce.argtypes = [vp, i32]
         L.vsfh_set_imdecode_reduce.restype = None
+        L.vsfh_set_resize.argtypes = [vp, i32, i32, i32, i32]
+        L.vsfh_set_resize.restype = None
         L.vsfh_set_compressed_cap.argtypes = [vp, sz]
         L.vsfh_set_compressed_cap.restype = None
         L.vsfh_debug_image_compressed_format.argtypes = [vp, i32]
@@ -163,11 +165,17 @@ class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False, imdecode_reduce: int = 1,
-                 compressed_cap: int = 0, debug_colour_seed=None, cam_to_robot=None):
+                 compressed_cap: int = 0, debug_colour_seed=None, cam_to_robot=None, resize_to=None):
+        """resize_to=(w, h): FrontendConfig::resize_width_ / resize_height_ -- the context has that size, width x height is
+        the CAMERA's (what device frames are taken to be; raw and compressed frames bring their own), every frame goes through
+        cv::resize on the device, and the calibration is the caller's, for the resized image."""
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
-        self._h = lib().vsfh_frontend_create(nfeatures, width, height, device, _p(F), best_percent, frame_life)
+        cw, ch = (width, height) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
+        self._h = lib().vsfh_frontend_create(nfeatures, cw, ch, device, _p(F), best_percent, frame_life)
         self.cap = nfeatures + 256
         self.size, self.device = (width, height), device
+        if resize_to is not None:
+            lib().vsfh_set_resize(self._h, cw, ch, width, height)
         if debug_colour_seed is not None:  # FrontendConfig::debug_colour_seeded_ / _seed_: the object's own rand(), before the switch
             lib().vsfh_set_debug_colour_seed(self._h, 1, int(debug_colour_seed))
         if debug_images:  # FrontendConfig::debug_images_ (the reference's default is on, slam_frontend.cc:552)
@@ -476,7 +484,11 @@ class FrontendGroup:
     def __init__(self, width: int, height: int, fundamentals, nfeatures: int = 10000, device: int = 0, best_percents=None,
                  frame_life: int = 0, imdecode_reduces=None, compressed_cap: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, debug_colour_seeds=None, cam_to_robots=None,
-                 visualization: bool = False):
+                 visualization: bool = False, resize_to=None, camera_sizes=None):
+        """resize_to=[(w, h) or None, ...]: FrontendConfig::resize_width_ / resize_height_ per member (None: off) -- a resized
+        member takes frames of its camera's size and shares the group's width x height context, so (w, h) is width x height;
+        camera_sizes=[(W, H) or None, ...]: what member i's DEVICE frames are taken to be (raw and compressed frames bring
+        their own size)."""
         F = np.ascontiguousarray(fundamentals, np.float32).reshape(-1, 9)
         n = len(F)
         bp = None if best_percents is None else np.ascontiguousarray(best_percents, np.float32).reshape(n)
@@ -496,6 +508,13 @@ class FrontendGroup:
             m.size, m.device = (width, height), device
             m.close = lambda: None  # (the group owns its members)
             self.members.append(m)
+        for i, r in enumerate(resize_to or ()):  # per camera: FrontendConfig::resize_width_ / resize_height_ of member i
+            if r is not None:
+                cam = (camera_sizes or [None] * n)[i] or (0, 0)
+                lib().vsfh_set_resize(self.members[i]._h, int(r[0]), int(r[1]), int(cam[0]), int(cam[1]))
+                self._check(i, "FrontendGroup(resize_to=)")
+                if cam != (0, 0):
+                    self.members[i].size = (int(cam[0]), int(cam[1]))
         for i, d in enumerate(imdecode_reduces or ()):  # per camera: FrontendConfig::imdecode_reduce_ of member i
             self.members[i].set_imdecode_reduce(d)
         if compressed_cap:  # the group's queue has ONE byte cap: size it for the largest camera's files

@@ -174,6 +174,11 @@ void vsfh_set_debug_colour_seed(void* f, int seeded, uint32_t seed) {
 }
 // FrontendConfig::imdecode_reduce_ (a group's member: the pointer vsfh_group_member returns)
 void vsfh_set_imdecode_reduce(void* f, int reduce) { static_cast<Frontend*>(f)->set_imdecode_reduce(reduce); }
+// FrontendConfig::resize_width_ / resize_height_ (a group's member: the pointer vsfh_group_member returns); camera_width x
+// camera_height > 0: image_width / image_height too, what device frames are taken to be
+void vsfh_set_resize(void* f, int width, int height, int camera_width, int camera_height) {
+  static_cast<Frontend*>(f)->set_resize(width, height, camera_width, camera_height);
+}
 // FrontendConfig::compressed_cap_ (a group's member: the group's)
 void vsfh_set_compressed_cap(void* f, size_t cap_per_image) { static_cast<Frontend*>(f)->set_compressed_cap(cap_per_image); }
 // The format of what vsfh_debug_image_compressed returns: 0 none, 1 "jpeg", 2 "png".

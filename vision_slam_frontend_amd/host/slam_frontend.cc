@@ -128,6 +128,7 @@ FrontendConfig::FrontendConfig() {
   debug_colour_seed_ = 1;
   visualization_ = false;
   imdecode_reduce_ = 1;  // IMREAD_GRAYSCALE, the reference's flag
+  resize_width_ = resize_height_ = 0;  // no cv::resize in front
   compressed_cap_ = 0;   // the library's default: the context's width x height + 64 KB
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
   descriptor_extract_type_ = DescriptorExtractorType::ORB;
@@ -245,7 +246,7 @@ Frontend::Frontend(const std::string& config_path) : Frontend(config_path, Front
 
 Frontend::Frontend(const std::string& /*config_path*/, const FrontendConfig& config, int device)
     : Frontend(config, device, nullptr, 0) {
-  if (config_.image_width > 0 && config_.image_height > 0) EnsureContext(config_.image_width, config_.image_height);
+  if (ContextWidth(config_) > 0 && ContextHeight(config_) > 0) EnsureContext(ContextWidth(config_), ContextHeight(config_));
 }
 
 // Everything but the context: a Frontend of its own builds it right away (above), a group builds ONE for all its members.
@@ -302,6 +303,7 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
   last_status_ = vsf_create(&p, device_, &ctx_);
   if (last_status_ != VSF_OK) return false;
   ctx_generation_++;
+  declared_w_ = declared_h_ = 0;  // (a new context's streams have no declared input size)
   ctx_depth_ = queue_depth();
   last_status_ = vsf_set_option(ctx_, VSF_OPT_OBSERVE_THREAD, queue_thread_ ? 1 : 0);
   if (last_status_ == VSF_OK) last_status_ = vsf_set_option(ctx_, VSF_OPT_OBSERVE_COPY_THREAD, copy_thread_ ? 1 : 0);
@@ -642,11 +644,28 @@ bool Frontend::ObserveImageFused(const Image& left_image, const Image& right_ima
   return ObserveFused(left_image.cols, left_image.rows, fp);
 }
 
+bool Frontend::DeclareInput(int width, int height) {
+  if (width == declared_w_ && height == declared_h_) return true;
+  // a frame of another size than the one before: the library takes a new size only while no frame of the stream is in
+  // flight, so those are booked first (a group's in its order)
+  if (!(group_ ? group_->Flush() : Flush())) return false;
+  last_status_ = vsf_observe_set_input_size(ctx_, stream_, width, height);
+  if (last_status_ != VSF_OK) return false;
+  declared_w_ = width;
+  declared_h_ = height;
+  return true;
+}
+
 bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
-  if (!EnsureContext(width, height)) {
+  // config.resize_width_ / resize_height_: the context has the resized size, the frame its own
+  const int cw = resizing() ? config_.resize_width_ : width, ch = resizing() ? config_.resize_height_ : height;
+  if (!EnsureContext(cw, ch)) {
     if (last_status_ == VSF_OK) last_status_ = VSF_ERR_INVALID_ARG;
     return false;
   }
+  // (a frame that has the context's size already is a frame like any other: no declared size, no resize launch)
+  const bool other = width != cw || height != ch;
+  if (!DeclareInput(other ? width : 0, other ? height : 0)) return false;
   const vsf_calibration calib = MakeCalibration(config_);
   // the queue must have room: when it is full, the oldest frame is collected and booked first
   // (a group member: the queue is the group's, and so is the order its frames are retired in)
@@ -949,6 +968,10 @@ void Frontend::FinishNode(const Frame& curr_frame, const std::vector<VisionFeatu
   frame_list_.push_back(curr_frame);
 }
 
+// The size of the context a configuration asks for: the resized size where a resize is set, else the camera's.
+int ContextWidth(const FrontendConfig& c) { return c.resize_width_ > 0 && c.resize_height_ > 0 ? c.resize_width_ : c.image_width; }
+int ContextHeight(const FrontendConfig& c) { return c.resize_width_ > 0 && c.resize_height_ > 0 ? c.resize_height_ : c.image_height; }
+
 // The denominators the library takes are stated in the library: vsf_reduced_size refuses every other one.
 static bool ReduceOk(int reduce) {
   int w = 0, h = 0;
@@ -970,7 +993,10 @@ bool Frontend::ObserveCompressedImage(const uint8_t* left, size_t left_bytes, co
     return false;
   }
   int width = 0, height = 0;
-  if (ctx_) {
+  if (resizing()) {  // every file states its own size; the context's is config.resize_width_ x resize_height_
+    last_status_ = reduce > 1 || !left || !right ? VSF_ERR_INVALID_ARG : vsf_compressed_image_size(left, left_bytes, &width, &height);
+    if (last_status_ != VSF_OK) return false;  // (a reduced decode and a resize are not combined)
+  } else if (ctx_) {
     vsf_params p;
     vsf_get_params(ctx_, &p);
     width = p.width;
@@ -1001,7 +1027,7 @@ bool Frontend::ObserveDeviceImage(const void* left, size_t left_pitch, const voi
     return false;
   }
   int width = config_.image_width, height = config_.image_height;
-  if (ctx_) {
+  if (ctx_ && !resizing()) {  // (with a resize the configuration states the camera's size, the context has the resized one)
     vsf_params p;
     vsf_get_params(ctx_, &p);
     width = p.width;
@@ -1030,6 +1056,23 @@ bool Frontend::ObserveImage(const Image& left_image, const Image& right_image, d
       left_image.step == right_image.step && config_.orb_nfeatures + 256 < 65536 && config_.frame_life_ >= 1 &&
       config_.frame_life_ + 1 <= 64)
     return ObserveImageFused(left_image, right_image);
+  if (resizing() && !left_image.empty() && !right_image.empty() &&
+      (left_image.cols != config_.resize_width_ || left_image.rows != config_.resize_height_)) {
+    // per-call mode: cv::resize of both images first (vsf_resize_gray: the queue's kernel, host to host), then the frame as ever
+    const int w = config_.resize_width_, h = config_.resize_height_;
+    if (left_image.cols != right_image.cols || left_image.rows != right_image.rows || !EnsureContext(w, h)) {
+      if (last_status_ == VSF_OK) last_status_ = VSF_ERR_INVALID_ARG;
+      return false;
+    }
+    const Image* in[2] = {&left_image, &right_image};
+    for (int k = 0; k < 2; k++) {
+      resized_[k].resize((size_t)w * h);
+      last_status_ = vsf_resize_gray(ctx_, in[k]->data, 1, in[k]->cols, in[k]->rows, 0, in[k]->step, resized_[k].data(), w, h, 0, (size_t)w);
+      if (last_status_ != VSF_OK) return false;
+    }
+    // (the odometry gate above is asked again inside and answers the same: nothing it reads has changed)
+    return ObserveImage(Image(resized_[0].data(), h, w, (size_t)w), Image(resized_[1].data(), h, w, (size_t)w), 0.0);
+  }
   Frame curr_frame, right_temp_frame;
   if (!ExtractFeaturesPair(left_image, right_image, &curr_frame, &right_temp_frame)) return false;
   const std::vector<vsf_dmatch> stereo_matches = GetMatches(curr_frame, right_temp_frame, config_.nn_match_ratio_);
@@ -1116,6 +1159,18 @@ void Frontend::set_debug_jpeg_quality(int quality) {
   }
   config_.debug_jpeg_quality_ = quality;
   if (ctx_ && (config_.debug_images_ || quality == 0)) last_status_ = vsf_observe_set_debug_jpeg(ctx_, quality);
+}
+
+void Frontend::set_resize(int width, int height, int camera_width, int camera_height) {
+  const bool off = width == 0 && height == 0;
+  last_status_ = off || (width >= 1 && height >= 1 && width <= 32767 && height <= 32767) ? VSF_OK : VSF_ERR_INVALID_ARG;
+  if (last_status_ != VSF_OK) return;
+  config_.resize_width_ = width;
+  config_.resize_height_ = height;
+  if (camera_width > 0 && camera_height > 0) {
+    config_.image_width = camera_width;
+    config_.image_height = camera_height;
+  }
 }
 
 void Frontend::set_imdecode_reduce(int reduce) {
@@ -1280,8 +1335,8 @@ FrontendGroup::FrontendGroup(const std::vector<FrontendConfig>& configs, int dev
     }
   for (const FrontendConfig& c : configs)  // what the one context is built with
     if (c.orb_nfeatures != lead.orb_nfeatures || c.nn_match_ratio_ != lead.nn_match_ratio_ ||
-        c.residual_order != lead.residual_order || c.frame_life_ != lead.frame_life_ || c.image_width != lead.image_width ||
-        c.image_height != lead.image_height || c.visualization_ != lead.visualization_ || c.debug_images_ != lead.debug_images_ ||
+        c.residual_order != lead.residual_order || c.frame_life_ != lead.frame_life_ || ContextWidth(c) != ContextWidth(lead) ||
+        ContextHeight(c) != ContextHeight(lead) || c.visualization_ != lead.visualization_ || c.debug_images_ != lead.debug_images_ ||
         c.debug_jpeg_quality_ != lead.debug_jpeg_quality_ || c.debug_png_ != lead.debug_png_ ||
         c.debug_colour_seeded_ != lead.debug_colour_seeded_) {
       last_status_ = VSF_ERR_INVALID_ARG;
@@ -1292,7 +1347,7 @@ FrontendGroup::FrontendGroup(const std::vector<FrontendConfig>& configs, int dev
     if (last_status_ == VSF_OK) last_status_ = members_.back()->last_status_;
   }
   ready_ = true;
-  if (last_status_ == VSF_OK && lead.image_width > 0 && lead.image_height > 0) EnsureContext(lead.image_width, lead.image_height);
+  if (last_status_ == VSF_OK && ContextWidth(lead) > 0 && ContextHeight(lead) > 0) EnsureContext(ContextWidth(lead), ContextHeight(lead));
 }
 
 // (frames in flight are dropped, as a Frontend's are; the first member owns the context)
@@ -1363,6 +1418,7 @@ bool FrontendGroup::EnsureContext(int width, int height) {
       m->ctx_depth_ = lead.ctx_depth_;
       m->pending_.assign((size_t)(lead.ctx_depth_ > 0 ? lead.ctx_depth_ : 1), Frontend::PendingFrame());
       m->pending_head_ = m->pending_count_ = 0;
+      m->declared_w_ = m->declared_h_ = 0;
     }
   }
   if (!ok)

@@ -104,6 +104,15 @@ struct FrontendConfig {
   // (VSF_ERR_INVALID_ARG: a mosaic cannot be reduced in the DCT domain).  In a FrontendGroup it is per member: a 1280 x 960
   // camera at 2 and a 640 x 480 camera at 1 share one 640 x 480 context.
   int imdecode_reduce_;
+  // An addition: cv::resize(img, Size(resize_width_, resize_height_)) in front of everything (0 x 0, the default: off).  When
+  // set, the object's context has THAT size and ObserveImage / ObserveDeviceImage / ObserveCompressedImage take frames of the
+  // camera's own size, whatever it is: the queue declares it to the object's stream (vsf_observe_set_input_size) and resizes
+  // on the device inside the batch; per-call mode resizes through vsf_resize_gray.  A frame of another size than the one
+  // before books what is in flight, then re-declares.  The calibration is the caller's, for the RESIZED image.  Device frames
+  // have no size of their own: image_width x image_height states the camera's.  With imdecode_reduce_ > 1 as well, compressed
+  // frames are refused (VSF_ERR_INVALID_ARG: the two are not combined).  In a FrontendGroup the field is per member; the
+  // resized size -- the context's -- is what the members must agree on.
+  int resize_width_, resize_height_;
   // An addition: bytes one compressed payload may have (vsf_observe_set_compressed_cap), applied when the context is created.
   // 0 (the default): the library's, width x height + 64 KB OF THE CONTEXT'S SIZE -- with imdecode_reduce_ > 1 that is the
   // REDUCED size, and a camera's files of N times the side are usually larger: set this (vsf_observe_default_compressed_cap of
@@ -135,6 +144,9 @@ struct FrontendConfig {
 
 // FrontendConfig's stereo calibration in the layout of the C ABI (include/vsf.h vsf_calibration).
 vsf_calibration MakeCalibration(const FrontendConfig& config);
+// The size of the context a configuration asks for: resize_width_ x resize_height_ where set, else image_width x image_height.
+int ContextWidth(const FrontendConfig& config);
+int ContextHeight(const FrontendConfig& config);
 // config.left_cam_to_robot as the 3 x 4 row-major matrix the point cloud's calls take, and such a matrix as the transform.
 void CamToRobot(const FrontendConfig& config, float out[12]);
 Affine3f AffineFromRowMajor(const float m[12]);
@@ -265,6 +277,10 @@ class Frontend {
   // config.imdecode_reduce_ (1, 2, 4, 8; anything else: VSF_ERR_INVALID_ARG and no change).  Legal at any time: it is read by
   // each ObserveCompressedImage; the image size stays what the first frame made it.
   void set_imdecode_reduce(int reduce);
+  // config.resize_width_ / resize_height_ (0, 0: off; one side 0 or a side above 32767: VSF_ERR_INVALID_ARG and no change);
+  // camera_width x camera_height > 0: config.image_width / image_height as well (what device frames are taken to be).
+  // Before the first frame, or at any time: the next frame sizes the context and declares its own size.
+  void set_resize(int width, int height, int camera_width = 0, int camera_height = 0);
   // config.compressed_cap_.  Before the first compressed frame, or while no frame is in flight (vsf_observe_set_compressed_cap's
   // rule; otherwise last_status() says VSF_ERR_INVALID_ARG and nothing changes on the device).
   void set_compressed_cap(size_t cap_per_image);
@@ -339,7 +355,14 @@ class Frontend {
     int reduce = 1;  // compressed: config.imdecode_reduce_ at the call
     void* hip_stream = nullptr;
   };
+  // (width x height: the frame's own size -- the context's, or the camera's with config.resize_width_ / resize_height_ set)
   bool ObserveFused(int width, int height, const FramePayload& fp);
+  bool resizing() const { return config_.resize_width_ > 0 && config_.resize_height_ > 0; }
+  // What the object's stream has been told its frames' size is (0 x 0: the context's): vsf_observe_set_input_size, with what
+  // is in flight booked first.  (A new context starts at 0 x 0.)
+  bool DeclareInput(int width, int height);
+  int declared_w_ = 0, declared_h_ = 0;
+  std::vector<uint8_t> resized_[2];  // per-call mode: the two resized images
   void FinishNode(const Frame& curr_frame, const std::vector<slam_types::VisionFeature>& features);
   // visualization_: the newest node and the factors booked with it (vision factors from index `first_vision_factor`) join the
   // pose-graph lists; points [xyz, xyz + 3 n) -- the node's, made on the device -- join the cloud.
