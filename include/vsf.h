@@ -186,7 +186,12 @@ typedef enum {
                                    * cell; read by every call, so it may change between two calls */
   VSF_OPT_FAST_EARLY_FORM = 12,   /* that early launch as a grid of one workgroup per four cells (0) or as one resident
                                    * workgroup per CU with 1 .. 3 waves per SIMD; default 0 */
-  VSF_OPT_COUNT = 13
+  VSF_OPT_BLUR_EARLY = 13,        /* pipelined calls of 32 images or more: 1 (default) = the call's blur is queued behind its
+                                   * pyramid chain on that chain's stream, into the other of two blurred pyramids: it starts
+                                   * beside the end of the PREVIOUS call's matcher, before the call's own stream has reached its
+                                   * FAST; 0: forked from the call's own stream, beside its FAST.  Read by every call, so it
+                                   * may change between two calls */
+  VSF_OPT_COUNT = 14
 } vsf_option;
 vsf_status vsf_set_option(vsf_ctx* ctx, int option, int value);
 vsf_status vsf_get_option(const vsf_ctx* ctx, int option, int* value);

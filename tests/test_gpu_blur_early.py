@@ -1,0 +1,138 @@
+"""VSF_OPT_BLUR_EARLY on the GPU: the blur of a pipelined call of 32 images or more is queued behind the call's pyramid chain
+on the pipe stream, into the other of two blurred pyramids, and is not ordered behind the PREVIOUS call's descriptors, which
+may still read theirs (csrc/vsf_blur_plan.h, csrc/vsf_api.hip extract_on).  Nothing a call returns may depend on it:
+
+* five consecutive pipelined vsf_stereo_batch_dev calls on five different image sets with the option 1 throughout, toggled
+  1, 0, 1, 1, 0, with every call's images produced late on another stream and handed over by vsf_set_input_event, with a
+  16-image call (which keeps the blur on its own stream and buffer 0) in the middle of the pipelined sequence, and with that
+  call made with pipelining switched off around it -- keypoints, descriptors, counts (and the stereo matches) of EVERY call
+  byte for byte what the same calls give on a fresh context that never pipelines;
+* debug_level_image(i, l, True) after the last call against the CPU oracle, every level of the first and the last image: the
+  hook follows the buffer the last call wrote.
+
+Shape: 32 images (16 stereo frames, the smallest batch whose blur runs beside other stages) of 160x120, 300 features, in the
+50-level / 1.04 and the 8-level / 1.2 pyramids."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+W, H, B, NF = 160, 120, 16, 300
+CALLS = 5
+SMALL = 8  # frames of the 16-image call
+NAMES = ("kp", "desc", "counts", "matches", "nmatches")
+PYRAMIDS = [(50, 1.04), (8, 1.2)]
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from vision_slam_frontend_amd import capi
+    capi.lib()
+    return capi
+
+
+@pytest.fixture(scope="module")
+def sets():
+    from vision_slam_frontend_amd import synth
+    return [synth.bench_batch(B, W, H, seed=synth.BASE_SEED + 170 + k, n_scenes=4) for k in range(CALLS)]
+
+
+def _sequence(capi, sets, pyramid, option, pipeline=True, small_at=None, small_unpipelined=False, events=False, levels_of=()):
+    """The CALLS calls, `option`: VSF_OPT_BLUR_EARLY for every call or one value per call; small_at: a call of the first SMALL
+    frames of set `small_at` goes in front of call `small_at`.  -> per call the five output arrays (the small call's under
+    the key "small"), and {(image, level): blurred level} of the LAST call for the images in levels_of."""
+    import torch
+    dev = torch.device("cuda", 0)
+    nlevels, scale = pyramid
+    with capi.Context(capi.default_params(W, H, max_images=2 * B, nfeatures=NF, nlevels=nlevels, scale_factor=scale)) as ctx:
+        K = ctx.params.max_keypoints
+
+        def outputs(frames):
+            return (torch.zeros((2 * frames, K, 28), dtype=torch.uint8, device=dev),
+                    torch.zeros((2 * frames, K, 32), dtype=torch.uint8, device=dev),
+                    torch.zeros(2 * frames, dtype=torch.int32, device=dev), torch.zeros((frames, K, 16), dtype=torch.uint8, device=dev),
+                    torch.zeros(frames, dtype=torch.int32, device=dev))
+
+        host = [torch.from_numpy(np.ascontiguousarray(f)) for f in sets]
+        d_img = [torch.zeros_like(h, device=dev) if events else h.to(dev) for h in host]
+        outs = {c: outputs(B) for c in range(CALLS)}
+        outs["small"] = outputs(SMALL)
+        producer = torch.cuda.Stream(dev) if events else None
+        ready = [torch.cuda.Event() for _ in range(CALLS)] if events else None
+        staged = [h.pin_memory() for h in host] if events else None
+        filler = torch.ones((2048, 2048), device=dev) if events else None
+        torch.cuda.synchronize()
+        ctx.set_pipeline(pipeline)
+        per_call = list(option) if isinstance(option, (list, tuple)) else [option] * CALLS
+        for c in range(CALLS):
+            if small_at == c:
+                if small_unpipelined:
+                    ctx.set_pipeline(False)
+                ctx.stereo_batch_dev(d_img[c].data_ptr(), SMALL, W * H, W, *[t.data_ptr() for t in outs["small"]])
+                if small_unpipelined:
+                    ctx.set_pipeline(True)
+            ctx.set_option(capi.OPT_BLUR_EARLY, per_call[c])
+            assert ctx.get_option(capi.OPT_BLUR_EARLY) == per_call[c]
+            if events:  # the images arrive late, on another stream; the call learns of them through the event alone
+                with torch.cuda.stream(producer):
+                    for _ in range(40):
+                        filler.mul_(1.0001)
+                    d_img[c].copy_(staged[c], non_blocking=True)
+                    ready[c].record(producer)
+                ctx.set_input_event(ready[c].cuda_event)
+            ctx.stereo_batch_dev(d_img[c].data_ptr(), B, W * H, W, *[t.data_ptr() for t in outs[c]])
+        assert ctx.sync() == capi.VSF_OK
+        torch.cuda.synchronize()
+        blurred = {(i, l): ctx.debug_level_image(i, l, True) for i in levels_of for l in range(ctx.nlevels)}
+        res = {k: [t.cpu().numpy() for t in o] for k, o in outs.items()}
+    return res, blurred
+
+
+_refs = {}
+
+
+def _reference(capi, sets, pyramid):
+    """the same calls, the 16-image one (on set 2) included, on a fresh context that never pipelines: computed once"""
+    if pyramid not in _refs:
+        _refs[pyramid] = _sequence(capi, sets, pyramid, 0, pipeline=False, small_at=2)[0]
+    return _refs[pyramid]
+
+
+def _same(ref, got, what, small=False):
+    for c in list(range(CALLS)) + (["small"] if small else []):
+        for name, a, b in zip(NAMES, ref[c], got[c]):
+            assert a.tobytes() == b.tobytes(), "%s: call %s: %s differs" % (what, c, name)
+    assert int(got[0][2].min()) > 20, "the scene gives too few keypoints to tell anything"
+
+
+@pytest.mark.parametrize("pyramid", PYRAMIDS)
+@pytest.mark.parametrize("option", [1, (1, 0, 1, 1, 0)], ids=["on", "toggled"])
+def test_byte_identity(capi, sets, pyramid, option):
+    got, _ = _sequence(capi, sets, pyramid, option)
+    _same(_reference(capi, sets, pyramid), got, "option %r, pyramid %r" % (option, pyramid))
+
+
+@pytest.mark.parametrize("pyramid", PYRAMIDS)
+def test_byte_identity_with_input_events(capi, sets, pyramid):
+    got, _ = _sequence(capi, sets, pyramid, 1, events=True)
+    _same(_reference(capi, sets, pyramid), got, "input events, pyramid %r" % (pyramid,))
+
+
+@pytest.mark.parametrize("pyramid", PYRAMIDS)
+@pytest.mark.parametrize("unpipelined", [False, True], ids=["small", "small-unpipelined"])
+def test_byte_identity_with_a_16_image_call_in_the_middle(capi, sets, pyramid, unpipelined):
+    got, _ = _sequence(capi, sets, pyramid, 1, small_at=2, small_unpipelined=unpipelined)
+    _same(_reference(capi, sets, pyramid), got, "16-image call in the middle, pyramid %r" % (pyramid,), small=True)
+
+
+@pytest.mark.parametrize("pyramid", PYRAMIDS)
+def test_blurred_levels_of_the_last_call_against_the_oracle(capi, oracle, sets, pyramid):
+    images = (0, 2 * B - 1)
+    _, blurred = _sequence(capi, sets, pyramid, 1, levels_of=images)
+    nlevels, scale = pyramid
+    frames = sets[CALLS - 1]
+    for image in images:
+        o = oracle.Orb(nfeatures=NF, nlevels=nlevels, scale_factor=scale)
+        o.run(frames[image // 2, image & 1])
+        for l in range(nlevels):
+            np.testing.assert_array_equal(blurred[(image, l)], o.level_image(l, True), err_msg="image %d level %d" % (image, l))

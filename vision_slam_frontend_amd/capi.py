@@ -56,7 +56,7 @@ EXPORTS = [
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
  OPT_PIPE_AFTER_FAST, OPT_PIPE_PRIORITY, OPT_OBSERVE_THREAD, OPT_PYRAMID_TAIL_MIN, OPT_OBSERVE_COPY_THREAD,
- OPT_FAST_EARLY_LEVELS, OPT_FAST_EARLY_FORM) = range(13)
+ OPT_FAST_EARLY_LEVELS, OPT_FAST_EARLY_FORM, OPT_BLUR_EARLY) = range(14)
 STAGE_COUNT = 8
 # vsf_observe_stats' values, in order (include/vsf.h)
 OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits", "depth", "bmax", "copy_ns", "launch_ns",

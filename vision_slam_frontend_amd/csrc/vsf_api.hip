@@ -213,6 +213,30 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
   im.base += (size_t)i0 * im.image_stride;
   im.n = n;
   const size_t K = (size_t)ctx->p.max_keypoints;
+  // The blur runs beside other stages in batches of 32 images or more (the comment above `resident` below).  Where, into
+  // which of the two blurred pyramids, behind which release: vsf_blur_plan.h.  VSF_OPT_BLUR_EARLY (read here, per call)
+  // makes a pipelined call of that kind VSF_BLUR_EARLY; the tune call, smaller batches, two lanes and own_side extractions
+  // keep the fork beside FAST and buffer 0.
+  const bool beside_ok = ctx->blur_overlap && im.n >= 32 && ctx->blur_stream;
+  const bool blur_early = pipe && beside_ok && ctx->tuning.blur_early && ctx->blur_alt && ctx->fast_force < 0 && !own_side;
+  const VsfBlurKind blur_kind = blur_early                                      ? VSF_BLUR_EARLY
+                                : st == ctx->stream                             ? VSF_BLUR_MAIN
+                                : ctx->lanes == 2 && st == ctx->aux_stream.get() ? VSF_BLUR_LANE
+                                                                                : VSF_BLUR_OWN;
+  const VsfBlurPlan bp = vsf_blur_plan(&ctx->blur_plan, blur_kind, (bool)ctx->blur_alt);
+  if (bp.buf) d.blur = ctx->blur_alt.get() + (size_t)i0 * g.pyr_bytes;
+  if (blur_kind != VSF_BLUR_LANE) ctx->last_blur = bp.buf ? ctx->blur_alt.get() : ctx->dorb.d.blur;
+  auto launch_blur = [&](hipStream_t bs) {
+    // ... not before the descriptors that last read this buffer are through, where stream order does not say so already
+    if (bp.wait_free) vsf_note(hipStreamWaitEvent(bs, ctx->ev_blur_free[bp.buf], 0));
+    StageTimer t(ctx, bs, VSF_STAGE_BLUR, 1);
+    if (im.n >= 32)
+      vsf_launch_blur_mma(d, g, im, ctx->dorb.blur_mma_units, (int)ctx->orb.blur_mma_units.size(), ctx->dorb.blur_tcol,
+                          ctx->dorb.blur_tv, ctx->orb.blur_bias, bs);
+    else
+      vsf_launch_blur_mma(d, g, im, ctx->dorb.blur_mma_units_small, (int)ctx->orb.blur_mma_units_small.size(),
+                          ctx->dorb.blur_tcol, ctx->dorb.blur_tv, ctx->orb.blur_bias, bs);
+  };
   if (pipe) {
     // The pyramid depends on the input images only.  The caller promised they are complete (vsf_set_pipeline), so the
     // chain goes onto the pipe streams WITHOUT being ordered after this stream's earlier work and overlaps the previous
@@ -266,6 +290,17 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
     if (n_early > 0 && !early.fired) hook.fn(&early, ps);  // (no launch of the chain made that level: behind all of it)
     vsf_note(hipEventRecord(ctx->ev_pyr_done, ps));
     vsf_note(hipStreamWaitEvent(st, ctx->ev_pyr_done, 0));
+    // VSF_BLUR_EARLY: the blur follows the chain in stream order instead of being forked from the main stream together with
+    // FAST.  The chain fills the whole of the previous call's selection -> descriptors -> matcher (48 launches, 3.35 ms beside
+    // them against 1.28 ms alone), so the blur starts where those end: 0.1 ms before the matcher is through and 0.2 ms before the
+    // main stream reaches the late FAST part, and it is through when FAST is (5.61-5.73 -> 5.56-5.61 ms per 256-frame step;
+    // NOTES.md "Blur: behind the pipelined pyramid chain").  Not on blur_stream: the early FAST launch lives there and the
+    // blur would wait behind it.  The next call's chain on this stream waits for this call's FAST anyway (traced: the blur
+    // ends with FAST or just before it), so the blur in front of it delays nothing.
+    if (blur_early) {
+      launch_blur(ps);
+      vsf_note(hipEventRecord(ctx->ev_blur_done, ps));
+    }
   } else {
     StageTimer t(ctx, st, VSF_STAGE_PYRAMID, g.nlevels - 1);
     // one lane: the aux stream is idle, the pyramid chain of the second half of the batch runs on it
@@ -288,7 +323,12 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
   // step).  Left out: fewer levels (1 / 2 / 4 / 8: 5.81 / 5.84 / 5.73 / 5.66 ms) or all 20 (5.67); that early part as a
   // resident launch of one, two or three waves per SIMD (5.72-5.95: it does not finish before the pyramid does, and the
   // late part waits for it).
-  const bool beside_ok = ctx->blur_overlap && im.n >= 32 && ctx->blur_stream;
+  // Measured and KEPT (NOTES.md, "Blur: behind the pipelined pyramid chain"): the blur of a pipelined call queued behind its
+  // chain on the pipe stream, into the other blurred pyramid (VSF_OPT_BLUR_EARLY, above: 5.61-5.73 -> 5.56-5.61 ms).  What
+  // was hoped for -- the blur beside the previous call's descriptors and matcher, FAST alone in its phase -- did not
+  // happen: the chain ends when that phase does, and that phase is full (everything in it runs at half its own rate).
+  // With that blur: 0 / 4 / 8 / 20 early levels 5.76-5.90 / 5.66-5.68 / 5.57-5.65 / 5.61-5.63 ms against 5.52-5.56 at
+  // 12; the late part resident with three waves 5.69-5.71, the tune call picks the grid.
   // With the blur beside it FAST can run as ONE resident workgroup per CU (k_fast.hip): three waves per SIMD keep 92 % of
   // its own rate and leave the other 224 of a SIMD's 512 registers -- which a grid of one workgroup per four cells fills
   // for as long as cells are left -- to the blur, which then finishes INSIDE the FAST pass instead of after it.  Whether
@@ -309,22 +349,13 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
       resident = ctx->fast_tune.choice;
   }
   const bool blur_beside = beside_ok;
-  auto launch_blur = [&](hipStream_t bs) {
-    StageTimer t(ctx, bs, VSF_STAGE_BLUR, 1);
-    if (im.n >= 32)
-      vsf_launch_blur_mma(d, g, im, ctx->dorb.blur_mma_units, (int)ctx->orb.blur_mma_units.size(), ctx->dorb.blur_tcol,
-                          ctx->dorb.blur_tv, ctx->orb.blur_bias, bs);
-    else
-      vsf_launch_blur_mma(d, g, im, ctx->dorb.blur_mma_units_small, (int)ctx->orb.blur_mma_units_small.size(),
-                          ctx->dorb.blur_tcol, ctx->dorb.blur_tv, ctx->orb.blur_bias, bs);
-  };
   auto fork_blur = [&]() {
     vsf_note(hipEventRecord(ctx->ev_blur_fork, st));
     vsf_note(hipStreamWaitEvent(ctx->blur_stream, ctx->ev_blur_fork, 0));
     launch_blur(ctx->blur_stream);
     vsf_note(hipEventRecord(ctx->ev_blur_done, ctx->blur_stream));
   };
-  if (blur_beside) fork_blur();  // (on blur_stream behind the early FAST part: stream order)
+  if (blur_beside && !blur_early) fork_blur();  // (on blur_stream behind the early FAST part: stream order)
   if (n_early > 0) vsf_note(hipStreamWaitEvent(st, ctx->ev_early_done, 0));
   {
     StageTimer t(ctx, st, VSF_STAGE_FAST, 1);
@@ -352,6 +383,7 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
     vsf_launch_describe(d, g, im, ctx->p.max_keypoints, d_kp + i0 * K, d_desc + i0 * K * VSF_DESC_BYTES, d_counts + i0,
                         st);
   }
+  if (bp.record_free) vsf_note(hipEventRecord(ctx->ev_blur_free[bp.buf], st));  // the only reader of this blurred pyramid is queued
   if (pipe) {  // every reader of this pyramid buffer is queued: the call after the next may overwrite it
     const int buf = ctx->pyr_flip;
     vsf_note(hipEventRecord(ctx->ev_pyr_free[buf], st));
@@ -430,6 +462,10 @@ vsf_status ensure_pipeline_buffers(vsf_ctx* ctx) {
   VSF_HIP(ctx->ev_pyr_done.alloc(hipEventDisableTiming));
   VSF_HIP(ctx->ev_fast_done.alloc(hipEventDisableTiming));
   for (Event& e : ctx->ev_pyr_free) VSF_HIP(e.alloc(hipEventDisableTiming));
+  // the other blurred pyramid and the releases of both (VSF_OPT_BLUR_EARLY, vsf_blur_plan.h); the buffer last: a context
+  // that has blur_alt has the events
+  for (Event& e : ctx->ev_blur_free) VSF_HIP(e.alloc(hipEventDisableTiming));
+  VSF_HIP(ctx->blur_alt.alloc((size_t)ctx->p.max_images * ctx->orb.g.pyr_bytes));
   return VSF_OK;
 }
 
@@ -674,6 +710,7 @@ vsf_status vsf_set_option(vsf_ctx* ctx, int option, int value) {
       if (value < 0 || value > 3) return VSF_ERR_INVALID_ARG;
       t.fast_early_form = value;
       break;
+    case VSF_OPT_BLUR_EARLY: t.blur_early = value != 0; break;  // (read by each call)
     case VSF_OPT_OBSERVE_THREAD: t.observe_thread = value != 0; break;  // (read when the queue is built)
     case VSF_OPT_OBSERVE_COPY_THREAD: t.observe_copy_thread = value != 0; break;
     case VSF_OPT_PIPE_PRIORITY:
@@ -712,6 +749,7 @@ vsf_status vsf_get_option(const vsf_ctx* ctx, int option, int* value) {
     case VSF_OPT_PIPE_AFTER_FAST: *value = t.pipe_after_fast; break;
     case VSF_OPT_FAST_EARLY_LEVELS: *value = t.fast_early_levels; break;
     case VSF_OPT_FAST_EARLY_FORM: *value = t.fast_early_form; break;
+    case VSF_OPT_BLUR_EARLY: *value = t.blur_early; break;
     case VSF_OPT_OBSERVE_THREAD: *value = t.observe_thread; break;
     case VSF_OPT_OBSERVE_COPY_THREAD: *value = t.observe_copy_thread; break;
     case VSF_OPT_PIPE_PRIORITY: *value = t.pipe_priority; break;
@@ -748,6 +786,7 @@ vsf_status vsf_set_pipeline(vsf_ctx* ctx, int on) {
   ctx->pipeline = on != 0;
   ctx->pyr_free_valid[0] = ctx->pyr_free_valid[1] = false;
   ctx->cand_free_valid[0] = ctx->cand_free_valid[1] = false;
+  // (blur_plan keeps its releases: a reader of buffer 0 may sit on a stream that was not waited for here)
   ctx->fast_done_valid = false;
   return VSF_OK;
 }

@@ -10,6 +10,7 @@
 #include <memory>
 #include <vector>
 
+#include "vsf_blur_plan.h"
 #include "vsf_internal.h"
 #include "vsf_observe_plan.h"
 #include "vsf_observe_queue.h"
@@ -90,6 +91,14 @@ struct vsf_ctx {
   int cand_flip = 0;
   vsfi::Event ev_cand_free[2], ev_early_go, ev_early_done;
   bool cand_free_valid[2] = {false, false};
+  // ... and its blur (VSF_OPT_BLUR_EARLY) follows that chain on the same stream, not ordered behind call k's descriptors: it
+  // writes the other of two blurred pyramids (dorb.blur / blur_alt) while call k's descriptors may still read theirs.  Which
+  // buffer, and which release a call waits for and records: vsf_blur_plan.h from `blur_plan` (.flip is blur_flip: the buffer
+  // the LAST call's blur wrote; .free_valid is blur_free_valid).  ev_blur_free[i]: behind the descriptors that last read
+  // buffer i, the only reader.  last_blur: that buffer, for the debug hooks.
+  VsfBlurState blur_plan;
+  vsfi::Event ev_blur_free[2];
+  const uint8_t* last_blur = nullptr;
   // A producer the library owns (the Bayer ingest) records this on the context's stream; a pipelined pyramid, which is
   // NOT ordered after that stream's earlier work, waits for it.
   vsfi::Event ev_ingest_done;
@@ -282,6 +291,7 @@ struct vsf_ctx {
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----
   vsfi::DevBuf<uint8_t> pyr_alt;  // the other pyramid buffer of cross-call pipelining
+  vsfi::DevBuf<uint8_t> blur_alt;  // ... and the other blurred pyramid (buffer 1 of vsf_blur_plan.h; buffer 0 is dorb.blur)
   vsfi::DevBuf<uint32_t> cand_alt;      // ... and the other pair of FAST's candidate segments and row-start tables
   vsfi::DevBuf<uint16_t> rowstart_alt;  //     (pair 0 is dorb.cand / dorb.rowstart)
   vsfi::Geometry orb, fast;

@@ -149,7 +149,7 @@ vsf_status vsf_debug_level_image(vsf_ctx* ctx, int image, int level, int blurred
     src = ctx->last_images.base + (size_t)image * ctx->last_images.image_stride;
     pitch = ctx->last_images.row_stride;
   } else {
-    src = (blurred ? ctx->dorb.d.blur : (ctx->last_pyr ? ctx->last_pyr : ctx->dorb.d.pyr)) +
+    src = (blurred ? (ctx->last_blur ? ctx->last_blur : ctx->dorb.d.blur) : (ctx->last_pyr ? ctx->last_pyr : ctx->dorb.d.pyr)) +
           (size_t)image * ctx->orb.g.pyr_bytes + L.offset;
     pitch = (size_t)L.pitch;
   }

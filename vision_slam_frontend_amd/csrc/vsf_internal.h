@@ -103,6 +103,9 @@ struct VsfTuning {
                                // inside its pyramid chain, beside the previous call's selection / descriptors (0: one FAST pass;
                                // 12, as a grid: NOTES.md "FAST: the wide levels start beside the previous call")
   int fast_early_form = 0;    // VSF_OPT_FAST_EARLY_FORM: that early launch as a grid (0) or resident with 1..3 waves per SIMD
+  int blur_early = 1;         // VSF_OPT_BLUR_EARLY: 1 = a pipelined call's blur follows its pyramid chain on the pipe stream, in front of
+                              // its late FAST part, into the other blurred pyramid; 0: forked from the main stream beside FAST
+                              // (NOTES.md "Blur: behind the pipelined pyramid chain")
   int jpeg_serial = 0;     // 1: every file through the one-wave-per-image decoder (set when the parallel decoder's LDS is refused)
   int pyramid_few = 16;    // VSF_OPT_PYRAMID_FEW: largest batch (images) that takes the slab kernel for every level
   int pyramid_chain = 8;   // VSF_OPT_PYRAMID_CHAIN: levels per slab launch (0: keep the per-level launches)
