@@ -63,7 +63,13 @@ typedef struct {
 typedef struct {
   /* --- cv::ORB::create arguments (reference literals slam_frontend.cc:205-213) --- */
   int32_t nfeatures;      /* 10000 in the reference; BASELINE configs use 2000 / 8000 */
-  float scale_factor;     /* 1.04f */
+  /* 1.04f.  Any value > 1 whose pyramid the resize kernels can build: for every level l >= 1, with cv::resize's own
+   * INTER_LINEAR taps from level l - 1, the taps of each group of four adjacent output pixels must lie inside one
+   * 8-byte window of the source row (ratios w(l-1) / w(l) up to about 2: 640 -> 320 fits, 333 -> 166 = 2.006 does not,
+   * 2.5 never does), and level l - 1 must be at least 8 pixels wide.  vsf_create returns VSF_ERR_INVALID_ARG otherwise;
+   * nothing is computed approximately.  Above 1 + 1/7 no level shares source rows between output rows any more: the
+   * frame-latency chain and the image-major tail are not taken, every level is one launch of the general resize kernel. */
+  float scale_factor;
   int32_t nlevels;        /* 50 (<= VSF_MAX_LEVELS) */
   int32_t edge_threshold; /* 31 */
   int32_t first_level;    /* 0 (only value supported) */
@@ -959,6 +965,11 @@ vsf_status vsf_debug_fast_work(const vsf_params* p, int orb, int nms, uint32_t* 
 /* Final per-level keypoints in level coordinates (after both retainBest cuts, with angle). */
 vsf_status vsf_debug_level_keypoints(vsf_ctx* ctx, int image, int level, vsf_keypoint* kp_out, int cap,
                                      int* n_out);
+/* Which form of the describe kernel ONE launch over n_images images takes in this context: 4 or 8 consecutive output
+ * keypoints per wave (a batched call is one launch with one lane, one launch per half with two: vsf_set_lanes).  The
+ * launcher's own choice, read back; VSF_ERR_INVALID_ARG (1) for a null context or n_images < 1.  n_images may exceed
+ * max_images: a small context with the same max_keypoints answers for a large one.  Host only, nothing is launched. */
+int vsf_debug_describe_form(const vsf_ctx* ctx, int n_images);
 /* Test hook of the order-exact selection (cv::KeyPointsFilter::retainBest as left by libstdc++'s nth_element +
  * partition): applies retainBest(n_points) on the GPU to n (key, id) pairs given as two host arrays, in place.
  * mode 0: keys are float bit patterns compared as floats; mode 1: only the top byte of the key is compared

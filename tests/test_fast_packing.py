@@ -103,6 +103,12 @@ def test_standalone_fast_cells_packed_once(capi, w, h, nms):
     check(levels, full, packs)
 
 
+# pyramids steeper than 1.2 (every level is built by the general resize kernel; tests/test_gpu_pyramid_scales.py)
+STEEP = (dict(nlevels=6, scale_factor=1.34), dict(nlevels=5, scale_factor=1.5), dict(nlevels=4, scale_factor=1.7),
+         dict(nlevels=4, scale_factor=2.0))
+STEEP_SIZES = ((640, 480), (267, 203), (97, 61))
+
+
 def test_other_pyramids(capi):
     for kw in (dict(nlevels=8, scale_factor=1.2), dict(nlevels=1), dict(nlevels=20, scale_factor=1.1)):
         for w, h in ((640, 480), (333, 257), (1920, 1080)):
@@ -111,6 +117,26 @@ def test_other_pyramids(capi):
                 setattr(p, k, v)
             full, packs, levels = work(capi, p)
             check(levels, full, packs)
+    for kw in STEEP:
+        for w, h in STEEP_SIZES + ((333, 217),) * (kw["scale_factor"] == 1.7):
+            p = capi.default_params(w, h)
+            for k, v in kw.items():
+                setattr(p, k, v)
+            full, packs, levels = work(capi, p)
+            assert len(levels) == kw["nlevels"]
+            check(levels, full, packs)
+
+
+@pytest.mark.parametrize("w,h,nlevels,scale", [(333, 217, 4, 2.0), (640, 480, 3, 2.5)])
+def test_refused_pyramids(capi, w, h, nlevels, scale):
+    """A level whose four-pixel x-tap groups do not fit the 8-byte source window (333 -> 166 is a ratio of 2.006; 2.5 never
+    fits) is refused as a whole, not computed some other way."""
+    p = capi.default_params(w, h)
+    p.nlevels, p.scale_factor = nlevels, scale
+    nw, nf = C.c_int(), C.c_int()
+    words = np.zeros(1 << 16, np.uint32)
+    st = capi.lib().vsf_debug_fast_work(C.byref(p), 1, 1, words.ctypes.data, len(words), C.byref(nw), C.byref(nf), None, 0)
+    assert st == capi.VSF_ERR_INVALID_ARG
 
 
 def test_sweep_reaches_short_last_strips_and_mixed_waves(capi):

@@ -52,6 +52,7 @@ EXPORTS = [
     "vsf_observe_submit_compressed_reduced", "vsf_observe_stereo_compressed_reduced",
     "vsf_observe_set_debug_seeds", "vsf_observe_set_stream_cam_to_robot",
     "vsf_resize_gray_batch_dev", "vsf_observe_set_input_size", "vsf_resize_gray",
+    "vsf_debug_describe_form",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -340,6 +341,7 @@ def lib() -> C.CDLL:
         L.vsf_debug_fast_candidates.argtypes = [vp, i32, i32, vp, i32, ip]
         L.vsf_debug_fast_work.argtypes = [vp, i32, i32, vp, i32, ip, ip, vp, i32]
         L.vsf_debug_level_keypoints.argtypes = [vp, i32, i32, vp, i32, ip]
+        L.vsf_debug_describe_form.argtypes = [vp, i32]
         L.vsf_algorithmic_bytes_per_image.argtypes = [vp]
         L.vsf_algorithmic_bytes_per_image.restype = C.c_uint64
         L.vsf_pyramid_pixels.argtypes = [vp]
@@ -1057,6 +1059,13 @@ class Context:
         self._check(lib().vsf_debug_fast_candidates(self._h, image, level, _p(kp), cap, C.byref(n)),
                     "vsf_debug_fast_candidates")
         return kp[:min(n.value, cap)]
+
+    def debug_describe_form(self, n_images: int) -> int:
+        """Keypoints per wave (4 or 8) of the describe kernel one launch over n_images images takes (vsf_debug_describe_form)."""
+        form = lib().vsf_debug_describe_form(self._h, int(n_images))
+        if form not in (4, 8):
+            raise VsfError(form, "vsf_debug_describe_form")
+        return form
 
     def debug_level_keypoints(self, image: int, level: int, cap: int = 1 << 15) -> np.ndarray:
         kp = np.zeros(cap, KEYPOINT_DTYPE)

@@ -12,7 +12,7 @@
 //       = pair 8k+i, LSB first, exactly OpenCV's packing).  Per sample: x = px*a - py*b, y = px*b + py*a as
 //       separately rounded float ops (no FMA), cvRound (round-half-even), one byte load.
 // Both run in one kernel over the image's keypoints in output order (level-major; a level's slot is the sum of the
-// preceding levels' counts), four consecutive keypoints per wave.
+// preceding levels' counts), four or eight consecutive keypoints per wave (vsf_describe_kp_per_wave, vsf_internal.h).
 #include <algorithm>
 
 #include "vsf_internal.h"
@@ -105,14 +105,16 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // Consecutive output keypoints per wave (template parameter KPW).  At 2000 keypoints per image, per 256-frame step: 2 -> 0.89
 // ms, 4 -> 0.83, 8 -> 0.85, 16 -> 0.89, 32 -> 0.97: the kernel lives on waves in flight, not on amortised prologues -- FOUR.
 // At the reference's 10 000 there are waves enough either way and the prologue counts: 8 -> 3.07 ms against 3.20 (the step
-// 11.77 -> 11.51 ms; at 2000 the step LOSES 2 % with 8) -- EIGHT for large batches of >= 4096 keypoints per image (the
-// launcher decides).
+// 11.77 -> 11.51 ms; at 2000 the step LOSES 2 % with 8) -- EIGHT for large batches of >= 4096 keypoints per image
+// (vsf_describe_kp_per_wave in vsf_internal.h decides; vsf_debug_describe_form reports it).
 
 // K6 + K8 + output assembly.  The image's keypoints are numbered in output order (level-major, retainBest order
-// inside a level); wave w of the image takes numbers [4 w, 4 w + 4), whatever levels they belong to: lane k < 4
-// looks up keypoint k's level (binary search in the wave-scanned level counts), record and level geometry once, and
-// the wave then walks its keypoints with v_readlane broadcasts.  (One workgroup per (level, image) left most waves
-// with two or three keypoints and a prologue longer than their work.)
+// inside a level); wave w of the image takes numbers [KPW w, KPW w + KPW), KPW = 4 or 8, whatever levels they belong to
+// (eight keypoints of sparse levels can span three or more): lane k < KPW looks up keypoint k's level (binary search in
+// the wave-scanned level counts), record and level geometry once, and the wave then walks its keypoints with v_readlane
+// broadcasts; the last wave of an image holds what is left (1 .. KPW) and its spare lanes repeat its last keypoint.
+// The prefetch chains (moments: one keypoint ahead; windows: the two-tile LDS ping-pong) are KPW steps long.  (One
+// workgroup per (level, image) left most waves with two or three keypoints and a prologue longer than their work.)
 template <int kKpPerWave>
 __global__ __launch_bounds__(256) void orb_orient_describe_kernel(DescribeArgs a) {
   constexpr int kWinRows = 39, kWinPitch = 64, kWinBytes = kWinRows * kWinPitch;
@@ -357,9 +359,7 @@ void vsf_launch_describe(const VsfDev& d, const VsfGeom& g, const VsfImages& im,
   a.counts = d_counts;
   a.status = d.status;
   a.status_stride = d.status_stride;
-  // (eight per wave needs a launch that still fills the chip with waves: 512 images x 10 000 keypoints; 64-192 images of
-  // 8 000 -- 1920x1080 -- run 1-2 % faster with four)
-  const int kpw = (max_keypoints >= 4096 && (long)im.n * max_keypoints >= 3000000L) ? 8 : 4;
+  const int kpw = vsf_describe_kp_per_wave(max_keypoints, im.n);
   a.nblocks = std::max((max_keypoints + 4 * kpw - 1) / (4 * kpw), 1);
   a.nimages = im.n;
   if (kpw == 8)

@@ -224,6 +224,14 @@ vsf_status vsf_debug_fast_work(const vsf_params* p, int orb, int nms, uint32_t* 
   return VSF_OK;
 }
 
+// The launcher's own choice (vsf_describe_kp_per_wave), so that a test knows which instantiation of the describe kernel its
+// batch ran without restating the thresholds.  Host only; n_images is not held against max_images, so that a small context
+// can be asked where the form changes before the large one is built.
+int vsf_debug_describe_form(const vsf_ctx* ctx, int n_images) {
+  if (!ctx || n_images < 1) return (int)VSF_ERR_INVALID_ARG;
+  return vsf_describe_kp_per_wave(ctx->p.max_keypoints, n_images);
+}
+
 vsf_status vsf_debug_level_keypoints(vsf_ctx* ctx, int image, int level, vsf_keypoint* kp_out, int cap, int* n_out) {
   VsfErrorScope scope_(ctx);
   if (!ctx || !n_out || !ctx->last_valid || image < 0 || image >= ctx->last_images.n || level < 0 ||

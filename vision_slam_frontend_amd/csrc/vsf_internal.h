@@ -214,6 +214,12 @@ void vsf_launch_blur_mma(const VsfDev& d, const VsfGeom& g, const VsfImages& im,
                          const uint4* d_tcol, const uint4* d_tv, int bias, hipStream_t s);
 void vsf_launch_describe(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int max_keypoints,
                          vsf_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t s);
+// Consecutive output keypoints per wave of one describe launch over n_images images (k_describe.hip has the measurements):
+// eight needs a launch that still fills the chip with waves -- 512 images x 10 000 keypoints; 64-192 images of 8 000
+// (1920x1080) run 1-2 % faster with four.  The one statement of the choice: the launcher and vsf_debug_describe_form read it.
+inline int vsf_describe_kp_per_wave(int max_keypoints, int n_images) {
+  return (max_keypoints >= 4096 && (long)n_images * max_keypoints >= 3000000L) ? 8 : 4;
+}
 void vsf_launch_fast_emit(const VsfDev& d, const VsfGeom& g, int n_images, int max_keypoints, vsf_keypoint* d_kp,
                           int32_t* d_counts, hipStream_t s);
 void vsf_launch_knn2(const uint8_t* d_desc, const int32_t* d_counts, size_t set_stride, const int32_t* d_q_set,

@@ -415,15 +415,22 @@ class Frontend:
         so far (it does NOT flush the queue; complete after flush()).  Returns (cloud, nodes, odometry, vision): the point
         cloud as an (n, 3) float64 array, one point per node, and the two end points of every odometry / vision factor's line
         as (m, 2, 3) arrays.  host=True: the same computed on the CPU from the whole problem, as the reference's driver does
-        (GetSLAMProblem + AddFeaturePoints / AddPoseGraph; that flushes)."""
-        out = []
-        for which in (3, 0, 1, 2):
-            n = lib().vsfh_visualization_points(self._h, int(host), which, None, 0)
-            if n < 0:
-                raise capi.VsfError(lib().vsfh_last_status(self._h), "Frontend::GetVisualization")
-            a = np.zeros((max(n, 1), 3), np.float64)
-            n = min(n, lib().vsfh_visualization_points(self._h, int(host), which, _p(a), len(a)))
-            out.append(a[:n].copy())
+        (GetSLAMProblem + AddFeaturePoints / AddPoseGraph; that flushes).
+        Every vsfh_visualization_points is a GetVisualization of its own, and a pipelined Frontend books whatever has finished
+        in each of them: a batch that lands between two reads leaves nodes and odometry lines of different moments (every node
+        but the first comes with one line).  Such a torn read is taken again, a few times at the most; nothing is read more
+        often than before when it is whole (an extra poll is an extra chance for the queue to send a small batch)."""
+        for _ in range(4):
+            out = []
+            for which in (3, 0, 1, 2):
+                n = lib().vsfh_visualization_points(self._h, int(host), which, None, 0)
+                if n < 0:
+                    raise capi.VsfError(lib().vsfh_last_status(self._h), "Frontend::GetVisualization")
+                a = np.zeros((max(n, 1), 3), np.float64)
+                n = min(n, lib().vsfh_visualization_points(self._h, int(host), which, _p(a), len(a)))
+                out.append(a[:n].copy())
+            if len(out[2]) == 2 * max(len(out[1]) - 1, 0):
+                break
         return out[0], out[1], out[2].reshape(-1, 2, 3), out[3].reshape(-1, 2, 3)
 
     def serialize_visualization(self, host: bool = False):
