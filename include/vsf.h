@@ -976,6 +976,16 @@ int vsf_debug_describe_form(const vsf_ctx* ctx, int n_images);
  * (packed FAST candidates).  use_lds: run on an LDS copy when n <= 4096.  *n_out = surviving count. */
 vsf_status vsf_debug_retain_best(vsf_ctx* ctx, uint32_t* key_bits, uint32_t* ids, int n, int n_points, int use_lds,
                                  int mode, int* n_out);
+/* The same, in the forms production runs: one stage of the selection kernel on chosen keys, with the template arguments,
+ * memory plan (LDS arrays, HBM scratch blocks, mask carve-out, table placement, the stage-1 LDS hand-over), element types,
+ * comparators and residency rule of the production kernel.  form 0..3: the wide (1024 threads, 12288 entries), common
+ * (256, 3072), 9216-entry (256, 16-bit tables in HBM) and tiny (64, 1536) instances.  stage 1: 32-bit candidates
+ * (key_bits[i] in 0..255 is the score byte, ids[i] < 2^24), in LDS when n <= entries; stage 2: (float bits, id) pairs, in
+ * LDS when n <= 512.  level_cap >= n, >= 1: the capacity of the level's slice of each scratch block, as a level's segment
+ * capacity is in production.  key_bits and ids hold level_cap entries each: the first n are the array, the rest lie behind
+ * it in the slice and come back as the device left them.  *n_out = surviving count. */
+vsf_status vsf_debug_retain_best_form(vsf_ctx* ctx, int form, int stage, uint32_t* key_bits, uint32_t* ids, int n,
+                                      int n_points, int level_cap, int* n_out);
 /* Test hook of the order-exact sort of Frontend::GetFeatureMatches (slam_frontend.cc:289-291): n_lists lists of n host
  * matches each (list i at matches + i * n; the context's max_keypoints bounds n) go through the device's std::sort
  * restatement + the cut to int(n * best_percent); pairs_out[i * n * 2 ...] receives (queryIdx, trainIdx) of the survivors

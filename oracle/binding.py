@@ -71,6 +71,8 @@ def lib() -> C.CDLL:
         L.vsfo_orb_stage_keypoints.argtypes = [vp, i32, i32, vp, i32]
         L.vsfo_orb_result.argtypes = [vp, vp, vp, i32]
         L.vsfo_retain_best.argtypes = [vp, vp, i32, i32]
+        L.vsfo_killer_for_nth.argtypes = [i32, i32, i32, vp]
+        L.vsfo_nth_trace.argtypes = [vp, i32, i32, vp, i32, C.POINTER(C.c_int32)]
         L.vsfo_knn2_hamming.argtypes = [vp, i32, vp, i32, vp, vp]
         L.vsfo_get_matches.argtypes = [vp, i32, vp, i32, C.c_double, vp, i32]
         L.vsfo_get_matches_mt.argtypes = [vp, i32, vp, i32, C.c_double, vp, i32, i32]
@@ -163,6 +165,27 @@ def retain_best(keys: np.ndarray, n_points: int):
     ids = np.arange(len(r), dtype=np.uint32)
     n = lib().vsfo_retain_best(_p(r), _p(ids), len(r), n_points)
     return r[:n], ids[:n]
+
+
+def killer_for_nth(n: int, nth: int, depth: int | None = None) -> np.ndarray:
+    """McIlroy's adversary against the host std::nth_element(.., greater) at position nth: float32 keys (a permutation of
+    0..n-1 up to ties at the top) that send it into its depth-limit fallback.  depth: play against std::__introselect
+    with that many passes left instead of nth_element's own 2 * floor(log2 n) -- the tail of a longer selection."""
+    keys = np.empty(n, np.float32)
+    assert lib().vsfo_killer_for_nth(n, nth, -1 if depth is None else depth, _p(keys)) == 0
+    return keys
+
+
+def nth_trace(keys: np.ndarray, nth: int):
+    """(ranges, fallback): last - first before every partition pass of std::nth_element(a, a + nth, a + n, greater) on
+    (keys[i], i), and the range at which the depth limit was met (heap select), or -1."""
+    k = np.ascontiguousarray(keys, np.float32)
+    cap = 2 * max(int(len(k)), 1).bit_length() + 2  # (the depth limit is 2 * floor(log2 n) passes)
+    ranges = np.zeros(cap, np.int32)
+    fb = C.c_int32(-1)
+    passes = lib().vsfo_nth_trace(_p(k), len(k), nth, _p(ranges), cap, C.byref(fb))
+    assert 0 <= passes <= cap, passes
+    return [int(r) for r in ranges[:passes]], int(fb.value)
 
 
 class Orb:

@@ -711,6 +711,88 @@ int vsfo_retain_best(float* response, uint32_t* id, int n, int n_points) {
   return (int)kps.size();
 }
 
+// ---- adversarial inputs for the selection, and the path libstdc++ takes on an input ----
+namespace {
+// McIlroy's adaptive adversary ("A Killer Adversary for Quicksort"): answers comparisons so that the pivots are bad and
+// freezes the values it had to commit to; the frozen values are an ordinary input that repeats the bad run.
+struct Adversary {
+  std::vector<int> val;
+  int nsolid = 0, candidate = 0, gas;
+  explicit Adversary(int n) : val(n, n - 1), gas(n - 1) {}
+  bool less(int x, int y) {
+    if (val[x] == gas && val[y] == gas) {
+      if (x == candidate)
+        val[x] = nsolid++;
+      else
+        val[y] = nsolid++;
+    }
+    if (val[x] == gas)
+      candidate = x;
+    else if (val[y] == gas)
+      candidate = y;
+    return val[x] < val[y];
+  }
+};
+struct KeyId {
+  float key;
+  int id;
+};
+struct KeyGreater {
+  bool operator()(const KeyId& a, const KeyId& b) const { return a.key > b.key; }
+};
+}  // namespace
+
+int vsfo_killer_for_nth(int n, int nth, int depth, float* keys) {
+  if (n < 1 || nth < 0 || nth >= n || !keys) return -1;
+  Adversary adv(n);
+  std::vector<int> idx(n);
+  for (int i = 0; i < n; i++) idx[i] = i;
+  // comparator "greater": x before y if val[x] > val[y]
+  auto greater = [&](int x, int y) { return adv.less(y, x); };
+  if (depth < 0)
+    std::nth_element(idx.begin(), idx.begin() + nth, idx.end(), greater);
+  else  // (what std::nth_element calls with 2 * floor(log2 n): here the array is the tail of a longer selection)
+    std::__introselect(idx.begin(), idx.begin() + nth, idx.end(), depth, __gnu_cxx::__ops::__iter_comp_iter(greater));
+  for (int i = 0; i < n; i++) keys[i] = (float)adv.val[i];
+  return 0;
+}
+
+// std::__introselect, loop by loop, with libstdc++'s own partition step (bits/stl_algo.h), so that the state before every
+// pass can be written down; the permutation it leaves is held against std::nth_element's before anything is returned.
+int vsfo_nth_trace(const float* keys, int n, int nth, int32_t* ranges, int cap, int32_t* fallback_range) {
+  if (n < 1 || nth < 0 || nth >= n || !keys || !fallback_range || cap < 0 || (cap > 0 && !ranges)) return -1;
+  std::vector<KeyId> a(n);
+  for (int i = 0; i < n; i++) a[i] = KeyId{keys[i], i};
+  std::vector<KeyId> want = a;
+  std::nth_element(want.begin(), want.begin() + nth, want.end(), KeyGreater());
+  auto comp = __gnu_cxx::__ops::__iter_comp_iter(KeyGreater());
+  auto first = a.begin(), last = a.end(), pos = a.begin() + nth;
+  int depth = std::__lg(n) * 2, passes = 0;
+  *fallback_range = -1;
+  bool done = false;
+  while (last - first > 3) {
+    if (depth == 0) {
+      *fallback_range = (int32_t)(last - first);
+      std::__heap_select(first, pos + 1, last, comp);
+      std::iter_swap(first, pos);
+      done = true;
+      break;
+    }
+    --depth;
+    if (passes < cap) ranges[passes] = (int32_t)(last - first);
+    ++passes;
+    auto cut = std::__unguarded_partition_pivot(first, last, comp);
+    if (cut <= pos)
+      first = cut;
+    else
+      last = cut;
+  }
+  if (!done) std::__insertion_sort(first, last, comp);
+  for (int i = 0; i < n; i++)
+    if (a[i].id != want[i].id) return -2;  // (this restatement is not what std::nth_element did)
+  return passes;
+}
+
 vsfo_orb* vsfo_orb_create(const vsfo_orb_params* p) {
   vsfo_orb* o = new vsfo_orb();
   o->p = *p;

@@ -83,6 +83,17 @@ const int8_t* vsfo_orb_pattern31(void);
  * std::partition), in place; returns the surviving count. */
 int vsfo_retain_best(float* response, uint32_t* id, int n, int n_points);
 
+/* McIlroy's adversary against the host std::nth_element(a, a + nth, a + n, greater): keys[0..n) receives an input that
+ * drives it into its depth-limit (heap select) fallback.  depth < 0: the limit std::nth_element itself sets, 2 * floor(log2 n);
+ * else the adversary plays against std::__introselect with that many passes left, as when the n elements are what an
+ * earlier pass of a longer selection left.  0, or -1 for bad arguments. */
+int vsfo_killer_for_nth(int n, int nth, int depth, float* keys);
+
+/* The path of std::nth_element(a, a + nth, a + n, greater) on (keys[i], i): ranges[p] = last - first before partition
+ * pass p (at most cap of them are stored), *fallback_range = last - first when the depth limit was met (heap select), or
+ * -1.  Returns the number of passes; -1 for bad arguments, -2 if the traced loop did not leave std::nth_element's order. */
+int vsfo_nth_trace(const float* keys, int n, int nth, int32_t* ranges, int cap, int32_t* fallback_range);
+
 /* ---- ORB detectAndCompute with every intermediate kept for kernel-level parity ---- */
 typedef struct vsfo_orb vsfo_orb;
 vsfo_orb* vsfo_orb_create(const vsfo_orb_params* p);

@@ -13,6 +13,8 @@ import numpy as np
 
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libvsf_hip.so"
+# The instances of the selection kernel (k_select.hip): threads, stage-1 entries kept in LDS, stage-2 pairs kept in LDS
+SELECT_FORMS = {"A": (1024, 12288, 512), "B": (256, 3072, 512), "C": (256, 9216, 512), "D": (64, 1536, 512)}
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                            ("octave", "<i4"), ("class_id", "<i4")])
@@ -32,7 +34,7 @@ EXPORTS = [
     "vsf_fast_detect", "vsf_knn2_hamming", "vsf_get_matches", "vsf_extract_pair", "vsf_get_matches_multi", "vsf_extract_batch_dev", "vsf_match_batch_dev",
     "vsf_stereo_batch_dev", "vsf_set_lanes", "vsf_set_pipeline", "vsf_set_blur_overlap", "vsf_set_fast_resident", "vsf_get_fast_resident", "vsf_remove_ambig_stereo_batch_dev", "vsf_feature_matches_batch_dev", "vsf_bayer_bg_to_gray_batch_dev", "vsf_debug_level_image", "vsf_debug_fast_candidates", "vsf_debug_fast_work", "vsf_debug_level_keypoints",
     "vsf_algorithmic_bytes_per_image", "vsf_pyramid_pixels", "vsf_profile_enable", "vsf_profile_read",
-    "vsf_stage_name", "vsf_debug_retain_best", "vsf_debug_sort_trim", "vsf_stereo_residuals_batch_dev", "vsf_stereo_thresholds_dev",
+    "vsf_stage_name", "vsf_debug_retain_best", "vsf_debug_retain_best_form", "vsf_debug_sort_trim", "vsf_stereo_residuals_batch_dev", "vsf_stereo_thresholds_dev",
     "vsf_stereo_filter_batch_dev", "vsf_vision_features_batch_dev", "vsf_packed_outputs_capacity",
     "vsf_pack_outputs_dev", "vsf_observe_capacity", "vsf_observe_stereo", "vsf_observe_submit", "vsf_observe_collect", "vsf_observe_reset",
     "vsf_observe_configure", "vsf_observe_collect_view", "vsf_observe_stats", "vsf_observe_poll", "vsf_debug_jpeg_serial",
@@ -347,6 +349,7 @@ def lib() -> C.CDLL:
         L.vsf_pyramid_pixels.argtypes = [vp]
         L.vsf_pyramid_pixels.restype = C.c_uint64
         L.vsf_debug_retain_best.argtypes = [vp, vp, vp, i32, i32, i32, i32, ip]
+        L.vsf_debug_retain_best_form.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, ip]
         L.vsf_profile_enable.argtypes = [vp, i32]
         L.vsf_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
         L.vsf_stage_name.argtypes = [i32]
@@ -1020,6 +1023,25 @@ class Context:
         self._check(lib().vsf_debug_retain_best(self._h, _p(kb), _p(ids), len(kb), n_points, int(use_lds), mode,
                                                 C.byref(n)), "vsf_debug_retain_best")
         return kb[:n.value], ids[:n.value]
+
+    def debug_retain_best_form(self, form: str, stage: int, keys: np.ndarray, n_points: int, level_cap: int | None = None,
+                               poison: tuple = (0xAB, 0xCDEF01)):
+        """retainBest as ONE stage of the production selection kernel runs it.  form: "A" wide, "B" common, "C" 9 216-entry,
+        "D" tiny (SELECT_FORMS); stage 1: keys are score bytes 0..255, stage 2: float32 responses.  level_cap (default
+        len(keys) + 19) is the capacity of the level's scratch slices; the entries behind the array hold `poison`.
+        Returns (keys, ids, tail_intact): survivors as uint32 key bits (stage 1: the byte) and ids in the device's order,
+        and whether everything behind the array came back untouched."""
+        n = len(keys)
+        cap = n + 19 if level_cap is None else level_cap
+        kb = np.full(cap, poison[0], np.uint32)
+        ids = np.full(cap, poison[1], np.uint32)
+        kb[:n] = np.asarray(keys).astype(np.uint32) if stage == 1 else np.ascontiguousarray(keys, np.float32).view(np.uint32)
+        ids[:n] = np.arange(n, dtype=np.uint32)
+        m = C.c_int()
+        self._check(lib().vsf_debug_retain_best_form(self._h, "ABCD".index(form), stage, _p(kb), _p(ids), n, n_points, cap,
+                                                     C.byref(m)), "vsf_debug_retain_best_form")
+        intact = bool((kb[n:] == poison[0]).all() and (ids[n:] == poison[1]).all())
+        return kb[:m.value], ids[:m.value], intact
 
     def debug_sort_trim(self, matches: np.ndarray, best_percent: float = 1.0, serial: bool = False):
         """matches: (n_lists, n) DMATCH_DTYPE.  Returns a list of (queryIdx, trainIdx) int arrays, one per list: the first

@@ -18,7 +18,9 @@
 //   * the split point follows from the table entries next to the last swap.
 // Pivot choice (median of first+1 / mid / last-1), the depth limit, the heap-select fallback and the final
 // insertion sort are the sequential restatement of vsf_select.h; ranges <= 256 elements are finished by a single
-// wave (ballot masks in SGPRs, no workgroup barriers), the rare depth-limit / heap-select case by one lane.
+// wave (ballot masks in SGPRs, no workgroup barriers), the rare depth-limit / heap-select case by one lane
+// (tests/test_gpu_select_forms.py drives every form of the kernel into it with adversarial keys, in each of the three
+// places it lives: reg_introselect, wave_introselect, par_introselect).
 // The arrays live in LDS when they fit and in an HBM scratch area otherwise.
 #include "vsf_gather.h"
 #include <cstdlib>
@@ -525,26 +527,98 @@ __device__ __forceinline__ float harris_response(const uint8_t* __restrict__ img
   return (fa * fb - fc * fc - 0.04f * (fa + fb) * (fa + fb)) * scale_sq_sq;
 }
 
+// ---- the memory plan of one level's selection: stated ONCE, for orb_select_kernel and for select_form_test_kernel ----
 // ENTRIES: stage-1 candidates kept in LDS; STAGE2: stage-2 pairs kept in LDS; MAXW: mask words of a parallel pass.
 // LDS_TABLES = false (round 4, the class of the widest levels): the ARRAY of a level with up to ENTRIES candidates lives in
 // LDS from the gather on, and only the rank -> position tables of its passes (16-bit, written once and read once per pass)
 // go through the level's HBM scratch -- instead of the array itself, its masks and 32-bit tables living there until the
 // selection range has shrunk to the common class's 3 072 entries (two or three passes over 4 ... 8 000 elements each).
-template <int NT, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES = true, int WGS = (NT == 256 ? 5 : 1)>
-__global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
+template <int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES>
+struct SelectLds {
+  static constexpr int POS16 = LDS_TABLES ? 2 * ENTRIES : 4096;  // 16-bit words of pos
+  uint32_t* A;    // [ENTRIES] stage-1 candidates
+  uint16_t* pos;  // [POS16] rank -> position tables of the LDS-resident passes (and the gather's scratch)
+  uint2* B;       // [STAGE2] stage-2 pairs
+  unsigned long long* mask;  // [2 * MAXW]
+  int* pre;                  // [2 * MAXW]
+  PassCtl* ctl;
+  static_assert(ENTRIES <= 65536 && ENTRIES / 64 <= MAXW && STAGE2 <= ENTRIES && ENTRIES >= 1025, "scratch sizes");
+  // wave scratch: stage 1 borrows the (still unused) stage-2 array, stage 2 the stage-1 array (consumed by then)
+  static_assert(sizeof(uint2) * STAGE2 >= kWaveScratch && sizeof(uint32_t) * ENTRIES >= kWaveScratch, "wave scratch");
+};
+// The shared arrays of the calling kernel (KERNEL: one set of LDS variables per kernel template that uses the plan).
+// Separate variables, not members of one __shared__ struct: as a struct they changed orb_select_kernel's register and
+// scratch figures (NOTES.md).
+template <int KERNEL, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES>
+__device__ __forceinline__ SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES> select_lds() {
   __shared__ __attribute__((aligned(16))) uint32_t sA[ENTRIES];
-  constexpr int POS16 = LDS_TABLES ? 2 * ENTRIES : 4096;  // 16-bit words of sPos
-  __shared__ uint16_t sPos[POS16];  // rank -> position tables of the LDS-resident passes (and the gather's scratch)
+  __shared__ uint16_t sPos[SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES>::POS16];
   __shared__ __attribute__((aligned(16))) uint2 sB[STAGE2];
   __shared__ unsigned long long sMask[2 * MAXW];
   __shared__ int sPre[2 * MAXW];
   __shared__ PassCtl ctl;
+  return SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES>{sA, sPos, sB, sMask, sPre, &ctl};
+}
+
+// Where everything else lives, given the image's six scratch blocks (gscratch: [6][cand_entries] 32-bit words: stage-1
+// array, stage-2 pairs (x2), rank tables (x2), masks) and the level's slice [cand_offset, cand_offset + level_cap) of each.
+template <int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES>
+struct SelectPlan {
+  uint32_t* A_lds;
+  uint32_t* gA;  // stage-1 array when n > ENTRIES
+  uint2* gB;     // stage-2 pairs when m1 > STAGE2
+  PassMem<uint16_t> pm_lds, pm_lds2;  // (the *2 twins: stage 2, with the other wave scratch)
+  PassMem<uint32_t> pm_hbm, pm_hbm2;
+  // where an HBM-resident stage 1 continues once its range fits (A is idle while the array lives in HBM)
+  __device__ __forceinline__ LdsStage<uint32_t> stage1() const { return LdsStage<uint32_t>{A_lds, ENTRIES, &pm_lds}; }
+
+  __device__ __forceinline__ SelectPlan(const SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES>& s, uint32_t* gscratch,
+                                        uint32_t cand_entries, uint32_t cand_offset, int level_cap) {
+    A_lds = s.A;
+    gA = gscratch + cand_offset;
+    gB = reinterpret_cast<uint2*>(gscratch + cand_entries) + cand_offset;
+    uint8_t* wbuf1 = reinterpret_cast<uint8_t*>(s.B);
+    uint8_t* wbuf2 = reinterpret_cast<uint8_t*>(s.A);
+    // (LDS_TABLES = false: the two 16-bit tables sit in the level's slices of scratch blocks 3 and 4 -- level_cap 32-bit
+    // words each, i.e. room for 2 level_cap positions -- where the HBM-resident passes keep their 32-bit ones)
+    uint16_t* tabL = LDS_TABLES ? s.pos : reinterpret_cast<uint16_t*>(gscratch + 3 * cand_entries + cand_offset);
+    uint16_t* tabR = LDS_TABLES ? s.pos + ENTRIES : reinterpret_cast<uint16_t*>(gscratch + 4 * cand_entries + cand_offset);
+    pm_lds = PassMem<uint16_t>{s.mask, s.mask + MAXW, s.pre, s.pre + MAXW, tabL, tabR, ENTRIES / 64, s.ctl, wbuf1};
+    // HBM-resident passes keep their masks in HBM as well (24 bytes per 64 elements, carved from the level's slice of
+    // the sixth scratch block), so a level of any candidate count runs the parallel passes
+    const int hbm_w = (level_cap + 63) / 64;
+    unsigned long long* gmask = reinterpret_cast<unsigned long long*>(
+        (reinterpret_cast<uintptr_t>(gscratch + 5 * cand_entries + cand_offset) + 7) & ~(uintptr_t)7);
+    int* gpre = reinterpret_cast<int*>(gmask + 2 * hbm_w);
+    // Always true for real levels: an array only goes to HBM when it has more elements than its LDS array holds (stage 1:
+    // n > ENTRIES >= 1536; stage 2: m1 > STAGE2 = 512), and level_cap >= n, so level_cap >= 513, hbm_w >= 9 and
+    // 6 * hbm_w + 2 <= 6 * (level_cap + 63) / 64 + 2 < level_cap.  The LDS masks (which bound the range at MAXW * 64)
+    // only stand in for a geometry that cannot occur, so no test drives that side (tests/test_gpu_select_forms.py).
+    const bool hbm_masks = 6 * hbm_w + 2 <= level_cap;
+    pm_hbm = PassMem<uint32_t>{hbm_masks ? gmask : s.mask,
+                               hbm_masks ? gmask + hbm_w : s.mask + MAXW,
+                               hbm_masks ? gpre : s.pre,
+                               hbm_masks ? gpre + hbm_w : s.pre + MAXW,
+                               gscratch + 3 * cand_entries + cand_offset,
+                               gscratch + 4 * cand_entries + cand_offset,
+                               hbm_masks ? hbm_w : MAXW,
+                               s.ctl,
+                               wbuf1};
+    pm_lds2 = pm_lds;
+    pm_hbm2 = pm_hbm;
+    pm_lds2.wbuf = pm_hbm2.wbuf = wbuf2;
+  }
+};
+
+template <int NT, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES = true, int WGS = (NT == 256 ? 5 : 1)>
+__global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
+  const SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES> lds = select_lds<0, ENTRIES, STAGE2, MAXW, LDS_TABLES>();
   __shared__ int lds4[16];
-  static_assert(ENTRIES <= 65536 && ENTRIES / 64 <= MAXW && STAGE2 <= ENTRIES && ENTRIES >= 1025, "scratch sizes");
+  constexpr int POS16 = SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES>::POS16;
   // the gather borrows the position tables: three quarters for the cell prefix array, one for the row-start tables
   constexpr int kCellCap = (POS16 / 2) * 3 / 4, kRsUnits = (POS16 / 8) * 2 / VSF_FAST_RS_STRIDE;
   static_assert(kCellCap >= VSF_FAST_STRIP_ROWS * 16 + 1 && kRsUnits >= 8, "gather scratch");
-  int* cellpre = reinterpret_cast<int*>(sPos);
+  int* cellpre = reinterpret_cast<int*>(lds.pos);
   uint16_t* rs_lds = reinterpret_cast<uint16_t*>(cellpre + kCellCap);
   const int tid = threadIdx.x;
   // image -> XCD affinity (workgroups go to the 8 XCDs round-robin by linear id): an image's candidates, pixels and
@@ -570,36 +644,12 @@ __global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
   // ---- gather: merge the FAST units' segments into the level's raster order (vsf_gather.h) ----
   const uint16_t* rs_img = a.rowstart + (size_t)image * a.nunits * VSF_FAST_RS_STRIDE;
   uint32_t* gscratch = a.scratch + (size_t)image * 6 * a.cand_entries;
-  uint32_t* gA = gscratch + L.cand_offset;
-  uint2* gB = reinterpret_cast<uint2*>(gscratch + a.cand_entries) + L.cand_offset;
-  // wave scratch: stage 1 borrows the (still unused) stage-2 array, stage 2 the stage-1 array (consumed by then)
-  static_assert(sizeof(uint2) * STAGE2 >= kWaveScratch && sizeof(uint32_t) * ENTRIES >= kWaveScratch, "wave scratch");
-  uint8_t* wbuf1 = reinterpret_cast<uint8_t*>(sB);
-  uint8_t* wbuf2 = reinterpret_cast<uint8_t*>(sA);
-  // (LDS_TABLES = false: the two 16-bit tables sit in the level's slices of scratch blocks 3 and 4 -- level_cap 32-bit
-  // words each, i.e. room for 2 level_cap positions -- where the HBM-resident passes keep their 32-bit ones)
-  uint16_t* tabL = LDS_TABLES ? sPos : reinterpret_cast<uint16_t*>(gscratch + 3 * a.cand_entries + L.cand_offset);
-  uint16_t* tabR = LDS_TABLES ? sPos + ENTRIES : reinterpret_cast<uint16_t*>(gscratch + 4 * a.cand_entries + L.cand_offset);
-  const PassMem<uint16_t> pm_lds{sMask, sMask + MAXW, sPre, sPre + MAXW, tabL, tabR, ENTRIES / 64, &ctl, wbuf1};
-  // HBM-resident passes keep their masks in HBM as well (24 bytes per 64 elements, carved from the level's slice of
-  // the sixth scratch block), so a level of any candidate count runs the parallel passes
-  const int level_cap = L.seg_cap * L.nbands * L.nstrips, hbm_w = (level_cap + 63) / 64;
-  unsigned long long* gmask = reinterpret_cast<unsigned long long*>(
-      (reinterpret_cast<uintptr_t>(gscratch + 5 * a.cand_entries + L.cand_offset) + 7) & ~(uintptr_t)7);
-  int* gpre = reinterpret_cast<int*>(gmask + 2 * hbm_w);
-  const bool hbm_masks = 6 * hbm_w + 2 <= level_cap;  // (always true for real levels; else the LDS masks bound the range)
-  const PassMem<uint32_t> pm_hbm{hbm_masks ? gmask : sMask,
-                                 hbm_masks ? gmask + hbm_w : sMask + MAXW,
-                                 hbm_masks ? gpre : sPre,
-                                 hbm_masks ? gpre + hbm_w : sPre + MAXW,
-                                 gscratch + 3 * a.cand_entries + L.cand_offset,
-                                 gscratch + 4 * a.cand_entries + L.cand_offset,
-                                 hbm_masks ? hbm_w : MAXW,
-                                 &ctl,
-                                 wbuf1};
-  PassMem<uint16_t> pm_lds2 = pm_lds;
-  PassMem<uint32_t> pm_hbm2 = pm_hbm;
-  pm_lds2.wbuf = pm_hbm2.wbuf = wbuf2;
+  const SelectPlan<ENTRIES, STAGE2, MAXW, LDS_TABLES> P(lds, gscratch, a.cand_entries, L.cand_offset,
+                                                        L.seg_cap * L.nbands * L.nstrips);
+  uint32_t* const sA = lds.A;
+  uint2* const sB = lds.B;
+  uint32_t* const gA = P.gA;
+  uint2* const gB = P.gB;
   bool a_in_lds = true;
   const uint32_t* cand_img = a.cand + (size_t)image * a.cand_entries;
   const int n = vsf_gather_level<NT>(
@@ -615,10 +665,9 @@ __global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
   // ---- K3: retainBest(2 * n_l) on the FAST score ----
   int m1;
   if (a_in_lds)
-    m1 = par_retain_best<NT>(sA, n, 2 * L.nfeatures, ScoreGreater(), ScoreGe(), pm_lds);
+    m1 = par_retain_best<NT>(sA, n, 2 * L.nfeatures, ScoreGreater(), ScoreGe(), P.pm_lds);
   else
-    m1 = par_retain_best<NT>(gA, n, 2 * L.nfeatures, ScoreGreater(), ScoreGe(), pm_hbm,
-                             LdsStage<uint32_t>{sA, ENTRIES, &pm_lds});  // (sA is idle while the array lives in HBM)
+    m1 = par_retain_best<NT>(gA, n, 2 * L.nfeatures, ScoreGreater(), ScoreGe(), P.pm_hbm, P.stage1());
   __syncthreads();
 
   // ---- K4: Harris responses (one lane per keypoint) ----
@@ -637,9 +686,9 @@ __global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
   // ---- K5: retainBest(n_l) on the Harris response ----
   int m2;
   if (b_in_lds)
-    m2 = par_retain_best<NT>(sB, m1, L.nfeatures, RespGreater(), RespGe(), pm_lds2);
+    m2 = par_retain_best<NT>(sB, m1, L.nfeatures, RespGreater(), RespGe(), P.pm_lds2);
   else
-    m2 = par_retain_best<NT>(gB, m1, L.nfeatures, RespGreater(), RespGe(), pm_hbm2);
+    m2 = par_retain_best<NT>(gB, m1, L.nfeatures, RespGreater(), RespGe(), P.pm_hbm2);
   __syncthreads();
 
   // ---- survivors in retainBest order; K6 (ICAngles) runs in k_describe.hip, one wave per keypoint ----
@@ -695,6 +744,43 @@ __global__ __launch_bounds__(NT) void retain_best_test_kernel(uint2* data, uint3
     m = par_retain_best<NT>(data, n, n_points, G(), GE(), pm_hbm);
   }
   if (threadIdx.x == 0) *out_n = m;
+}
+
+// Test hook: one stage of orb_select_kernel's selection on chosen keys, with the production template arguments, memory
+// plan, element types, comparators and residency rule.  gscratch: the six scratch blocks of one image; the stage's array
+// comes and goes in its HBM home (P.gA / P.gB), where the gather / the Harris loop would have put it when it does not fit.
+template <int NT, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES = true, int WGS = (NT == 256 ? 5 : 1)>
+__global__ __launch_bounds__(NT, WGS) void select_form_test_kernel(uint32_t* gscratch, uint32_t cand_entries,
+                                                                   uint32_t cand_offset, int level_cap, int stage, int n,
+                                                                   int n_points, int* out_n) {
+  const SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES> lds = select_lds<1, ENTRIES, STAGE2, MAXW, LDS_TABLES>();
+  const SelectPlan<ENTRIES, STAGE2, MAXW, LDS_TABLES> P(lds, gscratch, cand_entries, cand_offset, level_cap);
+  const int tid = threadIdx.x;
+  int m;
+  if (stage == 1) {
+    const bool a_in_lds = n <= ENTRIES;
+    if (a_in_lds) {
+      for (int i = tid; i < n; i += NT) lds.A[i] = P.gA[i];
+      __syncthreads();
+      m = par_retain_best<NT>(lds.A, n, n_points, ScoreGreater(), ScoreGe(), P.pm_lds);
+      __syncthreads();
+      for (int i = tid; i < n; i += NT) P.gA[i] = lds.A[i];
+    } else {
+      m = par_retain_best<NT>(P.gA, n, n_points, ScoreGreater(), ScoreGe(), P.pm_hbm, P.stage1());
+    }
+  } else {
+    const bool b_in_lds = n <= STAGE2;
+    if (b_in_lds) {
+      for (int i = tid; i < n; i += NT) lds.B[i] = P.gB[i];
+      __syncthreads();
+      m = par_retain_best<NT>(lds.B, n, n_points, RespGreater(), RespGe(), P.pm_lds2);
+      __syncthreads();
+      for (int i = tid; i < n; i += NT) P.gB[i] = lds.B[i];
+    } else {
+      m = par_retain_best<NT>(P.gB, n, n_points, RespGreater(), RespGe(), P.pm_hbm2);
+    }
+  }
+  if (tid == 0) *out_n = m;
 }
 
 }  // namespace
@@ -790,6 +876,30 @@ void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_leve
     a.nlv = g.nlevels - ntiny0;
     hipLaunchKernelGGL((orb_select_kernel<64, 1536, 512, 64>), dim3(a.nlv * n8), dim3(64), 0, s, a);
   }
+}
+
+// form 0..3: the four instances vsf_launch_select launches, in the order of its text (A wide, B common, C 9 216-entry, D tiny).
+bool vsf_launch_select_form_test(int form, uint32_t* d_scratch, uint32_t cand_entries, uint32_t cand_offset, int level_cap,
+                                 int stage, int n, int n_points, int* d_out_n, hipStream_t s) {
+  switch (form) {
+    case 0:
+      hipLaunchKernelGGL((select_form_test_kernel<1024, 12288, 512, 192>), dim3(1), dim3(1024), 0, s, d_scratch, cand_entries,
+                         cand_offset, level_cap, stage, n, n_points, d_out_n);
+      return true;
+    case 1:
+      hipLaunchKernelGGL((select_form_test_kernel<256, 3072, 512, 64>), dim3(1), dim3(256), 0, s, d_scratch, cand_entries,
+                         cand_offset, level_cap, stage, n, n_points, d_out_n);
+      return true;
+    case 2:
+      hipLaunchKernelGGL((select_form_test_kernel<256, 9216, 512, 144, false, 3>), dim3(1), dim3(256), 0, s, d_scratch,
+                         cand_entries, cand_offset, level_cap, stage, n, n_points, d_out_n);
+      return true;
+    case 3:
+      hipLaunchKernelGGL((select_form_test_kernel<64, 1536, 512, 64>), dim3(1), dim3(64), 0, s, d_scratch, cand_entries,
+                         cand_offset, level_cap, stage, n, n_points, d_out_n);
+      return true;
+  }
+  return false;
 }
 
 void vsf_launch_retain_best_test(uint2* d_data, uint32_t* d_tables, int n, int n_points, int use_lds, int mode,

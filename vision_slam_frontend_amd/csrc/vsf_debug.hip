@@ -98,6 +98,57 @@ vsf_status vsf_debug_retain_best(vsf_ctx* ctx, uint32_t* key_bits, uint32_t* ids
   return VSF_OK;
 }
 
+vsf_status vsf_debug_retain_best_form(vsf_ctx* ctx, int form, int stage, uint32_t* key_bits, uint32_t* ids, int n,
+                                      int n_points, int level_cap, int* n_out) {
+  VsfErrorScope scope_(ctx);
+  if (!ctx || !n_out || !key_bits || !ids || form < 0 || form > 3 || (stage != 1 && stage != 2) || n < 0 || level_cap < 1 ||
+      n > level_cap || level_cap > (1 << 24))
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // One image's six scratch blocks as vsf_launch_select's callers allocate them (6 * cand_entries words), with this
+  // level's slice neither first nor last in its block: an odd offset, so the mask carve-out has to align itself.
+  const uint32_t cand_offset = 37, cand_entries = (cand_offset + (uint32_t)level_cap + 11 + 1) & ~1u;
+  const size_t cap = (size_t)level_cap;
+  DevBuf<uint32_t> ds;
+  DevBuf<int> dn;
+  VSF_HIP(ds.alloc((size_t)6 * cand_entries * sizeof(uint32_t)));
+  VSF_HIP(dn.alloc(sizeof(int)));
+  VSF_HIP(hipMemset(ds, 0xA5, (size_t)6 * cand_entries * sizeof(uint32_t)));
+  std::vector<uint32_t> h1;
+  std::vector<uint2> h2;
+  uint32_t* home;  // the array's place in the scratch: block 0 (stage 1), blocks 1 and 2 (stage 2)
+  size_t bytes;
+  const void* src;
+  if (stage == 1) {
+    h1.resize(cap);
+    for (size_t i = 0; i < cap; i++) h1[i] = (key_bits[i] << 24) | (ids[i] & 0xFFFFFFu);
+    home = ds + cand_offset;
+    bytes = cap * sizeof(uint32_t);
+    src = h1.data();
+  } else {
+    h2.resize(cap);
+    for (size_t i = 0; i < cap; i++) h2[i] = make_uint2(key_bits[i], ids[i]);
+    home = ds + cand_entries + 2 * cand_offset;
+    bytes = cap * sizeof(uint2);
+    src = h2.data();
+  }
+  VSF_HIP(hipMemcpy(home, src, bytes, hipMemcpyHostToDevice));
+  if (!vsf_launch_select_form_test(form, ds, cand_entries, cand_offset, level_cap, stage, n, n_points, dn, ctx->stream))
+    return VSF_ERR_INVALID_ARG;
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(stage == 1 ? (void*)h1.data() : (void*)h2.data(), home, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(n_out, dn, sizeof(int), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    ctx->last_hip = (int)e;
+    return VSF_ERR_HIP;
+  }
+  for (size_t i = 0; i < cap; i++) {
+    key_bits[i] = stage == 1 ? h1[i] >> 24 : h2[i].x;
+    ids[i] = stage == 1 ? h1[i] & 0xFFFFFFu : h2[i].y;
+  }
+  return VSF_OK;
+}
+
 vsf_status vsf_debug_sort_trim(vsf_ctx* ctx, const vsf_dmatch* matches, int n_lists, int n, float best_percent,
                                int serial, uint64_t* pairs_out, int32_t* counts_out) {
   VsfErrorScope scope_(ctx);

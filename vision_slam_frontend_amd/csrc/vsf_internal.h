@@ -209,6 +209,9 @@ void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_leve
                        hipStream_t s);
 void vsf_launch_retain_best_test(uint2* d_data, uint32_t* d_tables, int n, int n_points, int use_lds, int mode,
                                  int* d_out_n, hipStream_t s);
+// d_scratch: [6][cand_entries] words, as one image's share of VsfDev::scratch; false: no such form
+bool vsf_launch_select_form_test(int form, uint32_t* d_scratch, uint32_t cand_entries, uint32_t cand_offset, int level_cap,
+                                 int stage, int n, int n_points, int* d_out_n, hipStream_t s);
 // Matrix-core blur (k_blur.hip, round 3): units = level << 24 | band pair << 16 | first double step << 8 | double steps.
 void vsf_launch_blur_mma(const VsfDev& d, const VsfGeom& g, const VsfImages& im, const uint32_t* d_units, int nunits,
                          const uint4* d_tcol, const uint4* d_tv, int bias, hipStream_t s);
