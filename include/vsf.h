@@ -625,10 +625,72 @@ typedef struct {
   const void* right;
   size_t left_pitch, right_pitch;
 } vsf_dev_frame;
-enum { VSF_PIX_MONO8 = 0, VSF_PIX_BAYER_RGGB8 = 1 };
+/* PIXEL FORMATS of raw frames.  The codes 2 .. 15 are unknown and STAY unknown for good (every call that takes a pixfmt
+ * answers them, negatives and codes above 22 with VSF_ERR_INVALID_ARG): new formats start at 16.
+ *   MONO8: the bytes are the gray image.
+ *   BAYER_*8, one byte per pixel: COLOR_Bayer*2BGR + COLOR_BGR2GRAY (slam_frontend_main.cc:101-106) -- imgproc's
+ * Bayer2RGB_<uchar>, bilinear, the one-pixel frame copied from its inner neighbour (columns first, then rows), then
+ * RGB2Gray<uchar>.  The order is named as sensor_msgs names it, by the first two pixels of the first two rows, i.e. by
+ * where RED sits:  RGGB (even x, even y),  GRBG (odd x, even y),  GBRG (even x, odd y),  BGGR (odd x, odd y).  An image
+ * with a side below 3 comes out all zero (OpenCV's loops leave it so); a mosaic is at most 16384 wide.
+ *   BGR8 / RGB8 (3 bytes per pixel), BGRA8 / RGBA8 (4): RGB2Gray<uchar> on the channels in the order the name gives,
+ * gray = (1868 B + 9617 G + 4899 R + 8192) >> 14; alpha is ignored.
+ *   16-bit, YUV and planar formats are not taken: the reference states no rule for them. */
+enum {
+  VSF_PIX_MONO8 = 0,
+  VSF_PIX_BAYER_RGGB8 = 1,
+  VSF_PIX_BAYER_GRBG8 = 16,
+  VSF_PIX_BAYER_GBRG8 = 17,
+  VSF_PIX_BAYER_BGGR8 = 18,
+  VSF_PIX_BGR8 = 19,
+  VSF_PIX_RGB8 = 20,
+  VSF_PIX_BGRA8 = 21,
+  VSF_PIX_RGBA8 = 22
+};
+/* Bytes per pixel of a format: 1, 3 or 4; 0 for an unknown code.  No context, no device. */
+int vsf_pixfmt_bytes_per_pixel(int pixfmt);
+/* The format of a sensor_msgs/Image encoding: "mono8", "bayer_rggb8", "bayer_grbg8", "bayer_gbrg8", "bayer_bggr8", "bgr8",
+ * "rgb8", "bgra8", "rgba8".  Anything else is VSF_ERR_UNSUPPORTED (a null pointer VSF_ERR_INVALID_ARG), *pixfmt untouched.
+ * No context, no device. */
+vsf_status vsf_pixfmt_from_encoding(const char* ros_encoding, int* pixfmt);
+/* (vsf_observe_submit_dev takes EVERY format above.  An image is width x height pixels of vsf_pixfmt_bytes_per_pixel bytes:
+ * a pitch must be >= width x that, and the launch's rule about what it reads holds for rows of that many bytes.  Mosaics of
+ * the four orders wait in the device ring as MONO8 does; packed colour waits in a device ring of big slots -- the ring
+ * vsf_observe_set_input_size builds, sized by BYTES per row -- and becomes gray inside the batch.) */
 vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame* frames, int n, int pixfmt,
                                   void* producer_stream, const vsf_calibration* calib, float best_percent, int frame_life,
                                   int64_t* tickets);
+/* RAW HOST FRAMES OF ANY PIXEL FORMAT: sensor_msgs/Image as the driver publishes it (vsf_pixfmt_from_encoding maps its
+ * `encoding`).  left / right: width x height pixels, rows stride_bytes apart, stride_bytes >= width x bytes per pixel;
+ * width x height is the stream's declared size (vsf_observe_set_input_size) or the context's.
+ *   VSF_PIX_MONO8: this IS vsf_observe_submit_stream, byte for byte and launch for launch.
+ *   Mosaics are staged and uploaded as gray frames are -- the batch's one copy -- into the buffer compressed mosaics are
+ * decoded into, and ONE launch on the copy stream (where decode, demosaic and resize run) makes the batch's gray images.
+ *   Packed colour waits in the pinned ring of big slots that a declared input size builds, sized by bytes per row (3 - 4 x
+ * the pinned memory and 3 - 4 x the bytes of the upload, which is what bounds this path); the first frame that needs more
+ * room than the slots have does what declaring a larger size does: what waits is sent, the device is waited for, the
+ * buffers are rebuilt.  One launch converts a run of such frames straight into the batch's images.
+ *   With a declared input size the order is cv::resize(to_gray(frame)): gray at the arriving size, then the resize.
+ *   BATCHES: a batch holds frames of ONE pixel format -- the rule `bayer` follows: a frame of another format sends what
+ * waits first.  Results do not depend on how frames were batched, and they are those of vsf_observe_submit_stream fed the
+ * gray images, byte for byte.
+ *   A refused call issues no ticket (*ticket = -1), books nothing and launches nothing.  VSF_ERR_INVALID_ARG: an unknown
+ * pixfmt (2 .. 15, negative, above 22), stride_bytes < width x bytes per pixel, another size than the stream's, and
+ * whatever vsf_observe_submit_stream refuses.  VSF_ERR_UNSUPPORTED: a mosaic wider than 16384, a colour image of 2^31
+ * bytes or more.
+ *   vsf_observe_stats [30] frames that came in one of the formats 16 .. 22 or as a raw host mosaic, [31] launches and copy
+ * commands issued for them (a batch's conversion, the uploads out of the big slots), [32] bytes of every buffer such a frame
+ * made the queue build or enlarge (the mosaics' buffer and the big slots: shared with the compressed and resize paths and
+ * counted in [13] / [28] too) -- all 0 for a queue that never saw such a frame. */
+vsf_status vsf_observe_submit_stream_pix(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int width,
+                                         int height, size_t stride_bytes, int pixfmt, const vsf_calibration* calib,
+                                         float best_percent, int frame_life, int64_t* ticket);
+/* The Bayer order of a stream's COMPRESSED mosaics: what vsf_observe_submit_compressed(_stream) decodes with bayer != 0 is
+ * demosaiced in this order (one of the four VSF_PIX_BAYER_* codes; anything else is VSF_ERR_INVALID_ARG).  A stream never
+ * told is RGGB, so the existing calls and their `bayer` argument mean what they meant.  Legal when
+ * vsf_observe_reset_stream is (no frame of the stream submitted and not collected, else VSF_ERR_INVALID_ARG); kept across
+ * resets, dropped when vsf_observe_set_streams changes the count. */
+vsf_status vsf_observe_set_bayer_order(vsf_ctx* ctx, int stream, int pixfmt);
 /* HBM the device ring takes in a queue of `depth` frames (0: the depth vsf_observe_configure set, or its default):
  * depth x 2 images at the staging pitch (width rounded up to 64) -- 157 MB at depth 256 and 640 x 480.  0 for a depth outside
  * [0, 1024].  No device work. */
@@ -643,7 +705,8 @@ size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth);
  * copy commands the device path issued (a submit's one launch, a batch's copies out of the ring, its demosaic where no
  * compressed frame brings one), [19] bytes of the device ring -- the last three are 0 for a queue that has seen no device
  * frame; [20] .. [22] the point cloud's (vsf_observe_set_world_points); [23] frames launched at a reduced size
- * (vsf_observe_submit_compressed_reduced with reduce > 1); [24], [25] the colour generators' (vsf_observe_set_debug_seeds) }. */
+ * (vsf_observe_submit_compressed_reduced with reduce > 1); [24], [25] the colour generators' (vsf_observe_set_debug_seeds);
+ * [26] .. [29] vsf_observe_set_input_size's; [30] .. [32] the pixel formats' (vsf_observe_submit_stream_pix) }. */
 vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n);
 /* The queue's debug images (the Frontend's, slam_frontend.cc:74-115, 167-171, 458-466).  With the switch on, every batch's
  * tail also builds each frame's drawing operations on the device from the filtered keypoints and sorted pairs it holds,
@@ -862,6 +925,29 @@ vsf_status vsf_reduced_size(int w, int h, int reduce, int* rw, int* rh);
 vsf_status vsf_bayer_bg_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height,
                                           size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst,
                                           size_t dst_image_stride, size_t dst_row_stride);
+/* The same for every pixel format (VSF_PIX_*, defined above vsf_observe_submit_dev): n raw images of width x height pixels
+ * resident in HBM -> their gray images, in ONE launch on the context's stream.  VSF_PIX_BAYER_RGGB8 is
+ * vsf_bayer_bg_to_gray_batch_dev, launch for launch; VSF_PIX_MONO8 is a copy.
+ *   STRIDES: image i at base + i * image_stride, rows row_stride bytes apart; both bases and all four strides are multiples
+ * of 4.  A source row is width x vsf_pixfmt_bytes_per_pixel(pixfmt) bytes: src_row_stride >= that;
+ * dst_row_stride >= (width + 3) & ~3; image_stride >= row_stride x height on either side.  width <= 16384 (the demosaic's
+ * limit, kept for every format), height and n_images <= 65535, src_row_stride x height < 2^31.
+ *   READS: mosaics as vsf_bayer_bg_to_gray_batch_dev reads them (whole dwords of a row, its padding included, inside the
+ * image's row_stride x height bytes; padding never reaches a pixel of the result).  Packed colour and MONO8: only aligned
+ * dwords that begin before the end of the image's last row, rounded up to 4 bytes.
+ *   WRITES: bytes [0, (width + 3) & ~3) of each of the height destination rows and nothing else.  The up to 3 bytes behind
+ * column width - 1 are zero for packed colour and MONO8 and unspecified for mosaics.
+ *   COST: one pass, bpp bytes read and 1 written per pixel; no scratch memory.
+ *   VSF_ERR_INVALID_ARG: a null pointer, an unknown pixfmt, a size or stride outside these rules; nothing is launched then. */
+vsf_status vsf_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int pixfmt,
+                                 size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst, size_t dst_image_stride,
+                                 size_t dst_row_stride);
+/* The same HOST TO HOST (upload, the one launch, download; synchronous): n raw images in host memory -> n gray images of
+ * width x height bytes in host memory.  ANY addresses and strides with src_row_stride >= width x bytes per pixel and
+ * dst_row_stride >= width (with more than one image: image strides that hold an image); exactly width bytes of each
+ * destination row are written.  width <= 16384, height <= 32767.  What slam::Frontend's per-call mode converts with. */
+vsf_status vsf_to_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int pixfmt, size_t src_image_stride,
+                       size_t src_row_stride, uint8_t* dst, size_t dst_image_stride, size_t dst_row_stride);
 
 /* cv::resize(src, dst, Size(dst_width, dst_height)) of OpenCV 3.2 with its default interpolation (INTER_LINEAR) on CV_8UC1,
  * for n images resident in HBM, device to device, in ONE launch (k_resize.hip).  Independent of the context's own image

@@ -55,6 +55,8 @@ EXPORTS = [
     "vsf_observe_set_debug_seeds", "vsf_observe_set_stream_cam_to_robot",
     "vsf_resize_gray_batch_dev", "vsf_observe_set_input_size", "vsf_resize_gray",
     "vsf_debug_describe_form",
+    "vsf_pixfmt_bytes_per_pixel", "vsf_pixfmt_from_encoding", "vsf_to_gray_batch_dev",
+    "vsf_observe_submit_stream_pix", "vsf_observe_set_bayer_order", "vsf_to_gray",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -67,9 +69,10 @@ OBSERVE_STATS = ("frames", "batches", "max_batch", "solo", "forced", "slot_waits
                  "multi_stream_batches", "device_frames", "device_commands", "device_ring_bytes",
                  "world_points_frames", "world_points_commands", "world_points_ring_bytes", "reduced_frames",
                  "seeded_colour_frames", "colour_commands", "resized_frames", "resize_commands", "resize_bytes",
-                 "multi_size_batches")
-# vsf_observe_submit_dev's pixel formats (include/vsf.h)
+                 "multi_size_batches", "pixfmt_frames", "pixfmt_commands", "pixfmt_bytes")
+# pixel formats of raw frames (include/vsf.h; 2 .. 15 stay unknown)
 PIX_MONO8, PIX_BAYER_RGGB8 = 0, 1
+PIX_BAYER_GRBG8, PIX_BAYER_GBRG8, PIX_BAYER_BGGR8, PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8 = range(16, 23)
 
 
 class VsfParams(C.Structure):
@@ -125,6 +128,25 @@ def device_image(t, width: int, height: int, device: int):
     return int(t.data_ptr()), int(t.stride(0)) if height > 1 else max(int(t.stride(0)), width)
 
 
+def device_image_pix(t, width: int, height: int, device: int, pixfmt: int):
+    """device_image for any PIX_* format: packed colour is a (height, width, 3 or 4) torch.uint8 tensor whose pixels are dense
+    (stride(2) == 1, stride(1) == bytes per pixel; any stride(0) >= width * bytes per pixel)."""
+    bpp = {PIX_BGR8: 3, PIX_RGB8: 3, PIX_BGRA8: 4, PIX_RGBA8: 4}.get(pixfmt, 1)
+    if bpp == 1:
+        return device_image(t, width, height, device)
+    if not (hasattr(t, "data_ptr") and hasattr(t, "stride") and hasattr(t, "is_cuda")):
+        raise ValueError("a device image is a torch tensor, not %s" % type(t).__name__)
+    if str(t.dtype) != "torch.uint8":
+        raise ValueError("a device image is torch.uint8, not %s" % t.dtype)
+    if not t.is_cuda or (t.device.index or 0) != device:
+        raise ValueError("a device image lives on GPU %d, not on %s" % (device, t.device))
+    if t.dim() != 3 or tuple(t.shape) != (height, width, bpp):
+        raise ValueError("a device image of this format is %d x %d x %d, not %s" % (height, width, bpp, tuple(t.shape)))
+    if t.stride(2) != 1 or t.stride(1) != bpp or (height > 1 and t.stride(0) < width * bpp):
+        raise ValueError("a colour device image has dense pixels and rows, not strides %s" % (tuple(t.stride()),))
+    return int(t.data_ptr()), int(t.stride(0)) if height > 1 else max(int(t.stride(0)), width * bpp)
+
+
 class VsfDrawCanvas(C.Structure):
     """vsf_draw_canvas: GRAY2BGR of src0 (and src1 to its right) with ops[op_begin, op_begin + op_count) drawn on it."""
     _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
@@ -150,6 +172,18 @@ def reduced_size(width: int, height: int, reduce: int):
     w, h = C.c_int(0), C.c_int(0)
     st = lib().vsf_reduced_size(width, height, reduce, C.byref(w), C.byref(h))
     return st, int(w.value), int(h.value)
+
+
+def pixfmt_bytes_per_pixel(pixfmt: int) -> int:
+    """vsf_pixfmt_bytes_per_pixel: 1, 3 or 4; 0 for an unknown code.  No context, no device."""
+    return int(lib().vsf_pixfmt_bytes_per_pixel(pixfmt))
+
+
+def pixfmt_from_encoding(encoding: str):
+    """vsf_pixfmt_from_encoding: (status, PIX_* code or None) of a sensor_msgs/Image encoding.  No context, no device."""
+    code = C.c_int(-1)
+    st = lib().vsf_pixfmt_from_encoding(encoding.encode(), C.byref(code))
+    return st, (int(code.value) if st == VSF_OK else None)
 
 
 def probe_compressed_reduced(data: bytes, reduce: int, width: int, height: int, cap_per_image: int, force_serial: bool = False):
@@ -257,6 +291,11 @@ def lib() -> C.CDLL:
         L.vsf_remove_ambig_stereo_batch_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.c_float, vp, vp, vp, vp, vp, vp]
         L.vsf_feature_matches_batch_dev.argtypes = [vp, vp, vp, sz, vp, vp, i32, C.c_float, vp, vp]
         L.vsf_bayer_bg_to_gray_batch_dev.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_to_gray_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_to_gray.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_pixfmt_bytes_per_pixel.argtypes = [i32]
+        L.vsf_pixfmt_bytes_per_pixel.restype = C.c_int
+        L.vsf_pixfmt_from_encoding.argtypes = [C.c_char_p, ip]
         L.vsf_jpeg_encode_capacity.argtypes = [i32, i32, i32]
         L.vsf_jpeg_encode_capacity.restype = sz
         L.vsf_jpeg_encode_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, i32, vp, sz, vp]
@@ -300,6 +339,9 @@ def lib() -> C.CDLL:
         L.vsf_resize_gray.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, i32, i32, sz, sz]
         L.vsf_observe_submit_stream.argtypes = [vp, i32, vp, vp, i32, i32, sz, C.POINTER(VsfCalibration), C.c_float, i32,
                                                 C.POINTER(C.c_int64)]
+        L.vsf_observe_submit_stream_pix.argtypes = [vp, i32, vp, vp, i32, i32, sz, i32, C.POINTER(VsfCalibration), C.c_float, i32,
+                                                    C.POINTER(C.c_int64)]
+        L.vsf_observe_set_bayer_order.argtypes = [vp, i32, i32]
         L.vsf_observe_submit_compressed_stream.argtypes = [vp, i32, vp, sz, vp, sz, i32, C.POINTER(VsfCalibration), C.c_float,
                                                            i32, C.POINTER(C.c_int64)]
         L.vsf_observe_submit_dev.argtypes = [vp, i32, C.POINTER(VsfDevFrame), i32, i32, vp, C.POINTER(VsfCalibration), C.c_float,
@@ -738,6 +780,33 @@ class Context:
             raise VsfError(st, "vsf_observe_submit_stream", lib().vsf_last_hip_error(self._h))
         return (st, int(t.value)) if allow_status else int(t.value)
 
+    def observe_submit_stream_pix(self, stream: int, left: np.ndarray, right: np.ndarray, pixfmt: int, calib: VsfCalibration,
+                                  best_percent: float = 0.3, frame_life: int = 10, allow_status=(), width: int = None,
+                                  stride: int = None):
+        """vsf_observe_submit_stream_pix: one raw host frame of any PIX_* format -- (h, w) arrays for MONO8 and the Bayer
+        orders, (h, w, 3 or 4) for packed colour.  width / stride override what the arrays say (for refusal tests).  Returns
+        the ticket -- or, with `allow_status`, (status, ticket)."""
+        left, right = np.asarray(left, np.uint8), np.asarray(right, np.uint8)
+        if left.strides[-1] != 1 or (left.ndim == 3 and left.strides[1] != left.shape[2]):
+            left = np.ascontiguousarray(left)
+        if right.strides != left.strides or right.shape != left.shape:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+        assert left.shape == right.shape and left.strides == right.strides and left.ndim in (2, 3)
+        t = C.c_int64(-1)
+        st = lib().vsf_observe_submit_stream_pix(self._h, stream, _p(left), _p(right), left.shape[1] if width is None else width,
+                                                 left.shape[0], left.strides[0] if stride is None else stride, pixfmt,
+                                                 C.byref(calib), float(np.float32(best_percent)), frame_life, C.byref(t))
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_submit_stream_pix", lib().vsf_last_hip_error(self._h))
+        return (st, int(t.value)) if allow_status else int(t.value)
+
+    def observe_set_bayer_order(self, stream: int, pixfmt: int, allow_status=()) -> int:
+        """vsf_observe_set_bayer_order: the order of the mosaics `stream`'s compressed submits carry with bayer=True."""
+        st = lib().vsf_observe_set_bayer_order(self._h, stream, pixfmt)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, "vsf_observe_set_bayer_order", lib().vsf_last_hip_error(self._h))
+        return st
+
     def observe_submit_compressed_stream(self, stream: int, left: bytes, right: bytes, calib: VsfCalibration,
                                          bayer: bool = False, best_percent: float = 0.3, frame_life: int = 10,
                                          allow_status=()):
@@ -764,7 +833,7 @@ class Context:
         arr = (VsfDevFrame * max(len(frames), 1))()
         for i, f in enumerate(frames):
             if len(f) == 2:
-                (lp, ls), (rp, rs) = (device_image(t, w, h, self.device) for t in f)
+                (lp, ls), (rp, rs) = (device_image_pix(t, w, h, self.device, pixfmt) for t in f)
             else:
                 lp, ls, rp, rs = (int(v) for v in f)
             arr[i] = VsfDevFrame(lp, rp, ls, rs)
@@ -1014,6 +1083,21 @@ class Context:
         self._check(lib().vsf_bayer_bg_to_gray_batch_dev(self._h, _p(d_src), n_images, width, height, src_image_stride,
                                                          src_row_stride, _p(d_dst), dst_image_stride, dst_row_stride),
                     "vsf_bayer_bg_to_gray_batch_dev")
+
+    def to_gray(self, imgs: np.ndarray, pixfmt: int) -> np.ndarray:
+        """vsf_to_gray: (n, h, w) or (n, h, w, 3 or 4) raw images in host memory -> (n, h, w) gray images."""
+        imgs = np.ascontiguousarray(imgs, np.uint8)
+        n, h, w = imgs.shape[:3]
+        row = w * (imgs.shape[3] if imgs.ndim == 4 else 1)
+        out = np.zeros((n, h, w), np.uint8)
+        self._check(lib().vsf_to_gray(self._h, _p(imgs), n, w, h, pixfmt, row * h, row, _p(out), w * h, w), "vsf_to_gray")
+        return out
+
+    def to_gray_batch_dev(self, d_src: int, n_images: int, width: int, height: int, pixfmt: int, src_image_stride: int,
+                          src_row_stride: int, d_dst: int, dst_image_stride: int, dst_row_stride: int) -> int:
+        """vsf_to_gray_batch_dev: raw images of any PIX_* format resident in HBM -> gray, one launch.  Returns the status."""
+        return lib().vsf_to_gray_batch_dev(self._h, _p(d_src), n_images, width, height, pixfmt, src_image_stride,
+                                           src_row_stride, _p(d_dst), dst_image_stride, dst_row_stride)
 
     def debug_retain_best(self, keys: np.ndarray, n_points: int, use_lds: bool = False, mode: int = 0):
         """retainBest on the GPU; returns (keys, ids) of the survivors in the order the GPU left them."""

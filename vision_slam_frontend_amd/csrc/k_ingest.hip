@@ -26,21 +26,22 @@ struct BayerArgs {
   size_t dst_image_stride;
   int dst_pitch;
   int w, h;
+  int swap_rb, flip_rows;  // the mosaic's order as two wave-uniform flags (see bayer_gray_kernel)
 };
 
 // gray of interior pixel (x, y), 1 <= x <= w - 2, 1 <= y <= h - 2 (scalar; only for a last column whose source column
 // belongs to another wave, i.e. widths of the form 256 k + 1)
-__device__ __forceinline__ uint32_t gray_at(const uint8_t* img, int pitch, int x, int y) {
+__device__ __forceinline__ uint32_t gray_at(const uint8_t* img, int pitch, int x, int y, bool swap_rb, bool flip_rows) {
   const uint8_t* c = img + (size_t)y * pitch + x;
   const uint8_t* u = c - pitch;
   const uint8_t* d = c + pitch;
   const int cross = (u[0] + d[0] + c[-1] + c[1] + 2) >> 2, diag = (u[-1] + u[1] + d[-1] + d[1] + 2) >> 2;
   const int hor = (c[-1] + c[1] + 1) >> 1, ver = (u[0] + d[0] + 1) >> 1, cen = c[0];
-  const bool ex = x & 1, ey = y & 1;
+  const bool ex = x & 1, ey = (y & 1) != flip_rows;
   const int G = ex == ey ? cross : cen;
   const int B = ey ? (ex ? cen : hor) : (ex ? ver : diag);
   const int R = ey ? (ex ? diag : ver) : (ex ? hor : cen);
-  return (uint32_t)(1868 * B + 9617 * G + 4899 * R + 8192) >> 14;
+  return (uint32_t)((swap_rb ? 4899 : 1868) * B + 9617 * G + (swap_rb ? 1868 : 4899) * R + 8192) >> 14;
 }
 
 __device__ __forceinline__ v2u pick(uint32_t hi, uint32_t lo, uint32_t sel) {
@@ -49,7 +50,16 @@ __device__ __forceinline__ v2u pick(uint32_t hi, uint32_t lo, uint32_t sel) {
 
 constexpr int kStripRows = 16;  // output rows per wave
 
-__global__ __launch_bounds__(256) void bayer_bg_gray_kernel(BayerArgs a) {
+// The four orders are one loop (as in OpenCV, which starts the same loop with two other flags).  Stated for RGGB -- red at
+// (even x, even y), blue at (odd, odd) --, the others are
+//   BGGR: red and blue exchanged;   GBRG: the rows' parity flipped;   GRBG: both.
+// Both flags are kernel arguments, so they are wave-uniform: they select which constant goes into which v_dot2 operand
+// (a few scalar selects per row) and never touch the vector arithmetic.  kAnyOrder = false is the RGGB instantiation with both
+// flags folded away at compile time: measured in alternating runs, the general form's median on 512 RGGB mosaics of 640 x 480 lay
+// 0.05 us (of 128) above the parent's slowest run, so RGGB keeps the code it had (NOTES.md).
+template <bool kAnyOrder>
+__global__ __launch_bounds__(256) void bayer_gray_kernel(BayerArgs a) {
+  const bool swap_rb = kAnyOrder && a.swap_rb, flip_rows = kAnyOrder && a.flip_rows;
   // wave = 256 columns (4 per lane) x 16 rows, walked top to bottom with a three-row register window: a new row costs
   // three dword loads per lane (requested one row ahead) instead of nine, and a wave lives long enough to cover the
   // memory latency (one short-lived wave per row ran at a quarter of this rate).
@@ -91,14 +101,14 @@ __global__ __launch_bounds__(256) void bayer_bg_gray_kernel(BayerArgs a) {
   auto dot = [](v2u q, uint32_t wpair, uint32_t acc) -> uint32_t {
     return __builtin_amdgcn_udot2(q, __builtin_bit_cast(v2u, wpair), acc, false);
   };
-  // One output row.  A pair of pixels is (even x, odd x) in the (low, high) halves of every packed quantity; a pixel's
+  // One output row (of an RGGB mosaic; the other orders: above).  A pair of pixels is (even x, odd x) in the (low, high) halves of every packed quantity; a pixel's
   // gray is three weighted quantities of its half, so three v_dot2_u32_u16 with the weight in that half and zero in the
   // other give it without unpacking.  Which quantity carries which weight depends on the row parity only (scalar):
   //   odd row : even x = green (G cen, B hor, R ver),  odd x = blue site (B cen, G cross, R diag)
   //   even row: even x = red site (R cen, G cross, B diag),  odd x = green (G cen, R hor, B ver)
   auto yc_of = [&](int y) -> int { return min(max(y, 1), a.h - 2); };
   auto emit = [&](int y, const Row& U, const Row& C, const Row& D, bool ey) {
-    const uint32_t kB = 1868u, kG = 9617u, kR = 4899u;
+    const uint32_t kB = swap_rb ? 4899u : 1868u, kG = 9617u, kR = swap_rb ? 1868u : 4899u;
     // weights of (cen, cross, diag, hor, ver) for the even-x pixel (low half) ...
     const uint32_t e_cen = ey ? kG : kR, e_cross = ey ? 0u : kG, e_diag = ey ? 0u : kB, e_hor = ey ? kB : 0u,
                    e_ver = ey ? kR : 0u;
@@ -130,7 +140,7 @@ __global__ __launch_bounds__(256) void bayer_bg_gray_kernel(BayerArgs a) {
     uint32_t g = gpair[0] | (gpair[1] << 16);
     const uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)g, 0x138, 0xF, 0xF, false);  // lane - 1's dword
     if (x4 == 0) g = (g & 0xFFFFFF00u) | ((g >> 8) & 0xFFu);                      // column 0 <- column 1
-    if (jr == 0) g = (g & 0xFFFFFF00u) | (lone_right ? gray_at(img, a.src_pitch, a.w - 2, yc_of(y)) : (left >> 24));
+    if (jr == 0) g = (g & 0xFFFFFF00u) | (lone_right ? gray_at(img, a.src_pitch, a.w - 2, yc_of(y), swap_rb, flip_rows) : (left >> 24));
     if (jr >= 1 && jr <= 3) {                                                     // column w - 1 <- column w - 2
       const uint32_t sh = 8u * (uint32_t)jr;
       g = (g & ~(0xFFu << sh)) | (((g >> (sh - 8u)) & 0xFFu) << sh);
@@ -145,12 +155,74 @@ __global__ __launch_bounds__(256) void bayer_bg_gray_kernel(BayerArgs a) {
     const int ycn = min(max(y + 1, 1), a.h - 2);  // next output row's centre row (wave-uniform)
     Row N = D;
     if (ycn != yc) N = load(ycn + 1);  // requested before this row's arithmetic
-    emit(y, U, C, D, yc & 1);
+    emit(y, U, C, D, (yc & 1) != flip_rows);
     if (ycn != yc) {
       U = C;
       C = D;
       D = N;
       yc = ycn;
+    }
+  }
+}
+
+// Packed colour (bgr8 / rgb8 / bgra8 / rgba8) -> gray, color.cpp RGB2Gray<uchar> on the channels the name gives:
+//   gray = (1868 B + 9617 G + 4899 R + 8192) >> 14,  alpha ignored.
+// BPP bytes read + 1 written per pixel.  A lane owns 4 adjacent pixels: BPP aligned dwords in (buffer loads, lane offset in a
+// VGPR, row offset in an SGPR), one aligned dword out.  Per pixel one v_perm puts (c0, c1) into the two 16-bit halves of a
+// register and another isolates c2 -- for 3-byte pixels the selectors reach across the dword seam --, then
+// v_dot2_u32_u16 (c0, c1) . (w0, w1) + 8192 and v_mad_u32_u24 c2 * w2.  bgr / rgb differ in w0 <-> w2 only (wave-uniform).
+// A wave owns 256 columns x kStripRows rows and requests kPackedRows rows (up to 16 dwords per lane) before the first
+// sum, so it lives through several memory round trips (cf. bayer_gray_kernel).  BPP = 1 is the copy of VSF_PIX_MONO8.
+// Source and destination are in the queue's staging layout: bases and pitches are multiples of 4.  A dword is read only
+// if it begins before the end of the image's last row rounded up to 4 bytes (the descriptor's range; what lies outside
+// reads as zero); columns >= w of a row's last dword are written as zero.
+constexpr int kPackedRows = 4;  // rows in flight per lane
+
+template <int BPP>
+__global__ __launch_bounds__(256) void packed_gray_kernel(BayerArgs a) {
+  const int strip = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6)), image = blockIdx.z;
+  const int x4 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
+  const int y0 = strip * kStripRows, y1 = min(y0 + kStripRows, a.h);
+  if (x4 >= a.w || y0 >= a.h) return;
+  const uint32_t src_bytes = (uint32_t)(a.h - 1) * (uint32_t)a.src_pitch + (((uint32_t)a.w * BPP + 3u) & ~3u);
+  const uint32_t dst_bytes = (uint32_t)(a.h - 1) * (uint32_t)a.dst_pitch + (((uint32_t)a.w + 3u) & ~3u);
+  const __amdgpu_buffer_rsrc_t src_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint8_t*>(a.src) + (size_t)image * a.src_image_stride, 0, src_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t dst_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(a.dst + (size_t)image * a.dst_image_stride, 0, dst_bytes, 0x00020000);
+  const uint32_t w0 = a.swap_rb ? 4899u : 1868u, w2 = a.swap_rb ? 1868u : 4899u;  // swap_rb: the first channel is red
+  const v2u w01 = __builtin_bit_cast(v2u, w0 | (9617u << 16));
+  const int left = a.w - x4;  // pixels of the row from this lane's first on
+  const uint32_t keep = left >= 4 ? 0xFFFFFFFFu : (1u << (8 * left)) - 1u;
+  for (int y = y0; y < y1; y += kPackedRows) {
+    uint32_t d[kPackedRows][BPP];
+#pragma unroll
+    for (int u = 0; u < kPackedRows; u++)
+#pragma unroll
+      for (int k = 0; k < BPP; k++)
+        d[u][k] = y + u < y1 ? __builtin_amdgcn_raw_buffer_load_b32(src_rsrc, (uint32_t)x4 * BPP + 4u * k,
+                                                                    (uint32_t)(y + u) * (uint32_t)a.src_pitch, 0)
+                             : 0u;
+#pragma unroll
+    for (int u = 0; u < kPackedRows; u++) {
+      if (y + u >= y1) break;  // (wave-uniform)
+      uint32_t g;
+      if (BPP == 1) {
+        g = d[u][0];
+      } else {
+        g = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          // pixel j begins at byte BPP j of the lane's run: byte k of dword lo, its channels at k, k + 1, k + 2 of lo | hi
+          const int o = BPP * j, k = o & 3;
+          const uint32_t lo = d[u][o >> 2], hi = d[u][min((o >> 2) + 1, BPP - 1)];
+          const v2u c01 = pick(hi, lo, 0x0C000C00u | (uint32_t)k | ((uint32_t)(k + 1) << 16));
+          const uint32_t c2 = __builtin_amdgcn_perm(hi, lo, 0x0C0C0C00u | (uint32_t)(k + 2));
+          const uint32_t sum = __builtin_amdgcn_udot2(c01, w01, 8192u, false) + __umul24(c2, w2);
+          g |= (sum >> 14) << (8 * j);
+        }
+      }
+      __builtin_amdgcn_raw_buffer_store_b32(g & keep, dst_rsrc, (uint32_t)x4, (uint32_t)(y + u) * (uint32_t)a.dst_pitch, 0);
     }
   }
 }
@@ -175,7 +247,7 @@ __global__ __launch_bounds__(256) void ingest_finish_kernel(uint8_t* __restrict_
 // never straddles a page, so a row that ends on the last byte of an allocation is read to that byte and no further --;
 // what is not read counts as zero, and the columns >= w of the last 16-byte piece are written as zero.
 // A workgroup walks kIngestRows rows of one image as a flat list of 16-byte pieces, four per lane in flight (20 dword
-// loads) before the first store, so a wave lives through several memory round trips (cf. bayer_bg_gray_kernel above).
+// loads) before the first store, so a wave lives through several memory round trips (cf. bayer_gray_kernel above).
 struct IngestRingArgs {
   uint8_t* ring;
   size_t image_stride;
@@ -247,7 +319,42 @@ void vsf_launch_bayer_bg_gray(const uint8_t* d_src, int n, int w, int h, size_t 
                               uint8_t* d_dst, size_t dst_image_stride, int dst_pitch, hipStream_t s) {
   BayerArgs a{d_src, src_image_stride, src_pitch, d_dst, dst_image_stride, dst_pitch, w, h};
   const int nstrips = (h + kStripRows - 1) / kStripRows;
-  hipLaunchKernelGGL(bayer_bg_gray_kernel, dim3((w + 255) / 256, (nstrips + 3) / 4, n), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(bayer_gray_kernel<false>, dim3((w + 255) / 256, (nstrips + 3) / 4, n), dim3(256), 0, s, a);
+}
+
+// Any known pixel format -> gray (an unknown one launches nothing: the callers have refused it).  src_pitch >= w * bpp.
+void vsf_launch_to_gray(int pixfmt, const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch,
+                        uint8_t* d_dst, size_t dst_image_stride, int dst_pitch, hipStream_t s) {
+  BayerArgs a{d_src, src_image_stride, src_pitch, d_dst, dst_image_stride, dst_pitch, w, h, 0, 0};
+  const int nstrips = (h + kStripRows - 1) / kStripRows;
+  const dim3 grid((w + 255) / 256, (nstrips + 3) / 4, n), block(256);
+  switch (pixfmt) {
+    case VSF_PIX_BAYER_RGGB8:
+      hipLaunchKernelGGL(bayer_gray_kernel<false>, grid, block, 0, s, a);
+      break;
+    case VSF_PIX_BAYER_GRBG8:
+    case VSF_PIX_BAYER_GBRG8:
+    case VSF_PIX_BAYER_BGGR8:
+      a.swap_rb = pixfmt == VSF_PIX_BAYER_GRBG8 || pixfmt == VSF_PIX_BAYER_BGGR8;
+      a.flip_rows = pixfmt == VSF_PIX_BAYER_GRBG8 || pixfmt == VSF_PIX_BAYER_GBRG8;
+      hipLaunchKernelGGL(bayer_gray_kernel<true>, grid, block, 0, s, a);
+      break;
+    case VSF_PIX_MONO8:
+      hipLaunchKernelGGL(packed_gray_kernel<1>, grid, block, 0, s, a);
+      break;
+    case VSF_PIX_BGR8:
+    case VSF_PIX_RGB8:
+      a.swap_rb = pixfmt == VSF_PIX_RGB8;
+      hipLaunchKernelGGL(packed_gray_kernel<3>, grid, block, 0, s, a);
+      break;
+    case VSF_PIX_BGRA8:
+    case VSF_PIX_RGBA8:
+      a.swap_rb = pixfmt == VSF_PIX_RGBA8;
+      hipLaunchKernelGGL(packed_gray_kernel<4>, grid, block, 0, s, a);
+      break;
+    default:
+      break;
+  }
 }
 
 // (pitch and image_stride are multiples of 4 and rows * pitch <= image_stride: the queue's staging layout)

@@ -145,7 +145,8 @@ struct vsf_ctx {
     uint8_t kind[2] = {0, 0};    // left / right: 0 a raw image in h_img, VSF_FILE_JPEG / VSF_FILE_PNG: a file in h_cmp,
                                  // kObserveKindDevice (both): the images are in the slot of the device ring d_ring
     uint32_t nbytes[2] = {0, 0};  // ... and the files' sizes
-    bool bayer = false;          // compressed and device frames: the (decoded) images are bayer_rggb8 mosaics
+    int pixfmt = 0;              // VSF_PIX_*: what the (decoded) images are -- not MONO8: they become gray inside the batch
+    bool pix_new = false;        // vsf_observe_stats [30]: it came in a format or through a call the queue did not have before
     int in_w = 0, in_h = 0;      // the size it was handed in at (vsf_observe_set_input_size), 0 x 0: the context's
     uint8_t reduce = 1;          // compressed frames: both files decode at 1 / reduce (vsf_observe_submit_compressed_reduced)
     int dev_event = -1;          // device frames: the slot whose event in dev_ev follows the copy into the ring ...
@@ -261,6 +262,7 @@ struct vsf_ctx {
     std::vector<uint8_t> rs_kinds;
     std::vector<uint8_t> run_kinds;          // launch_batch's: the batch's kinds as observe_batch_runs takes them ...
     std::vector<vsfi::ObserveRun> runs;      // ... and splits them
+    bool pix_seen = false;                   // a frame with pix_new has been submitted (vsf_observe_stats [30] .. [32])
     int64_t stat_dev_commands = 0;           // the caller's share of vsf_observe_stats value 18 (the submits' launches)
     size_t out_cap = 0, out_stride = 0;
     ObserveBatch batch[kObserveBatchSlots];
@@ -287,6 +289,9 @@ struct vsf_ctx {
   // vsf_observe_set_input_size: the size a stream's frames arrive at (0 x 0: the context's), brought to the context's by
   // k_resize.hip inside the batch.  Kept across resets, dropped when vsf_observe_set_streams changes the count.
   int ob_in_w[VSF_OBSERVE_MAX_STREAMS] = {0}, ob_in_h[VSF_OBSERVE_MAX_STREAMS] = {0};
+  // vsf_observe_set_bayer_order: the order of a stream's compressed mosaics (`bayer` != 0); RGGB until told otherwise.  Kept
+  // and dropped as the declared sizes are.
+  int ob_bayer_order[VSF_OBSERVE_MAX_STREAMS] = {0};  // (0: never told)
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----

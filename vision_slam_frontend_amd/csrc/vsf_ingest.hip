@@ -208,6 +208,28 @@ vsf_status vsf_bayer_bg_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, in
   return record_ingest_done(ctx);
 }
 
+// Every raw pixel format -> gray (k_ingest.hip): the four Bayer orders, packed colour, and the copy MONO8 is.
+vsf_status vsf_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int pixfmt,
+                                 size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst, size_t dst_image_stride,
+                                 size_t dst_row_stride) {
+  VsfErrorScope scope_(ctx);
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (!ctx || !d_src || !d_dst || bpp == 0 || n_images < 1 || width < 1 || height < 1 || width > 16384 || height > 65535 ||
+      n_images > 65535)
+    return VSF_ERR_INVALID_ARG;
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 3) || (src_image_stride & 3) || (src_row_stride & 3) ||
+      (dst_image_stride & 3) || (dst_row_stride & 3) || src_row_stride < (size_t)width * (size_t)bpp ||
+      dst_row_stride < (size_t)((width + 3) & ~3) || src_row_stride * (size_t)height > 0x7FFFFFFF ||
+      dst_row_stride * (size_t)height > 0x7FFFFFFF || src_image_stride < src_row_stride * (size_t)height ||
+      dst_image_stride < dst_row_stride * (size_t)height)
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  vsf_launch_to_gray(pixfmt, d_src, n_images, width, height, src_image_stride, (int)src_row_stride, d_dst, dst_image_stride,
+                     (int)dst_row_stride, ctx->stream);
+  VSF_STICKY();
+  return record_ingest_done(ctx);
+}
+
 // cv::resize(src, dst, Size(dst_width, dst_height)), INTER_LINEAR on CV_8UC1 (k_resize.hip): what cv::imdecode's reduced
 // modes do to a PNG, and how a camera of another size than the context's gets in.
 vsf_status vsf_resize_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int src_width, int src_height,
@@ -259,6 +281,44 @@ vsf_status vsf_resize_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int s
   for (size_t i = 0; i < n; i++)
     VSF_HIP(hipMemcpy2DAsync(dst + i * dst_image_stride, dst_row_stride, d_dst + i * d_img, dp, (size_t)dst_width,
                              (size_t)dst_height, hipMemcpyDeviceToHost, ctx->stream));
+  VSF_HIP(hipStreamSynchronize(ctx->stream));
+  VSF_STICKY();
+  return VSF_OK;
+}
+
+// vsf_to_gray_batch_dev host to host (the per-call mode's way in for frames that are not gray): upload, the one launch, download.
+vsf_status vsf_to_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int pixfmt, size_t src_image_stride,
+                       size_t src_row_stride, uint8_t* dst, size_t dst_image_stride, size_t dst_row_stride) {
+  VsfErrorScope scope_(ctx);
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (!ctx || !src || !dst || bpp == 0 || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 16384 ||
+      height > 32767 || src_row_stride < (size_t)width * (size_t)bpp || dst_row_stride < (size_t)width)
+    return VSF_ERR_INVALID_ARG;
+  const size_t n = (size_t)n_images, row = (size_t)width * (size_t)bpp;
+  if (n > 1 && (src_image_stride < (size_t)(height - 1) * src_row_stride + row ||
+                dst_image_stride < (size_t)(height - 1) * dst_row_stride + (size_t)width))
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // device staging: sources | destinations, rows at a multiple of 4 on both sides (the kernels' rule)
+  const size_t sp = (row + 3) & ~(size_t)3, dp = ((size_t)width + 3) & ~(size_t)3;
+  const size_t s_img = (sp * (size_t)height + 15) & ~(size_t)15, d_img = (dp * (size_t)height + 15) & ~(size_t)15;
+  if (s_img > 0x7FFFFFFFu) return VSF_ERR_INVALID_ARG;
+  const size_t need = n * (s_img + d_img);
+  VsfEncodeScratch& e = ctx->encode;
+  if (need > e.staging_cap) {
+    const vsf_status gs = grow_scratch(ctx, e.staging, need);
+    if (gs != VSF_OK) return gs;
+    e.staging_cap = need;
+  }
+  uint8_t* d_src = e.staging;
+  uint8_t* d_dst = d_src + n * s_img;
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(d_src + i * s_img, sp, src + i * src_image_stride, src_row_stride, row, (size_t)height,
+                             hipMemcpyHostToDevice, ctx->stream));
+  vsf_launch_to_gray(pixfmt, d_src, n_images, width, height, s_img, (int)sp, d_dst, d_img, (int)dp, ctx->stream);
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(dst + i * dst_image_stride, dst_row_stride, d_dst + i * d_img, dp, (size_t)width, (size_t)height,
+                             hipMemcpyDeviceToHost, ctx->stream));
   VSF_HIP(hipStreamSynchronize(ctx->stream));
   VSF_STICKY();
   return VSF_OK;

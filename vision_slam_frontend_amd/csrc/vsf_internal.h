@@ -188,6 +188,9 @@ struct VsfSideStream {
 };
 void vsf_launch_bayer_bg_gray(const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch,
                               uint8_t* d_dst, size_t dst_image_stride, int dst_pitch, hipStream_t s);
+// ... and for every VSF_PIX_* format (RGGB: the launch above; MONO8: a copy); src_pitch >= w * bytes per pixel
+void vsf_launch_to_gray(int pixfmt, const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch,
+                        uint8_t* d_dst, size_t dst_image_stride, int dst_pitch, hipStream_t s);
 // `hook` (single chain only, side == NULL): called once, right behind the launch that produces level hook->level (0: before
 // the first launch) -- the caller records an event there and starts work on the levels that exist by then.
 struct VsfPyramidHook {

@@ -278,6 +278,11 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   return VSF_OK;
 }
 
+bool pix_is_bayer(int pixfmt) {
+  return pixfmt == VSF_PIX_BAYER_RGGB8 || pixfmt == VSF_PIX_BAYER_GRBG8 || pixfmt == VSF_PIX_BAYER_GBRG8 ||
+         pixfmt == VSF_PIX_BAYER_BGGR8;
+}
+
 // The pinned ring the compressed files wait in (and, for bayer_rggb8 frames, the buffer their mosaics are decoded into):
 // built by the first compressed submit -- a queue that only ever sees raw frames owns none of this.
 // Bytes a compressed file may have: ONE derivation, for the submit's probe and for the ring (vsf_observe_set_compressed_cap
@@ -327,9 +332,11 @@ vsf_status ensure_device_ring(vsf_ctx* ctx, bool bayer, bool resized = false) {
 // raw frame's upload, a compressed frame's decoded image), the mosaics of a Bayer batch.
 enum { kInHostRing = 1, kInDeviceRing = 2, kInBatch = 4, kInBayer = 8 };
 
-vsf_status ensure_input(vsf_ctx* ctx, int what) {
+// need: bytes the arriving frame's image takes where that is more than every declared size's (a packed-colour frame,
+// observe_pix_image_bytes: its rows are w * bpp bytes); the first frame that needs more room rebuilds, as a larger declared size does
+vsf_status ensure_input(vsf_ctx* ctx, int what, size_t need = 0) {
   vsf_ctx::Observe& o = ctx->ob;
-  const size_t half = observe_input_half_bytes(ctx->ob_in_w, ctx->ob_in_h, ctx->ob_streams);
+  const size_t half = std::max(observe_input_half_bytes(ctx->ob_in_w, ctx->ob_in_h, ctx->ob_streams), need);
   if (half == 0) return VSF_ERR_INVALID_ARG;
   if (o.in_half != 0 && half > o.in_half) {
     // A larger size has been declared since these were built, and frames of other streams may wait in them or be on their
@@ -379,11 +386,12 @@ vsf_status ingest_resized(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, in
   ObserveLaunchStats& stats = o.queue->stats;
   const ObserveResizePlan& R = o.resize_plan;
   const size_t half = o.in_half, slot = 2 * half;
-  const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
+  const int pixfmt = o.frames[(size_t)(t0 % o.depth)].pixfmt, bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  const bool bayer = pix_is_bayer(pixfmt);
   *files = false;
   for (const ObserveUpload& u : R.uploads) {
     VSF_HIP(hipMemcpyAsync(b.d_in + (size_t)u.f0 * slot, o.h_in + (size_t)u.slot0 * slot, (size_t)u.n * slot, hipMemcpyHostToDevice, s));
-    stats.resize_commands++;
+    (bpp > 1 ? stats.pix_commands : stats.resize_commands)++;  // (packed colour is in the big slots whatever its size)
   }
   // ---- cv::imdecode of the files, whole, at the size they have: a decode_runs per distinct size among them ----
   const int N = 2 * n;
@@ -416,7 +424,7 @@ vsf_status ingest_resized(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, in
     if (!b.blob_in.uploaded) VSF_HIP(b.blob_in.uploaded.alloc(hipEventDisableTiming));
     int runs = 0;
     const vsf_status st = decode_runs(ctx, fl.data(), sizes.data(), kinds.data(), N, lead.w, lead.h, b.blob_in, o.ing_scratch,
-                                      bayer ? o.d_bayer_in : b.d_in, half, (int)observe_input_pitch(lead.w), b.status, 1, s, &runs);
+                                      bayer ? o.d_bayer_in.get() : b.d_in.get(), half, (int)observe_input_pitch(lead.w), b.status, 1, s, &runs);
     if (st != VSF_OK) return st;
     stats.resize_commands += 1 + runs;  // (the upload, each run's decode)
     *files = true;
@@ -427,10 +435,34 @@ vsf_status ingest_resized(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, in
     uint8_t* staged = b.d_in + (size_t)r.f0 * slot;
     const uint8_t* src = r.where == kObserveInDeviceRing ? o.d_in_ring + (size_t)r.src0 * slot : staged;
     if (bayer) {  // the images are mosaics: where they lie -> the batch's big slots
-      const uint8_t* mosaic = r.where == kObserveInDeviceRing ? src : o.d_bayer_in + (size_t)r.f0 * slot;
-      vsf_launch_bayer_bg_gray(mosaic, 2 * r.n, r.w, r.h, half, pitch, staged, half, pitch, s);
+      // (a raw host mosaic was uploaded into the batch's big slot itself: it goes through the mosaics' buffer and back)
+      uint8_t* mosaics = o.d_bayer_in + (size_t)r.f0 * slot;
+      int n_new = 0;
+      for (int f = r.f0; f < r.f0 + r.n; f++) {
+        n_new += o.frames[(size_t)((t0 + f) % o.depth)].pix_new;
+        if (r.where == kObserveInDeviceRing || o.resize_in[(size_t)f].kind != 0) continue;
+        VSF_HIP(hipMemcpyAsync(mosaics + (size_t)(f - r.f0) * slot, staged + (size_t)(f - r.f0) * slot, slot, hipMemcpyDeviceToDevice, s));
+        stats.pix_commands++;
+      }
+      const uint8_t* mosaic = r.where == kObserveInDeviceRing ? src : mosaics;
+      vsf_launch_to_gray(pixfmt, mosaic, 2 * r.n, r.w, r.h, half, pitch, staged, half, pitch, s);
       stats.resize_commands++;
+      stats.pix_commands += n_new != 0;
+      stats.pix_frames += n_new;
       src = staged;
+    } else if (bpp > 1) {  // packed colour, rows of w * bpp bytes: cv::resize(to_gray(frame)) -- gray at the arriving size first
+      const int cpitch = (int)observe_pix_pitch(r.w, bpp);
+      stats.pix_commands++;
+      stats.pix_frames += r.n;
+      if (r.w == cw && r.h == ch) {  // ... which is the context's: straight into the batch's images, nothing to resize
+        vsf_launch_to_gray(pixfmt, src, 2 * r.n, r.w, r.h, half, cpitch, b.d_img + (size_t)r.f0 * 2 * ctx->st_img_stride,
+                           ctx->st_img_stride, (int)ctx->st_img_pitch, s);
+        for (int f = r.f0; f < r.f0 + r.n; f++) stats.device_frames += o.resize_in[(size_t)f].kind == kObserveKindDevice;
+        continue;
+      }
+      uint8_t* gray = o.d_bayer_in + (size_t)r.f0 * slot;
+      vsf_launch_to_gray(pixfmt, src, 2 * r.n, r.w, r.h, half, cpitch, gray, half, pitch, s);
+      src = gray;
     }
     vsf_launch_resize_gray(src, 2 * r.n, r.w, r.h, half, (size_t)pitch, b.d_img + (size_t)r.f0 * 2 * ctx->st_img_stride, cw, ch,
                            ctx->st_img_stride, ctx->st_img_pitch, s);
@@ -447,7 +479,8 @@ vsf_status ingest_resized(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, in
 // The device frames of batch [t0, t0 + n) (o.runs): the copy stream waits for the launches that filled their slots -- for
 // the newest event of every stretch of frames that came over one producer stream: it is behind the others --, then ONE copy
 // command per run takes the slots into the batch's images (into the mosaics' buffer for a Bayer batch).
-vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, bool bayer, bool demosaic, hipStream_t s) {
+vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, int pixfmt, bool demosaic, hipStream_t s) {
+  const bool bayer = pix_is_bayer(pixfmt);
   vsf_ctx::Observe& o = ctx->ob;
   ObserveLaunchStats& stats = o.queue->stats;
   const vsf_ctx::ObserveFrame* last = nullptr;
@@ -468,8 +501,8 @@ vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0
   }
   // (a Bayer batch that also holds compressed frames is demosaiced once, behind its decoders: ingest_batch)
   if (demosaic) {
-    vsf_launch_bayer_bg_gray(o.d_bayer, 2 * n, ctx->p.width, ctx->p.height, ctx->st_img_stride, (int)ctx->st_img_pitch, b.d_img,
-                             ctx->st_img_stride, (int)ctx->st_img_pitch, s);
+    vsf_launch_to_gray(pixfmt, o.d_bayer, 2 * n, ctx->p.width, ctx->p.height, ctx->st_img_stride, (int)ctx->st_img_pitch, b.d_img,
+                       ctx->st_img_stride, (int)ctx->st_img_pitch, s);
     stats.device_commands++;
   }
   return VSF_OK;
@@ -483,7 +516,8 @@ vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0
 vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s, bool finish = true) {
   vsf_ctx::Observe& o = ctx->ob;
   const int w = ctx->p.width, h = ctx->p.height, N = 2 * n;
-  const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
+  const int pixfmt = o.frames[(size_t)(t0 % o.depth)].pixfmt;
+  const bool bayer = pix_is_bayer(pixfmt);
   std::vector<const uint8_t*> files((size_t)N);
   std::vector<size_t> sizes((size_t)N);
   std::vector<uint8_t> kinds((size_t)N), reduces((size_t)N);
@@ -503,11 +537,11 @@ vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int 
   int runs = 0;
   // (every file passed the decoders' host half at its submit; b.blob is free: the slot's previous batch has left the GPU)
   const vsf_status st = decode_runs(ctx, files.data(), sizes.data(), kinds.data(), N, w, h, b.blob, o.ing_scratch,
-                                    bayer ? o.d_bayer : b.d_img, stride, pitch, b.status, 1, s, &runs,
+                                    bayer ? o.d_bayer.get() : b.d_img.get(), stride, pitch, b.status, 1, s, &runs,
                                     any_reduced ? reduces.data() : nullptr);
   if (st != VSF_OK || runs == 0) return st;
   // bayer_rggb8 (slam_frontend_main.cc:101-109): every image of such a batch is a decoded mosaic
-  if (bayer) vsf_launch_bayer_bg_gray(o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
+  if (bayer) vsf_launch_to_gray(pixfmt, o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
   if (finish) vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
   // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
   o.queue->stats.ingest_commands += (finish ? 2 : 1) + runs + (bayer ? 1 : 0);
@@ -641,17 +675,34 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
     const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
     const size_t frame_bytes = 2 * ctx->st_img_stride;
     // (a batch that mixes raw and compressed frames copies its whole span of the raw ring: the decoders write behind it)
+    // (raw host mosaics, vsf_observe_submit_stream_pix: into the mosaics' buffer, as the decoders' and the device ring's are)
+    const int pixfmt = o.frames[(size_t)(t0 % o.depth)].pixfmt;
+    const bool mosaics = pix_is_bayer(pixfmt);
+    uint8_t* up = mosaics ? o.d_bayer.get() : b.d_img.get();
     if (any_raw)
-      VSF_HIP(hipMemcpyAsync(b.d_img, o.h_img + (size_t)slot0 * frame_bytes, (size_t)first * frame_bytes,
+      VSF_HIP(hipMemcpyAsync(up, o.h_img + (size_t)slot0 * frame_bytes, (size_t)first * frame_bytes,
                              hipMemcpyHostToDevice, s_copy));
     if (any_raw && first < n)
-      VSF_HIP(hipMemcpyAsync(b.d_img + (size_t)first * frame_bytes, o.h_img, (size_t)(n - first) * frame_bytes,
+      VSF_HIP(hipMemcpyAsync(up + (size_t)first * frame_bytes, o.h_img, (size_t)(n - first) * frame_bytes,
                              hipMemcpyHostToDevice, s_copy));
     // ---- device frames: out of the device ring, behind the launches that put them there ----
     if (any_dev || rs_dev) {  // (rs_dev alone: the waits for the producers' events, no copy)
-      const bool bayer = o.frames[(size_t)(t0 % o.depth)].bayer;
-      const vsf_status st = ingest_device_runs(ctx, b, t0, n, bayer, bayer && any_dev && !any_cmp, s_copy);
+      const vsf_status st = ingest_device_runs(ctx, b, t0, n, pixfmt, mosaics && any_dev && !any_cmp, s_copy);
       if (st != VSF_OK) return st;
+    }
+    // ---- raw host mosaics alone: their demosaic (with device or compressed frames in the batch, theirs takes these along) ----
+    if (mosaics && any_raw && !any_dev && !any_cmp) {
+      vsf_launch_to_gray(pixfmt, o.d_bayer, 2 * n, ctx->p.width, ctx->p.height, ctx->st_img_stride, (int)ctx->st_img_pitch, b.d_img,
+                         ctx->st_img_stride, (int)ctx->st_img_pitch, s_copy);
+    }
+    if (mosaics && (any_raw || any_dev || any_cmp)) {  // (vsf_observe_stats [30], [31]; frames in big slots: ingest_resized)
+      int n_new = 0;
+      for (int f = 0; f < n; f++) {
+        const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
+        n_new += fr.pix_new && !(may_resize && fr.in_w != 0);
+      }
+      stats.pix_frames += n_new;
+      stats.pix_commands += n_new != 0;  // (the batch's one demosaic)
     }
     // ---- compressed frames: one more copy command for their files, the decoders, the ingest finish ----
     if (any_cmp) {
@@ -1016,7 +1067,7 @@ vsf_status vsf_observe_set_streams(vsf_ctx* ctx, int n_streams) {
   if (n_streams != ctx->ob_streams)  // (vsf_observe_set_stream_cam_to_robot: the streams are other cameras now)
     for (bool& set : ctx->ob_stream_c2r_set) set = false;
   if (n_streams != ctx->ob_streams)  // (vsf_observe_set_input_size: ... of other sizes)
-    for (int s = 0; s < VSF_OBSERVE_MAX_STREAMS; s++) ctx->ob_in_w[s] = ctx->ob_in_h[s] = 0;
+    for (int s = 0; s < VSF_OBSERVE_MAX_STREAMS; s++) ctx->ob_in_w[s] = ctx->ob_in_h[s] = ctx->ob_bayer_order[s] = 0;
   ctx->ob_streams = n_streams;
   return VSF_OK;
 }
@@ -1049,6 +1100,15 @@ vsf_status vsf_observe_set_input_size(vsf_ctx* ctx, int stream, int width, int h
   if (ctx->ob.ready && ctx->ob.streams[(size_t)stream].uncollected != 0) return VSF_ERR_INVALID_ARG;
   ctx->ob_in_w[stream] = width;
   ctx->ob_in_h[stream] = height;
+  return VSF_OK;
+}
+
+vsf_status vsf_observe_set_bayer_order(vsf_ctx* ctx, int stream, int pixfmt) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams || !pix_is_bayer(pixfmt)) return VSF_ERR_INVALID_ARG;
+  // (the rule of vsf_observe_reset_stream: no frame of the stream submitted and not collected)
+  if (ctx->ob.ready && ctx->ob.streams[(size_t)stream].uncollected != 0) return VSF_ERR_INVALID_ARG;
+  ctx->ob_bayer_order[stream] = pixfmt;
   return VSF_OK;
 }
 
@@ -1088,7 +1148,10 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
-  const int64_t v[30] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
+  // every buffer a frame of a new format made the queue build or enlarge (they are the compressed and resize paths' too:
+  // the mosaics' buffer and the big slots, counted in [13] and [28] as well)
+  const size_t pix_bytes = o.pix_seen ? input_bytes(ctx) + (o.d_bayer ? 2 * (size_t)o.bmax * ctx->st_img_stride : 0) : 0;
+  const int64_t v[33] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
                          s.file_commands, (int64_t)ctx->ob_streams, s.multi,
@@ -1097,8 +1160,9 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
                          s.cloud_frames, s.cloud_commands,
                          (int64_t)(o.h_wp ? (size_t)o.depth * ((size_t)ctx->p.max_keypoints * 3 * sizeof(double) + sizeof(int32_t)) : 0),
                          s.reduced, s.seeded_frames, s.colour_commands,
-                         s.resized, s.resize_commands, (int64_t)input_bytes(ctx), s.multi_size};
-  for (int i = 0; i < n && i < 30; i++) out[i] = v[i];
+                         s.resized, s.resize_commands, (int64_t)input_bytes(ctx), s.multi_size,
+                         s.pix_frames, s.pix_commands, (int64_t)pix_bytes};
+  for (int i = 0; i < n && i < 33; i++) out[i] = v[i];
   return VSF_OK;
 }
 
@@ -1121,8 +1185,10 @@ static void capture_placement(const vsf_ctx* ctx, int stream, vsf_ctx::ObserveFr
 // Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
 // have passed vsf_observe_probe_compressed_reduced as kinds[0 / 1] at 1 / reduce.
 static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
-                                 const int* kinds, const size_t* nbytes, bool bayer, const vsf_calibration* calib,
-                                 float best_percent, int frame_life, int64_t* ticket, int reduce = 1) {
+                                 const int* kinds, const size_t* nbytes, int pixfmt, const vsf_calibration* calib,
+                                 float best_percent, int frame_life, int64_t* ticket, int reduce = 1, bool pix_call = false) {
+  const bool bayer = pix_is_bayer(pixfmt);
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
   if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6)
@@ -1145,7 +1211,7 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     std::unique_lock<std::mutex> lk(q.mu);
     if (q.status != VSF_OK) return q.status;
     if (q.next_launch < q.next_ticket) {
-      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].bayer != bayer;
+      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].pixfmt != pixfmt;
       const int64_t mine = o.streams[(size_t)stream].last_ticket;
       if (!cut && mine >= q.next_launch) {
         const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
@@ -1170,11 +1236,16 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     }
   }
   vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
-  const bool resized = ctx->ob_in_w[stream] != 0;  // (w x h is the stream's declared size then: the callers have checked)
+  // (w x h is the stream's declared size then: the callers have checked; packed colour waits in the big slots whatever its size)
+  const bool resized = ctx->ob_in_w[stream] != 0 || bpp > 1;
   if (resized) {
     if (bayer && w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
-    st = ensure_input(ctx, kinds ? (bayer ? kInBatch | kInBayer : kInBatch) : kInHostRing | kInBatch);
+    const bool gray_slots = bayer || (bpp > 1 && (w != ctx->p.width || h != ctx->p.height));  // (the conversion's other buffer)
+    st = ensure_input(ctx, (kinds ? kInBatch : kInHostRing | kInBatch) | (gray_slots ? kInBayer : 0),
+                      bpp > 1 ? observe_pix_image_bytes(w, h, bpp) : 0);
     if (st != VSF_OK) return st;
+  } else if (bayer && !kinds && !o.d_bayer) {  // (raw host mosaics of the context's size: uploaded into the mosaics' buffer)
+    VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
   }
   const int64_t t_copy = now_ns();
   if (kinds) {
@@ -1188,11 +1259,12 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
   } else {
     // (a frame of a declared size: into its big slot of the pinned ring of such slots, rows at ITS width's pitch)
     uint8_t* h_img = resized ? o.h_in + (size_t)slot * 2 * o.in_half : o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
-    const size_t h_stride = resized ? o.in_half : ctx->st_img_stride, h_pitch = resized ? observe_input_pitch(w) : ctx->st_img_pitch;
-    const ObserveCopyHelper::Job jr{h_img + h_stride, right, h_pitch, stride, (size_t)w, h};
+    const size_t h_stride = resized ? o.in_half : ctx->st_img_stride, h_pitch = resized ? observe_pix_pitch(w, bpp) : ctx->st_img_pitch;
+    const size_t row = (size_t)w * (size_t)bpp;  // bytes
+    const ObserveCopyHelper::Job jr{h_img + h_stride, right, h_pitch, stride, row, h};
     // frames are streaming in (the previous one is still in the queue): the helper thread takes the right image
     const bool helped = o.copy_helper && q.next_ticket > q.next_collect && o.copy_helper->post(jr);
-    stage_image(h_img, h_pitch, left, stride, (size_t)w, h);
+    stage_image(h_img, h_pitch, left, stride, row, h);
     if (helped)
       o.copy_helper->wait();
     else
@@ -1203,7 +1275,9 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     fr.kind[k] = kinds ? (uint8_t)kinds[k] : 0;
     fr.nbytes[k] = kinds ? (uint32_t)nbytes[k] : 0u;
   }
-  fr.bayer = bayer;
+  fr.pixfmt = pixfmt;
+  fr.pix_new = pix_call ? pixfmt != VSF_PIX_MONO8 : pixfmt >= VSF_PIX_BAYER_GRBG8;
+  o.pix_seen |= fr.pix_new;
   fr.reduce = (uint8_t)reduce;
   if (o.in_half != 0) {  // (a queue that has seen no declared size: the records' sizes are 0 x 0 and stay so)
     fr.in_w = resized ? w : 0;
@@ -1240,7 +1314,28 @@ vsf_status vsf_observe_submit_stream(vsf_ctx* ctx, int stream, const uint8_t* le
   if (w != (declared ? ctx->ob_in_w[stream] : ctx->p.width) || h != (declared ? ctx->ob_in_h[stream] : ctx->p.height) ||
       stride < (size_t)w || ctx->p.max_images < 2)
     return VSF_ERR_INVALID_ARG;
-  return observe_submit(ctx, stream, left, right, w, h, stride, nullptr, nullptr, false, calib, best_percent, frame_life, ticket);
+  return observe_submit(ctx, stream, left, right, w, h, stride, nullptr, nullptr, VSF_PIX_MONO8, calib, best_percent, frame_life, ticket);
+}
+
+// Raw host frames of any pixel format.  MONO8 is the call above, byte for byte and launch for launch.
+vsf_status vsf_observe_submit_stream_pix(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h,
+                                         size_t stride_bytes, int pixfmt, const vsf_calibration* calib, float best_percent,
+                                         int frame_life, int64_t* ticket) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
+      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
+    return VSF_ERR_INVALID_ARG;
+  *ticket = -1;
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (bpp == 0 || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
+  const bool declared = ctx->ob_in_w[stream] != 0;
+  if (w != (declared ? ctx->ob_in_w[stream] : ctx->p.width) || h != (declared ? ctx->ob_in_h[stream] : ctx->p.height) ||
+      stride_bytes < (size_t)w * (size_t)bpp || ctx->p.max_images < 2)
+    return VSF_ERR_INVALID_ARG;
+  if (pix_is_bayer(pixfmt) && w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
+  if (bpp > 1 && observe_pix_image_bytes(w, h, bpp) == 0) return VSF_ERR_UNSUPPORTED;  // (2^31 bytes or more an image)
+  return observe_submit(ctx, stream, left, right, w, h, stride_bytes, nullptr, nullptr, pixfmt, calib, best_percent, frame_life,
+                        ticket, 1, true);
 }
 
 vsf_status vsf_observe_submit_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
@@ -1294,8 +1389,10 @@ static vsf_status observe_submit_files(vsf_ctx* ctx, int stream, const uint8_t* 
   if (st == VSF_OK)
     st = vsf_observe_probe_compressed_reduced(right, right_bytes, reduce, w, h, cap, ctx->tuning.jpeg_serial, &kinds[1]);
   if (st != VSF_OK) return st;
-  return observe_submit(ctx, stream, left, right, w, h, 0, kinds, nbytes, bayer != 0, calib, best_percent, frame_life, ticket,
-                        reduce);
+  // (`bayer`: the order vsf_observe_set_bayer_order named for this stream, RGGB for a stream never told)
+  const int order = ctx->ob_bayer_order[stream] ? ctx->ob_bayer_order[stream] : VSF_PIX_BAYER_RGGB8;
+  return observe_submit(ctx, stream, left, right, w, h, 0, kinds, nbytes, bayer != 0 ? order : VSF_PIX_MONO8, calib, best_percent,
+                        frame_life, ticket, reduce);
 }
 
 size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth) {
@@ -1315,19 +1412,22 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
       frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
     return VSF_ERR_INVALID_ARG;
   for (int i = 0; i < n; i++) tickets[i] = -1;
-  if (pixfmt != VSF_PIX_MONO8 && pixfmt != VSF_PIX_BAYER_RGGB8) return VSF_ERR_INVALID_ARG;
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (bpp == 0) return VSF_ERR_INVALID_ARG;  // (2 .. 15 included)
   if (ctx->p.max_images < 2 || n > 1024) return VSF_ERR_INVALID_ARG;
   if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   // (the images have the stream's declared size, vsf_observe_set_input_size, or the context's)
-  const bool resized = ctx->ob_in_w[stream] != 0;
-  const int in_w = resized ? ctx->ob_in_w[stream] : ctx->p.width, in_h = resized ? ctx->ob_in_h[stream] : ctx->p.height;
-  const size_t w = (size_t)in_w;
+  const bool declared = ctx->ob_in_w[stream] != 0;
+  const int in_w = declared ? ctx->ob_in_w[stream] : ctx->p.width, in_h = declared ? ctx->ob_in_h[stream] : ctx->p.height;
+  const bool resized = declared || bpp > 1;  // (packed colour waits in the ring of big slots whatever its size)
+  const size_t w = (size_t)in_w * (size_t)bpp;  // a row's bytes
   for (int i = 0; i < n; i++)
     if (!frames[i].left || !frames[i].right || frames[i].left_pitch < w || frames[i].right_pitch < w) return VSF_ERR_INVALID_ARG;
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
-  if (resized && pixfmt == VSF_PIX_BAYER_RGGB8 && in_w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
+  if (resized && pix_is_bayer(pixfmt) && in_w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
+  if (bpp > 1 && observe_pix_image_bytes(in_w, in_h, bpp) == 0) return VSF_ERR_UNSUPPORTED;  // (2^31 bytes or more an image)
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6) return VSF_ERR_INVALID_ARG;
-  const bool bayer = pixfmt == VSF_PIX_BAYER_RGGB8;
+  const bool bayer = pix_is_bayer(pixfmt);
   hipStream_t producer = static_cast<hipStream_t>(producer_stream);
   VSF_HIP(hipSetDevice(ctx->device));
   vsf_ctx::Observe& o = ctx->ob;
@@ -1345,7 +1445,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     std::unique_lock<std::mutex> lk(q.mu);
     if (q.status != VSF_OK) return q.status;
     if (q.next_launch < q.next_ticket) {
-      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].bayer != bayer;
+      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].pixfmt != pixfmt;
       const int64_t mine = o.streams[(size_t)stream].last_ticket;
       if (!cut && mine >= q.next_launch) {
         const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
@@ -1358,7 +1458,11 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     }
   }
   st = ensure_device_ring(ctx, bayer, resized);
-  if (st == VSF_OK && resized) st = ensure_input(ctx, bayer ? kInDeviceRing | kInBayer : kInDeviceRing);
+  if (st == VSF_OK && resized) {
+    // (kInBayer: the conversion's other buffer -- also the batches' own big slots, where a mosaic's gray image goes)
+    const bool gray_slots = bayer || (bpp > 1 && (in_w != ctx->p.width || in_h != ctx->p.height));
+    st = ensure_input(ctx, gray_slots ? kInDeviceRing | kInBayer : kInDeviceRing, bpp > 1 ? observe_pix_image_bytes(in_w, in_h, bpp) : 0);
+  }
   if (st != VSF_OK) return st;
   if (o.debug && !o.seeded) {  // the stereo lines' colours, drawn ahead for every frame of the call (observe_submit)
     const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + n - q.next_collect) * K;
@@ -1379,7 +1483,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     e[1] = {static_cast<const uint8_t*>(frames[i].right), frames[i].right_pitch};
   }
   if (resized)  // (into the ring of big slots, rows at the declared width's pitch: k_resize.hip reads them there)
-    vsf_launch_ingest_ring(o.d_in_ring, o.in_half, (int)observe_input_pitch(in_w), in_w, in_h, span.slot0, o.depth, n, inl,
+    vsf_launch_ingest_ring(o.d_in_ring, o.in_half, (int)observe_pix_pitch(in_w, bpp), in_w * bpp, in_h, span.slot0, o.depth, n, inl,
                            by_table ? o.h_dev_src.get() : nullptr, producer);
   else
     vsf_launch_ingest_ring(o.d_ring, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.width, ctx->p.height, span.slot0, o.depth, n,
@@ -1393,7 +1497,9 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((span.slot0 + i) % o.depth)];
     fr.kind[0] = fr.kind[1] = kObserveKindDevice;
     fr.nbytes[0] = fr.nbytes[1] = 0u;
-    fr.bayer = bayer;
+    fr.pixfmt = pixfmt;
+    fr.pix_new = pixfmt >= VSF_PIX_BAYER_GRBG8;
+    o.pix_seen |= fr.pix_new;
     fr.reduce = 1;
     if (o.in_half != 0) {
       fr.in_w = resized ? in_w : 0;

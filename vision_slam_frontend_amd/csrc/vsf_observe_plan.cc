@@ -117,6 +117,18 @@ size_t observe_input_half_bytes(const int* in_w, const int* in_h, int n_streams)
   return half;
 }
 
+size_t observe_pix_pitch(int w, int bpp) {
+  if (w < 1 || w > 32767 || (bpp != 1 && bpp != 3 && bpp != 4)) return 0;
+  return ((size_t)w * (size_t)bpp + 63) & ~(size_t)63;
+}
+
+size_t observe_pix_image_bytes(int w, int h, int bpp) {
+  const size_t pitch = observe_pix_pitch(w, bpp);
+  if (pitch == 0 || h < 1 || h > 32767) return 0;
+  const size_t bytes = pitch * (size_t)h;
+  return bytes <= 0x7FFFFFFFu ? (bytes + 255) & ~(size_t)255 : 0;
+}
+
 size_t observe_input_ring_bytes(int depth, size_t half) {
   if (depth < 1 || depth > 1024 || half == 0) return 0;
   return (size_t)depth * 2 * half;
@@ -164,3 +176,43 @@ bool observe_resize_plan(const ObserveResizeIn* in, int n, int64_t t0, int depth
 }
 
 }  // namespace vsfi
+
+// ---- pixel formats (include/vsf.h): the table behind every call that takes a pixfmt ----
+extern "C" {
+
+int vsf_pixfmt_bytes_per_pixel(int pixfmt) {
+  switch (pixfmt) {
+    case VSF_PIX_MONO8:
+    case VSF_PIX_BAYER_RGGB8:
+    case VSF_PIX_BAYER_GRBG8:
+    case VSF_PIX_BAYER_GBRG8:
+    case VSF_PIX_BAYER_BGGR8:
+      return 1;
+    case VSF_PIX_BGR8:
+    case VSF_PIX_RGB8:
+      return 3;
+    case VSF_PIX_BGRA8:
+    case VSF_PIX_RGBA8:
+      return 4;
+    default:
+      return 0;  // (2 .. 15 included: they stay unknown)
+  }
+}
+
+vsf_status vsf_pixfmt_from_encoding(const char* ros_encoding, int* pixfmt) {
+  static const struct {
+    const char* name;
+    int pixfmt;
+  } kTable[] = {{"mono8", VSF_PIX_MONO8},           {"bayer_rggb8", VSF_PIX_BAYER_RGGB8}, {"bayer_grbg8", VSF_PIX_BAYER_GRBG8},
+                {"bayer_gbrg8", VSF_PIX_BAYER_GBRG8}, {"bayer_bggr8", VSF_PIX_BAYER_BGGR8}, {"bgr8", VSF_PIX_BGR8},
+                {"rgb8", VSF_PIX_RGB8},             {"bgra8", VSF_PIX_BGRA8},             {"rgba8", VSF_PIX_RGBA8}};
+  if (!ros_encoding || !pixfmt) return VSF_ERR_INVALID_ARG;
+  for (const auto& e : kTable)
+    if (std::strcmp(ros_encoding, e.name) == 0) {
+      *pixfmt = e.pixfmt;
+      return VSF_OK;
+    }
+  return VSF_ERR_UNSUPPORTED;
+}
+
+}  // extern "C"

@@ -100,6 +100,13 @@ size_t observe_input_pitch(int w);               // 0: w outside 1 .. 32767
 size_t observe_input_image_bytes(int w, int h);  // 0: a size outside 1 .. 32767
 // in_w[s], in_h[s]: stream s's declared size, 0 x 0: none.  0: no stream has one (or an argument is out of range).
 size_t observe_input_half_bytes(const int* in_w, const int* in_h, int n_streams);
+// A frame of packed colour (VSF_PIX_BGR8 ..., bpp = 3 or 4 bytes per pixel; bpp = 1: the functions above) waits in the same
+// big slots, whether its stream has a declared size or not: its rows are w * bpp bytes, observe_pix_pitch apart (rounded
+// up to 64, the same rule in bytes), and `half` is at least observe_pix_image_bytes of the largest such frame seen.
+// 0: w or h outside 1 .. 32767, another bpp, or an image of 2^31 bytes or more (the conversion kernel addresses an image
+// with 32-bit offsets).
+size_t observe_pix_pitch(int w, int bpp);
+size_t observe_pix_image_bytes(int w, int h, int bpp);
 // A ring of `depth` such slots, 0 where there is none.
 size_t observe_input_ring_bytes(int depth, size_t half);
 

@@ -85,6 +85,7 @@ struct ObserveLaunchStats {
   int64_t device_frames = 0, device_commands = 0;  // vsf_observe_submit_dev: frames launched, the batches' copies and kernels
   int64_t cloud_frames = 0, cloud_commands = 0;    // vsf_observe_set_world_points: frames launched, the batches' one kernel each
   int64_t reduced = 0;                             // vsf_observe_submit_compressed_reduced: frames launched with reduce > 1
+  int64_t pix_frames = 0, pix_commands = 0;  // new pixel formats: frames converted, the batches' launches and copies for them
   int64_t resized = 0, resize_commands = 0, multi_size = 0;        // vsf_observe_set_input_size: frames resized, the batches' launches and copies for them
   int64_t seeded_frames = 0, colour_commands = 0;  // vsf_observe_set_debug_seeds: frames coloured by a stream's generator, the kernel's launches
 };

@@ -29,6 +29,12 @@ def lib() -> C.CDLL:
         L.vsfh_observe_image.argtypes = [vp, vp, vp, i32, i32, sz, dbl]
         L.vsfh_observe_compressed_image.argtypes = [vp, vp, sz, vp, sz, i32, dbl]
         L.vsfh_observe_device_image.argtypes = [vp, vp, sz, vp, sz, vp, dbl, i32]
+        L.vsfh_observe_image_pix.argtypes = [vp, vp, vp, i32, i32, sz, i32, dbl]
+        L.vsfh_observe_device_image_pix.argtypes = [vp, vp, sz, vp, sz, vp, dbl, i32]
+        L.vsfh_group_observe_image_pix.argtypes = [vp, i32, vp, vp, i32, i32, sz, i32, dbl]
+        L.vsfh_group_observe_device_image_pix.argtypes = [vp, i32, vp, sz, vp, sz, vp, dbl, i32]
+        L.vsfh_set_bayer_order.argtypes = [vp, i32]
+        L.vsfh_set_bayer_order.restype = None
         L.vsfh_group_observe_device_image.argtypes = [vp, i32, vp, sz, vp, sz, vp, dbl, i32]
         L.vsfh_last_status.argtypes = [vp]
         L.vsfh_refused_frames.argtypes = [vp]
@@ -131,11 +137,20 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-def _device_frame(left, right, width: int, height: int, device: int, stream):
+def _host_frame(left, right, pixfmt: int):
+    """Two raw host images of one PIX_* format -- (h, w), or (h, w, 3 or 4) for packed colour -- as contiguous arrays, with
+    their width in pixels and their row stride in bytes."""
+    left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+    bpp = capi.pixfmt_bytes_per_pixel(pixfmt)
+    assert left.shape == right.shape and (left.ndim == 2 if bpp <= 1 else left.ndim == 3 and left.shape[2] == bpp), left.shape
+    return left, right, left.shape[1], left.shape[0], left.strides[0]
+
+
+def _device_frame(left, right, width: int, height: int, device: int, stream, pixfmt: int = 0):
     """What vsfh_observe_device_image takes of two tensors: (left address, left pitch, right address, right pitch, stream).
     ValueError -- before any call into the library -- for a tensor that is not height x width torch.uint8 with dense rows on
     GPU `device`; stream None: torch.cuda.current_stream() of that device, else a torch stream or a hipStream_t as an integer."""
-    (lp, ls), (rp, rs) = capi.device_image(left, width, height, device), capi.device_image(right, width, height, device)
+    (lp, ls), (rp, rs) = (capi.device_image_pix(t, width, height, device, pixfmt) for t in (left, right))
     if stream is None:
         import torch
         stream = torch.cuda.current_stream(device)
@@ -281,7 +296,24 @@ class Frontend:
         q = np.ascontiguousarray(rotation_wxyz, np.float32)
         lib().vsfh_observe_odometry(self._h, _p(t), _p(q), timestamp)
 
-    def observe_image(self, left: np.ndarray, right: np.ndarray, time: float = 0.0) -> bool:
+    def set_bayer_order(self, pixfmt: int):
+        """FrontendConfig::bayer_order_: the order of the mosaics observe_compressed_image(bayer_rggb8=True) decodes (one of
+        capi.PIX_BAYER_*).  Legal at any time; VsfError(INVALID_ARG) and no change for anything else."""
+        lib().vsfh_set_bayer_order(self._h, int(pixfmt))
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "Frontend::set_bayer_order")
+
+    def observe_image(self, left: np.ndarray, right: np.ndarray, time: float = 0.0, pixfmt: int = capi.PIX_MONO8) -> bool:
+        """Frontend::ObserveImage.  pixfmt: what the arrays hold (capi.PIX_*): (h, w) for mono8 and the Bayer orders,
+        (h, w, 3 or 4) for packed colour -- sensor_msgs/Image as the driver publishes it, made gray on the GPU."""
+        if pixfmt != capi.PIX_MONO8:
+            left, right, w, h, stride = _host_frame(left, right, pixfmt)
+            added = bool(lib().vsfh_observe_image_pix(self._h, _p(left), _p(right), w, h, stride, pixfmt, time))
+            st = lib().vsfh_last_status(self._h)
+            if st != capi.VSF_OK:
+                raise capi.VsfError(st, "Frontend::ObserveImage")
+            return added
         left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
         assert left.shape == right.shape and left.ndim == 2
         added = bool(lib().vsfh_observe_image(self._h, _p(left), _p(right), left.shape[1], left.shape[0],
@@ -291,11 +323,19 @@ class Frontend:
             raise capi.VsfError(st, "Frontend::ObserveImage")
         return added
 
-    def observe_device_image(self, left, right, time: float = 0.0, bayer_rggb8: bool = False, stream=None) -> bool:
+    def observe_device_image(self, left, right, time: float = 0.0, bayer_rggb8: bool = False, stream=None,
+                             pixfmt: int | None = None) -> bool:
         """Frontend::ObserveDeviceImage: the frame as two 2-D torch.uint8 tensors that already live on the Frontend's GPU
         (stride(1) == 1, any stride(0)), stream-ordered on `stream` (None: torch.cuda.current_stream()): they may still be
         being written by work queued on that stream, and may be overwritten by work queued on it afterwards.  A tensor of
         another dtype, device, size or inner stride raises ValueError before the library is called."""
+        if pixfmt is not None:  # (any capi.PIX_* format; packed colour: (h, w, 3 or 4) tensors with dense pixels)
+            lp, ls, rp, rs, s = _device_frame(left, right, self.size[0], self.size[1], self.device, stream, pixfmt)
+            added = bool(lib().vsfh_observe_device_image_pix(self._h, lp, ls, rp, rs, s, time, int(pixfmt)))
+            st = lib().vsfh_last_status(self._h)
+            if st != capi.VSF_OK:
+                raise capi.VsfError(st, "Frontend::ObserveDeviceImage")
+            return added
         lp, ls, rp, rs, s = _device_frame(left, right, self.size[0], self.size[1], self.device, stream)
         added = bool(lib().vsfh_observe_device_image(self._h, lp, ls, rp, rs, s, time, int(bool(bayer_rggb8))))
         st = lib().vsfh_last_status(self._h)
@@ -555,7 +595,12 @@ class FrontendGroup:
         q = np.ascontiguousarray(rotation_wxyz, np.float32)
         lib().vsfh_group_observe_odometry(self._h, i, _p(t), _p(q), timestamp)
 
-    def observe_image(self, i: int, left: np.ndarray, right: np.ndarray, time: float = 0.0) -> bool:
+    def observe_image(self, i: int, left: np.ndarray, right: np.ndarray, time: float = 0.0, pixfmt: int = capi.PIX_MONO8) -> bool:
+        if pixfmt != capi.PIX_MONO8:  # (Frontend.observe_image's pixfmt, for member i)
+            left, right, w, h, stride = _host_frame(left, right, pixfmt)
+            added = bool(lib().vsfh_group_observe_image_pix(self._h, i, _p(left), _p(right), w, h, stride, pixfmt, time))
+            self._check(i, "FrontendGroup::ObserveImage")
+            return added
         left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
         assert left.shape == right.shape and left.ndim == 2
         added = bool(lib().vsfh_group_observe_image(self._h, i, _p(left), _p(right), left.shape[1], left.shape[0],
@@ -563,9 +608,15 @@ class FrontendGroup:
         self._check(i, "FrontendGroup::ObserveImage")
         return added
 
-    def observe_device_image(self, i: int, left, right, time: float = 0.0, bayer_rggb8: bool = False, stream=None) -> bool:
+    def observe_device_image(self, i: int, left, right, time: float = 0.0, bayer_rggb8: bool = False, stream=None,
+                             pixfmt: int | None = None) -> bool:
         """FrontendGroup::ObserveDeviceImage(i, ...): Frontend.observe_device_image for member i."""
         m = self.members[i]
+        if pixfmt is not None:
+            lp, ls, rp, rs, s = _device_frame(left, right, m.size[0], m.size[1], m.device, stream, pixfmt)
+            added = bool(lib().vsfh_group_observe_device_image_pix(self._h, i, lp, ls, rp, rs, s, time, int(pixfmt)))
+            self._check(i, "FrontendGroup::ObserveDeviceImage")
+            return added
         lp, ls, rp, rs, s = _device_frame(left, right, m.size[0], m.size[1], m.device, stream)
         added = bool(lib().vsfh_group_observe_device_image(self._h, i, lp, ls, rp, rs, s, time, int(bool(bayer_rggb8))))
         self._check(i, "FrontendGroup::ObserveDeviceImage")

@@ -407,6 +407,30 @@ int vsfh_observe_device_image(void* f, const void* left, size_t left_pitch, cons
   return static_cast<Frontend*>(f)->ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time, bayer_rggb8 != 0) ? 1 : 0;
 }
 
+// ... of any pixel format (VSF_PIX_*): w x h pixels, stride / pitches in bytes
+int vsfh_observe_image_pix(void* f, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, int pixfmt, double time) {
+  return static_cast<Frontend*>(f)->ObserveImage(slam::Image(left, h, w, stride), slam::Image(right, h, w, stride), time, pixfmt) ? 1 : 0;
+}
+int vsfh_observe_device_image_pix(void* f, const void* left, size_t left_pitch, const void* right, size_t right_pitch,
+                                  void* hip_stream, double time, int pixfmt) {
+  return static_cast<Frontend*>(f)->ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time, pixfmt) ? 1 : 0;
+}
+int vsfh_group_observe_image_pix(void* g, int i, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride, int pixfmt,
+                                 double time) {
+  return static_cast<slam::FrontendGroup*>(g)->ObserveImage(i, slam::Image(left, h, w, stride), slam::Image(right, h, w, stride), time,
+                                                            pixfmt)
+             ? 1
+             : 0;
+}
+int vsfh_group_observe_device_image_pix(void* g, int i, const void* left, size_t left_pitch, const void* right, size_t right_pitch,
+                                        void* hip_stream, double time, int pixfmt) {
+  return static_cast<slam::FrontendGroup*>(g)->ObserveDeviceImage(i, left, left_pitch, right, right_pitch, hip_stream, time, pixfmt)
+             ? 1
+             : 0;
+}
+// FrontendConfig::bayer_order_ (a group's member: the pointer vsfh_group_member returns)
+void vsfh_set_bayer_order(void* f, int pixfmt) { static_cast<Frontend*>(f)->set_bayer_order(pixfmt); }
+
 unsigned long long vsfh_refused_frames(void* f) { return static_cast<Frontend*>(f)->refused_frames(); }
 int vsfh_last_status(void* f) { return (int)static_cast<Frontend*>(f)->last_status(); }
 int vsfh_num_poses(void* f) { return static_cast<Frontend*>(f)->GetNumPoses(); }

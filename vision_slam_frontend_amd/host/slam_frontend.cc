@@ -128,6 +128,7 @@ FrontendConfig::FrontendConfig() {
   debug_colour_seed_ = 1;
   visualization_ = false;
   imdecode_reduce_ = 1;  // IMREAD_GRAYSCALE, the reference's flag
+  bayer_order_ = VSF_PIX_BAYER_RGGB8;  // COLOR_BayerBG2BGR, the reference's
   resize_width_ = resize_height_ = 0;  // no cv::resize in front
   compressed_cap_ = 0;   // the library's default: the context's width x height + 64 KB
   // reference: AKAZE (cc:553, quirk Q1); ORB is the north-star path and the only extractor built here
@@ -304,6 +305,7 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
   if (last_status_ != VSF_OK) return false;
   ctx_generation_++;
   declared_w_ = declared_h_ = 0;  // (a new context's streams have no declared input size)
+  told_bayer_order_ = 0;          // (... and have been told no Bayer order)
   ctx_depth_ = queue_depth();
   last_status_ = vsf_set_option(ctx_, VSF_OPT_OBSERVE_THREAD, queue_thread_ ? 1 : 0);
   if (last_status_ == VSF_OK) last_status_ = vsf_set_option(ctx_, VSF_OPT_OBSERVE_COPY_THREAD, copy_thread_ ? 1 : 0);
@@ -636,12 +638,24 @@ void Frontend::UndistortFeaturePoints(std::vector<VisionFeature>* features_ptr) 
 // UndistortFeaturePoints run on the device back to back and come home in one compact buffer; the kept frames'
 // descriptors never leave HBM.  What stays here is the reference's bookkeeping (is_initial_ / initial_ids_, nodes,
 // factors, the sliding window), in the reference's order.
-bool Frontend::ObserveImageFused(const Image& left_image, const Image& right_image) {
+bool Frontend::ObserveImageFused(const Image& left_image, const Image& right_image, int pixfmt) {
   FramePayload fp;
   fp.left = left_image.data;
   fp.right = right_image.data;
   fp.step = left_image.step;
+  if (pixfmt != VSF_PIX_MONO8) fp.pixfmt = pixfmt;  // (MONO8: the call the queue has always had)
   return ObserveFused(left_image.cols, left_image.rows, fp);
+}
+
+bool Frontend::DeclareBayerOrder() {
+  const int order = config_.bayer_order_;
+  if (order == (told_bayer_order_ ? told_bayer_order_ : (int)VSF_PIX_BAYER_RGGB8)) return true;
+  // (the library takes a new order only while no frame of the stream is in flight: the rule of DeclareInput)
+  if (!(group_ ? group_->Flush() : Flush())) return false;
+  last_status_ = vsf_observe_set_bayer_order(ctx_, stream_, order);
+  if (last_status_ != VSF_OK) return false;
+  told_bayer_order_ = order;
+  return true;
 }
 
 bool Frontend::DeclareInput(int width, int height) {
@@ -666,6 +680,7 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   // (a frame that has the context's size already is a frame like any other: no declared size, no resize launch)
   const bool other = width != cw || height != ch;
   if (!DeclareInput(other ? width : 0, other ? height : 0)) return false;
+  if (fp.compressed && fp.bayer && !DeclareBayerOrder()) return false;
   const vsf_calibration calib = MakeCalibration(config_);
   // the queue must have room: when it is full, the oldest frame is collected and booked first
   // (a group member: the queue is the group's, and so is the order its frames are retired in)
@@ -677,8 +692,9 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
   if (config_.visualization_ && !SetQueuePose()) return false;
   if (fp.device) {  // (already in HBM: one launch on the producer's stream, no staging copy, no upload)
     const vsf_dev_frame df{fp.left, fp.right, fp.left_bytes, fp.right_bytes};
-    last_status_ = vsf_observe_submit_dev(ctx_, stream_, &df, 1, fp.bayer ? VSF_PIX_BAYER_RGGB8 : VSF_PIX_MONO8, fp.hip_stream,
-                                          &calib, config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
+    const int pixfmt = fp.pixfmt >= 0 ? fp.pixfmt : fp.bayer ? (int)VSF_PIX_BAYER_RGGB8 : (int)VSF_PIX_MONO8;
+    last_status_ = vsf_observe_submit_dev(ctx_, stream_, &df, 1, pixfmt, fp.hip_stream, &calib, config_.best_percent_,
+                                          (int)config_.frame_life_, &pf.ticket);
   } else if (fp.compressed && fp.reduce > 1)  // IMREAD_REDUCED_GRAYSCALE_N (refusals as below)
     last_status_ = vsf_observe_submit_compressed_reduced(ctx_, stream_, fp.left, fp.left_bytes, fp.right, fp.right_bytes, fp.reduce,
                                                          &calib, config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
@@ -686,6 +702,9 @@ bool Frontend::ObserveFused(int width, int height, const FramePayload& fp) {
     last_status_ = vsf_observe_submit_compressed_stream(ctx_, stream_, fp.left, fp.left_bytes, fp.right, fp.right_bytes,
                                                         fp.bayer ? 1 : 0, &calib, config_.best_percent_,
                                                         (int)config_.frame_life_, &pf.ticket);
+  else if (fp.pixfmt >= 0)  // sensor_msgs/Image as published: gray on the device, inside the batch
+    last_status_ = vsf_observe_submit_stream_pix(ctx_, stream_, fp.left, fp.right, width, height, fp.step, fp.pixfmt, &calib,
+                                                 config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
   else
     last_status_ = vsf_observe_submit_stream(ctx_, stream_, fp.left, fp.right, width, height, fp.step, &calib,
                                              config_.best_percent_, (int)config_.frame_life_, &pf.ticket);
@@ -1017,9 +1036,15 @@ bool Frontend::ObserveCompressedImage(const uint8_t* left, size_t left_bytes, co
   return ObserveFused(width, height, fp);
 }
 
+bool Frontend::ObserveDeviceImage(const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
+                                  double time, bool bayer_rggb8) {
+  return ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time,
+                            bayer_rggb8 ? (int)VSF_PIX_BAYER_RGGB8 : (int)VSF_PIX_MONO8);
+}
+
 // cc:400-472 for a frame that is in device memory already.
 bool Frontend::ObserveDeviceImage(const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
-                                  double /*time*/, bool bayer_rggb8) {
+                                  double /*time*/, int pixfmt) {
   if (!OdomCheck()) return false;
   if (!fused_ || config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::ORB ||
       config_.orb_nfeatures + 256 >= 65536 || config_.frame_life_ < 1 || config_.frame_life_ + 1 > 64) {
@@ -1043,9 +1068,40 @@ bool Frontend::ObserveDeviceImage(const void* left, size_t left_pitch, const voi
   fp.left_bytes = left_pitch;
   fp.right_bytes = right_pitch;
   fp.device = true;
-  fp.bayer = bayer_rggb8;
+  fp.pixfmt = pixfmt;
   fp.hip_stream = hip_stream;
   return ObserveFused(width, height, fp);
+}
+
+// A raw frame of any pixel format: the queue takes it as it is; per-call mode makes the two gray images first.
+bool Frontend::ObserveImage(const Image& left_image, const Image& right_image, double time, int pixfmt) {
+  if (pixfmt == VSF_PIX_MONO8) return ObserveImage(left_image, right_image, time);
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (bpp == 0 || left_image.empty() || right_image.empty() || left_image.cols != right_image.cols ||
+      left_image.rows != right_image.rows || left_image.step != right_image.step ||
+      left_image.step < (size_t)left_image.cols * (size_t)bpp) {
+    last_status_ = VSF_ERR_INVALID_ARG;
+    return false;
+  }
+  if (fused_ && config_.descriptor_extract_type_ == FrontendConfig::DescriptorExtractorType::ORB &&
+      config_.orb_nfeatures + 256 < 65536 && config_.frame_life_ >= 1 && config_.frame_life_ + 1 <= 64) {
+    if (!OdomCheck()) return false;
+    return ObserveImageFused(left_image, right_image, pixfmt);
+  }
+  // per-call mode: both images to gray (vsf_to_gray: the queue's kernels, host to host), then the frame as ever -- the
+  // odometry gate is asked inside, once
+  const int w = left_image.cols, h = left_image.rows;
+  if (!EnsureContext(resizing() ? config_.resize_width_ : w, resizing() ? config_.resize_height_ : h)) {
+    if (last_status_ == VSF_OK) last_status_ = VSF_ERR_INVALID_ARG;
+    return false;
+  }
+  const Image* in[2] = {&left_image, &right_image};
+  for (int k = 0; k < 2; k++) {
+    gray_[k].resize((size_t)w * h);
+    last_status_ = vsf_to_gray(ctx_, in[k]->data, 1, w, h, pixfmt, 0, in[k]->step, gray_[k].data(), 0, (size_t)w);
+    if (last_status_ != VSF_OK) return false;
+  }
+  return ObserveImage(Image(gray_[0].data(), h, w, (size_t)w), Image(gray_[1].data(), h, w, (size_t)w), time);
 }
 
 // cc:400-472
@@ -1171,6 +1227,13 @@ void Frontend::set_resize(int width, int height, int camera_width, int camera_he
     config_.image_width = camera_width;
     config_.image_height = camera_height;
   }
+}
+
+void Frontend::set_bayer_order(int pixfmt) {
+  const bool ok = pixfmt == VSF_PIX_BAYER_RGGB8 || pixfmt == VSF_PIX_BAYER_GRBG8 || pixfmt == VSF_PIX_BAYER_GBRG8 ||
+                  pixfmt == VSF_PIX_BAYER_BGGR8;
+  last_status_ = ok ? VSF_OK : VSF_ERR_INVALID_ARG;
+  if (ok) config_.bayer_order_ = pixfmt;
 }
 
 void Frontend::set_imdecode_reduce(int reduce) {
@@ -1419,6 +1482,7 @@ bool FrontendGroup::EnsureContext(int width, int height) {
       m->pending_.assign((size_t)(lead.ctx_depth_ > 0 ? lead.ctx_depth_ : 1), Frontend::PendingFrame());
       m->pending_head_ = m->pending_count_ = 0;
       m->declared_w_ = m->declared_h_ = 0;
+      m->told_bayer_order_ = 0;
     }
   }
   if (!ok)

@@ -104,6 +104,9 @@ struct FrontendConfig {
   // (VSF_ERR_INVALID_ARG: a mosaic cannot be reduced in the DCT domain).  In a FrontendGroup it is per member: a 1280 x 960
   // camera at 2 and a 640 x 480 camera at 1 share one 640 x 480 context.
   int imdecode_reduce_;
+  // The Bayer order of compressed topics (ObserveCompressedImage with bayer_rggb8 set): one of VSF_PIX_BAYER_RGGB8 (the
+  // default: the reference's PointGrey pair), _GRBG8, _GBRG8, _BGGR8 -- vsf_observe_set_bayer_order.
+  int bayer_order_;
   // An addition: cv::resize(img, Size(resize_width_, resize_height_)) in front of everything (0 x 0, the default: off).  When
   // set, the object's context has THAT size and ObserveImage / ObserveDeviceImage / ObserveCompressedImage take frames of the
   // camera's own size, whatever it is: the queue declares it to the object's stream (vsf_observe_set_input_size) and resizes
@@ -185,6 +188,12 @@ class Frontend {
 
   // True iff a new SLAM node was added.  Never throws; a failing GPU call is reported by last_status().
   bool ObserveImage(const Image& left_image, const Image& right_image, double time);
+  // The same for raw frames of any pixel format (VSF_PIX_*, include/vsf.h: sensor_msgs/Image as the driver publishes it --
+  // mono8, the four bayer_*8 orders, bgr8 / rgb8 / bgra8 / rgba8): cols x rows PIXELS, `step` in BYTES.  The frame becomes
+  // gray on the device (inside the queue's batch; in per-call mode by one vsf_to_gray call in front of the steps) and is
+  // observed exactly as ObserveImage observes that gray image: the problem is the same, byte for byte.  VSF_PIX_MONO8 is the
+  // call above.  An unknown code or a step below cols x bytes per pixel: false, last_status() == VSF_ERR_INVALID_ARG, nothing booked.
+  bool ObserveImage(const Image& left_image, const Image& right_image, double time, int pixfmt);
   // The reference's CompressedImageCallback in one call (slam_frontend_main.cc:98-133): the two messages' payloads -- JPEG
   // (baseline or progressive) or PNG -- are decoded on the GPU inside the queue (cv::imdecode IMREAD_GRAYSCALE; with
   // bayer_rggb8 also COLOR_BayerBG2BGR + COLOR_BGR2GRAY) and observed exactly as ObserveImage observes the decoded images,
@@ -207,6 +216,13 @@ class Frontend {
   // synchronous or pipelined; the problem is the one ObserveImage builds from the same pixels, byte for byte.
   bool ObserveDeviceImage(const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
                           double time, bool bayer_rggb8 = false);
+  // ... of any pixel format (VSF_PIX_*): a pitch is >= width x bytes per pixel.
+  bool ObserveDeviceImage(const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
+                          double time, int pixfmt);
+  // config.bayer_order_ (one of the four VSF_PIX_BAYER_* codes; anything else: VSF_ERR_INVALID_ARG and no change).  Legal
+  // at any time: it is read by the next ObserveCompressedImage with bayer_rggb8 set, which books the frames in flight
+  // before the queue is told (vsf_observe_set_bayer_order).
+  void set_bayer_order(int pixfmt);
   void ObserveOdometry(const Vector3f& translation, const Quaternionf& rotation, double timestamp);
   void GetSLAMProblem(slam_types::SLAMProblem* problem) const;
   int GetNumPoses();
@@ -345,13 +361,17 @@ class Frontend {
   enum { kFormRaw = 0, kFormJpeg = 1, kFormPng = 2 };
   int debug_file_form() const { return (config_.debug_jpeg_quality_ > 0 ? kFormJpeg : 0) | (config_.debug_png_ ? kFormPng : 0); }
   const char* debug_file_format() const { return (debug_file_form() & kFormPng) ? "png" : "jpeg"; }  // CompressedView::format
-  bool ObserveImageFused(const Image& left_image, const Image& right_image);
+  bool ObserveImageFused(const Image& left_image, const Image& right_image, int pixfmt = VSF_PIX_MONO8);
+  bool DeclareBayerOrder();  // the queue learns config.bayer_order_ (frames in flight are booked first)
+  int told_bayer_order_ = 0;  // what it was told last (0: nothing: RGGB)
+  std::vector<uint8_t> gray_[2];  // per-call mode: the gray images of a frame of another pixel format
   struct FramePayload {  // what a frame brings to the queue: two raw images at `step`, two compressed files, or two
                          // images in device memory at left_bytes / right_bytes per row, ordered on `hip_stream`
     const uint8_t* left = nullptr;
     const uint8_t* right = nullptr;
     size_t step = 0, left_bytes = 0, right_bytes = 0;
     bool compressed = false, bayer = false, device = false;
+    int pixfmt = -1;  // raw and device frames: a VSF_PIX_* code; -1: `bayer` says it (MONO8 or BAYER_RGGB8)
     int reduce = 1;  // compressed: config.imdecode_reduce_ at the call
     void* hip_stream = nullptr;
   };
@@ -470,6 +490,13 @@ class FrontendGroup {
   bool ObserveDeviceImage(int i, const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
                           double time, bool bayer_rggb8 = false) {
     return member(i).ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time, bayer_rggb8);
+  }
+  bool ObserveImage(int i, const Image& left_image, const Image& right_image, double time, int pixfmt) {
+    return member(i).ObserveImage(left_image, right_image, time, pixfmt);
+  }
+  bool ObserveDeviceImage(int i, const void* left, size_t left_pitch, const void* right, size_t right_pitch, void* hip_stream,
+                          double time, int pixfmt) {
+    return member(i).ObserveDeviceImage(left, left_pitch, right, right_pitch, hip_stream, time, pixfmt);
   }
   bool ObserveCompressedImage(int i, const uint8_t* left, size_t left_bytes, const uint8_t* right, size_t right_bytes,
                               bool bayer_rggb8, double time) {
