@@ -299,6 +299,67 @@ def test_declared_input_size(oracle, pixfmt):
         assert s["resized_frames"] == 6 and s["pixfmt_frames"] == 6, s
 
 
+# ---- 5b. ONE Bayer batch fed from all three sources: host mosaics, device mosaics and compressed mosaics ----
+def _submit_mixed(ctx, dev, calib, sources, frames, files):
+    """Frame i from sources[i]: "host" (the raw host call), "dev" (odd offset, odd pitch) or a file of files[i]."""
+    tickets = []
+    for i, src in enumerate(sources):
+        l, r = frames[i]
+        if src == "host":
+            tickets.append(ctx.observe_submit_stream_pix(0, l, r, pr.PIX_BAYER_GRBG8, calib, best_percent=BP, frame_life=LIFE))
+        elif src == "dev":
+            lp, ls = dev.put(l, 1 + i % 3, (1, 3, 5)[i % 3], poison=0xA5 if i & 1 else 0x3C)
+            rp, rs = dev.put(r, 3, 7, tail=0 if i == 5 else 64)
+            tickets += ctx.observe_submit_dev([(lp, ls, rp, rs)], calib, pixfmt=pr.PIX_BAYER_GRBG8, best_percent=BP, frame_life=LIFE)
+        else:
+            tickets.append(ctx.observe_submit_compressed_stream(0, *files[i], calib, bayer=True, best_percent=BP, frame_life=LIFE)[1])
+    return tickets
+
+
+def test_own_size_mosaics_from_host_device_and_files_in_one_batch(world, oracle):
+    """326 x 246 GRBG, depth 8, everything waits together: host, dev, png, host, jpeg, dev, dev, host leave as ONE batch with
+    ONE demosaic, behind the last step that wrote mosaics (the decoders)."""
+    from vision_slam_frontend_amd import capi
+    calib, size = _calib(), SIZES[1]
+    sources = ["host", "dev", "png", "host", "jpeg", "dev", "dev", "host"]
+    frames = world[size, pr.PIX_BAYER_GRBG8][0][:8]
+    files = {i: (_encode(frames[i][0], s), _encode(frames[i][1], s)) for i, s in enumerate(sources) if s in ("png", "jpeg")}
+    mosaics = [(oracle.jpeg_decode_gray(files[i][0]), oracle.jpeg_decode_gray(files[i][1])) if s == "jpeg" else frames[i]
+               for i, s in enumerate(sources)]
+    want = _raw_results(*size, _gray(mosaics, pr.PIX_BAYER_GRBG8))
+    dev = _Dev()
+    with _context(*size, 8, min_batch=8) as ctx:
+        assert ctx.observe_set_bayer_order(0, pr.PIX_BAYER_GRBG8) == capi.VSF_OK
+        tickets = _submit_mixed(ctx, dev, calib, sources, frames, files)
+        got = [ctx.observe_collect_bytes(t, LIFE)[1].tobytes() for t in tickets]
+        s = ctx.observe_stats()
+    _assert_equal(got, want)
+    assert s["batches"] == 1 and s["pixfmt_frames"] == 8 and s["pixfmt_commands"] == 1, s
+    assert s["compressed"] == 2 and s["device_frames"] == 3, s
+
+
+def test_declared_size_mosaics_from_host_device_and_files_in_one_batch(oracle):
+    """The 96 x 80 GRBG scene of test_declared_input_size into the 320 x 240 context, depth 8: host, dev, png, dev, host, png
+    leave as ONE batch; every frame is cv::resize(to_gray(mosaic))."""
+    from vision_slam_frontend_amd import capi
+    calib, (W, H), f = _calib(), SIZES[0], pr.PIX_BAYER_GRBG8
+    rng = np.random.default_rng(5)
+    small = [(_raw_image(l, f, rng), _raw_image(r, f, rng)) for l, r in _scene(96, 80, n=6, n_objects=60)]
+    want = _raw_results(W, H, [(oracle.resize_linear(pr.to_gray(l, f), W, H), oracle.resize_linear(pr.to_gray(r, f), W, H))
+                               for l, r in small])
+    sources = ["host", "dev", "png", "dev", "host", "png"]
+    files = {i: (_encode(small[i][0], s), _encode(small[i][1], s)) for i, s in enumerate(sources) if s == "png"}
+    dev = _Dev()
+    with _context(W, H, 8, min_batch=6) as ctx:
+        ctx.observe_set_input_size(0, 96, 80)
+        assert ctx.observe_set_bayer_order(0, f) == capi.VSF_OK
+        tickets = _submit_mixed(ctx, dev, calib, sources, small, files)
+        got = [ctx.observe_collect_bytes(t, LIFE)[1].tobytes() for t in tickets]
+        s = ctx.observe_stats()
+    _assert_equal(got, want)
+    assert s["batches"] == 1 and s["resized_frames"] == 6 and s["compressed"] == 2, s
+
+
 # ---- 6. reset_stream; the stats of a queue that never saw a new format ----
 def test_reset_stream_and_stats(world):
     from vision_slam_frontend_amd import capi

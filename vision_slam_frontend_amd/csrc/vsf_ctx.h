@@ -255,13 +255,12 @@ struct vsf_ctx {
     vsfi::PinnedBuf<uint8_t> h_in;            // pinned [depth] big slots
     vsfi::DevBuf<uint8_t> d_in_ring;          // [depth] big slots
     vsfi::DevBuf<uint8_t> d_bayer_in;         // [bmax] big slots
-    std::vector<vsfi::ObserveResizeIn> resize_in;  // launch_batch's: the batch as observe_resize_plan takes it ...
-    vsfi::ObserveResizePlan resize_plan;           // ... and plans it
-    std::vector<const uint8_t*> rs_files;          // ingest_resized's: the batch's files, their sizes and kinds per decode
-    std::vector<size_t> rs_sizes;
-    std::vector<uint8_t> rs_kinds;
-    std::vector<uint8_t> run_kinds;          // launch_batch's: the batch's kinds as observe_batch_runs takes them ...
-    std::vector<vsfi::ObserveRun> runs;      // ... and splits them
+    // launch_batch's: what every frame of the batch is and the commands of its ingest (vsf_observe_plan.h; kept from batch to
+    // batch, as `plan` is: no allocation per batch); ingest()'s: the batch's files, their sizes, kinds and denominators per decode
+    vsfi::ObserveIngestPlan ingest;
+    std::vector<const uint8_t*> dec_files;
+    std::vector<size_t> dec_sizes;
+    std::vector<uint8_t> dec_kinds, dec_reduces;
     bool pix_seen = false;                   // a frame with pix_new has been submitted (vsf_observe_stats [30] .. [32])
     int64_t stat_dev_commands = 0;           // the caller's share of vsf_observe_stats value 18 (the submits' launches)
     size_t out_cap = 0, out_stride = 0;
@@ -449,6 +448,20 @@ vsf_status reserve_scratch(vsf_ctx* ctx, int n_frames, int n_pairs);
 vsf_status ensure_pipeline_buffers(vsf_ctx* ctx);
 void free_observe(vsf_ctx* ctx);          // vsf_observe.hip: the queue's threads stop, then everything the queue owns goes
 void stop_observe_threads(vsf_ctx* ctx);  // ... before anything waits for the context's streams to drain
+// vsf_observe_ingest.hip: how a batch's images reach its own buffer, and the buffers that takes -- each built by the first
+// frame that needs it (a queue that only ever sees raw mono frames of the context's size owns none of them).
+size_t compressed_cap(const vsf_ctx* ctx);    // bytes a compressed file may have: the submit's probe and the ring
+vsf_status ensure_compressed(vsf_ctx* ctx);   // the pinned ring of files
+vsf_status ensure_device_ring(vsf_ctx* ctx, bool big_slots);  // the events and the table of sources; !big_slots: the device ring
+size_t mosaics_bytes(const vsf_ctx* ctx);     // the mosaics' buffer of own-size Bayer batches ...
+vsf_status ensure_mosaics(vsf_ctx* ctx);      // ... its ONE allocation
+enum { kInHostRing = 1, kInDeviceRing = 2, kInBatch = 4, kInBayer = 8 };  // the buffers of big slots (vsf_observe_plan.h)
+vsf_status ensure_input(vsf_ctx* ctx, int what, size_t need = 0);
+size_t input_bytes(const vsf_ctx* ctx);  // vsf_observe_stats: every byte the big slots take
+// The copy stream's command sequence for frames [t0, t0 + n) as `plan` has it (observe_ingest_plan), up to ev_uploaded, which
+// the context's stream waits for.
+vsf_status ingest(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, const vsfi::ObserveIngestPlan& plan,
+                  hipStream_t s_copy);
 
 vsf_status check_status_word(vsf_ctx* ctx);
 vsf_status validate_images(const vsf_ctx* ctx, const uint8_t* d_imgs, int n, size_t image_stride, size_t row_stride);

@@ -81,6 +81,17 @@ MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
   return v;
 }
 
+// The tail's scratch o.floats: means [bmax] | thr [bmax + 1] | thr_state [n_streams] (cc:353, what crosses batches) ...
+size_t tail_floats(const vsf_ctx::Observe& o) { return 2 * (size_t)o.bmax + 1 + (size_t)o.n_streams; }
+float* tail_means(const vsf_ctx::Observe& o) { return o.floats.get(); }
+float* tail_thr(const vsf_ctx::Observe& o) { return o.floats.get() + o.bmax; }
+float* tail_thr_state(const vsf_ctx::Observe& o) { return o.floats.get() + 2 * o.bmax + 1; }
+// ... and o.ints: counts_f [2 bmax] | nfeat [bmax] | npoints [bmax]
+size_t tail_ints(const vsf_ctx::Observe& o) { return 4 * (size_t)o.bmax; }
+int32_t* tail_counts_f(const vsf_ctx::Observe& o) { return o.ints.get(); }
+int32_t* tail_nfeat(const vsf_ctx::Observe& o) { return o.ints.get() + 2 * o.bmax; }
+int32_t* tail_npoints(const vsf_ctx::Observe& o) { return o.ints.get() + 3 * o.bmax; }
+
 }  // namespace
 
 namespace vsfi {
@@ -166,8 +177,7 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   const int NS = ctx->ob_streams;
   std::vector<float> thr_state((size_t)NS, 10000.0f);  // cc:353, per stream
   if (o.floats)
-    VSF_HIP(hipMemcpy(thr_state.data(), o.floats + 2 * o.bmax + 1, (size_t)std::min(NS, o.n_streams) * sizeof(float),
-                      hipMemcpyDeviceToHost));
+    VSF_HIP(hipMemcpy(thr_state.data(), tail_thr_state(o), (size_t)std::min(NS, o.n_streams) * sizeof(float), hipMemcpyDeviceToHost));
   free_observe(ctx);
   o.n_streams = NS;
   o.streams.assign((size_t)NS, vsf_ctx::ObserveStream());
@@ -186,12 +196,12 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   VSF_HIP(o.set_counts.alloc(S * sizeof(int32_t)));
   VSF_HIP(hipMemset(o.set_counts, 0, S * sizeof(int32_t)));
   VSF_HIP(o.residual.alloc(B * K * sizeof(float)));
-  VSF_HIP(o.floats.alloc((2 * B + 1 + NS) * sizeof(float)));
-  VSF_HIP(hipMemset(o.floats, 0, (2 * B + 1 + NS) * sizeof(float)));
-  VSF_HIP(hipMemcpy(o.floats + 2 * B + 1, thr_state.data(), (size_t)NS * sizeof(float), hipMemcpyHostToDevice));
+  VSF_HIP(o.floats.alloc(tail_floats(o) * sizeof(float)));
+  VSF_HIP(hipMemset(o.floats, 0, tail_floats(o) * sizeof(float)));
+  VSF_HIP(hipMemcpy(tail_thr_state(o), thr_state.data(), (size_t)NS * sizeof(float), hipMemcpyHostToDevice));
   VSF_HIP(o.kpf.alloc(2 * B * K * sizeof(vsf_keypoint)));
-  VSF_HIP(o.ints.alloc(4 * B * sizeof(int32_t)));
-  VSF_HIP(hipMemset(o.ints, 0, 4 * B * sizeof(int32_t)));
+  VSF_HIP(o.ints.alloc(tail_ints(o) * sizeof(int32_t)));
+  VSF_HIP(hipMemset(o.ints, 0, tail_ints(o) * sizeof(int32_t)));
   VSF_HIP(o.ex_idx2.alloc(B * K * 2 * sizeof(int32_t)));
   VSF_HIP(o.ex_dist2.alloc(B * K * 2 * sizeof(int32_t)));
   VSF_HIP(o.t_idx2.alloc(P * K * 2 * sizeof(int32_t)));
@@ -278,278 +288,6 @@ vsf_status ensure_observe(vsf_ctx* ctx, int frame_life) {
   return VSF_OK;
 }
 
-bool pix_is_bayer(int pixfmt) {
-  return pixfmt == VSF_PIX_BAYER_RGGB8 || pixfmt == VSF_PIX_BAYER_GRBG8 || pixfmt == VSF_PIX_BAYER_GBRG8 ||
-         pixfmt == VSF_PIX_BAYER_BGGR8;
-}
-
-// The pinned ring the compressed files wait in (and, for bayer_rggb8 frames, the buffer their mosaics are decoded into):
-// built by the first compressed submit -- a queue that only ever sees raw frames owns none of this.
-// Bytes a compressed file may have: ONE derivation, for the submit's probe and for the ring (vsf_observe_set_compressed_cap
-// retires a ring built for another cap, so a ring that exists was built for this value).
-size_t compressed_cap(const vsf_ctx* ctx) {
-  return ctx->ob_cmp_cap ? ctx->ob_cmp_cap : vsf_observe_default_compressed_cap(ctx->p.width, ctx->p.height);
-}
-
-vsf_status ensure_compressed(vsf_ctx* ctx, bool bayer) {
-  vsf_ctx::Observe& o = ctx->ob;
-  if (!o.h_cmp) {
-    const size_t cap = compressed_cap(ctx);
-    const size_t ring = vsf_observe_compressed_ring_bytes(o.depth, cap);
-    if (ring == 0) return VSF_ERR_INVALID_ARG;
-    VSF_HIP(o.h_cmp.alloc(ring, hipHostMallocDefault));
-    o.cmp_cap = cap;
-    o.cmp_slot = vsf_observe_compressed_slot_bytes(cap);
-  }
-  if (bayer && !o.d_bayer) VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
-  return VSF_OK;
-}
-
-// The device ring, its table of sources and its events: built by the first device frame -- a queue that never sees one owns
-// none of this (vsf_observe_device_ring_bytes says what it costs).
-// (resized: the frames have a declared input size -- they wait in the ring of big slots, ensure_input, not in this one)
-vsf_status ensure_device_ring(vsf_ctx* ctx, bool bayer, bool resized = false) {
-  vsf_ctx::Observe& o = ctx->ob;
-  if (o.dev_ev.empty()) {
-    std::vector<Event> ev((size_t)o.depth);
-    for (Event& e : ev) VSF_HIP(e.alloc(hipEventDisableTiming));
-    VSF_HIP(o.h_dev_src.alloc((size_t)o.depth * 2 * sizeof(VsfIngestSrc), hipHostMallocMapped));
-    o.dev_ev = std::move(ev);
-  }
-  if (resized) return VSF_OK;
-  if (!o.d_ring) {
-    const size_t bytes = vsf_observe_device_ring_bytes(ctx, o.depth);
-    if (bytes == 0) return VSF_ERR_INVALID_ARG;
-    VSF_HIP(o.d_ring.alloc(bytes));
-  }
-  if (bayer && !o.d_bayer) VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
-  return VSF_OK;
-}
-
-// ---- frames of a declared input size (vsf_observe_set_input_size) ----
-// The buffers of big slots (vsf_observe_plan.h), each built by the first frame that needs it -- a queue that never sees a
-// declared size owns none of this: the pinned ring raw host frames wait in, the device ring, the batches' own big slots (a
-// raw frame's upload, a compressed frame's decoded image), the mosaics of a Bayer batch.
-enum { kInHostRing = 1, kInDeviceRing = 2, kInBatch = 4, kInBayer = 8 };
-
-// need: bytes the arriving frame's image takes where that is more than every declared size's (a packed-colour frame,
-// observe_pix_image_bytes: its rows are w * bpp bytes); the first frame that needs more room rebuilds, as a larger declared size does
-vsf_status ensure_input(vsf_ctx* ctx, int what, size_t need = 0) {
-  vsf_ctx::Observe& o = ctx->ob;
-  const size_t half = std::max(observe_input_half_bytes(ctx->ob_in_w, ctx->ob_in_h, ctx->ob_streams), need);
-  if (half == 0) return VSF_ERR_INVALID_ARG;
-  if (o.in_half != 0 && half > o.in_half) {
-    // A larger size has been declared since these were built, and frames of other streams may wait in them or be on their
-    // way out of them: what waits leaves, what left finishes, then they go (rare, and the one place the resize path waits).
-    ObserveQueue& q = *o.queue;
-    {
-      std::unique_lock<std::mutex> lk(q.mu);
-      if (q.status != VSF_OK) return q.status;
-      if (q.next_launch < q.next_ticket) {
-        const vsf_status st = q.caller_pump(lk, true);
-        if (st != VSF_OK) return st;
-      }
-    }
-    VSF_HIP(hipDeviceSynchronize());
-    if (o.h_in) ctx->retired_host.emplace_back(o.h_in.release());
-    o.d_in_ring = DevBuf<uint8_t>();
-    o.d_bayer_in = DevBuf<uint8_t>();
-    for (vsf_ctx::ObserveBatch& b : o.batch) b.d_in = DevBuf<uint8_t>();
-  }
-  o.in_half = std::max(o.in_half, half);
-  const size_t slot = 2 * o.in_half;
-  if ((what & kInHostRing) && !o.h_in) VSF_HIP(o.h_in.alloc((size_t)o.depth * slot, hipHostMallocDefault));
-  if ((what & kInDeviceRing) && !o.d_in_ring) VSF_HIP(o.d_in_ring.alloc((size_t)o.depth * slot));
-  if ((what & kInBayer) && !o.d_bayer_in) VSF_HIP(o.d_bayer_in.alloc((size_t)o.bmax * slot));
-  if (what & (kInBatch | kInBayer))
-    for (vsf_ctx::ObserveBatch& b : o.batch)
-      if (!b.d_in) VSF_HIP(b.d_in.alloc((size_t)o.bmax * slot));
-  return VSF_OK;
-}
-
-size_t input_bytes(const vsf_ctx* ctx) {  // vsf_observe_stats: every byte the resize path owns
-  const vsf_ctx::Observe& o = ctx->ob;
-  const size_t slot = 2 * o.in_half;
-  size_t bytes = (o.h_in ? (size_t)o.depth * slot : 0) + (o.d_in_ring ? (size_t)o.depth * slot : 0) +
-                 (o.d_bayer_in ? (size_t)o.bmax * slot : 0);
-  for (const vsf_ctx::ObserveBatch& b : o.batch) bytes += (b.d_in ? (size_t)o.bmax * slot : 0) + 2 * b.blob_in.cap;
-  return bytes;
-}
-
-// The batch's resized frames (o.resize_plan) on `s`: the raw host frames' uploads (ObserveUpload: one per stretch of them,
-// short gaps bridged) into the batch's big slots; the compressed frames' files decoded there at their own size, size by size; BayerBG -> gray at that
-// size for a Bayer batch; then ONE resize launch per run into the batch's images, where every other frame's pixels are
-// already (or, for a frame no kernel reads before, about to be) written.  *files: compressed frames were among them -- the
-// caller owes the batch its ingest finish.
-vsf_status ingest_resized(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s, bool* files) {
-  vsf_ctx::Observe& o = ctx->ob;
-  ObserveLaunchStats& stats = o.queue->stats;
-  const ObserveResizePlan& R = o.resize_plan;
-  const size_t half = o.in_half, slot = 2 * half;
-  const int pixfmt = o.frames[(size_t)(t0 % o.depth)].pixfmt, bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
-  const bool bayer = pix_is_bayer(pixfmt);
-  *files = false;
-  for (const ObserveUpload& u : R.uploads) {
-    VSF_HIP(hipMemcpyAsync(b.d_in + (size_t)u.f0 * slot, o.h_in + (size_t)u.slot0 * slot, (size_t)u.n * slot, hipMemcpyHostToDevice, s));
-    (bpp > 1 ? stats.pix_commands : stats.resize_commands)++;  // (packed colour is in the big slots whatever its size)
-  }
-  // ---- cv::imdecode of the files, whole, at the size they have: a decode_runs per distinct size among them ----
-  const int N = 2 * n;
-  // (kept from batch to batch: no allocation on the launch path)
-  std::vector<const uint8_t*>& fl = o.rs_files;
-  std::vector<size_t>& sizes = o.rs_sizes;
-  std::vector<uint8_t>& kinds = o.rs_kinds;
-  fl.resize((size_t)N);
-  sizes.resize((size_t)N);
-  kinds.resize((size_t)N);
-  const auto is_file = [&](int f) {
-    const ObserveResizeIn& w = o.resize_in[(size_t)f];
-    return w.w != 0 && w.kind != 0 && w.kind != kObserveKindDevice;
-  };
-  int done[VSF_OBSERVE_MAX_STREAMS][2], n_done = 0;  // the sizes decoded so far: at most one per stream
-  for (int f0 = 0; f0 < n; f0++) {
-    const ObserveResizeIn lead = o.resize_in[(size_t)f0];
-    bool seen = !is_file(f0);  // (a size is decoded at the first frame that has it)
-    for (int q = 0; q < n_done && !seen; q++) seen = done[q][0] == lead.w && done[q][1] == lead.h;
-    if (seen || n_done == VSF_OBSERVE_MAX_STREAMS) continue;
-    done[n_done][0] = lead.w, done[n_done++][1] = lead.h;
-    std::fill(kinds.begin(), kinds.end(), (uint8_t)VSF_FILE_NONE);
-    for (int i = 0; i < N; i++) {
-      const int f = i / 2, fslot = (int)((t0 + f) % o.depth);
-      const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)fslot];
-      fl[(size_t)i] = o.h_cmp + ((size_t)fslot * 2 + (size_t)(i & 1)) * o.cmp_slot;
-      sizes[(size_t)i] = fr.nbytes[i & 1];
-      if (fr.in_w == lead.w && fr.in_h == lead.h && fr.kind[0] != 0 && fr.kind[0] != kObserveKindDevice) kinds[(size_t)i] = fr.kind[i & 1];
-    }
-    if (!b.blob_in.uploaded) VSF_HIP(b.blob_in.uploaded.alloc(hipEventDisableTiming));
-    int runs = 0;
-    const vsf_status st = decode_runs(ctx, fl.data(), sizes.data(), kinds.data(), N, lead.w, lead.h, b.blob_in, o.ing_scratch,
-                                      bayer ? o.d_bayer_in.get() : b.d_in.get(), half, (int)observe_input_pitch(lead.w), b.status, 1, s, &runs);
-    if (st != VSF_OK) return st;
-    stats.resize_commands += 1 + runs;  // (the upload, each run's decode)
-    *files = true;
-  }
-  const int cw = ctx->p.width, ch = ctx->p.height;
-  for (const ObserveResizeRun& r : R.runs) {
-    const int pitch = (int)observe_input_pitch(r.w);
-    uint8_t* staged = b.d_in + (size_t)r.f0 * slot;
-    const uint8_t* src = r.where == kObserveInDeviceRing ? o.d_in_ring + (size_t)r.src0 * slot : staged;
-    if (bayer) {  // the images are mosaics: where they lie -> the batch's big slots
-      // (a raw host mosaic was uploaded into the batch's big slot itself: it goes through the mosaics' buffer and back)
-      uint8_t* mosaics = o.d_bayer_in + (size_t)r.f0 * slot;
-      int n_new = 0;
-      for (int f = r.f0; f < r.f0 + r.n; f++) {
-        n_new += o.frames[(size_t)((t0 + f) % o.depth)].pix_new;
-        if (r.where == kObserveInDeviceRing || o.resize_in[(size_t)f].kind != 0) continue;
-        VSF_HIP(hipMemcpyAsync(mosaics + (size_t)(f - r.f0) * slot, staged + (size_t)(f - r.f0) * slot, slot, hipMemcpyDeviceToDevice, s));
-        stats.pix_commands++;
-      }
-      const uint8_t* mosaic = r.where == kObserveInDeviceRing ? src : mosaics;
-      vsf_launch_to_gray(pixfmt, mosaic, 2 * r.n, r.w, r.h, half, pitch, staged, half, pitch, s);
-      stats.resize_commands++;
-      stats.pix_commands += n_new != 0;
-      stats.pix_frames += n_new;
-      src = staged;
-    } else if (bpp > 1) {  // packed colour, rows of w * bpp bytes: cv::resize(to_gray(frame)) -- gray at the arriving size first
-      const int cpitch = (int)observe_pix_pitch(r.w, bpp);
-      stats.pix_commands++;
-      stats.pix_frames += r.n;
-      if (r.w == cw && r.h == ch) {  // ... which is the context's: straight into the batch's images, nothing to resize
-        vsf_launch_to_gray(pixfmt, src, 2 * r.n, r.w, r.h, half, cpitch, b.d_img + (size_t)r.f0 * 2 * ctx->st_img_stride,
-                           ctx->st_img_stride, (int)ctx->st_img_pitch, s);
-        for (int f = r.f0; f < r.f0 + r.n; f++) stats.device_frames += o.resize_in[(size_t)f].kind == kObserveKindDevice;
-        continue;
-      }
-      uint8_t* gray = o.d_bayer_in + (size_t)r.f0 * slot;
-      vsf_launch_to_gray(pixfmt, src, 2 * r.n, r.w, r.h, half, cpitch, gray, half, pitch, s);
-      src = gray;
-    }
-    vsf_launch_resize_gray(src, 2 * r.n, r.w, r.h, half, (size_t)pitch, b.d_img + (size_t)r.f0 * 2 * ctx->st_img_stride, cw, ch,
-                           ctx->st_img_stride, ctx->st_img_pitch, s);
-    stats.resize_commands++;
-    stats.resized += r.n;
-    for (int f = r.f0; f < r.f0 + r.n; f++) {  // (what the frames also are)
-      stats.device_frames += o.resize_in[(size_t)f].kind == kObserveKindDevice;
-      stats.compressed += is_file(f);
-    }
-  }
-  return VSF_OK;
-}
-
-// The device frames of batch [t0, t0 + n) (o.runs): the copy stream waits for the launches that filled their slots -- for
-// the newest event of every stretch of frames that came over one producer stream: it is behind the others --, then ONE copy
-// command per run takes the slots into the batch's images (into the mosaics' buffer for a Bayer batch).
-vsf_status ingest_device_runs(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, int pixfmt, bool demosaic, hipStream_t s) {
-  const bool bayer = pix_is_bayer(pixfmt);
-  vsf_ctx::Observe& o = ctx->ob;
-  ObserveLaunchStats& stats = o.queue->stats;
-  const vsf_ctx::ObserveFrame* last = nullptr;
-  for (int f = 0; f <= n; f++) {
-    const vsf_ctx::ObserveFrame* fr = f < n ? &o.frames[(size_t)((t0 + f) % o.depth)] : nullptr;
-    if (fr && fr->kind[0] != kObserveKindDevice) continue;
-    if (last && (!fr || fr->dev_stream != last->dev_stream)) VSF_HIP(hipStreamWaitEvent(s, o.dev_ev[(size_t)last->dev_event], 0));
-    last = fr;
-  }
-  const size_t frame_bytes = 2 * ctx->st_img_stride;
-  uint8_t* dst = bayer ? o.d_bayer.get() : b.d_img.get();
-  for (const ObserveRun& r : o.runs) {
-    if (r.cls != kObserveRunDevice) continue;
-    VSF_HIP(hipMemcpyAsync(dst + (size_t)r.f0 * frame_bytes, o.d_ring + (size_t)r.slot0 * frame_bytes, (size_t)r.n * frame_bytes,
-                           hipMemcpyDeviceToDevice, s));
-    stats.device_commands++;
-    stats.device_frames += r.n;
-  }
-  // (a Bayer batch that also holds compressed frames is demosaiced once, behind its decoders: ingest_batch)
-  if (demosaic) {
-    vsf_launch_to_gray(pixfmt, o.d_bayer, 2 * n, ctx->p.width, ctx->p.height, ctx->st_img_stride, (int)ctx->st_img_pitch, b.d_img,
-                       ctx->st_img_stride, (int)ctx->st_img_pitch, s);
-    stats.device_commands++;
-  }
-  return VSF_OK;
-}
-
-// The compressed frames of batch [t0, t0 + n): the batch's 2n images go through decode_runs (vsf_ingest.hip) on `s` -- ONE
-// upload for every run of one format among them, a status word per image (b.status: damage lands on its own image) --, then
-// BayerBG -> gray for bayer_rggb8 frames, and the ingest finish: an image its decoder refused becomes all zero.  Raw frames of
-// the batch have been copied already.
-// finish == false: frames of a declared input size follow (ingest_resized), and the finish behind them is the caller's.
-vsf_status ingest_batch(vsf_ctx* ctx, vsf_ctx::ObserveBatch& b, int64_t t0, int n, hipStream_t s, bool finish = true) {
-  vsf_ctx::Observe& o = ctx->ob;
-  const int w = ctx->p.width, h = ctx->p.height, N = 2 * n;
-  const int pixfmt = o.frames[(size_t)(t0 % o.depth)].pixfmt;
-  const bool bayer = pix_is_bayer(pixfmt);
-  std::vector<const uint8_t*> files((size_t)N);
-  std::vector<size_t> sizes((size_t)N);
-  std::vector<uint8_t> kinds((size_t)N), reduces((size_t)N);
-  bool any_reduced = false;
-  for (int i = 0; i < N; i++) {
-    const int slot = (int)((t0 + i / 2) % o.depth);
-    const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
-    kinds[i] = fr.kind[i & 1] == kObserveKindDevice ? (uint8_t)VSF_FILE_NONE : fr.kind[i & 1];  // (in the ring: not a file)
-    if (o.in_half != 0 && fr.in_w != 0) kinds[i] = (uint8_t)VSF_FILE_NONE;  // (a file of another size: ingest_resized decodes it)
-    reduces[i] = fr.reduce;  // (frames of different denominators share the batch and its ONE upload: a run ends where it changes)
-    any_reduced |= fr.reduce > 1;
-    files[i] = o.h_cmp + ((size_t)slot * 2 + (size_t)(i & 1)) * o.cmp_slot;
-    sizes[i] = fr.nbytes[i & 1];
-  }
-  const size_t stride = ctx->st_img_stride;
-  const int pitch = (int)ctx->st_img_pitch;
-  int runs = 0;
-  // (every file passed the decoders' host half at its submit; b.blob is free: the slot's previous batch has left the GPU)
-  const vsf_status st = decode_runs(ctx, files.data(), sizes.data(), kinds.data(), N, w, h, b.blob, o.ing_scratch,
-                                    bayer ? o.d_bayer.get() : b.d_img.get(), stride, pitch, b.status, 1, s, &runs,
-                                    any_reduced ? reduces.data() : nullptr);
-  if (st != VSF_OK || runs == 0) return st;
-  // bayer_rggb8 (slam_frontend_main.cc:101-109): every image of such a batch is a decoded mosaic
-  if (bayer) vsf_launch_to_gray(pixfmt, o.d_bayer, N, w, h, stride, pitch, b.d_img, stride, pitch, s);
-  if (finish) vsf_launch_ingest_finish(b.d_img, stride, pitch, h, b.status, N, s);
-  // (vsf_observe_stats: one copy command, each run's decode -- counted as one, whatever kernels it takes --, the finish)
-  o.queue->stats.ingest_commands += (finish ? 2 : 1) + runs + (bayer ? 1 : 0);
-  for (int f = 0; f < n; f++) o.queue->stats.compressed += kinds[2 * f] != VSF_FILE_NONE;
-  for (int f = 0; f < n; f++) o.queue->stats.reduced += kinds[2 * f] != VSF_FILE_NONE && reduces[2 * f] > 1;
-  return VSF_OK;
-}
-
 int batches_on_gpu(vsf_ctx* ctx) {  // launched and not finished (a query costs 0.1 us)
   int n = 0;
   for (vsf_ctx::ObserveBatch& b : ctx->ob.batch)
@@ -615,14 +353,23 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   const size_t K = (size_t)ctx->p.max_keypoints;
   const int Kc = (int)K, life = o.frame_life;
   // ---- the batch's plan, before anything is enqueued: a refused batch leaves nothing on the streams ----
-  // (vsf_observe_plan.cc: sets, pairs, the calibration table; the submit has cut the list where a stream's parameters change)
+  // (vsf_observe_plan.cc: sets, pairs, the calibration table -- the submit has cut the list where a stream's parameters change --
+  // and the ingest: what every frame is, the commands that bring its images into b.d_img)
+  ObserveIngestPlan& I = o.ingest;
   o.plan_in.resize((size_t)n);
-  for (int f = 0; f < n; f++) {
+  I.in.resize((size_t)n);
+  for (int f = 0; f < n; f++) {  // the ONE pass over the batch's frames that says what they are
     const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
     o.plan_in[(size_t)f] = {fr.stream, fr.k, &fr.calib, fr.best_percent};
+    I.in[(size_t)f] = {fr.kind[0], fr.pix_new, fr.in_w, fr.in_h};
   }
   const ObservePlan& P = o.plan;
   if (!observe_plan(o.plan_in.data(), n, o.n_streams, o.ring, life, &o.plan) || !P.cuts.empty() || P.n_pairs > o.max_pairs)
+    return VSF_ERR_INVALID_ARG;
+  // (a batch has ONE pixel format: the submit has cut the list where it changes; in_half: the queue has seen a big-slot frame --
+  // until then no record's declared size is looked at or written)
+  if (!observe_ingest_plan(n, o.frames[(size_t)(t0 % o.depth)].pixfmt, t0, o.depth, o.in_half != 0,
+                           observe_upload_max_gap(2 * o.in_half), &I))
     return VSF_ERR_INVALID_ARG;
   const int n_pairs = P.n_pairs, max_pairs_per_frame = P.max_pairs_per_frame;
   // one calibration: it rides in the kernel arguments; one stream: the chain of the lone sequence (both: today's launches)
@@ -631,98 +378,12 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   // solo: a lone frame with nothing else on the GPU runs on ONE stream from upload to result (no event hops in its chain);
   // otherwise copy, extraction and tail have a stream each, so that the next batch's upload and extraction run beside
   // this one's tail.
-  // (any_*: frames of the context's size; rs_*: frames of a declared input size, which take the way of ingest_resized)
-  // (may_resize: the queue has seen a frame of a declared size -- until then no record's in_w is looked at or written)
-  const bool may_resize = o.in_half != 0;
-  bool any_raw = false, any_cmp = false, any_dev = false, rs_any = false, rs_cmp = false, rs_dev = false;
-  for (int f = 0; f < n; f++) {
-    const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
-    const uint8_t kind = fr.kind[0];
-    const bool rs = may_resize && fr.in_w != 0, dev = kind == kObserveKindDevice, cmp = kind != 0 && !dev;
-    any_raw |= !rs && kind == 0;
-    any_dev |= !rs && dev;
-    any_cmp |= !rs && cmp;
-    rs_any |= rs;
-    rs_dev |= rs && dev;
-    rs_cmp |= rs && cmp;
-  }
-  if (any_dev || rs_dev) {  // (vsf_observe_plan.cc: the runs of device frames, cut where the ring wraps)
-    o.run_kinds.resize((size_t)n);
-    for (int f = 0; f < n; f++) o.run_kinds[(size_t)f] = o.frames[(size_t)((t0 + f) % o.depth)].kind[0];
-    // (a device frame of a declared size is not copied: k_resize.hip reads it where it lies, in the ring of big slots)
-    for (int f = 0; rs_dev && f < n; f++)
-      if (o.frames[(size_t)((t0 + f) % o.depth)].in_w != 0) o.run_kinds[(size_t)f] = 0;
-    if (!observe_batch_runs(o.run_kinds.data(), n, t0, o.depth, &o.runs)) return VSF_ERR_INVALID_ARG;
-  }
-  if (rs_any) {
-    o.resize_in.resize((size_t)n);
-    for (int f = 0; f < n; f++) {
-      const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
-      o.resize_in[(size_t)f] = {fr.in_w, fr.in_h, fr.kind[0]};
-    }
-    if (!observe_resize_plan(o.resize_in.data(), n, t0, o.depth, observe_upload_max_gap(2 * o.in_half), &o.resize_plan)) return VSF_ERR_INVALID_ARG;
-    for (int f = 1; f < n; f++)  // (vsf_observe_stats: a batch whose frames came in at more than one size)
-      if (o.resize_in[(size_t)f].w != o.resize_in[0].w || o.resize_in[(size_t)f].h != o.resize_in[0].h) {
-        stats.multi_size++;
-        break;
-      }
-  }
   // (compressed frames are decoded on the copy stream whatever else runs: the decoders' scratch exists once, for that stream)
-  hipStream_t s_copy = solo && !any_cmp && !rs_cmp ? ctx->stream : o.copy_stream, s_ex = ctx->stream,
+  hipStream_t s_copy = solo && !I.files && !I.big_files ? ctx->stream : o.copy_stream, s_ex = ctx->stream,
               s_tail = solo ? ctx->stream : o.tail_stream;
-  // ---- upload: ONE copy command (two when the frames wrap around the staging ring) ----
   {
-    const int slot0 = (int)(t0 % o.depth), first = std::min(n, o.depth - slot0);
-    const size_t frame_bytes = 2 * ctx->st_img_stride;
-    // (a batch that mixes raw and compressed frames copies its whole span of the raw ring: the decoders write behind it)
-    // (raw host mosaics, vsf_observe_submit_stream_pix: into the mosaics' buffer, as the decoders' and the device ring's are)
-    const int pixfmt = o.frames[(size_t)(t0 % o.depth)].pixfmt;
-    const bool mosaics = pix_is_bayer(pixfmt);
-    uint8_t* up = mosaics ? o.d_bayer.get() : b.d_img.get();
-    if (any_raw)
-      VSF_HIP(hipMemcpyAsync(up, o.h_img + (size_t)slot0 * frame_bytes, (size_t)first * frame_bytes,
-                             hipMemcpyHostToDevice, s_copy));
-    if (any_raw && first < n)
-      VSF_HIP(hipMemcpyAsync(up + (size_t)first * frame_bytes, o.h_img, (size_t)(n - first) * frame_bytes,
-                             hipMemcpyHostToDevice, s_copy));
-    // ---- device frames: out of the device ring, behind the launches that put them there ----
-    if (any_dev || rs_dev) {  // (rs_dev alone: the waits for the producers' events, no copy)
-      const vsf_status st = ingest_device_runs(ctx, b, t0, n, pixfmt, mosaics && any_dev && !any_cmp, s_copy);
-      if (st != VSF_OK) return st;
-    }
-    // ---- raw host mosaics alone: their demosaic (with device or compressed frames in the batch, theirs takes these along) ----
-    if (mosaics && any_raw && !any_dev && !any_cmp) {
-      vsf_launch_to_gray(pixfmt, o.d_bayer, 2 * n, ctx->p.width, ctx->p.height, ctx->st_img_stride, (int)ctx->st_img_pitch, b.d_img,
-                         ctx->st_img_stride, (int)ctx->st_img_pitch, s_copy);
-    }
-    if (mosaics && (any_raw || any_dev || any_cmp)) {  // (vsf_observe_stats [30], [31]; frames in big slots: ingest_resized)
-      int n_new = 0;
-      for (int f = 0; f < n; f++) {
-        const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
-        n_new += fr.pix_new && !(may_resize && fr.in_w != 0);
-      }
-      stats.pix_frames += n_new;
-      stats.pix_commands += n_new != 0;  // (the batch's one demosaic)
-    }
-    // ---- compressed frames: one more copy command for their files, the decoders, the ingest finish ----
-    if (any_cmp) {
-      const vsf_status st = ingest_batch(ctx, b, t0, n, s_copy, !rs_cmp);
-      if (st != VSF_OK) return st;
-    }
-    // ---- frames of a declared input size: to the context's size, over whatever the steps above left in their places ----
-    if (rs_any) {
-      bool files = false;
-      const vsf_status st = ingest_resized(ctx, b, t0, n, s_copy, &files);
-      if (st != VSF_OK) return st;
-      if (files) {  // (an image its decoder refused becomes all zero, as in ingest_batch)
-        vsf_launch_ingest_finish(b.d_img, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.height, b.status, 2 * n, s_copy);
-        stats.resize_commands++;
-      }
-    }
-    if (s_copy != s_ex) {
-      VSF_HIP(hipEventRecord(b.ev_uploaded, s_copy));
-      VSF_HIP(hipStreamWaitEvent(s_ex, b.ev_uploaded, 0));
-    }
+    const vsf_status st = ingest(ctx, b, t0, n, I, s_copy);
+    if (st != VSF_OK) return st;
   }
   // ---- the batch's parameters, in pinned memory the kernels read directly ----
   const MetaView M = meta_view(b.h_meta, o.max_pairs, o.bmax);
@@ -763,8 +424,8 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   if (o.last_batch >= 0 && o.batch[o.last_batch].done_stream != s_tail)
     VSF_HIP(hipStreamWaitEvent(s_tail, o.batch[o.last_batch].ev_done, 0));
   // ---- RemoveAmbigStereo (cc:417): residuals, the threshold chain in frame order, the rebuilt frames ----
-  float *means = o.floats, *thr = o.floats + o.bmax, *thr_state = o.floats + 2 * o.bmax + 1;  // thr_state[n_streams]
-  int32_t *counts_f = o.ints, *nfeat = o.ints + 2 * o.bmax, *npoints = o.ints + 3 * o.bmax;
+  float *means = tail_means(o), *thr = tail_thr(o), *thr_state = tail_thr_state(o);
+  int32_t *counts_f = tail_counts_f(o), *nfeat = tail_nfeat(o), *npoints = tail_npoints(o);
   {
     StageTimer t(ctx, s_tail, VSF_STAGE_TAIL, 3);
     // (a lone frame: the three steps in one launch)
@@ -900,6 +561,13 @@ vsf_status set_debug_form(vsf_ctx* ctx, int kind, int quality) {
   return VSF_OK;
 }
 
+// The slot of a frame whose results the views may hand out: collected, and its slot not yet handed to a later frame (valid
+// until `depth` further frames have been submitted).  -1: `ticket` is no such frame, or there is no queue.
+int collected_slot(const vsf_ctx::Observe& o, int64_t ticket) {
+  if (!o.ready || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth) return -1;
+  return (int)(ticket % o.depth);
+}
+
 // A collected frame's two files inside the pinned ring of files; kind: which form the caller asks for.
 vsf_status debug_files_view(vsf_ctx* ctx, int kind, int64_t ticket, const uint8_t** stereo, size_t* stereo_bytes,
                             const uint8_t** match, size_t* match_bytes) {
@@ -908,9 +576,8 @@ vsf_status debug_files_view(vsf_ctx* ctx, int kind, int64_t ticket, const uint8_
   *stereo = *match = nullptr;
   *stereo_bytes = *match_bytes = 0;
   const vsf_ctx::Observe& o = ctx->ob;
-  if (!o.ready || !o.debug || o.files.form.kind != kind || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth)
-    return VSF_ERR_INVALID_ARG;
-  const int slot = (int)(ticket % o.depth);
+  const int slot = o.debug && o.files.form.kind == kind ? collected_slot(o, ticket) : -1;
+  if (slot < 0) return VSF_ERR_INVALID_ARG;
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
   const uint8_t* base = o.files.h_ring + (size_t)slot * o.files.slot;
   const int32_t* n = reinterpret_cast<const int32_t*>(base);
@@ -985,10 +652,8 @@ vsf_status vsf_observe_world_points_view(vsf_ctx* ctx, int64_t ticket, const dou
   *xyz = nullptr;
   *n = 0;
   const vsf_ctx::Observe& o = ctx->ob;
-  // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_debug_view)
-  if (!o.ready || !o.cloud || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth)
-    return VSF_ERR_INVALID_ARG;
-  const int slot = (int)(ticket % o.depth);
+  const int slot = o.cloud ? collected_slot(o, ticket) : -1;
+  if (slot < 0) return VSF_ERR_INVALID_ARG;
   const int32_t count = std::min(std::max(o.h_wp_n[slot], 0), ctx->p.max_keypoints);
   *n = count;
   if (count > 0) *xyz = o.h_wp + (size_t)slot * ctx->p.max_keypoints * 3;
@@ -1000,10 +665,9 @@ vsf_status vsf_observe_debug_view(vsf_ctx* ctx, int64_t ticket, const uint8_t** 
   if (!ctx || !stereo || !match) return VSF_ERR_INVALID_ARG;
   *stereo = *match = nullptr;
   const vsf_ctx::Observe& o = ctx->ob;
-  // collected, and its slot not yet handed to a later frame (the rule of vsf_observe_collect_view)
-  if (!o.ready || !o.debug || o.files.form.kind || ticket < 0 || ticket >= o.queue->next_collect || ticket < o.queue->next_ticket - o.depth)
-    return VSF_ERR_INVALID_ARG;  // (with vsf_observe_set_debug_jpeg / _png the raw canvases never leave the device)
-  const int slot = (int)(ticket % o.depth);
+  // (with vsf_observe_set_debug_jpeg / _png the raw canvases never leave the device)
+  const int slot = o.debug && !o.files.form.kind ? collected_slot(o, ticket) : -1;
+  if (slot < 0) return VSF_ERR_INVALID_ARG;
   const uint32_t flags = reinterpret_cast<const uint32_t*>(o.h_out + (size_t)slot * o.out_stride)[14];
   const uint8_t* base = o.h_dbg + (size_t)slot * o.dbg_stride;
   if (flags & 1) *stereo = base;
@@ -1105,7 +769,7 @@ vsf_status vsf_observe_set_input_size(vsf_ctx* ctx, int stream, int width, int h
 
 vsf_status vsf_observe_set_bayer_order(vsf_ctx* ctx, int stream, int pixfmt) {
   VsfErrorScope scope_(ctx, false);
-  if (!ctx || stream < 0 || stream >= ctx->ob_streams || !pix_is_bayer(pixfmt)) return VSF_ERR_INVALID_ARG;
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams || !observe_pix_is_bayer(pixfmt)) return VSF_ERR_INVALID_ARG;
   // (the rule of vsf_observe_reset_stream: no frame of the stream submitted and not collected)
   if (ctx->ob.ready && ctx->ob.streams[(size_t)stream].uncollected != 0) return VSF_ERR_INVALID_ARG;
   ctx->ob_bayer_order[stream] = pixfmt;
@@ -1125,7 +789,7 @@ vsf_status vsf_observe_reset_stream(vsf_ctx* ctx, int stream) {
   // may be running: they touch their own).  Its window is forgotten by counting its frames from 0 again -- the next frame
   // has no predecessor, and the sets fill in the same order as a fresh queue's.
   const float thr = 10000.0f;  // cc:353
-  VSF_HIP(hipMemcpy(o.floats + 2 * o.bmax + 1 + stream, &thr, sizeof(float), hipMemcpyHostToDevice));
+  VSF_HIP(hipMemcpy(tail_thr_state(o) + stream, &thr, sizeof(float), hipMemcpyHostToDevice));
   if (o.debug && o.seeded) {  // its kept frame goes, its generator is seeded again
     VSF_HIP(hipMemset(reinterpret_cast<int32_t*>(o.dbg_ints + 1) + stream, 0, sizeof(int32_t)));
     const vsf_status sr = upload_debug_generators(ctx, stream, 1);
@@ -1145,12 +809,13 @@ vsf_status vsf_observe_stats(const vsf_ctx* ctx, int64_t* out, int n) {
   const ObserveLaunchStats s = o.queue ? o.queue->stats : ObserveLaunchStats();
   // every byte the compressed path owns: 0 until the first compressed frame
   size_t cmp_bytes = o.h_cmp ? vsf_observe_compressed_ring_bytes(o.depth, o.cmp_cap) : 0;
-  if (o.d_bayer) cmp_bytes += 2 * (size_t)o.bmax * ctx->st_img_stride;
+  const size_t mosaics = o.d_bayer ? mosaics_bytes(ctx) : 0;
+  cmp_bytes += mosaics;
   for (const vsf_ctx::ObserveBatch& b : o.batch) cmp_bytes += 2 * b.blob.cap;
   cmp_bytes += o.ing_scratch.bytes();
   // every buffer a frame of a new format made the queue build or enlarge (they are the compressed and resize paths' too:
   // the mosaics' buffer and the big slots, counted in [13] and [28] as well)
-  const size_t pix_bytes = o.pix_seen ? input_bytes(ctx) + (o.d_bayer ? 2 * (size_t)o.bmax * ctx->st_img_stride : 0) : 0;
+  const size_t pix_bytes = o.pix_seen ? input_bytes(ctx) + mosaics : 0;
   const int64_t v[33] = {s.frames, s.batches, s.max_batch, s.solo, s.forced, s.slot_waits,
                          (int64_t)o.depth, (int64_t)o.bmax, o.stat_copy_ns, s.launch_ns, o.stat_wait_ns,
                          s.compressed, s.ingest_commands, (int64_t)cmp_bytes,
@@ -1182,12 +847,100 @@ static void capture_placement(const vsf_ctx* ctx, int stream, vsf_ctx::ObserveFr
                 sizeof(fr.cam_to_robot));
 }
 
-// Both submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
+// ---- what every submit does: the refusal of its arguments, the size its stream's frames arrive at, the queue opened for its
+// frames, the colours drawn ahead, the booking of a frame ----
+// (a, b: the call's two images, or its array of frames twice)
+static bool submit_args_ok(const vsf_ctx* ctx, const void* a, const void* b, const vsf_calibration* calib, const int64_t* tickets,
+                           float best_percent, int frame_life) {
+  return ctx && a && b && calib && tickets && best_percent >= 0.f && frame_life >= 0 && frame_life + 1 <= VSF_OBSERVE_MAX_PAIRS;
+}
+
+// The stream's declared size (vsf_observe_set_input_size), or the context's.
+struct StreamInput {
+  bool declared;
+  int w, h;
+};
+static StreamInput stream_input(const vsf_ctx* ctx, int stream) {
+  const bool declared = ctx->ob_in_w[stream] != 0;
+  return {declared, declared ? ctx->ob_in_w[stream] : ctx->p.width, declared ? ctx->ob_in_h[stream] : ctx->p.height};
+}
+
+// Whether a big-slot frame needs the conversion's other buffer (kInBayer; also the batches' own big slots): a mosaic's gray
+// image always, packed colour's unless it arrives at the context's size -- then it goes straight into the batch's images.
+static bool gray_slots(const vsf_ctx* ctx, int pixfmt, int w, int h) {
+  return observe_pix_is_bayer(pixfmt) || (vsf_pixfmt_bytes_per_pixel(pixfmt) > 1 && (w != ctx->p.width || h != ctx->p.height));
+}
+
+// Opens the queue -- built by the first submit of any kind -- for n consecutive frames of `stream`: their slots in *span.  What
+// waits and may not share a batch with them leaves first: a stream's frames of one batch share one calibration and one
+// best_percent, a batch's frames their pixel format, so frames that bring others than the waiting frame of THEIR stream in
+// front of them send what waits.
+static vsf_status open_queue(vsf_ctx* ctx, int stream, int pixfmt, const vsf_calibration* calib, float best_percent,
+                             int frame_life, int n, ObserveSpan* span) {
+  vsf_ctx::Observe& o = ctx->ob;
+  if (o.ready && o.frame_life != frame_life) {  // (re-sizing the window drops nothing that is still in the queue)
+    if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
+    stop_observe_threads(ctx);
+  }
+  const vsf_status st = ensure_observe(ctx, frame_life);
+  if (st != VSF_OK) return st;
+  ObserveQueue& q = *o.queue;
+  // (next_ticket and next_collect are the caller's own: nobody else writes them; no room: collect the oldest frame first;
+  // span == nullptr: ONE frame, whose slot is next_ticket % depth)
+  if (span ? !observe_submit_span(q.next_ticket, q.next_collect, o.depth, n, span) : q.next_ticket - q.next_collect >= o.depth)
+    return VSF_ERR_INVALID_ARG;
+  std::unique_lock<std::mutex> lk(q.mu);
+  if (q.status != VSF_OK) return q.status;
+  if (q.next_launch >= q.next_ticket) return VSF_OK;  // (nothing waits)
+  bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].pixfmt != pixfmt;
+  const int64_t mine = o.streams[(size_t)stream].last_ticket;
+  if (!cut && mine >= q.next_launch) {
+    const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
+    cut = observe_plan_must_cut(w0.calib, w0.best_percent, *calib, best_percent);
+  }
+  return cut ? q.caller_pump(lk, true) : VSF_OK;
+}
+
+// The stereo lines' colours, cv::Scalar(rand() % 255, rand() % 255, rand() % 255) (cc:95) in the reference's order -- GCC
+// evaluates the three calls right to left: the first is channel 2 -- drawn ahead for the call's n frames: enough for every
+// frame in the queue (a frame takes at most max_keypoints); the device takes them in frame order from its cursor.
+static void draw_colours_ahead(vsf_ctx* ctx, int n) {
+  vsf_ctx::Observe& o = ctx->ob;
+  if (!o.debug || o.seeded) return;
+  const ObserveQueue& q = *o.queue;
+  const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + n - q.next_collect) * K;
+  for (; o.col_generated < want; o.col_generated++) {
+    const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
+    o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
+  }
+}
+
+// Books the frame of the queue's next ticket in `slot`: its record, its stream's counters, the ticket.  fr: what the submits'
+// frames differ in -- where the two images are (kind, nbytes, reduce, dev_*) and what they are (pixfmt, pix_new, in_w x in_h;
+// 0 x 0: an own-size frame, and all a queue that has seen no big-slot frame ever writes).
+static vsf_status book_frame(vsf_ctx* ctx, int slot, int stream, vsf_ctx::ObserveFrame fr, const vsf_calibration* calib,
+                             float best_percent, int64_t* ticket) {
+  vsf_ctx::Observe& o = ctx->ob;
+  vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
+  fr.calib = *calib;
+  fr.best_percent = best_percent;
+  capture_placement(ctx, stream, fr);
+  fr.batch = -1;
+  fr.stream = stream;
+  fr.k = mine.frames++;
+  mine.uncollected++;
+  mine.last_ticket = o.queue->next_ticket;
+  o.pix_seen |= fr.pix_new;
+  o.frames[(size_t)slot] = fr;
+  return o.queue->submit(ticket);
+}
+
+// The host submits.  kinds == nullptr: raw images of w x h at `stride`; else left / right are files of nbytes[0 / 1] bytes that
 // have passed vsf_observe_probe_compressed_reduced as kinds[0 / 1] at 1 / reduce.
 static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
                                  const int* kinds, const size_t* nbytes, int pixfmt, const vsf_calibration* calib,
                                  float best_percent, int frame_life, int64_t* ticket, int reduce = 1, bool pix_call = false) {
-  const bool bayer = pix_is_bayer(pixfmt);
+  const bool bayer = observe_pix_is_bayer(pixfmt);
   const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
   if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
@@ -1195,69 +948,39 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
     return VSF_ERR_INVALID_ARG;
   VSF_HIP(hipSetDevice(ctx->device));
   vsf_ctx::Observe& o = ctx->ob;
-  // (re-sizing the window drops nothing that is still in the queue)
-  if (o.ready && o.frame_life != frame_life) {
-    if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
-    stop_observe_threads(ctx);
-  }
-  vsf_status st = ensure_observe(ctx, frame_life);
+  vsf_status st = open_queue(ctx, stream, pixfmt, calib, best_percent, frame_life, 1, nullptr);
   if (st != VSF_OK) return st;
-  ObserveQueue& q = *o.queue;
-  if (q.next_ticket - q.next_collect >= o.depth) return VSF_ERR_INVALID_ARG;  // collect the oldest frame first
+  const ObserveQueue& q = *o.queue;
   const int slot = (int)(q.next_ticket % o.depth);
-  {
-    // a stream's frames of one batch share one calibration and one best_percent, a batch's frames `bayer`: a frame that
-    // brings others than the waiting frame of ITS stream in front of it sends what waits first
-    std::unique_lock<std::mutex> lk(q.mu);
-    if (q.status != VSF_OK) return q.status;
-    if (q.next_launch < q.next_ticket) {
-      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].pixfmt != pixfmt;
-      const int64_t mine = o.streams[(size_t)stream].last_ticket;
-      if (!cut && mine >= q.next_launch) {
-        const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
-        cut = observe_plan_must_cut(w0.calib, w0.best_percent, *calib, best_percent);
-      }
-      if (cut) {
-        st = q.caller_pump(lk, true);
-        if (st != VSF_OK) return st;
-      }
-    }
-  }
-  // ---- the two images into the frame's slot of the pinned staging ring, rows at the device pitch (the slot's previous
-  // frame has been collected: its upload is long done) ----
-  if (o.debug && !o.seeded) {
-    // the stereo lines' colours, cv::Scalar(rand() % 255, rand() % 255, rand() % 255) (cc:95) in the reference's order --
-    // GCC evaluates the three calls right to left: the first is channel 2 -- drawn ahead: enough for every frame in the queue
-    // (a frame takes at most max_keypoints); the device takes them in frame order from its cursor
-    const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + 1 - q.next_collect) * K;
-    for (; o.col_generated < want; o.col_generated++) {
-      const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
-      o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
-    }
-  }
-  vsf_ctx::ObserveFrame& fr = o.frames[(size_t)slot];
+  draw_colours_ahead(ctx, 1);
   // (w x h is the stream's declared size then: the callers have checked; packed colour waits in the big slots whatever its size)
   const bool resized = ctx->ob_in_w[stream] != 0 || bpp > 1;
   if (resized) {
     if (bayer && w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
-    const bool gray_slots = bayer || (bpp > 1 && (w != ctx->p.width || h != ctx->p.height));  // (the conversion's other buffer)
-    st = ensure_input(ctx, (kinds ? kInBatch : kInHostRing | kInBatch) | (gray_slots ? kInBayer : 0),
+    st = ensure_input(ctx, (kinds ? kInBatch : kInHostRing | kInBatch) | (gray_slots(ctx, pixfmt, w, h) ? kInBayer : 0),
                       bpp > 1 ? observe_pix_image_bytes(w, h, bpp) : 0);
     if (st != VSF_OK) return st;
-  } else if (bayer && !kinds && !o.d_bayer) {  // (raw host mosaics of the context's size: uploaded into the mosaics' buffer)
-    VSF_HIP(o.d_bayer.alloc(2 * (size_t)o.bmax * ctx->st_img_stride));
   }
   const int64_t t_copy = now_ns();
   if (kinds) {
     // ---- the two files into the frame's slots of the compressed ring (built by the first such frame) ----
-    st = ensure_compressed(ctx, bayer);
+    st = ensure_compressed(ctx);
     if (st != VSF_OK) return st;
+  }
+  // (own-size mosaics go through the mosaics' buffer on their way in; a stream of compressed mosaics keeps one whatever its size)
+  if (bayer && (kinds || !resized)) {
+    st = ensure_mosaics(ctx);
+    if (st != VSF_OK) return st;
+  }
+  if (kinds) {
     if (o.cmp_cap != compressed_cap(ctx) || nbytes[0] > o.cmp_cap || nbytes[1] > o.cmp_cap) return VSF_ERR_CAPACITY;
     uint8_t* h_cmp = o.h_cmp + (size_t)slot * 2 * o.cmp_slot;
     std::memcpy(h_cmp, left, nbytes[0]);
     std::memcpy(h_cmp + o.cmp_slot, right, nbytes[1]);
   } else {
-    // (a frame of a declared size: into its big slot of the pinned ring of such slots, rows at ITS width's pitch)
+    // ---- the two images into the frame's slot of the pinned staging ring, rows at the device pitch (the slot's previous
+    // frame has been collected: its upload is long done); a big-slot frame: into its slot of the pinned ring of such slots,
+    // rows at ITS width's pitch ----
     uint8_t* h_img = resized ? o.h_in + (size_t)slot * 2 * o.in_half : o.h_img + (size_t)slot * 2 * ctx->st_img_stride;
     const size_t h_stride = resized ? o.in_half : ctx->st_img_stride, h_pitch = resized ? observe_pix_pitch(w, bpp) : ctx->st_img_pitch;
     const size_t row = (size_t)w * (size_t)bpp;  // bytes
@@ -1271,28 +994,17 @@ static vsf_status observe_submit(vsf_ctx* ctx, int stream, const uint8_t* left, 
       stage_image(jr.dst, jr.dst_pitch, jr.src, jr.src_pitch, jr.width, jr.rows);
   }
   o.stat_copy_ns += now_ns() - t_copy;
+  vsf_ctx::ObserveFrame fr{};
   for (int k = 0; k < 2; k++) {
     fr.kind[k] = kinds ? (uint8_t)kinds[k] : 0;
     fr.nbytes[k] = kinds ? (uint32_t)nbytes[k] : 0u;
   }
+  fr.reduce = (uint8_t)reduce;
   fr.pixfmt = pixfmt;
   fr.pix_new = pix_call ? pixfmt != VSF_PIX_MONO8 : pixfmt >= VSF_PIX_BAYER_GRBG8;
-  o.pix_seen |= fr.pix_new;
-  fr.reduce = (uint8_t)reduce;
-  if (o.in_half != 0) {  // (a queue that has seen no declared size: the records' sizes are 0 x 0 and stay so)
-    fr.in_w = resized ? w : 0;
-    fr.in_h = resized ? h : 0;
-  }
-  fr.calib = *calib;
-  fr.best_percent = best_percent;
-  capture_placement(ctx, stream, fr);
-  fr.batch = -1;
-  vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
-  fr.stream = stream;
-  fr.k = mine.frames++;
-  mine.uncollected++;
-  mine.last_ticket = q.next_ticket;
-  return q.submit(ticket);
+  fr.in_w = resized ? w : 0;
+  fr.in_h = resized ? h : 0;
+  return book_frame(ctx, slot, stream, fr, calib, best_percent, ticket);
 }
 
 vsf_status vsf_observe_submit(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
@@ -1304,16 +1016,11 @@ vsf_status vsf_observe_submit_stream(vsf_ctx* ctx, int stream, const uint8_t* le
                                      size_t stride, const vsf_calibration* calib, float best_percent, int frame_life,
                                      int64_t* ticket) {
   VsfErrorScope scope_(ctx, false);
-  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
-      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
-    return VSF_ERR_INVALID_ARG;
+  if (!submit_args_ok(ctx, left, right, calib, ticket, best_percent, frame_life)) return VSF_ERR_INVALID_ARG;
   *ticket = -1;
   if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
-  // (the stream's declared size, vsf_observe_set_input_size, or the context's)
-  const bool declared = ctx->ob_in_w[stream] != 0;
-  if (w != (declared ? ctx->ob_in_w[stream] : ctx->p.width) || h != (declared ? ctx->ob_in_h[stream] : ctx->p.height) ||
-      stride < (size_t)w || ctx->p.max_images < 2)
-    return VSF_ERR_INVALID_ARG;
+  const StreamInput in = stream_input(ctx, stream);
+  if (w != in.w || h != in.h || stride < (size_t)w || ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
   return observe_submit(ctx, stream, left, right, w, h, stride, nullptr, nullptr, VSF_PIX_MONO8, calib, best_percent, frame_life, ticket);
 }
 
@@ -1322,17 +1029,13 @@ vsf_status vsf_observe_submit_stream_pix(vsf_ctx* ctx, int stream, const uint8_t
                                          size_t stride_bytes, int pixfmt, const vsf_calibration* calib, float best_percent,
                                          int frame_life, int64_t* ticket) {
   VsfErrorScope scope_(ctx, false);
-  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
-      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
-    return VSF_ERR_INVALID_ARG;
+  if (!submit_args_ok(ctx, left, right, calib, ticket, best_percent, frame_life)) return VSF_ERR_INVALID_ARG;
   *ticket = -1;
   const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
   if (bpp == 0 || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
-  const bool declared = ctx->ob_in_w[stream] != 0;
-  if (w != (declared ? ctx->ob_in_w[stream] : ctx->p.width) || h != (declared ? ctx->ob_in_h[stream] : ctx->p.height) ||
-      stride_bytes < (size_t)w * (size_t)bpp || ctx->p.max_images < 2)
-    return VSF_ERR_INVALID_ARG;
-  if (pix_is_bayer(pixfmt) && w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
+  const StreamInput in = stream_input(ctx, stream);
+  if (w != in.w || h != in.h || stride_bytes < (size_t)w * (size_t)bpp || ctx->p.max_images < 2) return VSF_ERR_INVALID_ARG;
+  if (observe_pix_is_bayer(pixfmt) && w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
   if (bpp > 1 && observe_pix_image_bytes(w, h, bpp) == 0) return VSF_ERR_UNSUPPORTED;  // (2^31 bytes or more an image)
   return observe_submit(ctx, stream, left, right, w, h, stride_bytes, nullptr, nullptr, pixfmt, calib, best_percent, frame_life,
                         ticket, 1, true);
@@ -1371,17 +1074,15 @@ static vsf_status observe_submit_files(vsf_ctx* ctx, int stream, const uint8_t* 
                                        size_t right_bytes, int bayer, int reduce, const vsf_calibration* calib,
                                        float best_percent, int frame_life, int64_t* ticket) {
   VsfErrorScope scope_(ctx, false);
-  if (!ctx || !left || !right || !calib || !ticket || !(best_percent >= 0.f) || frame_life < 0 ||
-      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
-    return VSF_ERR_INVALID_ARG;
+  if (!submit_args_ok(ctx, left, right, calib, ticket, best_percent, frame_life)) return VSF_ERR_INVALID_ARG;
   *ticket = -1;
   if (ctx->p.max_images < 2 || stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
   // the decoders' host half, file by file: a refused file books nothing and leaves the queue as it was
   // a stream with a declared size (vsf_observe_set_input_size): the FILE's size must be that one -- it is decoded whole and
   // resized, cv::resize(DecodeImage(msg)); a reduced decode on top of that is not built
-  const bool declared = ctx->ob_in_w[stream] != 0;
-  if (declared && reduce != 1) return VSF_ERR_INVALID_ARG;
-  const int w = declared ? ctx->ob_in_w[stream] : ctx->p.width, h = declared ? ctx->ob_in_h[stream] : ctx->p.height;
+  const StreamInput in = stream_input(ctx, stream);
+  if (in.declared && reduce != 1) return VSF_ERR_INVALID_ARG;
+  const int w = in.w, h = in.h;
   const size_t cap = compressed_cap(ctx);
   const size_t nbytes[2] = {left_bytes, right_bytes};
   int kinds[2] = {0, 0};
@@ -1408,69 +1109,35 @@ size_t vsf_observe_device_ring_bytes(const vsf_ctx* ctx, int depth) {
 vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame* frames, int n, int pixfmt, void* producer_stream,
                                   const vsf_calibration* calib, float best_percent, int frame_life, int64_t* tickets) {
   VsfErrorScope scope_(ctx, false);
-  if (!ctx || !frames || !calib || !tickets || n < 1 || !(best_percent >= 0.f) || frame_life < 0 ||
-      frame_life + 1 > VSF_OBSERVE_MAX_PAIRS)
-    return VSF_ERR_INVALID_ARG;
+  if (!submit_args_ok(ctx, frames, frames, calib, tickets, best_percent, frame_life) || n < 1) return VSF_ERR_INVALID_ARG;
   for (int i = 0; i < n; i++) tickets[i] = -1;
   const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
   if (bpp == 0) return VSF_ERR_INVALID_ARG;  // (2 .. 15 included)
   if (ctx->p.max_images < 2 || n > 1024) return VSF_ERR_INVALID_ARG;
   if (stream < 0 || stream >= ctx->ob_streams) return VSF_ERR_INVALID_ARG;
-  // (the images have the stream's declared size, vsf_observe_set_input_size, or the context's)
-  const bool declared = ctx->ob_in_w[stream] != 0;
-  const int in_w = declared ? ctx->ob_in_w[stream] : ctx->p.width, in_h = declared ? ctx->ob_in_h[stream] : ctx->p.height;
-  const bool resized = declared || bpp > 1;  // (packed colour waits in the ring of big slots whatever its size)
-  const size_t w = (size_t)in_w * (size_t)bpp;  // a row's bytes
+  const StreamInput in = stream_input(ctx, stream);
+  const bool resized = in.declared || bpp > 1;  // (packed colour waits in the ring of big slots whatever its size)
+  const size_t w = (size_t)in.w * (size_t)bpp;  // a row's bytes
   for (int i = 0; i < n; i++)
     if (!frames[i].left || !frames[i].right || frames[i].left_pitch < w || frames[i].right_pitch < w) return VSF_ERR_INVALID_ARG;
   if (ctx->p.max_keypoints >= 65536) return VSF_ERR_UNSUPPORTED;
-  if (resized && pix_is_bayer(pixfmt) && in_w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
-  if (bpp > 1 && observe_pix_image_bytes(in_w, in_h, bpp) == 0) return VSF_ERR_UNSUPPORTED;  // (2^31 bytes or more an image)
+  const bool bayer = observe_pix_is_bayer(pixfmt);
+  if (resized && bayer && in.w > 16384) return VSF_ERR_UNSUPPORTED;  // (the demosaic's limit)
+  if (bpp > 1 && observe_pix_image_bytes(in.w, in.h, bpp) == 0) return VSF_ERR_UNSUPPORTED;  // (2^31 bytes or more an image)
   if (calib->triangulate_rows != 0 && calib->triangulate_rows != 4 && calib->triangulate_rows != 6) return VSF_ERR_INVALID_ARG;
-  const bool bayer = pix_is_bayer(pixfmt);
   hipStream_t producer = static_cast<hipStream_t>(producer_stream);
   VSF_HIP(hipSetDevice(ctx->device));
   vsf_ctx::Observe& o = ctx->ob;
-  if (o.ready && o.frame_life != frame_life) {  // (re-sizing the window drops nothing that is still in the queue)
-    if (frames_in_queue(ctx)) return VSF_ERR_INVALID_ARG;
-    stop_observe_threads(ctx);
-  }
-  vsf_status st = ensure_observe(ctx, frame_life);
+  ObserveSpan span;  // (the cut rule once: the call's frames share everything it looks at)
+  vsf_status st = open_queue(ctx, stream, pixfmt, calib, best_percent, frame_life, n, &span);
   if (st != VSF_OK) return st;
-  ObserveQueue& q = *o.queue;
-  ObserveSpan span;  // (next_ticket and next_collect are the caller's own: nobody else writes them)
-  if (!observe_submit_span(q.next_ticket, q.next_collect, o.depth, n, &span)) return VSF_ERR_INVALID_ARG;
-  {
-    // the cut rule of observe_submit, once: the call's frames share everything it looks at
-    std::unique_lock<std::mutex> lk(q.mu);
-    if (q.status != VSF_OK) return q.status;
-    if (q.next_launch < q.next_ticket) {
-      bool cut = o.frames[(size_t)((q.next_ticket - 1) % o.depth)].pixfmt != pixfmt;
-      const int64_t mine = o.streams[(size_t)stream].last_ticket;
-      if (!cut && mine >= q.next_launch) {
-        const vsf_ctx::ObserveFrame& w0 = o.frames[(size_t)(mine % o.depth)];
-        cut = observe_plan_must_cut(w0.calib, w0.best_percent, *calib, best_percent);
-      }
-      if (cut) {
-        st = q.caller_pump(lk, true);
-        if (st != VSF_OK) return st;
-      }
-    }
-  }
-  st = ensure_device_ring(ctx, bayer, resized);
-  if (st == VSF_OK && resized) {
-    // (kInBayer: the conversion's other buffer -- also the batches' own big slots, where a mosaic's gray image goes)
-    const bool gray_slots = bayer || (bpp > 1 && (in_w != ctx->p.width || in_h != ctx->p.height));
-    st = ensure_input(ctx, gray_slots ? kInDeviceRing | kInBayer : kInDeviceRing, bpp > 1 ? observe_pix_image_bytes(in_w, in_h, bpp) : 0);
-  }
+  st = ensure_device_ring(ctx, resized);
+  if (st == VSF_OK && bayer && !resized) st = ensure_mosaics(ctx);
+  if (st == VSF_OK && resized)
+    st = ensure_input(ctx, kInDeviceRing | (gray_slots(ctx, pixfmt, in.w, in.h) ? kInBayer : 0),
+                      bpp > 1 ? observe_pix_image_bytes(in.w, in.h, bpp) : 0);
   if (st != VSF_OK) return st;
-  if (o.debug && !o.seeded) {  // the stereo lines' colours, drawn ahead for every frame of the call (observe_submit)
-    const int64_t K = ctx->p.max_keypoints, want = o.col_retired + (q.next_ticket + n - q.next_collect) * K;
-    for (; o.col_generated < want; o.col_generated++) {
-      const uint32_t c2 = (uint32_t)(rand() % 255), c1 = (uint32_t)(rand() % 255), c0 = (uint32_t)(rand() % 255);
-      o.h_col[o.col_generated % o.col_ring] = c0 | (c1 << 8) | (c2 << 16);
-    }
-  }
+  draw_colours_ahead(ctx, n);
   // ---- ONE launch on the producer's stream: the 2 n images into the frames' slots of the ring (the slots' previous frames
   // have been collected: the copies out of them are long done), and the event the batch's copy stream will wait for ----
   const int64_t t_copy = now_ns();
@@ -1483,7 +1150,7 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
     e[1] = {static_cast<const uint8_t*>(frames[i].right), frames[i].right_pitch};
   }
   if (resized)  // (into the ring of big slots, rows at the declared width's pitch: k_resize.hip reads them there)
-    vsf_launch_ingest_ring(o.d_in_ring, o.in_half, (int)observe_pix_pitch(in_w, bpp), in_w * bpp, in_h, span.slot0, o.depth, n, inl,
+    vsf_launch_ingest_ring(o.d_in_ring, o.in_half, (int)observe_pix_pitch(in.w, bpp), in.w * bpp, in.h, span.slot0, o.depth, n, inl,
                            by_table ? o.h_dev_src.get() : nullptr, producer);
   else
     vsf_launch_ingest_ring(o.d_ring, ctx->st_img_stride, (int)ctx->st_img_pitch, ctx->p.width, ctx->p.height, span.slot0, o.depth, n,
@@ -1493,30 +1160,16 @@ vsf_status vsf_observe_submit_dev(vsf_ctx* ctx, int stream, const vsf_dev_frame*
   VSF_STICKY();
   o.stat_dev_commands++;
   o.stat_copy_ns += now_ns() - t_copy;
+  vsf_ctx::ObserveFrame fr{};
+  fr.kind[0] = fr.kind[1] = kObserveKindDevice;
+  fr.pixfmt = pixfmt;
+  fr.pix_new = pixfmt >= VSF_PIX_BAYER_GRBG8;
+  fr.in_w = resized ? in.w : 0;
+  fr.in_h = resized ? in.h : 0;
+  fr.dev_event = ev_slot;
+  fr.dev_stream = producer;
   for (int i = 0; i < n; i++) {
-    vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((span.slot0 + i) % o.depth)];
-    fr.kind[0] = fr.kind[1] = kObserveKindDevice;
-    fr.nbytes[0] = fr.nbytes[1] = 0u;
-    fr.pixfmt = pixfmt;
-    fr.pix_new = pixfmt >= VSF_PIX_BAYER_GRBG8;
-    o.pix_seen |= fr.pix_new;
-    fr.reduce = 1;
-    if (o.in_half != 0) {
-      fr.in_w = resized ? in_w : 0;
-      fr.in_h = resized ? in_h : 0;
-    }
-    fr.dev_event = ev_slot;
-    fr.dev_stream = producer;
-    fr.calib = *calib;
-    fr.best_percent = best_percent;
-    capture_placement(ctx, stream, fr);
-    fr.batch = -1;
-    vsf_ctx::ObserveStream& mine = o.streams[(size_t)stream];
-    fr.stream = stream;
-    fr.k = mine.frames++;
-    mine.uncollected++;
-    mine.last_ticket = q.next_ticket;
-    st = q.submit(&tickets[i]);
+    st = book_frame(ctx, (span.slot0 + i) % o.depth, stream, fr, calib, best_percent, &tickets[i]);
     if (st != VSF_OK) return st;
   }
   return VSF_OK;
@@ -1612,43 +1265,46 @@ vsf_status vsf_observe_collect_view(vsf_ctx* ctx, int64_t ticket, const uint8_t*
   return observe_wait(ctx, ticket, out, out_bytes);
 }
 
-vsf_status vsf_observe_stereo(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
-                              const vsf_calibration* calib, float best_percent, int frame_life, uint8_t* out,
-                              size_t cap, size_t* out_bytes) {
+}  // extern "C"
+
+// The synchronous calls: a submit and the collect of its ticket -- a batch of one.
+template <class Submit>
+static vsf_status stereo_call(vsf_ctx* ctx, uint8_t* out, size_t cap, size_t* out_bytes, Submit submit) {
   VsfErrorScope scope_(ctx, false);
   if (!out || !out_bytes) return VSF_ERR_INVALID_ARG;
   *out_bytes = 0;
   int64_t ticket = -1;
-  const vsf_status st = vsf_observe_submit(ctx, left, right, w, h, stride, calib, best_percent, frame_life, &ticket);
+  const vsf_status st = submit(&ticket);
   if (st != VSF_OK) return st;
   return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
+}
+
+extern "C" {
+
+vsf_status vsf_observe_stereo(vsf_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, size_t stride,
+                              const vsf_calibration* calib, float best_percent, int frame_life, uint8_t* out,
+                              size_t cap, size_t* out_bytes) {
+  return stereo_call(ctx, out, cap, out_bytes, [&](int64_t* t) {
+    return vsf_observe_submit(ctx, left, right, w, h, stride, calib, best_percent, frame_life, t);
+  });
 }
 
 vsf_status vsf_observe_stereo_compressed(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
                                          size_t right_bytes, int bayer, const vsf_calibration* calib, float best_percent,
                                          int frame_life, uint8_t* out, size_t cap, size_t* out_bytes) {
-  VsfErrorScope scope_(ctx, false);
-  if (!out || !out_bytes) return VSF_ERR_INVALID_ARG;
-  *out_bytes = 0;
-  int64_t ticket = -1;
-  const vsf_status st =
-      vsf_observe_submit_compressed(ctx, left, left_bytes, right, right_bytes, bayer, calib, best_percent, frame_life, &ticket);
-  if (st != VSF_OK) return st;
-  return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
+  return stereo_call(ctx, out, cap, out_bytes, [&](int64_t* t) {
+    return vsf_observe_submit_compressed(ctx, left, left_bytes, right, right_bytes, bayer, calib, best_percent, frame_life, t);
+  });
 }
 
 vsf_status vsf_observe_stereo_compressed_reduced(vsf_ctx* ctx, const uint8_t* left, size_t left_bytes, const uint8_t* right,
                                                  size_t right_bytes, int reduce, const vsf_calibration* calib,
                                                  float best_percent, int frame_life, uint8_t* out, size_t cap,
                                                  size_t* out_bytes) {
-  VsfErrorScope scope_(ctx, false);
-  if (!out || !out_bytes) return VSF_ERR_INVALID_ARG;
-  *out_bytes = 0;
-  int64_t ticket = -1;
-  const vsf_status st = vsf_observe_submit_compressed_reduced(ctx, 0, left, left_bytes, right, right_bytes, reduce, calib,
-                                                              best_percent, frame_life, &ticket);
-  if (st != VSF_OK) return st;
-  return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
+  return stereo_call(ctx, out, cap, out_bytes, [&](int64_t* t) {
+    return vsf_observe_submit_compressed_reduced(ctx, 0, left, left_bytes, right, right_bytes, reduce, calib, best_percent,
+                                                 frame_life, t);
+  });
 }
 
 }  // extern "C"

@@ -175,6 +175,55 @@ bool observe_resize_plan(const ObserveResizeIn* in, int n, int64_t t0, int depth
   return true;
 }
 
+bool observe_pix_is_bayer(int pixfmt) {
+  return pixfmt == VSF_PIX_BAYER_RGGB8 || pixfmt == VSF_PIX_BAYER_GRBG8 || pixfmt == VSF_PIX_BAYER_GBRG8 ||
+         pixfmt == VSF_PIX_BAYER_BGGR8;
+}
+
+bool observe_ingest_plan(int n, int pixfmt, int64_t t0, int depth, bool may_resize, int max_gap, ObserveIngestPlan* plan) {
+  if (!plan || depth < 1 || n < 1 || n > depth || t0 < 0 || max_gap < 0 || plan->in.size() < (size_t)n) return false;
+  ObserveIngestPlan& p = *plan;
+  p.pixfmt = pixfmt;
+  p.bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (p.bpp == 0) return false;
+  p.mosaics = observe_pix_is_bayer(pixfmt);
+  p.raw = p.files = p.dev = p.big = p.big_files = p.big_dev = p.multi_size = false;
+  p.own_pix_new = 0;
+  p.cls.resize((size_t)n);
+  p.run_kinds.resize((size_t)n);
+  p.resize_in.resize((size_t)n);
+  for (int f = 0; f < n; f++) {
+    const ObserveIngestIn& w = p.in[(size_t)f];
+    if (w.kind > kObserveKindDevice) return false;
+    const bool big = may_resize && w.in_w != 0, dev = w.kind == kObserveKindDevice, file = w.kind != 0 && !dev;
+    p.cls[(size_t)f] = (uint8_t)((big ? kObserveBigRaw : kObserveOwnRaw) + (file ? 1 : dev ? 2 : 0));
+    p.raw |= !big && !file && !dev;
+    p.files |= !big && file;
+    p.dev |= !big && dev;
+    p.big |= big;
+    p.big_files |= big && file;
+    p.big_dev |= big && dev;
+    p.own_pix_new += p.mosaics && !big && w.pix_new;
+    // (a device frame of a declared size is not copied: k_resize.hip reads it where it lies, in the ring of big slots)
+    p.run_kinds[(size_t)f] = big ? (uint8_t)0 : w.kind;
+    p.resize_in[(size_t)f] = {big ? w.in_w : 0, big ? w.in_h : 0, w.kind};
+    p.multi_size |= p.resize_in[(size_t)f].w != p.resize_in[0].w || p.resize_in[(size_t)f].h != p.resize_in[0].h;
+  }
+  p.multi_size &= p.big;
+  p.demosaic = !p.mosaics ? kObserveStepNone
+               : p.files  ? kObserveAfterDecode
+               : p.dev    ? kObserveAfterDeviceCopies
+               : p.raw    ? kObserveAfterUpload
+                          : kObserveStepNone;
+  p.finish = p.big_files ? kObserveAfterBigDecode : p.files ? kObserveAfterDecode : kObserveStepNone;
+  p.runs.clear();
+  if (p.dev && !observe_batch_runs(p.run_kinds.data(), n, t0, depth, &p.runs)) return false;
+  p.resize.runs.clear();
+  p.resize.uploads.clear();
+  p.resize.n_resized = 0;
+  return !p.big || observe_resize_plan(p.resize_in.data(), n, t0, depth, max_gap, &p.resize);
+}
+
 }  // namespace vsfi
 
 // ---- pixel formats (include/vsf.h): the table behind every call that takes a pixfmt ----

@@ -145,6 +145,52 @@ int observe_upload_max_gap(size_t slot_bytes);
 // keeps its storage.
 bool observe_resize_plan(const ObserveResizeIn* in, int n, int64_t t0, int depth, int max_gap, ObserveResizePlan* plan);
 
+// ---- the ingest of a batch: what every frame is, and which commands take the batch's images to its own buffer ----
+// (vsf_observe_ingest.hip ingest() executes this and decides nothing of it again)
+bool observe_pix_is_bayer(int pixfmt);  // VSF_PIX_BAYER_*
+
+// What a frame is.  OWN-size frames have the context's size and lie where the staging ring's layout puts them (raw: the
+// pinned staging ring, file: the ring of files, device: the device ring); BIG-slot frames have a declared size or packed
+// colour and wait in the rings of big slots (a file: in the ring of files all the same) until k_resize.hip / the gray
+// conversion brings them to the batch's images.
+enum ObserveFrameClass : uint8_t {
+  kObserveOwnRaw = 0, kObserveOwnFile, kObserveOwnDevice, kObserveBigRaw, kObserveBigFile, kObserveBigDevice
+};
+// The step of the copy stream's sequence (raw upload, device copies, decode of own-size files, ..., decode of big-slot files)
+// behind which a command that exists ONCE per batch runs.
+enum { kObserveStepNone = 0, kObserveAfterUpload, kObserveAfterDeviceCopies, kObserveAfterDecode, kObserveAfterBigDecode };
+
+struct ObserveIngestIn {  // a frame of the batch: ObserveFrame::kind[0], its declared size (0 x 0: none), ObserveFrame::pix_new
+  uint8_t kind;
+  bool pix_new;
+  int in_w, in_h;
+};
+struct ObserveIngestPlan {
+  std::vector<ObserveIngestIn> in;  // [n] the caller fills it in its ONE pass over the batch's frames
+  std::vector<uint8_t> cls;         // [n] ObserveFrameClass
+  bool raw = false, files = false, dev = false;  // an own-size frame of that kind is there
+  bool big = false, big_files = false, big_dev = false;  // a big-slot frame; one that is a file / a device frame
+  int pixfmt = 0, bpp = 1;  // the batch's ONE pixel format and its bytes per pixel
+  bool mosaics = false;     // ... is a Bayer order: own-size images go through the mosaics' buffer
+  // An own-size Bayer batch is demosaiced ONCE, behind the last step that wrote mosaics: kObserveAfterUpload / AfterDeviceCopies /
+  // AfterDecode; kObserveStepNone: not mosaics, or no own-size frame.
+  int demosaic = kObserveStepNone;
+  // The ingest finish (an image its decoder refused becomes all zero) is owed when a frame is a file, and runs ONCE, behind the
+  // last step that decodes files: kObserveAfterDecode / AfterBigDecode; kObserveStepNone: no file.
+  int finish = kObserveStepNone;
+  int own_pix_new = 0;      // own-size frames with pix_new of a mosaics batch (vsf_observe_stats [30], [31])
+  bool multi_size = false;  // big-slot frames are there and the batch's frames came in at more than one size
+  std::vector<ObserveRun> runs;  // own-size frames: the device ring's copies (big-slot device frames are read where they lie:
+                                 // they are no device run).  Empty without an own-size device frame.
+  ObserveResizePlan resize;      // big-slot frames.  Empty without one.
+  std::vector<uint8_t> run_kinds;          // (scratch: the batch as observe_batch_runs ...
+  std::vector<ObserveResizeIn> resize_in;  //  ... and observe_resize_plan take it)
+};
+// Classifies plan->in[0, n) -- the frames of tickets [t0, t0 + n) in rings of `depth` slots -- and plans their ingest.
+// may_resize: the queue has seen a big-slot frame (until then no record's declared size means anything); max_gap:
+// observe_upload_max_gap of a big slot.  `plan` keeps its storage from batch to batch.  false: an argument is out of range.
+bool observe_ingest_plan(int n, int pixfmt, int64_t t0, int depth, bool may_resize, int max_gap, ObserveIngestPlan* plan);
+
 }  // namespace vsfi
 
 #endif  // VSF_OBSERVE_PLAN_H_
