@@ -16,12 +16,14 @@
 //    the pixel is a FAST-9 corner iff max(A, B) > t and cornerScore is max(A, B) - 1.  Two pixels are processed per
 //    VALU lane-op on packed 16-bit halves; circle bytes are pulled out of the window with v_perm_b32.  Arcs 2j and 2j + 1
 //    share eight pixels, so max(arc 2j, arc 2j + 1) = min(octet, max(d[2j], d[2j + 9])) (min / max distribute): an octet
-//    is two quads of two pixel pairs -> 8 + 8 + 8 two-input ops, 8 THREE-input ops and a 4-op reduction = 36 packed ops
-//    per polarity (59 with prefix / suffix minima of the circle halves, 80 naively).  The three-input ops are gfx950's
-//    v_pk_minimum3_f16 / v_pk_maximum3_f16 applied to the pixel values as they sit in the halves: 0..255 are f16
-//    denormals, ordered like the integers and not flushed in the default mode (tools/exp/m3.hip: all 2^24 triples, full
-//    issue rate).  With 1.86 G wave-instructions per 512-image launch the kernel issues at 93 % of the vector ALU's rate:
-//    the floor of a dense score;
+//    is two quads, a quad is the minimum of four consecutive circle pixels, and only the four ODD pixel pairs are made
+//    on their own: an even quad is min3(pixel, pixel, pair), an odd one min3(pair, pixel, pixel) -> 4 + 8 two-input ops,
+//    8 + 8 THREE-input ops and a 4-op reduction = 32 packed ops per polarity (36 with all eight pairs, 59 with prefix /
+//    suffix minima of the circle halves, 80 naively).  The three-input ops are gfx950's v_pk_minimum3_f16 /
+//    v_pk_maximum3_f16 applied to the pixel values as they sit in the halves: 0..255 are f16 denormals, ordered like the
+//    integers and not flushed in the default mode (tools/exp/m3.hip: all 2^24 triples, full issue rate).  The kernels
+//    issue 1.22 G wave-instructions per 512-image step (profiles/traffic.json; 1.32 G with 36 ops per polarity), two
+//    thirds of them in this network: the vector ALU's issue rate is the floor of a dense score;
 //  * the only branch is wave-wide: a row is skipped when v_sad_u8 of every lane's 4 pixels against the rows 3 above
 //    and 3 below stays <= t (circle pixels 0 and 8: every 9-arc contains one of them);
 //  * scores stay in registers; the strict 8-neighbour NMS is packed too (row-wise 3-maxima shared between the rows
@@ -80,8 +82,10 @@ __device__ __forceinline__ T uniform_copy(const T* p) {
 // into the two 16-bit halves -- the layout the score works on: pixel pairs (x, x + 2) and (x + 1, x + 3), so that the
 // second pair's circle pixel at column offset dx IS the first pair's at dx + 1.  Over its seven steps in the window a row
 // is asked for exactly the eight pairs b1 .. b8 (as row y +- 3: b3..b6, y +- 2: b2, b3, b6, b7, y +- 1 and y: b1, b2, b7, b8
-// and, as the centre row, b4 / b5 themselves), so they are made ONCE when the row enters -- 3 mask / shift operations, 4
-// DPP moves and 4 v_alignbit -- instead of one v_perm_b32 per use (34 per step in round 3's kernel: profiles/r04/).
+// and, as the centre row, b4 / b5 themselves), so they are made ONCE when the row enters -- straight from
+// the raw dword and its two DPP neighbours: 2 DPP moves, 6 v_perm_b32 and 2 v_and (10 ops; 11 when the even and odd bytes
+// were split first and each half shifted across the lanes) -- instead of one v_perm_b32 per use (34 per step in round 3's
+// kernel: profiles/r04/).
 struct RowP {
   uint32_t d;                            // the raw dword (row pre-check)
   v2s b1, b2, b3, b4, b5, b6, b7, b8;
@@ -91,31 +95,32 @@ __device__ __forceinline__ v2s as_v2s(uint32_t v) { return __builtin_bit_cast(v2
 __device__ __forceinline__ uint32_t as_u32(v2s v) { return __builtin_bit_cast(uint32_t, v); }
 
 __device__ __forceinline__ void prep_row(RowP& r) {
-  const uint32_t e = r.d & 0x00FF00FFu, o = (r.d >> 8) & 0x00FF00FFu;  // (byte 4, byte 6), (byte 5, byte 7)
-  const uint32_t ep = wave_shr1(e), op = wave_shr1(o);                 // (0, 2), (1, 3)
-  const uint32_t en = wave_shl1(e), on = wave_shl1(o);                 // (8, 10), (9, 11)
-  r.b1 = as_v2s(op);
-  r.b2 = as_v2s(__builtin_amdgcn_alignbit(e, ep, 16));                 // (2, 4)
-  r.b3 = as_v2s(__builtin_amdgcn_alignbit(o, op, 16));                 // (3, 5)
-  r.b4 = as_v2s(e);
-  r.b5 = as_v2s(o);
-  r.b6 = as_v2s(__builtin_amdgcn_alignbit(en, e, 16));                 // (6, 8)
-  r.b7 = as_v2s(__builtin_amdgcn_alignbit(on, o, 16));                 // (7, 9)
-  r.b8 = as_v2s(en);
+  const uint32_t d = r.d, p = wave_shr1(d), n = wave_shl1(d);          // bytes 4..7, 0..3 and 8..11 of the run
+  // v_perm_b32: selector bytes 0..3 pick from the second operand, 4..7 from the first, 0x0c gives a zero byte
+  r.b1 = as_v2s(__builtin_amdgcn_perm(0u, p, 0x0c030c01u));            // (1, 3)
+  r.b2 = as_v2s(__builtin_amdgcn_perm(d, p, 0x0c040c02u));             // (2, 4)
+  r.b3 = as_v2s(__builtin_amdgcn_perm(d, p, 0x0c050c03u));             // (3, 5)
+  r.b4 = as_v2s(d & 0x00FF00FFu);                                      // (4, 6)
+  r.b5 = as_v2s(__builtin_amdgcn_perm(0u, d, 0x0c030c01u));            // (5, 7)
+  r.b6 = as_v2s(__builtin_amdgcn_perm(n, d, 0x0c040c02u));             // (6, 8)
+  r.b7 = as_v2s(__builtin_amdgcn_perm(n, d, 0x0c050c03u));             // (7, 9)
+  r.b8 = as_v2s(n & 0x00FF00FFu);                                      // (8, 10)
 }
 
 __device__ __forceinline__ v2s vmin(v2s a, v2s b) { return __builtin_elementwise_min(a, b); }
 __device__ __forceinline__ v2s vmax(v2s a, v2s b) { return __builtin_elementwise_max(a, b); }
-// Three-input packed minimum / maximum of values 0..255 held in 16-bit halves (see score_pair).
+// Three-input packed minimum / maximum of values 0..255 held in 16-bit halves (see score_from_circle): the nested f16
+// minimum / maximum is selected as ONE v_pk_minimum3_f16 / v_pk_maximum3_f16.  Written with the builtins and not as an asm
+// statement, so that the compiler knows the instruction: it schedules the ops apart from their consumers and places a wait
+// state only where the hardware needs one (behind an asm statement it assumes the worst: 13 s_nop per scoring block of
+// this network instead of 4).
+typedef _Float16 v2h __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2h as_v2h(v2s v) { return __builtin_bit_cast(v2h, v); }
 __device__ __forceinline__ v2s vmin3(v2s a, v2s b, v2s c) {
-  v2s r;
-  asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
+  return __builtin_bit_cast(v2s, __builtin_elementwise_minimum(__builtin_elementwise_minimum(as_v2h(a), as_v2h(b)), as_v2h(c)));
 }
 __device__ __forceinline__ v2s vmax3(v2s a, v2s b, v2s c) {
-  v2s r;
-  asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
+  return __builtin_bit_cast(v2s, __builtin_elementwise_maximum(__builtin_elementwise_maximum(as_v2h(a), as_v2h(b)), as_v2h(c)));
 }
 // max(a - b, 0) per half (v_pk_sub_u16 with clamp): a, b in 0 .. 255
 __device__ __forceinline__ v2s vsubsat(v2s a, v2s b) {
@@ -133,22 +138,28 @@ template <bool NMS>
 __device__ __forceinline__ v2s score_from_circle(const v2s (&d)[16], v2s v, v2s toff) {
   // Arc k = d[k .. k+8] (indices mod 16).  Arcs 2j and 2j+1 share the eight pixels C = d[2j+1 .. 2j+8]:
   //   max(min(d[2j], C), min(C, d[2j+9])) = min(C, max(d[2j], d[2j+9]))                       (distributive lattice)
-  // and C is four pixel pairs E_i = min(d[2i+1], d[2i+2]), i = j .. j+3, i.e. two quads F_i = min(E_i, E_{i+1}):
+  // and C is two quads F_j, F_{j+2}, where F_i = min(d[2i+1 .. 2i+4]) is four consecutive pixels:
   //   A = max_j min3(F_j, F_{j+2}, max(d[2j], d[2j+9])),     Bm likewise with min and max exchanged.
-  // 8 + 8 + 8 two-input ops, 8 three-input ops and a 4-op reduction = 36 per polarity (59 with prefix / suffix minima of
-  // the two circle halves).  The three-input ops are gfx950's v_pk_minimum3_f16 / v_pk_maximum3_f16 on the pixel values
+  // With the pixel pairs E_i = min(d[2i+1], d[2i+2]) a quad is min(E_i, E_{i+1}); minimum is associative, so one pair of
+  // each quad can stay two pixels of a three-input op and only the four ODD pairs are ever made:
+  //   i even: F_i = min3(d[2i+1], d[2i+2], E_{i+1}),     i odd: F_i = min3(E_i, d[2i+3], d[2i+4])
+  // (the same numbers, whatever the pixels).  4 + 8 two-input ops, 8 + 8 three-input ops and a 4-op reduction = 32 per
+  // polarity (36 with all eight pairs and F_i = min(E_i, E_{i+1}); 59 with prefix / suffix minima of the two circle
+  // halves).  The three-input ops are gfx950's v_pk_minimum3_f16 / v_pk_maximum3_f16 on the pixel values
   // as they sit in the 16-bit halves: 0..255 are f16 denormals, whose order is the integer order (f16 denormals are
   // never flushed in the default mode; exhaustively checked on MI355X for all 2^24 triples, tools/exp/m3.hip).
   v2s E[8], G[8], F[8], H[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) {
+  for (int j = 1; j < 8; j += 2) {
     E[j] = vmin(d[2 * j + 1], d[(2 * j + 2) & 15]);
     G[j] = vmax(d[2 * j + 1], d[(2 * j + 2) & 15]);
   }
 #pragma unroll
-  for (int j = 0; j < 8; j++) {
-    F[j] = vmin(E[j], E[(j + 1) & 7]);
-    H[j] = vmax(G[j], G[(j + 1) & 7]);
+  for (int j = 0; j < 8; j += 2) {
+    F[j] = vmin3(d[2 * j + 1], d[2 * j + 2], E[j + 1]);
+    H[j] = vmax3(d[2 * j + 1], d[2 * j + 2], G[j + 1]);
+    F[j + 1] = vmin3(E[j + 1], d[(2 * j + 5) & 15], d[(2 * j + 6) & 15]);
+    H[j + 1] = vmax3(G[j + 1], d[(2 * j + 5) & 15], d[(2 * j + 6) & 15]);
   }
   v2s ta[8], tb[8];
 #pragma unroll
