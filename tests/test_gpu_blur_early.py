@@ -1,6 +1,6 @@
 """VSF_OPT_BLUR_EARLY on the GPU: the blur of a pipelined call of 32 images or more is queued behind the call's pyramid chain
 on the pipe stream, into the other of two blurred pyramids, and is not ordered behind the PREVIOUS call's descriptors, which
-may still read theirs (csrc/vsf_blur_plan.h, csrc/vsf_api.hip extract_on).  Nothing a call returns may depend on it:
+may still read theirs (csrc/vsf_extract_plan.h, csrc/vsf_api.hip extract_on).  Nothing a call returns may depend on it:
 
 * five consecutive pipelined vsf_stereo_batch_dev calls on five different image sets with the option 1 throughout, toggled
   1, 0, 1, 1, 0, with every call's images produced late on another stream and handed over by vsf_set_input_event, with a

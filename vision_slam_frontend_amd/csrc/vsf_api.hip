@@ -180,216 +180,147 @@ VsfDev shifted(const VsfDev& d, const VsfGeom& g, int i0) {
   return o;
 }
 
+namespace {
+
+// The GPU backend of vsf_extract_plan.h: its stream and event ids are the context's handles, its stages the launchers.
+struct ExtractHip {
+  vsf_ctx* ctx;
+  const VsfExtractPlan& p;
+  hipStream_t streams[VSF_XS_COUNT];
+  const VsfDev& d;
+  const VsfImages& im;
+  const VsfSideStream* side;  // of a chain on the call's own stream
+  vsf_keypoint* d_kp;
+  uint8_t* d_desc;
+  int32_t* d_counts;
+  bool early_fired = false;
+
+  hipEvent_t event(VsfXEvent e) const {
+    switch (e) {
+      case VSF_XE_FAST_DONE: return ctx->ev_fast_done;
+      case VSF_XE_INGEST_DONE: return ctx->ev_ingest_done;
+      case VSF_XE_INPUT: return ctx->input_event;
+      case VSF_XE_EARLY_GO: return ctx->ev_early_go;
+      case VSF_XE_EARLY_DONE: return ctx->ev_early_done;
+      case VSF_XE_PYR_DONE: return ctx->ev_pyr_done;
+      case VSF_XE_BLUR_FORK: return ctx->ev_blur_fork;
+      case VSF_XE_BLUR_DONE: return ctx->ev_blur_done;
+      default: break;
+    }
+    return e < VSF_XE_CAND_FREE   ? ctx->ev_pyr_free[e - VSF_XE_PYR_FREE]
+           : e < VSF_XE_BLUR_FREE ? ctx->ev_cand_free[e - VSF_XE_CAND_FREE]
+                                  : ctx->ev_blur_free[e - VSF_XE_BLUR_FREE];
+  }
+  void wait(VsfXStream s, VsfXEvent e) { vsf_note(hipStreamWaitEvent(streams[s], event(e), 0)); }
+  void record(VsfXEvent e, VsfXStream s) { vsf_note(hipEventRecord(event(e), streams[s])); }
+  void early() {
+    early_fired = true;
+    vsf_extract_issue_early(p, *this, VSF_XS_PIPE);
+  }
+  void launch(VsfXStage stage, VsfXStream xs) {
+    static const int kTimed[] = {VSF_STAGE_PYRAMID, VSF_STAGE_FAST, VSF_STAGE_FAST, VSF_STAGE_SELECT, VSF_STAGE_BLUR, VSF_STAGE_DESCRIBE};
+    const VsfGeom& g = ctx->orb.g;
+    hipStream_t s = streams[xs];
+    // The chain on the pipe stream is a single chain (ROCm multiplexes streams onto a few hardware queues; the context's aux
+    // stream is known to run beside the main one).  The early FAST part goes behind its launch of level early_levels - 1:
+    // the chain has waited for the inputs by then, and level 0 needs no more than that.
+    const bool hooked = stage == VSF_XG_PYRAMID && xs == VSF_XS_PIPE && p.n_early > 0;
+    {
+      // (the pyramid books its launches; the early FAST part 0: the step's launch count stays what the one-pass FAST reports)
+      StageTimer t(ctx, s, kTimed[stage], stage == VSF_XG_PYRAMID ? g.nlevels - 1 : stage != VSF_XG_FAST_EARLY);
+      const bool big = im.n >= 32;  // the blur's long strips
+      switch (stage) {
+        case VSF_XG_PYRAMID: {
+          const VsfPyramidHook hook{p.early_levels - 1, [](void* self, hipStream_t) { static_cast<ExtractHip*>(self)->early(); }, this};
+          vsf_launch_pyramid(d, g, ctx->orb.levels.data(), im, s, xs == VSF_XS_PIPE ? nullptr : side, hooked ? &hook : nullptr);
+          break;
+        }
+        case VSF_XG_FAST_EARLY:
+          vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, s, ctx->tuning.fast_early_form, ctx->n_cus, ctx->fast_cells,
+                          VSF_FAST_EARLY, p.n_early);
+          break;
+        case VSF_XG_FAST:
+          vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, s, p.resident, ctx->n_cus, ctx->fast_cells,
+                          p.n_early > 0 ? VSF_FAST_LATE : VSF_FAST_ALL, p.n_early);
+          break;
+        case VSF_XG_SELECT: vsf_launch_select(d, g, ctx->orb.levels.data(), im, s); break;
+        case VSF_XG_BLUR:
+          vsf_launch_blur_mma(d, g, im, big ? ctx->dorb.blur_mma_units : ctx->dorb.blur_mma_units_small,
+                              (int)(big ? ctx->orb.blur_mma_units : ctx->orb.blur_mma_units_small).size(), ctx->dorb.blur_tcol,
+                              ctx->dorb.blur_tv, ctx->orb.blur_bias, s);
+          break;
+        case VSF_XG_DESCRIBE: vsf_launch_describe(d, g, im, ctx->p.max_keypoints, d_kp, d_desc, d_counts, s); break;
+      }
+    }
+    if (hooked && !early_fired) early();  // (no launch of the chain made that level: behind all of it)
+  }
+};
+
+}  // namespace
+
 // detectAndCompute for images [i0, i0 + n) of `im` on stream `st`.  `status`: the status word the kernels report capacity
-// overflows into (the context's, or the word of the frame in flight that owns this extraction).
+// overflows into (the context's, or the word of the frame in flight that owns this extraction).  What is queued, where and
+// in which order is vsf_extract_plan.h's; this fills in the facts, the buffers the plan names and the handles.
 void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, int n, vsf_keypoint* d_kp,
                 uint8_t* d_desc, int32_t* d_counts, bool inputs_complete, const VsfSideStream* own_side, int32_t* status,
                 int status_stride) {
   const VsfGeom& g = ctx->orb.g;
-  const bool pipe = ctx->pipeline && inputs_complete && ctx->lanes == 1 && st == ctx->stream && i0 == 0;
-  // VSF_OPT_FAST_EARLY_LEVELS (read here, per call): the full cells of levels < early_levels -- the head [0, n_early) of the
-  // work list, vsf_fast_split.h -- are scored by a launch of their own on blur_stream, which starts as soon as the chain
-  // below has produced level early_levels - 1 and so runs beside the PREVIOUS call's selection and descriptors, whose
-  // kernels wait on latency and leave vector-ALU issue slots unused.  Pipelined calls only; never the tune call.
-  const int early_levels = pipe && ctx->cand_alt && ctx->blur_stream && ctx->fast_force < 0
-                               ? std::min(ctx->tuning.fast_early_levels, g.fast_split_levels)
-                               : 0;
-  const int n_early = early_levels > 0 ? vsf_fast_n_early(ctx->orb.levels.data(), g.nlevels, early_levels) : 0;
-  // Such a call takes the other pair of candidate buffers: its early part writes them while the previous call's selection
-  // may still read its own.  (A call without an early part stays on the pair the last call used: its FAST follows that
-  // call's selection on this stream.  Every pipelined call records the release of the pair it read, so the option may change
-  // from call to call.)
-  if (n_early > 0) {
-    ctx->cand_flip ^= 1;
-    ctx->dorb.d.cand = ctx->cand_flip ? ctx->cand_alt.get() : ctx->dorb.cand.get();
-    ctx->dorb.d.rowstart = ctx->cand_flip ? ctx->rowstart_alt.get() : ctx->dorb.rowstart.get();
-  }
+  const VsfTuning& tn = ctx->tuning;
+  VsfExtractFacts f{};
+  f.pipeline = ctx->pipeline;
+  f.inputs_complete = inputs_complete;
+  f.lanes = ctx->lanes;
+  f.on_main = st == ctx->stream;
+  f.on_aux = st == ctx->aux_stream.get();
+  f.first_image = i0 == 0;
+  f.own_side = own_side != nullptr;
+  f.n = n;
+  f.blur_overlap = ctx->blur_overlap != 0;
+  f.blur_stream = (bool)ctx->blur_stream;
+  f.cand_alt = (bool)ctx->cand_alt;
+  f.blur_alt = (bool)ctx->blur_alt;
+  f.pipe_after_fast = tn.pipe_after_fast != 0;
+  f.blur_early = tn.blur_early != 0;
+  f.early_levels = std::min(tn.fast_early_levels, g.fast_split_levels);  // (read here, per call)
+  f.n_early = f.pipeline ? vsf_fast_n_early(ctx->orb.levels.data(), g.nlevels, f.early_levels) : 0;  // (only such a call asks)
+  f.fast_force = ctx->fast_force;
+  f.fast_resident = ctx->fast_resident;
+  f.tune_n = ctx->fast_tune.n;
+  f.tune_choice = ctx->fast_tune.choice;
+  f.ingest_pending = ctx->ingest_done_valid;
+  f.input_pending = ctx->input_event != nullptr;
+  const VsfExtractPlan p = vsf_extract_plan(&ctx->extract_state, f);
+  // the buffers the plan names (dorb.d.cand / .rowstart, last_pyr, last_blur: what the LAST call used, for every other
+  // path and the debug hooks)
+  ctx->dorb.d.cand = p.cand_buf ? ctx->cand_alt.get() : ctx->dorb.cand.get();
+  ctx->dorb.d.rowstart = p.cand_buf ? ctx->rowstart_alt.get() : ctx->dorb.rowstart.get();
   VsfDev d = shifted(ctx->dorb.d, g, i0);
   if (status) {
     d.status = status;
     d.status_stride = status_stride;
   }
+  if (p.pyr_buf) d.pyr = ctx->pyr_alt.get() + (size_t)i0 * g.pyr_bytes;
+  if (p.blur_buf) d.blur = ctx->blur_alt.get() + (size_t)i0 * g.pyr_bytes;
+  ctx->last_pyr = d.pyr - (size_t)i0 * g.pyr_bytes;
+  if (!p.blur_lane) ctx->last_blur = p.blur_buf ? ctx->blur_alt.get() : ctx->dorb.d.blur;
   VsfImages im = im_all;
   im.base += (size_t)i0 * im.image_stride;
   im.n = n;
   const size_t K = (size_t)ctx->p.max_keypoints;
-  // The blur runs beside other stages in batches of 32 images or more (the comment above `resident` below).  Where, into
-  // which of the two blurred pyramids, behind which release: vsf_blur_plan.h.  VSF_OPT_BLUR_EARLY (read here, per call)
-  // makes a pipelined call of that kind VSF_BLUR_EARLY; the tune call, smaller batches, two lanes and own_side extractions
-  // keep the fork beside FAST and buffer 0.
-  const bool beside_ok = ctx->blur_overlap && im.n >= 32 && ctx->blur_stream;
-  const bool blur_early = pipe && beside_ok && ctx->tuning.blur_early && ctx->blur_alt && ctx->fast_force < 0 && !own_side;
-  const VsfBlurKind blur_kind = blur_early                                      ? VSF_BLUR_EARLY
-                                : st == ctx->stream                             ? VSF_BLUR_MAIN
-                                : ctx->lanes == 2 && st == ctx->aux_stream.get() ? VSF_BLUR_LANE
-                                                                                : VSF_BLUR_OWN;
-  const VsfBlurPlan bp = vsf_blur_plan(&ctx->blur_plan, blur_kind, (bool)ctx->blur_alt);
-  if (bp.buf) d.blur = ctx->blur_alt.get() + (size_t)i0 * g.pyr_bytes;
-  if (blur_kind != VSF_BLUR_LANE) ctx->last_blur = bp.buf ? ctx->blur_alt.get() : ctx->dorb.d.blur;
-  auto launch_blur = [&](hipStream_t bs) {
-    // ... not before the descriptors that last read this buffer are through, where stream order does not say so already
-    if (bp.wait_free) vsf_note(hipStreamWaitEvent(bs, ctx->ev_blur_free[bp.buf], 0));
-    StageTimer t(ctx, bs, VSF_STAGE_BLUR, 1);
-    if (im.n >= 32)
-      vsf_launch_blur_mma(d, g, im, ctx->dorb.blur_mma_units, (int)ctx->orb.blur_mma_units.size(), ctx->dorb.blur_tcol,
-                          ctx->dorb.blur_tv, ctx->orb.blur_bias, bs);
-    else
-      vsf_launch_blur_mma(d, g, im, ctx->dorb.blur_mma_units_small, (int)ctx->orb.blur_mma_units_small.size(),
-                          ctx->dorb.blur_tcol, ctx->dorb.blur_tv, ctx->orb.blur_bias, bs);
-  };
-  if (pipe) {
-    // The pyramid depends on the input images only.  The caller promised they are complete (vsf_set_pipeline), so the
-    // chain goes onto the pipe streams WITHOUT being ordered after this stream's earlier work and overlaps the previous
-    // call's later stages; it writes the pyramid buffer the previous call does not use, once the call before that has
-    // released it.
-    const int buf = ctx->pyr_flip;
-    d.pyr = buf ? ctx->pyr_alt : ctx->dorb.d.pyr;
-    // (ROCm multiplexes streams onto a few hardware queues; the context's aux stream is known to run beside the
-    // main one, so the chain goes there, as a single chain)
-    hipStream_t ps = ctx->pipe_stream ? ctx->pipe_stream : ctx->aux_stream;
-    if (ctx->pyr_free_valid[buf]) vsf_note(hipStreamWaitEvent(ps, ctx->ev_pyr_free[buf], 0));
-    // ... and not before the previous call's FAST kernel has finished: FAST fills every register of the chip, the
-    // stages after it (selection, descriptors, matcher) are latency-bound and leave room for the resize chain
-    if (ctx->fast_done_valid && ctx->tuning.pipe_after_fast) vsf_note(hipStreamWaitEvent(ps, ctx->ev_fast_done, 0));
-    // ... and not before images this library itself is still producing on the context's stream are complete
-    if (ctx->ingest_done_valid) vsf_note(hipStreamWaitEvent(ps, ctx->ev_ingest_done, 0));
-    // ... nor before the caller's own producer has finished them (vsf_set_input_event)
-    if (ctx->input_event) vsf_note(hipStreamWaitEvent(ps, ctx->input_event, 0));
-    struct Early {
-      vsf_ctx* ctx;
-      const VsfDev* d;
-      const VsfImages* im;
-      int n_early;
-      bool fired;
-    } early{ctx, &d, &im, n_early, false};
-    // behind the launch of level early_levels - 1 (ps has waited for the inputs by then: level 0 needs no more than that)
-    const VsfPyramidHook hook{early_levels - 1,
-                              [](void* arg, hipStream_t chain) {
-                                Early& e = *static_cast<Early*>(arg);
-                                vsf_ctx* c = e.ctx;
-                                hipStream_t es = c->blur_stream;
-                                e.fired = true;
-                                vsf_note(hipEventRecord(c->ev_early_go, chain));
-                                vsf_note(hipStreamWaitEvent(es, c->ev_early_go, 0));
-                                // ... and not before the selection that last read this pair of buffers is through
-                                if (c->cand_free_valid[c->cand_flip])
-                                  vsf_note(hipStreamWaitEvent(es, c->ev_cand_free[c->cand_flip], 0));
-                                {
-                                  // (0 launches: the step's launch count stays what the one-pass FAST reports)
-                                  StageTimer t(c, es, VSF_STAGE_FAST, 0);
-                                  vsf_launch_fast(*e.d, c->orb.g, *e.im, c->p.fast_threshold, 1, es, c->tuning.fast_early_form,
-                                                  c->n_cus, c->fast_cells, VSF_FAST_EARLY, e.n_early);
-                                }
-                                vsf_note(hipEventRecord(c->ev_early_done, es));
-                              },
-                              &early};
-    {
-      StageTimer t(ctx, ps, VSF_STAGE_PYRAMID, g.nlevels - 1);
-      vsf_launch_pyramid(d, g, ctx->orb.levels.data(), im, ps, nullptr, n_early > 0 ? &hook : nullptr);
-    }
-    if (n_early > 0 && !early.fired) hook.fn(&early, ps);  // (no launch of the chain made that level: behind all of it)
-    vsf_note(hipEventRecord(ctx->ev_pyr_done, ps));
-    vsf_note(hipStreamWaitEvent(st, ctx->ev_pyr_done, 0));
-    // VSF_BLUR_EARLY: the blur follows the chain in stream order instead of being forked from the main stream together with
-    // FAST.  The chain fills the whole of the previous call's selection -> descriptors -> matcher (48 launches, 3.35 ms beside
-    // them against 1.28 ms alone), so the blur starts where those end: 0.1 ms before the matcher is through and 0.2 ms before the
-    // main stream reaches the late FAST part, and it is through when FAST is (5.61-5.73 -> 5.56-5.61 ms per 256-frame step;
-    // NOTES.md "Blur: behind the pipelined pyramid chain").  Not on blur_stream: the early FAST launch lives there and the
-    // blur would wait behind it.  The next call's chain on this stream waits for this call's FAST anyway (traced: the blur
-    // ends with FAST or just before it), so the blur in front of it delays nothing.
-    if (blur_early) {
-      launch_blur(ps);
-      vsf_note(hipEventRecord(ctx->ev_blur_done, ps));
-    }
-  } else {
-    StageTimer t(ctx, st, VSF_STAGE_PYRAMID, g.nlevels - 1);
-    // one lane: the aux stream is idle, the pyramid chain of the second half of the batch runs on it
-    // (own_side: a caller that runs several extractions at once on different streams brings a side-stream set of its own --
-    // the context's fork / join events must not be recorded from two streams at a time)
-    vsf_launch_pyramid(d, g, ctx->orb.levels.data(), im, st, own_side ? own_side : (ctx->lanes == 1 ? &ctx->side : nullptr));
-  }
-  ctx->last_pyr = d.pyr - (size_t)i0 * g.pyr_bytes;
-  // The blur needs the pyramid only.  It lives on the matrix cores and on memory bandwidth, FAST on the vector ALU (at its
-  // issue ceiling: profiles/r04/valu_ceiling.json) and the selection on latency: forked behind the pyramid onto its own
-  // stream, the blur's workgroups fill in as FAST drains and run beside the selection (7.61 -> 7.25 ms per 256-frame step).
-  // Measured and left out: forking behind FAST instead (7.52: the overlap with FAST's tail is lost); making room beside
-  // FAST with an LDS reservation that caps FAST at four workgroups per CU (7.46: the reservation is LDS the blur needs; the
-  // resident kernel below caps FAST without it); a high- or low-priority blur stream (7.39 / 7.65); slices of the blur
-  // forked from INSIDE the pyramid's launch chain as soon as their levels exist (the chain's dependent launches stretch from
-  // 1.28 to 1.8-2.2 ms beside the blur's memory traffic, 7.37-7.46 ms per step against 7.31); the first 3 / 6 / 10 / 16
-  // levels blurred in line in front of FAST and only the rest beside it (7.25-7.36: noise).
-  // Measured and KEPT (NOTES.md, "FAST: the wide levels start beside the previous call"): FAST on the full cells of the
-  // first 12 levels as a grid launch from inside the next call's pyramid chain (5.81-5.94 -> 5.63-5.73 ms per 256-frame
-  // step).  Left out: fewer levels (1 / 2 / 4 / 8: 5.81 / 5.84 / 5.73 / 5.66 ms) or all 20 (5.67); that early part as a
-  // resident launch of one, two or three waves per SIMD (5.72-5.95: it does not finish before the pyramid does, and the
-  // late part waits for it).
-  // Measured and KEPT (NOTES.md, "Blur: behind the pipelined pyramid chain"): the blur of a pipelined call queued behind its
-  // chain on the pipe stream, into the other blurred pyramid (VSF_OPT_BLUR_EARLY, above: 5.61-5.73 -> 5.56-5.61 ms).  What
-  // was hoped for -- the blur beside the previous call's descriptors and matcher, FAST alone in its phase -- did not
-  // happen: the chain ends when that phase does, and that phase is full (everything in it runs at half its own rate).
-  // With that blur: 0 / 4 / 8 / 20 early levels 5.76-5.90 / 5.66-5.68 / 5.57-5.65 / 5.61-5.63 ms against 5.52-5.56 at
-  // 12; the late part resident with three waves 5.69-5.71, the tune call picks the grid.
-  // With the blur beside it FAST can run as ONE resident workgroup per CU (k_fast.hip): three waves per SIMD keep 92 % of
-  // its own rate and leave the other 224 of a SIMD's 512 registers -- which a grid of one workgroup per four cells fills
-  // for as long as cells are left -- to the blur, which then finishes INSIDE the FAST pass instead of after it.  Whether
-  // that pays depends on the batch and on how well the blur hides behind the selection anyway (frames per second, grid ->
-  // resident; 640x480 / 2000 features: 512 frames per step 35.4 -> 37.5 k, 256 frames 35.0 -> 36.4 k, 128 frames equal,
-  // 64 frames 31.3 -> 29.8 k, 32 frames 25.7 -> 24.3 k; 1920x1080 / 8000: 32 frames 4 900 -> 4 700, 96 frames
-  // 5 000 -> 5 140, 192 frames 5 030 -> 5 320; four waves per SIMD at 256 VGA frames 7.09-7.12 ms against 7.03, two 8.0).
-  // No rule on batch size got all of these right, so the caller may have it MEASURED: vsf_tune_fast_resident (explicit,
-  // blocking) times both forms on the caller's own batch and this call takes what it found for this batch size -- the grid
-  // form for a size nobody measured.  vsf_set_fast_resident overrides.  Nothing is measured, and nothing waits, in here.
-  int resident = 0;
-  if (beside_ok && ctx->lanes == 1 && st == ctx->stream && i0 == 0 && !own_side) {
-    if (ctx->fast_force >= 0)
-      resident = ctx->fast_force;
-    else if (ctx->fast_resident >= 0)
-      resident = ctx->fast_resident;
-    else if (ctx->fast_tune.n == im.n && ctx->fast_tune.choice > 0)
-      resident = ctx->fast_tune.choice;
-  }
-  const bool blur_beside = beside_ok;
-  auto fork_blur = [&]() {
-    vsf_note(hipEventRecord(ctx->ev_blur_fork, st));
-    vsf_note(hipStreamWaitEvent(ctx->blur_stream, ctx->ev_blur_fork, 0));
-    launch_blur(ctx->blur_stream);
-    vsf_note(hipEventRecord(ctx->ev_blur_done, ctx->blur_stream));
-  };
-  if (blur_beside && !blur_early) fork_blur();  // (on blur_stream behind the early FAST part: stream order)
-  if (n_early > 0) vsf_note(hipStreamWaitEvent(st, ctx->ev_early_done, 0));
-  {
-    StageTimer t(ctx, st, VSF_STAGE_FAST, 1);
-    vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, st, blur_beside ? resident : 0, ctx->n_cus, ctx->fast_cells,
-                    n_early > 0 ? VSF_FAST_LATE : VSF_FAST_ALL, n_early);
-  }
-  if (pipe) {
-    vsf_note(hipEventRecord(ctx->ev_fast_done, st));
-    ctx->fast_done_valid = true;
-  }
-  {
-    StageTimer t(ctx, st, VSF_STAGE_SELECT, 1);
-    vsf_launch_select(d, g, ctx->orb.levels.data(), im, st);
-  }
-  if (pipe && ctx->cand_alt) {  // the last reader of this pair of candidate buffers is queued
-    vsf_note(hipEventRecord(ctx->ev_cand_free[ctx->cand_flip], st));
-    ctx->cand_free_valid[ctx->cand_flip] = true;
-  }
-  if (blur_beside)
-    vsf_note(hipStreamWaitEvent(st, ctx->ev_blur_done, 0));
-  else
-    launch_blur(st);
-  {
-    StageTimer t(ctx, st, VSF_STAGE_DESCRIBE, 1);
-    vsf_launch_describe(d, g, im, ctx->p.max_keypoints, d_kp + i0 * K, d_desc + i0 * K * VSF_DESC_BYTES, d_counts + i0,
-                        st);
-  }
-  if (bp.record_free) vsf_note(hipEventRecord(ctx->ev_blur_free[bp.buf], st));  // the only reader of this blurred pyramid is queued
-  if (pipe) {  // every reader of this pyramid buffer is queued: the call after the next may overwrite it
-    const int buf = ctx->pyr_flip;
-    vsf_note(hipEventRecord(ctx->ev_pyr_free[buf], st));
-    ctx->pyr_free_valid[buf] = true;
-    ctx->pyr_flip ^= 1;
-  }
+  // one lane: the aux stream is idle, the pyramid chain of the second half of the batch runs on it (own_side: a caller that
+  // runs several extractions at once on different streams brings a side-stream set of its own -- the context's fork / join
+  // events must not be recorded from two streams at a time)
+  const VsfSideStream* side = own_side ? own_side : (ctx->lanes == 1 ? &ctx->side : nullptr);
+  ExtractHip hip{ctx,
+                 p,
+                 {st, ctx->pipe_stream ? ctx->pipe_stream.get() : ctx->aux_stream.get(), ctx->blur_stream.get()},
+                 d,
+                 im,
+                 side,
+                 d_kp + i0 * K,
+                 d_desc + i0 * K * VSF_DESC_BYTES,
+                 d_counts + i0};
+  vsf_extract_issue(p, hip);
 }
 
 // knnMatch(k = 2) + ratio test for pairs [p0, p0 + n) on stream `st`.
@@ -462,7 +393,7 @@ vsf_status ensure_pipeline_buffers(vsf_ctx* ctx) {
   VSF_HIP(ctx->ev_pyr_done.alloc(hipEventDisableTiming));
   VSF_HIP(ctx->ev_fast_done.alloc(hipEventDisableTiming));
   for (Event& e : ctx->ev_pyr_free) VSF_HIP(e.alloc(hipEventDisableTiming));
-  // the other blurred pyramid and the releases of both (VSF_OPT_BLUR_EARLY, vsf_blur_plan.h); the buffer last: a context
+  // the other blurred pyramid and the releases of both (VSF_OPT_BLUR_EARLY, vsf_extract_plan.h); the buffer last: a context
   // that has blur_alt has the events
   for (Event& e : ctx->ev_blur_free) VSF_HIP(e.alloc(hipEventDisableTiming));
   VSF_HIP(ctx->blur_alt.alloc((size_t)ctx->p.max_images * ctx->orb.g.pyr_bytes));
@@ -784,10 +715,7 @@ vsf_status vsf_set_pipeline(vsf_ctx* ctx, int on) {
     if (st != VSF_OK) return st;
   }
   ctx->pipeline = on != 0;
-  ctx->pyr_free_valid[0] = ctx->pyr_free_valid[1] = false;
-  ctx->cand_free_valid[0] = ctx->cand_free_valid[1] = false;
-  // (blur_plan keeps its releases: a reader of buffer 0 may sit on a stream that was not waited for here)
-  ctx->fast_done_valid = false;
+  ctx->extract_state.reset_pipeline();
   return VSF_OK;
 }
 

@@ -10,7 +10,7 @@
 #include <memory>
 #include <vector>
 
-#include "vsf_blur_plan.h"
+#include "vsf_extract_plan.h"
 #include "vsf_internal.h"
 #include "vsf_observe_plan.h"
 #include "vsf_observe_queue.h"
@@ -81,23 +81,20 @@ struct vsf_ctx {
   bool pipeline = false;
   vsfi::Stream pipe_stream;  // the pipelined chain's own stream when VSF_OPT_PIPE_PRIORITY asks for a priority
   int pipe_stream_priority = 0;
-  int pyr_flip = 0;
   vsfi::Event ev_pyr_done, ev_pyr_free[2], ev_fast_done;
-  bool pyr_free_valid[2] = {false, false}, fast_done_valid = false;
   // ... and FAST on the full cells of its first levels (VSF_OPT_FAST_EARLY_LEVELS) starts from inside that chain, on
   // blur_stream: it writes the candidate buffers while call k's selection still reads its own, so a call with an early
-  // part takes the other of two pairs (cand_flip: the pair dorb.d.cand / .rowstart point at -- what the LAST call used, and
-  // what every other path and the debug hooks use).  ev_cand_free[i]: behind the pipelined selection that last read pair i.
-  int cand_flip = 0;
+  // part takes the other of two pairs (dorb.d.cand / .rowstart point at the pair the LAST call used -- what every other path
+  // and the debug hooks use).  ev_cand_free[i]: behind the pipelined selection that last read pair i.
   vsfi::Event ev_cand_free[2], ev_early_go, ev_early_done;
-  bool cand_free_valid[2] = {false, false};
   // ... and its blur (VSF_OPT_BLUR_EARLY) follows that chain on the same stream, not ordered behind call k's descriptors: it
-  // writes the other of two blurred pyramids (dorb.blur / blur_alt) while call k's descriptors may still read theirs.  Which
-  // buffer, and which release a call waits for and records: vsf_blur_plan.h from `blur_plan` (.flip is blur_flip: the buffer
-  // the LAST call's blur wrote; .free_valid is blur_free_valid).  ev_blur_free[i]: behind the descriptors that last read
-  // buffer i, the only reader.  last_blur: that buffer, for the debug hooks.
-  VsfBlurState blur_plan;
+  // writes the other of two blurred pyramids (dorb.blur / blur_alt) while call k's descriptors may still read theirs.
+  // ev_blur_free[i]: behind the descriptors that last read buffer i, the only reader.  last_blur: the buffer the last call's
+  // blur wrote, for the debug hooks.
   vsfi::Event ev_blur_free[2];
+  // Which buffer of each pair a call takes, which of these events it waits for and records, and which have been recorded:
+  // the books of vsf_extract_plan.h, which states the whole schedule (extract_on issues it).
+  VsfExtractState extract_state;
   const uint8_t* last_blur = nullptr;
   // A producer the library owns (the Bayer ingest) records this on the context's stream; a pipelined pyramid, which is
   // NOT ordered after that stream's earlier work, waits for it.
@@ -295,7 +292,7 @@ struct vsf_ctx {
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----
   vsfi::DevBuf<uint8_t> pyr_alt;  // the other pyramid buffer of cross-call pipelining
-  vsfi::DevBuf<uint8_t> blur_alt;  // ... and the other blurred pyramid (buffer 1 of vsf_blur_plan.h; buffer 0 is dorb.blur)
+  vsfi::DevBuf<uint8_t> blur_alt;  // ... and the other blurred pyramid (buffer 1 of vsf_extract_plan.h; buffer 0 is dorb.blur)
   vsfi::DevBuf<uint32_t> cand_alt;      // ... and the other pair of FAST's candidate segments and row-start tables
   vsfi::DevBuf<uint16_t> rowstart_alt;  //     (pair 0 is dorb.cand / dorb.rowstart)
   vsfi::Geometry orb, fast;
