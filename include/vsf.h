@@ -853,6 +853,15 @@ vsf_status vsf_draw_canvases(vsf_ctx* ctx, const vsf_draw_canvas* canvases, int 
  * custom tables.  Arithmetic-coded, 12-bit and lossless files and progressive files whose scans stop short of full
  * precision (libjpeg shows an approximation of those) return VSF_ERR_UNSUPPORTED, files of another size or with malformed headers
  * VSF_ERR_INVALID_ARG (nothing is launched then).
+ * Sampling factors: every component's horizontal and vertical factor may be 1 .. 4, the chroma components' need not be equal,
+ * and a one-component file has one block per MCU whatever its factors say (T.81 A.2.2).  As libjpeg does, an interleaved scan
+ * -- the one scan of a baseline file, or any scan of several components in a multi-scan or progressive file -- may hold at
+ * most 10 blocks per MCU (D_MAX_BLOCKS_IN_MCU): more is VSF_ERR_INVALID_ARG, as libjpeg refuses such a file.  A file whose
+ * scans never interleave its components may carry up to 4 x 4 luminance blocks per MCU.  One deviation from libjpeg: the
+ * luminance component must carry the largest horizontal AND vertical factor of the frame; a file in which a chroma component
+ * is sampled more finely (Y 1 x 1 beside Cb 2 x 2, Y 2 x 1 beside Cb 1 x 2), whose luminance libjpeg would upsample, is
+ * VSF_ERR_UNSUPPORTED -- refused, never decoded differently.  Accepted files are bit for bit libjpeg's at every layout
+ * (tests/test_gpu_jpeg_sampling.py).
  * The images land at d_dst + i * dst_image_stride (DEVICE memory, rows dst_row_stride apart; base and strides multiples
  * of 4) -- the input of vsf_bayer_bg_to_gray_batch_dev or of the extraction.  The files are copied before the call
  * returns; the decode is asynchronous on the context's stream (one wave per image: run it on a context / stream of its

@@ -424,3 +424,109 @@ def multiscan_sequential_cases():
     c422 = [comp(2, 1, 6, 10), comp(1, 1, 6, 5), comp(1, 1, 6, 5)]
     out.append(("cr_then_y_with_cb_422", write_multiscan_sequential_jpeg(77, 45, c422, [(2,), (0, 1)], restart_interval=2), 77, 45))
     return out
+
+
+# ---- every sampling layout the host parser accepts (csrc/vsf_jpeg_host.cc parse_jpeg), and the ones it refuses -------------
+# Factor sets are ((h, v) of Y, of Cb, of Cr).  An interleaved scan may hold at most 10 blocks per MCU (libjpeg's
+# D_MAX_BLOCKS_IN_MCU); a frame whose scans never interleave may go up to 4 x 4 luminance blocks.
+_C11 = ((1, 1), (1, 1))
+SAMPLING_INTERLEAVED = [((1, 2),) + _C11, ((4, 1),) + _C11, ((3, 1),) + _C11, ((1, 3),) + _C11, ((1, 4),) + _C11,
+                        ((4, 2),) + _C11, ((2, 4),) + _C11, ((3, 2),) + _C11, ((2, 3),) + _C11,
+                        ((2, 2), (2, 1), (1, 1)), ((2, 2), (1, 2), (2, 1)), ((3, 2), (2, 1), (1, 2)), ((2, 2), (1, 1), (2, 2))]
+SAMPLING_SEPARATE_ONLY = [((3, 3),) + _C11, ((4, 3),) + _C11, ((3, 4),) + _C11, ((4, 4),) + _C11, ((4, 4), (2, 2), (1, 1))]
+SAMPLING_GRAY = [((2, 2),), ((3, 1),)]          # one component: one block per MCU whatever the factors say
+SAMPLING_TOO_MANY_BLOCKS = [((2, 2), (2, 2), (2, 2)), ((4, 2), (2, 1), (1, 1)), ((3, 3),) + _C11]   # interleaved: libjpeg refuses
+SAMPLING_LUMA_BELOW_MAX = [((1, 1), (2, 2), (1, 1)), ((2, 1), (1, 2), (1, 1))]                      # libjpeg upsamples the luminance
+SAMPLING_LONG = [((3, 1),) + _C11, ((4, 2),) + _C11, ((3, 2), (2, 1), (1, 2))]   # 640 x 480: >= 16 blocks per segment of the parallel decoder
+SAMPLING_CONTROL = ((2, 2),) + _C11                                              # ... beside an ordinary 4:2:0 file
+
+
+def sampling_name(factors):
+    return "_".join("%dx%d" % hv for hv in factors)
+
+
+def _sampling_scripts(ncomp):
+    """{process: ('seq', scans, restart interval) | ('prog', script)} for a frame of `ncomp` components."""
+    if ncomp == 1:
+        return {"base": ("seq", [(0,)], 0), "base_rst": ("seq", [(0,)], 3),
+                "prog_sep": ("prog", [((0,), 0, 0, 0, 1), ((0,), 1, 63, 0, 0), ((0,), 0, 0, 1, 0)])}
+    every = (0, 1, 2)
+    chroma_ac = [((1,), 1, 63, 0, 0), ((2,), 1, 63, 0, 0)]
+    return {
+        "base": ("seq", [every], 0),
+        "base_rst": ("seq", [every], 3),
+        "multi_sep": ("seq", [(1,), (0,), (2,)], 3),
+        "multi_y_cb": ("seq", [(0, 1), (2,)], 0),
+        # interleaved DC, the luminance band cut in two and refined twice, the DC refinement interleaved as well
+        "prog_il": ("prog", [(every, 0, 0, 0, 1), ((0,), 1, 5, 0, 2), ((0,), 6, 63, 0, 2), ((0,), 1, 63, 2, 1)] + chroma_ac +
+                    [(every, 0, 0, 1, 0), ((0,), 1, 63, 1, 0)]),
+        # no scan interleaves anything: the luminance walks ceil(W / 8) x ceil(H / 8) blocks in every one
+        "prog_sep": ("prog", [((0,), 0, 0, 0, 1), ((1,), 0, 0, 0, 0), ((2,), 0, 0, 0, 0), ((0,), 1, 63, 0, 0), ((0,), 0, 0, 1, 0)] +
+                     chroma_ac),
+        # the luminance DC first in a scan of its own (block rows), its refinement interleaved (MCU rows)
+        "prog_mix": ("prog", [((0,), 0, 0, 0, 1), ((1,), 0, 0, 0, 1), ((2,), 0, 0, 0, 1), ((0,), 1, 63, 0, 0), (every, 0, 0, 1, 0)] +
+                     chroma_ac),
+    }
+
+
+def write_sampling_file(rng, w, h, factors, process):
+    """One file of `factors` at w x h from fresh random coefficients; small quantiser steps as everywhere in this module."""
+    hmax, vmax = max(f[0] for f in factors), max(f[1] for f in factors)
+    mx, my = -(-w // (8 * hmax)), -(-h // (8 * vmax))
+    comps = [(fh, fv, rng.integers(1, 5, 64), random_coefficients(rng, my * fv, mx * fh)) for fh, fv in factors]
+    kind = _sampling_scripts(len(factors))[process]
+    if kind[0] == "seq":
+        return write_multiscan_sequential_jpeg(w, h, comps, kind[1], restart_interval=kind[2])
+    return write_progressive_jpeg(w, h, comps, kind[1])
+
+
+def sampling_processes(factors, w, h):
+    """The processes a factor set is written in at a size (75 x 61: all it can have; 96 x 96: every MCU size divides it;
+    25 x 9 and 1 x 1: one MCU, most of it outside the image)."""
+    blocks = [fh * fv for fh, fv in factors]
+    if len(factors) == 1:
+        return ["base", "base_rst", "prog_sep"] if (w, h) == (75, 61) else ["base", "prog_sep"]
+    if sum(blocks) > 10:            # legal only when no scan interleaves the components
+        return ["multi_sep", "prog_sep"] if (w, h) == (75, 61) else ["prog_sep"]
+    if (w, h) == (75, 61):
+        return ["base", "base_rst", "multi_sep"] + (["multi_y_cb"] if blocks[0] + blocks[1] <= 10 else []) + \
+               ["prog_il", "prog_sep", "prog_mix"]
+    return ["base", "prog_il"] if (w, h) == (96, 96) else ["base", "prog_sep"]
+
+
+_sampling_cache = {}
+
+
+def sampling_cases():
+    """-> [(name, bytes, w, h, factors, process)]: every accepted factor set in every process it can have, at 75 x 61 (partial
+    last blocks; with h = 4 two blocks of the last MCU lie wholly right of the image, with v = 3 a block row wholly below),
+    96 x 96, 25 x 9 and 1 x 1, and three 640 x 480 one-scan files beside a 4:2:0 control.  Written once per process."""
+    if "cases" not in _sampling_cache:
+        rng = np.random.default_rng(9)
+        out = []
+        for factors in SAMPLING_INTERLEAVED + SAMPLING_SEPARATE_ONLY + SAMPLING_GRAY:
+            for w, h in ((75, 61), (96, 96), (25, 9), (1, 1)):
+                for process in sampling_processes(factors, w, h):
+                    out.append(("%s_%dx%d_%s" % (sampling_name(factors), w, h, process),
+                                write_sampling_file(rng, w, h, factors, process), w, h, factors, process))
+        for factors in SAMPLING_LONG + [SAMPLING_CONTROL]:
+            out.append(("%s_640x480_base" % sampling_name(factors), write_sampling_file(rng, 640, 480, factors, "base"), 640, 480,
+                        factors, "base"))
+        _sampling_cache["cases"] = out
+    return _sampling_cache["cases"]
+
+
+def sampling_refusals():
+    """-> [(name, bytes, w, h, factors, process, answer)], 75 x 61: answer "invalid_arg" for an interleaved scan of more than
+    10 blocks (libjpeg: JERR_BAD_MCU_SIZE), "unsupported" for a luminance component below the largest factors (libjpeg
+    decodes such a file: it upsamples the luminance, which this library does not do)."""
+    if "refusals" not in _sampling_cache:
+        rng = np.random.default_rng(90)
+        out = []
+        for answer, sets in (("invalid_arg", SAMPLING_TOO_MANY_BLOCKS), ("unsupported", SAMPLING_LUMA_BELOW_MAX)):
+            for factors in sets:
+                for process in ("base", "prog_il"):
+                    out.append(("%s_75x61_%s" % (sampling_name(factors), process), write_sampling_file(rng, 75, 61, factors, process),
+                                75, 61, factors, process, answer))
+        _sampling_cache["refusals"] = out
+    return _sampling_cache["refusals"]
