@@ -903,6 +903,44 @@ vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, co
                                    int width, int height, uint8_t* d_dst, size_t dst_image_stride,
                                    size_t dst_row_stride);
 
+/* cv::imdecode(data, cv::IMREAD_COLOR) of OpenCV 3.2 -- the other way the reference reads a CompressedImage (bag_extract.cc:73)
+ * -- for n JPEG / PNG files in HOST memory: the contract of vsf_imdecode_gray_batch (format told by the first bytes, runs of
+ * one format, one upload per run, asynchronous on the context's stream, data errors at the next vsf_sync, nothing decoded so far
+ * is undone when a later run is refused), three bytes a pixel.
+ * Destination: DEVICE memory, image i at d_dst + i * dst_image_stride; a row is 3 * width bytes, blue, green, red per pixel --
+ * the layout vsf_jpeg_encode_batch_dev(channels = 3), vsf_png_encode_batch_dev and vsf_to_gray_batch_dev(VSF_PIX_BGR8) read.  d_dst,
+ * dst_image_stride and dst_row_stride are multiples of 4, dst_row_stride >= (3 * width + 3) & ~3 and dst_image_stride >=
+ * height * dst_row_stride, else VSF_ERR_INVALID_ARG.  Exactly the 3 * width bytes of each of the height rows are written: not
+ * the rest of a row's last dword, no padding, no row below.
+ * JPEG (vsf_jpeg_decode_bgr_batch): what grfmt_jpeg.cpp makes libjpeg do -- out_color_space = JCS_RGB, three output components,
+ * the library's defaults otherwise (fancy upsampling, hence no merged upsampling), red and blue swapped afterwards.  Every
+ * component takes the ISLOW inverse DCT at full size into a plane of its own; one kernel then upsamples the chroma planes as
+ * libjpeg-turbo's jdsample.c does for the component's ratio (1 x 1 as it is; 2 x 1 and 2 x 2 by the triangle filters when the
+ * component's row has more than two samples, by replication otherwise; 1 x 2 by its two-row filter; any other integral ratio by
+ * replication; the rows next to the first and last row of the component are those rows again), applies jdcolor.c's 16-bit
+ * fixed-point YCbCr -> RGB with range limiting and stores B, G, R.  A one-component file gives B = G = R = Y, in every process
+ * the gray call reads.  Bit for bit the library's bytes (tests/jpeg_ref_bgr.py).
+ * A three-component file is decoded when libjpeg reads it as YCbCr (jdapimin.c: a JFIF marker; else the Adobe marker's transform
+ * flag; else the component ids), in every process the gray call reads: one interleaved scan (SOF0 / SOF1, with or without
+ * restart intervals), several sequential scans, progressive (SOF2; every coefficient of EVERY component must reach full
+ * precision).  VSF_ERR_UNSUPPORTED, never a guess: a file libjpeg reads as RGB (Adobe transform 0; ids 'R' 'G' 'B' without a
+ * JFIF marker), four components, a luminance component below the frame's largest factors, and what the gray call answers so
+ * (arithmetic-coded, 12-bit, lossless, progressive scans that stop short of full precision).  VSF_ERR_INVALID_ARG: a layout libjpeg refuses for a colour
+ * read although it takes it for a gray one -- a chroma factor that does not divide the luminance's (JERR_FRACT_SAMPLE_NOTIMPL) --
+ * and what the gray call answers so (more than 10 blocks in an interleaved MCU, another size, malformed headers).
+ * PNG (vsf_png_decode_bgr_batch): grfmt_png.cpp's settings for an 8-bit three-channel destination -- strip_16, strip_alpha (a
+ * palette's tRNS included), palette_to_rgb, expand_gray_1_2_4_to_8, set_bgr for files with the colour bit and gray_to_rgb for
+ * the others.  Inflate, row filters, Adam7 and every refusal of the chunks and of the stream are those of
+ * vsf_png_decode_gray_batch; no gamma transform is asked of libpng on this path, so gAMA / sRGB / iCCP / cHRM change nothing and
+ * the files the gray call refuses for them are read.  Bit for bit libpng's bytes (tests/png_ref_bgr.py).
+ * No reduced sizes, no resize, no CMYK. */
+vsf_status vsf_imdecode_bgr_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images, int width,
+                                  int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride);
+vsf_status vsf_jpeg_decode_bgr_batch(vsf_ctx* ctx, const uint8_t* const* jpeg, const size_t* nbytes, int n_images, int width,
+                                     int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride);
+vsf_status vsf_png_decode_bgr_batch(vsf_ctx* ctx, const uint8_t* const* png, const size_t* nbytes, int n_images, int width,
+                                    int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride);
+
 /* The siblings of that flag: cv::imdecode(data, cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8) for reduce = 2, 4, 8.  For a JPEG
  * file OpenCV sets libjpeg's scale_num / scale_denom = 1 / reduce, and libjpeg decodes with its reduced inverse DCTs
  * (jidctred.c: 4 x 4, 2 x 2 or 1 x 1 pixels per block of coefficients) -- no resize runs -- to

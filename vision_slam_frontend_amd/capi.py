@@ -50,6 +50,7 @@ EXPORTS = [
     "vsf_observe_submit_dev", "vsf_observe_device_ring_bytes",
     "vsf_world_points_batch_dev", "vsf_world_points", "vsf_observe_set_world_points", "vsf_observe_set_pose",
     "vsf_observe_world_points_view",
+    "vsf_imdecode_bgr_batch", "vsf_jpeg_decode_bgr_batch", "vsf_png_decode_bgr_batch",
     "vsf_imdecode_reduced_gray_batch", "vsf_reduced_size", "vsf_observe_probe_compressed_reduced",
     "vsf_observe_submit_compressed_reduced", "vsf_observe_stereo_compressed_reduced",
     "vsf_observe_set_debug_seeds", "vsf_observe_set_stream_cam_to_robot",
@@ -374,6 +375,8 @@ def lib() -> C.CDLL:
         L.vsf_jpeg_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_png_decode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_imdecode_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
+        for f in (L.vsf_imdecode_bgr_batch, L.vsf_jpeg_decode_bgr_batch, L.vsf_png_decode_bgr_batch):
+            f.argtypes = [vp, vp, vp, i32, i32, i32, vp, sz, sz]
         L.vsf_imdecode_reduced_gray_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, sz, sz]
         L.vsf_reduced_size.argtypes = [i32, i32, i32, ip, ip]
         L.vsf_observe_probe_compressed_reduced.argtypes = [vp, sz, i32, i32, i32, sz, i32, ip]
@@ -1000,6 +1003,22 @@ class Context:
                                            _p(d_dst), dst_image_stride, dst_row_stride)
         if st != VSF_OK and st not in allow_status:
             raise VsfError(st, "vsf_imdecode_gray_batch", lib().vsf_last_hip_error(self._h))
+        return st
+
+    def imdecode_bgr_batch(self, files, width: int, height: int, d_dst: int, dst_image_stride: int, dst_row_stride: int,
+                           allow_status=(), only: str = ""):
+        """cv::imdecode(IMREAD_COLOR) of JPEG and PNG payloads, mixed (vsf_imdecode_bgr_batch): image i at
+        d_dst + i * dst_image_stride, rows of 3 * width bytes (blue, green, red) dst_row_stride apart.  only = "jpeg" / "png":
+        the call of that one format (vsf_jpeg_decode_bgr_batch / vsf_png_decode_bgr_batch)."""
+        name = {"": "vsf_imdecode_bgr_batch", "jpeg": "vsf_jpeg_decode_bgr_batch", "png": "vsf_png_decode_bgr_batch"}[only]
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        sizes = (C.c_size_t * n)(*[len(b) for b in bufs])
+        st = getattr(lib(), name)(self._h, C.cast(ptrs, C.c_void_p), C.cast(sizes, C.c_void_p), n, width, height,
+                                  _p(d_dst), dst_image_stride, dst_row_stride)
+        if st != VSF_OK and st not in allow_status:
+            raise VsfError(st, name, lib().vsf_last_hip_error(self._h))
         return st
 
     def imdecode_reduced_gray_batch(self, files, reduce: int, width: int, height: int, d_dst: int, dst_image_stride: int,

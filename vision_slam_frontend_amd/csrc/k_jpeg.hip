@@ -35,6 +35,14 @@
 // shared with a CPU test program) in both places it lives: jpeg_gray_kernel<D> and jpeg_idct_reduced_kernel<D>.  The image is
 // ceil(W / D) x ceil(H / D), a block gives 8 / D x 8 / D pixels at its origin / D, the last block of a row or column is
 // cropped.  Checked bit for bit against the system's libjpeg at those scales (tests/test_gpu_jpeg_reduced.py).
+//
+// COLOUR (cv::IMREAD_COLOR, vsf_imdecode_bgr_batch: out_color_space = JCS_RGB).  Each decoder has a colour form, a kernel of its
+// own beside the gray one: jpeg_par_colour_kernel (one-scan files: DC sums per component, every block kept), jpeg_colour_kernel
+// (the one-wave decoder) and jpeg_prog_colour_kernel (several scans, scan after scan).  The chroma blocks take the luminance's
+// IDCT, each component into a plane of the run's scratch (jpeg_idct_chroma_kernel, or the one-wave kernel itself); the
+// luminance plane stands where a gray read has its image; jpeg_finish_bgr_kernel then upsamples the chroma as jdsample.c does,
+// converts as jdcolor.c does and stores B G R.
+// Checked bit for bit against the system's libjpeg (tests/test_gpu_imdecode_bgr.py).
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -368,6 +376,162 @@ __device__ __forceinline__ void store_reduced_packed(uint8_t* __restrict__ out, 
   }
 }
 
+// A colour read (cv::IMREAD_COLOR) keeps every component in a plane of its own until jpeg_finish_bgr_kernel has upsampled and
+// converted them: per file a slot of 3 x `plane` bytes in the run's scratch -- the luminance at the image's size, rows `ypitch`
+// apart (what the gray decoders write, so a one-component file takes them as they are), then the two chroma components, each at
+// its own block-padded size mcus_x h[c] 8 x mcus_y v[c] 8 with rows as wide as that.
+struct ColourPlanes {
+  uint8_t* base;
+  size_t plane;               // bytes of one plane's slot (the largest block-padded luminance plane of the run, a multiple of 16)
+  int ypitch;
+  const uint16_t* qt_chroma;  // [file][2][64], natural order
+};
+
+// The one-wave decoder WITH its chroma (a colour read's three-component files that the parallel decoder cannot take, and
+// everything under VSF_OPT_JPEG_SERIAL): jpeg_gray_kernel<1> below with every block of an MCU kept.  A kernel of its own -- the
+// two share BitReader and the IDCT routines, not their bodies -- so that the gray kernels' code objects stay what they were.  The
+// chroma blocks are parked, transformed and stored like the luminance's (up to ten blocks an MCU), each into its plane of `cp`:
+// a file's slot is 3 planes long, the luminance first at the image's size.
+__global__ __launch_bounds__(64) void jpeg_colour_kernel(const DevImage* __restrict__ images, const uint32_t* __restrict__ index,
+                                                          const DevTables* __restrict__ tables,
+                                                          const uint8_t* __restrict__ stream, int width, int height,
+                                                          ColourPlanes cp) {
+  __shared__ uint16_t s_qt[3][64];
+  __shared__ __attribute__((aligned(16))) int16_t s_coef[kGroupBlocks][64];
+  __shared__ __attribute__((aligned(16))) int32_t s_ws[kGroupBlocks][64];
+  __shared__ int32_t s_dest[kGroupBlocks];  // y0 << 16 | x0
+  __shared__ uint8_t s_comp[kGroupBlocks];  // the component a parked block belongs to
+  const int lane = threadIdx.x;
+  const uint32_t image = index[blockIdx.x];
+  const DevImage& im = images[image];
+  const DevTables* tab = tables + im.tables;
+  s_qt[0][lane] = tab->qt_luma[lane];
+  s_qt[1][lane] = cp.qt_chroma[(size_t)image * 128 + lane];
+  s_qt[2][lane] = cp.qt_chroma[(size_t)image * 128 + 64 + lane];
+  uint8_t* out = cp.base + (size_t)image * 3 * cp.plane;
+  // geometry and decoder state: wave-uniform (see BitReader)
+  const int ncomp = im.ncomp, restart_interval = im.restart_interval, mcus_x = im.mcus_x;
+  const int nmcu = mcus_x * im.mcus_y;
+  const int h0 = im.h[0], v0 = im.v[0], luma_per_mcu = h0 * v0;
+  const int nblk1 = ncomp > 1 ? im.h[1] * im.v[1] : 0, nblk2 = ncomp > 2 ? im.h[2] * im.v[2] : 0;
+  const DevHuff *dc0 = &tab->huff[im.dc_slot[0]], *ac0 = &tab->huff[im.ac_slot[0]];
+  const DevHuff *dc1 = &tab->huff[im.dc_slot[ncomp > 1 ? 1 : 0]], *ac1 = &tab->huff[im.ac_slot[ncomp > 1 ? 1 : 0]];
+  const DevHuff *dc2 = &tab->huff[im.dc_slot[ncomp > 2 ? 2 : 0]], *ac2 = &tab->huff[im.ac_slot[ncomp > 2 ? 2 : 0]];
+  const uint32_t* zz32 = reinterpret_cast<const uint32_t*>(c_zigzag);
+  BitReader br{reinterpret_cast<const uint32_t*>(stream + im.stream_off), 0u, im.stream_len, 0ull, 0, false};
+  int pred0 = 0, pred1 = 0, pred2 = 0;
+  int mcu = 0, until_restart = restart_interval, next_restart = 0;
+  // one block: DC difference + AC run / size pairs (T.81 F.2.2.1, F.2.2.2); coefficients go to `coef` in natural order
+  auto block = [&](const DevHuff* hd, const DevHuff* ha, int& pred, int16_t* coef) {
+    br.fill();
+    const int t = br.decode(hd) & 15;  // (the host refuses DC tables with symbols above 15, as libjpeg does: second line of defence)
+    br.fill();
+    pred += br.receive_extend(t);
+    coef[0] = (int16_t)pred;
+    for (int k = 1; k < 64;) {
+      br.fill();
+      const int rs = br.decode(ha);
+      const int r = rs >> 4, sz = rs & 15;
+      if (sz == 0) {
+        if (r != 15) break;  // EOB
+        k += 16;
+        continue;
+      }
+      k += r;
+      const int val = br.receive_extend(sz);
+      // (damaged data can run past the block's end: libjpeg's jpeg_natural_order has sixteen spare entries that all say 63,
+      // so the value lands on the last coefficient and the block ends)
+      coef[k > 63 ? 63u : (zz32[k >> 2] >> (8 * (k & 3))) & 63u] = (int16_t)val;
+      k++;
+    }
+  };
+  // the blocks of one component in the MCU (mx, my): decoded (unless the data have run out) and booked with their place
+  auto component = [&](int c, const DevHuff* hd, const DevHuff* ha, int& pred, int hc, int vc, int mx, int my, bool skipped,
+                       int& count) {
+    for (int by = 0; by < vc; by++)
+      for (int bx = 0; bx < hc; bx++) {
+        if (!skipped) block(hd, ha, pred, s_coef[count]);
+        s_dest[count] = ((my * vc * 8 + by * 8) << 16) | (mx * hc * 8 + bx * 8);
+        s_comp[count] = (uint8_t)c;
+        count++;
+      }
+  };
+  __syncthreads();
+  for (;;) {
+    {  // clear the coefficient buffer
+      uint32_t* c = reinterpret_cast<uint32_t*>(&s_coef[0][0]);
+      for (int i = lane; i < kGroupBlocks * 32; i += 64) c[i] = 0u;
+    }
+    __syncthreads();
+    // ---- entropy decoding of as many whole MCUs as fit the coefficient buffer: uniform, every lane the same ----
+    int count = 0;
+    while (mcu < nmcu && count + luma_per_mcu + nblk1 + nblk2 <= kGroupBlocks) {
+      if (restart_interval && until_restart == 0) {
+        br.restart_as_libjpeg(next_restart);
+        pred0 = pred1 = pred2 = 0;
+        until_restart = restart_interval;
+      }
+      const int my = mcu / mcus_x, mx = mcu - my * mcus_x;
+      // jdhuff.c decode_mcu: "If we've run out of data, just leave the MCU set to zeroes.  This way, we return uniform gray
+      // for the remainder of the segment."  (The MCU in which the data ran out is finished on zero bits; an MCU without data is
+      // zeroes in every component.)
+      const bool skipped = br.starved();
+      component(0, dc0, ac0, pred0, h0, v0, mx, my, skipped, count);
+      if (nblk1 > 0) component(1, dc1, ac1, pred1, im.h[1], im.v[1], mx, my, skipped, count);
+      if (nblk2 > 0) component(2, dc2, ac2, pred2, im.h[2], im.v[2], mx, my, skipped, count);
+      if (restart_interval) until_restart--;
+      mcu++;
+    }
+    const bool done = mcu >= nmcu;
+    __syncthreads();
+    // ---- dequantise + IDCT of the parked blocks: 8 blocks x 8 columns, then 8 blocks x 8 rows, per round ----
+    for (int b0 = 0; b0 < count; b0 += 8) {
+      const int b = b0 + (lane >> 3), i = lane & 7;
+      if (b < count) {
+        int32_t d[8], r[8];
+        const uint16_t* qt = s_qt[s_comp[b]];
+#pragma unroll
+        for (int k = 0; k < 8; k++) d[k] = (int32_t)s_coef[b][8 * k + i] * (int32_t)qt[8 * k + i];
+        idct8_descaled(d, r, 11);  // DESCALE(., CONST_BITS - PASS1_BITS)
+#pragma unroll
+        for (int k = 0; k < 8; k++) s_ws[b][8 * k + i] = r[k];
+      }
+      __syncthreads();
+      if (b < count) {
+        int32_t d[8], r[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) d[k] = s_ws[b][8 * i + k];
+        idct8_descaled(d, r, 18);  // DESCALE(., 13 + 2 + 3)
+        const int x0 = s_dest[b] & 0xFFFF, y = (s_dest[b] >> 16) + i, c = s_comp[b];
+        // where the block's plane begins, how far its rows are apart and where it ends: the image for the luminance; a chroma
+        // plane is block-padded
+        uint8_t* plane = out + (size_t)c * cp.plane;
+        const int pitch = c == 0 ? cp.ypitch : mcus_x * im.h[c] * 8;
+        const int wlim = c == 0 ? width : pitch, hlim = c == 0 ? height : im.mcus_y * im.v[c] * 8;
+        if (y < hlim && x0 < wlim) {
+          uint8_t px[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++) px[k] = range_limit(r[k]);
+          uint8_t* row = plane + (size_t)y * pitch + x0;
+          if (x0 + 8 <= wlim) {
+            uint32_t lo, hi;
+            memcpy(&lo, px, 4);
+            memcpy(&hi, px + 4, 4);
+            reinterpret_cast<uint32_t*>(row)[0] = lo;  // (x0 % 8 == 0, base and pitch are multiples of 4)
+            reinterpret_cast<uint32_t*>(row)[1] = hi;
+          } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++)  // (unrolled: a run-time index would put px into scratch memory)
+              if (x0 + k < wlim) row[k] = px[k];
+          }
+        }
+      }
+      __syncthreads();
+    }
+    if (done) break;
+  }
+}  // (nothing in here breaks a file off -- what the data lack is zero bits, as in libjpeg --: no status word)
+
 // `index`: the images (positions in `images` and in the destination) this launch decodes, one per workgroup.
 // D: the denominator of the output size (IMREAD_REDUCED_GRAYSCALE_D; 1 = full size); width, height: the OUTPUT size.
 template <int D>
@@ -609,7 +773,11 @@ constexpr int kProgSpinCap = 1 << 19;
 // as libjpeg's jdphuff.c decodes it.  Wave-uniform (the reader state lives in SGPRs); the 64 lanes are the 64 coefficients
 // of the block at hand.  PIPE: the scans of a file run in different waves of one workgroup; a refinement scan waits, block
 // row by block row, for the scans it refines (ProgWait) and every scan publishes the rows it has completed.
-template <bool PIPE, class Image>
+// COLOUR (a colour read; never PIPE): every scan of the file is listed, and the chroma components have coefficients of their own
+// behind the luminance's -- component c's blocks in the order of the frame's interleaved MCUs, h[c] x v[c] to the MCU, as the
+// luminance's are -- which jpeg_idct_chroma_kernel turns into the chroma planes.  A scan of one component walks THAT component's
+// blocks: ceil(ceil(W h[c] / h[0]) / 8) x ceil(ceil(H v[c] / v[0]) / 8) of them (T.81 A.2.2).
+template <bool PIPE, bool COLOUR = false, class Image>
 __device__ __forceinline__ void prog_scan(const Image& im, int si, const DevScan* __restrict__ scans,
                                           const DevHuffLite* __restrict__ huffs, const uint8_t* __restrict__ stream,
                                           int16_t* __restrict__ coef, int width, int height, int lane, int nat, const ProgWait W,
@@ -656,10 +824,24 @@ __device__ __forceinline__ void prog_scan(const Image& im, int si, const DevScan
     // the MCUs of this scan: the frame's interleaved MCUs, or -- a scan of the luminance alone -- its own blocks in raster
     // order over ceil(W / 8) x ceil(H / 8) (T.81 A.2.2; the luminance is sampled at the full rate)
     const bool interleaved = ns > 1;
-    const int units_x = interleaved ? mcus_x : (width + 7) >> 3, units_y = interleaved ? im.mcus_y : (height + 7) >> 3;
-    auto block_of = [&](int by, int bx) __attribute__((always_inline)) -> int {  // a luminance block's place in the coefficient buffer
-      const int my = by / v0, mx = bx / h0;
-      return (my * mcus_x + mx) * lum + (by - my * v0) * h0 + (bx - mx * h0);
+    // COLOUR: the component of a one-component scan, its blocks per MCU and where its coefficients begin (in blocks)
+    const int c0 = COLOUR ? (int)sc.comp[0] : 0;
+    const int ch = COLOUR ? im.h[c0] : h0, cv = COLOUR ? im.v[c0] : v0;
+    auto comp_base = [&](int ci) __attribute__((always_inline)) -> int {
+      const int mcus = mcus_x * im.mcus_y;
+      return ci == 0 ? 0 : (ci == 1 ? mcus * lum : mcus * (lum + im.h[1] * im.v[1]));
+    };
+    const int own_w = COLOUR ? (width * ch + h0 - 1) / h0 : width, own_h = COLOUR ? (height * cv + v0 - 1) / v0 : height;
+    const int units_x = interleaved ? mcus_x : (own_w + 7) >> 3, units_y = interleaved ? im.mcus_y : (own_h + 7) >> 3;
+    const int own_base = COLOUR ? comp_base(c0) : 0;
+    auto block_of = [&](int by, int bx) __attribute__((always_inline)) -> int {  // a block's place in the coefficient buffer
+      if constexpr (COLOUR) {
+        const int my = by / cv, mx = bx / ch;
+        return own_base + (my * mcus_x + mx) * (ch * cv) + (by - my * cv) * ch + (bx - mx * ch);
+      } else {
+        const int my = by / v0, mx = bx / h0;
+        return (my * mcus_x + mx) * lum + (by - my * v0) * h0 + (bx - mx * h0);
+      }
     };
     if (Ss == 0) {
       // ---- DC scans ----
@@ -735,7 +917,10 @@ __device__ __forceinline__ void prog_scan(const Image& im, int si, const DevScan
                 const DevHuffLite* ta = c == 0 ? a0 : (c == 1 ? a1 : a2);
                 int pred = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);  // (by value: a reference picked at run time would
                 for (int b = 0; b < hh * vv; b++)                      //  put the three predictions into scratch memory)
-                  dc_block(t, ta, pred, ci == 0 ? coef + ((size_t)(uy * mcus_x + ux) * lum + b) * 64 : nullptr);
+                  if constexpr (COLOUR)
+                    dc_block(t, ta, pred, coef + ((size_t)comp_base(ci) + (size_t)(uy * mcus_x + ux) * (hh * vv) + b) * 64);
+                  else
+                    dc_block(t, ta, pred, ci == 0 ? coef + ((size_t)(uy * mcus_x + ux) * lum + b) * 64 : nullptr);
                 pred0 = c == 0 ? pred : pred0;
                 pred1 = c == 1 ? pred : pred1;
                 pred2 = c == 2 ? pred : pred2;
@@ -896,6 +1081,35 @@ __global__ __launch_bounds__(64) void jpeg_prog_kernel(const DevImage* __restric
   const ProgWait none{nullptr, -1, -1, -1, -1};
   for (int si = 0; si < im.n_scans && !broken; si++)
     prog_scan<false>(im, si, scans, huffs, stream, coef, width, height, lane, nat, none, broken, suspect);
+  if (lane == 0 && broken) atomicOr(status + (size_t)image * status_stride, 2);
+}
+
+// ... in a colour read: every scan, every component's coefficients (3 x the luminance's room: the chroma blocks are at most as
+// many as the luminance's each).  One-component files of the run come through here as well.
+__global__ __launch_bounds__(64) void jpeg_prog_colour_kernel(const DevImage* __restrict__ images,
+                                                               const uint32_t* __restrict__ index,
+                                                               const DevScan* __restrict__ scans,
+                                                               const DevHuffLite* __restrict__ huffs,
+                                                               const uint8_t* __restrict__ stream, int16_t* __restrict__ coef_all,
+                                                               size_t coef_stride, int slot0, int width, int height,
+                                                               int32_t* __restrict__ status, int status_stride) {
+  const int lane = threadIdx.x;
+  const uint32_t image = in_constant(index)[blockIdx.x];
+  const auto& im = *in_constant(images + image);
+  int16_t* coef = coef_all + (size_t)(slot0 + blockIdx.x) * (coef_stride / sizeof(int16_t));
+  const int mcus = im.mcus_x * im.mcus_y;
+  int nblocks = mcus * im.h[0] * im.v[0];
+  if (im.ncomp == 3) nblocks += mcus * (im.h[1] * im.v[1] + im.h[2] * im.v[2]);
+  {  // nothing is known yet
+    uint32_t* c32 = reinterpret_cast<uint32_t*>(coef);
+    for (int i = lane; i < nblocks * 32; i += 64) c32[i] = 0u;
+  }
+  const int nat = c_zigzag[lane];
+  bool broken = false;
+  bool suspect = false;
+  const ProgWait none{nullptr, -1, -1, -1, -1};
+  for (int si = 0; si < im.n_scans && !broken; si++)
+    prog_scan<false, true>(im, si, scans, huffs, stream, coef, width, height, lane, nat, none, broken, suspect);
   if (lane == 0 && broken) atomicOr(status + (size_t)image * status_stride, 2);
 }
 
@@ -1553,6 +1767,482 @@ __global__ __launch_bounds__(kParThreads) void jpeg_par_decode_kernel(const DevI
   }
 }
 
+// ---- the parallel decoder WITH its chroma (a colour read: jpeg_par_colour_kernel).  Copies of par_count, par_write and the
+// kernel, so that the gray ones keep their text and their code objects: what differs is that every component's DC differences
+// are summed (a prediction per component), and that every block is kept -- component c's blocks behind those of the components in
+// front of it, MCU order, the layout jpeg_prog_colour_kernel writes and jpeg_idct_kernel / jpeg_idct_chroma_kernel read. ----
+struct ParMarks3 {
+  uint32_t q[kMarks];
+  uint32_t cr[kMarks];
+  int dc[kMarks], dc1[kMarks], dc2[kMarks];  // DC differences of the luminance, Cb and Cr from the mark to the segment's end
+};
+
+__device__ __forceinline__ void par_count_colour(const ParGeom& G, ParWin& W, lds_u16 tab, uint32_t limit, uint32_t& q_io, int& c_io,
+                                          int& k_io, ParMarks3& marks, uint32_t& blocks, int& dcsum, int& dcsum1, int& dcsum2,
+                                                 bool& merged) {
+  uint32_t q = q_io, done = 0;
+  int c = c_io, k = k_io, dc = 0, dc1 = 0, dc2 = 0;
+  merged = false;
+  W.open(G, q);
+  uint32_t tq[kMarks], tcn[kMarks];
+  int td[kMarks], td1[kMarks], td2[kMarks];
+#pragma unroll
+  for (int i = 0; i < kMarks; i++) {
+    tq[i] = 0xFFFFFFFFu;
+    tcn[i] = 0u;
+    td[i] = td1[i] = td2[i] = 0;
+  }
+  while (q < limit && !merged) {
+    {
+      int kk, val;
+      const bool lum = c < G.lum, cb = !lum && c < G.lum + G.n1;
+      const bool end = par_symbol(G, W, tab, q, c, k, kk, val);
+      if (kk == 0) {  // (selects, not an index: the three sums stay in registers)
+        dc += lum ? val : 0;
+        dc1 += cb ? val : 0;
+        dc2 += lum || cb ? 0 : val;
+      }
+      if (end) {
+        k = 0;
+        done++;
+        c = c + 1 == G.m ? 0 : c + 1;
+        if (q == marks.q[0] || q == marks.q[1] || q == marks.q[2] || q == marks.q[3]) {  // (rare: kept out of the way)
+#pragma unroll
+          for (int i = 0; i < kMarks; i++)
+            if (q == marks.q[i] && (uint32_t)c == (marks.cr[i] & 255u)) {
+              merged = true;
+              done += marks.cr[i] >> 8;
+              dc += marks.dc[i];
+              dc1 += marks.dc1[i];
+              dc2 += marks.dc2[i];
+            }
+        } else if (done <= (2u << (kMarks - 1)) && (done & (done - 1u)) == 0u) {
+#pragma unroll
+          for (int i = 0; i < kMarks; i++)
+            if (done == (2u << i)) {
+              tq[i] = q;
+              tcn[i] = (uint32_t)c | (done << 8);
+              td[i] = dc;
+              td1[i] = dc1;
+              td2[i] = dc2;
+            }
+        }
+      }
+    }
+  }
+  if (!merged) {
+#pragma unroll
+    for (int i = 0; i < kMarks; i++) {
+      marks.q[i] = tq[i];
+      marks.cr[i] = (tcn[i] & 255u) | ((done - (tcn[i] >> 8)) << 8);
+      marks.dc[i] = dc - td[i];
+      marks.dc1[i] = dc1 - td1[i];
+      marks.dc2[i] = dc2 - td2[i];
+    }
+    q_io = q;
+    c_io = c;
+    k_io = k;
+  }
+  blocks = done;
+  dcsum = dc;
+  dcsum1 = dc1;
+  dcsum2 = dc2;
+}
+
+template <bool kClip = false>
+__device__ __forceinline__ uint32_t par_write_colour(const ParGeom& G, ParWin& W, lds_u16 tab, lds_u8 zz, uint32_t* blk_wave,
+                                              int lane, uint32_t limit, uint32_t q, int c, int k, uint32_t g, int pred,
+                                                     int pred1, int pred2, uint32_t nmcu, uint32_t* __restrict__ coef32,
+                                                     uint32_t total_blocks, bool finish, uint32_t data_end) {
+  // where a component's blocks begin (in blocks) and how many it has per MCU
+  const uint32_t lum = (uint32_t)G.lum, n1 = (uint32_t)G.n1, n2 = (uint32_t)G.m - lum - n1;
+  const uint32_t base1 = nmcu * lum, base2 = nmcu * (lum + n1);
+  uint32_t done = 0;
+  uint32_t mcu = (g - (uint32_t)c) / (uint32_t)G.m;                      // the MCU the lane stands in
+  bool skip = k != 0;                                                    // inside a block somebody else started
+  int16_t* mine = reinterpret_cast<int16_t*>(blk_wave + lane * kBlkStride);
+  auto has_work = [&]() {
+    const bool more = g + done < total_blocks;
+    return q < limit || (k != 0 && more) || (finish && more && (c != 0 || q <= data_end) && q < 0xFFFF0000u);
+  };
+  bool busy = has_work();
+  if (__ballot(busy) != 0ull) W.open(G, q);
+  while (__ballot(busy) != 0ull) {
+    bool flush = false;
+    uint32_t dst = 0;
+    if (busy) {
+      int kk, val;
+      const bool more = g + done < total_blocks;
+      const bool is0 = (uint32_t)c < lum, is1 = !is0 && (uint32_t)c < lum + n1;
+      const bool end = par_symbol<kClip>(G, W, tab, q, c, k, kk, val, data_end);
+      if (!skip && more && kk >= 0) {
+        if (kk == 0) {  // (a block's DC symbol is its first: never inside a skipped rest)
+          val += is0 ? pred : (is1 ? pred1 : pred2);
+          pred = is0 ? val : pred;
+          pred1 = is1 ? val : pred1;
+          pred2 = is0 || is1 ? pred2 : val;
+        }
+        mine[zz[kk]] = (int16_t)val;
+      }
+      if (end) {
+        flush = !skip && more;
+        dst = is0 ? mcu * lum + (uint32_t)c
+                  : (is1 ? base1 + mcu * n1 + ((uint32_t)c - lum) : base2 + mcu * n2 + ((uint32_t)c - lum - n1));
+        skip = false;
+        k = 0;
+        done++;
+        if (++c == G.m) {
+          c = 0;
+          mcu++;
+        }
+      }
+      busy = has_work();
+    }
+    uint64_t todo = __ballot(flush);
+    while (todo) {  // wave-uniform: one finished block per round, 32 lanes x 4 bytes
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1ull;
+      const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)dst, src);
+      if (lane < 32) {
+        uint32_t* p = blk_wave + src * kBlkStride + lane;
+        coef32[(size_t)d * 32 + lane] = *p;
+        *p = 0u;
+      }
+    }
+  }
+  {  // the MCUs a finishing lane has left out: zero coefficients (the buffer holds the last call's)
+    const uint32_t first = (g + done) / (uint32_t)G.m, last = total_blocks / (uint32_t)G.m;  // in MCUs
+    uint64_t todo = __ballot(finish && first < last);
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1ull;
+      const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)first, src), m1 = (uint32_t)__builtin_amdgcn_readlane((int)last, src);
+      for (uint32_t i = m0 * lum * 32u + (uint32_t)lane; i < m1 * lum * 32u; i += 64u) coef32[i] = 0u;
+      for (uint32_t i = (base1 + m0 * n1) * 32u + (uint32_t)lane; i < (base1 + m1 * n1) * 32u; i += 64u) coef32[i] = 0u;
+      for (uint32_t i = (base2 + m0 * n2) * 32u + (uint32_t)lane; i < (base2 + m1 * n2) * 32u; i += 64u) coef32[i] = 0u;
+    }
+  }
+  return q;  // (where the lane stopped)
+}
+
+__global__ __launch_bounds__(kParThreads) void jpeg_par_colour_kernel(const DevImage* __restrict__ images,
+                                                                       const uint32_t* __restrict__ index,
+                                                                       const DevTables* __restrict__ tables,
+                                                                       const uint8_t* __restrict__ stream,
+                                                                       uint32_t* __restrict__ clean_all,
+                                                                       uint32_t* __restrict__ trans_all,
+                                                                       int16_t* __restrict__ coef_all, size_t coef_stride,
+                                                                       int max_slots, int32_t* __restrict__ status,
+                                                                       int status_stride) {
+  constexpr int kWaves = kParThreads / 64;
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];  // max_slots Huffman tables (DevTables::huff): what
+                                                                     // the batch's files use -- two for gray streams
+  __shared__ uint32_t s_q[kParThreads + 1], s_ck[kParThreads + 1];  // end states; [t] = start of segment t (entry 0: truth)
+  __shared__ uint32_t s_cnt[kParThreads];
+  __shared__ int s_dc[3][kParThreads];
+  __shared__ uint32_t s_scan[4][kWaves], s_rscan[2][kWaves];
+  __shared__ uint32_t s_end, s_changed;
+  __shared__ uint8_t s_zz[64];
+  __shared__ uint32_t s_blk[kParThreads * kBlkStride];  // one coefficient block per thread (the writing pass)
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  for (int i = t; i < kParThreads * kBlkStride; i += kParThreads) s_blk[i] = 0u;
+  const DevImage& im = images[index[blockIdx.x]];  // (the coefficient buffer is indexed by the launch's own numbering)
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(tables + im.tables);
+    for (int i = t; i < max_slots * (int)(sizeof(DevHuff) / 4); i += kParThreads) s_tab[i] = src[i];
+  }
+  if (t < 64) s_zz[t] = c_zigzag[t];
+  if (t == 0) s_end = 0xFFFFFFFFu;
+  const uint8_t* raw = stream + im.stream_off;
+  const uint32_t* raw32 = reinterpret_cast<const uint32_t*>(raw);  // (stream_off is a multiple of 4)
+  uint8_t* clean8 = reinterpret_cast<uint8_t*>(clean_all) + im.stream_off;
+  const uint32_t* clean = clean_all + (im.stream_off >> 2);
+  const uint32_t len = im.stream_len;
+  __syncthreads();
+  // ---- 1. remove the byte stuffing: raw -> clean, a tile of 16 bytes per thread at a time (coalesced) ----
+  // Per dword: flags (bit 7 of each byte) for "is 0xFF" and "is 0x00"; a zero after an 0xFF is dropped, an 0xFF before a
+  // non-zero byte is a marker and ends the entropy-coded data (EOI, normally).  The clean offset of the first marker --
+  // or of the end of the segment -- is the length of the clean stream.
+  // Files with restart intervals (ri > 0): an RSTn marker (0xFF, 0xD0..0xD7) is dropped as well and the clean offset
+  // behind it -- where the next interval begins, byte-aligned -- goes into the interval table (ivl, in the space the
+  // segment-major copy would take).
+  const int ri = im.restart_interval;
+  uint32_t* trans = trans_all + ((im.stream_off + (uint32_t)blockIdx.x * (uint32_t)kTransSlack) >> 2);
+  uint32_t* ivl = trans;
+  const uint32_t ivl_cap = (len + (uint32_t)kTransSlack) >> 2;  // entries of the table (the host sends only files that fit)
+  uint32_t kept_before = 0, rst_before = 0;  // clean bytes / RSTn markers of earlier tiles (uniform)
+  for (uint32_t tile = 0, round = 0; tile < len; tile += kTileBytes, round++) {
+    const uint32_t i = tile + (uint32_t)t * 16u;
+    uint32_t d[4] = {0u, 0u, 0u, 0u}, ff[4], zz[4], rs[4] = {0u, 0u, 0u, 0u};
+    uint32_t prev_ff = 0u, next_zero = 0x80u, next_rst = 0u;
+    const int valid = i < len ? (int)min(16u, len - i) : 0;
+    if (valid) {  // (the host pads every segment with 32 zero bytes: these loads stay inside)
+#pragma unroll
+      for (int j = 0; j < 4; j++) d[j] = raw32[(i >> 2) + j];
+      prev_ff = i && raw[i - 1] == 0xFFu ? 0x80000000u : 0u;
+      const uint32_t nx = raw[i + 16];
+      next_zero = nx == 0u ? 0x80u : 0u;
+      next_rst = ri && (nx & 0xF8u) == 0xD0u && i + 16u < len ? 0x80u : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t n = ~d[j];
+      ff[j] = ~((((n & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | n) | 0x7F7F7F7Fu);
+      zz[j] = ~((((d[j] & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d[j]) | 0x7F7F7F7Fu);
+    }
+    if (ri) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t y = (d[j] ^ 0xD0D0D0D0u) & 0xF8F8F8F8u;  // zero bytes: 0xD0..0xD7
+        rs[j] = ~((((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) | 0x7F7F7F7Fu);
+      }
+    }
+    uint32_t drop[4], mark[4], rstb[4];
+    int kc = 0, rc = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t live = valid >= 4 * j + 4 ? 0x80808080u : (valid > 4 * j ? (0x80808080u >> (8 * (4 * j + 4 - valid))) : 0u);
+      const uint32_t after_ff = __builtin_amdgcn_alignbit(ff[j], j ? ff[j - 1] : prev_ff, 24);  // the byte before is 0xFF
+      const uint32_t rst_first = ff[j] & __builtin_amdgcn_alignbit(j < 3 ? rs[j + 1] : next_rst, rs[j], 8);  // 0xFF of an RSTn
+      rstb[j] = rs[j] & after_ff & live;                                                                    // its second byte
+      drop[j] = ((zz[j] & after_ff) | rst_first | rstb[j]) & live;
+      mark[j] = ff[j] & ~__builtin_amdgcn_alignbit(j < 3 ? zz[j + 1] : next_zero, zz[j], 8) & ~rst_first & live;
+      kc += __popc(live & ~drop[j]);
+      rc += __popc(rstb[j]);
+    }
+    uint32_t inc = (uint32_t)kc, incr = (uint32_t)rc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t v = __shfl_up(inc, o, 64);
+      const uint32_t vr = __shfl_up(incr, o, 64);
+      if (lane >= o) {
+        inc += v;
+        incr += vr;
+      }
+    }
+    if (lane == 63) {
+      s_scan[round & 1u][wid] = inc;
+      s_rscan[round & 1u][wid] = incr;
+    }
+    __syncthreads();
+    uint32_t off = kept_before + inc - (uint32_t)kc, tile_total = 0;
+    uint32_t ridx = rst_before + incr - (uint32_t)rc, tile_rst = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; w++) {
+      const uint32_t v = s_scan[round & 1u][w], vr = s_rscan[round & 1u][w];
+      if (w < wid) {
+        off += v;
+        ridx += vr;
+      }
+      tile_total += v;
+      tile_rst += vr;
+    }
+    kept_before += tile_total;
+    rst_before += tile_rst;
+    if (rc) {  // (rare) interval ridx + 1 begins at the clean offset behind this marker
+      uint32_t o = off;
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const uint32_t bit = 1u << (8 * (j & 3) + 7);
+        if (rstb[j >> 2] & bit) {
+          ++ridx;
+          if (ridx < ivl_cap) ivl[ridx] = o;
+        }
+        if (j < valid && !(drop[j >> 2] & bit)) o++;
+      }
+    }
+    if (valid) {
+      if ((mark[0] | mark[1] | mark[2] | mark[3]) != 0u) {  // the clean offset of the first marker in here
+        uint32_t o = off;
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          if (!found && mark[j]) {
+            const uint32_t below = (1u << (__ffs(mark[j]) - 8)) - 1u;  // the bytes before the marker in this dword
+            o += __popc(~drop[j] & 0x80808080u & below);
+            found = true;
+          }
+          if (!found) o += __popc(~drop[j] & 0x80808080u);
+        }
+        atomicMin(&s_end, o);
+      }
+      if (valid == 16 && (drop[0] | drop[1] | drop[2] | drop[3]) == 0u) {
+        __builtin_memcpy(clean8 + off, d, 16);
+      } else {
+        uint32_t o = off;
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+          if (j < valid && !((drop[j >> 2] >> (8 * (j & 3) + 7)) & 1u)) clean8[o++] = (uint8_t)(d[j >> 2] >> (8 * (j & 3)));
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t L = min(s_end, kept_before);  // clean bytes
+  if (t < 8) clean8[L + t] = 0;  // (zero bits are what libjpeg feeds past the end of the data; the buffer is padded)
+  __threadfence_block();
+  __syncthreads();
+  const int ncomp = im.ncomp;
+  const uint32_t nbits = L * 8u;
+  const uint32_t ndw = (L + 3u) >> 2;
+  ParGeom G;
+  G.lum = im.h[0] * im.v[0];
+  G.n1 = ncomp > 1 ? im.h[1] * im.v[1] : 0;
+  G.m = G.lum + G.n1 + (ncomp > 2 ? im.h[2] * im.v[2] : 0);  // blocks per MCU
+  G.dc_slots = (uint32_t)im.dc_slot[0] | ((uint32_t)im.dc_slot[ncomp > 1 ? 1 : 0] << 8) |
+               ((uint32_t)im.dc_slot[ncomp > 2 ? 2 : 0] << 16);
+  G.ac_slots = (uint32_t)im.ac_slot[0] | ((uint32_t)im.ac_slot[ncomp > 1 ? 1 : 0] << 8) |
+               ((uint32_t)im.ac_slot[ncomp > 2 ? 2 : 0] << 16);
+  const lds_u16 tab = (lds_u16)(&s_tab[0]);
+  const lds_u8 zz = (lds_u8)(&s_zz[0]);
+  uint32_t* coef32 = reinterpret_cast<uint32_t*>(coef_all + (size_t)blockIdx.x * (coef_stride / sizeof(int16_t)));
+  if (ri) {
+    // ---- files with restart intervals: every interval starts in a known state (byte-aligned, first block of an MCU,
+    // DC prediction zero), so there is nothing to guess: thread t decodes intervals t, t + 256, ... straight into the
+    // coefficient buffer (the writing pass of the other files, over the clean stream as it lies) ----
+    const uint32_t nmcu = (uint32_t)(im.mcus_x * im.mcus_y);
+    const uint32_t want = (nmcu + (uint32_t)ri - 1u) / (uint32_t)ri, have = min(rst_before + 1u, ivl_cap);
+    const uint32_t n_use = min(want, have);
+    bool broken = have < want;  // a restart marker is missing (what the one-wave decoder reports, too)
+    if (t == 0) ivl[0] = 0u;
+    __threadfence_block();
+    __syncthreads();
+    G.trans = nullptr;
+    G.segdw = 1u;
+    G.magic = 0u;
+    ParWin W;
+    W.col = nullptr;
+    W.lin = clean;
+    W.rows = ndw;
+    W.gbase = 0u;
+    W.jb = W.w0 = W.w1 = 0u;
+    for (uint32_t j0 = 0; j0 < n_use; j0 += kParThreads) {
+      const uint32_t j = j0 + (uint32_t)t;
+      const bool live = j < n_use;
+      const uint32_t begin = live ? ivl[j] * 8u : 0u, end = live && j + 1u < have ? ivl[j + 1u] * 8u : nbits;
+      const uint32_t g = j * (uint32_t)ri * (uint32_t)G.m;
+      const uint32_t blocks = live ? min((uint32_t)ri, nmcu - j * (uint32_t)ri) * (uint32_t)G.m : 0u;
+      // (an interval whose data run out before its blocks do: gray MCUs, a warning in libjpeg)
+      (void)par_write_colour<true>(G, W, tab, zz, s_blk + wid * 64 * kBlkStride, lane, 0u, begin, 0, 0, g, 0, 0, 0, nmcu, coef32,
+                                   g + blocks, true, end);
+    }
+    if (broken) atomicOr(status + (size_t)index[blockIdx.x] * status_stride, 2);
+    return;
+  }
+  // ---- 2. segment end states until they stop changing ----
+  const uint32_t seg = max(64u, ((nbits + kParThreads - 1) / kParThreads + 31u) & ~31u);
+  const uint32_t limit = min((uint32_t)(t + 1) * seg, nbits);
+  const uint32_t segdw = seg >> 5;
+  for (uint32_t j = 0; j < segdw + kOverlap; j++) {  // the segment-major copy (zero bits past the end, as libjpeg feeds them)
+    const uint32_t b = (uint32_t)t * segdw + j;
+    trans[j * (uint32_t)kParThreads + (uint32_t)t] = b < ndw ? __builtin_bswap32(clean[b]) : 0u;
+  }
+  __threadfence_block();
+  __syncthreads();
+  G.trans = trans;
+  G.segdw = segdw;
+  G.magic = 0xFFFFFFFFu / segdw + 1u;
+  ParWin W;
+  W.col = trans + t;
+  W.lin = nullptr;
+  W.rows = segdw + kOverlap;
+  W.gbase = (uint32_t)t * segdw;
+  W.jb = W.w0 = W.w1 = 0u;
+  uint32_t sq = (uint32_t)t * seg, sck = 0;  // assumed start: first block of an MCU, DC next (true for t == 0)
+  ParMarks3 marks;
+#pragma unroll
+  for (int i = 0; i < kMarks; i++) {
+    marks.q[i] = 0xFFFFFFFFu;
+    marks.cr[i] = 0u;
+    marks.dc[i] = marks.dc1[i] = marks.dc2[i] = 0;
+  }
+  if (t == 0) {
+    s_q[0] = 0;
+    s_ck[0] = 0;
+    s_changed = 0;
+  }
+  {
+    uint32_t q = min(sq, nbits), cnt;
+    int c = 0, k = 0, dc, dc1, dc2;
+    bool merged;
+    par_count_colour(G, W, tab, limit, q, c, k, marks, cnt, dc, dc1, dc2, merged);
+    s_cnt[t] = cnt;
+    s_dc[0][t] = dc;
+    s_dc[1][t] = dc1;
+    s_dc[2][t] = dc2;
+    s_q[t + 1] = q;
+    s_ck[t + 1] = ((uint32_t)c << 8) | (uint32_t)k;
+  }
+  __syncthreads();
+  for (int round = 0; round < kParThreads; round++) {
+    const uint32_t nq = s_q[t], nck = s_ck[t];  // the predecessor's end state (the truth for t == 0)
+    bool redo = t > 0 && (nq != sq || nck != sck), merged = false;
+    uint32_t q = nq, cnt = 0;
+    int c = (int)(nck >> 8), k = (int)(nck & 255u), dc = 0, dc1 = 0, dc2 = 0;
+    if (redo) par_count_colour(G, W, tab, limit, q, c, k, marks, cnt, dc, dc1, dc2, merged);
+    __syncthreads();  // (everybody has read its predecessor's state)
+    if (redo) {
+      sq = nq;
+      sck = nck;
+      s_cnt[t] = cnt;
+      s_dc[0][t] = dc;
+      s_dc[1][t] = dc1;
+      s_dc[2][t] = dc2;
+      if (!merged) {  // (merged: the rest of the way, end state included, is the one already on record)
+        const uint32_t eck = ((uint32_t)c << 8) | (uint32_t)k;
+        if (s_q[t + 1] != q || s_ck[t + 1] != eck) atomicOr(&s_changed, 1u);
+        s_q[t + 1] = q;
+        s_ck[t + 1] = eck;
+      }
+    }
+    __syncthreads();
+    const uint32_t any = s_changed;
+    __syncthreads();
+    if (t == 0) s_changed = 0;
+    if (!any) break;  // uniform: nothing moved, so nothing will
+  }
+  __syncthreads();
+  // (thread 0 never re-ran: its start was true; sq / sck of the others now equal their predecessors' end states)
+  // ---- 3. block and DC offsets, then the writing pass ----
+  const uint32_t mine = s_cnt[t];
+  const int mine_dc = s_dc[0][t], mine_dc1 = s_dc[1][t], mine_dc2 = s_dc[2][t];
+  uint32_t incb = mine;
+  int incd = mine_dc, incd1 = mine_dc1, incd2 = mine_dc2;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(incb, o, 64);
+    const int d = __shfl_up(incd, o, 64), d1 = __shfl_up(incd1, o, 64), d2 = __shfl_up(incd2, o, 64);
+    if (lane >= o) {
+      incb += v;
+      incd += d;
+      incd1 += d1;
+      incd2 += d2;
+    }
+  }
+  if (lane == 63) {
+    s_scan[0][wid] = incb;
+    s_scan[1][wid] = (uint32_t)incd;
+    s_scan[2][wid] = (uint32_t)incd1;
+    s_scan[3][wid] = (uint32_t)incd2;
+  }
+  __syncthreads();
+  uint32_t g = incb - mine;
+  int pred = incd - mine_dc, pred1 = incd1 - mine_dc1, pred2 = incd2 - mine_dc2;
+  for (int w = 0; w < wid; w++) {
+    g += s_scan[0][w];
+    pred += (int)s_scan[1][w];
+    pred1 += (int)s_scan[2][w];
+    pred2 += (int)s_scan[3][w];
+  }
+  {
+    const uint32_t total_blocks = (uint32_t)(im.mcus_x * im.mcus_y * G.m);
+    uint32_t q = t == 0 ? 0u : s_q[t];
+    const uint32_t ck = t == 0 ? 0u : s_ck[t];
+    int c = (int)(ck >> 8), k = (int)(ck & 255u);
+    (void)par_write_colour(G, W, tab, zz, s_blk + wid * 64 * kBlkStride, lane, limit, q, c, k, g, pred, pred1, pred2,
+                           (uint32_t)(im.mcus_x * im.mcus_y), coef32, total_blocks, t == kParThreads - 1, nbits);
+  }
+}
+
 // dequantisation + IDCT + range limit of 8 luminance blocks per wave, from the coefficient buffer
 __global__ __launch_bounds__(64) void jpeg_idct_kernel(const DevImage* __restrict__ images,
                                                         const uint32_t* __restrict__ index,
@@ -1600,6 +2290,53 @@ __global__ __launch_bounds__(64) void jpeg_idct_kernel(const DevImage* __restric
         for (int k = 0; k < 8 && x0 + k < width; k++) row[k] = px[k];
       }
     }
+  }
+}
+
+// The chroma components of a colour read from the coefficient buffer (jpeg_prog_colour_kernel's layout: component c behind the
+// components in front of it, MCU order) into their block-padded planes: blockIdx.z = component - 1.  Every block of the padded
+// grid is written whole.
+__global__ __launch_bounds__(64) void jpeg_idct_chroma_kernel(const DevImage* __restrict__ images,
+                                                               const uint32_t* __restrict__ index,
+                                                               const int16_t* __restrict__ coef_all, size_t coef_stride,
+                                                               ColourPlanes cp) {
+  __shared__ int32_t s_ws[8][64];
+  const uint32_t image = index[blockIdx.y];
+  const DevImage& im = images[image];
+  const int c = 1 + blockIdx.z;
+  const bool file = im.ncomp == 3;  // (a one-component file has no chroma)
+  const int hc = file ? im.h[c] : 1, vc = file ? im.v[c] : 1, per = hc * vc, mcus = im.mcus_x * im.mcus_y;
+  const int nb = file ? mcus * per : 0;
+  const int base = mcus * im.h[0] * im.v[0] + (c == 2 && file ? mcus * im.h[1] * im.v[1] : 0);
+  const int lane = threadIdx.x, b = blockIdx.x * 8 + (lane >> 3), i = lane & 7;
+  const int16_t* coef = coef_all + (size_t)blockIdx.y * (coef_stride / sizeof(int16_t)) + ((size_t)base + b) * 64;
+  const uint16_t* qt = cp.qt_chroma + (size_t)image * 128 + 64 * (c - 1);
+  if (b < nb) {
+    int32_t d[8], r[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = (int32_t)coef[8 * k + i] * (int32_t)qt[8 * k + i];
+    idct8_descaled(d, r, 11);
+#pragma unroll
+    for (int k = 0; k < 8; k++) s_ws[lane >> 3][8 * k + i] = r[k];
+  }
+  __syncthreads();
+  if (b < nb) {
+    int32_t d[8], r[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = s_ws[lane >> 3][8 * i + k];
+    idct8_descaled(d, r, 18);
+    const int mcu = b / per, k0 = b - mcu * per;
+    const int my = mcu / im.mcus_x, mx = mcu - my * im.mcus_x;
+    const int x0 = (mx * hc + k0 % hc) * 8, y = (my * vc + k0 / hc) * 8 + i, pitch = im.mcus_x * hc * 8;
+    uint8_t px[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) px[k] = range_limit(r[k]);
+    uint32_t lo, hi;
+    memcpy(&lo, px, 4);
+    memcpy(&hi, px + 4, 4);
+    uint32_t* row = reinterpret_cast<uint32_t*>(cp.base + ((size_t)image * 3 + c) * cp.plane + (size_t)y * pitch + x0);
+    row[0] = lo;  // (x0 and the pitch are multiples of 8, the planes of 16)
+    row[1] = hi;
   }
 }
 
@@ -1673,6 +2410,97 @@ __global__ __launch_bounds__(64) void jpeg_idct_reduced_kernel(const DevImage* _
   }
 }
 
+// The last step of a colour read (out_color_space = JCS_RGB, do_fancy_upsampling on, so no merged upsampling; OpenCV swaps red
+// and blue afterwards): each chroma plane is upsampled to the luminance's grid as libjpeg-turbo's jdsample.c does for the
+// component's ratio, jdcolor.c's ycc_rgb_convert (16-bit fixed point, range-limited) makes the colours, B G R are stored.
+//   1 x 1          the sample itself (fullsize_upsample)
+//   2 x 1          the triangle filter 3/4 1/4 along the row (h2v1_fancy_upsample) when the component's row has more than two
+//                  samples, else each sample twice; the first and the last output column are the edge samples themselves
+//   1 x 2          3/4 of the nearer row and 1/4 of the further one, rounded up in the lower output row only (h1v2_fancy_upsample)
+//   2 x 2          both (h2v2_fancy_upsample: column sums 3 near + far, then 3 this + the neighbour's, bias 8 to the left and 7
+//                  to the right), under the same width rule as 2 x 1
+//   anything else  each sample hr x vr times (int_upsample)
+// The two-row filters' further row is the component's neighbouring row whichever MCU row it was decoded in; above the first row
+// and below the last row the image HAS (ceil(H v[c] / v[0]): not the block padding) it is the edge row again, as jdmainct.c's
+// context rows have it.  A widths's edge is the last sample the image has in the same way.
+// A lane makes four pixels of one row: a dword of luminance in, three dwords out (x0 = 4 k, so 3 x0 is a multiple of 4 and base
+// and pitch are); a row's last pixels go out byte by byte, so exactly 3 width bytes of a row are written.
+__device__ __forceinline__ int chroma_sample(const uint8_t* __restrict__ P, int pitch, int dw, int dh, int hr, int vr, int x, int y) {
+  if (hr == 1 && vr == 1) return P[(size_t)y * pitch + x];
+  if (hr == 2 && vr == 1 && dw > 2) {
+    const uint8_t* in = P + (size_t)y * pitch;
+    const int i = x >> 1;
+    if (x == 0 || x == 2 * dw - 1) return in[i];
+    return (x & 1) ? (3 * in[i] + in[i + 1] + 2) >> 2 : (3 * in[i] + in[i - 1] + 1) >> 2;
+  }
+  if (hr == 1 && vr == 2) {
+    const int r = y >> 1, nb = (y & 1) ? min(r + 1, dh - 1) : max(r - 1, 0);
+    return (3 * P[(size_t)r * pitch + x] + P[(size_t)nb * pitch + x] + ((y & 1) ? 2 : 1)) >> 2;
+  }
+  if (hr == 2 && vr == 2 && dw > 2) {
+    const int r = y >> 1, nb = (y & 1) ? min(r + 1, dh - 1) : max(r - 1, 0);
+    const uint8_t *in0 = P + (size_t)r * pitch, *in1 = P + (size_t)nb * pitch;
+    const int i = x >> 1, here = 3 * in0[i] + in1[i];
+    if (x == 0) return (4 * here + 8) >> 4;
+    if (x == 2 * dw - 1) return (4 * here + 7) >> 4;
+    return (x & 1) ? (3 * here + 3 * in0[i + 1] + in1[i + 1] + 7) >> 4 : (3 * here + 3 * in0[i - 1] + in1[i - 1] + 8) >> 4;
+  }
+  return P[(size_t)(y / vr) * pitch + x / hr];
+}
+
+constexpr int kFinishRows = 4;  // rows a workgroup takes, a wave each
+__global__ __launch_bounds__(64 * kFinishRows) void jpeg_finish_bgr_kernel(const DevImage* __restrict__ images, ColourPlanes cp, int width,
+                                                              int height, uint8_t* __restrict__ dst, size_t dst_image_stride,
+                                                              int dst_pitch) {
+  const int image = blockIdx.z, y = blockIdx.y * kFinishRows + threadIdx.y, x0 = 4 * (blockIdx.x * 64 + threadIdx.x);
+  if (x0 >= width || y >= height) return;
+  const DevImage& im = images[image];
+  const uint8_t* Y = cp.base + (size_t)image * 3 * cp.plane;
+  uint32_t y4 = *reinterpret_cast<const uint32_t*>(Y + (size_t)y * cp.ypitch + x0);  // (the row's padding is inside the plane,
+  if (x0 + 4 > width) y4 &= (1u << (8 * (width - x0))) - 1u;                         //  but nobody wrote it: not looked at)
+  uint32_t out[3] = {0, 0, 0};  // the twelve bytes, kept in registers: every index below is a constant once unrolled
+  auto put = [&](int j, uint32_t v) __attribute__((always_inline)) { out[j >> 2] |= v << (8 * (j & 3)); };
+  if (im.ncomp == 1) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t v = (y4 >> (8 * k)) & 255u;
+      put(3 * k, v);
+      put(3 * k + 1, v);
+      put(3 * k + 2, v);
+    }
+  } else {
+    const int h0 = im.h[0], v0 = im.v[0];
+    const int hr1 = h0 / im.h[1], vr1 = v0 / im.v[1], hr2 = h0 / im.h[2], vr2 = v0 / im.v[2];
+    const int p1 = im.mcus_x * im.h[1] * 8, p2 = im.mcus_x * im.h[2] * 8;
+    const int dw1 = (width * im.h[1] + h0 - 1) / h0, dh1 = (height * im.v[1] + v0 - 1) / v0;
+    const int dw2 = (width * im.h[2] + h0 - 1) / h0, dh2 = (height * im.v[2] + v0 - 1) / v0;
+    const uint8_t *Cb = Y + cp.plane, *Cr = Y + 2 * cp.plane;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int x = min(x0 + k, width - 1);  // (pixels behind the row's end are computed and not stored)
+      const int yy = (int)((y4 >> (8 * k)) & 255u);
+      const int cb = chroma_sample(Cb, p1, dw1, dh1, hr1, vr1, x, y) - 128, cr = chroma_sample(Cr, p2, dw2, dh2, hr2, vr2, x, y) - 128;
+      // jdcolor.c build_ycc_rgb_table: FIX(1.40200), FIX(1.77200), FIX(0.71414), FIX(0.34414) at 16 bits, ONE_HALF where it adds it
+      const int r = yy + ((91881 * cr + 32768) >> 16), b = yy + ((116130 * cb + 32768) >> 16);
+      const int g = yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+      put(3 * k, (uint32_t)min(max(b, 0), 255));
+      put(3 * k + 1, (uint32_t)min(max(g, 0), 255));
+      put(3 * k + 2, (uint32_t)min(max(r, 0), 255));
+    }
+  }
+  uint8_t* row = dst + (size_t)image * dst_image_stride + (size_t)y * dst_pitch + (size_t)3 * x0;
+  if (x0 + 4 <= width) {
+    uint32_t* w = reinterpret_cast<uint32_t*>(row);
+    w[0] = out[0];
+    w[1] = out[1];
+    w[2] = out[2];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; k++)  // (at most three pixels are left)
+      if (k < 3 * (width - x0)) row[k] = (uint8_t)(out[k >> 2] >> (8 * (k & 3)));
+  }
+}
+
 // Bytes of the parallel decoder's stream scratch: the clean streams in the layout of the upload's stream part, then
 // their segment-major copies.
 size_t clean_bytes(size_t stream_bytes, int n_par) {
@@ -1681,7 +2509,8 @@ size_t clean_bytes(size_t stream_bytes, int n_par) {
 }
 
 // Bytes of one file's slot in the coefficient buffer: every luminance block of the largest padded image, written whole.
-size_t coef_slot_bytes(const VsfJpegPlan& p) { return (size_t)p.max_luma_blocks * 64 * sizeof(int16_t); }
+// (a colour read: three times that -- a chroma component has at most as many blocks as the luminance)
+size_t coef_slot_bytes(const VsfJpegPlan& p) { return (size_t)p.max_luma_blocks * 64 * sizeof(int16_t) * (p.colour ? 3 : 1); }
 
 }  // namespace
 
@@ -1694,6 +2523,7 @@ VsfDecodeNeed vsf_jpeg_scratch_need(const VsfJpegPlan& p) {
   if (p.n_par + p.n_prog > 0)
     need.coef = (size_t)(p.n_par + p.n_prog) * coef_slot_bytes(p) + (size_t)p.n_prog_huff * sizeof(DevHuffLite);
   need.flags = (size_t)p.n_prog * sizeof(int32_t);
+  if (p.colour) need.planes = (size_t)p.stream_off.size() * 3 * ((p.max_plane + 15) & ~(size_t)15);
   return need;
 }
 
@@ -1701,7 +2531,9 @@ VsfDecodeNeed vsf_jpeg_scratch_need(const VsfJpegPlan& p) {
 hipError_t vsf_prepare_jpeg_kernels(int lds_limit) {
   const int need = (int)(kMaxSlots * sizeof(DevHuff));
   if (need > lds_limit) return hipErrorInvalidValue;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(jpeg_par_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, need);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(jpeg_par_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, need);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(jpeg_par_colour_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, need);
 }
 
 // Both decoders over one upload: the files without restart intervals (n_par of them, listed first in the index array
@@ -1713,6 +2545,21 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
                             const VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride, int dst_pitch,
                             int32_t* d_status, int status_stride, bool prog_serial, hipStream_t s) {
   const int n_par = p.n_par, n_prog = p.n_prog, n_ser = n - n_par - n_prog;
+  // a colour read: the decoders write into the planes of the run's scratch (the luminance where a gray read has its image) and
+  // the finishing kernel at the end writes the destination
+  ColourPlanes cp{};
+  uint8_t* const d_bgr = d_dst;
+  const size_t bgr_image_stride = dst_image_stride;
+  const int bgr_pitch = dst_pitch;
+  if (p.colour) {
+    cp.base = scratch.planes;
+    cp.plane = (p.max_plane + 15) & ~(size_t)15;
+    cp.ypitch = (width + 3) & ~3;
+    cp.qt_chroma = reinterpret_cast<const uint16_t*>(d_blob + p.off_qt_chroma);
+    d_dst = cp.base;
+    dst_image_stride = 3 * cp.plane;
+    dst_pitch = cp.ypitch;
+  }
   const size_t coef_stride = coef_slot_bytes(p);
   int16_t* d_coef = scratch.coef;
   DevHuffLite* d_prog_huff = reinterpret_cast<DevHuffLite*>(reinterpret_cast<uint8_t*>(d_coef) + (size_t)(n_par + n_prog) * coef_stride);
@@ -1728,7 +2575,8 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
   const int file_w = width * d, file_h = height * d;
   if (n_par > 0) {
     // (static + dynamic LDS exceed 64 KB for colour files: vsf_prepare_jpeg_kernels raised the limit at vsf_create)
-    hipLaunchKernelGGL(jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads), (size_t)p.max_slots * sizeof(DevHuff), s, images, index, tables, stream,
+    hipLaunchKernelGGL(p.colour ? jpeg_par_colour_kernel : jpeg_par_decode_kernel, dim3(n_par), dim3(kParThreads),
+                       (size_t)p.max_slots * sizeof(DevHuff), s, images, index, tables, stream,
                        reinterpret_cast<uint32_t*>(scratch.clean.get()),
                        reinterpret_cast<uint32_t*>(scratch.clean + clean_bytes(stream_bytes, 0)), d_coef, coef_stride,
                        p.max_slots, d_status, status_stride);
@@ -1741,16 +2589,24 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
     // The pipelined form pays while the CUs' scalar units have slots left: 256 files per call 7.1 k images/s against 3.7 k
     // scan after scan, 512 files 11.5 against 7.1 k, 768 files 14.9 against 10.3 k; from ~1000 files on the one-wave form
     // fills the scalar units by itself (1024: 13.1 / 13.3 k, 1536: 12.1 / 15.8 k, 2048: 13.5 / 16.7 k).
-    if (!prog_serial && scratch.flags && n_prog <= kProgPipeMaxFiles) {
+    if (p.colour) {  // every scan of every component, scan after scan (the pipelined form orders luminance scans only)
+      hipLaunchKernelGGL(jpeg_prog_colour_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par, scans,
+                         static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, file_w, file_h, d_status,
+                         status_stride);
+    } else if (!prog_serial && scratch.flags && n_prog <= kProgPipeMaxFiles) {
       hipLaunchKernelGGL(jpeg_prog_pipe_kernel, dim3(n_prog), dim3(64 * kProgWaves), 0, s, images, index + n_par, scans,
                          static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, file_w, file_h,
                          scratch.flags);
       only = scratch.flags;  // (the one-wave kernel below then repeats the files that kernel flagged, and no others)
     }
-    hipLaunchKernelGGL(jpeg_prog_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par, scans,
-                       static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, file_w, file_h, d_status,
-                       status_stride, only);
+    if (!p.colour)
+      hipLaunchKernelGGL(jpeg_prog_kernel, dim3(n_prog), dim3(64), 0, s, images, index + n_par, scans,
+                         static_cast<const DevHuffLite*>(d_prog_huff), stream, d_coef, coef_stride, n_par, file_w, file_h, d_status,
+                         status_stride, only);
   }
+  if (p.colour && n_par + n_prog > 0)  // (a chroma component has at most as many blocks as the luminance)
+    hipLaunchKernelGGL(jpeg_idct_chroma_kernel, dim3((p.max_luma_blocks + 7) / 8, n_par + n_prog, 2), dim3(64), 0, s, images, index,
+                       static_cast<const int16_t*>(d_coef), coef_stride, cp);
   if (n_par + n_prog > 0 && d == 1)
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((p.max_luma_blocks + 7) / 8, n_par + n_prog), dim3(64), 0, s, images, index, tables,
                        d_coef, coef_stride, width, height, d_dst, dst_image_stride, dst_pitch);
@@ -1762,10 +2618,17 @@ void vsf_launch_jpeg_decode(const uint8_t* d_blob, const VsfJpegPlan& p, int n, 
     hipLaunchKernelGGL(k, dim3(waves, n_par + n_prog), dim3(64), 0, s, images, index, tables, static_cast<const int16_t*>(d_coef),
                        coef_stride, width, height, d_dst, dst_image_stride, dst_pitch);
   }
-  if (n_ser > 0) {
+  if (n_ser > 0 && p.colour) {
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, stream, width,
+                       height, cp);
+  } else if (n_ser > 0) {
     auto* k = d == 1 ? jpeg_gray_kernel<1> : (d == 2 ? jpeg_gray_kernel<2> : (d == 4 ? jpeg_gray_kernel<4> : jpeg_gray_kernel<8>));
     hipLaunchKernelGGL(k, dim3(n_ser), dim3(64), 0, s, images, index + n_par + n_prog, tables, stream,
                        (uint32_t)(stream_bytes & ~(size_t)3), width, height, d_dst, dst_image_stride, dst_pitch,
                        d_status, status_stride);
   }
+  if (p.colour)
+    hipLaunchKernelGGL(jpeg_finish_bgr_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)((height + kFinishRows - 1) / kFinishRows), (unsigned)n),
+                       dim3(64, kFinishRows), 0, s, images,
+                       cp, width, height, d_bgr, bgr_image_stride, bgr_pitch);
 }

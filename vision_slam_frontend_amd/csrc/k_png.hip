@@ -1130,8 +1130,30 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(PngArgs a) {
   }
 }
 
+// Where a pixel's value goes.  BGR (cv::IMREAD_COLOR, vsf_imdecode_bgr_batch): a pixel is three bytes, blue first, and a gray
+// value is all three of them (png_set_gray_to_rgb); otherwise the byte it always was.  `x` counts pixels from `row`.
+template <bool BGR>
+__device__ __forceinline__ void put_gray(uint8_t* row, int x, uint8_t v) {
+  if constexpr (BGR) {
+    row[3 * x] = v;
+    row[3 * x + 1] = v;
+    row[3 * x + 2] = v;
+  } else {
+    row[x] = v;
+  }
+}
+
+// Pixel x of a row in the colour form: the palette's entry `v` (three bytes, blue first) or, without a palette, the gray value v.
+__device__ __forceinline__ void put_bgr(uint8_t* row, int x, const uint8_t* lut, uint32_t v) {
+  const uint8_t* e = lut ? lut + 3 * v : nullptr;
+  row[3 * x] = e ? e[0] : (uint8_t)v;
+  row[3 * x + 1] = e ? e[1] : (uint8_t)v;
+  row[3 * x + 2] = e ? e[2] : (uint8_t)v;
+}
+
 // Filters (PNG specification 9.2), one wave per image, rows r0 .. r0 + 63 as a wavefront.
 // This one: gray and gray + alpha files, not interlaced -- what a camera driver writes.
+template <bool BGR>
 __global__ __launch_bounds__(64) void png_unfilter_kernel(PngArgs a) {
   const int lane = threadIdx.x;
   const int image = blockIdx.x;
@@ -1179,13 +1201,13 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(PngArgs a) {
         if (act) {
           if (lane == 63) frow[1 + j * bpp] = (uint8_t)R;  // the next 64 rows' "above"
           if (depth >= 8) {
-            dst[(size_t)row * a.dst_pitch + j] = (uint8_t)R;
+            put_gray<BGR>(dst + (size_t)row * a.dst_pitch, j, (uint8_t)R);
           } else {  // 1, 2, 4 bits: the samples of a byte, most significant first, replicated to 8 bits
             const int ppb = 8 / depth;
             const uint32_t mask = (1u << depth) - 1u, mul = 255u / mask;
             for (int p = 0; p < ppb; p++) {
               const int x = j * ppb + p;
-              if (x < w) dst[(size_t)row * a.dst_pitch + x] = (uint8_t)(((R >> (8 - depth * (p + 1))) & mask) * mul);
+              if (x < w) put_gray<BGR>(dst + (size_t)row * a.dst_pitch, x, (uint8_t)(((R >> (8 - depth * (p + 1))) & mask) * mul));
             }
           }
         }
@@ -1197,7 +1219,9 @@ __global__ __launch_bounds__(64) void png_unfilter_kernel(PngArgs a) {
 }
 
 // The same for palette files (the index goes through the file's 256 gray values) and interlaced files of either kind: seven
-// passes, each a small image with filter bytes of its own, written to their places (Adam7).
+// passes, each a small image with filter bytes of its own, written to their places (Adam7).  BGR: the palette's table holds
+// three bytes an entry (blue, green, red: png_set_palette_to_rgb + png_set_bgr; a tRNS chunk's alpha is stripped again).
+template <bool BGR>
 __global__ __launch_bounds__(64) void png_unfilter_general_kernel(PngArgs a) {
   const int lane = threadIdx.x;
   const int image = blockIdx.x;
@@ -1227,7 +1251,7 @@ __global__ __launch_bounds__(64) void png_unfilter_general_kernel(PngArgs a) {
       const uint8_t* above_row = filt + (size_t)(r0 > 0 ? r0 - 1 : 0) * rb1;  // lane 0's "above": reconstructed in place by lane 63
       const int ftype = rowok ? frow[0] : 0;
       if (ftype > 4) bad = true;
-      uint8_t* drow = dst + (size_t)(g.y0 + row * g.dy) * a.dst_pitch + g.x0;
+      uint8_t* drow = dst + (size_t)(g.y0 + row * g.dy) * a.dst_pitch + g.x0 * (BGR ? 3 : 1);
       uint32_t ra = 0, rc = 0, last = 0;
       for (int s0 = 0; s0 < nb + 63; s0 += 8) {
         uint32_t F[8], U[8];
@@ -1255,14 +1279,21 @@ __global__ __launch_bounds__(64) void png_unfilter_general_kernel(PngArgs a) {
           if (act) {
             if (lane == 63) frow[1 + j * bpp] = (uint8_t)R;  // the next 64 rows' "above"
             if (depth >= 8) {
-              drow[j * g.dx] = lut ? lut[R] : (uint8_t)R;
+              if constexpr (BGR)
+                put_bgr(drow, j * g.dx, lut, R);
+              else
+                drow[j * g.dx] = lut ? lut[R] : (uint8_t)R;
             } else {  // 1, 2, 4 bits: the samples of a byte, most significant first -- replicated to 8 bits, or looked up
               const int ppb = 8 / depth;
               const uint32_t mask = (1u << depth) - 1u, mul = 255u / mask;
               for (int p = 0; p < ppb; p++) {
                 const int x = j * ppb + p;
                 const uint32_t v = (R >> (8 - depth * (p + 1))) & mask;
-                if (x < w) drow[x * g.dx] = lut ? lut[v] : (uint8_t)(v * mul);
+                if constexpr (BGR) {
+                  if (x < w) put_bgr(drow, x * g.dx, lut, lut ? v : v * mul);
+                } else {
+                  if (x < w) drow[x * g.dx] = lut ? lut[v] : (uint8_t)(v * mul);
+                }
               }
             }
           }
@@ -1281,6 +1312,8 @@ __global__ __launch_bounds__(64) void png_unfilter_general_kernel(PngArgs a) {
 // grfmt_png.cpp asks for (9797, 19234, 3737 of 32768): 8-bit samples truncated; 16-bit samples rounded, of which the read
 // keeps the high byte (png_set_strip_16 comes behind); with the file's gamma tables (8-bit only: the host refuses the rest)
 // gray = from_linear[(weighted sum of to_linear[r, g, b] + 16384) >> 15] unless r = g = b.
+// BGR: no weighting -- blue, green, red as the file has them (png_set_bgr), the high byte of 16-bit samples (png_set_strip_16).
+template <bool BGR>
 __global__ __launch_bounds__(64) void png_unfilter_rgb_kernel(PngArgs a) {
   const int lane = threadIdx.x;
   const int image = blockIdx.x;
@@ -1340,9 +1373,17 @@ __global__ __launch_bounds__(64) void png_unfilter_rgb_kernel(PngArgs a) {
       const int rows = min(64, h - r0);
       for (int rr = 0; rr < rows; rr++) {
         const uint8_t* src = filt + (size_t)(r0 + rr) * rb1 + 1;
-        uint8_t* out = dst + (size_t)(g.y0 + (r0 + rr) * g.dy) * a.dst_pitch + g.x0;
+        uint8_t* out = dst + (size_t)(g.y0 + (r0 + rr) * g.dy) * a.dst_pitch + g.x0 * (BGR ? 3 : 1);
         for (int x = lane; x < w; x += 64) {
           const uint8_t* px = src + (size_t)x * bpp;
+          if constexpr (BGR) {
+            const int step = planes == 3 ? 1 : 2;  // (16-bit samples: big-endian, the high byte first)
+            uint8_t* o = out + 3 * x * g.dx;
+            o[0] = px[2 * step];
+            o[1] = px[step];
+            o[2] = px[0];
+            continue;
+          }
           uint32_t gray;
           if (planes == 3) {
             const uint32_t r = px[0], gr = px[1], b = px[2];
@@ -1396,9 +1437,11 @@ void vsf_launch_png_decode(const uint8_t* d_blob, const VsfPngPlan& p, int n, in
   a.status_stride = status_stride;
   a.file_status = scratch.file_status;
   hipLaunchKernelGGL(png_inflate_kernel, dim3(n), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(png_unfilter_kernel, dim3(n), dim3(64), 0, s, a);
-  if (p.any_general) hipLaunchKernelGGL(png_unfilter_general_kernel, dim3(n), dim3(64), 0, s, a);
-  if (p.any_rgb) hipLaunchKernelGGL(png_unfilter_rgb_kernel, dim3(n), dim3(64), 0, s, a);
+  // (p.bgr: the same kernels in their three-bytes-a-pixel form; dst_pitch stays a count of bytes)
+  hipLaunchKernelGGL(p.bgr ? png_unfilter_kernel<true> : png_unfilter_kernel<false>, dim3(n), dim3(64), 0, s, a);
+  if (p.any_general)
+    hipLaunchKernelGGL(p.bgr ? png_unfilter_general_kernel<true> : png_unfilter_general_kernel<false>, dim3(n), dim3(64), 0, s, a);
+  if (p.any_rgb) hipLaunchKernelGGL(p.bgr ? png_unfilter_rgb_kernel<true> : png_unfilter_rgb_kernel<false>, dim3(n), dim3(64), 0, s, a);
 }
 
 #ifdef VSF_PNG_STATS

@@ -431,10 +431,12 @@ void free_retired(vsf_ctx* ctx);  // (callers have waited for every stream of th
 // d_dst + i * dst_image_stride, file i's damage in d_status[i * status_stride].  *n_runs (optional): the runs launched.
 // Which staging pair is free is the caller's business (VsfStaging::uploaded).  The caller checks for launch errors.
 // reduces (optional): width x height is the OUTPUT size and file i decodes at 1 / reduces[i] (vsf_plan_runs).
+// out_format: VSF_OUT_GRAY (a byte a pixel: IMREAD_GRAYSCALE) or VSF_OUT_BGR (three, blue first: IMREAD_COLOR; dst_pitch is
+// still bytes) -- what vsf_plan_runs takes in that format is what is decoded.
 vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width,
                        int height, VsfStaging& stage, VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride,
                        int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs = nullptr,
-                       const uint8_t* reduces = nullptr);
+                       const uint8_t* reduces = nullptr, int out_format = VSF_OUT_GRAY);
 vsf_status ensure_match_buffers(vsf_ctx* ctx, int pairs, int rows);
 vsf_status ensure_match_host_staging(vsf_ctx* ctx, int rows);  // (host-pointer, synchronous entry points only)
 vsf_status ensure_residual_buffers(vsf_ctx* ctx, int n_frames);

@@ -52,16 +52,18 @@ vsf_status record_ingest_done(vsf_ctx* ctx) {
   return VSF_OK;
 }
 
-// vsf_jpeg_decode_gray_batch / vsf_png_decode_gray_batch: n_images files of ONE format, asynchronous on the context's stream.
-vsf_status decode_gray_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* files, const size_t* nbytes, int n_images,
-                             int width, int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride,
-                             int reduce = 1) {
+// vsf_jpeg_decode_gray_batch / vsf_png_decode_gray_batch and their _bgr_ siblings: n_images files of ONE format, asynchronous
+// on the context's stream.  out_format = VSF_OUT_BGR: three bytes a pixel, and a row must hold them rounded up to a dword.
+vsf_status decode_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* files, const size_t* nbytes, int n_images,
+                        int width, int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride,
+                        int reduce = 1, int out_format = VSF_OUT_GRAY) {
   VsfErrorScope scope_(ctx);
   if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
   if (!ctx || !files || !nbytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 65535 ||
       height > 65535 || !d_dst)
     return VSF_ERR_INVALID_ARG;
-  if (((uintptr_t)d_dst & 3) || (dst_image_stride & 3) || (dst_row_stride & 3) || dst_row_stride < (size_t)width ||
+  const size_t min_row = out_format == VSF_OUT_BGR ? (3 * (size_t)width + 3) & ~(size_t)3 : (size_t)width;
+  if (((uintptr_t)d_dst & 3) || (dst_image_stride & 3) || (dst_row_stride & 3) || dst_row_stride < min_row ||
       dst_row_stride > 0x7FFFFFFF || dst_image_stride < dst_row_stride * (size_t)height)
     return VSF_ERR_INVALID_ARG;
   const size_t min_bytes = kind == VSF_FILE_JPEG ? 4 : 8;
@@ -75,7 +77,7 @@ vsf_status decode_gray_batch(vsf_ctx* ctx, uint8_t kind, const uint8_t* const* f
   const std::vector<uint8_t> kinds((size_t)n_images, kind), reduces((size_t)n_images, (uint8_t)reduce);
   const vsf_status st = decode_runs(ctx, files, nbytes, kinds.data(), n_images, width, height, stage, ctx->ingest_scratch, d_dst,
                                     dst_image_stride, (int)dst_row_stride, ctx->d_status, 0, ctx->stream, nullptr,
-                                    reduce > 1 ? reduces.data() : nullptr);
+                                    reduce > 1 ? reduces.data() : nullptr, out_format);
   if (st != VSF_OK) return st;  // (refused by the host half: nothing was uploaded or launched)
   ctx->ingest_flip ^= 1;
   VSF_STICKY();
@@ -143,11 +145,12 @@ namespace vsfi {
 
 vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width,
                        int height, VsfStaging& stage, VsfDecodeScratch& scratch, uint8_t* d_dst, size_t dst_image_stride,
-                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs, const uint8_t* reduces) {
+                       int dst_pitch, int32_t* d_status, int status_stride, hipStream_t s, int* n_runs, const uint8_t* reduces,
+                       int out_format) {
   if (n_runs) *n_runs = 0;
   const bool serial = ctx->tuning.jpeg_serial != 0;
   VsfDecodeRuns plan;
-  vsf_status st = vsf_plan_runs(files, nbytes, kinds, n, width, height, serial, &plan, reduces);
+  vsf_status st = vsf_plan_runs(files, nbytes, kinds, n, width, height, serial, &plan, reduces, out_format);
   if (st != VSF_OK || plan.runs.empty()) return st;
   VsfDecodeNeed need;  // the runs decode one after the other on `s`: they share one scratch of the largest need
   for (const VsfDecodeRun& r : plan.runs) {
@@ -157,6 +160,7 @@ vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* 
     need.flags = std::max(need.flags, q.flags);
     need.filtered = std::max(need.filtered, q.filtered);
     need.file_status = std::max(need.file_status, q.file_status);
+    need.planes = std::max(need.planes, q.planes);
   }
   if (plan.total > stage.cap)
     st = grow_staging(ctx, stage, plan.total);
@@ -167,6 +171,7 @@ vsf_status decode_runs(vsf_ctx* ctx, const uint8_t* const* files, const size_t* 
   if (st == VSF_OK) st = grow_decode_scratch(ctx, scratch.flags, scratch.flags_cap, need.flags);
   if (st == VSF_OK) st = grow_decode_scratch(ctx, scratch.filtered, scratch.filtered_cap, need.filtered);
   if (st == VSF_OK) st = grow_decode_scratch(ctx, scratch.file_status, scratch.file_status_cap, need.file_status);
+  if (st == VSF_OK) st = grow_decode_scratch(ctx, scratch.planes, scratch.planes_cap, need.planes);
   if (st != VSF_OK) return st;
   vsf_fill_runs(plan, files, stage.h);  // the one pass over the compressed bytes on the host
   VSF_HIP(hipMemcpyAsync(stage.d, stage.h, plan.total, hipMemcpyHostToDevice, s));
@@ -329,7 +334,7 @@ vsf_status vsf_to_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int width
 vsf_status vsf_jpeg_decode_gray_batch(vsf_ctx* ctx, const uint8_t* const* jpeg, const size_t* nbytes, int n_images,
                                       int width, int height, uint8_t* d_dst, size_t dst_image_stride,
                                       size_t dst_row_stride) {
-  return decode_gray_batch(ctx, VSF_FILE_JPEG, jpeg, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride);
+  return decode_batch(ctx, VSF_FILE_JPEG, jpeg, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride);
 }
 
 // ... and for PNG files: chunks and CRCs on the host, inflate + filters on the device (k_png.hip).  Same staging and the same
@@ -337,7 +342,7 @@ vsf_status vsf_jpeg_decode_gray_batch(vsf_ctx* ctx, const uint8_t* const* jpeg, 
 vsf_status vsf_png_decode_gray_batch(vsf_ctx* ctx, const uint8_t* const* png, const size_t* nbytes, int n_images,
                                      int width, int height, uint8_t* d_dst, size_t dst_image_stride,
                                      size_t dst_row_stride) {
-  return decode_gray_batch(ctx, VSF_FILE_PNG, png, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride);
+  return decode_batch(ctx, VSF_FILE_PNG, png, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride);
 }
 
 // cv::imdecode(msg.data, IMREAD_GRAYSCALE) as the reference calls it (slam_frontend_main.cc:99-100): whatever the payload
@@ -355,8 +360,39 @@ vsf_status vsf_imdecode_gray_batch(vsf_ctx* ctx, const uint8_t* const* files, co
   }
   for (int i0 = 0, i1; i0 < n_images; i0 = i1) {
     i1 = vsf_run_end(kinds.data(), n_images, i0);
-    const vsf_status st = decode_gray_batch(ctx, kinds[i0], files + i0, nbytes + i0, i1 - i0, width, height,
+    const vsf_status st = decode_batch(ctx, kinds[i0], files + i0, nbytes + i0, i1 - i0, width, height,
                                             d_dst + (size_t)i0 * dst_image_stride, dst_image_stride, dst_row_stride);
+    if (st != VSF_OK) return st;
+  }
+  return VSF_OK;
+}
+
+// cv::imdecode(data, cv::IMREAD_COLOR) for PNG files (bag_extract.cc:73 reads a CompressedImage that way): the same chunks,
+// inflate and filters; the last step per pixel is png_set_bgr / png_set_gray_to_rgb in place of png_set_rgb_to_gray.
+vsf_status vsf_png_decode_bgr_batch(vsf_ctx* ctx, const uint8_t* const* png, const size_t* nbytes, int n_images, int width,
+                                    int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride) {
+  return decode_batch(ctx, VSF_FILE_PNG, png, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride, 1, VSF_OUT_BGR);
+}
+
+vsf_status vsf_jpeg_decode_bgr_batch(vsf_ctx* ctx, const uint8_t* const* jpeg, const size_t* nbytes, int n_images, int width,
+                                     int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride) {
+  return decode_batch(ctx, VSF_FILE_JPEG, jpeg, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride, 1, VSF_OUT_BGR);
+}
+
+// ... and whatever the payload is, run by run as vsf_imdecode_gray_batch: the runs in front of one that is refused have been
+// launched and are not undone.
+vsf_status vsf_imdecode_bgr_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images, int width,
+                                  int height, uint8_t* d_dst, size_t dst_image_stride, size_t dst_row_stride) {
+  if (!ctx || !files || !nbytes || n_images < 1 || !d_dst) return VSF_ERR_INVALID_ARG;
+  std::vector<uint8_t> kinds((size_t)n_images);
+  for (int i = 0; i < n_images; i++) {
+    kinds[i] = (uint8_t)vsf_file_kind(files[i], nbytes[i]);
+    if (kinds[i] == VSF_FILE_NONE) return VSF_ERR_UNSUPPORTED;
+  }
+  for (int i0 = 0, i1; i0 < n_images; i0 = i1) {
+    i1 = vsf_run_end(kinds.data(), n_images, i0);
+    const vsf_status st = decode_batch(ctx, kinds[i0], files + i0, nbytes + i0, i1 - i0, width, height,
+                                       d_dst + (size_t)i0 * dst_image_stride, dst_image_stride, dst_row_stride, 1, VSF_OUT_BGR);
     if (st != VSF_OK) return st;
   }
   return VSF_OK;
@@ -376,7 +412,7 @@ vsf_status vsf_imdecode_reduced_gray_batch(vsf_ctx* ctx, const uint8_t* const* f
     const int kind = vsf_file_kind(files[i], nbytes[i]);
     if (kind != VSF_FILE_JPEG) return VSF_ERR_UNSUPPORTED;
   }
-  return decode_gray_batch(ctx, VSF_FILE_JPEG, files, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride,
+  return decode_batch(ctx, VSF_FILE_JPEG, files, nbytes, n_images, width, height, d_dst, dst_image_stride, dst_row_stride,
                            reduce);
 }
 

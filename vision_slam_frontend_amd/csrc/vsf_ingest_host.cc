@@ -28,9 +28,11 @@ int vsf_run_end(const uint8_t* kinds, int n, int i0) {
 // reduces[i] > 1: file i decodes at 1 / reduces[i] into width x height (JPEG only: imdecode would resize a PNG); a run is
 // files of one format AND one denominator.
 vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
-                         bool force_serial, VsfDecodeRuns* out, const uint8_t* reduces) {
+                         bool force_serial, VsfDecodeRuns* out, const uint8_t* reduces, int out_format) {
   out->runs.clear();
   out->total = 0;
+  if (out_format != VSF_OUT_GRAY && out_format != VSF_OUT_BGR) return VSF_ERR_INVALID_ARG;
+  const bool bgr = out_format == VSF_OUT_BGR;
   for (int i0 = 0, i1; i0 < n; i0 = i1) {
     i1 = vsf_run_end(kinds, n, i0);
     if (kinds[i0] == VSF_FILE_NONE) continue;
@@ -46,8 +48,9 @@ vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, cons
     r.kind = kinds[i0];
     r.off = (out->total + 255) & ~(size_t)255;
     if (r.kind == VSF_FILE_PNG && reduce > 1) return VSF_ERR_UNSUPPORTED;
-    const vsf_status st = r.kind == VSF_FILE_JPEG ? vsf_jpeg_plan(files + i0, nbytes + i0, r.n, width, height, force_serial, &r.jp, reduce)
-                                                  : vsf_png_plan(files + i0, nbytes + i0, r.n, width, height, &r.pp);
+    if (bgr && reduce > 1) return VSF_ERR_UNSUPPORTED;  // (no reduced colour decode)
+    const vsf_status st = r.kind == VSF_FILE_JPEG ? vsf_jpeg_plan(files + i0, nbytes + i0, r.n, width, height, force_serial, &r.jp, reduce, bgr)
+                                                  : vsf_png_plan(files + i0, nbytes + i0, r.n, width, height, &r.pp, bgr);
     if (st != VSF_OK) return st;
     out->total = r.off + (r.kind == VSF_FILE_JPEG ? r.jp.total : r.pp.total);
   }

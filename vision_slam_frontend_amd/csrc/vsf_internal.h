@@ -381,10 +381,15 @@ struct VsfJpegPlan {  // layout of one upload: [image descriptors | decode order
   int max_luma_blocks = 0;   // luminance blocks of the (padded) image, largest over the batch
   int max_slots = 1;         // Huffman tables one file's scan uses, largest over the batch
   int reduce = 1;            // the files are decoded at 1 / reduce (1, 2, 4, 8): IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8
+  bool colour = false;       // the files are read as IMREAD_COLOR (vsf_imdecode_bgr_batch): chroma is kept, see k_jpeg.hip
+  size_t off_qt_chroma = 0;  // ... [n][2][64] quantisation tables of components 1 and 2 (in front of the segments)
+  size_t max_plane = 0;      // ... bytes of the largest block-padded luminance plane of the batch
 };
 // width x height: the OUTPUT size; a file of W x H is taken when ceil(W / reduce) == width and ceil(H / reduce) == height.
 vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n, int width, int height, bool force_serial,
-                         VsfJpegPlan* plan, int reduce = 1);
+                         VsfJpegPlan* plan, int reduce = 1, bool colour = false);
+// libjpeg's colour-space decision for three components (jdapimin.c): VSF_OK = YCbCr, VSF_ERR_UNSUPPORTED = it reads RGB.
+vsf_status vsf_jpeg_colourspace(bool saw_jfif, bool saw_adobe, int adobe_transform, const int cid[3]);
 void vsf_jpeg_fill(const VsfJpegPlan& plan, const uint8_t* const* jpeg, int n, uint8_t* dst);
 #endif
 // k_png.hip / vsf_png_host.cc (row f4: cv::imdecode(IMREAD_GRAYSCALE) for grayscale PNG)
@@ -397,8 +402,10 @@ struct VsfPngPlan {  // layout of one upload: [image descriptors | ends of the I
   size_t filtered_stride = 0;  // device scratch per image: the inflated scanlines
   bool any_rgb = false;        // a file of colour type 2 or 6 among them (a kernel of its own)
   bool any_general = false;    // a palette file or an interlaced gray one among them (another)
+  bool bgr = false;            // the files are read as IMREAD_COLOR: three bytes a pixel, blue first (vsf_imdecode_bgr_batch)
 };
-vsf_status vsf_png_plan(const uint8_t* const* png, const size_t* nbytes, int n, int width, int height, VsfPngPlan* plan);
+vsf_status vsf_png_plan(const uint8_t* const* png, const size_t* nbytes, int n, int width, int height, VsfPngPlan* plan,
+                        bool bgr = false);
 void vsf_png_fill(const VsfPngPlan& plan, const uint8_t* const* png, int n, uint8_t* dst);
 #endif
 // ---- one decode path for compressed payloads (the C ABI's decoders and the ObserveImage queue) ----
@@ -410,11 +417,12 @@ struct VsfDecodeScratch {
   vsfi::DevBuf<int32_t> flags;        // JPEG: per progressive file "damaged: decode again scan after scan"
   vsfi::DevBuf<uint8_t> filtered;     // PNG: the inflated scanlines
   vsfi::DevBuf<int32_t> file_status;  // PNG: per file, what its inflate made of the stream
-  size_t clean_cap = 0, coef_cap = 0, flags_cap = 0, filtered_cap = 0, file_status_cap = 0;
-  size_t bytes() const { return clean_cap + coef_cap + flags_cap + filtered_cap + file_status_cap; }
+  vsfi::DevBuf<uint8_t> planes;       // JPEG, colour read: per file the luminance and the two chroma planes in front of the finishing kernel
+  size_t clean_cap = 0, coef_cap = 0, flags_cap = 0, filtered_cap = 0, file_status_cap = 0, planes_cap = 0;
+  size_t bytes() const { return clean_cap + coef_cap + flags_cap + filtered_cap + file_status_cap + planes_cap; }
 };
 struct VsfDecodeNeed {  // bytes of each; the needs of several runs on one stream combine by maximum
-  size_t clean = 0, coef = 0, flags = 0, filtered = 0, file_status = 0;
+  size_t clean = 0, coef = 0, flags = 0, filtered = 0, file_status = 0, planes = 0;
 };
 // Pinned staging + its device copy for ONE upload.  `uploaded` (optional): recorded behind the upload, and waited for before
 // the host writes the pair again -- an owner that knows the pair to be free by other means leaves it null.
@@ -439,6 +447,7 @@ void vsf_launch_png_decode(const uint8_t* d_blob, const VsfPngPlan& plan, int n,
 
 // vsf_ingest_host.cc (plain C++, no HIP call): what a list of files is, and the host half of decoding it.
 enum { VSF_FILE_NONE = 0, VSF_FILE_JPEG = 1, VSF_FILE_PNG = 2 };  // (ObserveFrame::kind: 0 is the raw frame there)
+enum { VSF_OUT_GRAY = 0, VSF_OUT_BGR = 1 };  // what a decode writes: cv::IMREAD_GRAYSCALE's byte or cv::IMREAD_COLOR's three
 int vsf_file_kind(const uint8_t* file, size_t nbytes);  // by the first bytes, as cv::imdecode's findDecoder tells them apart
 int vsf_run_end(const uint8_t* kinds, int n, int i0);   // one past the last file of the run of one kind that starts at i0
 // The denominators a decode takes, stated ONCE: 1 (full size) and cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8.
@@ -459,8 +468,10 @@ struct VsfDecodeRuns {
 // denominator changes, so one upload carries files of several.  reduces[i] > 1 (2, 4, 8) with a PNG file is
 // VSF_ERR_UNSUPPORTED (cv::imdecode decodes a PNG at full size and calls cv::resize, which is not built here); a value
 // outside {1, 2, 4, 8} VSF_ERR_INVALID_ARG.
+// out_format = VSF_OUT_BGR (cv::IMREAD_COLOR): the files are planned for three bytes a pixel at full size (JPEG files keep
+// their chroma: vsf_jpeg_plan's `colour`); a denominator above 1 is VSF_ERR_UNSUPPORTED in that format.
 vsf_status vsf_plan_runs(const uint8_t* const* files, const size_t* nbytes, const uint8_t* kinds, int n, int width, int height,
-                         bool force_serial, VsfDecodeRuns* out, const uint8_t* reduces = nullptr);
+                         bool force_serial, VsfDecodeRuns* out, const uint8_t* reduces = nullptr, int out_format = VSF_OUT_GRAY);
 void vsf_fill_runs(const VsfDecodeRuns& plan, const uint8_t* const* files, uint8_t* dst);
 // ---- one encode path for JPEG / PNG files (the C ABI's encoders and the ObserveImage queue's debug files) ----
 // cv::imencode(".jpg", img, {IMWRITE_JPEG_QUALITY, quality}) / cv::imencode(".png", img) of n equally sized images: image i

@@ -250,6 +250,16 @@ static bool baseline_tail_ok(const uint8_t* p, size_t n, int restart_interval, s
   return true;
 }
 
+// libjpeg's colour-space decision for a three-component file (jdapimin.c default_decompress_parms): VSF_OK for YCbCr,
+// VSF_ERR_UNSUPPORTED for a file it reads as RGB (never a guess: such a file would need no conversion, which is not built).
+// An Adobe transform flag other than 0 or 1 is read as YCbCr with a warning, as are component ids it does not know (a trace).
+vsf_status vsf_jpeg_colourspace(bool saw_jfif, bool saw_adobe, int adobe_transform, const int cid[3]) {
+  if (saw_jfif) return VSF_OK;
+  if (saw_adobe) return adobe_transform == 0 ? VSF_ERR_UNSUPPORTED : VSF_OK;
+  if (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B') return VSF_ERR_UNSUPPORTED;
+  return VSF_OK;
+}
+
 // Parses one JPEG file; fills the image descriptor (without stream_off / tables) and the table set it needs.
 // Returns VSF_OK, VSF_ERR_INVALID_ARG (malformed, or not width x height) or VSF_ERR_UNSUPPORTED.
 // reduce = d > 1 (IMREAD_REDUCED_GRAYSCALE_d): width x height is the OUTPUT size, and the file's own W x H must reduce to it
@@ -259,18 +269,30 @@ static bool baseline_tail_ok(const uint8_t* p, size_t n, int restart_interval, s
 // `prog` with the Huffman tables in force when it starts; scans of chroma alone are stepped over.  The progression must be
 // the orderly one (each scan continues where the last one over the same coefficients stopped) and must end with every
 // luminance coefficient at full precision: anything else libjpeg answers with an approximation, and is refused here.
+// colour (cv::IMREAD_COLOR: out_color_space = JCS_RGB): a three-component file must be one libjpeg reads as YCbCr
+// (jdapimin.c default_decompress_parms: a JFIF marker; else the Adobe marker's transform flag; else the component ids), with
+// chroma factors that divide the luminance's (jdsample.c: anything else is JERR_FRACT_SAMPLE_NOTIMPL -> VSF_ERR_INVALID_ARG);
+// qt_chroma receives the quantisation tables of components 1 and 2 (natural order), each as it stood at the component's first
+// scan.  In several scans EVERY scan is listed in `prog` and every component must reach full precision.  A file libjpeg reads as
+// RGB (Adobe transform 0, ids 'R' 'G' 'B') is VSF_ERR_UNSUPPORTED.
 static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int height, int reduce, DevImage* im,
-                             HostTableSet* tab, size_t* scan_begin, ProgFile* prog) {
+                             HostTableSet* tab, size_t* scan_begin, ProgFile* prog, bool colour = false,
+                             uint16_t* qt_chroma = nullptr) {
   if (!data || nbytes < 4 || data[0] != 0xFF || data[1] != 0xD8) return VSF_ERR_INVALID_ARG;
   uint16_t qt[4][64];
   bool qt_present[4] = {false, false, false, false};
   HostHuff dc[4], ac[4];
   int ncomp = 0, cid[3], ch[3], cv[3], ctq[3], W = 0, H = 0, restart_interval = 0;
   bool have_sof = false, progressive = false, yq_latched = false;
+  bool saw_jfif = false, saw_adobe = false;
+  int adobe_transform = 0;
   bool multiscan = false;  // a sequential frame whose components come in several scans: its scans are listed like progressive ones
   uint16_t yq[64];
-  int cbits[64];  // progressive: precision still missing per luminance coefficient (-1: nothing received yet)
-  for (int& b : cbits) b = -1;
+  int cbits[3][64];  // progressive: precision still missing per coefficient of each component (-1: nothing received yet); a gray
+  for (auto& row : cbits)  // read follows the luminance's alone
+    for (int& b : row) b = -1;
+  const bool colour3 = colour;  // (with three components: every scan is listed, and every component must reach full precision)
+  bool qc_latched[3] = {false, false, false};
   size_t pos = 2;
   std::memset(im, 0, sizeof(*im));
   prog->scans.clear();
@@ -291,6 +313,10 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
     const uint8_t* s = data + pos + 2;
     const size_t n = len - 2;
     if (m == 0xDA && have_sof && !progressive && n >= 1 && s[0] != ncomp) multiscan = true;
+    if (m == 0xDA && colour && have_sof && ncomp == 3) {  // the colour space is settled at the first scan header
+      const vsf_status cs = vsf_jpeg_colourspace(saw_jfif, saw_adobe, adobe_transform, cid);
+      if (cs != VSF_OK) return cs;
+    }
     if (m == 0xDB) {
       for (size_t i = 0; i < n;) {
         const int pq = s[i] >> 4, tq = s[i] & 15;
@@ -334,6 +360,13 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
       have_sof = true;
     } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       return VSF_ERR_UNSUPPORTED;  // lossless, arithmetic, hierarchical
+    } else if (m == 0xE0) {  // jdmarker.c examine_app0: "JFIF\0" in a segment of at least 14 data bytes
+      if (n >= 14 && std::memcmp(s, "JFIF\0", 5) == 0) saw_jfif = true;
+    } else if (m == 0xEE) {  // examine_app14: "Adobe" in a segment of at least 12 data bytes; byte 11 is the transform flag
+      if (n >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
+        saw_adobe = true;
+        adobe_transform = s[11];
+      }
     } else if (m == 0xDD) {
       if (n < 2) return VSF_ERR_INVALID_ARG;
       restart_interval = (s[0] << 8) | s[1];
@@ -372,13 +405,24 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
         if ((Ah != 0 && Al != Ah - 1) || Al > 13) return VSF_ERR_INVALID_ARG;
       }
       const size_t begin = pos + len, end = ecs_end(data, begin, nbytes);
-      if (has_luma) {
-        for (int k = Ss; k <= Se; k++) {
-          if (Ah != (cbits[k] < 0 ? 0 : cbits[k]) || (cbits[k] >= 0 && Ah == 0)) return VSF_ERR_UNSUPPORTED;
-          cbits[k] = Al;
+      const bool listed = has_luma || (colour3 && ncomp == 3);
+      if (listed) {
+        for (int c = 0; c < ns; c++) {
+          const int ci = sc.comp[c];
+          if (ci != 0 && !(colour3 && ncomp == 3)) continue;  // (a gray read: chroma beside the luminance is parsed and dropped)
+          int* cb = cbits[ci];
+          for (int k = Ss; k <= Se; k++) {
+            if (Ah != (cb[k] < 0 ? 0 : cb[k]) || (cb[k] >= 0 && Ah == 0)) return VSF_ERR_UNSUPPORTED;
+            cb[k] = Al;
+          }
+          if (Ss > 0 && cb[0] < 0) return VSF_ERR_UNSUPPORTED;  // AC before any DC scan
+          if (ci != 0 && !qc_latched[ci]) {  // latch_quant_tables, for a chroma component
+            if (!qt_present[ctq[ci]]) return VSF_ERR_INVALID_ARG;
+            if (qt_chroma) std::memcpy(qt_chroma + 64 * (ci - 1), qt[ctq[ci]], 64 * sizeof(uint16_t));
+            qc_latched[ci] = true;
+          }
         }
-        if (Ss > 0 && cbits[0] < 0) return VSF_ERR_UNSUPPORTED;  // AC before any DC scan
-        if (!yq_latched) {  // jdinput.c latch_quant_tables: the table in force at the component's first scan
+        if (has_luma && !yq_latched) {  // jdinput.c latch_quant_tables: the table in force at the component's first scan
           if (!qt_present[ctq[0]]) return VSF_ERR_INVALID_ARG;
           std::memcpy(yq, qt[ctq[0]], sizeof(yq));
           yq_latched = true;
@@ -440,6 +484,12 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
       }
       if (ncomp > 1 && (ch[0] != hmax || cv[0] != vmax)) return VSF_ERR_UNSUPPORTED;  // luminance would need upsampling
       if ((W + reduce - 1) / reduce != width || (H + reduce - 1) / reduce != height) return VSF_ERR_INVALID_ARG;
+      if (colour && ncomp == 3) {
+        for (int c = 1; c < 3; c++) {
+          if (hmax % ch[c] != 0 || vmax % cv[c] != 0) return VSF_ERR_INVALID_ARG;  // JERR_FRACT_SAMPLE_NOTIMPL
+          if (qt_chroma) std::memcpy(qt_chroma + 64 * (c - 1), qt[ctq[c]], 64 * sizeof(uint16_t));
+        }
+      }
       const bool single = ncomp == 1;  // T.81 A.2.2: a one-component scan has one block per MCU
       const int mw = single ? 8 : 8 * hmax, mh = single ? 8 : 8 * vmax;
       if (!single && hmax * vmax > kGroupBlocks) return VSF_ERR_UNSUPPORTED;
@@ -469,8 +519,9 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
     pos += len;
   }
   if (!(progressive || multiscan) || !have_sof || prog->scans.empty() || !yq_latched) return VSF_ERR_INVALID_ARG;
-  for (int k = 0; k < 64; k++)
-    if (cbits[k] != 0) return VSF_ERR_UNSUPPORTED;  // the scans stop short of full precision
+  for (int c = 0; c < (colour3 && ncomp == 3 ? 3 : 1); c++)
+    for (int k = 0; k < 64; k++)
+      if (cbits[c][k] != 0) return VSF_ERR_UNSUPPORTED;  // the scans stop short of full precision (a colour read: in any component)
   {
     int hmax = 1, vmax = 1;
     for (int c = 0; c < ncomp; c++) {
@@ -479,6 +530,9 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
     }
     if (ch[0] != hmax || cv[0] != vmax) return VSF_ERR_UNSUPPORTED;  // luminance would need upsampling
     if ((W + reduce - 1) / reduce != width || (H + reduce - 1) / reduce != height) return VSF_ERR_INVALID_ARG;
+    if (colour3 && ncomp == 3)
+      for (int c = 1; c < 3; c++)
+        if (hmax % ch[c] != 0 || vmax % cv[c] != 0) return VSF_ERR_INVALID_ARG;  // JERR_FRACT_SAMPLE_NOTIMPL
     // the coefficient buffer is laid out as the frame's interleaved MCUs (what the IDCT kernel walks): for a gray frame that
     // is one block per MCU whatever its sampling factors say
     const bool single = ncomp == 1;
@@ -504,9 +558,13 @@ static vsf_status parse_jpeg(const uint8_t* data, size_t nbytes, int width, int 
 // distinct table sets (consecutive frames of a camera share theirs: compared with the previous file's first), packed
 // entropy-coded segments -- without touching the segments themselves.
 vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n, int width, int height, bool force_serial,
-                         VsfJpegPlan* plan, int reduce) {
+                         VsfJpegPlan* plan, int reduce, bool colour) {
   if (!vsf_reduce_ok(reduce)) return VSF_ERR_INVALID_ARG;
+  if (colour && reduce != 1) return VSF_ERR_UNSUPPORTED;
   plan->reduce = reduce;
+  plan->colour = colour;
+  plan->max_plane = 0;
+  std::vector<uint16_t> qt_chroma(colour ? (size_t)n * 128 : 0, 0);  // per file: the tables of components 1 and 2
   std::vector<DevImage> images((size_t)n);
   std::vector<DevTables> tables;
   std::vector<HostTableSet> sets;
@@ -520,8 +578,10 @@ vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n
   size_t stream_bytes = 0;
   for (int i = 0; i < n; i++) {
     HostTableSet t;
-    const vsf_status st = parse_jpeg(jpeg[i], nbytes[i], width, height, reduce, &images[i], &t, &plan->scan_begin[i], &prog);
+    const vsf_status st = parse_jpeg(jpeg[i], nbytes[i], width, height, reduce, &images[i], &t, &plan->scan_begin[i], &prog, colour,
+                                     colour ? qt_chroma.data() + (size_t)i * 128 : nullptr);
     if (st != VSF_OK) return st;
+    plan->max_plane = std::max(plan->max_plane, (size_t)images[i].mcus_x * images[i].h[0] * 8 * (size_t)images[i].mcus_y * images[i].v[0] * 8);
     if (images[i].n_scans > 0) {
       images[i].first_scan = (uint32_t)scans.size();
       const uint32_t huff0 = (uint32_t)prog_huff.size();
@@ -620,7 +680,8 @@ vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n
   plan->off_tables = (plan->off_index + index.size() * sizeof(uint32_t) + 15) & ~(size_t)15;
   plan->off_scans = (plan->off_tables + tables.size() * sizeof(DevTables) + 15) & ~(size_t)15;
   plan->off_prog_huff = (plan->off_scans + scans.size() * sizeof(DevScan) + 15) & ~(size_t)15;
-  plan->off_stream = (plan->off_prog_huff + prog_huff.size() * sizeof(DevHuffSrc) + 15) & ~(size_t)15;
+  plan->off_qt_chroma = (plan->off_prog_huff + prog_huff.size() * sizeof(DevHuffSrc) + 15) & ~(size_t)15;
+  plan->off_stream = (plan->off_qt_chroma + qt_chroma.size() * sizeof(uint16_t) + 15) & ~(size_t)15;
   plan->n_prog_huff = (int)prog_huff.size();
   plan->total = plan->off_stream + stream_bytes + 16;
   plan->head.assign(plan->off_stream, 0);
@@ -629,6 +690,7 @@ vsf_status vsf_jpeg_plan(const uint8_t* const* jpeg, const size_t* nbytes, int n
   std::memcpy(plan->head.data() + plan->off_tables, tables.data(), tables.size() * sizeof(DevTables));
   if (!scans.empty()) std::memcpy(plan->head.data() + plan->off_scans, scans.data(), scans.size() * sizeof(DevScan));
   if (!prog_huff.empty()) std::memcpy(plan->head.data() + plan->off_prog_huff, prog_huff.data(), prog_huff.size() * sizeof(DevHuffSrc));
+  if (!qt_chroma.empty()) std::memcpy(plan->head.data() + plan->off_qt_chroma, qt_chroma.data(), qt_chroma.size() * sizeof(uint16_t));
   plan->stream_off.resize((size_t)n);
   plan->stream_len.resize((size_t)n);
   for (int i = 0; i < n; i++) {

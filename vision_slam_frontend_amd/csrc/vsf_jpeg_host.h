@@ -59,8 +59,8 @@ struct DevHuffLite {             // what the one-wave decoders read of a table (
 static_assert(sizeof(DevHuffSrc) == 276 && sizeof(DevHuffLite) == 1024 + 72 + 68 + 256, "progressive table layouts");
 
 // One scan of a progressive file (T.81 Annex G) -- or of a sequential file whose components come in several scans: then
-// Ss = 0, Se = 63 and a block is decoded whole (F.2.2) -- as the device walks it.  Only scans with the luminance component
-// are listed: scans of chroma alone never touch what a gray read returns.
+// Ss = 0, Se = 63 and a block is decoded whole (F.2.2) -- as the device walks it.  A gray read lists only the scans
+// with the luminance component (scans of chroma alone never touch what it returns), a colour read every scan.
 struct DevScan {
   uint32_t off, len;             // its entropy-coded segment, relative to the image's stream_off
   int32_t restart_interval;      // as the last DRI in front of the scan set it

@@ -84,7 +84,10 @@ uint8_t rgb_to_gray8(uint32_t r, uint32_t g, uint32_t b, const uint8_t* to_1, co
   return from_1[(kRc * to_1[r] + kGc * to_1[g] + kBc * to_1[b] + 16384) >> 15];
 }
 
-vsf_status parse_png(const uint8_t* f, size_t n, int width, int height, DevImage* im, std::vector<Piece>* pieces,
+// bgr: the read is cv::imdecode(IMREAD_COLOR)'s -- png_set_bgr / png_set_gray_to_rgb in place of png_set_rgb_to_gray.  Nothing
+// then asks libpng for a gamma transform, so gAMA / sRGB / iCCP / cHRM are the ancillary chunks they are to every other read, and a
+// palette file's table holds its entries as they are: 256 x (blue, green, red).
+vsf_status parse_png(const uint8_t* f, size_t n, int width, int height, bool bgr, DevImage* im, std::vector<Piece>* pieces,
                      std::vector<uint8_t>* table) {
   pieces->clear();
   table->clear();
@@ -192,7 +195,7 @@ vsf_status parse_png(const uint8_t* f, size_t n, int width, int height, DevImage
       }
       continue;
     }
-    if (colour) {  // what decides whether rgb_to_gray works on the samples as they are (pngrutil.c png_handle_gAMA / sRGB / iCCP)
+    if (colour && !bgr) {  // what decides whether rgb_to_gray works on the samples as they are (pngrutil.c png_handle_gAMA / sRGB / iCCP)
       const bool in_place = !have_plte && !have_idat;
       if (std::memcmp(type, "gAMA", 4) == 0) {
         if (!in_place || len != 4) continue;  // "out of place" / "invalid": skipped
@@ -240,7 +243,13 @@ vsf_status parse_png(const uint8_t* f, size_t n, int width, int height, DevImage
   // for an image of this size; a smaller declared window is refused here rather than decoded more leniently than libpng.
   if ((hdr[0] >> 4) < 7) return VSF_ERR_UNSUPPORTED;
   im->stream_len = (uint32_t)stream_len;
-  if (colour) {
+  if (colour && bgr) {
+    if (im->kind == kPalette) {  // (entries the file does not define are black: libpng's palette is 256 zeroed entries)
+      table->assign(3 * 256, 0);
+      for (uint32_t i = 0; i < plte_entries; i++)
+        for (int c = 0; c < 3; c++) (*table)[3 * i + c] = plte[3 * i + 2 - c];
+    }
+  } else if (colour) {
     if (unsupported_colourspace || n_iccp > 0 || n_gama > 1 || n_srgb > 1 || (odd_chrm && n_gama + n_srgb > 0)) return VSF_ERR_UNSUPPORTED;
     // png_init_read_transformations: the screen's gamma defaults to the reciprocal of the file's; tables are built when either
     // is "significant"
@@ -271,7 +280,8 @@ vsf_status parse_png(const uint8_t* f, size_t n, int width, int height, DevImage
 }  // namespace
 
 // Step 1: every file's chunks (CRC pass included, a few threads when there is enough of it).
-vsf_status vsf_png_plan(const uint8_t* const* png, const size_t* nbytes, int n, int width, int height, VsfPngPlan* plan) {
+vsf_status vsf_png_plan(const uint8_t* const* png, const size_t* nbytes, int n, int width, int height, VsfPngPlan* plan, bool bgr) {
+  plan->bgr = bgr;
   std::vector<DevImage> images((size_t)n);
   std::vector<std::vector<Piece>> pieces((size_t)n);
   std::vector<std::vector<uint8_t>> tables((size_t)n);
@@ -279,7 +289,7 @@ vsf_status vsf_png_plan(const uint8_t* const* png, const size_t* nbytes, int n, 
   auto parse_range = [&](int i0, int i1) {
     for (int i = i0; i < i1; i++) {
       std::memset(&images[i], 0, sizeof(DevImage));
-      status[i] = parse_png(png[i], nbytes[i], width, height, &images[i], &pieces[i], &tables[i]);
+      status[i] = parse_png(png[i], nbytes[i], width, height, bgr, &images[i], &pieces[i], &tables[i]);
     }
   };
   size_t all = 0;
