@@ -71,7 +71,14 @@ typedef struct {
    * frame-latency chain and the image-major tail are not taken, every level is one launch of the general resize kernel. */
   float scale_factor;
   int32_t nlevels;        /* 50 (<= VSF_MAX_LEVELS) */
-  int32_t edge_threshold; /* 31 */
+  /* 31.  Any value >= 22: keypoints sit at edge_threshold <= x < w - edge_threshold, edge_threshold <= y < h - edge_threshold
+   * of their level (runByImageBorder).  22 is the reach of what is read around a keypoint (the rotated pattern, 19, on a
+   * level blurred over 3 more pixels; the IC-angle disc reaches 15, Harris 4): the borders of a level are not
+   * materialised, so vsf_create returns VSF_ERR_UNSUPPORTED below it.  A level no larger than 2 * edge_threshold in either
+   * direction has no keypoints, as in the reference.  A border of at least half the image leaves every level empty: such a
+   * context is created all the same, and every call on it returns VSF_OK with zero counts and writes no keypoint or
+   * descriptor.  (tests/test_gpu_edge_threshold.py) */
+  int32_t edge_threshold;
   int32_t first_level;    /* 0 (only value supported) */
   int32_t wta_k;          /* 2 (only value supported) */
   int32_t score_type;     /* 0 = cv::ORB::HARRIS_SCORE (only value supported) */

@@ -100,11 +100,12 @@ def _u8img(img: np.ndarray) -> np.ndarray:
 
 
 def orb_params(nfeatures: int = 10000, fast_threshold: int = 20, nlevels: int = 50, scale_factor: float = 1.04,
-               blur_sse2: int = 1) -> OrbParams:
+               blur_sse2: int = 1, edge_threshold: int = 31) -> OrbParams:
     p = OrbParams()
     lib().vsfo_orb_params_default(C.byref(p))
     p.nfeatures, p.fast_threshold, p.nlevels, p.blur_sse2 = nfeatures, fast_threshold, nlevels, blur_sse2
     p.scale_factor = scale_factor
+    p.edge_threshold = edge_threshold
     return p
 
 

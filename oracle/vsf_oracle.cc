@@ -512,10 +512,13 @@ void OrbDescriptor(const Level& L, const vsfo_keypoint& kp, uint8_t desc[32]) {
 int OrbRun(vsfo_orb* o, const uint8_t* img, int w, int h, size_t stride) {
   const vsfo_orb_params& p = o->p;
   if (p.first_level != 0 || p.wta_k != 2 || p.score_type != 0 || p.patch_size != 31 || p.nlevels < 1) return -1;
+  if (p.edge_threshold < 22) return -1;  // (the borders below are not materialised)
   Layout(o, w, h);
   const int nlevels = p.nlevels;
   // Pyramid: level 0 is the image; level l is resize(level l-1 interior). Borders are never read by any
-  // output (edgeThreshold 31 > Harris 4 / IC 15 / descriptor 19+3), so they are not materialised.
+  // output while edgeThreshold >= 22 (Harris 4 / IC 15 / descriptor 19+3: the rotated pattern reaches 19 pixels on a
+  // level blurred over 3 more), so they are not materialised.  tests/cpp/test_oracle_border.cc runs 22 and 25 under
+  // AddressSanitizer, every level in a heap block of its own.
   for (int l = 0; l < nlevels; l++) {
     Level& L = o->levels[l];
     if (L.w < 1 || L.h < 1) return -2;

@@ -39,7 +39,7 @@ typedef struct {
   int32_t nfeatures;      /* 10000 in the reference; 2000 / 8000 in BASELINE configs */
   float scale_factor;     /* 1.04f */
   int32_t nlevels;        /* 50 */
-  int32_t edge_threshold; /* 31 */
+  int32_t edge_threshold; /* 31; vsfo_orb_run refuses values below 22 (borders are not materialised) */
   int32_t first_level;    /* 0 (only 0 is supported) */
   int32_t wta_k;          /* 2 (only 2 is supported) */
   int32_t score_type;     /* 0 = HARRIS_SCORE (only) */

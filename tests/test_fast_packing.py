@@ -14,6 +14,9 @@ PACK_WORDS = 4 + 2 * PACK_SEGS
 
 SIZES = [(640, 480), (1920, 1080), (97, 71), (1283, 727), (333, 257), (161, 131), (100, 75), (64, 64), (801, 601),
          (1001, 99), (99, 1001), (515, 322), (1279, 719), (2047, 1535)]
+# edge_threshold: 22 is the least vsf_create accepts; 22 .. 25 give fast_a0 = x_lo & ~3 every residue of x_lo & 3 (31 has 3,
+# as has the stand-alone detector's border of 3); 26, 40 and 64 repeat residues 2, 0 and 0 with other band and strip counts
+BORDERS = [22, 23, 24, 25, 26, 31, 40, 64]
 
 
 @pytest.fixture(scope="module")
@@ -87,12 +90,57 @@ def issued_lane_steps(levels, full, packs):
     return n + sum(64 * (int(it[1]) + 2) for it in packs)
 
 
-@pytest.mark.parametrize("w,h", SIZES)
-def test_orb_cells_packed_once(capi, w, h):
-    p = capi.default_params(w, h)
+def check_levels(levels, p, border):
+    """The level table against the rule of runByImageBorder, from the image size and the border alone."""
+    for l, lv in enumerate(levels):
+        w, h, x_lo, x_hi, y_lo, y_hi, a0, nbands, nstrips = (int(v) for v in lv[:9])
+        if w <= 2 * border or h <= 2 * border:
+            assert nbands * nstrips == 0 and x_hi - x_lo <= 0 and y_hi - y_lo <= 0, "level %d (%d x %d) is empty" % (l, w, h)
+            continue
+        assert (x_lo, x_hi, y_lo, y_hi) == (border, w - border, border, h - border), l
+        assert a0 == border & ~3 and a0 <= x_lo < a0 + 4
+        assert nbands == -(-(x_hi - a0) // BAND) and nstrips == -(-(y_hi - y_lo) // SR)
+    assert (int(levels[0][0]), int(levels[0][1])) == (p.width, p.height)
+
+
+def packed_once(capi, w, h, border):
+    p = capi.default_params(w, h, edge_threshold=border)
+    assert p.edge_threshold == border
     full, packs, levels = work(capi, p)
+    check_levels(levels, p, border)
     check(levels, full, packs)
     assert all(int(it[3]) == 0 for it in packs)  # the ORB border keeps every score row off FAST's rim
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+def test_orb_cells_packed_once(capi, w, h):
+    packed_once(capi, w, h, 31)
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("border", [b for b in BORDERS if b != 31])
+def test_orb_cells_packed_once_at_other_borders(capi, w, h, border):
+    packed_once(capi, w, h, border)
+
+
+@pytest.mark.parametrize("border", [120, 200])
+def test_every_level_empty(capi, border):
+    """A border of at least half the image: no level has a cell, the work list is empty, and that is VSF_OK (work() asserts it)."""
+    p = capi.default_params(320, 240, edge_threshold=border)
+    full, packs, levels = work(capi, p)
+    assert len(full) == 0 and len(packs) == 0 and len(levels) == p.nlevels
+    check_levels(levels, p, border)
+    assert not levels[:, 7].any() and not levels[:, 8].any()
+    assert check(levels, full, packs) == {}
+
+
+def test_one_narrow_cell(capi):
+    """320x240 at border 119: level 0 keeps 82 x 2 pixels, one narrow cell alone in its wave, and no other level has any."""
+    p = capi.default_params(320, 240, edge_threshold=119)
+    full, packs, levels = work(capi, p)
+    check_levels(levels, p, 119)
+    assert check(levels, full, packs) == {(0, 0, 0): 1}
+    assert len(full) == 1 and len(packs) == 0 and cell_shape(levels[0], 0, 0) == ((201 - 116 + 3) // 4 + 2, 2)
 
 
 @pytest.mark.parametrize("w,h", SIZES)
@@ -112,11 +160,11 @@ STEEP_SIZES = ((640, 480), (267, 203), (97, 61))
 def test_other_pyramids(capi):
     for kw in (dict(nlevels=8, scale_factor=1.2), dict(nlevels=1), dict(nlevels=20, scale_factor=1.1)):
         for w, h in ((640, 480), (333, 257), (1920, 1080)):
-            p = capi.default_params(w, h)
-            for k, v in kw.items():
-                setattr(p, k, v)
-            full, packs, levels = work(capi, p)
-            check(levels, full, packs)
+            for border in (31, 22, 25):
+                p = capi.default_params(w, h, edge_threshold=border, **kw)
+                full, packs, levels = work(capi, p)
+                check_levels(levels, p, border)
+                check(levels, full, packs)
     for kw in STEEP:
         for w, h in STEEP_SIZES + ((333, 217),) * (kw["scale_factor"] == 1.7):
             p = capi.default_params(w, h)
@@ -139,14 +187,23 @@ def test_refused_pyramids(capi, w, h, nlevels, scale):
     assert st == capi.VSF_ERR_INVALID_ARG
 
 
-def test_sweep_reaches_short_last_strips_and_mixed_waves(capi):
+def sweep_reaches(capi, border):
     rows_seen, mixed = set(), 0
     for w, h in SIZES:
-        full, packs, levels = work(capi, capi.default_params(w, h))
+        full, packs, levels = work(capi, capi.default_params(w, h, edge_threshold=border))
         for it in packs:
             mixed += int(it[2])
             rows_seen |= {int(it[5 + 2 * k]) >> 16 for k in range(int(it[0]))}
     assert {1, 2} <= rows_seen and mixed > 0
+
+
+def test_sweep_reaches_short_last_strips_and_mixed_waves(capi):
+    sweep_reaches(capi, 31)
+
+
+@pytest.mark.parametrize("border", [b for b in BORDERS if b != 31])
+def test_sweep_reaches_them_at_other_borders(capi, border):
+    sweep_reaches(capi, border)
 
 
 def test_packing_lowers_issued_lanes_at_640x480(capi):

@@ -1,7 +1,7 @@
 """Where FAST's list of full cells is cut for VSF_OPT_FAST_EARLY_LEVELS (csrc/vsf_fast_split.h, one plain function the host
 and this test share), on the CPU: tests/cpp/test_fast_split.cc checks it for every number of early levels against the
 work lists the library itself builds (vsf_debug_fast_work, no device needed) for 640x480, 1920x1080 and the 352x160 of
-tests/test_gpu_fast_split.py -- the head holds exactly the full-width cells of the early levels, n_early(0) == 0, n_early
+tests/test_gpu_fast_split.py, each at every edge_threshold of BORDERS -- the head holds exactly the full-width cells of the early levels, n_early(0) == 0, n_early
 is monotone -- and once more as a stand-alone program under AddressSanitizer / UBSan."""
 import ctypes as C
 import subprocess
@@ -14,6 +14,10 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 SRC = ROOT / "tests" / "cpp" / "test_fast_split.cc"
 SHAPES = [(640, 480), (1920, 1080), (352, 160), (160, 120)]
+# edge_threshold (tests/test_fast_packing.py BORDERS): every residue of x_lo & 3, and borders that move the last level with a
+# full-width cell; 120 leaves 160x120 without a cell at all
+BORDERS = [31, 22, 23, 24, 25, 26, 40, 64, 120]
+CASES = [(w, h, b) for b in BORDERS for w, h in SHAPES]
 
 
 @pytest.fixture(scope="module")
@@ -28,9 +32,9 @@ def capi():
 
 @pytest.fixture(scope="module")
 def lists(capi, tmp_path_factory):
-    lines = [str(len(SHAPES))]
-    for w, h in SHAPES:
-        p = capi.default_params(w, h)
+    lines = [str(len(CASES))]
+    for w, h, border in CASES:
+        p = capi.default_params(w, h, edge_threshold=border)
         cap = 1 << 20
         words = np.zeros(cap, np.uint32)
         levels = np.zeros((64, 10), np.int32)
@@ -76,7 +80,7 @@ def test_cut_for_every_number_of_early_levels(lists, tmp_path):
     r = subprocess.run(["g++", "-O1", "-std=c++17", "-o", str(exe), str(SRC)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     p = subprocess.run([str(exe), str(lists)], capture_output=True, text=True, timeout=60)
-    assert p.returncode == 0 and p.stdout.startswith("ok %d shapes" % len(SHAPES)), (p.stdout[-2000:], p.stderr[-2000:])
+    assert p.returncode == 0 and p.stdout.startswith("ok %d shapes" % len(CASES)), (p.stdout[-2000:], p.stderr[-2000:])
 
 
 def test_cut_under_sanitizers(lists, tmp_path):

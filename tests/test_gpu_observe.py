@@ -12,15 +12,19 @@ F_RECT = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)
 POINT_RTOL, PIXEL_ATOL = 1e-5, 1e-4
 
 
-def _follow_reference_sequence(oracle, frames, width, height, NF, LIFE, F=F_RECT, order=0, max_keypoints=0, results=None):
+def _follow_reference_sequence(oracle, frames, width, height, NF, LIFE, F=F_RECT, order=0, max_keypoints=0, results=None,
+                               edge_threshold=31):
     """Runs `frames` [(left, right)] through vsf_observe_stereo and through the reference's sequence on the oracle, frame by
     frame; returns the context (still open), the calibration and the per-frame feature counts.  F: the fundamental matrix;
     order: vsf_params::residual_order (the oracle follows it); max_keypoints: the context's capacity (0: the default);
-    results: the observations to check, one per frame, instead of the synchronous calls' (a queue's, say)."""
+    results: the observations to check, one per frame, instead of the synchronous calls' (a queue's, say); edge_threshold:
+    vsf_params::edge_threshold (the oracle follows it)."""
     from vision_slam_frontend_amd import capi, frontend
     calib = frontend.default_calibration().set("fundamental", F)
     bp = float(np.float32(0.3))
     over = dict(max_keypoints=max_keypoints) if max_keypoints else {}
+    if edge_threshold != 31:
+        over["edge_threshold"] = edge_threshold
     ctx = capi.Context(capi.default_params(width, height, max_images=2, nfeatures=NF, residual_order=order, **over))
     thr = np.float32(10000.0)
     window = []  # filtered left descriptors of the kept frames, oldest first
@@ -30,7 +34,7 @@ def _follow_reference_sequence(oracle, frames, width, height, NF, LIFE, F=F_RECT
         for fid, (left, right) in enumerate(frames):
             got = results[fid] if results is not None else ctx.observe_stereo(left, right, calib, best_percent=bp, frame_life=LIFE)
             # --- the reference's sequence on the oracle ---
-            ol, orr = oracle.Orb(nfeatures=NF), oracle.Orb(nfeatures=NF)
+            ol, orr = oracle.Orb(nfeatures=NF, edge_threshold=edge_threshold), oracle.Orb(nfeatures=NF, edge_threshold=edge_threshold)
             ol.run(left)
             orr.run(right)
             kl, dl = ol.result()
@@ -73,18 +77,41 @@ def _follow_reference_sequence(oracle, frames, width, height, NF, LIFE, F=F_RECT
     return ctx, calib, sizes
 
 
-def test_observe_stereo_follows_the_reference_sequence(oracle):
-    from vision_slam_frontend_amd import synth
+def _reference_sequence_case(oracle, edge_threshold=31, depth=0):
+    """depth 0: the synchronous calls; otherwise the same frames through a queue of that depth, as fast as it takes them."""
+    from vision_slam_frontend_amd import capi, frontend, synth
     sc = synth.Scene(320, 240, n_objects=400)
     frames = [(sc.render(f, 0), sc.render(f, 1)) for f in range(7)]
     frames[3] = (frames[3][0], np.full_like(frames[3][1], 128))  # no stereo match in frame 3
-    ctx, calib, sizes = _follow_reference_sequence(oracle, frames, 320, 240, NF, LIFE)
+    results = None
+    if depth:
+        calib = frontend.default_calibration().set("fundamental", F_RECT)
+        bp = float(np.float32(0.3))
+        with capi.Context(capi.default_params(320, 240, max_images=2 * depth, nfeatures=NF, edge_threshold=edge_threshold)) as q:
+            q.observe_configure(depth, 0, 0)
+            results, tickets = [], []
+            for l, r in frames:
+                if len(tickets) == depth:
+                    results.append(q.observe_collect(tickets.pop(0), frame_life=LIFE))
+                tickets.append(q.observe_submit(l, r, calib, best_percent=bp, frame_life=LIFE))
+            results += [q.observe_collect(t, frame_life=LIFE) for t in tickets]
+    ctx, calib, sizes = _follow_reference_sequence(oracle, frames, 320, 240, NF, LIFE, results=results, edge_threshold=edge_threshold)
     assert sizes[3] == 0 and sizes[4] == 0 and sizes[5] > 20  # no match; NaN threshold; filtering resumes
     # a reset forgets the window and the threshold
     ctx.observe_reset()
     again = ctx.observe_stereo(*frames[0], calib, best_percent=float(np.float32(0.3)), frame_life=LIFE)
     assert again["threshold"] == np.float32(10000.0) and len(again["factors"]) == 0
     ctx.close()
+
+
+def test_observe_stereo_follows_the_reference_sequence(oracle):
+    _reference_sequence_case(oracle)
+
+
+def test_queue_follows_the_reference_sequence_at_edge_threshold_22(oracle):
+    """The same case with vsf_params::edge_threshold = 22 through a queue of depth 4 (the other oracle-held cases run at 31):
+    keypoints from 22 pixels inside a level's edge on enter the matcher, the stereo filter and the window."""
+    _reference_sequence_case(oracle, edge_threshold=22, depth=4)
 
 
 def test_observe_stereo_on_photographs(oracle):
