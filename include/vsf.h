@@ -49,7 +49,7 @@ typedef struct {
   float x, y;      /* pt, level-0 pixel coordinates */
   float size;      /* 31 * scale_l (ORB) / 7 (FAST) */
   float angle;     /* degrees, [0,360) (ORB) / -1 (FAST) */
-  float response;  /* Harris response (ORB) / FAST score (FAST) */
+  float response;  /* Harris response (ORB, HARRIS_SCORE) / FAST score (ORB with FAST_SCORE; FAST) */
   int32_t octave;  /* pyramid level */
   int32_t class_id;/* -1 */
 } vsf_keypoint;
@@ -59,6 +59,10 @@ typedef struct {
   int32_t queryIdx, trainIdx, imgIdx; /* imgIdx is always 0 */
   float distance;                     /* (float) Hamming distance */
 } vsf_dmatch;
+
+/* vsf_params::score_type, numbered as cv::ORB's enum */
+#define VSF_SCORE_HARRIS 0
+#define VSF_SCORE_FAST 1
 
 typedef struct {
   /* --- cv::ORB::create arguments (reference literals slam_frontend.cc:205-213) --- */
@@ -81,7 +85,21 @@ typedef struct {
   int32_t edge_threshold;
   int32_t first_level;    /* 0 (only value supported) */
   int32_t wta_k;          /* 2 (only value supported) */
-  int32_t score_type;     /* 0 = cv::ORB::HARRIS_SCORE (only value supported) */
+  /* 0 = cv::ORB::HARRIS_SCORE (the reference's, the default); 1 = cv::ORB::FAST_SCORE; anything else VSF_ERR_UNSUPPORTED.
+   * FAST_SCORE (OpenCV 3.2 computeKeyPoints): per level FAST + runByImageBorder, then ONE retainBest(n_l) on the FAST
+   * score -- no HarrisResponses, no second cut -- and everything behind it (ICAngles, GaussianBlur, the descriptors) as in
+   * HARRIS mode; vsf_keypoint::response is the FAST score.  The cut sits on an 8-bit key and retainBest keeps, beyond
+   * its n_l, every candidate whose score is not below that of element n_l - 1 as std::nth_element left it (one of the
+   * best n_l, not always the lowest of them): a level keeps between n_l and n_l + every candidate that shares the cut's
+   * score, and an image can hold MORE than nfeatures keypoints (640x480, nfeatures 2000: 2039 on a natural-looking
+   * scene, 2388 on a checkerboard of period 8, where counting every tie would give 2057 and 2698).
+   * Room, the one rule: an image holds max_keypoints keypoints and, in FAST_SCORE mode, a level holds
+   * n_l + max(max_keypoints - nfeatures, 0) of them -- the headroom the caller buys with max_keypoints (256 by default) is
+   * available to every level.  A level or an image that needs more is VSF_ERR_CAPACITY, as in HARRIS mode (results
+   * truncated per level / per image, counts as documented at vsf_extract; in the ObserveImage queue on that frame's
+   * ticket alone), never a silent cut.  In HARRIS mode a level holds 2 n_l + 64 whatever max_keypoints is: unchanged.
+   * vsf_debug_level_room states both for a parameter set without a device.  (tests/test_gpu_score_type.py) */
+  int32_t score_type;
   int32_t patch_size;     /* 31 (only value supported) */
   int32_t fast_threshold; /* 20 */
   /* 1: GaussianBlur column pass rounds like OpenCV's SSE2 SymmColumnVec_32s8u (half-even) on columns
@@ -1102,9 +1120,16 @@ vsf_status vsf_debug_fast_candidates(vsf_ctx* ctx, int image, int level, vsf_key
  * level_cap levels): w, h, x_lo, x_hi, y_lo, y_hi, fast_a0, nbands, nstrips, unit0.  VSF_ERR_CAPACITY if cap is short. */
 vsf_status vsf_debug_fast_work(const vsf_params* p, int orb, int nms, uint32_t* words, int cap, int* n_words, int* n_full,
                                int32_t* levels_out, int level_cap);
-/* Final per-level keypoints in level coordinates (after both retainBest cuts, with angle). */
+/* Final per-level keypoints in level coordinates, with angle: after both retainBest cuts in HARRIS_SCORE mode; in
+ * FAST_SCORE mode after its one cut (response = the FAST score) -- there the list "after the first cut" and the final
+ * list are the same list. */
 vsf_status vsf_debug_level_keypoints(vsf_ctx* ctx, int image, int level, vsf_keypoint* kp_out, int cap,
                                      int* n_out);
+/* Host only, no device needed: the keypoint room vsf_create would give *p (vsf_params::score_type states the rule).
+ * room[l], l < min(nlevels, cap): records level l's segment holds; nfeat[l] (may be NULL): its budget n_l;
+ * *records_per_image: their sum, one image's share of the level-keypoint buffer (20 bytes a record).
+ * VSF_ERR_UNSUPPORTED for a score_type vsf_create refuses, VSF_ERR_INVALID_ARG for a geometry it refuses. */
+vsf_status vsf_debug_level_room(const vsf_params* p, int32_t* room, int32_t* nfeat, int cap, int64_t* records_per_image);
 /* Which form of the describe kernel ONE launch over n_images images takes in this context: 4 or 8 consecutive output
  * keypoints per wave (a batched call is one launch with one lane, one launch per half with two: vsf_set_lanes).  The
  * launcher's own choice, read back; VSF_ERR_INVALID_ARG (1) for a null context or n_images < 1.  n_images may exceed

@@ -55,7 +55,7 @@ EXPORTS = [
     "vsf_observe_submit_compressed_reduced", "vsf_observe_stereo_compressed_reduced",
     "vsf_observe_set_debug_seeds", "vsf_observe_set_stream_cam_to_robot",
     "vsf_resize_gray_batch_dev", "vsf_observe_set_input_size", "vsf_resize_gray",
-    "vsf_debug_describe_form",
+    "vsf_debug_describe_form", "vsf_debug_level_room",
     "vsf_pixfmt_bytes_per_pixel", "vsf_pixfmt_from_encoding", "vsf_to_gray_batch_dev",
     "vsf_observe_submit_stream_pix", "vsf_observe_set_bayer_order", "vsf_to_gray",
 ]
@@ -388,6 +388,7 @@ def lib() -> C.CDLL:
         L.vsf_debug_fast_candidates.argtypes = [vp, i32, i32, vp, i32, ip]
         L.vsf_debug_fast_work.argtypes = [vp, i32, i32, vp, i32, ip, ip, vp, i32]
         L.vsf_debug_level_keypoints.argtypes = [vp, i32, i32, vp, i32, ip]
+        L.vsf_debug_level_room.argtypes = [vp, vp, vp, i32, vp]
         L.vsf_debug_describe_form.argtypes = [vp, i32]
         L.vsf_algorithmic_bytes_per_image.argtypes = [vp]
         L.vsf_algorithmic_bytes_per_image.restype = C.c_uint64
@@ -423,6 +424,20 @@ def default_params(width: int, height: int, max_images: int = 2, nfeatures: int 
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+HARRIS_SCORE, FAST_SCORE = 0, 1  # vsf_params::score_type (cv::ORB::HARRIS_SCORE / FAST_SCORE)
+
+
+def level_room(params: VsfParams):
+    """vsf_debug_level_room (host only): (room per level, n_l per level, records per image) vsf_create would give `params`."""
+    room = np.zeros(params.nlevels, np.int32)
+    nfeat = np.zeros(params.nlevels, np.int32)
+    total = C.c_int64()
+    st = lib().vsf_debug_level_room(C.byref(params), _p(room), _p(nfeat), params.nlevels, C.byref(total))
+    if st != VSF_OK:
+        raise VsfError(st, "vsf_debug_level_room")
+    return room, nfeat, int(total.value)
 
 
 class Context:

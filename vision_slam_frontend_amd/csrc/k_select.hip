@@ -6,6 +6,8 @@
 //   K4       HarrisResponses(blockSize 7, k 0.04f) for the survivors           (int32 sums, 6 float ops, no FMA)
 //   K5       KeyPointsFilter::retainBest(n_l) on the Harris response          (order-exact)
 //   (K6, ICAngles + fastAtan2, runs per keypoint in k_describe.hip)
+// cv::ORB::FAST_SCORE (vsf_params::score_type 1) is a compile-time form of the same kernel: gather, K3 as retainBest(n_l),
+// and the survivors leave with their FAST score as the response; K4 and K5 have no code in it.
 //
 // Order-exact selection.  retainBest leaves libstdc++'s std::nth_element + std::partition
 // permutation, which later stages turn into keypoint indices, so it has to be reproduced exactly.  Both are
@@ -610,7 +612,9 @@ struct SelectPlan {
   }
 };
 
-template <int NT, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES = true, int WGS = (NT == 256 ? 5 : 1)>
+// FAST_SCORE (cv::ORB::FAST_SCORE, vsf_params::score_type 1): K3 cuts at n_l and is the only cut -- the survivors leave
+// straight from the stage-1 array with the FAST score as their response; K4 and K5 have no code in that form.
+template <int NT, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES = true, int WGS = (NT == 256 ? 5 : 1), bool FAST_SCORE = false>
 __global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
   const SelectLds<ENTRIES, STAGE2, MAXW, LDS_TABLES> lds = select_lds<0, ENTRIES, STAGE2, MAXW, LDS_TABLES>();
   __shared__ int lds4[16];
@@ -661,6 +665,33 @@ __global__ __launch_bounds__(NT, WGS) void orb_select_kernel(SelectArgs a) {
           gA[dst] = cd;
       });
   __syncthreads();
+
+  if constexpr (FAST_SCORE) {
+    // ---- K3: retainBest(n_l) on the FAST score, the one cut of this mode (ties at the cut all stay) ----
+    int m1;
+    if (a_in_lds)
+      m1 = par_retain_best<NT>(sA, n, L.nfeatures, ScoreGreater(), ScoreGe(), P.pm_lds);
+    else
+      m1 = par_retain_best<NT>(gA, n, L.nfeatures, ScoreGreater(), ScoreGe(), P.pm_hbm, P.stage1());
+    __syncthreads();
+    VsfLevelKp* out = a.lvlkp + (size_t)image * a.lvlkp_entries + L.kp_offset;
+    const int m_out = min(m1, L.kp_cap);
+    for (int i = tid; i < m_out; i += NT) {
+      const uint32_t cd = a_in_lds ? sA[i] : gA[i];
+      VsfLevelKp kp;
+      kp.xy = cd & 0xFFFFFFu;
+      kp.response = (float)(cd >> 24);
+      kp.angle = -1.f;
+      kp.ca = 1.f;
+      kp.sb = 0.f;
+      out[i] = kp;
+    }
+    if (tid == 0) {
+      a.lvl_count[(size_t)image * a.nlevels + level] = m_out;
+      if (m1 > L.kp_cap) atomicOr(a.status + (size_t)image * a.status_stride, 1);
+    }
+    return;
+  }
 
   // ---- K3: retainBest(2 * n_l) on the FAST score ----
   int m1;
@@ -785,8 +816,20 @@ __global__ __launch_bounds__(NT, WGS) void select_form_test_kernel(uint32_t* gsc
 
 }  // namespace
 
+namespace {
+// One production form of orb_select_kernel in the context's mode (g.score_type): the same grid either way.
+template <int NT, int ENTRIES, int STAGE2, int MAXW, bool LDS_TABLES = true, int WGS = (NT == 256 ? 5 : 1)>
+void launch_select_form(bool fast_score, int nblocks, hipStream_t s, const SelectArgs& a) {
+  if (fast_score)
+    hipLaunchKernelGGL((orb_select_kernel<NT, ENTRIES, STAGE2, MAXW, LDS_TABLES, WGS, true>), dim3(nblocks), dim3(NT), 0, s, a);
+  else
+    hipLaunchKernelGGL((orb_select_kernel<NT, ENTRIES, STAGE2, MAXW, LDS_TABLES, WGS>), dim3(nblocks), dim3(NT), 0, s, a);
+}
+}  // namespace
+
 void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, const VsfImages& im,
                        hipStream_t s) {
+  const bool fast_score = g.score_type == 1;
   SelectArgs a;
   a.levels = d.levels;
   a.img0 = im.base;
@@ -838,7 +881,7 @@ void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_leve
     if ((long)g.nlevels * im.n <= 256) ntiny0 = g.nlevels;  // ... and the small top levels ride along (one launch)
     a.level0 = 0;
     a.nlv = ntiny0;
-    hipLaunchKernelGGL((orb_select_kernel<1024, 12288, 512, 192>), dim3(a.nlv * n8), dim3(1024), 0, s, a);
+    launch_select_form<1024, 12288, 512, 192>(fast_score, a.nlv * n8, s, a);
   } else if (ntiny0 > 0) {
     // Levels whose area holds more than 3 072 but (on a busy scene: one candidate per ~30 pixels) no more than 9 216
     // candidates take the 9 216-entry class, three per CU: their array lives in LDS from the gather on.  Larger levels
@@ -859,14 +902,14 @@ void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_leve
       if (l1 <= l0) return;
       a.level0 = l0;
       a.nlv = l1 - l0;
-      hipLaunchKernelGGL((orb_select_kernel<256, 3072, 512, 64>), dim3(a.nlv * n8), dim3(256), 0, s, a);
+      launch_select_form<256, 3072, 512, 64>(fast_score, a.nlv * n8, s, a);
     };
     if (nwide_end == nhuge) nhuge = nwide_end = 0;  // (no wide class this time: ONE launch of the common class, as before)
     common(0, nhuge);
     if (nwide_end > nhuge) {
       a.level0 = nhuge;
       a.nlv = nwide_end - nhuge;
-      hipLaunchKernelGGL((orb_select_kernel<256, 9216, 512, 144, false, 3>), dim3(a.nlv * n8), dim3(256), 0, s, a);
+      launch_select_form<256, 9216, 512, 144, false, 3>(fast_score, a.nlv * n8, s, a);
     }
     // (one after the other on the stream: beside each other on two streams the pair took 0.4 ms longer per step)
     common(nwide_end, ntiny0);
@@ -874,7 +917,7 @@ void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_leve
   if (ntiny0 < g.nlevels) {
     a.level0 = ntiny0;
     a.nlv = g.nlevels - ntiny0;
-    hipLaunchKernelGGL((orb_select_kernel<64, 1536, 512, 64>), dim3(a.nlv * n8), dim3(64), 0, s, a);
+    launch_select_form<64, 1536, 512, 64>(fast_score, a.nlv * n8, s, a);
   }
 }
 

@@ -465,7 +465,8 @@ const char* vsf_status_string(vsf_status s) {
 vsf_status vsf_create(const vsf_params* p, int device, vsf_ctx** out) {
   if (!p || !out) return VSF_ERR_INVALID_ARG;
   *out = nullptr;
-  if (p->first_level != 0 || p->wta_k != 2 || p->score_type != 0 || p->patch_size != 31) return VSF_ERR_UNSUPPORTED;
+  if (p->first_level != 0 || p->wta_k != 2 || (p->score_type != 0 && p->score_type != 1) || p->patch_size != 31)
+    return VSF_ERR_UNSUPPORTED;
   if (p->nlevels < 1 || p->nlevels > VSF_MAX_LEVELS || p->width < 16 || p->height < 16 || p->max_images < 1 ||
       p->nfeatures < 0 || p->edge_threshold < 0 || !(p->scale_factor > 1.0f))
     return VSF_ERR_INVALID_ARG;

@@ -275,6 +275,25 @@ vsf_status vsf_debug_fast_work(const vsf_params* p, int orb, int nms, uint32_t* 
   return VSF_OK;
 }
 
+// The keypoint room of a parameter set, from the geometry vsf_create itself would build (max_keypoints resolved as it does).
+vsf_status vsf_debug_level_room(const vsf_params* p, int32_t* room, int32_t* nfeat, int cap, int64_t* records_per_image) {
+  if (!p || cap < 0 || (cap > 0 && !room) || !records_per_image) return VSF_ERR_INVALID_ARG;
+  if (p->score_type != 0 && p->score_type != 1) return VSF_ERR_UNSUPPORTED;
+  if (p->nlevels < 1 || p->nlevels > VSF_MAX_LEVELS || p->width < 16 || p->height < 16 || !(p->scale_factor > 1.0f) ||
+      p->edge_threshold < 0 || p->first_level != 0 || p->nfeatures < 0)
+    return VSF_ERR_INVALID_ARG;
+  vsf_params q = *p;
+  if (q.max_keypoints <= 0) q.max_keypoints = q.nfeatures + 256;
+  Geometry G;
+  if (!build_geometry(q, true, true, &G)) return VSF_ERR_INVALID_ARG;
+  for (int l = 0; l < (int)G.levels.size() && l < cap; l++) {
+    room[l] = G.levels[l].kp_cap;
+    if (nfeat) nfeat[l] = G.levels[l].nfeatures;
+  }
+  *records_per_image = G.g.lvlkp_entries;
+  return VSF_OK;
+}
+
 // The launcher's own choice (vsf_describe_kp_per_wave), so that a test knows which instantiation of the describe kernel its
 // batch ran without restating the thresholds.  Host only; n_images is not held against max_images, so that a small context
 // can be asked where the form changes before the large one is built.

@@ -148,6 +148,7 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
   G.g.nlevels = nlevels;
   G.g.width = p.width;
   G.g.height = p.height;
+  G.g.score_type = orb ? p.score_type : 0;  // (the stand-alone FAST detector has no selection)
   const double scale_factor = (double)p.scale_factor;
   // per-level budget
   std::vector<int> nfeat(nlevels, 0);
@@ -222,7 +223,7 @@ bool build_geometry(const vsf_params& p, bool orb, bool nms, Geometry* out) {
     L.cand_offset = cand;
     cand += (uint32_t)L.seg_cap * (uint32_t)(L.nstrips * L.nbands);
     L.kp_offset = kp_off;
-    L.kp_cap = 2 * L.nfeatures + 64;
+    L.kp_cap = vsf_level_kp_cap(G.g.score_type, L.nfeatures, p.nfeatures, p.max_keypoints);
     kp_off += L.kp_cap;
   }
   G.g.cand_entries = std::max(cand, 1u);

@@ -56,7 +56,7 @@ struct VsfLevel {
   uint32_t cand_offset;    // u32 index of this level's first candidate segment (per image)
   int32_t seg_cap;         // capacity of one unit's candidate segment
   int32_t kp_offset;       // index of this level's final-keypoint segment (per image)
-  int32_t kp_cap;          // its capacity
+  int32_t kp_cap;          // its capacity (vsf_level_kp_cap)
   int32_t blur_vec_end;    // columns [0, blur_vec_end) round half-even (SSE2 path), the rest half-up
   uint32_t xtab, ytab;     // entry offsets of this level's resize tables in the host-side Geometry (level >= 1)
   int32_t resize_rows;     // largest strip height (16, 8, 4) the shared-row resize kernel may use for this level, or 0
@@ -79,6 +79,17 @@ struct VsfLevelKp {
   float ca, sb;    // cos / sin of the angle as computeOrbDescriptors takes them
 };
 
+// Records one level's segment of VsfDev::lvlkp holds (include/vsf.h, vsf_params::score_type, states the rule).
+// HARRIS_SCORE: the first cut's 2 n_l and room for its ties; the second cut's ties sit on a float and are rare.
+// FAST_SCORE: the one cut sits on an 8-bit key, so ties are the rule: n_l and the whole headroom the caller bought for the
+// image (max_keypoints - nfeatures; max_keypoints <= 0 stands for its default, nfeatures + 256).
+inline int vsf_level_kp_cap(int score_type, int n_l, int nfeatures, int max_keypoints) {
+  if (score_type != 1) return 2 * n_l + 64;
+  const long mk = max_keypoints > 0 ? (long)max_keypoints : (long)nfeatures + 256;
+  const long room = mk - nfeatures;
+  return n_l + (int)(room > 0 ? room : 0);
+}
+
 struct VsfGeom {
   int nlevels;
   int width, height;
@@ -88,6 +99,7 @@ struct VsfGeom {
   int nwork_full, nwork_pack;  // FAST work items: waves covering one cell / packed items of narrow cells
   int fast_split_levels;       // levels 0 .. this - 1 have full cells: the most VSF_OPT_FAST_EARLY_LEVELS can mean (vsf_fast_split.h)
   int lvlkp_entries;        // one image's level-keypoint buffer (VsfLevelKp entries)
+  int score_type;           // vsf_params::score_type of an ORB geometry (0 HARRIS_SCORE, 1 FAST_SCORE): the selection's form
   uint64_t pyramid_pixels;
 };
 

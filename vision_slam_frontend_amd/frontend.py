@@ -24,6 +24,8 @@ def lib() -> C.CDLL:
         vp, i32, f32, sz, dbl = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_double
         L.vsfh_frontend_create.argtypes = [i32, i32, i32, i32, vp, f32, i32]
         L.vsfh_frontend_create.restype = vp
+        L.vsfh_frontend_create_score.argtypes = [i32, i32, i32, i32, vp, f32, i32, i32]
+        L.vsfh_frontend_create_score.restype = vp
         L.vsfh_frontend_destroy.argtypes = [vp]
         L.vsfh_observe_odometry.argtypes = [vp, vp, vp, dbl]
         L.vsfh_observe_image.argtypes = [vp, vp, vp, i32, i32, sz, dbl]
@@ -84,6 +86,8 @@ def lib() -> C.CDLL:
         L.vsfh_set_left_cam_to_robot.restype = None
         L.vsfh_group_create_ex.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32]
         L.vsfh_group_create_ex.restype = vp
+        L.vsfh_group_create_score.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32]
+        L.vsfh_group_create_score.restype = vp
         L.vsfh_set_imdecode_reduce.argtypes = [vp, i32]
         L.vsfh_set_imdecode_reduce.restype = None
         L.vsfh_set_resize.argtypes = [vp, i32, i32, i32, i32]
@@ -180,13 +184,15 @@ class Frontend:
     def __init__(self, width: int, height: int, nfeatures: int = 10000, device: int = 0, fundamental=None,
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False, imdecode_reduce: int = 1,
-                 compressed_cap: int = 0, debug_colour_seed=None, cam_to_robot=None, resize_to=None):
-        """resize_to=(w, h): FrontendConfig::resize_width_ / resize_height_ -- the context has that size, width x height is
+                 compressed_cap: int = 0, debug_colour_seed=None, cam_to_robot=None, resize_to=None,
+                 score_type: int = capi.HARRIS_SCORE):
+        """score_type: FrontendConfig::orb_score_type_ (capi.HARRIS_SCORE, the reference's, or capi.FAST_SCORE).
+        resize_to=(w, h): FrontendConfig::resize_width_ / resize_height_ -- the context has that size, width x height is
         the CAMERA's (what device frames are taken to be; raw and compressed frames bring their own), every frame goes through
         cv::resize on the device, and the calibration is the caller's, for the resized image."""
         F = None if fundamental is None else np.ascontiguousarray(fundamental, np.float32).reshape(9)
         cw, ch = (width, height) if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
-        self._h = lib().vsfh_frontend_create(nfeatures, cw, ch, device, _p(F), best_percent, frame_life)
+        self._h = lib().vsfh_frontend_create_score(nfeatures, cw, ch, device, _p(F), best_percent, frame_life, int(score_type))
         self.cap = nfeatures + 256
         self.size, self.device = (width, height), device
         if resize_to is not None:
@@ -531,8 +537,9 @@ class FrontendGroup:
     def __init__(self, width: int, height: int, fundamentals, nfeatures: int = 10000, device: int = 0, best_percents=None,
                  frame_life: int = 0, imdecode_reduces=None, compressed_cap: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, debug_colour_seeds=None, cam_to_robots=None,
-                 visualization: bool = False, resize_to=None, camera_sizes=None):
-        """resize_to=[(w, h) or None, ...]: FrontendConfig::resize_width_ / resize_height_ per member (None: off) -- a resized
+                 visualization: bool = False, resize_to=None, camera_sizes=None, score_type: int = capi.HARRIS_SCORE):
+        """score_type: every member's FrontendConfig::orb_score_type_ (one context, one mode).
+        resize_to=[(w, h) or None, ...]: FrontendConfig::resize_width_ / resize_height_ per member (None: off) -- a resized
         member takes frames of its camera's size and shares the group's width x height context, so (w, h) is width x height;
         camera_sizes=[(W, H) or None, ...]: what member i's DEVICE frames are taken to be (raw and compressed frames bring
         their own size)."""
@@ -541,8 +548,9 @@ class FrontendGroup:
         bp = None if best_percents is None else np.ascontiguousarray(best_percents, np.float32).reshape(n)
         seeds = None if debug_colour_seeds is None else np.ascontiguousarray(debug_colour_seeds, np.uint32).reshape(n)
         c2r = None if cam_to_robots is None else np.ascontiguousarray(cam_to_robots, np.float32).reshape(n, 12)
-        self._h = lib().vsfh_group_create_ex(n, nfeatures, width, height, device, _p(F), _p(bp), frame_life, int(debug_images),
-                                             int(debug_jpeg_quality), int(debug_png), _p(seeds), _p(c2r), int(visualization))
+        self._h = lib().vsfh_group_create_score(n, nfeatures, width, height, device, _p(F), _p(bp), frame_life, int(debug_images),
+                                                int(debug_jpeg_quality), int(debug_png), _p(seeds), _p(c2r), int(visualization),
+                                                int(score_type))
         st = lib().vsfh_group_last_status(self._h)
         if st != capi.VSF_OK:
             self.close()

@@ -12,16 +12,23 @@ using slam::FrontendConfig;
 
 extern "C" {
 
-void* vsfh_frontend_create(int nfeatures, int width, int height, int device, const float* fundamental9,
-                           float best_percent, int frame_life) {
+// score_type: FrontendConfig::orb_score_type_ (VSF_SCORE_HARRIS / VSF_SCORE_FAST)
+void* vsfh_frontend_create_score(int nfeatures, int width, int height, int device, const float* fundamental9,
+                                 float best_percent, int frame_life, int score_type) {
   FrontendConfig cfg;
   cfg.orb_nfeatures = nfeatures;
+  cfg.orb_score_type_ = score_type;
   cfg.image_width = width;
   cfg.image_height = height;
   if (fundamental9) std::memcpy(cfg.fundamental.m, fundamental9, 9 * sizeof(float));
   if (best_percent > 0) cfg.best_percent_ = best_percent;
   if (frame_life > 0) cfg.frame_life_ = (uint32_t)frame_life;
   return new Frontend("", cfg, device);
+}
+// (the call as it was before the score type: the reference's HARRIS_SCORE)
+void* vsfh_frontend_create(int nfeatures, int width, int height, int device, const float* fundamental9,
+                           float best_percent, int frame_life) {
+  return vsfh_frontend_create_score(nfeatures, width, height, device, fundamental9, best_percent, frame_life, VSF_SCORE_HARRIS);
 }
 
 // The stereo calibration of a default-constructed FrontendConfig (the reference's hard-coded constants,
@@ -313,13 +320,15 @@ void vsfh_frontend_destroy(void* f) { delete static_cast<Frontend*>(f); }
 // with: the debug images' switch and form (0 / 0 / 0: none), a colour seed per member (NULL: the process's rand() -- refused with
 // more than one member and debug images), a left_cam_to_robot per member (n x 12 floats, 3 x 4 row-major; NULL: the
 // reference's) and visualization_.
-void* vsfh_group_create_ex(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
-                           const float* best_percent, int frame_life, int debug_images, int debug_jpeg_quality, int debug_png,
-                           const uint32_t* colour_seeds, const float* cam_to_robots, int visualization) {
+// ... and score_type: every member's FrontendConfig::orb_score_type_ (one context, one mode).
+void* vsfh_group_create_score(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
+                              const float* best_percent, int frame_life, int debug_images, int debug_jpeg_quality, int debug_png,
+                              const uint32_t* colour_seeds, const float* cam_to_robots, int visualization, int score_type) {
   std::vector<FrontendConfig> cfgs((size_t)(n > 0 ? n : 0));
   for (int i = 0; i < n; i++) {
     FrontendConfig& cfg = cfgs[(size_t)i];
     cfg.orb_nfeatures = nfeatures;
+    cfg.orb_score_type_ = score_type;
     cfg.image_width = width;
     cfg.image_height = height;
     if (fundamental9) std::memcpy(cfg.fundamental.m, fundamental9 + 9 * i, 9 * sizeof(float));
@@ -334,6 +343,13 @@ void* vsfh_group_create_ex(int n, int nfeatures, int width, int height, int devi
     if (cam_to_robots) cfg.left_cam_to_robot = slam::AffineFromRowMajor(cam_to_robots + 12 * i);
   }
   return new slam::FrontendGroup(cfgs, device);
+}
+// (the call as it was before the score type)
+void* vsfh_group_create_ex(int n, int nfeatures, int width, int height, int device, const float* fundamental9,
+                           const float* best_percent, int frame_life, int debug_images, int debug_jpeg_quality, int debug_png,
+                           const uint32_t* colour_seeds, const float* cam_to_robots, int visualization) {
+  return vsfh_group_create_score(n, nfeatures, width, height, device, fundamental9, best_percent, frame_life, debug_images,
+                                 debug_jpeg_quality, debug_png, colour_seeds, cam_to_robots, visualization, VSF_SCORE_HARRIS);
 }
 // (the call as it was before the group took debug images and extrinsics)
 void* vsfh_group_create(int n, int nfeatures, int width, int height, int device, const float* fundamental9,

@@ -140,6 +140,7 @@ FrontendConfig::FrontendConfig() {
   min_odom_translation = 0.2f;
   min_vision_matches = 10;
   orb_nfeatures = 10000;  // cc:205
+  orb_score_type_ = VSF_SCORE_HARRIS;  // cc:211 (cv::ORB::HARRIS_SCORE)
   residual_order = 0;     // Eigen 3.3's reduction order of a fixed-size-3 lazy product (cc:381-383)
   image_width = 0;        // 0: taken from the first observed image
   image_height = 0;
@@ -298,6 +299,7 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
   vsf_params p;
   vsf_params_default(&p, width, height, 2 * batch_frames());  // extraction buffers for one batch of stereo frames
   p.nfeatures = config_.orb_nfeatures;
+  p.score_type = config_.orb_score_type_;
   p.residual_order = config_.residual_order;
   last_status_ = vsf_params_set_ratio(&p, config_.nn_match_ratio_);
   if (last_status_ != VSF_OK) return false;
@@ -1397,7 +1399,7 @@ FrontendGroup::FrontendGroup(const std::vector<FrontendConfig>& configs, int dev
       return;
     }
   for (const FrontendConfig& c : configs)  // what the one context is built with
-    if (c.orb_nfeatures != lead.orb_nfeatures || c.nn_match_ratio_ != lead.nn_match_ratio_ ||
+    if (c.orb_nfeatures != lead.orb_nfeatures || c.orb_score_type_ != lead.orb_score_type_ || c.nn_match_ratio_ != lead.nn_match_ratio_ ||
         c.residual_order != lead.residual_order || c.frame_life_ != lead.frame_life_ || ContextWidth(c) != ContextWidth(lead) ||
         ContextHeight(c) != ContextHeight(lead) || c.visualization_ != lead.visualization_ || c.debug_images_ != lead.debug_images_ ||
         c.debug_jpeg_quality_ != lead.debug_jpeg_quality_ || c.debug_png_ != lead.debug_png_ ||

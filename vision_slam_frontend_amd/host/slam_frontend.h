@@ -138,6 +138,11 @@ struct FrontendConfig {
   // ORB parameters the reference hard-codes in cv::ORB::create (cc:205-213); exposed so BASELINE configs can set
   // nfeatures = 2000 / 8000.
   int orb_nfeatures;
+  // cv::ORB::create's scoreType (vsf_params::score_type): VSF_SCORE_HARRIS (0, the reference's literal, the default) or
+  // VSF_SCORE_FAST (1: one cut per level on the FAST score, no Harris responses; a frame can hold more than orb_nfeatures
+  // keypoints, see include/vsf.h).  Honoured in per-call, synchronous and pipelined mode alike -- the mode belongs to the
+  // context; the members of a FrontendGroup share one context and must agree on it.
+  int orb_score_type_;
   // How RemoveAmbigStereo's three-term dot products are summed (vsf_params::residual_order): 0 = as Eigen 3.3 does,
   // a0 b0 + (a1 b1 + a2 b2) (default); 1 = left to right.
   int residual_order;
