@@ -1021,6 +1021,63 @@ vsf_status vsf_to_gray_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_image
 vsf_status vsf_to_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int pixfmt, size_t src_image_stride,
                        size_t src_row_stride, uint8_t* dst, size_t dst_image_stride, size_t dst_row_stride);
 
+/* The COLOUR image of a raw frame: the link between cv::imdecode(data, 1) and cv::imwrite in src/test/bag_extract.cc:75-88,
+ *     if format contains "bayer_rggb8":  cv::split(image) -> channel 0;  cv::cvtColor(channel 0, image, cv::COLOR_BayerBG2BGR)
+ * for n raw images of width x height pixels resident in HBM -> their B G R images, in ONE launch on the context's stream
+ * (k_to_bgr.hip).  The sibling of vsf_to_gray_batch_dev: vsf_to_gray_batch_dev(vsf_to_bgr_batch_dev(x), VSF_PIX_BGR8) is
+ * vsf_to_gray_batch_dev(x), byte for byte, for every format.
+ *   FORMATS: the four VSF_PIX_BAYER_* orders are cv::cvtColor(COLOR_Bayer??2BGR) of OpenCV 3.2 (demosaicing.cpp Bayer2RGB_<uchar>,
+ * three destination channels): bilinear inside, the one-pixel frame copies its inner neighbour (columns first, then rows), an image
+ * narrower or lower than 3 pixels is all zero.  VSF_PIX_BAYER_RGGB8 is the reference's COLOR_BayerBG2BGR.  The packed formats
+ * are what cv_bridge makes of them for a "bgr8" request: VSF_PIX_MONO8 B = G = R; VSF_PIX_BGR8 a copy; VSF_PIX_RGB8 red and blue
+ * exchanged; VSF_PIX_BGRA8 / VSF_PIX_RGBA8 alpha dropped.
+ *   SOURCE: the rules of vsf_to_gray_batch_dev -- image i at base + i * image_stride, rows row_stride bytes apart, base and both
+ * strides multiples of 4, src_row_stride >= width x vsf_pixfmt_bytes_per_pixel(pixfmt), src_image_stride >= src_row_stride x
+ * height, src_row_stride x height < 2^31.  READS: mosaics as vsf_bayer_bg_to_gray_batch_dev reads them (whole dwords of a row, its
+ * padding included, inside the image's row_stride x height bytes; padding never reaches a pixel of the result).  Packed colour and
+ * MONO8: only aligned dwords that begin before the end of their own row rounded up to 4 bytes.
+ *   DESTINATION: the layout of vsf_imdecode_bgr_batch, which the BGR encoders and vsf_to_gray_batch_dev(VSF_PIX_BGR8) read: a row is
+ * 3 * width bytes, blue, green, red per pixel; d_dst, dst_image_stride and dst_row_stride are multiples of 4, dst_row_stride >=
+ * (3 * width + 3) & ~3, dst_image_stride >= dst_row_stride x height, dst_row_stride x height < 2^31.
+ *   WRITES: bytes [0, (3 * width + 3) & ~3) of each of the height destination rows and nothing else.  The up to 3 bytes behind
+ * byte 3 * width - 1 are zero.
+ *   LIMITS: width <= 16384 (the demosaic's limit, kept for every format), height and n_images <= 65535.
+ *   COST: one pass, bpp bytes read and 3 written per pixel; no scratch memory.
+ *   VSF_ERR_INVALID_ARG: a null pointer, an unknown pixfmt, a size or stride outside these rules; nothing is launched then. */
+vsf_status vsf_to_bgr_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int pixfmt,
+                                size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst, size_t dst_image_stride,
+                                size_t dst_row_stride);
+/* The same HOST TO HOST (upload, the one launch, download; synchronous): ANY addresses and strides with src_row_stride >= width x
+ * bytes per pixel and dst_row_stride >= 3 * width (with more than one image: image strides that hold an image); exactly
+ * 3 * width bytes of each destination row are written.  width <= 16384, height <= 32767. */
+vsf_status vsf_to_bgr(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int pixfmt, size_t src_image_stride,
+                      size_t src_row_stride, uint8_t* dst, size_t dst_image_stride, size_t dst_row_stride);
+
+/* src/test/bag_extract.cc:73-90 as ONE call, for n JPEG / PNG payloads of width x height pixels in HOST memory -> n JPEG files
+ * in HOST memory; synchronous:
+ *     image = cv::imdecode(data, 1)                                   (:73)   vsf_imdecode_bgr_batch
+ *     if format contains "bayer_rggb8":                               (:75)   bayer_pixfmt != 0
+ *         cv::split(image) -> channel 0                               (:77-78)
+ *         cv::cvtColor(channel 0, image, cv::COLOR_BayerBG2BGR)       (:82)   vsf_to_bgr_batch_dev
+ *     cv::imwrite("....jpg", image)                                   (:88)   vsf_jpeg_encode_batch_dev, channels 3
+ * The result is what those three calls give by hand; nothing goes home between the stages, and the images between them live in
+ * scratch the context owns (grown like the decoders' scratch, never shrunk).
+ *   bayer_pixfmt: 0 -- the topic is no mosaic: colour read, colour encode; one of the four VSF_PIX_BAYER_* codes -- colour read,
+ * channel 0, demosaic in that order, colour encode (VSF_PIX_BAYER_RGGB8 is the reference's own case; width <= 16384 then); any
+ * other code is VSF_ERR_INVALID_ARG.
+ *   The mosaic is channel 0 of the COLOUR read, always: Y for a one-component JPEG and the gray of a gray PNG (B = G = R there),
+ * the BLUE channel of a three-component file -- never the gray read of it.  Decided per file from its frame header: a
+ * one-component JPEG is decoded by the gray decoders straight into its mosaic (the same bytes, the same refusals); every other
+ * file takes the colour decode and one more kernel keeps the first byte of each pixel.
+ *   quality: as in vsf_jpeg_encode (1 .. 100; 0 = 95, which is what cv::imwrite uses).
+ *   File i is written at out + i * out_stride and its size to out_bytes[i].  A file that does not fit out_stride gives
+ * out_bytes[i] = -1 and VSF_ERR_CAPACITY, the other files are delivered (vsf_jpeg_encode_capacity(width, height, 3) always fits).
+ * On any other status than VSF_OK / VSF_ERR_CAPACITY every out_bytes[i] is -1: no partial delivery.  The statuses are the
+ * decoders': VSF_ERR_UNSUPPORTED / VSF_ERR_INVALID_ARG as vsf_imdecode_bgr_batch gives them (a file of another size among them:
+ * VSF_ERR_INVALID_ARG, nothing launched; a stream that breaks off inside its data: VSF_ERR_INVALID_ARG). */
+vsf_status vsf_bag_extract_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images, int width,
+                                 int height, int bayer_pixfmt, int quality, uint8_t* out, size_t out_stride, int32_t* out_bytes);
+
 /* cv::resize(src, dst, Size(dst_width, dst_height)) of OpenCV 3.2 with its default interpolation (INTER_LINEAR) on CV_8UC1,
  * for n images resident in HBM, device to device, in ONE launch (k_resize.hip).  Independent of the context's own image
  * size.  Bit for bit cv::resize's integers: the coefficients of csrc/vsf_resize.h (the pyramid's), HResizeLinear's and

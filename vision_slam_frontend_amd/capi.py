@@ -58,6 +58,7 @@ EXPORTS = [
     "vsf_debug_describe_form", "vsf_debug_level_room",
     "vsf_pixfmt_bytes_per_pixel", "vsf_pixfmt_from_encoding", "vsf_to_gray_batch_dev",
     "vsf_observe_submit_stream_pix", "vsf_observe_set_bayer_order", "vsf_to_gray",
+    "vsf_to_bgr_batch_dev", "vsf_to_bgr", "vsf_bag_extract_batch",
 ]
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
@@ -294,6 +295,9 @@ def lib() -> C.CDLL:
         L.vsf_bayer_bg_to_gray_batch_dev.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, sz, sz]
         L.vsf_to_gray_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, sz]
         L.vsf_to_gray.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_to_bgr_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_to_bgr.argtypes = [vp, vp, i32, i32, i32, i32, sz, sz, vp, sz, sz]
+        L.vsf_bag_extract_batch.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]
         L.vsf_pixfmt_bytes_per_pixel.argtypes = [i32]
         L.vsf_pixfmt_bytes_per_pixel.restype = C.c_int
         L.vsf_pixfmt_from_encoding.argtypes = [C.c_char_p, ip]
@@ -1132,6 +1136,40 @@ class Context:
         """vsf_to_gray_batch_dev: raw images of any PIX_* format resident in HBM -> gray, one launch.  Returns the status."""
         return lib().vsf_to_gray_batch_dev(self._h, _p(d_src), n_images, width, height, pixfmt, src_image_stride,
                                            src_row_stride, _p(d_dst), dst_image_stride, dst_row_stride)
+
+    def to_bgr(self, imgs: np.ndarray, pixfmt: int) -> np.ndarray:
+        """vsf_to_bgr: (n, h, w) or (n, h, w, 3 or 4) raw images in host memory -> (n, h, w, 3) B G R images."""
+        imgs = np.ascontiguousarray(imgs, np.uint8)
+        n, h, w = imgs.shape[:3]
+        row = w * (imgs.shape[3] if imgs.ndim == 4 else 1)
+        out = np.zeros((n, h, w, 3), np.uint8)
+        self._check(lib().vsf_to_bgr(self._h, _p(imgs), n, w, h, pixfmt, row * h, row, _p(out), 3 * w * h, 3 * w), "vsf_to_bgr")
+        return out
+
+    def to_bgr_batch_dev(self, d_src: int, n_images: int, width: int, height: int, pixfmt: int, src_image_stride: int,
+                         src_row_stride: int, d_dst: int, dst_image_stride: int, dst_row_stride: int) -> int:
+        """vsf_to_bgr_batch_dev: raw images of any PIX_* format resident in HBM -> B G R (vsf_imdecode_bgr_batch's layout), one
+        launch.  Returns the status."""
+        return lib().vsf_to_bgr_batch_dev(self._h, _p(d_src), n_images, width, height, pixfmt, src_image_stride,
+                                          src_row_stride, _p(d_dst), dst_image_stride, dst_row_stride)
+
+    def bag_extract_batch(self, files, width: int, height: int, bayer_pixfmt: int = 0, quality: int = 0,
+                          out_stride: int | None = None, allow_status=()):
+        """src/test/bag_extract.cc:73-90 for JPEG / PNG payloads of one size (vsf_bag_extract_batch): colour read, on a Bayer
+        topic (bayer_pixfmt = one of the four PIX_BAYER_* codes) channel 0 demosaiced in that order, colour JPEG files.
+        Returns (status, files): files[i] is bytes, or None where out_bytes[i] is -1."""
+        n = len(files)
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        sizes = (C.c_size_t * n)(*[len(b) for b in bufs])
+        stride = int(lib().vsf_jpeg_encode_capacity(width, height, 3)) if out_stride is None else out_stride
+        out = np.zeros((max(n, 1), max(stride, 1)), np.uint8)
+        nbytes = np.zeros(max(n, 1), np.int32)
+        st = lib().vsf_bag_extract_batch(self._h, C.cast(ptrs, C.c_void_p), C.cast(sizes, C.c_void_p), n, width, height,
+                                         bayer_pixfmt, quality, _p(out), stride, _p(nbytes))
+        if st not in (VSF_OK, VSF_ERR_CAPACITY) and st not in allow_status:
+            raise VsfError(st, "vsf_bag_extract_batch", lib().vsf_last_hip_error(self._h))
+        return st, [out[i, :nbytes[i]].tobytes() if nbytes[i] >= 0 else None for i in range(n)]
 
     def debug_retain_best(self, keys: np.ndarray, n_points: int, use_lds: bool = False, mode: int = 0):
         """retainBest on the GPU; returns (keys, ids) of the survivors in the order the GPU left them."""

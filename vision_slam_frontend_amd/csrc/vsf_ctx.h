@@ -353,6 +353,7 @@ struct vsf_ctx {
   int ingest_flip = 0;
   VsfDecodeScratch ingest_scratch;
   VsfEncodeScratch encode;  // vsf_jpeg_encode* / vsf_png_encode*
+  VsfBagScratch bag;        // vsf_bag_extract_batch
   vsfi::DevBuf<uint8_t> mh_desc;  // host-API descriptor staging: 2 sets
   vsfi::DevBuf<int32_t> mh_counts;
   vsfi::DevBuf<vsf_dmatch> mh_matches;

@@ -329,6 +329,181 @@ vsf_status vsf_to_gray(vsf_ctx* ctx, const uint8_t* src, int n_images, int width
   return VSF_OK;
 }
 
+// Every raw pixel format -> B G R (k_to_bgr.hip): the four Bayer orders (cvtColor(COLOR_Bayer??2BGR), bag_extract.cc:78-82), and the
+// packed formats as cv_bridge converts them for "bgr8".  The sibling of vsf_to_gray_batch_dev; the destination is
+// vsf_imdecode_bgr_batch's layout.
+vsf_status vsf_to_bgr_batch_dev(vsf_ctx* ctx, const uint8_t* d_src, int n_images, int width, int height, int pixfmt,
+                                size_t src_image_stride, size_t src_row_stride, uint8_t* d_dst, size_t dst_image_stride,
+                                size_t dst_row_stride) {
+  VsfErrorScope scope_(ctx);
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (!ctx || !d_src || !d_dst || bpp == 0 || n_images < 1 || width < 1 || height < 1 || width > 16384 || height > 65535 ||
+      n_images > 65535)
+    return VSF_ERR_INVALID_ARG;
+  if (((uintptr_t)d_src & 3) || ((uintptr_t)d_dst & 3) || (src_image_stride & 3) || (src_row_stride & 3) ||
+      (dst_image_stride & 3) || (dst_row_stride & 3) || src_row_stride < (size_t)width * (size_t)bpp ||
+      dst_row_stride < ((3 * (size_t)width + 3) & ~(size_t)3) || src_row_stride * (size_t)height > 0x7FFFFFFF ||
+      dst_row_stride * (size_t)height > 0x7FFFFFFF || src_image_stride < src_row_stride * (size_t)height ||
+      dst_image_stride < dst_row_stride * (size_t)height)
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  vsf_launch_to_bgr(pixfmt, d_src, n_images, width, height, src_image_stride, (int)src_row_stride, d_dst, dst_image_stride,
+                    (int)dst_row_stride, ctx->stream);
+  VSF_STICKY();
+  return record_ingest_done(ctx);
+}
+
+// vsf_to_bgr_batch_dev host to host: upload, the one launch, download (device staging shared with vsf_to_gray and the encoders).
+vsf_status vsf_to_bgr(vsf_ctx* ctx, const uint8_t* src, int n_images, int width, int height, int pixfmt, size_t src_image_stride,
+                      size_t src_row_stride, uint8_t* dst, size_t dst_image_stride, size_t dst_row_stride) {
+  VsfErrorScope scope_(ctx);
+  const int bpp = vsf_pixfmt_bytes_per_pixel(pixfmt);
+  if (!ctx || !src || !dst || bpp == 0 || n_images < 1 || n_images > 65535 || width < 1 || height < 1 || width > 16384 ||
+      height > 32767 || src_row_stride < (size_t)width * (size_t)bpp || dst_row_stride < 3 * (size_t)width)
+    return VSF_ERR_INVALID_ARG;
+  const size_t n = (size_t)n_images, row = (size_t)width * (size_t)bpp, out_row = 3 * (size_t)width;
+  if (n > 1 && (src_image_stride < (size_t)(height - 1) * src_row_stride + row ||
+                dst_image_stride < (size_t)(height - 1) * dst_row_stride + out_row))
+    return VSF_ERR_INVALID_ARG;
+  VSF_HIP(hipSetDevice(ctx->device));
+  // device staging: sources | destinations, rows at a multiple of 4 on both sides (the kernels' rule)
+  const size_t sp = (row + 3) & ~(size_t)3, dp = (out_row + 3) & ~(size_t)3;
+  const size_t s_img = (sp * (size_t)height + 15) & ~(size_t)15, d_img = (dp * (size_t)height + 15) & ~(size_t)15;
+  if (s_img > 0x7FFFFFFFu || d_img > 0x7FFFFFFFu) return VSF_ERR_INVALID_ARG;
+  const size_t need = n * (s_img + d_img);
+  VsfEncodeScratch& e = ctx->encode;
+  if (need > e.staging_cap) {
+    const vsf_status gs = grow_scratch(ctx, e.staging, need);
+    if (gs != VSF_OK) return gs;
+    e.staging_cap = need;
+  }
+  uint8_t* d_src = e.staging;
+  uint8_t* d_dst = d_src + n * s_img;
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(d_src + i * s_img, sp, src + i * src_image_stride, src_row_stride, row, (size_t)height,
+                             hipMemcpyHostToDevice, ctx->stream));
+  vsf_launch_to_bgr(pixfmt, d_src, n_images, width, height, s_img, (int)sp, d_dst, d_img, (int)dp, ctx->stream);
+  for (size_t i = 0; i < n; i++)
+    VSF_HIP(hipMemcpy2DAsync(dst + i * dst_image_stride, dst_row_stride, d_dst + i * d_img, dp, out_row, (size_t)height,
+                             hipMemcpyDeviceToHost, ctx->stream));
+  VSF_HIP(hipStreamSynchronize(ctx->stream));
+  VSF_STICKY();
+  return VSF_OK;
+}
+
+// src/test/bag_extract.cc:73-90 for n payloads of one size: cv::imdecode(data, 1); on a "bayer_rggb8" topic cv::split -> channel 0
+// -> cvtColor(COLOR_BayerBG2BGR); cv::imwrite(".jpg") (quality 95).  Host to host, synchronous; between the stages nothing leaves
+// the device.  The mosaic is channel 0 of the COLOUR read of every file.  Per file, from the frame header the host parser reads:
+//   a JPEG file of ONE component -- B = G = R = Y, and with one component vsf_jpeg_plan does the same in both output formats (its
+//     colour argument acts on three components only), so the refusals are the same too -- is decoded by the gray decoders straight
+//     into its mosaic;
+//   every other file (three components: the mosaic is the BLUE channel, not the gray read; every PNG: the gray read of a PNG
+//     refuses gamma chunks the colour read ignores) takes the colour decode, and k_to_bgr.hip keeps the first byte of every pixel.
+vsf_status vsf_bag_extract_batch(vsf_ctx* ctx, const uint8_t* const* files, const size_t* nbytes, int n_images, int width,
+                                 int height, int bayer_pixfmt, int quality, uint8_t* out, size_t out_stride, int32_t* out_bytes) {
+  VsfErrorScope scope_(ctx);
+  if (out_bytes && n_images >= 1 && n_images <= 65535)
+    for (int i = 0; i < n_images; i++) out_bytes[i] = -1;  // (whatever follows: no partial delivery)
+  const bool bayer = bayer_pixfmt != 0;
+  if (bayer && bayer_pixfmt != VSF_PIX_BAYER_RGGB8 && bayer_pixfmt != VSF_PIX_BAYER_GRBG8 && bayer_pixfmt != VSF_PIX_BAYER_GBRG8 &&
+      bayer_pixfmt != VSF_PIX_BAYER_BGGR8)
+    return VSF_ERR_INVALID_ARG;
+  if (!ctx || !files || !nbytes || !out || !out_bytes || n_images < 1 || n_images > 65535 || width < 1 || height < 1 ||
+      width > 65535 || height > 65535 || quality < 0 || quality > 100 || out_stride < 1)
+    return VSF_ERR_INVALID_ARG;
+  const size_t n = (size_t)n_images;
+  const size_t bp = (3 * (size_t)width + 3) & ~(size_t)3, mp = ((size_t)width + 3) & ~(size_t)3;  // rows of B G R / of a mosaic
+  if (bp * (size_t)height > 0x7FFFFFFF || (bayer && width > 16384)) return VSF_ERR_INVALID_ARG;  // (vsf_to_bgr_batch_dev's limits)
+  // which decode each file takes: kinds_bgr / kinds_gray name the file in ONE of the two lists and VSF_FILE_NONE in the other
+  std::vector<uint8_t> kinds_bgr(n), kinds_gray(n, (uint8_t)VSF_FILE_NONE);
+  size_t n_gray = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!files[i] || nbytes[i] > 0x40000000u) return VSF_ERR_INVALID_ARG;
+    kinds_bgr[i] = (uint8_t)vsf_file_kind(files[i], nbytes[i]);
+    if (kinds_bgr[i] == VSF_FILE_NONE) return VSF_ERR_UNSUPPORTED;
+    if (nbytes[i] < (kinds_bgr[i] == VSF_FILE_JPEG ? 4u : 8u)) return VSF_ERR_INVALID_ARG;
+    if (bayer && kinds_bgr[i] == VSF_FILE_JPEG && vsf_jpeg_frame_components(files[i], nbytes[i]) == 1) {
+      kinds_gray[i] = VSF_FILE_JPEG;
+      kinds_bgr[i] = VSF_FILE_NONE;
+      n_gray++;
+    }
+  }
+  VSF_HIP(hipSetDevice(ctx->device));
+  // scratch: [the mosaics | what cv::imwrite gets | the colour reads in front of cv::split] on a Bayer topic, else the colour reads alone
+  const size_t bgr_img = (bp * (size_t)height + 15) & ~(size_t)15, mono_img = (mp * (size_t)height + 15) & ~(size_t)15;
+  const size_t files_bytes = (n * out_stride + 15) & ~(size_t)15;
+  VsfBagScratch& b = ctx->bag;
+  const size_t images_need = !bayer ? n * bgr_img : n * (mono_img + bgr_img) + (n_gray < n ? n * bgr_img : 0);
+  vsf_status st = grow_decode_scratch(ctx, b.images, b.images_cap, images_need);
+  if (st == VSF_OK) st = grow_decode_scratch(ctx, b.files, b.files_cap, files_bytes + n * sizeof(int32_t));
+  if (st != VSF_OK) return st;
+  uint8_t* d_mosaic = b.images;
+  uint8_t* d_colour = bayer ? d_mosaic + n * mono_img : b.images.get();  // what cv::imwrite gets
+  uint8_t* d_read = bayer ? d_colour + n * bgr_img : d_colour;             // cv::imdecode(data, 1)
+  uint8_t* d_files = b.files;
+  int32_t* d_bytes = reinterpret_cast<int32_t*>(d_files + files_bytes);
+  bool launched = false;
+  for (int pass = 0; pass < 2 && st == VSF_OK; pass++) {  // the colour reads, then the gray ones: a staging pair each
+    if (pass == 0 ? n_gray == n : n_gray == 0) continue;
+    VsfStaging& stage = ctx->ingest_stage[ctx->ingest_flip];
+    if (!stage.uploaded) VSF_HIP(stage.uploaded.alloc(hipEventDisableTiming));
+    st = pass == 0 ? decode_runs(ctx, files, nbytes, kinds_bgr.data(), n_images, width, height, stage, ctx->ingest_scratch, d_read,
+                                 bgr_img, (int)bp, ctx->d_status, 0, ctx->stream, nullptr, nullptr, VSF_OUT_BGR)
+                   : decode_runs(ctx, files, nbytes, kinds_gray.data(), n_images, width, height, stage, ctx->ingest_scratch,
+                                 d_mosaic, mono_img, (int)mp, ctx->d_status, 0, ctx->stream, nullptr, nullptr, VSF_OUT_GRAY);
+    if (st != VSF_OK) break;  // (refused by the host half -- another size among them --: this pass uploaded and launched nothing)
+    ctx->ingest_flip ^= 1;
+    launched = true;
+  }
+  if (st != VSF_OK) {
+    if (launched) (void)check_status_word(ctx);  // the other pass is under way: wait for it and drop what it reports
+    return st;
+  }
+  if (bayer) {
+    for (int i0 = 0, i1; i0 < n_images; i0 = i1) {  // cv::split -> channel 0 of every run of colour reads
+      i1 = vsf_run_end(kinds_gray.data(), n_images, i0);
+      if (kinds_gray[i0] != VSF_FILE_NONE) continue;
+      vsf_launch_bgr_channel0(d_read + (size_t)i0 * bgr_img, i1 - i0, width, height, bgr_img, (int)bp, d_mosaic + (size_t)i0 * mono_img,
+                              mono_img, (int)mp, ctx->stream);
+    }
+    vsf_launch_to_bgr(bayer_pixfmt, d_mosaic, n_images, width, height, mono_img, (int)mp, d_colour, bgr_img, (int)bp, ctx->stream);
+  }
+  VSF_STICKY();
+  st = encode_batch_dev(ctx, {VSF_FILE_JPEG, n_images, width, height, 3, bgr_img, bp, quality, out_stride, 0}, d_colour, d_files,
+                        d_bytes);
+  std::vector<int32_t> sizes(n, -1);
+  if (st == VSF_OK) VSF_HIP(hipMemcpyAsync(sizes.data(), d_bytes, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  const vsf_status word = check_status_word(ctx);  // synchronises (and clears what the decoders reported, whatever the encoder said)
+  if (st == VSF_OK) st = word;
+  if (st != VSF_OK && st != VSF_ERR_CAPACITY) return st;
+  // The files home: packed one behind the other into pinned memory by asynchronous copies, ONE wait, then the host's own copies
+  // into the caller's slots (a hipMemcpy into pageable memory waits for itself, file after file).
+  size_t total = 0;
+  for (size_t i = 0; i < n; i++)
+    if (sizes[i] > 0) total += ((size_t)sizes[i] + 15) & ~(size_t)15;
+  if (total > b.home_cap) {  // (the stream is idle: nothing reads the outgrown buffer)
+    b.home_cap = 0;
+    VSF_HIP(b.home.alloc(total + total / 4, hipHostMallocDefault));
+    b.home_cap = total + total / 4;
+  }
+  size_t off = 0;
+  for (size_t i = 0; i < n; i++)
+    if (sizes[i] > 0) {
+      VSF_HIP(hipMemcpyAsync(b.home + off, d_files + i * out_stride, (size_t)sizes[i], hipMemcpyDeviceToHost, ctx->stream));
+      off += ((size_t)sizes[i] + 15) & ~(size_t)15;
+    }
+  VSF_HIP(hipStreamSynchronize(ctx->stream));
+  off = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (sizes[i] > 0) {
+      std::memcpy(out + i * out_stride, b.home + off, (size_t)sizes[i]);
+      off += ((size_t)sizes[i] + 15) & ~(size_t)15;
+    }
+    out_bytes[i] = sizes[i] > 0 ? sizes[i] : -1;
+  }
+  return st;
+}
+
 // cv::imdecode(IMREAD_GRAYSCALE) for JPEG files (slam_frontend_main.cc:99-100): markers and tables on the host, the entropy
 // decode and the IDCT on the device (k_jpeg.hip).
 vsf_status vsf_jpeg_decode_gray_batch(vsf_ctx* ctx, const uint8_t* const* jpeg, const size_t* nbytes, int n_images,

@@ -124,6 +124,31 @@ vsf_status vsf_compressed_image_size(const uint8_t* file, size_t nbytes, int* wi
   return VSF_OK;
 }
 
+}  // extern "C"
+
+// The component count of a JPEG file's frame header -- the first SOF0 / SOF1 / SOF2 segment, reached by the walk of
+// vsf_compressed_image_size above; vsf_jpeg_plan takes its ncomp from the same segment and refuses a second one.  0: no such
+// segment in front of the data.
+int vsf_jpeg_frame_components(const uint8_t* file, size_t nbytes) {
+  if (vsf_file_kind(file, nbytes) != VSF_FILE_JPEG) return 0;
+  size_t pos = 2;
+  while (pos + 4 <= nbytes) {
+    if (file[pos] != 0xFF) return 0;
+    while (pos < nbytes && file[pos] == 0xFF) pos++;
+    if (pos >= nbytes) return 0;
+    const int m = file[pos++];
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+    if (m == 0xD9 || m == 0xDA || pos + 2 > nbytes) return 0;
+    const size_t len = ((size_t)file[pos] << 8) | file[pos + 1];
+    if (len < 2 || len > nbytes - pos) return 0;
+    if (m >= 0xC0 && m <= 0xC2) return len >= 8 ? file[pos + 7] : 0;
+    pos += len;
+  }
+  return 0;
+}
+
+extern "C" {
+
 // What libjpeg's jpeg_calc_output_dimensions makes of w x h at scale 1 / reduce -- the size cv::imdecode returns for
 // IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8 (reduce = 1: the size itself).
 vsf_status vsf_reduced_size(int w, int h, int reduce, int* rw, int* rh) {

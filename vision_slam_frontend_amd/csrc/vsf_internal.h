@@ -462,6 +462,7 @@ enum { VSF_FILE_NONE = 0, VSF_FILE_JPEG = 1, VSF_FILE_PNG = 2 };  // (ObserveFra
 enum { VSF_OUT_GRAY = 0, VSF_OUT_BGR = 1 };  // what a decode writes: cv::IMREAD_GRAYSCALE's byte or cv::IMREAD_COLOR's three
 int vsf_file_kind(const uint8_t* file, size_t nbytes);  // by the first bytes, as cv::imdecode's findDecoder tells them apart
 int vsf_run_end(const uint8_t* kinds, int n, int i0);   // one past the last file of the run of one kind that starts at i0
+int vsf_jpeg_frame_components(const uint8_t* file, size_t nbytes);  // Nf of the first SOF0 / SOF1 / SOF2 segment; 0: none found
 // The denominators a decode takes, stated ONCE: 1 (full size) and cv::IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8.
 inline bool vsf_reduce_ok(int reduce) { return reduce == 1 || reduce == 2 || reduce == 4 || reduce == 8; }
 // what cv::resize on the device takes on either side (vsf_resize_gray_batch_dev): VsfTap's 16-bit fields hold the taps
@@ -547,6 +548,21 @@ struct VsfIngestSrc {
 #define VSF_INGEST_INLINE 8
 void vsf_launch_ingest_ring(uint8_t* d_ring, size_t image_stride, int dst_pitch, int w, int h, int slot0, int depth, int n_frames,
                             const VsfIngestSrc* inl, const VsfIngestSrc* table, hipStream_t s);
+
+// k_to_bgr.hip (bag_extract.cc:75-88): n raw images of any VSF_PIX_* format -> B G R, three bytes a pixel, ONE launch; bases and
+// pitches are multiples of 4, src_pitch >= w * bpp, dst_pitch >= (3 w + 3) & ~3 (the callers have checked).  An unknown format
+// launches nothing.  And cv::split(image)[0]: the first byte of every B G R pixel, one byte a pixel (dst_pitch >= (w + 3) & ~3).
+void vsf_launch_to_bgr(int pixfmt, const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch, uint8_t* d_dst,
+                       size_t dst_image_stride, int dst_pitch, hipStream_t s);
+void vsf_launch_bgr_channel0(const uint8_t* d_src, int n, int w, int h, size_t src_image_stride, int src_pitch, uint8_t* d_dst,
+                             size_t dst_image_stride, int dst_pitch, hipStream_t s);
+// vsf_bag_extract_batch: the images between its stages (the mosaics | the demosaiced B G R | the colour reads), what goes home (files
+// | byte counts) and the pinned buffer it goes through, on the context's stream.  Grown as the decoders' scratch is (a quarter of headroom, no wait; never shrunk).
+struct VsfBagScratch {
+  vsfi::DevBuf<uint8_t> images, files;
+  vsfi::PinnedBuf<uint8_t> home;  // the files of one call packed one behind the other, on their way to the caller's slots
+  size_t images_cap = 0, files_cap = 0, home_cap = 0;
+};
 
 // k_resize.hip: cv::resize (INTER_LINEAR, CV_8UC1) of n images of sw x sh into dw x dh, any base address and pitch on either
 // side; ONE launch (per 65535 images).  The caller has checked the sizes (1 .. 32767) and the pitches (>= the widths).

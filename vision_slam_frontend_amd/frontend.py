@@ -133,6 +133,14 @@ def lib() -> C.CDLL:
         L.vsfh_time_visualization.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_longlong)]
         L.vsfh_time_visualization.restype = dbl
         L.vsfh_queue_stats.argtypes = [vp, vp, i32]
+        L.vsfh_bag_extract_create.argtypes = [i32, i32, i32]
+        L.vsfh_bag_extract_create.restype = vp
+        L.vsfh_bag_extract_destroy.argtypes = [vp]
+        L.vsfh_bag_extract_destroy.restype = None
+        L.vsfh_bag_extract_run.argtypes = [vp, vp, vp, i32, C.c_char_p, vp, sz, C.POINTER(i32), C.POINTER(i32)]
+        L.vsfh_bag_extract_run.restype = sz
+        L.vsfh_bag_extract_path.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, vp, sz]
+        L.vsfh_bag_extract_path.restype = sz
         _lib = L
     return _lib
 
@@ -171,6 +179,47 @@ def add_feature_points(cam_to_robot, loc, quat_xyzw, point3d) -> np.ndarray:
     out = np.zeros((max(len(p), 1), 3), np.float64)
     n = lib().vsfh_add_feature_points(_p(c), _p(l), _p(q), _p(p), len(p), _p(out))
     return out[:n].copy()
+
+
+def bag_extract_path(output: str, count: int, index: int) -> str:
+    """slam::BagExtractPath: the reference's file name for message `index` of `count` (src/test/bag_extract.cc:81-87)."""
+    buf = C.create_string_buffer(len(output) + 64)
+    n = lib().vsfh_bag_extract_path(output.encode(), count, index, buf, len(buf))
+    return buf.raw[:n].decode()
+
+
+class BagExtract:
+    """slam::BagExtract (host/bag_extract.h): serialized sensor_msgs/CompressedImage messages -> colour JPEG files on disk, as
+    src/test/bag_extract.cc writes them; decode, demosaic and encode run on the GPU (vsf_bag_extract_batch)."""
+
+    def __init__(self, device: int = 0, quality: int = 0, max_per_call: int = 512):
+        self._h = lib().vsfh_bag_extract_create(device, quality, max_per_call)
+        self.last_status = capi.VSF_OK
+        self.calls = 0
+
+    def close(self):
+        if self._h:
+            lib().vsfh_bag_extract_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def run(self, messages, output: str):
+        """-> the paths written, in message order ('' where a message gave no file; see last_status)."""
+        blob = np.frombuffer(b"".join(bytes(m) for m in messages) or b"\0", np.uint8)
+        offsets = np.zeros(len(messages) + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(m) for m in messages], dtype=np.uint64)
+        st, calls = C.c_int32(0), C.c_int32(0)
+        buf = C.create_string_buffer((len(output) + 64) * max(len(messages), 1))
+        n = lib().vsfh_bag_extract_run(self._h, _p(blob), _p(offsets), len(messages), output.encode(), buf, len(buf),
+                                       C.byref(st), C.byref(calls))
+        assert n <= len(buf)
+        self.last_status, self.calls = st.value, calls.value
+        return buf.raw[:n].decode().split("\n")[:len(messages)]
 
 
 def default_calibration() -> capi.VsfCalibration:

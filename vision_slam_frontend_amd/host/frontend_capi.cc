@@ -4,6 +4,7 @@
 #include <vector>
 #include <cstring>
 
+#include "bag_extract.h"
 #include "slam_frontend.h"
 #include "slam_to_ros.h"
 
@@ -568,6 +569,33 @@ size_t vsfh_group_serialize_problem(void* g, int i, uint8_t* out, size_t cap) {
   slam_to_ros::SerializeSLAMProblem(p, &bytes);
   if (out && cap) std::memcpy(out, bytes.data(), bytes.size() < cap ? bytes.size() : cap);
   return bytes.size();
+}
+
+// slam::BagExtract (bag_extract.h: src/test/bag_extract.cc without the bag).  quality 0 = 95; max_per_call < 1 = 512.
+void* vsfh_bag_extract_create(int device, int quality, int max_per_call) {
+  return new slam::BagExtract(device, quality, max_per_call < 1 ? 512 : (size_t)max_per_call);
+}
+void vsfh_bag_extract_destroy(void* b) { delete static_cast<slam::BagExtract*>(b); }
+// n serialized sensor_msgs/CompressedImage messages, message j = blob[offsets[j], offsets[j + 1]).  The paths in message order,
+// each followed by '\n' (an empty line: no file for that message), into `paths`: returns their total size and copies
+// min(size, cap) bytes.  *status: BagExtract::last_status(); *calls: vsf_bag_extract_batch calls made.
+size_t vsfh_bag_extract_run(void* b, const uint8_t* blob, const size_t* offsets, int n, const char* output, char* paths, size_t cap,
+                            int* status, int* calls) {
+  slam::BagExtract* be = static_cast<slam::BagExtract*>(b);
+  std::vector<std::pair<const uint8_t*, size_t>> msgs;
+  for (int j = 0; j < n; j++) msgs.emplace_back(blob + offsets[j], offsets[j + 1] - offsets[j]);
+  std::string all;
+  for (const std::string& p : be->Run(msgs, output ? output : "")) all += p + "\n";
+  if (status) *status = (int)be->last_status();
+  if (calls) *calls = (int)be->calls();
+  if (paths && cap) std::memcpy(paths, all.data(), all.size() < cap ? all.size() : cap);
+  return all.size();
+}
+// slam::BagExtractPath: returns the path's size and copies min(size, cap) bytes.
+size_t vsfh_bag_extract_path(const char* output, uint64_t count, uint64_t index, char* out, size_t cap) {
+  const std::string p = slam::BagExtractPath(output ? output : "", count, index);
+  if (out && cap) std::memcpy(out, p.data(), p.size() < cap ? p.size() : cap);
+  return p.size();
 }
 
 }  // extern "C"
