@@ -316,6 +316,55 @@ vsf_status vsf_stereo_batch_dev(vsf_ctx* ctx, const uint8_t* d_imgs, int n_frame
                                 size_t row_stride, vsf_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts,
                                 vsf_dmatch* d_matches, int32_t* d_nmatches);
 
+/* ---------------- Detection masks: detectAndCompute's second argument (slam_frontend.cc:274-277) ----------------
+ * The reference passes cv::noArray() there; a rig with its hood, the other eye's housing, a rectification wedge or a time
+ * stamp in view passes a mask instead.  The rule below is RESTATED FROM MEMORY (OpenCV 3.2 orb.cpp / keypoint.cpp), not read
+ * from the sources:
+ *   - detectAndCompute builds a mask pyramid beside the image pyramid: level 0 is the caller's mask unchanged; level l >= 1 is
+ *     resize(level l - 1, size_l, INTER_LINEAR) followed by threshold(., 254, 0, THRESH_TOZERO), taken from the already
+ *     thresholded level l - 1.  A pixel of a level >= 1 is therefore 255 or 0, and 255 only where the fixed-point
+ *     interpolation gives exactly 255; a masked region erodes from level to level.
+ *   - computeKeyPoints, per level: FAST, then KeyPointsFilter::runByPixelsMask drops a corner whose own pixel
+ *     mask_l[(int)(y + 0.5f)][(int)(x + 0.5f)] is 0, then runByImageBorder, retainBest(2 n_l), HarrisResponses,
+ *     retainBest(n_l) (FAST_SCORE: the one cut), angles, blur, descriptors as without a mask.  The filter runs BEFORE both
+ *     cuts: a slot a masked corner frees goes to the next-best corner of that level.  Level 0 passes any non-zero value,
+ *     levels >= 1 only 255-derived pixels (a mask of 254 everywhere leaves level-0 keypoints only).
+ *   - FastFeatureDetector::detect(image, kps, mask) (vsf_fast_detect) is the level-0 rule alone.
+ * A mask is context state, set once per rig and kept in a slot: vsf_mask_set builds the slot's pyramid on the device (one byte
+ * a pixel and level: vsf_mask_slot_bytes), and FAST applies the predicate where it emits its candidates -- no launch is added
+ * and, with no mask in a launch, the kernels are the ones without the predicate.  Every capacity rule stays: a mask only
+ * removes candidates.  With no mask set every output of every call is what it was.
+ * Ordering: vsf_mask_set, vsf_mask_set_dev and vsf_mask_clear FLUSH INSIDE -- they send every frame that waits in the
+ * ObserveImage queue, wait for every stream of the context, change the slot, and (set) return when the slot's pyramid is built:
+ * every frame submitted before the call is extracted with the slot as it was, every frame and call after it sees the new
+ * state.  They are calls for when the rig changes, not per frame. */
+#define VSF_MAX_MASKS 64 /* 32 streams x 2 eyes */
+/* mask: w x h bytes (the context's size), rows `stride` >= w bytes apart, any base address; host memory, resp. device memory
+ * that stays valid until the call returns.  VSF_ERR_INVALID_ARG (slot unchanged): a null pointer, another size, stride < w,
+ * slot outside [0, VSF_MAX_MASKS). */
+vsf_status vsf_mask_set(vsf_ctx* ctx, int slot, const uint8_t* mask, int w, int h, size_t stride);
+vsf_status vsf_mask_set_dev(vsf_ctx* ctx, int slot, const uint8_t* d_mask, int w, int h, size_t stride);
+/* The slot holds no mask again (its memory is kept for the next set): images that name it are extracted without a mask. */
+vsf_status vsf_mask_clear(vsf_ctx* ctx, int slot);
+/* *is_set: 1 while the slot holds a mask. */
+vsf_status vsf_mask_is_set(const vsf_ctx* ctx, int slot, int* is_set);
+/* Bytes of device memory a set slot holds: one image's pyramid block, level 0 included. */
+vsf_status vsf_mask_slot_bytes(const vsf_ctx* ctx, size_t* bytes);
+/* Which slot the images of vsf_extract, vsf_extract_pair, vsf_extract_batch_dev, vsf_stereo_batch_dev, vsf_observe_stereo*
+ * and vsf_fast_detect take: image i of a call `even_slot` when i is even (the left eye), `odd_slot` when i is odd; -1: no
+ * mask.  Default (-1, -1).  A slot that holds no mask when the call is made is no mask.  Not for the ObserveImage queue's
+ * submits: vsf_observe_set_stream_masks. */
+vsf_status vsf_set_image_masks(vsf_ctx* ctx, int even_slot, int odd_slot);
+vsf_status vsf_get_image_masks(const vsf_ctx* ctx, int* even_slot, int* odd_slot);
+/* The queue's frames of `stream` (every submit form: raw, pix, compressed, reduced, device frames) take left_slot for the left
+ * image and right_slot for the right one; -1: no mask; default (-1, -1), kept until set again.  A frame takes what its stream
+ * names when it is SUBMITTED (as it takes the stream's pose), and the mask applies to the frame as the context extracts it:
+ * after decode, gray conversion and the resize of a declared input size -- a mask is at the context's size.  Frames of several
+ * streams with different slots, and frames without, share batches. */
+vsf_status vsf_observe_set_stream_masks(vsf_ctx* ctx, int stream, int left_slot, int right_slot);
+/* Test hook: level `level` of the slot's pyramid as 0 / non-zero bytes, level_w x level_h (vsf_level_info) at `ostride`. */
+vsf_status vsf_debug_mask_level(vsf_ctx* ctx, int slot, int level, uint8_t* out, size_t ostride);
+
 /* ---------------- the reference's own steps between matcher and outputs, on the device ---------------- */
 
 /* Frontend::RemoveAmbigStereo (slam_frontend.cc:353-398) for n_frames stereo frames in time order, applied to the

@@ -59,7 +59,11 @@ EXPORTS = [
     "vsf_pixfmt_bytes_per_pixel", "vsf_pixfmt_from_encoding", "vsf_to_gray_batch_dev",
     "vsf_observe_submit_stream_pix", "vsf_observe_set_bayer_order", "vsf_to_gray",
     "vsf_to_bgr_batch_dev", "vsf_to_bgr", "vsf_bag_extract_batch",
+    "vsf_mask_set", "vsf_mask_set_dev", "vsf_mask_clear", "vsf_mask_is_set", "vsf_mask_slot_bytes", "vsf_set_image_masks",
+    "vsf_get_image_masks", "vsf_debug_mask_level", "vsf_observe_set_stream_masks",
 ]
+MAX_MASKS = 64  # VSF_MAX_MASKS
+NO_MASK = -1
 # vsf_option (include/vsf.h)
 (OPT_FAST_BOTH_MAX, OPT_SELECT_WIDE, OPT_PYRAMID_FEW, OPT_PYRAMID_CHAIN, OPT_PYRAMID_ROWS, OPT_SELECT_BIG_CLASS,
  OPT_PIPE_AFTER_FAST, OPT_PIPE_PRIORITY, OPT_OBSERVE_THREAD, OPT_PYRAMID_TAIL_MIN, OPT_OBSERVE_COPY_THREAD,
@@ -278,6 +282,15 @@ def lib() -> C.CDLL:
         L.vsf_reserve.argtypes = [vp, i32, i32]
         L.vsf_set_blur_overlap.argtypes = [vp, i32]
         L.vsf_set_fast_resident.argtypes = [vp, i32]
+        L.vsf_mask_set.argtypes = [vp, i32, vp, i32, i32, sz]
+        L.vsf_mask_set_dev.argtypes = [vp, i32, vp, i32, i32, sz]
+        L.vsf_mask_clear.argtypes = [vp, i32]
+        L.vsf_mask_is_set.argtypes = [vp, i32, ip]
+        L.vsf_mask_slot_bytes.argtypes = [vp, C.POINTER(sz)]
+        L.vsf_set_image_masks.argtypes = [vp, i32, i32]
+        L.vsf_get_image_masks.argtypes = [vp, ip, ip]
+        L.vsf_debug_mask_level.argtypes = [vp, i32, i32, vp, sz]
+        L.vsf_observe_set_stream_masks.argtypes = [vp, i32, i32, i32]
         L.vsf_get_fast_resident.argtypes = [vp, C.POINTER(C.c_int)]
         L.vsf_tune_fast_resident.argtypes = [vp, vp, i32, sz, sz, vp, vp, vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.vsf_set_option.argtypes = [vp, i32, i32]
@@ -533,6 +546,49 @@ class Context:
         w = C.c_int(-1)
         self._check(lib().vsf_get_fast_resident(self._h, C.byref(w)), "vsf_get_fast_resident")
         return w.value
+
+    # ---- detection masks (detectAndCompute's mask argument; include/vsf.h "Detection masks") ----
+    def mask_set(self, slot: int, mask: np.ndarray):
+        """BLOCKING: builds the slot's mask pyramid from a (height, width) uint8 array; non-zero = a corner may sit there."""
+        mask = _u8(mask)
+        self._check(lib().vsf_mask_set(self._h, int(slot), _p(mask), mask.shape[1], mask.shape[0], mask.strides[0]),
+                    "vsf_mask_set")
+
+    def mask_set_dev(self, slot: int, d_mask: int, w: int, h: int, stride: int):
+        self._check(lib().vsf_mask_set_dev(self._h, int(slot), C.c_void_p(d_mask), w, h, stride), "vsf_mask_set_dev")
+
+    def mask_clear(self, slot: int):
+        self._check(lib().vsf_mask_clear(self._h, int(slot)), "vsf_mask_clear")
+
+    def mask_is_set(self, slot: int) -> bool:
+        v = C.c_int()
+        self._check(lib().vsf_mask_is_set(self._h, int(slot), C.byref(v)), "vsf_mask_is_set")
+        return bool(v.value)
+
+    def mask_slot_bytes(self) -> int:
+        v = C.c_size_t()
+        self._check(lib().vsf_mask_slot_bytes(self._h, C.byref(v)), "vsf_mask_slot_bytes")
+        return int(v.value)
+
+    def set_image_masks(self, even_slot: int = NO_MASK, odd_slot: int = NO_MASK):
+        """Image i of the extraction calls takes even_slot when i is even (the left eye), odd_slot when odd; -1: none."""
+        self._check(lib().vsf_set_image_masks(self._h, int(even_slot), int(odd_slot)), "vsf_set_image_masks")
+
+    def get_image_masks(self):
+        a, b = C.c_int(), C.c_int()
+        self._check(lib().vsf_get_image_masks(self._h, C.byref(a), C.byref(b)), "vsf_get_image_masks")
+        return a.value, b.value
+
+    def observe_set_stream_masks(self, stream: int, left_slot: int = NO_MASK, right_slot: int = NO_MASK):
+        """The queue's frames of `stream` submitted from now on take these slots (left image, right image); -1: none."""
+        self._check(lib().vsf_observe_set_stream_masks(self._h, int(stream), int(left_slot), int(right_slot)),
+                    "vsf_observe_set_stream_masks")
+
+    def debug_mask_level(self, slot: int, level: int) -> np.ndarray:
+        w, h, _, _ = self.level_info(level)
+        out = np.empty((h, w), np.uint8)
+        self._check(lib().vsf_debug_mask_level(self._h, int(slot), level, _p(out), w), "vsf_debug_mask_level")
+        return out
 
     def set_pipeline(self, on: bool):
         self._check(lib().vsf_set_pipeline(self._h, int(on)), "vsf_set_pipeline")

@@ -56,6 +56,8 @@ struct FastArgs {
   uint16_t* rowstart;
   int threshold;
   int nms;
+  // MASK kernels only (the others never read these): the detection masks of the launch's images, include/vsf.h "Detection masks"
+  VsfFastMask mask;
 };
 
 __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) {  // lane i <- lane i-1
@@ -221,8 +223,14 @@ __device__ __forceinline__ ScoreRow make_score_row(v2s s02, v2s s13) {
 //               so downstream nothing changes.  (The pyramid's 50 levels end in a narrow band almost everywhere:
 //               packing them lowers the lanes a 640x480 image keeps busy by 14 %.)
 // NMS = false (standalone FAST without suppression only) keeps every corner and a zero response.
+// MASK = true: KeyPointsFilter::runByPixelsMask at emission -- a survivor of the suppression is dropped when its own pixel is
+//               zero in the mask level of its image (a slot's block: one byte a pixel, 0x00 / 0xFF, in the layout of one image's
+//               pyramid block with level 0 at its place).  The row of the cell about to be emitted is requested when its step
+//               begins and met where the survivors are known; an image without a mask reads an empty buffer and passes
+//               everything.  MASK = false is the kernel without any of it: the launcher takes it whenever no image of the
+//               launch has a mask.
 // (`work`: index into a.units (PACK = false) or into the packed items -- wave-uniform)
-template <bool PACK, bool NMS>
+template <bool PACK, bool NMS, bool MASK>
 __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int image) {
   const int lane = threadIdx.x & 63;
   int level, band, strip, hl, nl, nrows0 = 0;
@@ -317,6 +325,22 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
   const unsigned long long from_m = ~0ull << cfirst, cell_m = from_m & (cend >= 64 ? ~0ull : (1ull << cend) - 1ull);
   const uint32_t from_lo = (uint32_t)from_m, from_hi = (uint32_t)(from_m >> 32);
   const uint32_t cell_lo = (uint32_t)cell_m, cell_hi = (uint32_t)(cell_m >> 32);
+  // MASK: the image's block (wave-uniform), this lane's 4 bytes of cell row 0 in it; reads outside the block return 0
+  // (the pair's two pointers are read into values first: a choice between the two FIELDS put them on the stack)
+  const uint8_t* mk_block = nullptr;
+  if constexpr (MASK) {
+    const uint8_t* const mk_even = a.mask.even;
+    const uint8_t* const mk_odd = a.mask.odd;
+    const uint8_t* const* const mk_table = a.mask.table;
+    mk_block = ((image + a.mask.parity) & 1) ? mk_odd : mk_even;
+    if (mk_table) mk_block = mk_table[image];
+  }
+  const bool mk_has = mk_block != nullptr;
+  const __amdgpu_buffer_rsrc_t mk_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(mk_block), 0, MASK && mk_has ? a.mask.bytes : 0u, 0x00020000);
+  const int mk_pitch = L.pitch;
+  // (a lane whose dword is not inside a row of the level gets an offset beyond any block: it emits nothing)
+  const uint32_t mk_base = valid && c0 >= 0 && c0 + 3 < mk_pitch ? L.offset + (uint32_t)(c0 + ys * mk_pitch) : 0x40000000u;
 
   // buffer loads: a lane's column offset sits in a VGPR, the row offset in an SGPR (PACK: both per lane, the row clamp
   // folded into the range of q); reads outside the level return 0
@@ -359,6 +383,12 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
   auto step = [&](int q, const RowP& R0, const RowP& R1, const RowP& R2, const RowP& R3, const RowP& R4,
                   const RowP& R5, RowP& R6, const ScoreRow& S_up, const ScoreRow& S_mid, ScoreRow& S_dn) {
     prep_row(R6);  // the row that has just entered the window
+    uint32_t mk = 0;  // MASK: the mask bytes of this lane's 4 pixels of cell row q - 2
+    if constexpr (MASK) {
+      if (q >= 2 && q - 2 < nrows0)
+        mk = PACK ? __builtin_amdgcn_raw_buffer_load_b32(mk_rsrc, mk_base + (uint32_t)__mul24(q - 2, mk_pitch), 0u, 0)
+                  : __builtin_amdgcn_raw_buffer_load_b32(mk_rsrc, mk_base, (uint32_t)((q - 2) * mk_pitch), 0);
+    }
     v2s s02 = zero2, s13 = zero2;
     const int sy = ys - 1 + q;
     const bool row_ok = sy >= 3 && sy < hrow - 3;  // (wave-uniform unless PACK; PACK tests it only where a cell needs it)
@@ -398,6 +428,10 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
           k13 = as_u32(S_mid.s13) & em13;
         }
         if (PACK && mixed && r >= nrows) k02 = k13 = 0;  // (a cell of the item may have fewer rows)
+        if constexpr (MASK) {  // bytes 0 / 2 and 1 / 3 spread over the halves of the pair layout
+          k02 &= mk_has ? __builtin_amdgcn_perm(0u, mk, 0x02020000u) : ~0u;
+          k13 &= mk_has ? __builtin_amdgcn_perm(0u, mk, 0x03030101u) : ~0u;
+        }
         const uint32_t yx = yx0 + ((uint32_t)r << 12);
         if (NMS) {
           // Strict NMS: two neighbouring pixels cannot both survive, so at most one of pixels 0 / 1 and at most one of
@@ -494,23 +528,23 @@ __device__ __forceinline__ void fast_march_body(const FastArgs& a, int work, int
 
 // (`first`: the launch walks work items [first, first + nwork) -- the list of full cells may be cut in two,
 // vsf_fast_split.h; 0 for the packed items)
-template <bool PACK, bool NMS>
+template <bool PACK, bool NMS, bool MASK>
 __global__ __launch_bounds__(256) void fast_march_kernel(FastArgs a, int first, int nwork) {
   const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (item >= nwork) return;  // wave-uniform
-  fast_march_body<PACK, NMS>(a, first + item, blockIdx.y);
+  fast_march_body<PACK, NMS, MASK>(a, first + item, blockIdx.y);
 }
 
 // Full cells and the packed items in ONE launch, for batches that leave the chip nearly empty: there a launch lasts as
 // long as one cell's march, and two launches in a row last twice that.
-template <bool NMS>
+template <bool NMS, bool MASK>
 __global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int first, int nfull, int npack) {
   const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (item >= nfull + npack) return;  // wave-uniform
   if (item < nfull)
-    fast_march_body<false, NMS>(a, first + item, blockIdx.y);
+    fast_march_body<false, NMS, MASK>(a, first + item, blockIdx.y);
   else
-    fast_march_body<true, NMS>(a, item - nfull, blockIdx.y);
+    fast_march_body<true, NMS, MASK>(a, item - nfull, blockIdx.y);
 }
 
 // The same cells walked by ONE resident workgroup per CU (4 x `waves per SIMD` waves; a second one does not fit beside it, so
@@ -519,7 +553,7 @@ __global__ __launch_bounds__(256) void fast_march_both_kernel(FastArgs a, int fi
 // long as cells are left and whatever else is queued waits behind it; a fixed set of resident waves leaves the rest of each
 // SIMD's registers to the kernel beside it.  Alone, FAST reaches 93 % of the vector ALU's issue rate with five waves per
 // SIMD, the same with four, 92 % of that with three and 76 % with two (occupancy sweep, NOTES.md section 6).
-template <bool PACK, bool NMS>
+template <bool PACK, bool NMS, bool MASK>
 __global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, int first, int nwork, int nimages,
                                                                   uint32_t* next_cell) {
   // cells are handed out through a counter (zeroed by the launcher): a wave slowed down by its neighbours takes fewer
@@ -540,7 +574,7 @@ __global__ __launch_bounds__(1024) void fast_march_resident_kernel(FastArgs a, i
     const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
     if (u >= (uint32_t)total) break;
     const int image = (int)u / nwork, cell = (int)u - image * nwork;
-    fast_march_body<PACK, NMS>(a, first + cell, image);
+    fast_march_body<PACK, NMS, MASK>(a, first + cell, image);
   }
 }
 
@@ -579,8 +613,47 @@ __global__ __launch_bounds__(256) void fast_emit_kernel(const VsfLevel* __restri
 
 }  // namespace
 
+namespace {
+
+// The launches of one FAST pass, for kernels with (MASK) or without the mask predicate.
+template <bool MASK>
+void launch_fast_forms(const FastArgs& a, const VsfDev& d, const VsfImages& im, int nms, hipStream_t s, int resident_waves_per_simd,
+                       int n_cus, uint32_t* d_cell_counters, int part, int f0, int nf, int np) {
+  if (resident_waves_per_simd > 0 && resident_waves_per_simd <= 4 && nms && d_cell_counters) {
+    // (an early part runs on another stream than the late part of the call before it: a counter of its own)
+    uint32_t* cnt = part == VSF_FAST_EARLY ? d_cell_counters + 2 : d_cell_counters;
+    vsf_note(hipMemsetAsync(cnt, 0, (part == VSF_FAST_EARLY ? 1 : 2) * sizeof(uint32_t), s));
+    const dim3 block(256 * resident_waves_per_simd);
+    if (nf > 0)
+      hipLaunchKernelGGL((fast_march_resident_kernel<false, true, MASK>), dim3(n_cus), block, 0, s, a, f0, nf, im.n, cnt);
+    if (np > 0)
+      hipLaunchKernelGGL((fast_march_resident_kernel<true, true, MASK>), dim3(n_cus), block, 0, s, a, 0, np, im.n, cnt + 1);
+    return;
+  }
+  const dim3 gf((nf + 3) / 4, im.n), gp((np + 3) / 4, im.n);
+  const int both_max = d.tune ? d.tune->fast_both_max : 16;
+  if (im.n <= both_max && nf > 0 && np > 0) {
+    const dim3 gb((nf + np + 3) / 4, im.n);
+    if (nms)
+      hipLaunchKernelGGL((fast_march_both_kernel<true, MASK>), gb, dim3(256), 0, s, a, f0, nf, np);
+    else
+      hipLaunchKernelGGL((fast_march_both_kernel<false, MASK>), gb, dim3(256), 0, s, a, f0, nf, np);
+    return;
+  }
+  if (nms) {
+    if (nf > 0) hipLaunchKernelGGL((fast_march_kernel<false, true, MASK>), gf, dim3(256), 0, s, a, f0, nf);
+    if (np > 0) hipLaunchKernelGGL((fast_march_kernel<true, true, MASK>), gp, dim3(256), 0, s, a, 0, np);
+  } else {
+    if (nf > 0) hipLaunchKernelGGL((fast_march_kernel<false, false, MASK>), gf, dim3(256), 0, s, a, f0, nf);
+    if (np > 0) hipLaunchKernelGGL((fast_march_kernel<true, false, MASK>), gp, dim3(256), 0, s, a, 0, np);
+  }
+}
+
+}  // namespace
+
 void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int threshold, int nms, hipStream_t s,
-                     int resident_waves_per_simd, int n_cus, uint32_t* d_cell_counters, int part, int n_early) {
+                     int resident_waves_per_simd, int n_cus, uint32_t* d_cell_counters, int part, int n_early,
+                     const VsfFastMask* mask) {
   // the work of this launch: full cells [f0, f0 + nf) and np packed items
   n_early = std::min(std::max(n_early, 0), g.nwork_full);
   const int f0 = part == VSF_FAST_LATE ? n_early : 0;
@@ -601,34 +674,12 @@ void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int
   a.rowstart = d.rowstart;
   a.threshold = threshold;
   a.nms = nms;
-  if (resident_waves_per_simd > 0 && resident_waves_per_simd <= 4 && nms && d_cell_counters) {
-    // (an early part runs on another stream than the late part of the call before it: a counter of its own)
-    uint32_t* cnt = part == VSF_FAST_EARLY ? d_cell_counters + 2 : d_cell_counters;
-    vsf_note(hipMemsetAsync(cnt, 0, (part == VSF_FAST_EARLY ? 1 : 2) * sizeof(uint32_t), s));
-    const dim3 block(256 * resident_waves_per_simd);
-    if (nf > 0)
-      hipLaunchKernelGGL((fast_march_resident_kernel<false, true>), dim3(n_cus), block, 0, s, a, f0, nf, im.n, cnt);
-    if (np > 0)
-      hipLaunchKernelGGL((fast_march_resident_kernel<true, true>), dim3(n_cus), block, 0, s, a, 0, np, im.n, cnt + 1);
-    return;
-  }
-  const dim3 gf((nf + 3) / 4, im.n), gp((np + 3) / 4, im.n);
-  const int both_max = d.tune ? d.tune->fast_both_max : 16;
-  if (im.n <= both_max && nf > 0 && np > 0) {
-    const dim3 gb((nf + np + 3) / 4, im.n);
-    if (nms)
-      hipLaunchKernelGGL((fast_march_both_kernel<true>), gb, dim3(256), 0, s, a, f0, nf, np);
-    else
-      hipLaunchKernelGGL((fast_march_both_kernel<false>), gb, dim3(256), 0, s, a, f0, nf, np);
-    return;
-  }
-  if (nms) {
-    if (nf > 0) hipLaunchKernelGGL((fast_march_kernel<false, true>), gf, dim3(256), 0, s, a, f0, nf);
-    if (np > 0) hipLaunchKernelGGL((fast_march_kernel<true, true>), gp, dim3(256), 0, s, a, 0, np);
-  } else {
-    if (nf > 0) hipLaunchKernelGGL((fast_march_kernel<false, false>), gf, dim3(256), 0, s, a, f0, nf);
-    if (np > 0) hipLaunchKernelGGL((fast_march_kernel<true, false>), gp, dim3(256), 0, s, a, 0, np);
-  }
+  a.mask = mask ? *mask : VsfFastMask{};
+  // the kernels with the predicate only where an image of the launch may have a mask: every other launch is the one it was
+  if (a.mask.table || a.mask.even || a.mask.odd)
+    launch_fast_forms<true>(a, d, im, nms, s, resident_waves_per_simd, n_cus, d_cell_counters, part, f0, nf, np);
+  else
+    launch_fast_forms<false>(a, d, im, nms, s, resident_waves_per_simd, n_cus, d_cell_counters, part, f0, nf, np);
 }
 
 void vsf_launch_fast_emit(const VsfDev& d, const VsfGeom& g, int n_images, int max_keypoints, vsf_keypoint* d_kp,

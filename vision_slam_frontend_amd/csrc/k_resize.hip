@@ -32,9 +32,7 @@ struct ResizeArgs {
 
 constexpr int kResizeRows = 8;  // output rows per wave
 
-__device__ __forceinline__ uint32_t vresize(int h0, int h1, int b0, int b1) {
-  return (uint32_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
-}
+__device__ __forceinline__ uint32_t vresize(int h0, int h1, int b0, int b1) { return resize_vertical(h0, h1, b0, b1); }
 
 // the pixel at `addr` out of the aligned dword that holds it
 __device__ __forceinline__ int pixel_at(uintptr_t addr) {

@@ -193,6 +193,7 @@ struct ExtractHip {
   vsf_keypoint* d_kp;
   uint8_t* d_desc;
   int32_t* d_counts;
+  VsfFastMask mask;  // the images' detection masks (both FAST parts)
   bool early_fired = false;
 
   hipEvent_t event(VsfXEvent e) const {
@@ -237,11 +238,11 @@ struct ExtractHip {
         }
         case VSF_XG_FAST_EARLY:
           vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, s, ctx->tuning.fast_early_form, ctx->n_cus, ctx->fast_cells,
-                          VSF_FAST_EARLY, p.n_early);
+                          VSF_FAST_EARLY, p.n_early, &mask);
           break;
         case VSF_XG_FAST:
           vsf_launch_fast(d, g, im, ctx->p.fast_threshold, 1, s, p.resident, ctx->n_cus, ctx->fast_cells,
-                          p.n_early > 0 ? VSF_FAST_LATE : VSF_FAST_ALL, p.n_early);
+                          p.n_early > 0 ? VSF_FAST_LATE : VSF_FAST_ALL, p.n_early, &mask);
           break;
         case VSF_XG_SELECT: vsf_launch_select(d, g, ctx->orb.levels.data(), im, s); break;
         case VSF_XG_BLUR:
@@ -263,7 +264,7 @@ struct ExtractHip {
 // in which order is vsf_extract_plan.h's; this fills in the facts, the buffers the plan names and the handles.
 void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, int n, vsf_keypoint* d_kp,
                 uint8_t* d_desc, int32_t* d_counts, bool inputs_complete, const VsfSideStream* own_side, int32_t* status,
-                int status_stride) {
+                int status_stride, const VsfFastMask* masks) {
   const VsfGeom& g = ctx->orb.g;
   const VsfTuning& tn = ctx->tuning;
   VsfExtractFacts f{};
@@ -319,7 +320,8 @@ void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, i
                  side,
                  d_kp + i0 * K,
                  d_desc + i0 * K * VSF_DESC_BYTES,
-                 d_counts + i0};
+                 d_counts + i0,
+                 masks ? *masks : image_masks(ctx, i0)};
   vsf_extract_issue(p, hip);
 }
 

@@ -151,6 +151,7 @@ struct vsf_ctx {
     int stream = 0;              // vsf_observe_submit_stream: whose sequence it belongs to
     int64_t k = 0;               // frames of its stream in front of it (since the queue was built or the stream reset)
     vsf_pose pose{};             // vsf_observe_set_pose: what its stream's pose was when it was submitted (read with `cloud`)
+    int mask_slot[2] = {-1, -1};  // vsf_observe_set_stream_masks: its stream's left / right slot when it was submitted
     float cam_to_robot[12] = {0};  // ... and its stream's left_cam_to_robot (vsf_observe_set_stream_cam_to_robot, or the context's)
   };
   struct ObserveStream {  // host side of one sequence of frames (vsf_observe_set_streams)
@@ -291,6 +292,21 @@ struct vsf_ctx {
   DebugForm ob_debug_form;  // vsf_observe_set_debug_jpeg / _png: ... and hands them out as files (in force while ob_debug is)
   size_t ob_cmp_cap = 0;  // vsf_observe_set_compressed_cap: bytes per compressed file (0: the default for the image size)
   // ---- buffers: every stream above, the queue's two included, outlives them ----
+  // Detection masks (vsf_mask.hip, include/vsf.h "Detection masks"): a slot's block is built once, by vsf_mask_set, and read by
+  // FAST's predicate (VsfFastMask); a slot that is not set is no mask.  mask_even / mask_odd: vsf_set_image_masks.
+  struct MaskSlot {
+    vsfi::DevBuf<uint8_t> block;  // [orb.g.pyr_bytes], kept across vsf_mask_clear
+    bool set = false;
+  };
+  MaskSlot masks[VSF_MAX_MASKS];
+  int mask_even = -1, mask_odd = -1;
+  struct StreamMasks {  // vsf_observe_set_stream_masks: what the queue's frames of a stream take (kept like the poses)
+    int left = -1, right = -1;
+  } ob_masks[VSF_OBSERVE_MAX_STREAMS];
+  // a vsf_observe_stereo* call is submitting its frame, which takes mask_even / mask_odd (set and cleared by stereo_call's scope
+  // around the submit; a context is driven by one host thread at a time, vsf_internal.h, and the launcher thread never reads it:
+  // the frame's slots are captured on the caller's thread when it is booked)
+  bool ob_sync_call = false;
   vsfi::DevBuf<uint8_t> pyr_alt;  // the other pyramid buffer of cross-call pipelining
   vsfi::DevBuf<uint8_t> blur_alt;  // ... and the other blurred pyramid (buffer 1 of vsf_extract_plan.h; buffer 0 is dorb.blur)
   vsfi::DevBuf<uint32_t> cand_alt;      // ... and the other pair of FAST's candidate segments and row-start tables
@@ -448,6 +464,7 @@ vsf_status reserve_scratch(vsf_ctx* ctx, int n_frames, int n_pairs);
 vsf_status ensure_pipeline_buffers(vsf_ctx* ctx);
 void free_observe(vsf_ctx* ctx);          // vsf_observe.hip: the queue's threads stop, then everything the queue owns goes
 void stop_observe_threads(vsf_ctx* ctx);  // ... before anything waits for the context's streams to drain
+void flush_observe(vsf_ctx* ctx);         // every frame that waits in the queue leaves for the GPU (the queue stays)
 // vsf_observe_ingest.hip: how a batch's images reach its own buffer, and the buffers that takes -- each built by the first
 // frame that needs it (a queue that only ever sees raw mono frames of the context's size owns none of them).
 size_t compressed_cap(const vsf_ctx* ctx);    // bytes a compressed file may have: the submit's probe and the ring
@@ -517,9 +534,12 @@ struct InputEventScope {
 
 // detectAndCompute for images [i0, i0 + n) of `im` on stream `st`.  `status`: the status word the kernels report capacity
 // overflows into (the context's, or the word of the frame in flight that owns this extraction).
+// `masks`: whose detection masks the images take; null: the context's (vsf_set_image_masks, image i0 + i by its parity).
 void extract_on(vsf_ctx* ctx, hipStream_t st, const VsfImages& im_all, int i0, int n, vsf_keypoint* d_kp, uint8_t* d_desc,
                 int32_t* d_counts, bool inputs_complete = false, const VsfSideStream* own_side = nullptr,
-                int32_t* status = nullptr, int status_stride = 0);
+                int32_t* status = nullptr, int status_stride = 0, const VsfFastMask* masks = nullptr);
+// vsf_mask.hip: the masks of vsf_set_image_masks for a launch whose first image is image `i0` of its call
+VsfFastMask image_masks(const vsf_ctx* ctx, int i0);
 // knnMatch(k = 2) + ratio test for pairs [p0, p0 + n) on stream `st`.
 void match_on(vsf_ctx* ctx, hipStream_t st, const uint8_t* d_desc, const int32_t* d_counts, size_t set_stride,
               const int32_t* d_q_set, const int32_t* d_t_set, int p0, int n, int32_t* d_idx2, int32_t* d_dist2,

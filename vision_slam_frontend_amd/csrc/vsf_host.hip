@@ -109,7 +109,8 @@ vsf_status vsf_fast_detect(vsf_ctx* ctx, const uint8_t* img, int w, int h, size_
   VsfImages im{ctx->st_img, ctx->st_img_stride, ctx->st_img_pitch, 1};
   // Output capacity: grow a private buffer if the caller's cap exceeds the extract staging.
   const int kcap = ctx->p.max_keypoints;
-  vsf_launch_fast(ctx->dfast.d, ctx->fast.g, im, threshold, want_nms ? 1 : 0, ctx->stream);
+  const VsfFastMask mk = image_masks(ctx, 0);  // (FastFeatureDetector::detect(image, kps, mask): the level-0 rule alone)
+  vsf_launch_fast(ctx->dfast.d, ctx->fast.g, im, threshold, want_nms ? 1 : 0, ctx->stream, 0, 0, nullptr, VSF_FAST_ALL, 0, &mk);
   vsf_keypoint* d_out = ctx->st_kp;
   DevBuf<vsf_keypoint> big;
   int outcap = kcap;

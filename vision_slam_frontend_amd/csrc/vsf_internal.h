@@ -217,9 +217,25 @@ void vsf_launch_pyramid(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_lev
 // part / n_early: VSF_FAST_ALL = every work item; VSF_FAST_EARLY = full cells [0, n_early) only; VSF_FAST_LATE = the full cells
 // from n_early on and every packed item (the two parts together are the whole list: vsf_fast_split.h).
 enum { VSF_FAST_ALL = 0, VSF_FAST_EARLY = 1, VSF_FAST_LATE = 2 };
+// Detection masks of a launch's images (include/vsf.h "Detection masks"; k_mask.hip builds a slot's block: one byte a pixel,
+// 0x00 / 0xFF, every level at its VsfLevel::offset and pitch of the ORB geometry -- level 0 included, which the stand-alone
+// detector's one-level geometry shares).  Image i of the launch reads table[i] when there is a table (device-visible memory),
+// else `odd` when parity + i is odd and `even` otherwise; a null block is no mask.  All null: the launch takes the kernels
+// without the predicate.
+struct VsfFastMask {
+  const uint8_t* even = nullptr;
+  const uint8_t* odd = nullptr;
+  const uint8_t* const* table = nullptr;
+  int parity = 0;
+  uint32_t bytes = 0;  // of one block
+};
 void vsf_launch_fast(const VsfDev& d, const VsfGeom& g, const VsfImages& im, int threshold, int nms, hipStream_t s,
                      int resident_waves_per_simd = 0, int n_cus = 0, uint32_t* d_cell_counters = nullptr,
-                     int part = VSF_FAST_ALL, int n_early = 0);
+                     int part = VSF_FAST_ALL, int n_early = 0, const VsfFastMask* mask = nullptr);
+// k_mask.hip: a slot's block from the caller's mask (w x h at any base address and pitch, device memory), level by level on `s`
+// (h_levels: the ORB geometry's; d_block: pyr_bytes bytes).
+void vsf_launch_mask_pyramid(const uint8_t* d_mask, size_t mask_pitch, const VsfLevel* h_levels, int nlevels, uint32_t block_bytes,
+                             uint8_t* d_block, hipStream_t s);
 void vsf_launch_select(const VsfDev& d, const VsfGeom& g, const VsfLevel* h_levels, const VsfImages& im,
                        hipStream_t s);
 void vsf_launch_retain_best_test(uint2* d_data, uint32_t* d_tables, int n, int n_points, int use_lds, int mode,

@@ -47,6 +47,7 @@ struct vsf_ctx::ObserveBatchMeta {
   //   q_set[max_pairs] | t_set[max_pairs] | best_percent[max_pairs] (float) | out_sets[2 bmax] | frames[bmax] |
   //   params[bmax] | calibs[bmax] -- the last two are written and read only by a batch that holds more than one stream or
   //   more than one calibration -- | transforms[bmax]: M_f of every frame, written and read only with the point cloud on
+  //   | (8-byte aligned) masks[2 bmax]: the detection mask block of every image, read only by a batch that has one
 };
 
 namespace {
@@ -60,11 +61,13 @@ struct MetaView {
   VsfObserveParam* params;
   vsf_calibration* calibs;
   vsfwp::Affine* transforms;
+  const uint8_t** masks;
 };
 
 size_t meta_bytes(int max_pairs, int bmax) {
   return 16 + (size_t)max_pairs * 12 + (size_t)bmax * 8 +
-         (size_t)bmax * (sizeof(VsfObserveFrame) + sizeof(VsfObserveParam) + sizeof(vsf_calibration) + sizeof(vsfwp::Affine));
+         (size_t)bmax * (sizeof(VsfObserveFrame) + sizeof(VsfObserveParam) + sizeof(vsf_calibration) + sizeof(vsfwp::Affine)) +
+         8 + (size_t)bmax * 2 * sizeof(const uint8_t*);
 }
 
 MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
@@ -78,6 +81,7 @@ MetaView meta_view(vsf_ctx::ObserveBatchMeta* m, int max_pairs, int bmax) {
   v.params = reinterpret_cast<VsfObserveParam*>(v.frames + bmax);
   v.calibs = reinterpret_cast<vsf_calibration*>(v.params + bmax);
   v.transforms = reinterpret_cast<vsfwp::Affine*>(v.calibs + bmax);
+  v.masks = reinterpret_cast<const uint8_t**>((reinterpret_cast<uintptr_t>(v.transforms + bmax) + 7) & ~(uintptr_t)7);
   return v;
 }
 
@@ -100,6 +104,10 @@ void stop_observe_threads(vsf_ctx* ctx) {
   vsf_ctx::Observe& o = ctx->ob;
   if (o.queue) o.queue->stop_thread();
   o.copy_helper.reset();
+}
+
+void flush_observe(vsf_ctx* ctx) {
+  if (ctx->ob.ready && ctx->ob.queue) ctx->ob.queue->drain();
 }
 
 void free_observe(vsf_ctx* ctx) {
@@ -411,7 +419,19 @@ vsf_status launch_batch(vsf_ctx* ctx, int64_t t0, int n, bool solo, int rows_hin
   // cross-call pipelining of vsf_set_pipeline -- 27.5 -> 23.4 k frames/s at 64 frames per batch, 31.9 -> 27.5 k at 128: the
   // single chain of 49 dependent launches is slower than the two chains + image-major kernel it replaces and takes the
   // vector ALU from the stages it runs beside.)
-  extract_on(ctx, s_ex, im, 0, 2 * n, b.kp_raw, b.desc_raw, b.counts_raw, false, nullptr, b.status, 1);
+  // the images' detection masks (vsf_observe_set_stream_masks, as each frame's stream had them when it was submitted): a table
+  // in the batch's pinned block; a batch without any takes the kernels without the predicate
+  VsfFastMask masks;
+  for (int f = 0; f < n; f++) {
+    const vsf_ctx::ObserveFrame& fr = o.frames[(size_t)((t0 + f) % o.depth)];
+    for (int side = 0; side < 2; side++) {
+      const int slot = fr.mask_slot[side];
+      M.masks[2 * f + side] = slot >= 0 && ctx->masks[slot].set ? ctx->masks[slot].block.get() : nullptr;
+      if (M.masks[2 * f + side]) masks.table = M.masks;
+    }
+  }
+  masks.bytes = ctx->orb.g.pyr_bytes;
+  extract_on(ctx, s_ex, im, 0, 2 * n, b.kp_raw, b.desc_raw, b.counts_raw, false, nullptr, b.status, 1, &masks);
   ctx->last_images = im;
   ctx->last_valid = true;
   match_on(ctx, s_ex, b.desc_raw, b.counts_raw, K * VSF_DESC_BYTES, nullptr, nullptr, 0, n, o.ex_idx2, o.ex_dist2, b.matches,
@@ -637,6 +657,16 @@ vsf_status vsf_observe_set_world_points(vsf_ctx* ctx, int on, const float* cam_t
   return VSF_OK;
 }
 
+vsf_status vsf_observe_set_stream_masks(vsf_ctx* ctx, int stream, int left_slot, int right_slot) {
+  VsfErrorScope scope_(ctx, false);
+  if (!ctx || stream < 0 || stream >= ctx->ob_streams || left_slot < -1 || left_slot >= VSF_MAX_MASKS || right_slot < -1 ||
+      right_slot >= VSF_MAX_MASKS)
+    return VSF_ERR_INVALID_ARG;
+  ctx->ob_masks[stream].left = left_slot;
+  ctx->ob_masks[stream].right = right_slot;
+  return VSF_OK;
+}
+
 vsf_status vsf_observe_set_pose(vsf_ctx* ctx, int stream, const float* loc, const float* quat_xyzw) {
   VsfErrorScope scope_(ctx, false);
   if (!ctx || stream < 0 || stream >= ctx->ob_streams || !loc || !quat_xyzw) return VSF_ERR_INVALID_ARG;
@@ -842,6 +872,10 @@ vsf_status vsf_observe_reset(vsf_ctx* ctx) {
 // the cloud on, the stream's own left_cam_to_robot (vsf_observe_set_stream_cam_to_robot) or the one the queue was built with.
 static void capture_placement(const vsf_ctx* ctx, int stream, vsf_ctx::ObserveFrame& fr) {
   fr.pose = ctx->ob_pose[stream];
+  // ... and, for the extraction, its detection masks: its stream's -- or, as the frame of a synchronous vsf_observe_stereo*
+  // call, the ones vsf_set_image_masks names for the calls outside the queue (image 0 the left, image 1 the right)
+  fr.mask_slot[0] = ctx->ob_sync_call ? ctx->mask_even : ctx->ob_masks[stream].left;
+  fr.mask_slot[1] = ctx->ob_sync_call ? ctx->mask_odd : ctx->ob_masks[stream].right;
   if (ctx->ob.cloud)
     std::memcpy(fr.cam_to_robot, ctx->ob_stream_c2r_set[stream] ? ctx->ob_stream_c2r[stream] : ctx->ob.cam_to_robot,
                 sizeof(fr.cam_to_robot));
@@ -1274,7 +1308,20 @@ static vsf_status stereo_call(vsf_ctx* ctx, uint8_t* out, size_t cap, size_t* ou
   if (!out || !out_bytes) return VSF_ERR_INVALID_ARG;
   *out_bytes = 0;
   int64_t ticket = -1;
-  const vsf_status st = submit(&ticket);
+  struct SyncScope {  // (capture_placement: the frame this call submits takes vsf_set_image_masks' slots; every way out clears it)
+    vsf_ctx* c;
+    explicit SyncScope(vsf_ctx* ctx) : c(ctx) {
+      if (c) c->ob_sync_call = true;
+    }
+    ~SyncScope() {
+      if (c) c->ob_sync_call = false;
+    }
+  };
+  vsf_status st;
+  {
+    SyncScope sync(ctx);
+    st = submit(&ticket);
+  }
   if (st != VSF_OK) return st;
   return vsf_observe_collect(ctx, ticket, out, cap, out_bytes);
 }

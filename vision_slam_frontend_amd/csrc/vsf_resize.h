@@ -67,6 +67,11 @@ VSF_RESIZE_HD inline VsfTap resize_ytap(int dy, double scale_y, int sh) {
   return VsfTap{(uint16_t)w.i0, (uint16_t)w.i1, (int16_t)w.c0, (int16_t)w.c1};
 }
 
+// VResizeLinear<uchar, int, short, >> 22> on two HResizeLinear sums (S[i0] * a0 + S[i1] * a1) and the row's weights
+VSF_RESIZE_HD inline uint32_t resize_vertical(int h0, int h1, int b0, int b1) {
+  return (uint32_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+}
+
 // k_resize.hip (any source size into any destination size): a wave's 256 output columns [256 c, 256 c + 255] read the pixels
 // [i0(first), i1(last)] of a source row -- the taps grow with the column -- through the aligned dwords that hold them, and a
 // row may begin anywhere in its first dword.  The dwords the widest of a row's waves may need: what the launch sizes its

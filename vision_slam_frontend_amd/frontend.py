@@ -92,6 +92,8 @@ def lib() -> C.CDLL:
         L.vsfh_set_imdecode_reduce.restype = None
         L.vsfh_set_resize.argtypes = [vp, i32, i32, i32, i32]
         L.vsfh_set_resize.restype = None
+        L.vsfh_set_masks.argtypes = [vp, vp, vp, i32, i32, sz]
+        L.vsfh_set_masks.restype = None
         L.vsfh_set_compressed_cap.argtypes = [vp, sz]
         L.vsfh_set_compressed_cap.restype = None
         L.vsfh_debug_image_compressed_format.argtypes = [vp, i32]
@@ -234,8 +236,10 @@ class Frontend:
                  best_percent: float = 0.0, frame_life: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, visualization: bool = False, imdecode_reduce: int = 1,
                  compressed_cap: int = 0, debug_colour_seed=None, cam_to_robot=None, resize_to=None,
-                 score_type: int = capi.HARRIS_SCORE):
+                 score_type: int = capi.HARRIS_SCORE, masks=None):
         """score_type: FrontendConfig::orb_score_type_ (capi.HARRIS_SCORE, the reference's, or capi.FAST_SCORE).
+        masks=(left, right): FrontendConfig::mask_left_ / mask_right_ -- detectAndCompute's mask argument per eye, uint8 arrays
+        of the context's size (the resized size with resize_to), non-zero where a corner may sit; None for an eye: no mask.
         resize_to=(w, h): FrontendConfig::resize_width_ / resize_height_ -- the context has that size, width x height is
         the CAMERA's (what device frames are taken to be; raw and compressed frames bring their own), every frame goes through
         cv::resize on the device, and the calibration is the caller's, for the resized image."""
@@ -246,6 +250,8 @@ class Frontend:
         self.size, self.device = (width, height), device
         if resize_to is not None:
             lib().vsfh_set_resize(self._h, cw, ch, width, height)
+        if masks is not None:
+            self.set_masks(*masks)
         if debug_colour_seed is not None:  # FrontendConfig::debug_colour_seeded_ / _seed_: the object's own rand(), before the switch
             lib().vsfh_set_debug_colour_seed(self._h, 1, int(debug_colour_seed))
         if debug_images:  # FrontendConfig::debug_images_ (the reference's default is on, slam_frontend.cc:552)
@@ -265,6 +271,18 @@ class Frontend:
         st = lib().vsfh_last_status(self._h)
         if st != capi.VSF_OK:
             raise capi.VsfError(st, "Frontend")
+
+    def set_masks(self, left=None, right=None):
+        """FrontendConfig::mask_left_ / mask_right_ (Frontend::set_masks): the object keeps copies; None: no mask for that eye."""
+        arrs = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in (left, right)]
+        shapes = {a.shape for a in arrs if a is not None}
+        if len(shapes) > 1 or any(len(s) != 2 for s in shapes):
+            raise ValueError("masks are 2-D uint8 arrays of one size")
+        h, w = shapes.pop() if shapes else (0, 0)
+        lib().vsfh_set_masks(self._h, _p(arrs[0]), _p(arrs[1]), w, h, w)
+        st = lib().vsfh_last_status(self._h)
+        if st != capi.VSF_OK:
+            raise capi.VsfError(st, "Frontend.set_masks")
 
     def set_fused(self, on: bool):
         """True (default): ObserveImage is one GPU submission (vsf_observe_stereo); False: one C-ABI call per
@@ -586,8 +604,10 @@ class FrontendGroup:
     def __init__(self, width: int, height: int, fundamentals, nfeatures: int = 10000, device: int = 0, best_percents=None,
                  frame_life: int = 0, imdecode_reduces=None, compressed_cap: int = 0, debug_images: bool = False,
                  debug_jpeg_quality: int = 0, debug_png: bool = False, debug_colour_seeds=None, cam_to_robots=None,
-                 visualization: bool = False, resize_to=None, camera_sizes=None, score_type: int = capi.HARRIS_SCORE):
+                 visualization: bool = False, resize_to=None, camera_sizes=None, score_type: int = capi.HARRIS_SCORE,
+                 masks=None):
         """score_type: every member's FrontendConfig::orb_score_type_ (one context, one mode).
+        masks=[(left, right) or None, ...]: FrontendConfig::mask_left_ / mask_right_ per member (width x height arrays).
         resize_to=[(w, h) or None, ...]: FrontendConfig::resize_width_ / resize_height_ per member (None: off) -- a resized
         member takes frames of its camera's size and shares the group's width x height context, so (w, h) is width x height;
         camera_sizes=[(W, H) or None, ...]: what member i's DEVICE frames are taken to be (raw and compressed frames bring
@@ -619,6 +639,9 @@ class FrontendGroup:
                 self._check(i, "FrontendGroup(resize_to=)")
                 if cam != (0, 0):
                     self.members[i].size = (int(cam[0]), int(cam[1]))
+        for i, m in enumerate(masks or ()):  # per camera: FrontendConfig::mask_left_ / mask_right_ of member i
+            if m is not None:
+                self.members[i].set_masks(*m)
         for i, d in enumerate(imdecode_reduces or ()):  # per camera: FrontendConfig::imdecode_reduce_ of member i
             self.members[i].set_imdecode_reduce(d)
         if compressed_cap:  # the group's queue has ONE byte cap: size it for the largest camera's files

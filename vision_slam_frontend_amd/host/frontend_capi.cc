@@ -187,6 +187,12 @@ void vsfh_set_imdecode_reduce(void* f, int reduce) { static_cast<Frontend*>(f)->
 void vsfh_set_resize(void* f, int width, int height, int camera_width, int camera_height) {
   static_cast<Frontend*>(f)->set_resize(width, height, camera_width, camera_height);
 }
+// FrontendConfig::mask_left_ / mask_right_ (a group's member: the pointer vsfh_group_member returns): two masks of w x h at
+// `step` (NULL: no mask for that eye); the object keeps copies.
+void vsfh_set_masks(void* f, const uint8_t* left, const uint8_t* right, int w, int h, size_t step) {
+  static_cast<Frontend*>(f)->set_masks(left ? slam::Image(left, h, w, step) : slam::Image(),
+                                       right ? slam::Image(right, h, w, step) : slam::Image());
+}
 // FrontendConfig::compressed_cap_ (a group's member: the group's)
 void vsfh_set_compressed_cap(void* f, size_t cap_per_image) { static_cast<Frontend*>(f)->set_compressed_cap(cap_per_image); }
 // The format of what vsfh_debug_image_compressed returns: 0 none, 1 "jpeg", 2 "png".

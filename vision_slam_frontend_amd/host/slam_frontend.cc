@@ -267,6 +267,7 @@ Frontend::Frontend(const FrontendConfig& config, int device, FrontendGroup* grou
       device_(device),
       last_status_(VSF_OK) {
   vsfrand::seed(colour_rng_, config_.debug_colour_seed_);
+  OwnMasks();
   if (config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::ORB &&
       config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::FREAK)
     last_status_ = VSF_ERR_UNSUPPORTED;  // the reference would build AKAZE / BRISK / SURF / SIFT here (cc:193-232)
@@ -323,6 +324,9 @@ bool Frontend::EnsureOwnContext(int width, int height, int n_streams) {
     CamToRobot(config_, cam_to_robot);
     last_status_ = vsf_observe_set_world_points(ctx_, 1, cam_to_robot);
   }
+  // the detection masks: each member's pair into its own slots, named to its stream
+  for (int i = 0; last_status_ == VSF_OK && i < n_streams; i++)
+    last_status_ = group_ ? group_->members_[(size_t)i]->ApplyMasks(ctx_) : ApplyMasks(ctx_);
   // ... placed with each camera's own left_cam_to_robot: a group's members are streams of this one queue
   for (int i = 0; group_ && last_status_ == VSF_OK && i < n_streams; i++) {
     float cam_to_robot[12];
@@ -382,11 +386,67 @@ bool Frontend::OdomCheck() {
 }
 
 // cc:266-280: detectAndCompute (ORB) or FAST detect (+ FREAK compute, which is not built: keypoints only).
-bool Frontend::ExtractFeatures(const Image& image, Frame* frame) {
+void Frontend::OwnMasks() {
+  Image* views[2] = {&config_.mask_left_, &config_.mask_right_};
+  for (int eye = 0; eye < 2; eye++) {
+    Image& v = *views[eye];
+    if (v.empty()) {
+      mask_store_[eye].clear();
+      v = Image();
+      continue;
+    }
+    std::vector<uint8_t> copy((size_t)v.rows * (size_t)v.cols);
+    for (int y = 0; y < v.rows; y++) std::memcpy(copy.data() + (size_t)y * v.cols, v.data + (size_t)y * v.step, (size_t)v.cols);
+    mask_store_[eye].swap(copy);
+    v = Image(mask_store_[eye].data(), v.rows, v.cols, (size_t)v.cols);
+  }
+}
+
+int Frontend::mask_slot(int eye) const {
+  return (eye ? config_.mask_right_ : config_.mask_left_).empty() ? -1 : 2 * stream_ + eye;
+}
+
+vsf_status Frontend::ApplyMasks(vsf_ctx* ctx) {
+  const Image* views[2] = {&config_.mask_left_, &config_.mask_right_};
+  for (int eye = 0; eye < 2; eye++) {
+    const Image& v = *views[eye];
+    const vsf_status st = v.empty() ? vsf_mask_clear(ctx, 2 * stream_ + eye)
+                                    : vsf_mask_set(ctx, 2 * stream_ + eye, v.data, v.cols, v.rows, v.step);
+    if (st != VSF_OK) return st;
+  }
+  vsf_status st = vsf_observe_set_stream_masks(ctx, stream_, mask_slot(0), mask_slot(1));
+  if (st == VSF_OK && !group_) st = vsf_set_image_masks(ctx, mask_slot(0), mask_slot(1));
+  return st;
+}
+
+void Frontend::set_masks(const Image& left, const Image& right) {
+  config_.mask_left_ = left;
+  config_.mask_right_ = right;
+  OwnMasks();
+  if (ctx_) last_status_ = ApplyMasks(ctx_);  // (no context yet: the next one takes them, and an earlier status stays)
+}
+
+void Frontend::SelectImageMasks(int first) {
+  // (the context's pair is (left, right) since ApplyMasks; an object without masks never asks)
+  if (mask_slot(0) >= 0 || mask_slot(1) >= 0) vsf_set_image_masks(ctx_, mask_slot(first), mask_slot(1));
+}
+
+bool Frontend::ExtractFeatures(const Image& image, Frame* frame, int eye) {
   if (image.empty() || !EnsureContext(image.cols, image.rows)) {
     if (last_status_ == VSF_OK) last_status_ = VSF_ERR_INVALID_ARG;
     return false;
   }
+  // the right image extracted on its own is image 0 of its call: the pair is (right, right) for that call alone
+  struct EyeScope {
+    Frontend* f;
+    int eye;
+    EyeScope(Frontend* fe, int e) : f(fe), eye(e) {
+      if (eye) f->SelectImageMasks(1);
+    }
+    ~EyeScope() {
+      if (eye) f->SelectImageMasks(0);
+    }
+  } eye_scope(this, eye);
   vsf_params p;
   vsf_get_params(ctx_, &p);
   int n = 0;
@@ -420,7 +480,7 @@ bool Frontend::ExtractFeaturesPair(const Image& left, const Image& right, Frame*
   const bool orb = config_.descriptor_extract_type_ != FrontendConfig::DescriptorExtractorType::FREAK;
   if (!orb || left.empty() || right.empty() || left.cols != right.cols || left.rows != right.rows ||
       left.step != right.step)
-    return ExtractFeatures(left, left_frame) && ExtractFeatures(right, right_frame);
+    return ExtractFeatures(left, left_frame, 0) && ExtractFeatures(right, right_frame, 1);
   if (!EnsureContext(left.cols, left.rows)) {
     if (last_status_ == VSF_OK) last_status_ = VSF_ERR_INVALID_ARG;
     return false;

@@ -116,6 +116,14 @@ struct FrontendConfig {
   // frames are refused (VSF_ERR_INVALID_ARG: the two are not combined).  In a FrontendGroup the field is per member; the
   // resized size -- the context's -- is what the members must agree on.
   int resize_width_, resize_height_;
+  // An addition: cv::ORB::detectAndCompute's (and FastFeatureDetector::detect's) mask argument, which the reference leaves at
+  // cv::noArray() (cc:274-277): 8-bit views of the CONTEXT's size (the resized size where resize_width_ is set), non-zero where
+  // a corner may sit -- the hood, the other eye's housing, a rectification wedge, a time stamp are zero.  Empty (the default):
+  // no mask.  The object copies the masks when it is built (and in set_masks), and sets them when its context is created
+  // (vsf_mask_set; include/vsf.h "Detection masks" states OpenCV's rule): in every mode the left image takes mask_left_ and
+  // the right image mask_right_.  A mask of another size than the context's is refused with VSF_ERR_INVALID_ARG.  In a
+  // FrontendGroup the pair is per member.
+  Image mask_left_, mask_right_;
   // An addition: bytes one compressed payload may have (vsf_observe_set_compressed_cap), applied when the context is created.
   // 0 (the default): the library's, width x height + 64 KB OF THE CONTEXT'S SIZE -- with imdecode_reduce_ > 1 that is the
   // REDUCED size, and a camera's files of N times the side are usually larger: set this (vsf_observe_default_compressed_cap of
@@ -302,6 +310,10 @@ class Frontend {
   // camera_width x camera_height > 0: config.image_width / image_height as well (what device frames are taken to be).
   // Before the first frame, or at any time: the next frame sizes the context and declares its own size.
   void set_resize(int width, int height, int camera_width = 0, int camera_height = 0);
+  // config.mask_left_ / mask_right_ (an empty view: no mask for that eye); the object keeps copies.  At any time: a context
+  // that exists takes them at once (vsf_mask_set sends every frame still waiting in the queue first, so frames observed before
+  // the call keep the masks they were observed with); otherwise the next context does.
+  void set_masks(const Image& left, const Image& right);
   // config.compressed_cap_.  Before the first compressed frame, or while no frame is in flight (vsf_observe_set_compressed_cap's
   // rule; otherwise last_status() says VSF_ERR_INVALID_ARG and nothing changes on the device).
   void set_compressed_cap(size_t cap_per_image);
@@ -342,7 +354,7 @@ class Frontend {
   // A member of a FrontendGroup: stream `stream` of the group's one context and queue.
   Frontend(const FrontendConfig& config, int device, FrontendGroup* group, int stream);
   bool OdomCheck();
-  bool ExtractFeatures(const Image& image, Frame* curr_frame);
+  bool ExtractFeatures(const Image& image, Frame* curr_frame, int eye = 0);  // eye: 0 the left image, 1 the right one
   // The two ExtractFeatures calls of ObserveImage (cc:411-412) as one batch of two images (vsf_extract_pair).
   bool ExtractFeaturesPair(const Image& left, const Image& right, Frame* left_frame, Frame* right_frame);
   // The temporal loop of ObserveImage (cc:424-434): GetFeatureMatches of every past frame against the new one, with
@@ -358,6 +370,15 @@ class Frontend {
                          slam_types::VisionFactor* matches_out = nullptr);
   bool EnsureContext(int width, int height);  // (a group member: the group's)
   bool EnsureOwnContext(int width, int height, int n_streams);
+  // config_.mask_left_ / mask_right_ into slots 2 stream_ and 2 stream_ + 1 of `ctx` (an empty view clears its slot), named to
+  // the object's stream of the queue and -- an object with a context of its own -- to the calls outside the queue.
+  vsf_status ApplyMasks(vsf_ctx* ctx);
+  int mask_slot(int eye) const;  // the slot of that eye's mask, -1: none
+  // Per-call mode: the context's pair becomes (eye `first`, right) -- (right, right) around the one call that extracts a right
+  // image on its own, (left, right), what ApplyMasks left, behind it.
+  void SelectImageMasks(int first);
+  void OwnMasks();  // config_'s views into copies the object owns
+  std::vector<uint8_t> mask_store_[2];
   // What the configuration asks of the queue's debug images, in the order the context takes it: everything off, the seeds
   // (one per stream: a group's lead hands in every member's), the switch, the form of file.
   vsf_status ApplyDebugConfig(int n_streams);
